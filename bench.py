@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- cells*steps/sec of advance_timestep on the MI355X-native hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 256|512|amr2|amr3] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 256|512|amr2|amr3] [--scaling weak|strong] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 STARTS ITS OWN N RANKS: the parent process touches neither torch.cuda nor HIP, spawns N children (one per
 GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their environment), waits for them and exits with their code;
@@ -144,6 +144,60 @@ def godunov_calibration(vo, n=128):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # what --dump-outputs writes in all (ranks included), below 64 MB with room for the .npy headers and dt / time
+
+
+def dump_outputs(G, outdir, amr, rank):
+    """--dump-outputs: the state the timed path hands its caller after the last timed step -- new velocity `u`, new scalars `s`
+    (rho, tracer), pressure gradient `gp` on the valid cells, nodal pressure `p`, and `dt` / `time` -- as float64 .npy files
+    lev<L>_box<B>_<field>.npy (B: the box's global index on level L; every rank writes the boxes it owns, rank 0 dt.npy and time.npy).
+    When the whole valid region of every box fits in DUMP_BUDGET_BYTES the fields are written whole, shape (nx, ny, nz, nc) (p: its
+    valid nodes, (nx+1, ny+1, nz+1, 1)).  Otherwise each box contributes a share of a fixed number of cells proportional to its size,
+    drawn without replacement by a generator seeded with (level, box) and sorted, shape (k, nc), p at each sampled cell's low node:
+    the same cells on every run with the same arguments.  Returns (files, bytes, sampled) of this rank."""
+    import numpy as np
+    levels = G.boxes if amr else [G.boxes]
+    local = G.local if amr else [G.local]
+    fields = (("u", G.uold), ("s", G.sold), ("gp", G.gp), ("p", G.p))     # (after a swap_state step uold / sold hold the new state)
+    ncc = sum(mfs[0].nc for name, mfs in fields if name != "p")        # cell-centred components per cell
+    size = [[tuple(b[1][d] - b[0][d] + 1 for d in range(3)) for b in lb] for lb in levels]
+    cells = sum(int(np.prod(sz)) for ls in size for sz in ls)
+    nodes = sum(int(np.prod([x + 1 for x in sz])) for ls in size for sz in ls)
+    budget = DUMP_BUDGET_BYTES - 16                                      # (dt and time)
+    whole = 8 * (ncc * cells + nodes) <= budget
+    npoints = budget // (8 * (ncc + 1))                                  # sampled cells in all (one p value per cell)
+    os.makedirs(outdir, exist_ok=True)
+    files = nbytes = 0
+
+    def save(name, a):
+        nonlocal files, nbytes
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        files, nbytes = files + 1, nbytes + a.nbytes
+
+    for lev in range(len(levels)):
+        for li, gi in enumerate(local[lev]):
+            sz = size[lev][gi]
+            ncell = int(np.prod(sz))
+            idx = None
+            if not whole:
+                k = min(ncell, npoints * ncell // cells)
+                idx = np.unravel_index(np.sort(np.random.default_rng([lev, gi]).choice(ncell, k, replace=False)), sz)
+            for name, mfs in fields:
+                mf = mfs[lev]
+                a = mf.to_numpy(li)
+                g = mf.ng
+                if whole:
+                    v = a[g:a.shape[0] - g, g:a.shape[1] - g, g:a.shape[2] - g]
+                else:
+                    v = a[idx[0] + g, idx[1] + g, idx[2] + g]
+                save("lev%d_box%d_%s" % (lev, gi, name), v)
+    if rank == 0:
+        save("dt", np.array([G.dt]))
+        save("time", np.array([G.time]))
+    return files, nbytes, not whole
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -163,7 +217,14 @@ def parse_args():
     ap.add_argument("--no-pmc", dest="no_pmc", action="store_true", help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes on tools/smoother_probe.py); "
                     "the committed counter summary is quoted instead.  Needed when bench.py itself runs under rocprofv3")
     ap.add_argument("--no-extra", dest="no_extra", action="store_true", help="skip the extra_workloads (512^3 in eight boxes and in one box, tagged two- and three-level hierarchies, the viscous 256^3 step, the viscous three-level run with regridding) of the default N = 1 line")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_dir", default=None, metavar="DIR",
+                    help="after the timed steps write the state the last one computed (u, s, gp, p, dt, time) to DIR/<name>.npy, float64, at most 64 MB in all "
+                         "(a fixed, seeded sample of cells when the fields are larger): two builds run with the same arguments can be compared output for output.  "
+                         "bench_outputs/ inside the tree is git-ignored")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -339,6 +400,9 @@ def main():
         comm = {"ghost_exchanges": cst[0] / k, "view_refreshes": cst[6] / k, "sends": cst[1] / k, "MB_sent": (cst[2] + cst[7]) * 8e-6 / k,
                 "allreduces": cst[3] / k, "allgathers": cst[4] / k,
                 "exchanges_by_log2_bytes": {str(10 + b): cst[8 + b] / k for b in range(16) if cst[8 + b]}}
+    dumped = None
+    if args.dump_dir:                                      # (after the clock stopped: the copies to the host are not timed)
+        dumped = dump_outputs(G, args.dump_dir, amr, rank)
     rho = None
     if rank == 0 and not amr:
         rho = G.sold[0].to_numpy()[..., 0]                  # rank 0's first box, for the smoother probe's coefficients
@@ -622,6 +686,8 @@ def main():
                                 % (args.warmup + 1, args.warmup + args.steps)) if (not amr and args.config == "256") else None},
             "roofline": roof, "cpu_baseline": cpu, "extra_workloads": extra,
         }
+        if dumped:                                         # (rank 0's files; the other ranks wrote their own boxes next to them)
+            out["outputs_dumped"] = {"dir": os.path.abspath(args.dump_dir), "files": dumped[0], "bytes": dumped[1], "sampled": dumped[2]}
         print(json.dumps(out), flush=True)
         for prt in ((cpu or {}).get("parity"), ((cpu or {}).get("sample_256") or {}).get("parity")):
             if prt:                                        # the bench FAILS when the GPU and the oracle disagree on a sample they both stepped

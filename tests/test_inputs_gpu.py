@@ -74,13 +74,13 @@ def test_reference_inputs_run(gpu, name, nsteps, nlev, tmp_path):
 
 
 @pytest.mark.gpu
-def test_vortextube_input_runs(gpu):
+def test_vortextube_input_runs(gpu, tmp_path):
     """exec/test/inputs_vortextube_3d: one level, triply periodic, prob_type 4 (vortex tube), max_step = 1; the initial projection
     runs with the absolute tolerance hgproject.f90:125-127 gives this problem"""
     from varden_amd import advance as adv
     from varden_amd import inputs
     text = open(os.path.join(INP, "inputs_vortextube_3d")).read().replace("verbose = 1", "verbose = 0")
-    nl, G = inputs.run(text, None, None)
+    nl, G = inputs.run(text, None, None, outdir=str(tmp_path))        # (plot_int = 1: the plot files go to the test's directory)
     assert G.istep == 1 and not hasattr(G, "nlev")
     u = G.unew[0].to_numpy()[3:-3, 3:-3, 3:-3]
     s = G.snew[0].to_numpy()[3:-3, 3:-3, 3:-3]
