@@ -50,7 +50,8 @@ enum { VDN_INITIAL_PROJECTION = 1, VDN_DIVU_ITERS = 2, VDN_PRESSURE_ITERS = 3, V
  *      (reference src/_parameters, src/probin.template).  One POD passed once. ------------- */
 typedef struct vdn_params {
   int    dm;              /* dim_in: 3, or 2 (one level, one box: BASELINE configs[0])         */
-  int    nscal;           /* nscal (2)                                                        */
+  int    nscal;           /* nscal (2): the density and nscal-1 passive tracers; 1..11        */
+                          /* (nscal+5 <= 16 bc components; vdn_init refuses others)           */
   int    slope_order;     /* 0, 2 or 4 (default 4)                                            */
   int    use_minion;      /* logical use_minion (default 0)                                   */
   int    boussinesq;      /* default 0                                                        */
@@ -220,6 +221,8 @@ int  vdn_multifab_physbc(vdn_multifab *mf, int scomp, int bccomp, int nc,
 /* ------------------------------------------------------------------------------------------- */
 /* the hot path.  Arrays of per-level multifab handles (length nlevel).                         */
 /* dx is [nlevel][3].  press_comp is the 1-based bc component (dm+nscal+1) as in the reference. */
+/* sold / snew / ext_scal_force carry nscal components, any nscal vdn_init accepted (1..11):   */
+/* component 1 (0-based 0) is the density, the others are passive tracers.                    */
 /* ------------------------------------------------------------------------------------------- */
 int  vdn_advance_timestep(int istep, vdn_layout *mla,
                           vdn_multifab **sold, vdn_multifab **uold,

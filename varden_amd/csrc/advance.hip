@@ -86,7 +86,7 @@ extern "C" int vdn_advance_timestep(int istep, vdn_layout *mla, vdn_multifab **s
   for (int n = 0; n < nlevs; n++) {
     REQUIRE(uold[n]->ng >= 3 && sold[n]->ng >= 3 && unew[n]->ng >= 3 && snew[n]->ng >= 3, "state needs ng_cell = 3");
     REQUIRE(gp[n]->ng >= 1 && p[n]->ng >= 1 && ext_vel_force[n]->ng >= 1 && ext_scal_force[n]->ng >= 1, "gp/p/ext forces need ng = 1");
-    REQUIRE(sold[n]->nc == nscal && nscal <= 3, "sold must have nscal (<= 3) components");
+    REQUIRE(sold[n]->nc == nscal, "sold must have nscal (= %d) components (got %d)", nscal, sold[n]->nc);
   }
   dbg_phase_hash("uold at entry", nlevs, uold); dbg_phase_hash("sold at entry", nlevs, sold); dbg_phase_hash("gp at entry", nlevs, gp);
   dbg_phase_hash("uold+ghosts at entry", nlevs, uold, 1, true); dbg_phase_hash("sold+ghosts at entry", nlevs, sold, 1, true); dbg_phase_hash("gp+ghosts at entry", nlevs, gp, 1, true);

@@ -1705,7 +1705,15 @@ static void fill_gargs(GArgs &A, const vdn_multifab *s, int ibox, const vdn_bc_t
 }
 static void k2_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *force, const double *dx, double dt, const vdn_bc_tower *bct);
 static void k2_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, vdn_multifab **umac, const vdn_multifab *force,
-                      const vdn_multifab *mac_rhs, const double *dx, double dt, const vdn_bc_tower *bct, bool is_vel, const int *is_cons);
+                      const vdn_multifab *mac_rhs, const double *dx, double dt, const vdn_bc_tower *bct, bool is_vel, int bccomp, const int *is_cons);
+// components [c0, c0 + nc) of m: the same boxes and memory, every fab offset by c0 component strides (FV.sc).  A value that owns nothing
+// (no destroy): the scalar Godunov kernels take at most three components per launch, so nscal > 3 runs them on windows of three
+static vdn_multifab comp_window(const vdn_multifab *m, int c0, int nc) {
+  vdn_multifab v = *m;
+  v.owns = false; v.nc = nc;
+  for (FV &f : v.fabs) f.p += f.sc * c0;
+  return v;
+}
 static FV work_fv(double *p, const BoxP &b, int nc_unused) {
   (void)nc_unused;
   FV f; f.p = p; f.a0 = b.lo[0] - 1; f.a1 = b.lo[1] - 1; f.a2 = b.lo[2] - 1;
@@ -1715,7 +1723,16 @@ static FV work_fv(double *p, const BoxP &b, int nc_unused) {
 }
 
 void k_slope(const vdn_multifab *s, vdn_multifab *slope, int dir, int bccomp, const vdn_bc_tower *bct) {
-  REQUIRE(s->ng >= 3 && slope->ng == 1 && slope->nc >= s->nc && s->nc <= 3, "k_slope: need s.ng>=3, slope.ng==1, nc<=3");
+  REQUIRE(s->ng >= 3 && slope->ng == 1 && slope->nc >= s->nc, "k_slope: need s.ng>=3, slope.ng==1, slope.nc>=s.nc");
+  if (s->nc > 3) {                                     // windows of three components (comp_window)
+    for (int c0 = 0; c0 < s->nc; c0 += 3) {
+      const int w = std::min(3, s->nc - c0);
+      const vdn_multifab sw = comp_window(s, c0, w);
+      vdn_multifab lw = comp_window(slope, c0, w);
+      k_slope(&sw, &lw, dir, bccomp + c0, bct);
+    }
+    return;
+  }
   for (int i = 0; i < s->nfabs(); i++) {
     GArgs A; fill_gargs(A, s, i, bct, bccomp, s->nc, nullptr, 0.0);
     Range3 r; for (int d = 0; d < 3; d++) { r.lo[d] = A.lo[d] - 1; r.hi[d] = A.hi[d] + 1; }
@@ -1723,19 +1740,15 @@ void k_slope(const vdn_multifab *s, vdn_multifab *slope, int dir, int bccomp, co
   }
 }
 
-// upd: the caller would run update_3d on the result next (one level): where the fused march is taken -- a level of one box -- the update of
-// every component runs inside it, sedge / flux stay unwritten and the call returns true; otherwise false and the caller updates as usual
-bool k_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, vdn_multifab **umac,
-              const vdn_multifab *force, const vdn_multifab *mac_rhs, const double *dx, double dt,
-              const vdn_bc_tower *bct, bool is_vel, const int *is_cons, const MkUpdate *upd) {
-  Prof prof_("mkflux");
-  god_xcd_init();
-  if (ctx().prm.dm == 2) { k2_mkflux(s, sedge, flux, umac, force, mac_rhs, dx, dt, bct, is_vel, is_cons); return false; }
+// one window of at most three components (k_mkflux below); bccomp: the bc-tower component of the window's first component
+static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, vdn_multifab **umac,
+                          const vdn_multifab *force, const vdn_multifab *mac_rhs, const double *dx, double dt,
+                          const vdn_bc_tower *bct, bool is_vel, int bccomp, const int *is_cons, const MkUpdate *upd) {
+  if (ctx().prm.dm == 2) { k2_mkflux(s, sedge, flux, umac, force, mac_rhs, dx, dt, bct, is_vel, bccomp, is_cons); return false; }
   bool updated = false;
   const int ncomp = s->nc;
-  REQUIRE(ncomp <= 3, "mkflux: at most 3 components per call (got %d)", ncomp);
+  REQUIRE(ncomp <= 3, "mkflux: at most 3 components per window (got %d)", ncomp);
   REQUIRE(s->ng >= 3 && umac[0]->ng >= 1 && force->ng >= 1 && mac_rhs->ng >= 1, "mkflux: ghost widths");
-  const int bccomp = is_vel ? 0 : bct->dm;            // mkflux.f90:62-66
   hipStream_t st = ctx().stream;
   if (use_batched(s) && !plain_godunov()) {            // every stage once for all boxes of the level
     size_t mark = arena_mark();
@@ -1931,6 +1944,38 @@ bool k_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, 
       #undef MK_ARGS_D
     }
     arena_release(mark);
+  }
+  return updated;
+}
+
+// upd: the caller would run update_3d on the result next (one level): where the fused march is taken -- a level of one box -- the update of
+// every component runs inside it, sedge / flux stay unwritten and the call returns true; otherwise false and the caller updates as usual.
+// More than three components (the scalars of nscal > 3) run as windows of three: offset views of s, force, sedge, flux and snew, the bc
+// components bccomp + c0 and the conservative flags from is_cons + c0.  Every window sees the same umac and so the same per-box dead band
+// (kk_macmax: the same maximum; kept once per step in macmax_cache on a level of one box), and nscal <= 3 is the one call it always was.
+bool k_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, vdn_multifab **umac,
+              const vdn_multifab *force, const vdn_multifab *mac_rhs, const double *dx, double dt,
+              const vdn_bc_tower *bct, bool is_vel, const int *is_cons, const MkUpdate *upd) {
+  Prof prof_("mkflux");
+  god_xcd_init();
+  const int ncomp = s->nc, dm = ctx().prm.dm;
+  const int bccomp = is_vel ? 0 : bct->dm;            // mkflux.f90:62-66
+  if (ncomp <= 3) return mkflux_window(s, sedge, flux, umac, force, mac_rhs, dx, dt, bct, is_vel, bccomp, is_cons, upd);
+  REQUIRE(!is_vel && ncomp <= VDN_MAXCOMP, "mkflux: %d components (velocity: dm; scalars: at most %d)", ncomp, VDN_MAXCOMP);
+  REQUIRE(force->nc >= ncomp && (!upd || (upd->fmode == 0 && upd->snew->nc >= ncomp)), "mkflux: force / snew need the components of s");
+  for (int d = 0; d < dm; d++) REQUIRE(sedge[d]->nc >= ncomp && flux[d]->nc >= ncomp, "mkflux: sedge / flux need the components of s");
+  bool updated = false;
+  for (int c0 = 0; c0 < ncomp; c0 += 3) {
+    const int w = std::min(3, ncomp - c0);
+    const vdn_multifab sw = comp_window(s, c0, w), fw = comp_window(force, c0, w);
+    vdn_multifab ew[3], xw[3], nw;
+    vdn_multifab *ep[3] = { nullptr, nullptr, nullptr }, *xp[3] = { nullptr, nullptr, nullptr };
+    for (int d = 0; d < dm; d++) { ew[d] = comp_window(sedge[d], c0, w); xw[d] = comp_window(flux[d], c0, w); ep[d] = &ew[d]; xp[d] = &xw[d]; }
+    MkUpdate U;
+    if (upd) { U = *upd; nw = comp_window(upd->snew, c0, w); U.snew = &nw; }
+    const bool u = mkflux_window(&sw, ep, xp, umac, &fw, mac_rhs, dx, dt, bct, is_vel, bccomp + c0, is_cons + c0, upd ? &U : nullptr);
+    REQUIRE(c0 == 0 || u == updated, "mkflux: the update rode along in some component windows of the level only");    // every window or none
+    updated = u;
   }
   return updated;
 }
@@ -2920,10 +2965,9 @@ static void k2_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_mul
   }
 }
 static void k2_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, vdn_multifab **umac, const vdn_multifab *force,
-                      const vdn_multifab *mac_rhs, const double *dx, double dt, const vdn_bc_tower *bct, bool is_vel, const int *is_cons) {
+                      const vdn_multifab *mac_rhs, const double *dx, double dt, const vdn_bc_tower *bct, bool is_vel, int bccomp, const int *is_cons) {
   const int ncomp = s->nc;
   REQUIRE(ncomp <= 3 && s->ng >= 3 && umac[0]->ng >= 1 && force->ng >= 1 && mac_rhs->ng >= 1, "mkflux (dm = 2): operand shapes");
-  const int bccomp = is_vel ? 0 : bct->dm;
   hipStream_t st = ctx().stream;
   for (int ib = 0; ib < s->nfabs(); ib++) {
     size_t mark = arena_mark();

@@ -451,7 +451,8 @@ extern "C" int vdn_init(const vdn_params *prm, int rank, int nranks, int device)
   REQUIRE(prm != nullptr, "vdn_init: null params");
   g_ctx.extruded2d = false;
   REQUIRE(prm->dm == 3 || prm->dm == 2, "vdn_init: dm must be 2 or 3 (got %d)", prm->dm);
-  REQUIRE(prm->nscal >= 1 && prm->nscal + 5 <= VDN_MAXCOMP, "vdn_init: bad nscal %d", prm->nscal);
+  REQUIRE(prm->nscal >= 1 && prm->nscal + 5 <= VDN_MAXCOMP, "vdn_init: nscal = %d is outside 1..%d (nscal + 5 <= VDN_MAXCOMP = %d: velocity, scalars, pressure and extrap components)",
+          prm->nscal, VDN_MAXCOMP - 5, VDN_MAXCOMP);
   REQUIRE(prm->visc_coef >= 0.0 && prm->diff_coef >= 0.0, "vdn_init: negative visc_coef / diff_coef");
   REQUIRE(prm->diffusion_type == 1 || prm->diffusion_type == 2, "BAD DIFFUSION TYPE");      // velocity_advance.f90:113
   REQUIRE(prm->slope_order == 0 || prm->slope_order == 2 || prm->slope_order == 4, "bad slope_order");
