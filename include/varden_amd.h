@@ -49,7 +49,7 @@ enum { VDN_INITIAL_PROJECTION = 1, VDN_DIVU_ITERS = 2, VDN_PRESSURE_ITERS = 3, V
 /* ---- runtime parameters read implicitly by the reference kernels through probin_module
  *      (reference src/_parameters, src/probin.template).  One POD passed once. ------------- */
 typedef struct vdn_params {
-  int    dm;              /* dim_in: 3, or 2 (one level, one box: BASELINE configs[0])         */
+  int    dm;              /* dim_in: 3, or 2 (one level, any list of boxes, any ranks)          */
   int    nscal;           /* nscal (2): the density and nscal-1 passive tracers; 1..11        */
                           /* (nscal+5 <= 16 bc components; vdn_init refuses others)           */
   int    slope_order;     /* 0, 2 or 4 (default 4)                                            */

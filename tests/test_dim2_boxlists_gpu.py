@@ -1,0 +1,372 @@
+"""dm = 2 on box lists: one level made of any list of boxes, on one or several ranks (dim2.hip).  The two 2-D solvers work on a gathered
+level, so their answer does not depend on the decomposition at all (bit for bit); whole steps differ from the one-box run only through the
+reference's per-box dead band of velpred_2d / mkflux_2d (velpred.f90:215-226); several ranks reproduce one rank on the same boxes bit for bit."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FAKE = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
+INP = os.path.join(ROOT, "tests", "golden", "inputs")
+
+BC2 = {"walls": [[15, 15], [15, 15]], "periodic": [[-1, -1], [-1, -1]], "periodic-x": [[-1, -1], [15, 15]], "inout": [[11, 12], [14, 15]]}
+
+
+def params2(phys, **kw):
+    from varden_amd.capi import default_params
+    p = default_params(dm=2, **kw)
+    for d in range(2):
+        for s in range(2):
+            if phys[d][s] == 11:
+                [p.u_bc, p.v_bc][d][d][s] = 1.0 if s == 0 else -1.0
+                p.rho_bc[d][s] = 1.0
+                p.trac_bc[d][s] = 0.5
+    return p
+
+
+def cuts(n, parts):
+    """box list of a 2-D domain of n x n cells: parts = (x widths, y widths)"""
+    xs, ys = parts
+    assert sum(xs) == n and sum(ys) == n
+    boxes, y0 = [], 0
+    for wy in ys:
+        x0 = 0
+        for wx in xs:
+            boxes.append(((x0, y0, 0), (x0 + wx - 1, y0 + wy - 1, 0)))
+            x0 += wx
+        y0 += wy
+    return boxes
+
+
+DECOMPS = {"1x1": ((64,), (64,)), "2x2": ((32, 32), (32, 32)), "4x4": ((16,) * 4, (16,) * 4), "48+16": ((48, 16), (64,))}
+
+
+class Level2:
+    """one 2-D level of n x n cells on a box list; fields are scattered from global arrays that carry their own ghost layer"""
+    def __init__(self, n, boxes, phys):
+        from varden_amd import boxlib as bl
+        self.bl, self.n, self.boxes = bl, n, boxes
+        self.pmask = [1 if phys[d][0] == -1 else 0 for d in range(2)] + [0]
+        self.mla = bl.MLLayout([((0, 0, 0), (n - 1, n - 1, 0))], [boxes], pmask=self.pmask)
+        self.mfs = []
+
+    def scatter(self, a, ng, nodal=(0, 0, 0)):
+        """a: global array (n + nodal + 2 ng) per direction of the plane, then nc"""
+        mf = self.bl.MultiFab(self.mla, 0, a.shape[-1], ng, nodal)
+        for i, (lo, hi) in enumerate(self.boxes):
+            sl = tuple(slice(lo[d], hi[d] + 1 + nodal[d] + 2 * ng) for d in range(2))
+            mf.from_numpy(np.array(a[sl][:, :, None, :], order="F"), i)
+        self.mfs.append(mf)
+        return mf
+
+    def gather(self, mf, ng, nodal=(0, 0, 0)):
+        out = np.full((self.n + nodal[0], self.n + nodal[1], mf.nc), np.nan)
+        for i, (lo, hi) in enumerate(self.boxes):
+            a = mf.to_numpy(i)[:, :, 0, :]
+            v = a[ng:a.shape[0] - ng, ng:a.shape[1] - ng] if ng else a
+            out[lo[0]:lo[0] + v.shape[0], lo[1]:lo[1] + v.shape[1]] = v
+        return out
+
+    def close(self):
+        for m in self.mfs:
+            m.destroy()
+        self.mla.destroy()
+
+
+def wrap(a, ng, pmask):
+    """the periodic images of a global array's ghost layer (a: n + 2 ng cells per direction)"""
+    for d in range(2):
+        if pmask[d]:
+            idx = [slice(None)] * a.ndim
+            n = a.shape[d] - 2 * ng
+            for g in range(ng):
+                lo, hi = list(idx), list(idx)
+                lo[d], hi[d] = g, g + n
+                a[tuple(lo)] = a[tuple(hi)]
+                lo[d], hi[d] = n + ng + g, ng + g
+                a[tuple(lo)] = a[tuple(hi)]
+    return a
+
+
+def cc_problem(n, phys, seed):
+    rng = np.random.default_rng(seed)
+    pm = [1 if phys[d][0] == -1 else 0 for d in range(2)]
+    X, Y = np.meshgrid((np.arange(n) + 0.5) / n, (np.arange(n) + 0.5) / n, indexing="ij")
+    rh = (np.sin(2 * np.pi * X) * np.cos(2 * np.pi * Y) + 0.1 * rng.standard_normal((n, n)))[:, :, None]
+    if all(pm) or (phys[0][0] != 11 and phys[0][1] != 12 and phys[1][0] != 11 and phys[1][1] != 12):
+        rh -= rh.mean()                                      # a compatible right-hand side where the system is singular
+    phi = wrap(rng.standard_normal((n + 2, n + 2, 1)), 1, pm)        # Dirichlet data in the ghost layer, initial guess inside
+    beta = [1.0 + 0.5 * rng.random((n + 1, n, 1)), 1.0 + 0.5 * rng.random((n, n + 1, 1))]
+    for d in range(2):
+        if pm[d]:                                            # the two copies of a periodic face agree
+            idx = [slice(None)] * 3
+            idx[d] = -1
+            src = [slice(None)] * 3
+            src[d] = 0
+            beta[d][tuple(idx)] = beta[d][tuple(src)]
+    return rh, phi, beta
+
+
+def ell_bc(phys):
+    """the pressure's elliptic boundary codes: Neumann at walls and inflow, Dirichlet at outflow, periodic"""
+    code = {-1: -1, 11: 2, 12: 1, 14: 2, 15: 2}
+    return [[code[phys[d][s]] for s in range(2)] for d in range(2)] + [[0, 0]]
+
+
+def solve_cc(n, boxes, phys, seed):
+    from varden_amd import advance as adv
+    L = Level2(n, boxes, phys)
+    rh, phi, beta = cc_problem(n, phys, seed)
+    gphi = L.scatter(phi, 1)
+    cyc = adv.cc_solve(L.scatter(rh, 0), gphi, [L.scatter(beta[0], 0, (1, 0, 0)), L.scatter(beta[1], 0, (0, 1, 0))], [1.0 / n] * 2, ell_bc(phys), 1e-11)
+    out = L.gather(gphi, 1)
+    ghost = [gphi.to_numpy(i)[:, :, 0, :] for i in range(len(boxes))]
+    L.close()
+    return out, cyc, ghost
+
+
+def solve_nd(n, boxes, phys, seed):
+    from varden_amd import advance as adv
+    rng = np.random.default_rng(seed)
+    L = Level2(n, boxes, phys)
+    pm = L.pmask
+    u = wrap(rng.standard_normal((n + 2, n + 2, 2)), 1, pm)
+    sig = wrap(1.0 + 0.5 * rng.random((n + 2, n + 2, 1)), 1, pm)
+    for d in range(2):                                       # beyond a non-periodic face: the zeros of the projection's coefficients and of
+        if not pm[d]:                                        # create_uvec's wall planes (a compatible right-hand side where the system is singular)
+            idx = [slice(None)] * 3
+            for g in (0, -1):
+                idx[d] = g
+                sig[tuple(idx)] = 0.0
+                u[tuple(idx)] = 0.0
+    rh = np.zeros((n + 3, n + 3, 1))
+    phi = np.zeros((n + 3, n + 3, 1))
+    gphi = L.scatter(phi, 1, (1, 1, 0))
+    cyc = adv.nd_solve(L.scatter(rh, 1, (1, 1, 0)), gphi, L.scatter(sig, 1), L.scatter(u, 1), [1.0 / n] * 2, ell_bc(phys), 1e-11)
+    out = L.gather(gphi, 1, (1, 1, 0))
+    L.close()
+    return out, cyc
+
+
+@pytest.fixture
+def dm2(gpu):
+    from varden_amd import boxlib as bl
+    bl.initialize(params2(BC2["walls"]), 0, 1, 0)
+    yield
+
+
+@pytest.mark.parametrize("bcname", ["walls", "periodic-x", "inout"])
+def test_cc_solve_is_decomposition_blind(dm2, bcname):
+    """the same right-hand side, coefficients and Dirichlet data on one box, 2 x 2, 4 x 4 and an unequal 48 + 16 cut: phi bit for bit, the same
+    cycle count, and every box's ghost layer holds its neighbours' phi (across a box face) or the closure's ghost value (across a domain face)"""
+    n, phys = 64, BC2[bcname]
+    ref, rc, rghost = solve_cc(n, cuts(n, DECOMPS["1x1"]), phys, 5)
+    assert rc[0] > 1 and np.isfinite(ref).all()
+    for name in ("2x2", "4x4", "48+16"):
+        boxes = cuts(n, DECOMPS[name])
+        got, gc, ghost = solve_cc(n, boxes, phys, 5)
+        assert gc == rc, (name, gc, rc)
+        assert np.array_equal(got, ref), "%s %s: max %.3e" % (bcname, name, np.abs(got - ref).max())
+        full = rghost[0]                                     # the one-box fab: valid cells and the closure's ghost layer
+        for i, (lo, hi) in enumerate(boxes):
+            assert np.array_equal(ghost[i], full[lo[0]:hi[0] + 3, lo[1]:hi[1] + 3]), (name, i)
+
+
+@pytest.mark.parametrize("bcname", ["walls", "periodic", "inout"])
+def test_nd_solve_is_decomposition_blind(dm2, bcname):
+    """the nodal solve with the divergence of u as its right-hand side (shared nodes: every box computes them from ghost-filled u) on the same
+    four decompositions: phi on every node bit for bit, the same cycle count"""
+    n, phys = 64, BC2[bcname]
+    ref, rc = solve_nd(n, cuts(n, DECOMPS["1x1"]), phys, 7)
+    assert rc[0] > 1 and np.isfinite(ref).all()
+    for name in ("2x2", "4x4", "48+16"):
+        got, gc = solve_nd(n, cuts(n, DECOMPS[name]), phys, 7)
+        assert gc == rc, (name, gc, rc)
+        assert np.array_equal(got, ref), "%s %s: max %.3e" % (bcname, name, np.abs(got - ref).max())
+
+
+# ---- whole steps ---------------------------------------------------------------------------------------------------------------------------
+def run2(n, phys, nsteps, decomp, prob=1, stats=False, **kw):
+    from varden_amd import advance as adv, driver
+    G = driver.Varden(n, [phys[0], phys[1], [0, 0]], params2(phys, cflfac=0.9, **kw), prob_type=prob, init_shrink=0.1, init_iter=1, decomp=decomp)
+    cyc = []
+    for _ in range(nsteps):
+        G.step()
+        cyc.append((adv.last_solver_stats("mac")[0], adv.last_solver_stats("hg")[0]))
+    out = dict(dt=G.dt, u=G.gather_valid(G.uold[0])[:, :, 0, :], s=G.gather_valid(G.sold[0])[:, :, 0, :], gp=G.gather_valid(G.gp[0])[:, :, 0, :], cyc=cyc)
+    G.close()
+    return out
+
+
+def where(a, b, n, bs):
+    """the cells where two fields differ most, and how far they are from the nearest box face (the per-box dead band acts there)"""
+    d = np.abs(a - b).max(axis=-1)
+    i, j = np.unravel_index(np.argmax(d), d.shape)
+    return "max %.3e at cell (%d, %d), %d / %d cells from a box face in x / y" % (d[i, j], i, j, min(i % bs, bs - 1 - i % bs), min(j % bs, bs - 1 - j % bs))
+
+
+@pytest.mark.parametrize("name,bc,prob", [("bubble-walls", "walls", 1), ("bubble-periodic", "periodic", 1), ("blob-inout", "inout", 2)])
+def test_steps_on_boxes_follow_one_box(gpu, name, bc, prob):
+    """64^2, four steps after the start-up sequence on one box and on 2 x 2 boxes: the same MAC / HG cycle counts every step, dt, u, rho and
+    grad p within 1e-8 of their scale; with walls the mass is conserved to 1e-12"""
+    n = 64
+    a = run2(n, BC2[bc], 4, (1, 1, 1), prob)
+    b = run2(n, BC2[bc], 4, (2, 2, 1), prob)
+    assert a["cyc"] == b["cyc"], (a["cyc"], b["cyc"])
+    assert abs(a["dt"] - b["dt"]) <= 1e-8 * a["dt"]
+    for f in ("u", "s", "gp"):
+        scale = max(np.abs(a[f]).max(), 1e-3)
+        assert np.abs(a[f] - b[f]).max() <= 1e-8 * scale, "%s %s: %s" % (name, f, where(a[f], b[f], n, n // 2))
+    if bc == "walls":
+        m0 = run2(n, BC2[bc], 0, (2, 2, 1), prob)["s"][..., 0].sum()
+        assert abs(b["s"][..., 0].sum() - m0) <= 1e-12 * m0
+
+
+@pytest.mark.parametrize("dtype", [1, 2])
+def test_viscous_steps_on_boxes_follow_one_box(gpu, dtype):
+    """the implicit viscous and diffusive solves (the cell-centred solver with alpha) on 4 x 4 boxes: Crank-Nicolson and backward Euler"""
+    n, bc = 64, BC2["walls"]
+    a = run2(n, bc, 3, (1, 1, 1), visc_coef=0.01, diff_coef=0.005, diffusion_type=dtype)
+    b = run2(n, bc, 3, (4, 4, 1), visc_coef=0.01, diff_coef=0.005, diffusion_type=dtype)
+    assert a["cyc"] == b["cyc"]
+    for f in ("u", "s", "gp"):
+        scale = max(np.abs(a[f]).max(), 1e-3)
+        assert np.abs(a[f] - b[f]).max() <= 1e-8 * scale, "viscous-%d %s: %s" % (dtype, f, where(a[f], b[f], n, n // 4))
+
+
+def _prm_pair(bc, **kw):
+    from varden_amd.capi import default_params
+    out = []
+    for dm in (2, 3):
+        p = default_params(dm=dm, cflfac=0.9, **kw) if dm == 2 else default_params(cflfac=0.9, **kw)
+        for d in range(2):
+            for s in range(2):
+                if bc[d][s] == 11:
+                    [p.u_bc, p.v_bc][d][d][s] = 1.0 if s == 0 else -1.0
+                    p.rho_bc[d][s] = 1.0
+                    p.trac_bc[d][s] = 0.5
+        out.append(p)
+    return out
+
+
+@pytest.mark.parametrize("name,bc,prob,visc,dtype", [("bubble-walls", [[15, 15], [15, 15]], 1, 0.0, 1), ("bubble-periodic-x-viscous", [[-1, -1], [15, 15]], 1, 0.001, 1),
+                                                      ("blob-inflow-outflow-walls", [[11, 12], [15, 15]], 2, 0.001, 1), ("blob-inflow-outflow-slip", [[11, 12], [14, 14]], 2, 0.0, 1),
+                                                      ("outflow-both-x", [[12, 12], [15, 15]], 2, 0.0, 1), ("outflow-y", [[15, 15], [12, 12]], 2, 0.0, 1),
+                                                      ("rayleigh-taylor-periodic-x", [[-1, -1], [15, 15]], 3, 0.01, 1), ("bubble-walls-backward-euler", [[15, 15], [15, 15]], 1, 0.01, 2)])
+def test_boxes_reproduce_the_extruded_copy_on_the_same_boxes(gpu, name, bc, prob, visc, dtype):
+    """tests/test_dim2_gpu.py::test_extruded_copy_reproduces_the_2d_path with both sides cut into 2 x 2 boxes (the 3-D copy applies the same per-box
+    dead band): four steps, dt to 1e-12, u and rho to 1e-10, grad p to 1e-8 of their scale"""
+    from varden_amd import driver
+    n, nz, nsteps = 32, 8, 4
+    p2, p3 = _prm_pair(bc, visc_coef=visc, diffusion_type=dtype)
+    kw = dict(prob_type=prob, init_shrink=0.1, init_iter=1)
+    G2 = driver.Varden(n, [bc[0], bc[1], [0, 0]], p2, decomp=(2, 2, 1), **kw)
+    assert len(G2.boxes) == 4
+    for _ in range(nsteps):
+        G2.step()
+    u2, s2, g2, dt2 = G2.gather_valid(G2.uold[0])[:, :, 0, :], G2.gather_valid(G2.sold[0])[:, :, 0, :], G2.gather_valid(G2.gp[0])[:, :, 0, :], G2.dt
+    G2.close()
+    u0_2, s0_2 = driver.initdata_numpy((n, n), [1.0 / n] * 2, prob, 3, 2, dm=2)
+    u0 = np.zeros((n + 6, n + 6, nz + 6, 3), order="F")
+    s0 = np.zeros((n + 6, n + 6, nz + 6, 2), order="F")
+    u0[..., :2] = u0_2[:, :, 0, None, :]
+    s0[...] = s0_2[:, :, 0, None, :]
+    G3 = driver.Varden((n, n, nz), [bc[0], bc[1], [-1, -1]], p3, prob_hi=(1.0, 1.0, nz / float(n)), u0=u0, s0=s0, grav_dir=1, extruded2d=True, decomp=(2, 2, 1), **kw)
+    for _ in range(nsteps):
+        G3.step()
+    u3, s3, g3 = G3.gather_valid(G3.uold[0]), G3.gather_valid(G3.sold[0]), G3.gather_valid(G3.gp[0])
+    assert abs(G3.dt - dt2) <= 1e-12 * dt2
+    G3.close()
+    su, sg = max(np.abs(u2).max(), 1e-3), max(np.abs(g2).max(), 1e-3)
+    assert np.abs(u3[:, :, 0, :2] - u2).max() <= 1e-10 * su, (name, where(u3[:, :, 0, :2], u2, n, n // 2))
+    assert np.abs(s3[:, :, 0, :] - s2).max() <= 1e-10 * np.abs(s2).max(), (name, where(s3[:, :, 0, :], s2, n, n // 2))
+    assert np.abs(g3[:, :, 0, :2] - g2).max() <= 1e-8 * sg, (name, where(g3[:, :, 0, :2], g2, n, n // 2))
+
+
+# ---- several ranks -------------------------------------------------------------------------------------------------------------------------
+def run_ranks(tmp_path, tag, nranks, decomp, n, nsteps, bcname):
+    if nranks > 1 and not os.path.exists(FAKE):
+        subprocess.check_call(["make", "-s", "-C", os.path.dirname(FAKE)])
+    idfile, prefix = str(tmp_path / (tag + ".id")), str(tmp_path / tag)
+    env = dict(os.environ, VDN_RCCL_LIB=FAKE, VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path))
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_dim2_ranks_worker.py"), str(r), str(nranks), idfile, prefix,
+                               str(decomp[0]), str(decomp[1]), str(n), str(nsteps), bcname], env=env, cwd=ROOT) for r in range(nranks)]
+    try:
+        rcs = [p.wait(timeout=400) for p in procs]
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+    assert rcs == [0] * len(procs), rcs
+    out = {}
+    for r in range(nranks):
+        with np.load(prefix + ".%d.npz" % r) as z:
+            for k in z.files:
+                if k == "dt":
+                    out.setdefault("dt", z[k])
+                    assert np.array_equal(out["dt"], z[k]), "ranks disagree on dt"
+                else:
+                    out[k] = z[k]
+    return out
+
+
+@pytest.mark.parametrize("nranks,decomp,bcname", [(2, (2, 2), "walls"), (4, (2, 2), "periodic"), (2, (4, 1), "periodic"), (4, (4, 1), "walls")])
+def test_ranks_reproduce_one_rank_bits(gpu, tmp_path, nranks, decomp, bcname):
+    """2 and 4 ranks (the RCCL test double) on 2 x 2 and 4 x 1 boxes of a 64^2 viscous bubble, start-up + three steps: dt, u, rho, grad p and p
+    bit for bit those of one rank on the same boxes"""
+    ref = run_ranks(tmp_path, "ref", 1, decomp, 64, 3, bcname)
+    got = run_ranks(tmp_path, "mr", nranks, decomp, 64, 3, bcname)
+    assert sorted(ref) == sorted(got) and len([k for k in got if k.startswith("u")]) == decomp[0] * decomp[1]
+    assert np.array_equal(ref["dt"], got["dt"]), (ref["dt"], got["dt"])
+    for k in sorted(ref):
+        assert np.array_equal(ref[k], got[k]), "%s differs: max %.3e" % (k, np.abs(ref[k] - got[k]).max())
+    assert np.isfinite(got["u0"]).all() and np.abs(got["u0"]).max() > 0
+
+
+# ---- inputs, plot files, restart -----------------------------------------------------------------------------------------------------------
+def one_level(text, **subs):
+    import re
+    text = re.sub(r"max_levs\s*=\s*\d+", "max_levs = 1", text).replace("verbose = 1", "verbose = 0")
+    for k, v in subs.items():
+        text = re.sub(r"%s\s*=\s*[-\w.]+" % k, "%s = %s" % (k, v), text)
+    return text
+
+
+@pytest.mark.parametrize("inputs_name", ["inputs_2d-regt", "inputs_bubble_2d"])
+def test_2d_inputs_with_one_level_run_on_four_boxes(gpu, tmp_path, inputs_name):
+    """the reference's 2-D inputs with max_levs = 1 (64^2 cells, max_grid_size 32: four boxes) run natively: a few steps, finite and within 1e-8
+    of the same text on one box (max_grid_size 64); the plot file lists four boxes and reads back; a checkpoint restarts bit for bit"""
+    from varden_amd import inputs, plotfile
+    base = open(os.path.join(INP, inputs_name)).read()
+    text = one_level(base, plot_int=4, chk_int=2)
+    (tmp_path / "a").mkdir(); (tmp_path / "b").mkdir()
+    nl, A = inputs.run(text, 4, None, outdir=str(tmp_path / "a"))
+    assert A.dm == 2 and len(A.boxes) == 4 and A.istep == 4
+    ua, sa = A.gather_valid(A.uold[0])[:, :, 0, :], A.gather_valid(A.sold[0])[:, :, 0, :]
+    assert np.isfinite(ua).all() and np.isfinite(sa).all() and np.abs(ua).max() > 0
+    ref = [A.uold[0].to_numpy(i) for i in range(4)] + [A.sold[0].to_numpy(i) for i in range(4)] + [A.p[0].to_numpy(i) for i in range(4)]
+    tA, dtA = A.time, A.dt
+    A.close()
+    nl, B = inputs.run(one_level(base, plot_int=0, chk_int=0, max_grid_size=64), 4, None, outdir=str(tmp_path / "b"))
+    assert len(B.boxes) == 1
+    ub, sb = B.gather_valid(B.uold[0])[:, :, 0, :], B.gather_valid(B.sold[0])[:, :, 0, :]
+    B.close()
+    assert np.abs(ua - ub).max() <= 1e-8 * max(np.abs(ub).max(), 1e-3), where(ua, ub, 64, 32)
+    assert np.abs(sa - sb).max() <= 1e-8 * np.abs(sb).max(), where(sa, sb, 64, 32)
+    plt = plotfile.read_ml_multifab(str(tmp_path / "a" / "plt00004"))
+    assert plt["dm"] == 2 and plt["nlevs"] == 1 and len(plt["levels"][0]["boxes"]) == 4
+    rho = np.full((64, 64), np.nan)
+    for gi, (lo, hi) in enumerate(plt["levels"][0]["boxes"]):
+        rho[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1] = plt["levels"][0]["fabs"][gi][:, :, 0, 2]
+    assert np.array_equal(rho, sa[..., 0])
+    nl, R = inputs.run(text.replace("&PROBIN", "&PROBIN\n restart = 2"), 4, None, outdir=str(tmp_path / "a"))
+    assert R.istep == 4 and R.time == tA and R.dt == dtA and len(R.boxes) == 4
+    got = [R.uold[0].to_numpy(i) for i in range(4)] + [R.sold[0].to_numpy(i) for i in range(4)] + [R.p[0].to_numpy(i) for i in range(4)]
+    R.close()
+    for k, (x, y) in enumerate(zip(ref, got)):
+        g = 3 if k < 8 else 1                                # valid cells / nodes of plane k = 0
+        assert np.array_equal(x[g:-g, g:-g, 0], y[g:-g, g:-g, 0]), k

@@ -1,6 +1,7 @@
 // dim2.hip -- the dm = 2 path of advance_timestep (BASELINE.json configs[0], the reference's CPU-runnable case).
 //
-// Reference routines restated (single level; one box -- the 2-D configuration is plumbing, not a performance target):
+// Reference routines restated (ONE level made of any list of boxes, on one or several ranks -- the 2-D configuration is plumbing, not a
+// performance target):
 //   mkvelforce_2d / mkscalforce_2d   src/mkforce.f90:82-142, 290-331
 //   update_2d                        src/update.f90:113-184
 //   estdt_2d                         src/estdt.f90:89-129
@@ -11,8 +12,19 @@
 // mg_cc.hip / mg_nd.hip (5-point red-black Gauss-Seidel V-cycles; 9-point Q1 damped-Jacobi V-cycles), in the expression
 // order of the oracle's dm = 2 mode (oracle/vo_macproject.c, oracle/vo_hgproject.c).
 //
+// Box lists: the pointwise stages run on every local box, one batched launch per stage (vdn_dev.h: launch_cells).  The two solvers
+// run on a GATHERED level: a private whole-domain array that the load launches fill from every local box and the store launches write
+// back to every local box (valid region and ghost layer), so the V-cycles themselves do not know about boxes -- and their arithmetic and
+// its order do not depend on the decomposition: phi is the same bit for bit on one box or many.  Every point of the domain array has ONE
+// writer box (a face or node that two boxes share comes from the box on its high side; the domain's high faces / nodes and the ghost ring
+// from the box that touches them), so nothing depends on two copies of a shared face being equal.  Several ranks: each rank loads its own
+// boxes into a zeroed array and a byte-wise MAX all-reduce completes it (the owner's bytes against zeros: the owner's value, exactly);
+// every rank then holds the same array and runs the same V-cycles, norms included -- no further reduction.  Memory: one whole level per
+// rank (a 4096^2 level: about 1 GB for the cell-centred solver's arrays and levels), which bounds the 2-D problems this path takes.
+//
 // Device layout of a 2-D fab: the 3-D layout with ONE valid z-plane (k = 0); its z-ghost planes exist but are never
-// read or written here.  vdn_multifab_copy_to/from_host present the BoxLib 2-D layout p(lo1-ng:hi1+ng, lo2-ng:hi2+ng, nc).
+// read or written here (nor moved by the ghost exchange, exchange.hip: xboxes_of).  vdn_multifab_copy_to/from_host present the
+// BoxLib 2-D layout p(lo1-ng:hi1+ng, lo2-ng:hi2+ng, nc).
 #include "vdn_dev.h"
 #include <vector>
 #include <algorithm>
@@ -21,108 +33,145 @@
 #define P2(f, i, j, c) fv_at(f, i, j, 0, c)
 static const dim3 B2(64, 4, 1);
 static Range3 rng2(int lo0, int hi0, int lo1, int hi1) { Range3 r; r.lo[0] = lo0; r.hi[0] = hi0; r.lo[1] = lo1; r.hi[1] = hi1; r.lo[2] = r.hi[2] = 0; return r; }
+// the 2-D solvers take one level whose boxes cover the domain (advance_timestep refuses dm = 2 hierarchies)
 static void require_2d(const vdn_multifab *mf, const char *who) {
-  REQUIRE(mf->la->nlev == 1 && mf->nfabs() == 1 && mf->la->boxes[0].size() == 1, "%s: the dm = 2 path supports one level with one box", who);
+  const vdn_layout *la = mf->la;
+  REQUIRE(la->nlev == 1 && mf->lev == 0, "%s: the dm = 2 path supports one level (of any list of boxes)", who);
+  long cells = 0;
+  for (const vdn_box &b : la->boxes[0]) cells += (long)(b.hi[0] - b.lo[0] + 1) * (b.hi[1] - b.lo[1] + 1);
+  const vdn_box &pd = la->pd[0];
+  REQUIRE(cells == (long)(pd.hi[0] - pd.lo[0] + 1) * (pd.hi[1] - pd.lo[1] + 1), "%s: the boxes of a dm = 2 level must cover its domain", who);
 }
+template <class K> static void run_cells(const std::vector<std::pair<K, Range3>> &v) { launch_cells(v, ctx().stream); }
 
 // ---- forcing, update, estdt -------------------------------------------------------------------------------------------
 struct F2Args { int lo[2], hi[2]; double coef, fac; int boussinesq, nscal; };
-__global__ void kk2_mkvelforce(FV vf, FV ext, FV gp, FV s, FV lapu, int has_lapu, F2Args A, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  const int out = (i < A.lo[0]) + (i > A.hi[0]) + (j < A.lo[1]) + (j > A.hi[1]);
-  if (out > 1) return;                               // the four edge halos only (mkforce.f90:118-139)
-  const int ic = min(max(i, A.lo[0]), A.hi[0]), jc = min(max(j, A.lo[1]), A.hi[1]);
-  const double rho = G2(s, i, j, 0);
-  #pragma unroll
-  for (int m = 0; m < 2; m++) {
-    const double l = has_lapu ? G2(lapu, ic, jc, m) : 0.0;
-    const double lapu_local = A.coef * A.fac * l;
-    double e = G2(ext, i, j, m);
-    if (out == 0 && A.boussinesq == 1) e = G2(s, i, j, 1) * e;
-    P2(vf, i, j, m) = e + (lapu_local - G2(gp, i, j, m)) / rho;
-  }
-}
-__global__ void kk2_mkscalforce(FV sf, FV ext, FV laps, int has_laps, F2Args A, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  const int out = (i < A.lo[0]) + (i > A.hi[0]) + (j < A.lo[1]) + (j > A.hi[1]);
-  if (out > 1) return;
-  const int ic = min(max(i, A.lo[0]), A.hi[0]), jc = min(max(j, A.lo[1]), A.hi[1]);
-  for (int m = 1; m < A.nscal; m++) {
-    const double l = has_laps ? G2(laps, ic, jc, m) : 0.0;
-    P2(sf, i, j, m) = G2(ext, i, j, m) + A.coef * A.fac * l;
-  }
-}
+struct mkvelforce2_K { FV vf, ext, gp, s, lapu; int has_lapu; F2Args A;
+  __device__ void cell(int i, int j, int) const {
+    const int out = (i < A.lo[0]) + (i > A.hi[0]) + (j < A.lo[1]) + (j > A.hi[1]);
+    if (out > 1) return;                               // the four edge halos only (mkforce.f90:118-139)
+    const int ic = min(max(i, A.lo[0]), A.hi[0]), jc = min(max(j, A.lo[1]), A.hi[1]);
+    const double rho = G2(s, i, j, 0);
+    #pragma unroll
+    for (int m = 0; m < 2; m++) {
+      const double l = has_lapu ? G2(lapu, ic, jc, m) : 0.0;
+      const double lapu_local = A.coef * A.fac * l;
+      double e = G2(ext, i, j, m);
+      if (out == 0 && A.boussinesq == 1) e = G2(s, i, j, 1) * e;
+      P2(vf, i, j, m) = e + (lapu_local - G2(gp, i, j, m)) / rho;
+    }
+  } };
+struct mkscalforce2_K { FV sf, ext, laps; int has_laps; F2Args A;
+  __device__ void cell(int i, int j, int) const {
+    const int out = (i < A.lo[0]) + (i > A.hi[0]) + (j < A.lo[1]) + (j > A.hi[1]);
+    if (out > 1) return;
+    const int ic = min(max(i, A.lo[0]), A.hi[0]), jc = min(max(j, A.lo[1]), A.hi[1]);
+    for (int m = 1; m < A.nscal; m++) {
+      const double l = has_laps ? G2(laps, ic, jc, m) : 0.0;
+      P2(sf, i, j, m) = G2(ext, i, j, m) + A.coef * A.fac * l;
+    }
+  } };
 void k2_mkvelforce(vdn_multifab *vf, const vdn_multifab *ext, const vdn_multifab *s, const vdn_multifab *gp, const vdn_multifab *lapu, double visc_fac) {
   mf_setval(vf, 0.0, 0, vf->nc, true);
+  std::vector<std::pair<mkvelforce2_K, Range3>> v;
   for (int b = 0; b < vf->nfabs(); b++) {
     F2Args A; const vdn_box &bx = vf->vbox[b];
     for (int d = 0; d < 2; d++) { A.lo[d] = bx.lo[d]; A.hi[d] = bx.hi[d]; }
     A.coef = ctx().prm.visc_coef; A.fac = visc_fac; A.boussinesq = ctx().prm.boussinesq; A.nscal = ctx().prm.nscal;
-    Range3 r = rng2(A.lo[0] - 1, A.hi[0] + 1, A.lo[1] - 1, A.hi[1] + 1);
-    hipLaunchKernelGGL(kk2_mkvelforce, grid_for(r), B2, 0, ctx().stream, vf->fabs[b], ext->fabs[b], gp->fabs[b], s->fabs[b], lapu ? lapu->fabs[b] : vf->fabs[b], lapu ? 1 : 0, A, r);
+    mkvelforce2_K K{ vf->fabs[b], ext->fabs[b], gp->fabs[b], s->fabs[b], lapu ? lapu->fabs[b] : vf->fabs[b], lapu ? 1 : 0, A };
+    v.push_back({ K, rng2(A.lo[0] - 1, A.hi[0] + 1, A.lo[1] - 1, A.hi[1] + 1) });
   }
+  run_cells(v);
 }
 void k2_mkscalforce(vdn_multifab *sf, const vdn_multifab *ext, const vdn_multifab *laps, double diff_fac) {
   mf_setval(sf, 0.0, 0, sf->nc, true);
+  std::vector<std::pair<mkscalforce2_K, Range3>> v;
   for (int b = 0; b < sf->nfabs(); b++) {
     F2Args A; const vdn_box &bx = sf->vbox[b];
     for (int d = 0; d < 2; d++) { A.lo[d] = bx.lo[d]; A.hi[d] = bx.hi[d]; }
     A.coef = ctx().prm.diff_coef; A.fac = diff_fac; A.boussinesq = 0; A.nscal = ctx().prm.nscal;
-    Range3 r = rng2(A.lo[0] - 1, A.hi[0] + 1, A.lo[1] - 1, A.hi[1] + 1);
-    hipLaunchKernelGGL(kk2_mkscalforce, grid_for(r), B2, 0, ctx().stream, sf->fabs[b], ext->fabs[b], laps ? laps->fabs[b] : sf->fabs[b], laps ? 1 : 0, A, r);
+    mkscalforce2_K K{ sf->fabs[b], ext->fabs[b], laps ? laps->fabs[b] : sf->fabs[b], laps ? 1 : 0, A };
+    v.push_back({ K, rng2(A.lo[0] - 1, A.hi[0] + 1, A.lo[1] - 1, A.hi[1] + 1) });
   }
+  run_cells(v);
 }
 
 struct U2Args { double dx[2], dt; int ncomp; int cons[VDN_MAXCOMP]; };
-__global__ void kk2_update(FV sold, FV snew, FV um, FV vm, FV sx, FV sy, FV fx, FV fy, FV force, U2Args A, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  const double ubar = 0.5 * (G2(um, i, j, 0) + G2(um, i + 1, j, 0));
-  const double vbar = 0.5 * (G2(vm, i, j, 0) + G2(vm, i, j + 1, 0));
-  for (int c = 0; c < A.ncomp; c++) {
-    const double so = G2(sold, i, j, c), f = G2(force, i, j, c);
-    double v;
-    if (A.cons[c]) {
-      const double divsu = (G2(fx, i + 1, j, c) - G2(fx, i, j, c)) / A.dx[0] + (G2(fy, i, j + 1, c) - G2(fy, i, j, c)) / A.dx[1];
-      v = so - A.dt * divsu + A.dt * f;
-    } else {
-      const double ug = ubar * (G2(sx, i + 1, j, c) - G2(sx, i, j, c)) / A.dx[0] + vbar * (G2(sy, i, j + 1, c) - G2(sy, i, j, c)) / A.dx[1];
-      v = so - A.dt * ug + A.dt * f;
+struct update2_K { FV sold, snew, um, vm, sx, sy, fx, fy, force; U2Args A;
+  __device__ void cell(int i, int j, int) const {
+    const double ubar = 0.5 * (G2(um, i, j, 0) + G2(um, i + 1, j, 0));
+    const double vbar = 0.5 * (G2(vm, i, j, 0) + G2(vm, i, j + 1, 0));
+    for (int c = 0; c < A.ncomp; c++) {
+      const double so = G2(sold, i, j, c), f = G2(force, i, j, c);
+      double v;
+      if (A.cons[c]) {
+        const double divsu = (G2(fx, i + 1, j, c) - G2(fx, i, j, c)) / A.dx[0] + (G2(fy, i, j + 1, c) - G2(fy, i, j, c)) / A.dx[1];
+        v = so - A.dt * divsu + A.dt * f;
+      } else {
+        const double ug = ubar * (G2(sx, i + 1, j, c) - G2(sx, i, j, c)) / A.dx[0] + vbar * (G2(sy, i, j + 1, c) - G2(sy, i, j, c)) / A.dx[1];
+        v = so - A.dt * ug + A.dt * f;
+      }
+      P2(snew, i, j, c) = v;
     }
-    P2(snew, i, j, c) = v;
-  }
-}
+  } };
 void k2_update(const vdn_multifab *sold, vdn_multifab **umac, vdn_multifab **sedge, vdn_multifab **flux, const vdn_multifab *force, vdn_multifab *snew,
                const double *dx, double dt, bool is_vel, const int *is_cons) {
+  U2Args A; A.dx[0] = dx[0]; A.dx[1] = dx[1]; A.dt = dt; A.ncomp = sold->nc;
+  for (int c = 0; c < sold->nc; c++) A.cons[c] = (!is_vel && is_cons[c]) ? 1 : 0;
+  std::vector<std::pair<update2_K, Range3>> v;
   for (int b = 0; b < sold->nfabs(); b++) {
-    U2Args A; A.dx[0] = dx[0]; A.dx[1] = dx[1]; A.dt = dt; A.ncomp = sold->nc;
-    for (int c = 0; c < sold->nc; c++) A.cons[c] = (!is_vel && is_cons[c]) ? 1 : 0;
     const vdn_box &bx = sold->vbox[b];
-    Range3 r = rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]);
-    hipLaunchKernelGGL(kk2_update, grid_for(r), B2, 0, ctx().stream, sold->fabs[b], snew->fabs[b], umac[0]->fabs[b], umac[1]->fabs[b],
-                       sedge[0]->fabs[b], sedge[1]->fabs[b], flux[0]->fabs[b], flux[1]->fabs[b], force->fabs[b], A, r);
+    update2_K K{ sold->fabs[b], snew->fabs[b], umac[0]->fabs[b], umac[1]->fabs[b], sedge[0]->fabs[b], sedge[1]->fabs[b], flux[0]->fabs[b], flux[1]->fabs[b], force->fabs[b], A };
+    v.push_back({ K, rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]) });
   }
+  run_cells(v);
+}
+DEVI void estdt2_cell(const FV &u, const FV &s, const FV &gp, const FV &ext, int i, int j, double m[4]) {
+  const double rho = G2(s, i, j, 0);
+  #pragma unroll
+  for (int c = 0; c < 2; c++) { m[c] = fabs(G2(u, i, j, c)); m[2 + c] = fabs(G2(gp, i, j, c) / rho - G2(ext, i, j, c)); }
 }
 __global__ void kk2_estdt(FV u, FV s, FV gp, FV ext, Range3 r, double *out6) {
   REDUCE_IJ(r)
   double m[4] = { 0, 0, 0, 0 };
-  if (in_ij) {
-    const double rho = G2(s, i, j, 0);
-    #pragma unroll
-    for (int c = 0; c < 2; c++) { m[c] = fabs(G2(u, i, j, c)); m[2 + c] = fabs(G2(gp, i, j, c) / rho - G2(ext, i, j, c)); }
-  }
+  if (in_ij) estdt2_cell(u, s, gp, ext, i, j, m);
+  block_atomic_max(out6 + 0, m[0]); block_atomic_max(out6 + 1, m[1]); block_atomic_max(out6 + 3, m[2]); block_atomic_max(out6 + 4, m[3]);
+}
+// several boxes: one launch, 64 x 4 tiles per box (the per-box kernel's), a workgroup finds its box by bisection
+struct Est2B { Range3 r; int g[2]; FV u, s, gp, ext; };
+__global__ void __launch_bounds__(256) kk2_estdt_b(const Est2B *args, const int *start, int nbox, double *out6) {
+  int lo = 0, hi = nbox - 1;
+  const int bid = (int)blockIdx.x;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (as_constant(start + mid) <= bid) lo = mid; else hi = mid - 1; }
+  const Est2B &a = as_constant(args + lo);
+  const int lb = bid - as_constant(start + lo);
+  const int i = a.r.lo[0] + (lb % a.g[0]) * 64 + (int)threadIdx.x, j = a.r.lo[1] + (lb / a.g[0]) * 4 + (int)threadIdx.y;
+  double m[4] = { 0, 0, 0, 0 };
+  if (i <= a.r.hi[0] && j <= a.r.hi[1]) estdt2_cell(a.u, a.s, a.gp, a.ext, i, j, m);
   block_atomic_max(out6 + 0, m[0]); block_atomic_max(out6 + 1, m[1]); block_atomic_max(out6 + 3, m[2]); block_atomic_max(out6 + 4, m[3]);
 }
 void k2_estdt_max(const vdn_multifab *u, const vdn_multifab *s, const vdn_multifab *gp, const vdn_multifab *ext, double out6[6]) {
   VdnCtx &c = ctx();
   HIPCHK(hipMemsetAsync(c.d_scal, 0, 6 * sizeof(double), c.stream));
-  for (int b = 0; b < u->nfabs(); b++) {
-    const vdn_box &bx = u->vbox[b];
+  const int nb = u->nfabs();
+  if (nb == 1) {
+    const vdn_box &bx = u->vbox[0];
     Range3 r = rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]);
-    hipLaunchKernelGGL(kk2_estdt, reduce_grid(r), B2, 0, c.stream, u->fabs[b], s->fabs[b], gp->fabs[b], ext->fabs[b], r, c.d_scal);
+    hipLaunchKernelGGL(kk2_estdt, reduce_grid(r), B2, 0, c.stream, u->fabs[0], s->fabs[0], gp->fabs[0], ext->fabs[0], r, c.d_scal);
+  } else if (nb > 1) {
+    std::vector<Est2B> v(nb); std::vector<int> start(nb); int tot = 0;
+    for (int b = 0; b < nb; b++) {
+      Est2B &a = v[b]; const vdn_box &bx = u->vbox[b];
+      a.r = rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]);
+      a.g[0] = (bx.hi[0] - bx.lo[0] + 64) / 64; a.g[1] = (bx.hi[1] - bx.lo[1] + 4) / 4;
+      a.u = u->fabs[b]; a.s = s->fabs[b]; a.gp = gp->fabs[b]; a.ext = ext->fabs[b];
+      start[b] = tot; tot += a.g[0] * a.g[1];
+    }
+    Est2B *d_args = (Est2B *)desc_scratch(sizeof(Est2B) * nb); int *d_start = (int *)desc_scratch(sizeof(int) * nb);
+    upload_staged(d_args, v.data(), sizeof(Est2B) * nb); upload_staged(d_start, start.data(), sizeof(int) * nb);
+    hipLaunchKernelGGL(kk2_estdt_b, dim3(tot), B2, 0, c.stream, (const Est2B *)d_args, (const int *)d_start, nb, c.d_scal);
   }
+  comm_allreduce_max_dev(c.d_scal, 6);        // every rank the same dt (MAX of the maxima == the reference's MIN over ranks of dt_proc)
   HIPCHK(hipMemcpyAsync(c.h_scal, c.d_scal, 6 * sizeof(double), hipMemcpyDeviceToHost, c.stream));
   HIPCHK(hipStreamSynchronize(c.stream));
   for (int k = 0; k < 6; k++) out6[k] = c.h_scal[k];
@@ -187,59 +236,72 @@ __global__ void kk_c2_periodic(C2 L, int per0, int per1) {
   if (j < 0) { g = true; if (per1) sj = j + L.n1; else ok = false; } else if (j >= L.n1) { g = true; if (per1) sj = j - L.n1; else ok = false; }
   if (g && ok) L.phi[c2i(L, i, j)] = L.phi[c2i(L, si, sj)];
 }
-struct C2Bc { int e[2][2]; int lo[2]; };
-// level 0: face coefficients with the boundary folding (Neumann b := 0, Dirichlet b := 2b), alpha
-__global__ void kk_c2_load_b(C2 L, FV bxf, FV byf, FV af, int has_alpha, C2Bc B) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
-  if (i > L.n0 || j > L.n1) return;
-  if (j < L.n1) {
-    double v = G2(bxf, B.lo[0] + i, B.lo[1] + j, 0);
-    const int side = (i == 0) ? 0 : ((i == L.n0) ? 1 : -1);
-    if (side >= 0) { if (B.e[0][side] == VDN_BC_NEU) v = 0.0; else if (B.e[0][side] == VDN_BC_DIR) v = 2.0 * v; }
-    L.bx[c2i(L, i, j)] = v;
-  }
-  if (i < L.n0) {
-    double v = G2(byf, B.lo[0] + i, B.lo[1] + j, 0);
-    const int side = (j == 0) ? 0 : ((j == L.n1) ? 1 : -1);
-    if (side >= 0) { if (B.e[1][side] == VDN_BC_NEU) v = 0.0; else if (B.e[1][side] == VDN_BC_DIR) v = 2.0 * v; }
-    L.by[c2i(L, i, j)] = v;
-  }
-  if (has_alpha && i < L.n0 && j < L.n1) L.alpha[c2i(L, i, j)] = G2(af, B.lo[0] + i, B.lo[1] + j, 0);
-}
-// right-hand side with the Dirichlet data (ghost cells of the incoming phi = boundary-face values) moved into it; phi
-__global__ void kk_c2_load_rh(C2 L, FV rh, FV phi, C2Bc B, double *nrm) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
-  double r0 = 0.0;
-  if (i < L.n0 && j < L.n1) {
-    const int gi = B.lo[0] + i, gj = B.lo[1] + j;
-    double r = G2(rh, gi, gj, 0);
-    r0 = r;
+struct C2Bc { int e[2][2]; int lo[2]; };               // elliptic boundary codes of the DOMAIN faces; lo: the domain's first cell
+struct C2Gx { C2 L; C2Bc B; int has_alpha; };           // what every box's load / store launch shares (kk_batched's `extra`)
+// The per-box descriptors of the gathered level (vdn_dev.h: kk_batched).  r: the points THIS box writes -- each point of the domain
+// array has one writer (require_2d: the boxes tile the domain).  hi: the box's last cell.
+// level 0: face coefficients with the boundary folding (Neumann b := 0, Dirichlet b := 2b), alpha.  r = the box's cells, grown by one
+// face at the domain's high sides: a face that two boxes share comes from the box on its high side.
+struct C2LoadB { Range3 r; int g[3]; FV bxf, byf, af; int hi[2];
+  static __device__ double body(const C2LoadB &q, int gi, int gj, int, const C2Gx &x) {
+    const C2 &L = x.L; const C2Bc &B = x.B;
+    const int i = gi - B.lo[0], j = gj - B.lo[1];
+    if (gj <= q.hi[1]) {
+      double v = G2(q.bxf, gi, gj, 0);
+      const int side = (i == 0) ? 0 : ((i == L.n0) ? 1 : -1);
+      if (side >= 0) { if (B.e[0][side] == VDN_BC_NEU) v = 0.0; else if (B.e[0][side] == VDN_BC_DIR) v = 2.0 * v; }
+      L.bx[c2i(L, i, j)] = v;
+    }
+    if (gi <= q.hi[0]) {
+      double v = G2(q.byf, gi, gj, 0);
+      const int side = (j == 0) ? 0 : ((j == L.n1) ? 1 : -1);
+      if (side >= 0) { if (B.e[1][side] == VDN_BC_NEU) v = 0.0; else if (B.e[1][side] == VDN_BC_DIR) v = 2.0 * v; }
+      L.by[c2i(L, i, j)] = v;
+    }
+    if (x.has_alpha && gi <= q.hi[0] && gj <= q.hi[1]) L.alpha[c2i(L, i, j)] = G2(q.af, gi, gj, 0);
+    return 0.0;
+  } };
+// right-hand side with the Dirichlet data (ghost cells of the incoming phi = boundary-face values) moved into it; phi.  r = the box's
+// cells; returns |rh| for the norm
+struct C2LoadRh { Range3 r; int g[3]; FV rh, phi;
+  static __device__ double body(const C2LoadRh &q, int gi, int gj, int, const C2Gx &x) {
+    const C2 &L = x.L; const C2Bc &B = x.B;
+    const int i = gi - B.lo[0], j = gj - B.lo[1];
+    double r = G2(q.rh, gi, gj, 0);
+    const double r0 = r;
     const long c = c2i(L, i, j);
-    if (i == 0 && B.e[0][0] == VDN_BC_DIR)        r = r + L.bx[c] * G2(phi, gi - 1, gj, 0) * L.hi2[0];
-    if (i == L.n0 - 1 && B.e[0][1] == VDN_BC_DIR) r = r + L.bx[c + 1] * G2(phi, gi + 1, gj, 0) * L.hi2[0];
-    if (j == 0 && B.e[1][0] == VDN_BC_DIR)        r = r + L.by[c] * G2(phi, gi, gj - 1, 0) * L.hi2[1];
-    if (j == L.n1 - 1 && B.e[1][1] == VDN_BC_DIR) r = r + L.by[c + L.P] * G2(phi, gi, gj + 1, 0) * L.hi2[1];
+    if (i == 0 && B.e[0][0] == VDN_BC_DIR)        r = r + L.bx[c] * G2(q.phi, gi - 1, gj, 0) * L.hi2[0];
+    if (i == L.n0 - 1 && B.e[0][1] == VDN_BC_DIR) r = r + L.bx[c + 1] * G2(q.phi, gi + 1, gj, 0) * L.hi2[0];
+    if (j == 0 && B.e[1][0] == VDN_BC_DIR)        r = r + L.by[c] * G2(q.phi, gi, gj - 1, 0) * L.hi2[1];
+    if (j == L.n1 - 1 && B.e[1][1] == VDN_BC_DIR) r = r + L.by[c + L.P] * G2(q.phi, gi, gj + 1, 0) * L.hi2[1];
     L.rh[c] = r;
-    L.phi[c] = G2(phi, gi, gj, 0);
-  }
-  block_atomic_max(nrm, fabs(r0));
-}
-// phi back into the fab incl. the ghost layer the closure implies (Neumann: phi_i, Dirichlet: -phi_i, periodic: image)
-__global__ void kk_c2_store(C2 L, FV phi, C2Bc B) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
-  if (i > L.n0 || j > L.n1) return;
-  const bool gi = (i < 0 || i >= L.n0), gj = (j < 0 || j >= L.n1);
-  if (gi && gj) return;                          // corners are not needed
-  double v;
-  if (!gi && !gj) v = L.phi[c2i(L, i, j)];
-  else {
-    const int d = gi ? 0 : 1, s = gi ? (i < 0 ? 0 : 1) : (j < 0 ? 0 : 1);
-    const int qi = gi ? (s ? L.n0 - 1 : 0) : i, qj = gj ? (s ? L.n1 - 1 : 0) : j;
-    if (B.e[d][s] == VDN_BC_NEU) v = L.phi[c2i(L, qi, qj)];
-    else if (B.e[d][s] == VDN_BC_DIR) v = -L.phi[c2i(L, qi, qj)];
-    else v = L.phi[c2i(L, i, j)];
-  }
-  P2(phi, B.lo[0] + i, B.lo[1] + j, 0) = v;
+    L.phi[c] = G2(q.phi, gi, gj, 0);
+    return fabs(r0);
+  } };
+// phi back into the box's fab incl. its ghost layer: inside the domain the neighbours' phi, beyond a domain face the ghost cell the
+// closure implies (Neumann: phi_i, Dirichlet: -phi_i, periodic: image).  r = the box's cells grown by one
+struct C2Store { Range3 r; int g[3]; FV phi;
+  static __device__ double body(const C2Store &q, int gi_, int gj_, int, const C2Gx &x) {
+    const C2 &L = x.L; const C2Bc &B = x.B;
+    const int i = gi_ - B.lo[0], j = gj_ - B.lo[1];
+    const bool gi = (i < 0 || i >= L.n0), gj = (j < 0 || j >= L.n1);
+    if (gi && gj) return 0.0;                      // the domain's corners are not needed
+    double v;
+    if (!gi && !gj) v = L.phi[c2i(L, i, j)];
+    else {
+      const int d = gi ? 0 : 1, s = gi ? (i < 0 ? 0 : 1) : (j < 0 ? 0 : 1);
+      const int qi = gi ? (s ? L.n0 - 1 : 0) : i, qj = gj ? (s ? L.n1 - 1 : 0) : j;
+      if (B.e[d][s] == VDN_BC_NEU) v = L.phi[c2i(L, qi, qj)];
+      else if (B.e[d][s] == VDN_BC_DIR) v = -L.phi[c2i(L, qi, qj)];
+      else v = L.phi[c2i(L, i, j)];
+    }
+    P2(q.phi, gi_, gj_, 0) = v;
+    return 0.0;
+  } };
+// several ranks: every rank has loaded its own boxes into a zeroed array; the byte-wise MAX over the ranks is then the owner's value
+// (its bytes against zeros) -- the whole array on every rank, bit for bit
+static void gather_level(double *base, long ndoubles) {
+  if (ctx().nranks > 1) comm_allreduce_max_u8_dev((unsigned char *)base, (size_t)ndoubles * sizeof(double));
 }
 static dim3 g2(int nx, int ny) { return dim3((nx + 63) / 64, (ny + 3) / 4, 1); }
 static double read_scal(double *d) {
@@ -279,26 +341,41 @@ int cc2_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const do
   REQUIRE(phi->ng >= 1, "cc multigrid: phi needs one ghost cell");
   hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
-  const vdn_box &bx = rh->vbox[0];
+  const vdn_box &pd = rh->la->pd[0];
   CC2MG M; M.per[0] = bc[0][0] == VDN_BC_PER; M.per[1] = bc[1][0] == VDN_BC_PER;
   M.d_nrm = (double *)arena_alloc(256);
-  int n0 = bx.hi[0] - bx.lo[0] + 1, n1 = bx.hi[1] - bx.lo[1] + 1; double h0 = dx[0], h1 = dx[1];
+  int n0 = pd.hi[0] - pd.lo[0] + 1, n1 = pd.hi[1] - pd.lo[1] + 1; double h0 = dx[0], h1 = dx[1];
+  long sz0 = 0;
   for (;;) {
     C2 L; L.n0 = n0; L.n1 = n1; L.P = n0 + 2; L.hi2[0] = 1.0 / (h0 * h0); L.hi2[1] = 1.0 / (h1 * h1);
     const long sz = c2_size(n0, n1);
     double *base = (double *)arena_alloc(sizeof(double) * sz * (alpha ? 6 : 5));
     HIPCHK(hipMemsetAsync(base, 0, sizeof(double) * sz * (alpha ? 6 : 5), st));
     L.phi = base; L.rh = base + sz; L.res = base + 2 * sz; L.bx = base + 3 * sz; L.by = base + 4 * sz; L.alpha = alpha ? base + 5 * sz : nullptr;
+    if (M.lev.empty()) sz0 = sz * (alpha ? 6 : 5);
     M.lev.push_back(L);
     if ((n0 & 1) || (n1 & 1) || n0 <= 2 || n1 <= 2 || M.lev.size() >= 31) break;
     n0 /= 2; n1 /= 2; h0 *= 2.0; h1 *= 2.0;
   }
-  C2Bc B; for (int d = 0; d < 2; d++) { B.lo[d] = bx.lo[d]; for (int s = 0; s < 2; s++) B.e[d][s] = bc[d][s]; }
+  C2Gx X; X.L = M.lev[0]; X.has_alpha = alpha ? 1 : 0;
+  for (int d = 0; d < 2; d++) { X.B.lo[d] = pd.lo[d]; for (int s = 0; s < 2; s++) X.B.e[d][s] = bc[d][s]; }
   const C2 &L0 = M.lev[0];
-  hipLaunchKernelGGL(kk_c2_load_b, g2(L0.n0 + 1, L0.n1 + 1), B2, 0, st, L0, beta[0]->fabs[0], beta[1]->fabs[0], alpha ? alpha->fabs[0] : rh->fabs[0], alpha ? 1 : 0, B);
-  for (size_t l = 1; l < M.lev.size(); l++) hipLaunchKernelGGL(kk_c2_coarsen, g2(M.lev[l].n0 + 1, M.lev[l].n1 + 1), B2, 0, st, M.lev[l - 1], M.lev[l]);
+  // level 0 of the gathered level: one launch per field over the local boxes, then (several ranks) the whole array on every rank
+  std::vector<C2LoadB> vb; std::vector<C2LoadRh> vr;
+  for (int b = 0; b < rh->nfabs(); b++) {
+    const vdn_box &bx = rh->vbox[b];
+    C2LoadB q; q.r = rng2(bx.lo[0], bx.hi[0] + (bx.hi[0] == pd.hi[0]), bx.lo[1], bx.hi[1] + (bx.hi[1] == pd.hi[1]));
+    q.bxf = beta[0]->fabs[b]; q.byf = beta[1]->fabs[b]; q.af = alpha ? alpha->fabs[b] : rh->fabs[b]; q.hi[0] = bx.hi[0]; q.hi[1] = bx.hi[1];
+    vb.push_back(q);
+    C2LoadRh w; w.r = rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]); w.rh = rh->fabs[b]; w.phi = phi->fabs[b];
+    vr.push_back(w);
+  }
   HIPCHK(hipMemsetAsync(M.d_nrm, 0, sizeof(double), st));
-  hipLaunchKernelGGL(kk_c2_load_rh, g2(L0.n0, L0.n1), B2, 0, st, L0, rh->fabs[0], phi->fabs[0], B, M.d_nrm);
+  launch_batched(vb, X, (double *)nullptr, 0, st);
+  launch_batched(vr, X, M.d_nrm, 0, st);
+  gather_level(L0.phi, sz0);
+  comm_allreduce_max_dev(M.d_nrm, 1);
+  for (size_t l = 1; l < M.lev.size(); l++) hipLaunchKernelGGL(kk_c2_coarsen, g2(M.lev[l].n0 + 1, M.lev[l].n1 + 1), B2, 0, st, M.lev[l - 1], M.lev[l]);
   const double bnorm = read_scal(M.d_nrm);
   const vdn_params &P = ctx().prm;
   int cyc = 0; bool conv = false; double rn = 0.0;
@@ -318,7 +395,13 @@ int cc2_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const do
     cyc++;
   }
   if (M.per[0] || M.per[1]) hipLaunchKernelGGL(kk_c2_periodic, g2(L0.n0 + 2, L0.n1 + 2), B2, 0, st, L0, M.per[0], M.per[1]);
-  hipLaunchKernelGGL(kk_c2_store, g2(L0.n0 + 2, L0.n1 + 2), B2, 0, st, L0, phi->fabs[0], B);
+  std::vector<C2Store> vs;
+  for (int b = 0; b < phi->nfabs(); b++) {
+    const vdn_box &bx = phi->vbox[b];
+    C2Store q; q.r = rng2(bx.lo[0] - 1, bx.hi[0] + 1, bx.lo[1] - 1, bx.hi[1] + 1); q.phi = phi->fabs[b];
+    vs.push_back(q);
+  }
+  launch_batched(vs, X, (double *)nullptr, 0, st);
   if (cycles) *cycles = cyc; if (res0) *res0 = bnorm; if (res) *res = rn;
   HIPCHK(hipStreamSynchronize(st));
   arena_release(mark);
@@ -326,56 +409,62 @@ int cc2_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const do
 }
 
 // ---- MAC projection ---------------------------------------------------------------------------------------------------
-__global__ void kk2_divumac(FV um, FV vm, FV macrhs, FV rh, double dxi0, double dxi1, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  const double d = (G2(um, i + 1, j, 0) - G2(um, i, j, 0)) * dxi0 + (G2(vm, i, j + 1, 0) - G2(vm, i, j, 0)) * dxi1;
-  P2(rh, i, j, 0) = d * -1.0 + G2(macrhs, i, j, 0);
-}
-__global__ void kk2_mac_coeffs(FV rho, FV bx, FV by, Range3 r, int hi0, int hi1) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  if (j <= hi1) P2(bx, i, j, 0) = 2.0 / (G2(rho, i, j, 0) + G2(rho, i - 1, j, 0));
-  if (i <= hi0) P2(by, i, j, 0) = 2.0 / (G2(rho, i, j, 0) + G2(rho, i, j - 1, 0));
-}
-struct Um2Args { int lo[2], hi[2]; double dx[2]; int ebc[2][2]; };
-__global__ void kk2_mkumac(FV um, FV vm, FV phi, FV bx, FV by, Um2Args A, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  if (j <= A.hi[1]) {
-    const int side = (i == A.lo[0]) ? 0 : ((i == A.hi[0] + 1) ? 1 : -1);
-    if (!(side >= 0 && A.ebc[0][side] == VDN_BC_NEU)) {
-      const double g = (G2(phi, i, j, 0) - G2(phi, i - 1, j, 0)) / A.dx[0];
-      P2(um, i, j, 0) = G2(um, i, j, 0) - G2(bx, i, j, 0) * g;
+struct divumac2_K { FV um, vm, macrhs, rh; double dxi0, dxi1;
+  __device__ void cell(int i, int j, int) const {
+    const double d = (G2(um, i + 1, j, 0) - G2(um, i, j, 0)) * dxi0 + (G2(vm, i, j + 1, 0) - G2(vm, i, j, 0)) * dxi1;
+    P2(rh, i, j, 0) = d * -1.0 + G2(macrhs, i, j, 0);
+  } };
+struct mac_coeffs2_K { FV rho, bx, by; int hi0, hi1;          // hi: the box's last cell; rho is read one cell across the box's low faces (ghost-filled)
+  __device__ void cell(int i, int j, int) const {
+    if (j <= hi1) P2(bx, i, j, 0) = 2.0 / (G2(rho, i, j, 0) + G2(rho, i - 1, j, 0));
+    if (i <= hi0) P2(by, i, j, 0) = 2.0 / (G2(rho, i, j, 0) + G2(rho, i, j - 1, 0));
+  } };
+struct Um2Args { int lo[2], hi[2]; int bhi[2]; double dx[2]; int ebc[2][2]; };     // lo / hi: the DOMAIN's cells (its faces carry ebc), bhi: the box's last cell
+struct mkumac2_K { FV um, vm, phi, bx, by; Um2Args A;
+  __device__ void cell(int i, int j, int) const {
+    if (j <= A.bhi[1]) {
+      const int side = (i == A.lo[0]) ? 0 : ((i == A.hi[0] + 1) ? 1 : -1);
+      if (!(side >= 0 && A.ebc[0][side] == VDN_BC_NEU)) {
+        const double g = (G2(phi, i, j, 0) - G2(phi, i - 1, j, 0)) / A.dx[0];
+        P2(um, i, j, 0) = G2(um, i, j, 0) - G2(bx, i, j, 0) * g;
+      }
     }
-  }
-  if (i <= A.hi[0]) {
-    const int side = (j == A.lo[1]) ? 0 : ((j == A.hi[1] + 1) ? 1 : -1);
-    if (!(side >= 0 && A.ebc[1][side] == VDN_BC_NEU)) {
-      const double g = (G2(phi, i, j, 0) - G2(phi, i, j - 1, 0)) / A.dx[1];
-      P2(vm, i, j, 0) = G2(vm, i, j, 0) - G2(by, i, j, 0) * g;
+    if (i <= A.bhi[0]) {
+      const int side = (j == A.lo[1]) ? 0 : ((j == A.hi[1] + 1) ? 1 : -1);
+      if (!(side >= 0 && A.ebc[1][side] == VDN_BC_NEU)) {
+        const double g = (G2(phi, i, j, 0) - G2(phi, i, j - 1, 0)) / A.dx[1];
+        P2(vm, i, j, 0) = G2(vm, i, j, 0) - G2(by, i, j, 0) * g;
+      }
     }
-  }
-}
+  } };
 void do2_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn_multifab **mac_rhs, const double *dx, const vdn_bc_tower *bct, int bc_comp0) {
   require_2d(rho[0], "macproject");
-  hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
   vdn_multifab *rh = mf_temp(mla, 0, 1, 0, -1, false, 0.0), *phi = mf_temp(mla, 0, 1, 1, -1, true, 0.0);
   vdn_multifab *beta[2] = { mf_temp(mla, 0, 1, 0, 0, false, 0.0), mf_temp(mla, 0, 1, 0, 1, false, 0.0) };
-  const vdn_box &bx = rh->vbox[0];
-  Range3 rv = rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]), rf = rng2(bx.lo[0], bx.hi[0] + 1, bx.lo[1], bx.hi[1] + 1);
-  hipLaunchKernelGGL(kk2_divumac, grid_for(rv), B2, 0, st, umac[0]->fabs[0], umac[1]->fabs[0], mac_rhs[0]->fabs[0], rh->fabs[0], 1.0 / dx[0], 1.0 / dx[1], rv);
-  hipLaunchKernelGGL(kk2_mac_coeffs, grid_for(rf), B2, 0, st, rho[0]->fabs[0], beta[0]->fabs[0], beta[1]->fabs[0], rf, bx.hi[0], bx.hi[1]);
+  std::vector<std::pair<divumac2_K, Range3>> vd; std::vector<std::pair<mac_coeffs2_K, Range3>> vc;
+  for (int b = 0; b < rh->nfabs(); b++) {
+    const vdn_box &bx = rh->vbox[b];
+    vd.push_back({ divumac2_K{ umac[0]->fabs[b], umac[1]->fabs[b], mac_rhs[0]->fabs[b], rh->fabs[b], 1.0 / dx[0], 1.0 / dx[1] }, rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]) });
+    vc.push_back({ mac_coeffs2_K{ rho[0]->fabs[b], beta[0]->fabs[b], beta[1]->fabs[b], bx.hi[0], bx.hi[1] }, rng2(bx.lo[0], bx.hi[0] + 1, bx.lo[1], bx.hi[1] + 1) });
+  }
+  run_cells(vd); run_cells(vc);
   int ebc[3][2];
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc[d][s] = d < 2 ? bct->ell_bc(0, 0, d, s, bc_comp0) : VDN_BC_INT;
   int cyc; double r0, rr;
   int rc = cc2_solve(rh, phi, beta, dx, ebc, ctx().prm.mac_rel_eps, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, nullptr);
   ctx().solver_cycles[0] = cyc; ctx().solver_res0[0] = r0; ctx().solver_res[0] = rr;
   solver_check(rc, "MAC multigrid (2-D)", cyc, rr, r0);
-  Um2Args A;
-  for (int d = 0; d < 2; d++) { A.lo[d] = bx.lo[d]; A.hi[d] = bx.hi[d]; A.dx[d] = dx[d]; for (int s = 0; s < 2; s++) A.ebc[d][s] = ebc[d][s]; }
-  hipLaunchKernelGGL(kk2_mkumac, grid_for(rf), B2, 0, st, umac[0]->fabs[0], umac[1]->fabs[0], phi->fabs[0], beta[0]->fabs[0], beta[1]->fabs[0], A, rf);
+  // (phi's ghost layer came from the gathered solve: the neighbours' phi across a box face, the closure across a domain face)
+  const vdn_box &pd = mla->pd[0];
+  std::vector<std::pair<mkumac2_K, Range3>> vu;
+  for (int b = 0; b < rh->nfabs(); b++) {
+    const vdn_box &bx = rh->vbox[b];
+    Um2Args A;
+    for (int d = 0; d < 2; d++) { A.lo[d] = pd.lo[d]; A.hi[d] = pd.hi[d]; A.bhi[d] = bx.hi[d]; A.dx[d] = dx[d]; for (int s = 0; s < 2; s++) A.ebc[d][s] = ebc[d][s]; }
+    vu.push_back({ mkumac2_K{ umac[0]->fabs[b], umac[1]->fabs[b], phi->fabs[b], beta[0]->fabs[b], beta[1]->fabs[b], A }, rng2(bx.lo[0], bx.hi[0] + 1, bx.lo[1], bx.hi[1] + 1) });
+  }
+  run_cells(vu);
   mf_fill_boundary(umac[0]); mf_fill_boundary(umac[1]);
   mf_temp_free(beta[0]); mf_temp_free(beta[1]); mf_temp_free(phi); mf_temp_free(rh);
   arena_release(mark);
@@ -383,67 +472,68 @@ void do2_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vd
 
 // ---- explicit diffusive term and the implicit viscous / diffusive solves ------------------------------------------------
 struct Lap2Args { int lo[2], hi[2]; int e[2][2]; double hi2[2]; int comp; };
-__global__ void kk2_lap(FV lap, FV data, Lap2Args A, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  const int q[2] = { i, j };
-  const double p0 = G2(data, i, j, A.comp);
-  double sum = 0.0;
-  #pragma unroll
-  for (int d = 0; d < 2; d++) {
-    const int mi = i - (d == 0), mj = j - (d == 1), pi = i + (d == 0), pj = j + (d == 1);
-    double fm = p0 - G2(data, mi, mj, A.comp), fp = G2(data, pi, pj, A.comp) - p0;
-    if (q[d] == A.lo[d]) { if (A.e[d][0] == VDN_BC_NEU) fm = 0.0; else if (A.e[d][0] == VDN_BC_DIR) fm = 2.0 * fm; }
-    if (q[d] == A.hi[d]) { if (A.e[d][1] == VDN_BC_NEU) fp = 0.0; else if (A.e[d][1] == VDN_BC_DIR) fp = 2.0 * fp; }
-    sum = sum + (fp - fm) * A.hi2[d];
-  }
-  P2(lap, i, j, A.comp) = sum;
-}
+struct lap2_K { FV lap, data; Lap2Args A;          // A: the box and its own boundary codes (interior faces: no folding)
+  __device__ void cell(int i, int j, int) const {
+    const int q[2] = { i, j };
+    const double p0 = G2(data, i, j, A.comp);
+    double sum = 0.0;
+    #pragma unroll
+    for (int d = 0; d < 2; d++) {
+      const int mi = i - (d == 0), mj = j - (d == 1), pi = i + (d == 0), pj = j + (d == 1);
+      double fm = p0 - G2(data, mi, mj, A.comp), fp = G2(data, pi, pj, A.comp) - p0;
+      if (q[d] == A.lo[d]) { if (A.e[d][0] == VDN_BC_NEU) fm = 0.0; else if (A.e[d][0] == VDN_BC_DIR) fm = 2.0 * fm; }
+      if (q[d] == A.hi[d]) { if (A.e[d][1] == VDN_BC_NEU) fp = 0.0; else if (A.e[d][1] == VDN_BC_DIR) fp = 2.0 * fp; }
+      sum = sum + (fp - fm) * A.hi2[d];
+    }
+    P2(lap, i, j, A.comp) = sum;
+  } };
 void k2_explicit_diffusive_term(vdn_multifab *lap, const vdn_multifab *data, int comp, int bccomp0, const double *dx, const vdn_bc_tower *bct) {
+  std::vector<std::pair<lap2_K, Range3>> v;
   for (int b = 0; b < lap->nfabs(); b++) {
     Lap2Args A; const vdn_box &bx = lap->vbox[b];
     for (int d = 0; d < 2; d++) { A.lo[d] = bx.lo[d]; A.hi[d] = bx.hi[d]; A.hi2[d] = 1.0 / (dx[d] * dx[d]); for (int s = 0; s < 2; s++) A.e[d][s] = bct->ell_bc(lap->lev, b + 1, d, s, bccomp0); }
     A.comp = comp;
-    Range3 r = rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]);
-    hipLaunchKernelGGL(kk2_lap, grid_for(r), B2, 0, ctx().stream, lap->fabs[b], data->fabs[b], A, r);
+    v.push_back({ lap2_K{ lap->fabs[b], data->fabs[b], A }, rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]) });
   }
+  run_cells(v);
 }
-struct Vr2Args { int d, dtype; double mu, third_mudt, dxd; };
-__global__ void kk2_visc_rhs(FV rh, FV phi, FV unew, FV rho, FV lapu, FV macrhs, Vr2Args A, Range3 rg, int lo0, int hi0, int lo1, int hi1) {
-  THREAD_IJK(rg)                        // rg = valid box grown by 1: phi takes unew incl. the ghost layer
-  if (!in_range) return;
-  P2(phi, i, j, 0) = G2(unew, i, j, A.d);
-  if (i < lo0 || i > hi0 || j < lo1 || j > hi1) return;
-  double r = G2(unew, i, j, A.d) * G2(rho, i, j, 0);
-  if (A.dtype == 1) r = r + A.mu * G2(lapu, i, j, A.d);
-  const int pi = i + (A.d == 0), pj = j + (A.d == 1), mi = i - (A.d == 0), mj = j - (A.d == 1);
-  r = r + A.third_mudt * (G2(macrhs, pi, pj, 0) - G2(macrhs, mi, mj, 0)) / A.dxd;
-  P2(rh, i, j, 0) = r;
-}
-__global__ void kk2_diff_rhs(FV rh, FV phi, FV snew, FV laps, int comp, int dtype, double mu, Range3 rg, int lo0, int hi0, int lo1, int hi1) {
-  THREAD_IJK(rg)
-  if (!in_range) return;
-  P2(phi, i, j, 0) = G2(snew, i, j, comp);
-  if (i < lo0 || i > hi0 || j < lo1 || j > hi1) return;
-  double r = G2(snew, i, j, comp);
-  if (dtype == 1) r = r + mu * G2(laps, i, j, comp);
-  P2(rh, i, j, 0) = r;
-}
+struct Vr2Args { int d, dtype; double mu, third_mudt, dxd; int lo[2], hi[2]; };
+struct visc_rhs2_K { FV rh, phi, unew, rho, lapu, macrhs; Vr2Args A;
+  __device__ void cell(int i, int j, int) const {      // range = valid box grown by 1: phi takes unew incl. the ghost layer
+    P2(phi, i, j, 0) = G2(unew, i, j, A.d);
+    if (i < A.lo[0] || i > A.hi[0] || j < A.lo[1] || j > A.hi[1]) return;
+    double r = G2(unew, i, j, A.d) * G2(rho, i, j, 0);
+    if (A.dtype == 1) r = r + A.mu * G2(lapu, i, j, A.d);
+    const int pi = i + (A.d == 0), pj = j + (A.d == 1), mi = i - (A.d == 0), mj = j - (A.d == 1);
+    r = r + A.third_mudt * (G2(macrhs, pi, pj, 0) - G2(macrhs, mi, mj, 0)) / A.dxd;
+    P2(rh, i, j, 0) = r;
+  } };
+struct diff_rhs2_K { FV rh, phi, snew, laps; int comp, dtype; double mu; int lo[2], hi[2];
+  __device__ void cell(int i, int j, int) const {
+    P2(phi, i, j, 0) = G2(snew, i, j, comp);
+    if (i < lo[0] || i > hi[0] || j < lo[1] || j > hi[1]) return;
+    double r = G2(snew, i, j, comp);
+    if (dtype == 1) r = r + mu * G2(laps, i, j, comp);
+    P2(rh, i, j, 0) = r;
+  } };
 void do2_visc_solve(vdn_layout *mla, vdn_multifab *unew, const vdn_multifab *lapu, const vdn_multifab *rho, const vdn_multifab *mac_rhs,
                     const double *dx, double mu, const vdn_bc_tower *bct) {
   require_2d(unew, "visc_solve");
-  hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
   vdn_multifab *rh = mf_temp(mla, 0, 1, 0, -1, false, 0.0), *phi = mf_temp(mla, 0, 1, 1, -1, true, 0.0), *alpha = mf_temp(mla, 0, 1, 0, -1, false, 0.0);
   vdn_multifab *beta[2] = { mf_temp(mla, 0, 1, 0, 0, true, mu), mf_temp(mla, 0, 1, 0, 1, true, mu) };
   mf_copy(alpha, 0, rho, 0, 1, 0);
-  const vdn_box &bx = unew->vbox[0];
-  Range3 rg = rng2(bx.lo[0] - 1, bx.hi[0] + 1, bx.lo[1] - 1, bx.hi[1] + 1);
   const int dtype = ctx().prm.diffusion_type;
   for (int d = 0; d < 2; d++) {
-    Vr2Args A; A.d = d; A.dtype = dtype; A.mu = mu; A.third_mudt = (1.0 / 3.0) * ((dtype == 1) ? 2.0 * mu : mu); A.dxd = dx[d];
-    hipLaunchKernelGGL(kk2_visc_rhs, grid_for(rg), B2, 0, st, rh->fabs[0], phi->fabs[0], unew->fabs[0], rho->fabs[0], lapu ? lapu->fabs[0] : unew->fabs[0], mac_rhs->fabs[0], A, rg,
-                       bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]);
+    std::vector<std::pair<visc_rhs2_K, Range3>> v;
+    for (int b = 0; b < unew->nfabs(); b++) {
+      const vdn_box &bx = unew->vbox[b];
+      Vr2Args A; A.d = d; A.dtype = dtype; A.mu = mu; A.third_mudt = (1.0 / 3.0) * ((dtype == 1) ? 2.0 * mu : mu); A.dxd = dx[d];
+      for (int a = 0; a < 2; a++) { A.lo[a] = bx.lo[a]; A.hi[a] = bx.hi[a]; }
+      v.push_back({ visc_rhs2_K{ rh->fabs[b], phi->fabs[b], unew->fabs[b], rho->fabs[b], lapu ? lapu->fabs[b] : unew->fabs[b], mac_rhs->fabs[b], A },
+                    rng2(bx.lo[0] - 1, bx.hi[0] + 1, bx.lo[1] - 1, bx.hi[1] + 1) });
+    }
+    run_cells(v);
     int ebc[3][2];
     for (int a = 0; a < 3; a++) for (int s = 0; s < 2; s++) ebc[a][s] = a < 2 ? bct->ell_bc(0, 0, a, s, d) : VDN_BC_INT;
     int cyc; double r0, rr;
@@ -456,14 +546,17 @@ void do2_visc_solve(vdn_layout *mla, vdn_multifab *unew, const vdn_multifab *lap
 }
 void do2_diff_scalar_solve(vdn_layout *mla, vdn_multifab *snew, const vdn_multifab *laps, const double *dx, double mu, const vdn_bc_tower *bct, int icomp, int bccomp0) {
   require_2d(snew, "diff_scalar_solve");
-  hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
   vdn_multifab *rh = mf_temp(mla, 0, 1, 0, -1, false, 0.0), *phi = mf_temp(mla, 0, 1, 1, -1, true, 0.0), *alpha = mf_temp(mla, 0, 1, 0, -1, true, 1.0);
   vdn_multifab *beta[2] = { mf_temp(mla, 0, 1, 0, 0, true, mu), mf_temp(mla, 0, 1, 0, 1, true, mu) };
-  const vdn_box &bx = snew->vbox[0];
-  Range3 rg = rng2(bx.lo[0] - 1, bx.hi[0] + 1, bx.lo[1] - 1, bx.hi[1] + 1);
-  hipLaunchKernelGGL(kk2_diff_rhs, grid_for(rg), B2, 0, st, rh->fabs[0], phi->fabs[0], snew->fabs[0], laps ? laps->fabs[0] : snew->fabs[0], icomp, ctx().prm.diffusion_type, mu, rg,
-                     bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]);
+  std::vector<std::pair<diff_rhs2_K, Range3>> v;
+  for (int b = 0; b < snew->nfabs(); b++) {
+    const vdn_box &bx = snew->vbox[b];
+    v.push_back({ diff_rhs2_K{ rh->fabs[b], phi->fabs[b], snew->fabs[b], laps ? laps->fabs[b] : snew->fabs[b], icomp, ctx().prm.diffusion_type, mu,
+                               { bx.lo[0], bx.lo[1] }, { bx.hi[0], bx.hi[1] } },
+                  rng2(bx.lo[0] - 1, bx.hi[0] + 1, bx.lo[1] - 1, bx.hi[1] + 1) });
+  }
+  run_cells(v);
   int ebc[3][2];
   for (int a = 0; a < 3; a++) for (int s = 0; s < 2; s++) ebc[a][s] = a < 2 ? bct->ell_bc(0, 0, a, s, bccomp0) : VDN_BC_INT;
   int cyc; double r0, rr;
@@ -568,34 +661,37 @@ __global__ void kk_n2_coarsen_sigma(N2 F, N2 C) {
   for (int b = 0; b < 2; b++) for (int a = 0; a < 2; a++) s = s + F.sig[s2i(F, 2 * i + a, 2 * j + b)];
   C.sig[s2i(C, i, j)] = s * 0.25;
 }
-__global__ void kk_n2_load_sigma(N2 L, FV coeffs, int lo0, int lo1) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
-  if (i > L.n0 || j > L.n1) return;
-  L.sig[s2i(L, i, j)] = G2(coeffs, lo0 + i, lo1 + j, 0);
-}
-__global__ void kk_n2_load(N2 L, FV rh, FV phi, int lo0, int lo1, double *nrm) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
-  double r = 0.0;
-  if (i <= L.n0 && j <= L.n1) {
+struct N2Gx { N2 L; int lo[2]; };                      // lo: the domain's first cell / node
+// gathered level (see cc2_solve): sigma on the box's cells, grown by the ghost cell at the domain's sides (the ring the smoother reads there)
+struct N2LoadSig { Range3 r; int g[3]; FV coeffs;
+  static __device__ double body(const N2LoadSig &q, int gi, int gj, int, const N2Gx &x) {
+    x.L.sig[s2i(x.L, gi - x.lo[0], gj - x.lo[1])] = G2(q.coeffs, gi, gj, 0);
+    return 0.0;
+  } };
+// b = -rh and phi on the box's nodes, grown by the high nodes at the domain's high sides (a node that boxes share comes from the box that
+// holds the cell on its high side along both directions); returns |rh| for the norm
+struct N2Load { Range3 r; int g[3]; FV rh, phi;
+  static __device__ double body(const N2Load &q, int gi, int gj, int, const N2Gx &x) {
+    const N2 &L = x.L;
+    const int i = gi - x.lo[0], j = gj - x.lo[1];
     const bool dir = n2_dir(L, i, j);
-    r = dir ? 0.0 : G2(rh, lo0 + i, lo1 + j, 0);
+    const double r = dir ? 0.0 : G2(q.rh, gi, gj, 0);
     L.b[n2i(L, i, j)] = -r;
-    L.phi[n2i(L, i, j)] = dir ? 0.0 : G2(phi, lo0 + i, lo1 + j, 0);
-  }
-  block_atomic_max(nrm, fabs(r));
-}
-__global__ void kk_n2_store(N2 L, FV phi, int lo0, int lo1) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
-  if (i > L.n0 + 1 || j > L.n1 + 1) return;
-  P2(phi, lo0 + i, lo1 + j, 0) = L.phi[n2i(L, i, j)];
-}
-__global__ void kk2_nd_divu(FV u, FV rh, double gx, double gy, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  const double dux = (G2(u, i, j, 0) + G2(u, i, j - 1, 0)) - (G2(u, i - 1, j, 0) + G2(u, i - 1, j - 1, 0));
-  const double duy = (G2(u, i, j, 1) + G2(u, i - 1, j, 1)) - (G2(u, i, j - 1, 1) + G2(u, i - 1, j - 1, 1));
-  P2(rh, i, j, 0) = G2(rh, i, j, 0) + (dux * gx + duy * gy);
-}
+    L.phi[n2i(L, i, j)] = dir ? 0.0 : G2(q.phi, gi, gj, 0);
+    return fabs(r);
+  } };
+// phi back on every node of the box's fab, ghost layer included (the domain array's ghost ring holds the periodic images / zeros)
+struct N2Store { Range3 r; int g[3]; FV phi;
+  static __device__ double body(const N2Store &q, int gi, int gj, int, const N2Gx &x) {
+    P2(q.phi, gi, gj, 0) = x.L.phi[n2i(x.L, gi - x.lo[0], gj - x.lo[1])];
+    return 0.0;
+  } };
+struct nd_divu2_K { FV u, rh; double gx, gy;
+  __device__ void cell(int i, int j, int) const {
+    const double dux = (G2(u, i, j, 0) + G2(u, i, j - 1, 0)) - (G2(u, i - 1, j, 0) + G2(u, i - 1, j - 1, 0));
+    const double duy = (G2(u, i, j, 1) + G2(u, i - 1, j, 1)) - (G2(u, i, j - 1, 1) + G2(u, i - 1, j - 1, 1));
+    P2(rh, i, j, 0) = G2(rh, i, j, 0) + (dux * gx + duy * gy);
+  } };
 struct ND2MG { std::vector<N2> lev; int per[2]; double *d_nrm; };
 static long n2_nsize(int n0, int n1) { return (long)(n0 + 3) * (n1 + 3); }
 static void n2_fill(const ND2MG &M, const N2 &L, double *a) { hipLaunchKernelGGL(kk_n2_fill_nodes, g2(L.n0 + 3, L.n1 + 3), B2, 0, ctx().stream, L, a, M.per[0], M.per[1]); }
@@ -633,10 +729,11 @@ int nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, c
   REQUIRE(phi->ng >= 1 && rh->ng >= 1 && coeffs->ng >= 1, "nodal multigrid: phi, rh, coeffs need one ghost layer");
   hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
-  const vdn_box &bx = coeffs->vbox[0];
+  const vdn_box &pd = coeffs->la->pd[0];
   ND2MG M; M.per[0] = coeffs->la->pmask[0]; M.per[1] = coeffs->la->pmask[1];
   M.d_nrm = (double *)arena_alloc(256);
-  int n0 = bx.hi[0] - bx.lo[0] + 1, n1 = bx.hi[1] - bx.lo[1] + 1; double h0 = dx[0], h1 = dx[1];
+  int n0 = pd.hi[0] - pd.lo[0] + 1, n1 = pd.hi[1] - pd.lo[1] + 1; double h0 = dx[0], h1 = dx[1];
+  long sz0 = 0;
   for (;;) {
     N2 L; L.n0 = n0; L.n1 = n1; L.PN = n0 + 3; L.PS = n0 + 2; L.f[0] = 1.0 / (6.0 * (h0 * h0)); L.f[1] = 1.0 / (6.0 * (h1 * h1));
     for (int d = 0; d < 2; d++) { L.dirlo[d] = bc[d][0] == VDN_BC_DIR; L.dirhi[d] = bc[d][1] == VDN_BC_DIR; }
@@ -644,22 +741,40 @@ int nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, c
     double *base = (double *)arena_alloc(sizeof(double) * (4 * nn + ns));
     HIPCHK(hipMemsetAsync(base, 0, sizeof(double) * (4 * nn + ns), st));
     L.phi = base; L.tmp = base + nn; L.b = base + 2 * nn; L.res = base + 3 * nn; L.sig = base + 4 * nn;
+    if (M.lev.empty()) sz0 = 4 * nn + ns;
     M.lev.push_back(L);
     if ((n0 & 1) || (n1 & 1) || n0 <= 2 || n1 <= 2 || M.lev.size() >= 31) break;
     n0 /= 2; n1 /= 2; h0 *= 2.0; h1 *= 2.0;
   }
   N2 &L0 = M.lev[0];
-  hipLaunchKernelGGL(kk_n2_load_sigma, g2(L0.n0 + 2, L0.n1 + 2), B2, 0, st, L0, coeffs->fabs[0], bx.lo[0], bx.lo[1]);
+  N2Gx X; X.L = L0; X.lo[0] = pd.lo[0]; X.lo[1] = pd.lo[1];
+  if (u) {
+    std::vector<std::pair<nd_divu2_K, Range3>> v;
+    for (int b = 0; b < rh->nfabs(); b++) {
+      const vdn_box &bx = rh->vbox[b];
+      v.push_back({ nd_divu2_K{ u->fabs[b], rh->fabs[b], 0.5 / dx[0], 0.5 / dx[1] }, rng2(bx.lo[0], bx.hi[0] + 1, bx.lo[1], bx.hi[1] + 1) });
+    }
+    run_cells(v);
+  }
+  // level 0 of the gathered level: one launch per field over the local boxes, then (several ranks) the whole array on every rank
+  std::vector<N2LoadSig> vs; std::vector<N2Load> vl;
+  for (int b = 0; b < coeffs->nfabs(); b++) {
+    const vdn_box &bx = coeffs->vbox[b];
+    const int alo[2] = { bx.lo[0] == pd.lo[0], bx.lo[1] == pd.lo[1] }, ahi[2] = { bx.hi[0] == pd.hi[0], bx.hi[1] == pd.hi[1] };
+    N2LoadSig q; q.r = rng2(bx.lo[0] - alo[0], bx.hi[0] + ahi[0], bx.lo[1] - alo[1], bx.hi[1] + ahi[1]); q.coeffs = coeffs->fabs[b];
+    vs.push_back(q);
+    N2Load w; w.r = rng2(bx.lo[0], bx.hi[0] + ahi[0], bx.lo[1], bx.hi[1] + ahi[1]); w.rh = rh->fabs[b]; w.phi = phi->fabs[b];
+    vl.push_back(w);
+  }
+  HIPCHK(hipMemsetAsync(M.d_nrm, 0, sizeof(double), st));
+  launch_batched(vs, X, (double *)nullptr, 0, st);
+  launch_batched(vl, X, M.d_nrm, 0, st);
+  gather_level(L0.phi, sz0);
+  comm_allreduce_max_dev(M.d_nrm, 1);
   for (size_t l = 1; l < M.lev.size(); l++) {
     hipLaunchKernelGGL(kk_n2_coarsen_sigma, g2(M.lev[l].n0, M.lev[l].n1), B2, 0, st, M.lev[l - 1], M.lev[l]);
     hipLaunchKernelGGL(kk_n2_fill_cells, g2(M.lev[l].n0 + 2, M.lev[l].n1 + 2), B2, 0, st, M.lev[l], M.per[0], M.per[1]);
   }
-  if (u) {
-    Range3 rn = rng2(bx.lo[0], bx.hi[0] + 1, bx.lo[1], bx.hi[1] + 1);
-    hipLaunchKernelGGL(kk2_nd_divu, grid_for(rn), B2, 0, st, u->fabs[0], rh->fabs[0], 0.5 / dx[0], 0.5 / dx[1], rn);
-  }
-  HIPCHK(hipMemsetAsync(M.d_nrm, 0, sizeof(double), st));
-  hipLaunchKernelGGL(kk_n2_load, g2(L0.n0 + 1, L0.n1 + 1), B2, 0, st, L0, rh->fabs[0], phi->fabs[0], bx.lo[0], bx.lo[1], M.d_nrm);
   const double bnorm = read_scal(M.d_nrm);
   const vdn_params &P = ctx().prm;
   int cyc = 0; bool conv = (bnorm == 0.0); double rn = 0.0;
@@ -679,7 +794,14 @@ int nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, c
     cyc++;
   }
   n2_fill(M, L0, L0.phi);
-  hipLaunchKernelGGL(kk_n2_store, g2(L0.n0 + 3, L0.n1 + 3), B2, 0, st, L0, phi->fabs[0], bx.lo[0], bx.lo[1]);
+  X.L = L0;                                          // (the smoother swaps phi and tmp)
+  std::vector<N2Store> vo;
+  for (int b = 0; b < phi->nfabs(); b++) {
+    const vdn_box &bx = phi->vbox[b];
+    N2Store q; q.r = rng2(bx.lo[0] - 1, bx.hi[0] + 2, bx.lo[1] - 1, bx.hi[1] + 2); q.phi = phi->fabs[b];
+    vo.push_back(q);
+  }
+  launch_batched(vo, X, (double *)nullptr, 0, st);
   if (cycles) *cycles = cyc; if (res0) *res0 = bnorm; if (res) *res = rn;
   HIPCHK(hipStreamSynchronize(st));
   arena_release(mark);
@@ -687,70 +809,67 @@ int nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, c
 }
 
 // ---- HG projection ------------------------------------------------------------------------------------------------------
-struct Uv2Args { int lo[2], hi[2]; int phys[2][2]; int proj_type; double dt, dtinv; };
-__global__ void kk2_create_uvec(FV unew, FV uold, FV rhohalf, FV gp, Uv2Args A, Range3 r) {
-  THREAD_IJK(r)                          // r = box grown by the ghost width of unew
-  if (!in_range) return;
-  const int q[2] = { i, j };
-  bool g1 = true, wall_plane = false, inlet_plane = false;
-  #pragma unroll
-  for (int d = 0; d < 2; d++) {
-    if (q[d] < A.lo[d] - 1 || q[d] > A.hi[d] + 1) g1 = false;
-    if (q[d] == A.lo[d] - 1) { const int p = A.phys[d][0]; if (p == VDN_SLIP_WALL || p == VDN_NO_SLIP_WALL) wall_plane = true; if (p == VDN_INLET) inlet_plane = true; }
-    if (q[d] == A.hi[d] + 1) { const int p = A.phys[d][1]; if (p == VDN_SLIP_WALL || p == VDN_NO_SLIP_WALL) wall_plane = true; if (p == VDN_INLET) inlet_plane = true; }
-  }
-  #pragma unroll
-  for (int m = 0; m < 2; m++) {
-    double gpv = 0.0;
-    if (g1) { gpv = G2(gp, i, j, m); if (inlet_plane) { gpv = 0.0; P2(gp, i, j, m) = 0.0; } }
-    if (wall_plane) { P2(unew, i, j, m) = 0.0; continue; }
-    if (!g1) continue;
-    double v = G2(unew, i, j, m);
-    if (A.proj_type == VDN_PRESSURE_ITERS) v = (v - G2(uold, i, j, m)) * A.dtinv;
-    else if (A.proj_type == VDN_REGULAR_TIMESTEP) v = v + A.dt * gpv / G2(rhohalf, i, j, 0);
-    P2(unew, i, j, m) = v;
-  }
-}
-__global__ void kk2_coeffs(FV coeffs, FV rhohalf, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  P2(coeffs, i, j, 0) = 1.0 / G2(rhohalf, i, j, 0);
-}
-struct Hg2Args { int hi[2]; double dt, dtinv, dxi[2]; int proj_type; };
-__global__ void kk2_hg_update(FV unew, FV uold, FV gp, FV rhohalf, FV p, FV phi, Hg2Args A, Range3 r) {
-  THREAD_IJK(r)                          // r covers nodes lo..hi+1
-  if (!in_range) return;
-  if (i <= A.hi[0] && j <= A.hi[1]) {
-    const double gph[2] = { 0.5 * (G2(phi, i + 1, j, 0) + G2(phi, i + 1, j + 1, 0) - G2(phi, i, j, 0) - G2(phi, i, j + 1, 0)) * A.dxi[0],      // mkgphi_2d
-                            0.5 * (G2(phi, i, j + 1, 0) + G2(phi, i + 1, j + 1, 0) - G2(phi, i, j, 0) - G2(phi, i + 1, j, 0)) * A.dxi[1] };
-    const double rho = G2(rhohalf, i, j, 0);
+struct Uv2Args { int lo[2], hi[2]; int phys[2][2]; int proj_type; double dt, dtinv; };     // the box and its own physical boundary codes
+struct create_uvec2_K { FV unew, uold, rhohalf, gp; Uv2Args A;
+  __device__ void cell(int i, int j, int) const {      // range = box grown by the ghost width of unew
+    const int q[2] = { i, j };
+    bool g1 = true, wall_plane = false, inlet_plane = false;
+    #pragma unroll
+    for (int d = 0; d < 2; d++) {
+      if (q[d] < A.lo[d] - 1 || q[d] > A.hi[d] + 1) g1 = false;
+      if (q[d] == A.lo[d] - 1) { const int p = A.phys[d][0]; if (p == VDN_SLIP_WALL || p == VDN_NO_SLIP_WALL) wall_plane = true; if (p == VDN_INLET) inlet_plane = true; }
+      if (q[d] == A.hi[d] + 1) { const int p = A.phys[d][1]; if (p == VDN_SLIP_WALL || p == VDN_NO_SLIP_WALL) wall_plane = true; if (p == VDN_INLET) inlet_plane = true; }
+    }
     #pragma unroll
     for (int m = 0; m < 2; m++) {
-      double v = G2(unew, i, j, m) - gph[m] / rho;
-      if (A.proj_type == VDN_PRESSURE_ITERS) v = G2(uold, i, j, m) + A.dt * v;
+      double gpv = 0.0;
+      if (g1) { gpv = G2(gp, i, j, m); if (inlet_plane) { gpv = 0.0; P2(gp, i, j, m) = 0.0; } }
+      if (wall_plane) { P2(unew, i, j, m) = 0.0; continue; }
+      if (!g1) continue;
+      double v = G2(unew, i, j, m);
+      if (A.proj_type == VDN_PRESSURE_ITERS) v = (v - G2(uold, i, j, m)) * A.dtinv;
+      else if (A.proj_type == VDN_REGULAR_TIMESTEP) v = v + A.dt * gpv / G2(rhohalf, i, j, 0);
       P2(unew, i, j, m) = v;
-      if (A.proj_type == VDN_PRESSURE_ITERS) P2(gp, i, j, m) = G2(gp, i, j, m) + gph[m];
-      else if (A.proj_type == VDN_REGULAR_TIMESTEP) P2(gp, i, j, m) = A.dtinv * gph[m];
     }
-  }
-  if (A.proj_type == VDN_PRESSURE_ITERS) P2(p, i, j, 0) = G2(p, i, j, 0) + G2(phi, i, j, 0);
-  else if (A.proj_type == VDN_REGULAR_TIMESTEP) P2(p, i, j, 0) = A.dtinv * G2(phi, i, j, 0);
-}
+  } };
+struct coeffs2_K { FV coeffs, rhohalf;
+  __device__ void cell(int i, int j, int) const { P2(coeffs, i, j, 0) = 1.0 / G2(rhohalf, i, j, 0); } };
+struct Hg2Args { int hi[2]; double dt, dtinv, dxi[2]; int proj_type; };
+struct hg_update2_K { FV unew, uold, gp, rhohalf, p, phi; Hg2Args A;
+  __device__ void cell(int i, int j, int) const {      // range = the box's nodes lo..hi+1
+    if (i <= A.hi[0] && j <= A.hi[1]) {
+      const double gph[2] = { 0.5 * (G2(phi, i + 1, j, 0) + G2(phi, i + 1, j + 1, 0) - G2(phi, i, j, 0) - G2(phi, i, j + 1, 0)) * A.dxi[0],      // mkgphi_2d
+                              0.5 * (G2(phi, i, j + 1, 0) + G2(phi, i + 1, j + 1, 0) - G2(phi, i, j, 0) - G2(phi, i + 1, j, 0)) * A.dxi[1] };
+      const double rho = G2(rhohalf, i, j, 0);
+      #pragma unroll
+      for (int m = 0; m < 2; m++) {
+        double v = G2(unew, i, j, m) - gph[m] / rho;
+        if (A.proj_type == VDN_PRESSURE_ITERS) v = G2(uold, i, j, m) + A.dt * v;
+        P2(unew, i, j, m) = v;
+        if (A.proj_type == VDN_PRESSURE_ITERS) P2(gp, i, j, m) = G2(gp, i, j, m) + gph[m];
+        else if (A.proj_type == VDN_REGULAR_TIMESTEP) P2(gp, i, j, m) = A.dtinv * gph[m];
+      }
+    }
+    if (A.proj_type == VDN_PRESSURE_ITERS) P2(p, i, j, 0) = G2(p, i, j, 0) + G2(phi, i, j, 0);
+    else if (A.proj_type == VDN_REGULAR_TIMESTEP) P2(p, i, j, 0) = A.dtinv * G2(phi, i, j, 0);
+  } };
 void do2_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_multifab **uold, vdn_multifab **rhohalf, vdn_multifab **p, vdn_multifab **gp,
                    const double *dx, double dt, const vdn_bc_tower *bct, int press_comp0) {
   vdn_multifab *un = unew[0], *uo = uold[0], *rhh = rhohalf[0], *pp = p[0], *gpp = gp[0];
   require_2d(un, "hgproject");
-  hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
   vdn_multifab *rh = mf_temp(mla, 0, 1, 1, 3, true, 0.0), *phi = mf_temp(mla, 0, 1, 1, 3, true, 0.0), *coeffs = mf_temp(mla, 0, 1, 1, -1, true, 0.0);
-  const vdn_box &bx = un->vbox[0];
-  BoxP bp = make_boxp(un, 0, bct);
-  Uv2Args A;
-  for (int d = 0; d < 2; d++) { A.lo[d] = bx.lo[d]; A.hi[d] = bx.hi[d]; A.phys[d][0] = bp.phys[d][0]; A.phys[d][1] = bp.phys[d][1]; }
-  A.proj_type = proj_type; A.dt = dt; A.dtinv = 1.0 / dt;
-  Range3 rgn = rng2(bx.lo[0] - un->ng, bx.hi[0] + un->ng, bx.lo[1] - un->ng, bx.hi[1] + un->ng), rv = rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]);
-  hipLaunchKernelGGL(kk2_create_uvec, grid_for(rgn), B2, 0, st, un->fabs[0], uo->fabs[0], rhh->fabs[0], gpp->fabs[0], A, rgn);
-  hipLaunchKernelGGL(kk2_coeffs, grid_for(rv), B2, 0, st, coeffs->fabs[0], rhh->fabs[0], rv);
+  std::vector<std::pair<create_uvec2_K, Range3>> vu; std::vector<std::pair<coeffs2_K, Range3>> vc;
+  for (int b = 0; b < un->nfabs(); b++) {
+    const vdn_box &bx = un->vbox[b];
+    BoxP bp = make_boxp(un, b, bct);
+    Uv2Args A;
+    for (int d = 0; d < 2; d++) { A.lo[d] = bx.lo[d]; A.hi[d] = bx.hi[d]; A.phys[d][0] = bp.phys[d][0]; A.phys[d][1] = bp.phys[d][1]; }
+    A.proj_type = proj_type; A.dt = dt; A.dtinv = 1.0 / dt;
+    vu.push_back({ create_uvec2_K{ un->fabs[b], uo->fabs[b], rhh->fabs[b], gpp->fabs[b], A }, rng2(bx.lo[0] - un->ng, bx.hi[0] + un->ng, bx.lo[1] - un->ng, bx.hi[1] + un->ng) });
+    vc.push_back({ coeffs2_K{ coeffs->fabs[b], rhh->fabs[b] }, rng2(bx.lo[0], bx.hi[0], bx.lo[1], bx.hi[1]) });
+  }
+  run_cells(vu); run_cells(vc);
   mf_fill_boundary(un); mf_fill_boundary(coeffs);
   double rel = ctx().prm.hg_rel_eps > 0.0 ? ctx().prm.hg_rel_eps : 1.e-12;
   double abs_eps = -1.0;
@@ -762,9 +881,13 @@ void do2_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_mult
   ctx().solver_cycles[1] = cyc; ctx().solver_res0[1] = r0; ctx().solver_res[1] = rr;
   solver_check(rc, "nodal multigrid (2-D)", cyc, rr, r0);
   if (proj_type == VDN_INITIAL_PROJECTION || proj_type == VDN_DIVU_ITERS) { mf_setval(gpp, 0.0, 0, gpp->nc, true); mf_setval(pp, 0.0, 0, 1, true); }
-  Hg2Args H; H.hi[0] = bx.hi[0]; H.hi[1] = bx.hi[1]; H.dt = dt; H.dtinv = 1.0 / dt; H.dxi[0] = 1.0 / dx[0]; H.dxi[1] = 1.0 / dx[1]; H.proj_type = proj_type;
-  Range3 rn = rng2(bx.lo[0], bx.hi[0] + 1, bx.lo[1], bx.hi[1] + 1);
-  hipLaunchKernelGGL(kk2_hg_update, grid_for(rn), B2, 0, st, un->fabs[0], uo->fabs[0], gpp->fabs[0], rhh->fabs[0], pp->fabs[0], phi->fabs[0], H, rn);
+  std::vector<std::pair<hg_update2_K, Range3>> vh;
+  for (int b = 0; b < un->nfabs(); b++) {
+    const vdn_box &bx = un->vbox[b];
+    Hg2Args H; H.hi[0] = bx.hi[0]; H.hi[1] = bx.hi[1]; H.dt = dt; H.dtinv = 1.0 / dt; H.dxi[0] = 1.0 / dx[0]; H.dxi[1] = 1.0 / dx[1]; H.proj_type = proj_type;
+    vh.push_back({ hg_update2_K{ un->fabs[b], uo->fabs[b], gpp->fabs[b], rhh->fabs[b], pp->fabs[b], phi->fabs[b], H }, rng2(bx.lo[0], bx.hi[0] + 1, bx.lo[1], bx.hi[1] + 1) });
+  }
+  run_cells(vh);
   mf_fill_boundary(gpp); mf_fill_boundary(pp);
   mf_temp_free(coeffs); mf_temp_free(phi); mf_temp_free(rh);
   arena_release(mark);

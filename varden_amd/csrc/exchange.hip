@@ -587,6 +587,7 @@ std::vector<XBoxInfo> xboxes_of(const vdn_multifab *mf) {
   for (size_t g = 0; g < bx.size(); g++) {
     XBoxInfo b; memset(&b, 0, sizeof b);
     for (int d = 0; d < 3; d++) { b.vlo[d] = bx[g].lo[d]; b.vhi[d] = bx[g].hi[d] + mf->nodal[d]; }
+    if (ctx().prm.dm == 2) b.vhi[2] = bx[g].hi[2];       // dm = 2: plane k = 0 alone (a field nodal along z has a second plane that nothing reads)
     b.owner = la->owner[mf->lev][g];
     if (b.owner == ctx().rank) b.fv = mf->fabs[li++];
     v.push_back(b);
