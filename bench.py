@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- cells*steps/sec of advance_timestep on the MI355X-native hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 256|512|amr2|amr3] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 256|512|amr2|amr3] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets the workload up, runs W warm-up and K timed steps, writes --dump-outputs and prints the line: `value` and `ms_per_step`
+are the timed steps, `config` their phase split, V-cycle counts and transport traffic.  Everything else the bench measures runs with
+`--full` only (the line's `roofline`, `cpu_baseline`, `extra_workloads` and `config.one_box_512` are null / empty without it).
 
 `--gpus N` with N > 1 STARTS ITS OWN N RANKS: the parent process touches neither torch.cuda nor HIP, spawns N children (one per
 GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their environment), waits for them and exits with their code;
@@ -21,7 +25,7 @@ cflfac 0.9, init_shrink 0.1, init_iter 1, MAC + HG projection every step, exec/t
 A "step" = one pass of the reference's time-loop body (src/varden.f90:291-328): ghost fills, estdt, advance_timestep, uold<-unew.
 All state is resident in HBM before the timed region.
 
-`roofline` is the MAC-multigrid red-black Gauss-Seidel colour pass on the finest level (48 algorithmic B/cell/pass; round 5: the level by colour),
+With `--full`: `roofline` is the MAC-multigrid red-black Gauss-Seidel colour pass on the finest level (48 algorithmic B/cell/pass; round 5: the level by colour),
 timed with HIP events on the launch stream inside the library, its HBM bytes per launch measured in the same run by two rocprofv3 --pmc child passes; `cpu_baseline` is the CPU oracle (a port, OpenMP) on a bounded
 sample of the same workload, with the survey's per-core timing of the reference's own Godunov kernels quoted next to it.
 """
@@ -206,6 +210,8 @@ def parse_args():
     ap.add_argument("--config", default=os.environ.get("VDN_BENCH_CONFIG", "256"), choices=["256", "512", "amr2", "amr3"])
     ap.add_argument("--scaling", default=os.environ.get("VDN_BENCH_SCALING", "weak"), choices=["weak", "strong"])
     ap.add_argument("--box", dest="n", type=int, default=256, help="box width (256/512) or base-level width (amr2/amr3)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the CPU baseline against the oracle, the roofline probe, the extra workloads "
+                    "and the 512 config's one-box companion (--cpu-box, --cpu-steps, --skip-cpu, --no-calib, --no-cpu256, --no-pmc and --no-extra shape these legs)")
     ap.add_argument("--cpu-box", dest="cpu_n", type=int, default=0, help="width of the CPU sample (0: 128, or 64 for amr)")
     ap.add_argument("--cpu-steps", dest="cpu_steps", type=int, default=3, help="timed oracle steps of the cpu_baseline leg (the median is reported; each is compared with the GPU)")
     ap.add_argument("--skip-cpu", dest="no_cpu", action="store_true")
@@ -216,7 +222,7 @@ def parse_args():
     ap.add_argument("--no-cpu256", dest="no_cpu256", action="store_true", help="skip cpu_baseline.sample_256 (one oracle step at the headline size, about 20 s with its start-up)")
     ap.add_argument("--no-pmc", dest="no_pmc", action="store_true", help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes on tools/smoother_probe.py); "
                     "the committed counter summary is quoted instead.  Needed when bench.py itself runs under rocprofv3")
-    ap.add_argument("--no-extra", dest="no_extra", action="store_true", help="skip the extra_workloads (512^3 in eight boxes and in one box, tagged two- and three-level hierarchies, the viscous 256^3 step, the viscous three-level run with regridding) of the default N = 1 line")
+    ap.add_argument("--no-extra", dest="no_extra", action="store_true", help="skip the extra_workloads (512^3 in eight boxes and in one box, tagged two- and three-level hierarchies, the viscous 256^3 step, the viscous three-level run with regridding) of the --full N = 1 line")
     ap.add_argument("--dump-outputs", dest="dump_dir", default=None, metavar="DIR",
                     help="after the timed steps write the state the last one computed (u, s, gp, p, dt, time) to DIR/<name>.npy, float64, at most 64 MB in all "
                          "(a fixed, seeded sample of cells when the fields are larger): two builds run with the same arguments can be compared output for output.  "
@@ -404,14 +410,14 @@ def main():
     if args.dump_dir:                                      # (after the clock stopped: the copies to the host are not timed)
         dumped = dump_outputs(G, args.dump_dir, amr, rank)
     rho = None
-    if rank == 0 and not amr:
+    if args.full and rank == 0 and not amr:
         rho = G.sold[0].to_numpy()[..., 0]                  # rank 0's first box, for the smoother probe's coefficients
     G.close()                                              # also tears the RCCL communicator down
 
     # ---- strong scaling's N = 1 point is the eight-box run; the same 512^3 domain as ONE box on this GPU beside it (the best one-GPU time: speed-ups read against
     #      the eight-box point are flattered by what the decomposition itself costs) ----------
     one_box_512 = None
-    if world == 1 and args.config == "512" and n == 256 and not args.no_extra:
+    if args.full and world == 1 and args.config == "512" and n == 256 and not args.no_extra:
         G1, cells1, wl1, _, _ = build_workload("256", 512)
         G1.step()
         torch.cuda.synchronize()
@@ -427,7 +433,7 @@ def main():
 
     # ---- the other single-GPU workloads of BASELINE.json, a few timed steps each (the headline stays configs[1]) ----------
     extra = []
-    if world == 1 and args.config == "256" and n == 256 and not args.no_extra:
+    if args.full and world == 1 and args.config == "256" and n == 256 and not args.no_extra:
         XS = 10                                            # timed steps of every extra workload (one warm-up step before)
         # 512^3 as eight boxes (configs[2] on one GPU), 512^3 as ONE box (north_star's single-GPU size), the tagged hierarchies of configs[3] and configs[4]
         for cfg, n2 in (("512", 256), ("256", 512), ("amr2", 256), ("amr3", 256)):
@@ -484,7 +490,7 @@ def main():
 
     # ---- roofline of the dominant kernel: one colour pass of the MAC-MG smoother at 256^3 ----------
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         bl.initialize(prm, 0, 1, local_rank)               # the probe is a single-rank, single-box measurement
         pn = n if not amr else 256
         if rho is None:                                     # amr: the same bubble density on one 256^3 box
@@ -564,7 +570,7 @@ def main():
 
     # ---- CPU baseline: the oracle (a port of the same algorithm, OpenMP) on a bounded sample ------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:      # reported at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:      # reported at N = 1 only
         nthreads = min(16, os.cpu_count() or 1)
         os.environ["OMP_NUM_THREADS"] = str(nthreads)
         from oracle import voracle as vo
@@ -674,7 +680,7 @@ def main():
             "value": round(value, 1), "unit": "cells*steps/s",
             "n_gpus": world, "rccl_nranks": rccl_nranks, "transport": transport, "library": capi.load().vdn_build_flavour().decode(), "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * el / args.steps, 3),
-            "higher_is_better": True, "scaling": args.scaling if not amr else "strong", "vs_baseline": None,
+            "higher_is_better": True, "scaling": args.scaling if not amr else "strong", "vs_baseline": None, "full": args.full,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": workload, "parallelism": par, "cells": cells,
                        "phase_ms_per_step": {k: round(1e3 * v / args.steps, 3) for k, v in phases.items()},

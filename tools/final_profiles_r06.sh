@@ -4,8 +4,8 @@
 export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/r06; mkdir -p $O
 if [ "$1" != "pmc" ]; then
-  # 0. the default line, exactly as the driver runs it
-  python bench.py > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log > $O/bench_default_line.json; tail -c 300 $O/bench_default.log; echo
+  # 0. the full line: in-run counters of the roofline pass, CPU baseline, extra workloads
+  python bench.py --full > $O/bench_default.log 2>&1; grep '^{' $O/bench_default.log > $O/bench_default_line.json; tail -c 300 $O/bench_default.log; echo
   # 1. kernel trace + stats of the headline workload
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o b -- python3 bench.py --steps 5 --warmup 2 --skip-cpu --no-extra --no-pmc > $O/bench.log 2>&1
   cp $(find $O/bench -name "*kernel_stats.csv" | head -1) $O/r06_bench_kernel_stats.csv

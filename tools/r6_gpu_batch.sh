@@ -8,6 +8,6 @@ VDN_LIB_FLAVOUR=testing VDN_MAC_SPLIT_MIN=0 VDN_MAC_SLAB=16 python tools/long_vs
 tail -2 $O/long_inviscid_128_split_slab_vs_oracle.txt
 VDN_FORCE_PACKED=2 python bench.py --config 512 --steps 3 --warmup 1 --skip-cpu --no-pmc > $O/bench512_one_gpu_rccl_self.log 2>&1
 grep '^{' $O/bench512_one_gpu_rccl_self.log > $O/bench512_one_gpu_rccl_self.json; tail -c 400 $O/bench512_one_gpu_rccl_self.log
-python bench.py --config 512 --steps 5 --warmup 2 --skip-cpu --no-pmc > $O/bench512.log 2>&1
+python bench.py --config 512 --full --steps 5 --warmup 2 --skip-cpu --no-pmc > $O/bench512.log 2>&1
 grep '^{' $O/bench512.log > $O/bench512.json
 python tools/exchange_probe.py > $O/exchange_probe.txt 2>&1; tail -12 $O/exchange_probe.txt
