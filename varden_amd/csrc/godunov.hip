@@ -113,55 +113,9 @@ __global__ void __launch_bounds__(256) kk_slopes(FV s, FV sl0, FV sl1, FV sl2, G
 
 // k-marching form of kk_slopes for all three directions at once: kk_slopes reads the five values of every direction through the L1 (13
 // loads per cell and component; texture addresser busy 73 %, 2.1 GB fetched for 0.43 GB of s).  Here a thread keeps the five planes
-// k-2 .. k+2 of its column in registers (one load per plane and component), takes x-neighbours from the lanes next to it and y-neighbours
-// from the rows next to it (LDS); tiles overlap by two cells either side (60 x 12 of 64 x 16 cells owned).  slope_vals on the same values.
-constexpr int SNY = 16;
-// (Measured and not kept: sharing the Fromm slopes between neighbours -- one fromm_of per cell and direction instead of three, exchanged like
-// the values -- needs more than the 128 VGPRs of a 1024-thread workgroup for three components: 3.1 ms spilling, 1.37 ms one component at a
-// time with two barriers each, against 0.69 ms for this form; two components: 0.46 against 0.47 ms.)
-template <int NC> __global__ void __launch_bounds__(64 * SNY) kk_slopes_m(FV s, FV sl0, FV sl1, FV sl2, GArgs A, Range3 r, int klen, double *vmax) {
-  __shared__ double ly[NC][SNY][64];
-  const int lane = threadIdx.x, row = threadIdx.y;
-  const int i = r.lo[0] - 2 + (int)blockIdx.x * 60 + lane, j = r.lo[1] - 2 + (int)blockIdx.y * (SNY - 4) + row;
-  const bool own_ij = lane >= 2 && lane <= 61 && row >= 2 && row <= SNY - 3 && i <= r.hi[0] && j <= r.hi[1];
-  const int ic = min(max(i, A.lo[0] - 3), A.hi[0] + 3), jc = min(max(j, A.lo[1] - 3), A.hi[1] + 3);
-  const int k0 = r.lo[2] + (int)blockIdx.z * klen, k1 = min(k0 + klen - 1, r.hi[2]);
-  const long sp = (long)s.n0 * s.n1;
-  const double *ps[NC];
-  #pragma unroll
-  for (int c = 0; c < NC; c++) ps[c] = s.p + fv_idx(s, ic, jc, s.a2) + s.sc * c;            // plane a2 of the column
-  #define SPL(c, kk) ps[c][(long)(min(max((kk), A.lo[2] - 3), A.hi[2] + 3) - s.a2) * sp]
-  #define SPEC(d, sd, c) (A.adv[d][sd][c] == VDN_EXT_DIR || A.adv[d][sd][c] == VDN_HOEXTRAP)
-  double w[NC][5];                                                    // the column's planes k-2 .. k+2
-  #pragma unroll
-  for (int c = 0; c < NC; c++) { w[c][0] = 0.0; for (int q = 1; q < 5; q++) w[c][q] = SPL(c, k0 - 3 + q); }
-  double m = 0.0;
-  for (int k = k0; k <= k1; k++) {
-    #pragma unroll
-    for (int c = 0; c < NC; c++) { w[c][0] = w[c][1]; w[c][1] = w[c][2]; w[c][2] = w[c][3]; w[c][3] = w[c][4]; w[c][4] = SPL(c, k + 2); }
-    #pragma unroll
-    for (int c = 0; c < NC; c++) ly[c][row][lane] = w[c][2];
-    __syncthreads();
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      const double s0 = w[c][2];
-      const double xm1 = lane_prev(s0), xp1 = lane_next(s0), xm2 = lane_prev(xm1), xp2 = lane_next(xp1);
-      if (own_ij) {
-        const double ym2 = ly[c][row - 2][lane], ym1 = ly[c][row - 1][lane], yp1 = ly[c][row + 1][lane], yp2 = ly[c][row + 2][lane];
-        fv_at(sl0, i, j, k, c) = slope_vals(xm2, xm1, s0, xp1, xp2, i, A.lo[0], A.hi[0], SPEC(0, 0, c), SPEC(0, 1, c), A.slope_order);
-        fv_at(sl1, i, j, k, c) = slope_vals(ym2, ym1, s0, yp1, yp2, j, A.lo[1], A.hi[1], SPEC(1, 0, c), SPEC(1, 1, c), A.slope_order);
-        fv_at(sl2, i, j, k, c) = slope_vals(w[c][0], w[c][1], s0, w[c][3], w[c][4], k, A.lo[2], A.hi[2], SPEC(2, 0, c), SPEC(2, 1, c), A.slope_order);
-        if (vmax && i >= A.lo[0] && i <= A.hi[0] && j >= A.lo[1] && j <= A.hi[1] && k >= A.lo[2] && k <= A.hi[2]) m = fmax(m, fabs(s0));
-      }
-    }
-    __syncthreads();      // (round 5, measured: double-buffering ly to drop this barrier made the march slower, 0.681 -> 0.736 ms: 48 KB of LDS per workgroup)
-  }
-  #undef SPL
-  #undef SPEC
-  if (vmax) block_atomic_max(vmax, m);
-}
-// The same march without the row exchange (round 5): the y-neighbours of plane k come straight from memory (they are the values the rows next door loaded
-// two planes ago: L2 hits), so there is no LDS, no barrier and no row overlap -- 64 x 4 threads own 60 x 4 cells, several workgroups share a CU.
+// k-2 .. k+2 of its column in registers (one load per plane and component) and takes x-neighbours from the lanes next to it; the y-neighbours
+// of plane k come straight from memory (they are the values the rows next door loaded two planes ago: L2 hits), so there is no LDS, no barrier
+// and no row overlap -- 64 x 4 threads own 60 x 4 cells, several workgroups share a CU.  slope_vals on the same values.
 // (Counters: 1.77 GB fetched per three-component launch for 0.43 GB of s -- the row and plane halos of neighbouring tiles rarely meet in one L2.  Measured and not
 // kept: the XCD-aware tile order of the other marches (xcd_tile) 0.645 -> 0.674 ms, with 64 x 8 workgroups 0.87 ms; fewer k-chunks no better.)
 // (Measured on this form and not kept: one fromm_of per cell along x and z -- the neighbours' from the lanes next door / carried from plane to plane -- instead of
@@ -214,8 +168,7 @@ template <int NC> __global__ void __launch_bounds__(256) kk_slopes_my(FV s, FV s
 }
 static void launch_slopes(const FV &s, const FV sl[3], const GArgs &A, const Range3 &rg, int ncomp, double *vmax, hipStream_t st) {
   static const bool marching = !(vdn_env("VDN_SLOPES_MARCH") && atoi(vdn_env("VDN_SLOPES_MARCH")) == 0);
-  static const bool yglobal = !(vdn_env("VDN_SLOPES_Y") && atoi(vdn_env("VDN_SLOPES_Y")) == 0);        // 0: the row exchange through LDS (kk_slopes_m: 0.691 / 0.470 ms)
-  if (marching && yglobal && (ncomp == 2 || ncomp == 3) && s.a0 <= A.lo[0] - 3 && s.a1 <= A.lo[1] - 3 && s.a2 <= A.lo[2] - 3) {
+  if (marching && (ncomp == 2 || ncomp == 3) && s.a0 <= A.lo[0] - 3 && s.a1 <= A.lo[1] - 3 && s.a2 <= A.lo[2] - 3) {
     const int nx = rg.hi[0] - rg.lo[0] + 1, ny = rg.hi[1] - rg.lo[1] + 1, nz = rg.hi[2] - rg.lo[2] + 1;
     const int tiles = ((nx + 59) / 60) * ((ny + 3) / 4);
     int chunks = std::max(1, std::min(nz / 8, (32 * 256 + tiles - 1) / tiles));      // (measured at 256^3, three / two components: 4 x 256 workgroups 0.741 / 0.477 ms, 8 x 0.667 / 0.418, 16 x 0.661 / 0.406, 32 x 0.645 / 0.384)
@@ -223,16 +176,6 @@ static void launch_slopes(const FV &s, const FV sl[3], const GArgs &A, const Ran
     const dim3 g((nx + 59) / 60, (ny + 3) / 4, (nz + klen - 1) / klen), blk(64, 4, 1);
     if (ncomp == 3) hipLaunchKernelGGL(kk_slopes_my<3>, g, blk, 0, st, s, sl[0], sl[1], sl[2], A, rg, klen, vmax);
     else hipLaunchKernelGGL(kk_slopes_my<2>, g, blk, 0, st, s, sl[0], sl[1], sl[2], A, rg, klen, vmax);
-    return;
-  }
-  if (marching && (ncomp == 2 || ncomp == 3) && s.a0 <= A.lo[0] - 3 && s.a1 <= A.lo[1] - 3 && s.a2 <= A.lo[2] - 3) {
-    const int nx = rg.hi[0] - rg.lo[0] + 1, ny = rg.hi[1] - rg.lo[1] + 1, nz = rg.hi[2] - rg.lo[2] + 1;
-    const int tiles = ((nx + 59) / 60) * ((ny + SNY - 5) / (SNY - 4));
-    int chunks = std::max(1, std::min(nz / 8, (4 * 256 + tiles - 1) / tiles));        // ~4 workgroups per CU, chunks of >= 8 planes
-    const int klen = (nz + chunks - 1) / chunks;
-    const dim3 g((nx + 59) / 60, (ny + SNY - 5) / (SNY - 4), (nz + klen - 1) / klen), blk(64, SNY, 1);
-    if (ncomp == 3) hipLaunchKernelGGL(kk_slopes_m<3>, g, blk, 0, st, s, sl[0], sl[1], sl[2], A, rg, klen, vmax);
-    else hipLaunchKernelGGL(kk_slopes_m<2>, g, blk, 0, st, s, sl[0], sl[1], sl[2], A, rg, klen, vmax);
     return;
   }
   hipLaunchKernelGGL(kk_slopes, grid_for(rg), dim3(64, 4, 1), 0, st, s, sl[0], sl[1], sl[2], A, rg, 7, vmax);
@@ -290,14 +233,13 @@ template <int D> DEVI void mk_pair(const GArgs &A, const FV &s, const FV &slp, c
 }
 
 // stage B: simh_D on the lower faces of cell (i,j,k);  SI has 3*ncomp comps: [D*ncomp + c]
-struct MkPlain { FV s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SI, SC, sex, sey, sez, flx, fly, flz; GArgs A; const double *umax; };
 DEVI void mk_B_cell(const FV &s, const FV &sl0, const FV &sl1, const FV &sl2, const FV &um, const FV &vm, const FV &wm, const FV &force, const FV &macrhs, const FV &SI,
-                    const GArgs &A, int i, int j, int k, double eps, int dmask = 7) {
+                    const GArgs &A, int i, int j, int k, double eps) {
   for (int c = 0; c < A.ncomp; c++) {
     double L, R;
-    if ((dmask & 1) && i >= A.lo[0]) { mk_pair<0>(A, s, sl0, um, force, macrhs, c, i, j, k, L, R); fv_at(SI, i, j, k, 0 * A.ncomp + c) = upwind_mac(L, R, fv_get(um, i, j, k), eps); }
-    if ((dmask & 2) && j >= A.lo[1]) { mk_pair<1>(A, s, sl1, vm, force, macrhs, c, i, j, k, L, R); fv_at(SI, i, j, k, 1 * A.ncomp + c) = upwind_mac(L, R, fv_get(vm, i, j, k), eps); }
-    if ((dmask & 4) && k >= A.lo[2]) { mk_pair<2>(A, s, sl2, wm, force, macrhs, c, i, j, k, L, R); fv_at(SI, i, j, k, 2 * A.ncomp + c) = upwind_mac(L, R, fv_get(wm, i, j, k), eps); }
+    if (i >= A.lo[0]) { mk_pair<0>(A, s, sl0, um, force, macrhs, c, i, j, k, L, R); fv_at(SI, i, j, k, 0 * A.ncomp + c) = upwind_mac(L, R, fv_get(um, i, j, k), eps); }
+    if (j >= A.lo[1]) { mk_pair<1>(A, s, sl1, vm, force, macrhs, c, i, j, k, L, R); fv_at(SI, i, j, k, 1 * A.ncomp + c) = upwind_mac(L, R, fv_get(vm, i, j, k), eps); }
+    if (k >= A.lo[2]) { mk_pair<2>(A, s, sl2, wm, force, macrhs, c, i, j, k, L, R); fv_at(SI, i, j, k, 2 * A.ncomp + c) = upwind_mac(L, R, fv_get(wm, i, j, k), eps); }
   }
 }
 __global__ void __launch_bounds__(256) kk_mk_B(FV s, FV sl0, FV sl1, FV sl2, FV um, FV vm, FV wm, FV force, FV macrhs, FV SI, GArgs A, Range3 r, const double *umax) {
@@ -338,14 +280,14 @@ template <int D, int T> DEVI void mk_C_one(const GArgs &A, const FV &s, const FV
 DEVI int sc_idx(int D, int T, int ncomp, int c) { return (D * 2 + (T > D ? T - 1 : T)) * ncomp + c; }
 
 DEVI void mk_C_cell(const FV &s, const FV &sl0, const FV &sl1, const FV &sl2, const FV &um, const FV &vm, const FV &wm, const FV &force, const FV &macrhs, const FV &SI, const FV &SC,
-                    const GArgs &A, int i, int j, int k, double eps, int dmask = 7) {
+                    const GArgs &A, int i, int j, int k, double eps) {
   for (int c = 0; c < A.ncomp; c++) {
-    if (dmask & 1) mk_C_one<0, 1>(A, s, sl0, um, vm, force, macrhs, SI, SC, c, i, j, k, eps);
-    if (dmask & 1) mk_C_one<0, 2>(A, s, sl0, um, wm, force, macrhs, SI, SC, c, i, j, k, eps);
-    if (dmask & 2) mk_C_one<1, 0>(A, s, sl1, vm, um, force, macrhs, SI, SC, c, i, j, k, eps);
-    if (dmask & 2) mk_C_one<1, 2>(A, s, sl1, vm, wm, force, macrhs, SI, SC, c, i, j, k, eps);
-    if (dmask & 4) mk_C_one<2, 0>(A, s, sl2, wm, um, force, macrhs, SI, SC, c, i, j, k, eps);
-    if (dmask & 4) mk_C_one<2, 1>(A, s, sl2, wm, vm, force, macrhs, SI, SC, c, i, j, k, eps);
+    mk_C_one<0, 1>(A, s, sl0, um, vm, force, macrhs, SI, SC, c, i, j, k, eps);
+    mk_C_one<0, 2>(A, s, sl0, um, wm, force, macrhs, SI, SC, c, i, j, k, eps);
+    mk_C_one<1, 0>(A, s, sl1, vm, um, force, macrhs, SI, SC, c, i, j, k, eps);
+    mk_C_one<1, 2>(A, s, sl1, vm, wm, force, macrhs, SI, SC, c, i, j, k, eps);
+    mk_C_one<2, 0>(A, s, sl2, wm, um, force, macrhs, SI, SC, c, i, j, k, eps);
+    mk_C_one<2, 1>(A, s, sl2, wm, vm, force, macrhs, SI, SC, c, i, j, k, eps);
   }
 }
 __global__ void __launch_bounds__(256) kk_mk_C(FV s, FV sl0, FV sl1, FV sl2, FV um, FV vm, FV wm, FV force, FV macrhs, FV SI, FV SC, GArgs A, Range3 r, const double *umax) {
@@ -401,11 +343,11 @@ template <int D> DEVI void mk_D_one(const GArgs &A, const FV &s, const FV &slp, 
 }
 
 DEVI void mk_D_cell(const FV &s, const FV &sl0, const FV &sl1, const FV &sl2, const FV &um, const FV &vm, const FV &wm, const FV &force, const FV &macrhs, const FV &SC,
-                    const FV &sex, const FV &sey, const FV &sez, const FV &flx, const FV &fly, const FV &flz, const GArgs &A, int i, int j, int k, double eps, int dmask = 7) {
+                    const FV &sex, const FV &sey, const FV &sez, const FV &flx, const FV &fly, const FV &flz, const GArgs &A, int i, int j, int k, double eps) {
   for (int c = 0; c < A.ncomp; c++) {
-    if (dmask & 1) mk_D_one<0>(A, s, sl0, um, vm, wm, force, macrhs, SC, sex, flx, c, i, j, k, eps);
-    if (dmask & 2) mk_D_one<1>(A, s, sl1, vm, um, wm, force, macrhs, SC, sey, fly, c, i, j, k, eps);
-    if (dmask & 4) mk_D_one<2>(A, s, sl2, wm, um, vm, force, macrhs, SC, sez, flz, c, i, j, k, eps);
+    mk_D_one<0>(A, s, sl0, um, vm, wm, force, macrhs, SC, sex, flx, c, i, j, k, eps);
+    mk_D_one<1>(A, s, sl1, vm, um, wm, force, macrhs, SC, sey, fly, c, i, j, k, eps);
+    mk_D_one<2>(A, s, sl2, wm, um, vm, force, macrhs, SC, sez, flz, c, i, j, k, eps);
   }
 }
 __global__ void __launch_bounds__(256) kk_mk_D(FV s, FV sl0, FV sl1, FV sl2, FV um, FV vm, FV wm, FV force, FV macrhs, FV SC,
@@ -415,43 +357,6 @@ __global__ void __launch_bounds__(256) kk_mk_D(FV s, FV sl0, FV sl1, FV sl2, FV 
   mk_D_cell(s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SC, sex, sey, sez, flx, fly, flz, A, i, j, k, eps_from(umax));
 }
 
-// ---- boundary slabs --------------------------------------------------------------------------------------------------------------
-// Round 2: the marching kernels below carry NO boundary code.  The physical boundary rules (bc_pair and the edge-state rules) only
-// change states ON the faces of a box that lie on a physical domain boundary: a two-dimensional set.  The marching kernels compute
-// every face with the interior formulas, and each stage is followed by ONE launch of the face-centred code above over the (at most
-// six) one-cell-thick slabs that hold those faces.  The face-centred and the marching forms are bit-identical
-// (tests/test_kernels_gpu.py::test_godunov_marching_equals_face_centred), so the result is what the round-1 kernels produced, while the
-// marches lose their branches, the register copies behind them (47 % of the instructions of kk_vp_B_m were v_mov) and ~100 VGPRs.
-struct Slabs { int n; int dir[6], pos[6]; Range3 r; };
-// slabs of range r (a stage's index range: lo-1..hi+1 for B and C, lo..hi+1 for D) that hold the physical boundary faces of the box
-static Slabs boundary_slabs(const GArgs &A, const Range3 &r) {
-  Slabs S; S.n = 0; S.r = r;
-  for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) {
-    const int ph = A.phys[d][sd];
-    if (ph == VDN_INTERIOR || ph == VDN_PERIODIC) continue;
-    S.dir[S.n] = d; S.pos[S.n] = sd == 0 ? A.lo[d] : A.hi[d] + 1; S.n++;
-  }
-  return S;
-}
-template <class F> __global__ void __launch_bounds__(256) kk_slabs(Slabs S, F f) {
-  const int sl = blockIdx.z;
-  const int d = S.dir[sl], da = d == 0 ? 1 : 0, db = d == 2 ? 1 : 2;
-  int q[3];
-  q[d] = S.pos[sl];
-  q[da] = S.r.lo[da] + (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  q[db] = S.r.lo[db] + (int)(blockIdx.y * blockDim.y + threadIdx.y);
-  if (q[da] > S.r.hi[da] || q[db] > S.r.hi[db]) return;
-  f(q[0], q[1], q[2], 1 << d);          // only the states on the faces normal to d change
-}
-template <class F> static void launch_slabs(const Slabs &S, const F &f, hipStream_t st) {
-  if (S.n == 0) return;
-  int m = 1;
-  for (int d = 0; d < 3; d++) m = std::max(m, S.r.hi[d] - S.r.lo[d] + 1);
-  hipLaunchKernelGGL((kk_slabs<F>), dim3((m + 63) / 64, (m + 3) / 4, S.n), dim3(64, 4, 1), 0, st, S, f);
-}
-struct MkBFix { MkPlain P; __device__ void operator()(int i, int j, int k, int dmask) const { mk_B_cell(P.s, P.sl0, P.sl1, P.sl2, P.um, P.vm, P.wm, P.force, P.macrhs, P.SI, P.A, i, j, k, eps_from(P.umax), dmask); } };
-struct MkCFix { MkPlain P; __device__ void operator()(int i, int j, int k, int dmask) const { mk_C_cell(P.s, P.sl0, P.sl1, P.sl2, P.um, P.vm, P.wm, P.force, P.macrhs, P.SI, P.SC, P.A, i, j, k, eps_from(P.umax), dmask); } };
-struct MkDFix { MkPlain P; __device__ void operator()(int i, int j, int k, int dmask) const { mk_D_cell(P.s, P.sl0, P.sl1, P.sl2, P.um, P.vm, P.wm, P.force, P.macrhs, P.SC, P.sex, P.sey, P.sez, P.flx, P.fly, P.flz, P.A, i, j, k, eps_from(P.umax), dmask); } };
 
 // ====================================================================================================
 // Cell-centred, k-marching form of the stage B / C / D kernels (the default path)
@@ -474,11 +379,9 @@ struct MkDFix { MkPlain P; __device__ void operator()(int i, int j, int k, int d
 // VDN_GODUNOV_BATCH=1 launches the descriptor (box-batched) kernels also for a level of one box. Measured at 256^3: they need
 // fewer VGPRs (mk_D<1> 116 vs 174) yet run slower there (scalar 6.6 vs 5.6 ms, velocity 10.0 vs 8.2 ms), so one box keeps the by-value kernels
 static bool batch_always() { static const bool b = vdn_env("VDN_GODUNOV_BATCH") && atoi(vdn_env("VDN_GODUNOV_BATCH")) != 0; return b; }
-// VDN_GOD_SLAB_BC=0: the round-1 marches with the boundary code inside (kept for comparison); default: interior marches + boundary slabs
-static bool slab_bc() { static const bool b = !(vdn_env("VDN_GOD_SLAB_BC") && atoi(vdn_env("VDN_GOD_SLAB_BC")) == 0); return b; }
 // one launch per stage for all boxes (descriptors) or one set of launches per box (arguments by value)?  A level of an adaptive
 // hierarchy (hundreds of 16^3 .. 32^3 boxes) is launch-bound box by box; a level of a few large boxes -- 512^3 cut into eight 256^3
-// boxes -- runs faster box by box: the by-value kernels carry no boundary code (boundary slabs) and need fewer registers (measured,
+// boxes -- runs faster box by box: the by-value kernels need fewer registers (measured,
 // eight 256^3 boxes on one GPU: scalar 52 -> 42 ms, velocity 76 -> 54 ms per step).  VDN_GODUNOV_BATCH=1 forces the descriptors.
 static bool use_batched(const vdn_multifab *s) {
   if (s->nfabs() == 0) return false;
@@ -490,369 +393,11 @@ static bool use_batched(const vdn_multifab *s) {
 }
 bool god_per_box(const vdn_multifab *s) { return s->nfabs() >= 1 && !use_batched(s); }
 static bool plain_godunov() { static const bool p = vdn_env("VDN_GODUNOV_PLAIN") != nullptr; return p; }
-// parameters of the marching bodies: by value under the by-value kernels, references into the (constant) descriptor under the batched ones
-template <class T, bool R> struct Prm { typedef T type; };
-template <class T> struct Prm<T, true> { typedef const T &type; };
 // tile order of the marching kernels: XCD-aware (vdn_dev.h xcd_tile)
 __constant__ int g_god_xcd = 1;
 DEVI void xcd_remap(int &bx, int &by, int &bz) { if (g_god_xcd) xcd_tile(bx, by, bz); else { bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z; } }
-static void god_xcd_init() {
-  static bool done = false;
-  if (done) return;
-  done = true;
-}
 constexpr int TNY = 8;              // rows per tile: workgroup = 64 x TNY threads
-static int march_chunks() { return 12; }
-static dim3 march_grid(const Range3 &r, int &klen) {
-  const int nx = r.hi[0] - r.lo[0] + 1, ny = r.hi[1] - r.lo[1] + 1, nz = r.hi[2] - r.lo[2] + 1;
-  klen = (nz + march_chunks() - 1) / march_chunks(); if (klen < 1) klen = 1;
-  return dim3((nx + 62) / 63, (ny + TNY - 2) / (TNY - 1), (nz + klen - 1) / klen);
-}
-// i, j: the thread's cell;  ic, jc: the same clamped into the grown box (load indices);  own_ij: this thread emits
-#define MARCH_SETUP(r)                                                                   \
-  const int lane = threadIdx.x, row = threadIdx.y;                                       \
-  const int i = (r).lo[0] - 1 + BX * 63 + lane;                                                                 \
-  const int j = (r).lo[1] - 1 + BY * (TNY - 1) + row;                                     \
-  const bool own_ij = lane >= 1 && row >= 1 && i <= (r).hi[0] && j <= (r).hi[1];         \
-  const int ic = min(max(i, A.lo[0] - 1), A.hi[0] + 1), jc = min(max(j, A.lo[1] - 1), A.hi[1] + 1); \
-  const int ip = min(ic + 1, A.hi[0] + 1), jp = min(jc + 1, A.hi[1] + 1);                \
-  const bool edge_ij = ic == A.lo[0] || ic >= A.hi[0] || jc == A.lo[1] || jc >= A.hi[1]; \
-  const bool vx = in_valid(A, 0, i), vy = in_valid(A, 1, j);                             \
-  const int k0 = (r).lo[2] + BZ * klen, k1 = min(k0 + klen - 1, (r).hi[2]);
-#define MARCH_PLANE                                                                      \
-    const int kc = min(max(k, A.lo[2] - 1), A.hi[2] + 1), kp = min(kc + 1, A.hi[2] + 1); \
-    const bool emit = own_ij && k >= k0;                                                 \
-    const bool vz = in_valid(A, 2, k);                                                   \
-    const bool edge = edge_ij || kc == A.lo[2] || kc >= A.hi[2];                         \
-    const int buf = k & 1;                                                               \
-    (void)kp; (void)vz; (void)edge; (void)ip; (void)jp; (void)vx; (void)vy;
-
 DEVI double shfl_prev(double v) { return lane_prev(v); }
-DEVI bool in_valid(const GArgs &A, int d, int q) { return q >= A.lo[d] && q <= A.hi[d]; }
-DEVI double tv(bool cons, double fcons, double fconv, double dxT, double sp, double s0, double mp, double m0) {   // = trans_term on values
-  if (cons) return (fcons / dxT) * (sp * mp - s0 * m0);
-  return (fconv / dxT) * (mp + m0) * (sp - s0);
-}
-
-// one-dimensional predictor bases of component c in a cell along D: Lb = left state of the cell's UPPER D-face,
-// Rb = right state of its LOWER D-face (mk_pair without the boundary rule)
-template <int D> DEVI void mk_bases(const GArgs &A, int c, double s0, double slD, double mlo, double mup, double fterm, double mterm, double &Lb, double &Rb) {
-  const double dt2 = 0.5 * A.dt;
-  Lb = s0 + (0.5 - dt2 * mup / A.dx[D]) * slD;
-  Rb = s0 - (0.5 + dt2 * mlo / A.dx[D]) * slD;
-  if (A.use_minion) {
-    Lb = Lb + fterm; Rb = Rb + fterm;
-    if (A.cons[c]) { Lb = Lb - mterm; Rb = Rb - mterm; }
-  }
-}
-// this cell's half of the boundary rule on its bases (cells next to a box face only)
-template <int D> DEVI void mk_premod(const GArgs &A, const FV &s, int c, int i, int j, int k, double &Lb, double &Rb) {
-  const int q = coord<D>(i, j, k);
-  if (q == A.lo[D]) { double o = Rb; bc_pair(o, Rb, A.phys[D][0], 0, A.is_vel != 0, c == D, ld<D>(s, i, j, k, -1, c), false); }
-  if (q == A.hi[D]) { double o = Lb; bc_pair(Lb, o, A.phys[D][1], 1, A.is_vel != 0, c == D, ld<D>(s, i, j, k, 1, c), false); }
-}
-// the complete boundary rule on an assembled pair of the lower D-face of cell (i,j,k)
-template <int D> DEVI void mk_face_bc(const GArgs &A, const FV &s, int c, int i, int j, int k, double s0, double &L, double &R) {
-  const int side = face_side<D>(A, i, j, k);
-  if (side >= 0) bc_pair(L, R, A.phys[D][side], side, A.is_vel != 0, c == D, side == 0 ? ld<D>(s, i, j, k, -1, c) : s0, false);
-}
-
-// the per-plane load batch shared by the three mkflux stages
-#define MK_LOAD_CELL                                                                                                   \
-    const double m_lo[3] = { fv_get(um, ic, jc, kc), fv_get(vm, ic, jc, kc), fv_get(wm, ic, jc, kc) };                   \
-    const double m_up[3] = { fv_get(um, ic + 1, jc, kc), fv_get(vm, ic, jc + 1, kc), fv_get(wm, ic, jc, kc + 1) };       \
-    double s0[NC], sl[NC][3];                                                                                           \
-    _Pragma("unroll") for (int c = 0; c < NC; c++) {                                                                    \
-      s0[c] = fv_get(s, ic, jc, kc, c0 + c);                                                                                  \
-      sl[c][0] = fv_get(sl0, ic, jc, kc, c0 + c); sl[c][1] = fv_get(sl1, ic, jc, kc, c0 + c); sl[c][2] = fv_get(sl2, ic, jc, kc, c0 + c); \
-    }
-
-// ---- stage B ----------------------------------------------------------------------------------------------------
-template <int NC, bool R, bool BC> __device__ __forceinline__ void mk_B_m_body(typename Prm<FV, R>::type s, typename Prm<FV, R>::type sl0, typename Prm<FV, R>::type sl1, typename Prm<FV, R>::type sl2, typename Prm<FV, R>::type um, typename Prm<FV, R>::type vm, typename Prm<FV, R>::type wm, typename Prm<FV, R>::type force, typename Prm<FV, R>::type macrhs, typename Prm<FV, R>::type SI, typename Prm<GArgs, R>::type A, typename Prm<Range3, R>::type r, int klen, const double *umax, int c0, int ns, const int BX, const int BY, const int BZ) {
-  __shared__ double ly[2][NC][TNY][64];
-  MARCH_SETUP(r)
-  const double eps = eps_from(umax);
-  const double dt2 = 0.5 * A.dt;
-  double Lz[NC];
-  #pragma unroll
-  for (int c = 0; c < NC; c++) Lz[c] = 0.0;
-  for (int k = k0 - 1; k <= k1; k++) {
-    MARCH_PLANE
-    MK_LOAD_CELL
-    double ft[NC], mt[NC];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) { ft[c] = 0.0; mt[c] = 0.0; }
-    if (A.use_minion) {
-      const double mr = fv_get(macrhs, ic, jc, kc);
-      #pragma unroll
-      for (int c = 0; c < NC; c++) { ft[c] = dt2 * fv_get(force, ic, jc, kc, c0 + c); mt[c] = dt2 * s0[c] * mr; }
-    }
-    double Lb[NC][3], Rb[NC][3];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      mk_bases<0>(A, c0 + c, s0[c], sl[c][0], m_lo[0], m_up[0], ft[c], mt[c], Lb[c][0], Rb[c][0]);
-      mk_bases<1>(A, c0 + c, s0[c], sl[c][1], m_lo[1], m_up[1], ft[c], mt[c], Lb[c][1], Rb[c][1]);
-      mk_bases<2>(A, c0 + c, s0[c], sl[c][2], m_lo[2], m_up[2], ft[c], mt[c], Lb[c][2], Rb[c][2]);
-    }
-    // (no premod needed in stage B: the owner's complete rule is applied to the untouched pair)
-    #pragma unroll
-    for (int c = 0; c < NC; c++) ly[buf][c][row][lane] = Lb[c][1];
-    __syncthreads();
-    double Lx[NC], Ly[NC], Lzc[NC];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      Lx[c] = shfl_prev(Lb[c][0]);
-      Ly[c] = ly[buf][c][row >= 1 ? row - 1 : 0][lane];
-      Lzc[c] = Lz[c]; Lz[c] = Lb[c][2];
-    }
-    if (emit) {
-      if (BC && edge) {
-        #pragma unroll
-        for (int c = 0; c < NC; c++) {
-          mk_face_bc<0>(A, s, c0 + c, i, j, k, s0[c], Lx[c], Rb[c][0]); mk_face_bc<1>(A, s, c0 + c, i, j, k, s0[c], Ly[c], Rb[c][1]); mk_face_bc<2>(A, s, c0 + c, i, j, k, s0[c], Lzc[c], Rb[c][2]);
-        }
-      }
-      #pragma unroll
-      for (int c = 0; c < NC; c++) {
-        if (i >= A.lo[0]) fv_at(SI, i, j, k, 0 * ns + c0 + c) = upwind_mac(Lx[c], Rb[c][0], m_lo[0], eps);
-        if (j >= A.lo[1]) fv_at(SI, i, j, k, 1 * ns + c0 + c) = upwind_mac(Ly[c], Rb[c][1], m_lo[1], eps);
-        if (k >= A.lo[2]) fv_at(SI, i, j, k, 2 * ns + c0 + c) = upwind_mac(Lzc[c], Rb[c][2], m_lo[2], eps);
-      }
-    }
-  }
-}
-template <int NC, bool BC = true> __global__ void __launch_bounds__(64 * TNY) kk_mk_B_m(FV s, FV sl0, FV sl1, FV sl2, FV um, FV vm, FV wm, FV force, FV macrhs, FV SI, GArgs A, Range3 r, int klen, const double *umax, int c0, int ns) {
-  int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
-  mk_B_m_body<NC, false, BC>(s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SI, A, r, klen, umax, c0, ns, bx_, by_, bz_);
-}
-
-
-// ---- stage C ----------------------------------------------------------------------------------------------------
-// per cell and component: the three transverse terms t_T (from SI_T, mac_T) and the six chains base_D - t_T
-template <int NC, bool R, bool BC> __device__ __forceinline__ void mk_C_m_body(typename Prm<FV, R>::type s, typename Prm<FV, R>::type sl0, typename Prm<FV, R>::type sl1, typename Prm<FV, R>::type sl2, typename Prm<FV, R>::type um, typename Prm<FV, R>::type vm, typename Prm<FV, R>::type wm, typename Prm<FV, R>::type force, typename Prm<FV, R>::type macrhs, typename Prm<FV, R>::type SI, typename Prm<FV, R>::type SC, typename Prm<GArgs, R>::type A, typename Prm<Range3, R>::type r, int klen, const double *umax, int c0, int ns, const int BX, const int BY, const int BZ) {
-  __shared__ double ly[2][NC][2][TNY][64];
-  MARCH_SETUP(r)
-  const double eps = eps_from(umax);
-  const double dt2 = 0.5 * A.dt, dt3 = A.dt / 3.0, dt6 = A.dt / 6.0;
-  double Lz[NC][2];
-  #pragma unroll
-  for (int c = 0; c < NC; c++) { Lz[c][0] = 0.0; Lz[c][1] = 0.0; }
-  for (int k = k0 - 1; k <= k1; k++) {
-    MARCH_PLANE
-    MK_LOAD_CELL
-    double si0[NC][3], si1[NC][3];          // SI_T at the cell's lower / upper T-face
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      si0[c][0] = fv_get(SI, ic, jc, kc, 0 * ns + c0 + c); si1[c][0] = fv_get(SI, ip, jc, kc, 0 * ns + c0 + c);
-      si0[c][1] = fv_get(SI, ic, jc, kc, 1 * ns + c0 + c); si1[c][1] = fv_get(SI, ic, jp, kc, 1 * ns + c0 + c);
-      si0[c][2] = fv_get(SI, ic, jc, kc, 2 * ns + c0 + c); si1[c][2] = fv_get(SI, ic, jc, kp, 2 * ns + c0 + c);
-    }
-    double ft[NC], mt[NC];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) { ft[c] = 0.0; mt[c] = 0.0; }
-    if (A.use_minion) {
-      const double mr = fv_get(macrhs, ic, jc, kc);
-      #pragma unroll
-      for (int c = 0; c < NC; c++) { ft[c] = dt2 * fv_get(force, ic, jc, kc, c0 + c); mt[c] = dt2 * s0[c] * mr; }
-    }
-    double Lb[NC][3], Rb[NC][3];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      mk_bases<0>(A, c0 + c, s0[c], sl[c][0], m_lo[0], m_up[0], ft[c], mt[c], Lb[c][0], Rb[c][0]);
-      mk_bases<1>(A, c0 + c, s0[c], sl[c][1], m_lo[1], m_up[1], ft[c], mt[c], Lb[c][1], Rb[c][1]);
-      mk_bases<2>(A, c0 + c, s0[c], sl[c][2], m_lo[2], m_up[2], ft[c], mt[c], Lb[c][2], Rb[c][2]);
-    }
-    if (BC && edge) {
-      #pragma unroll
-      for (int c = 0; c < NC; c++) { mk_premod<0>(A, s, c0 + c, ic, jc, kc, Lb[c][0], Rb[c][0]); mk_premod<1>(A, s, c0 + c, ic, jc, kc, Lb[c][1], Rb[c][1]); mk_premod<2>(A, s, c0 + c, ic, jc, kc, Lb[c][2], Rb[c][2]); }
-    }
-    // VL[c][D][n] / VR[c][D][n]: n = 0,1 -> the two transverse directions of D in increasing order
-    double VL[NC][3][2], VR[NC][3][2];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      const bool cons = A.cons[c0 + c] != 0;
-      double t[3];
-      t[0] = tv(cons, dt3, dt6, A.dx[0], si1[c][0], si0[c][0], m_up[0], m_lo[0]);
-      t[1] = tv(cons, dt3, dt6, A.dx[1], si1[c][1], si0[c][1], m_up[1], m_lo[1]);
-      t[2] = tv(cons, dt3, dt6, A.dx[2], si1[c][2], si0[c][2], m_up[2], m_lo[2]);
-      // D = 0: T = 1, 2;  D = 1: T = 0, 2;  D = 2: T = 0, 1
-      VL[c][0][0] = Lb[c][0] - t[1]; VR[c][0][0] = Rb[c][0] - t[1]; VL[c][0][1] = Lb[c][0] - t[2]; VR[c][0][1] = Rb[c][0] - t[2];
-      VL[c][1][0] = Lb[c][1] - t[0]; VR[c][1][0] = Rb[c][1] - t[0]; VL[c][1][1] = Lb[c][1] - t[2]; VR[c][1][1] = Rb[c][1] - t[2];
-      VL[c][2][0] = Lb[c][2] - t[0]; VR[c][2][0] = Rb[c][2] - t[0]; VL[c][2][1] = Lb[c][2] - t[1]; VR[c][2][1] = Rb[c][2] - t[1];
-    }
-    #pragma unroll
-    for (int c = 0; c < NC; c++) { ly[buf][c][0][row][lane] = VL[c][1][0]; ly[buf][c][1][row][lane] = VL[c][1][1]; }
-    __syncthreads();
-    double Lx[NC][2], Ly[NC][2], Lzc[NC][2];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      Lx[c][0] = shfl_prev(VL[c][0][0]); Lx[c][1] = shfl_prev(VL[c][0][1]);
-      Ly[c][0] = ly[buf][c][0][row >= 1 ? row - 1 : 0][lane]; Ly[c][1] = ly[buf][c][1][row >= 1 ? row - 1 : 0][lane];
-      Lzc[c][0] = Lz[c][0]; Lzc[c][1] = Lz[c][1];
-      Lz[c][0] = VL[c][2][0]; Lz[c][1] = VL[c][2][1];
-    }
-    if (emit) {
-      if (BC && edge) {
-        #pragma unroll
-        for (int c = 0; c < NC; c++) {
-          #pragma unroll
-          for (int n = 0; n < 2; n++) {
-            mk_face_bc<0>(A, s, c0 + c, i, j, k, s0[c], Lx[c][n], VR[c][0][n]); mk_face_bc<1>(A, s, c0 + c, i, j, k, s0[c], Ly[c][n], VR[c][1][n]); mk_face_bc<2>(A, s, c0 + c, i, j, k, s0[c], Lzc[c][n], VR[c][2][n]);
-          }
-        }
-      }
-      // SC index (D,T): (D*2 + (T > D ? T-1 : T)) * NC + c;  valid where the D-face index >= lo[D] and the T index is valid
-      #pragma unroll
-      for (int c = 0; c < NC; c++) {
-        if (i >= A.lo[0]) {
-          if (vy) fv_at(SC, i, j, k, 0 * ns + c0 + c) = upwind_mac(Lx[c][0], VR[c][0][0], m_lo[0], eps);
-          if (vz) fv_at(SC, i, j, k, 1 * ns + c0 + c) = upwind_mac(Lx[c][1], VR[c][0][1], m_lo[0], eps);
-        }
-        if (j >= A.lo[1]) {
-          if (vx) fv_at(SC, i, j, k, 2 * ns + c0 + c) = upwind_mac(Ly[c][0], VR[c][1][0], m_lo[1], eps);
-          if (vz) fv_at(SC, i, j, k, 3 * ns + c0 + c) = upwind_mac(Ly[c][1], VR[c][1][1], m_lo[1], eps);
-        }
-        if (k >= A.lo[2]) {
-          if (vx) fv_at(SC, i, j, k, 4 * ns + c0 + c) = upwind_mac(Lzc[c][0], VR[c][2][0], m_lo[2], eps);
-          if (vy) fv_at(SC, i, j, k, 5 * ns + c0 + c) = upwind_mac(Lzc[c][1], VR[c][2][1], m_lo[2], eps);
-        }
-      }
-    }
-  }
-}
-template <int NC, bool BC = true> __global__ void __launch_bounds__(64 * TNY) kk_mk_C_m(FV s, FV sl0, FV sl1, FV sl2, FV um, FV vm, FV wm, FV force, FV macrhs, FV SI, FV SC, GArgs A, Range3 r, int klen, const double *umax, int c0, int ns) {
-  int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
-  mk_C_m_body<NC, false, BC>(s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SI, SC, A, r, klen, umax, c0, ns, bx_, by_, bz_);
-}
-
-
-// ---- stage D ----------------------------------------------------------------------------------------------------
-template <int D> DEVI double mk_edge_bc(const GArgs &A, const FV &s, int c, int i, int j, int k, double s0, double L, double R, double e) {
-  const int side = face_side<D>(A, i, j, k);
-  if (side >= 0) {                                   // mkflux.f90:2369-2402
-    const int ph = A.phys[D][side];
-    const double in = (side == 0) ? R : L;
-    const bool vel = A.is_vel != 0;
-    if (ph == VDN_INLET) e = (side == 0) ? ld<D>(s, i, j, k, -1, c) : s0;
-    else if (ph == VDN_SLIP_WALL) e = (vel && c == D) ? 0.0 : in;
-    else if (ph == VDN_NO_SLIP_WALL) e = vel ? 0.0 : in;
-    else if (ph == VDN_OUTLET) e = (vel && c == D) ? ((side == 0) ? fmin(in, 0.0) : fmax(in, 0.0)) : in;
-  }
-  return e;
-}
-// the per-plane inputs of stage D for one cell
-//   q0[c][n] / q1[c][n]: SC component n at the cell's lower / upper face of the direction that component lives on
-//   n: 0 = (0,1) 1 = (0,2) on x-faces, 2 = (1,0) 3 = (1,2) on y-faces, 4 = (2,0) 5 = (2,1) on z-faces
-template <int NC> struct DPlane { double m_lo[3], m_up[3], s0[NC], sl[NC][3], mr, f[NC], q0[NC][6], q1[NC][6]; };
-template <int NC> DEVI void d_load_plane(DPlane<NC> &P, const FV &s, const FV &sl0, const FV &sl1, const FV &sl2, const FV &um, const FV &vm, const FV &wm,
-                                         const FV &force, const FV &macrhs, const FV &SC, const GArgs &A, int ic, int jc, int ip, int jp, int k, int c0, int ns) {
-  const int kc = min(max(k, A.lo[2] - 1), A.hi[2] + 1), kp = min(kc + 1, A.hi[2] + 1);
-  P.m_lo[0] = fv_get(um, ic, jc, kc); P.m_lo[1] = fv_get(vm, ic, jc, kc); P.m_lo[2] = fv_get(wm, ic, jc, kc);
-  P.m_up[0] = fv_get(um, ic + 1, jc, kc); P.m_up[1] = fv_get(vm, ic, jc + 1, kc); P.m_up[2] = fv_get(wm, ic, jc, kc + 1);
-  P.mr = fv_get(macrhs, ic, jc, kc);
-  #pragma unroll
-  for (int c = 0; c < NC; c++) {
-    P.s0[c] = fv_get(s, ic, jc, kc, c0 + c);
-    P.sl[c][0] = fv_get(sl0, ic, jc, kc, c0 + c); P.sl[c][1] = fv_get(sl1, ic, jc, kc, c0 + c); P.sl[c][2] = fv_get(sl2, ic, jc, kc, c0 + c);
-    P.f[c] = fv_get(force, ic, jc, kc, c0 + c);
-    #pragma unroll
-    for (int n = 0; n < 6; n++) P.q0[c][n] = fv_get(SC, ic, jc, kc, n * ns + c0 + c);
-    P.q1[c][0] = fv_get(SC, ip, jc, kc, 0 * ns + c0 + c); P.q1[c][1] = fv_get(SC, ip, jc, kc, 1 * ns + c0 + c);
-    P.q1[c][2] = fv_get(SC, ic, jp, kc, 2 * ns + c0 + c); P.q1[c][3] = fv_get(SC, ic, jp, kc, 3 * ns + c0 + c);
-    P.q1[c][4] = fv_get(SC, ic, jc, kp, 4 * ns + c0 + c); P.q1[c][5] = fv_get(SC, ic, jc, kp, 5 * ns + c0 + c);
-  }
-}
-template <int NC, bool R, bool PF, bool BC> __device__ __forceinline__ void mk_D_m_body(typename Prm<FV, R>::type s, typename Prm<FV, R>::type sl0, typename Prm<FV, R>::type sl1, typename Prm<FV, R>::type sl2, typename Prm<FV, R>::type um, typename Prm<FV, R>::type vm, typename Prm<FV, R>::type wm, typename Prm<FV, R>::type force, typename Prm<FV, R>::type macrhs, typename Prm<FV, R>::type SC, typename Prm<FV, R>::type sex, typename Prm<FV, R>::type sey, typename Prm<FV, R>::type sez, typename Prm<FV, R>::type flx, typename Prm<FV, R>::type fly, typename Prm<FV, R>::type flz, typename Prm<GArgs, R>::type A, typename Prm<Range3, R>::type r, int klen, const double *umax, int c0, int ns, const int BX, const int BY, const int BZ) {
-  __shared__ double ly[2][NC][TNY][64];
-  MARCH_SETUP(r)
-  const double eps = eps_from(umax);
-  const double dt2 = 0.5 * A.dt, dt4 = A.dt / 4.0;
-  double Lz[NC];
-  #pragma unroll
-  for (int c = 0; c < NC; c++) Lz[c] = 0.0;
-  DPlane<NC> Pn;
-  if (PF) d_load_plane<NC>(Pn, s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SC, A, ic, jc, ip, jp, k0 - 1, c0, ns);
-  for (int k = k0 - 1; k <= k1; k++) {
-    MARCH_PLANE
-    // the plane's loads: with PF they were issued one step ahead (while the previous plane was being computed), so that a workgroup
-    // keeps two planes of loads in flight -- at 2 waves per SIMD the marches are bound by load latency, not by bandwidth
-    DPlane<NC> P;
-    if (PF) { P = Pn; if (k < k1) d_load_plane<NC>(Pn, s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SC, A, ic, jc, ip, jp, k + 1, c0, ns); }
-    else d_load_plane<NC>(P, s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SC, A, ic, jc, ip, jp, k, c0, ns);
-    const double (&m_lo)[3] = P.m_lo, (&m_up)[3] = P.m_up; const double (&s0)[NC] = P.s0; const double (&sl)[NC][3] = P.sl;
-    const double (&q0)[NC][6] = P.q0, (&q1)[NC][6] = P.q1;
-    const double mr = P.mr;
-    double ft[NC], mt[NC];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) { ft[c] = dt2 * P.f[c]; mt[c] = dt2 * s0[c] * mr; }
-    double Lb[NC][3], Rb[NC][3];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      mk_bases<0>(A, c0 + c, s0[c], sl[c][0], m_lo[0], m_up[0], ft[c], mt[c], Lb[c][0], Rb[c][0]);
-      mk_bases<1>(A, c0 + c, s0[c], sl[c][1], m_lo[1], m_up[1], ft[c], mt[c], Lb[c][1], Rb[c][1]);
-      mk_bases<2>(A, c0 + c, s0[c], sl[c][2], m_lo[2], m_up[2], ft[c], mt[c], Lb[c][2], Rb[c][2]);
-    }
-    if (BC && edge) {
-      #pragma unroll
-      for (int c = 0; c < NC; c++) { mk_premod<0>(A, s, c0 + c, ic, jc, kc, Lb[c][0], Rb[c][0]); mk_premod<1>(A, s, c0 + c, ic, jc, kc, Lb[c][1], Rb[c][1]); mk_premod<2>(A, s, c0 + c, ic, jc, kc, Lb[c][2], Rb[c][2]); }
-    }
-    double VL[NC][3], VR[NC][3];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      const bool cons = A.cons[c0 + c] != 0;
-      // a_T = (dt2/dx_T) * s0 * (mac_T(+) - mac_T)
-      const double a[3] = { (dt2 / A.dx[0]) * s0[c] * (m_up[0] - m_lo[0]), (dt2 / A.dx[1]) * s0[c] * (m_up[1] - m_lo[1]), (dt2 / A.dx[2]) * s0[c] * (m_up[2] - m_lo[2]) };
-      #define CHAIN(Dd, T1, T2, n1, n2)                                                                    \
-        { const double t1 = tv(cons, dt2, dt4, A.dx[T1], q1[c][n1], q0[c][n1], m_up[T1], m_lo[T1]);          \
-          const double t2 = tv(cons, dt2, dt4, A.dx[T2], q1[c][n2], q0[c][n2], m_up[T2], m_lo[T2]);          \
-          double vl = Lb[c][Dd], vr = Rb[c][Dd];                                                             \
-          vl = vl - t1; vr = vr - t1; vl = vl - t2; vr = vr - t2;                                            \
-          if (cons) { vl = vl + a[T1]; vr = vr + a[T1]; vl = vl + a[T2]; vr = vr + a[T2]; }                  \
-          if (!A.use_minion) { vl = vl + ft[c]; vr = vr + ft[c]; if (cons) { vl = vl - mt[c]; vr = vr - mt[c]; } } \
-          VL[c][Dd] = vl; VR[c][Dd] = vr; }
-      CHAIN(0, 1, 2, 3, 5)      // D = 0: T1 = 1 with SC(1,2) = simhyz,  T2 = 2 with SC(2,1) = simhzy
-      CHAIN(1, 0, 2, 1, 4)      // D = 1: T1 = 0 with SC(0,2),           T2 = 2 with SC(2,0)
-      CHAIN(2, 0, 1, 0, 2)      // D = 2: T1 = 0 with SC(0,1),           T2 = 1 with SC(1,0)
-      #undef CHAIN
-    }
-    #pragma unroll
-    for (int c = 0; c < NC; c++) ly[buf][c][row][lane] = VL[c][1];
-    __syncthreads();
-    double L[NC][3];
-    #pragma unroll
-    for (int c = 0; c < NC; c++) {
-      L[c][0] = shfl_prev(VL[c][0]);
-      L[c][1] = ly[buf][c][row >= 1 ? row - 1 : 0][lane];
-      L[c][2] = Lz[c]; Lz[c] = VL[c][2];
-    }
-    if (emit) {
-      double e[NC][3];
-      #pragma unroll
-      for (int c = 0; c < NC; c++) { e[c][0] = upwind_mac(L[c][0], VR[c][0], m_lo[0], eps); e[c][1] = upwind_mac(L[c][1], VR[c][1], m_lo[1], eps); e[c][2] = upwind_mac(L[c][2], VR[c][2], m_lo[2], eps); }
-      if (BC && edge) {
-        #pragma unroll
-        for (int c = 0; c < NC; c++) {
-          e[c][0] = mk_edge_bc<0>(A, s, c0 + c, i, j, k, s0[c], L[c][0], VR[c][0], e[c][0]);
-          e[c][1] = mk_edge_bc<1>(A, s, c0 + c, i, j, k, s0[c], L[c][1], VR[c][1], e[c][1]);
-          e[c][2] = mk_edge_bc<2>(A, s, c0 + c, i, j, k, s0[c], L[c][2], VR[c][2], e[c][2]);
-        }
-      }
-      #pragma unroll
-      for (int c = 0; c < NC; c++) {
-        const bool cons = A.cons[c0 + c] != 0;
-        if (vy && vz) { fv_at(sex, i, j, k, c0 + c) = e[c][0]; if (cons) fv_at(flx, i, j, k, c0 + c) = e[c][0] * m_lo[0]; }
-        if (vx && vz) { fv_at(sey, i, j, k, c0 + c) = e[c][1]; if (cons) fv_at(fly, i, j, k, c0 + c) = e[c][1] * m_lo[1]; }
-        if (vx && vy) { fv_at(sez, i, j, k, c0 + c) = e[c][2]; if (cons) fv_at(flz, i, j, k, c0 + c) = e[c][2] * m_lo[2]; }
-      }
-    }
-  }
-}
-// (measured and rejected: capping the one-component kernel at 128 VGPRs -- 11 spilled -- so that two workgroups share a CU: 0.82 -> 1.04 ms)
-template <int NC, bool PF = false, bool BC = true> __global__ void __launch_bounds__(64 * TNY) kk_mk_D_m(FV s, FV sl0, FV sl1, FV sl2, FV um, FV vm, FV wm, FV force, FV macrhs, FV SC, FV sex, FV sey, FV sez, FV flx, FV fly, FV flz, GArgs A, Range3 r, int klen, const double *umax, int c0, int ns) {
-  int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
-  mk_D_m_body<NC, false, PF, BC>(s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SC, sex, sey, sez, flx, fly, flz, A, r, klen, umax, c0, ns, bx_, by_, bz_);
-}
-
 
 // ---- stages B + C + D in one march (one component per launch) ------------------------------------------------------------------
 // The three stages above exchange SI (3 fields per component) and SC (6 per component) through HBM: at 256^3 the velocity mkflux moves
@@ -860,9 +405,9 @@ template <int NC, bool PF = false, bool BC = true> __global__ void __launch_boun
 // the march loads plane kk and runs stage B on plane kk, stage C on plane kk-1 (its upper z-face SI is B's output of this iteration) and
 // stage D on plane kk-2 (its upper z-face SC is C's output of this iteration).  A cell's upper x-face value is the next lane's lower-face
 // value (DPP), its upper y-face value the next row's (LDS, written one iteration earlier), its own left states come from the previous
-// lane / row / plane exactly as in the separate stages.  A tile therefore owns lanes 1..62 and rows 1..TNY-2: the transverse couplings
+// lane / row / plane exactly as in the cell-centred scheme above.  A tile therefore owns lanes 1..62 and rows 1..TNY-2: the transverse couplings
 // alternate direction from stage to stage, so the footprint of an output face is one cell either side, not one per stage.
-// Every expression is the one of mk_B_m_body / mk_C_m_body / mk_D_m_body in the same order: bit-identical results
+// Every expression is the one of the face-centred stages (mk_pair, mk_C_one, mk_D_one) in the same order: bit-identical results
 // (tests/test_kernels_gpu.py::test_mkflux, test_godunov_marching_equals_face_centred).  Reads per component: s, three slopes, three MAC
 // components (+ their upper faces), force, mac_rhs; writes: three edge states (+ fluxes of conservative components).
 // Memory access: the launch carries, per field, the address of plane KB = lo_z - 1 of the component (bytes) and the bytes per plane; a thread
@@ -893,8 +438,9 @@ DEVI unsigned fg_off(const FGeo &G, int i, int j) { return 8u * (unsigned)((i - 
 DEVI double ldd(const char *q, unsigned o) { return *(const double *)(q + o); }
 DEVI void std_(char *q, unsigned o, double v) { *(double *)(q + o) = v; }
 struct FCell { double m_lo[3], m_up[3], s0, f, mr, Lb[3], Rb[3]; };      // a cell's loads and its bases (before any boundary rule)
-// mk_bases with the launch constants of FArgs: the bases of stage B (force / mac_rhs terms inside only with use_minion); stages C and D of
-// the separate kernels recompute the same ones -- six f64 divisions per cell and stage -- here they ride along with the cell
+// the one-dimensional predictor bases of a cell (mk_pair split by side, no boundary rule) with the launch constants of FArgs: Lb = left state
+// of the cell's upper D-face, Rb = right state of its lower D-face (force / mac_rhs terms inside only with use_minion); stages C and D of the
+// face-centred kernels recompute the same ones -- six f64 divisions per cell and stage -- here they ride along with the cell
 // A division by a power of two is an exact scaling: x / dx and x * (1 / dx) are the same double for every x (zeros, infinities and subnormal
 // results included: both are the correctly rounded value of the same real number), so where every dx is a power of two -- the unit cube on
 // 2^n cells, every level of a hierarchy over it -- the P2 kernels multiply.  The ten f64 divisions per cell and plane of the fused march were a
@@ -916,11 +462,10 @@ template <bool PW2> DEVI void f_bases(const FArgs &F, FCell &P, const double sl[
     P.Lb[d] = Lb; P.Rb[d] = Rb;
   }
 }
-DEVI double tvq(bool cons, double q, double sp, double s0, double mp, double m0) {     // tv with its quotient (fcons / dxT or fconv / dxT) given
+DEVI double tvq(bool cons, double q, double sp, double s0, double mp, double m0) {     // trans_term on values, its quotient (fcons / dxT or fconv / dxT) given
   if (cons) return q * (sp * mp - s0 * m0);
   return q * (mp + m0) * (sp - s0);
 }
-static bool god_oneb() { static const bool on = !(vdn_env("VDN_GOD_1B") && atoi(vdn_env("VDN_GOD_1B")) == 0); return on; }
 constexpr int FNX = 62, FNY = TNY - 2;      // cells a tile owns per row / rows it owns
 static dim3 fused_grid(const Range3 &r, int &klen) {
   // one 512-thread workgroup per CU at a time: the chunk count is the one that fills the last round of workgroups best
@@ -959,7 +504,7 @@ static bool fused_grid_cols(const Range3 &rf, dim3 &g, int &klen, int &full, int
   return true;
 }
 // The boundary rules in compact form.  bc_pair always leaves L = R = v, and upwind_mac(v, v, .) = v, so on a physical boundary face every
-// stage's output IS v -- the inflow value, zero, the inner state, or the inner state clamped (bc_pair / mk_edge_bc: the same four cases):
+// stage's output IS v -- the inflow value, zero, the inner state, or the inner state clamped (bc_pair / the edge-state rule of mk_D_one: the same four cases):
 //   mode 1: ghost value   2: zero   3: inner state   4: inner state, min(.,0) on a lo face / max(.,0) on a hi face
 // and the "premod" of stages C and D is the same v applied to the base of the cell next to the face.
 DEVI int bc_mode(int phys, bool is_vel, bool normal) {
@@ -1007,7 +552,7 @@ template <bool NAR> DEVI SegGeo seg_geo(int W_) {
 // next row's (LDS, read one iteration later, like SI and SC), the upper z one this thread's output for the next plane.  So the x-term of
 // plane k is formed with stage D of plane k, the y- and z-terms one iteration later, and seven doubles travel in between; a k-chunk runs
 // one plane further (the lower z-face of its successor's first plane).  sedge and flux are not stored.  Same expressions as update_cell.
-// ONEB (round 5): ONE workgroup barrier per plane instead of three.  The three stages exchange their y-direction left states through LDS (lB, lC, lD) and
+// One workgroup barrier per plane (round 5; round 4 had three).  The three stages exchange their y-direction left states through LDS (lB, lC, lD) and
 // each had its own write -> barrier -> read.  What a stage WRITES depends on no LDS value of the same iteration -- stage C's lC needs t[0] (x: DPP) and
 // t[2] (z: registers), stage D's lD the chain of direction y, whose transverse terms are x (DPP) and z (stage C's z-faces, registers) -- so all three
 // writes move in front of one barrier, with every x- and z-direction upwind that needs no LDS value, and everything that reads LDS (this iteration's
@@ -1015,7 +560,7 @@ template <bool NAR> DEVI SegGeo seg_geo(int W_) {
 // passed barrier kk reads buffer kk & 1 and last iteration's lSI / lSC / lE while the fastest wave writes buffer (kk + 1) & 1 and this iteration's.
 // the y-exchange arrays of the march, ONE allocation per kernel shared by the bodies inlined into it (boundary / lean, full-width / narrow)
 template <bool UPD> struct FShared { double lB[2][TNY][64], lSI[2][TNY][64], lC[2][2][TNY][64], lSC[2][2][TNY][64], lD[2][TNY][64], lE[UPD ? 2 : 1][UPD ? TNY : 1][64]; };
-template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, bool ONEB = true> __device__ __forceinline__ void mk_F_m_body(FShared<UPD> &S, const FArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
+template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __forceinline__ void mk_F_m_body(FShared<UPD> &S, const FArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
   double (&lB)[2][TNY][64] = S.lB, (&lSI)[2][TNY][64] = S.lSI, (&lC)[2][2][TNY][64] = S.lC, (&lSC)[2][2][TNY][64] = S.lSC, (&lD)[2][TNY][64] = S.lD;
   double (&lE)[UPD ? 2 : 1][UPD ? TNY : 1][64] = S.lE;
   const SegGeo G = seg_geo<NAR>(segw);
@@ -1106,7 +651,6 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, bool ONEB = t
       if (kc_ != kcur) { ps += F.sp[0]; psl0 += F.sp[1]; psl1 += F.sp[1]; psl2 += F.sp[1]; pum += F.sp[2]; pvm += F.sp[3]; pwm += F.sp[4]; pf += F.sp[5]; pmr += F.sp[6]; kcur = kc_; } }
   F_LOAD
   F_ADVANCE(k0 - 1)
-  if (ONEB) {
   for (int kk = k0 - 2; kk <= k1 + 2 + (UPD ? 1 : 0); kk++) {
     const int buf = kk & 1;
     P2 = P1; P1 = P0;
@@ -1276,159 +820,6 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, bool ONEB = t
     #pragma unroll
     for (int n = 0; n < 6; n++) qp[n] = qc[n];
   }
-  } else
-  for (int kk = k0 - 2; kk <= k1 + 2 + (UPD ? 1 : 0); kk++) {
-    const int buf = kk & 1;
-    P2 = P1; P1 = P0;
-    {
-      #pragma unroll
-      for (int d = 0; d < 3; d++) { P0.m_lo[d] = N.m_lo[d]; P0.m_up[d] = N.m_up[d]; }
-      P0.s0 = N.s0; P0.f = N.f; P0.mr = N.mr;
-      const double sl[3] = { N.sl[0], N.sl[1], N.sl[2] };
-      if (kk < k1 + 2) { F_LOAD  F_ADVANCE(kk + 2) }
-      f_bases<PW2>(F, P0, sl);
-    }
-    // ---------------- stage B, plane kk ----------------
-    double si0[3];
-    {
-      const int k = kk, kc = min(max(k, KB), KT);
-      const int zw = Z_WORD(k, kc);                                   // uniform
-      const double (&Lb)[3] = P0.Lb, (&Rb)[3] = P0.Rb;
-      LS(lB[buf]) = Lb[1];
-      __syncthreads();
-      const double Lx = shfl_prev(Lb[0]), Ly = LM(lB[buf]), Lzc = LzB;
-      LzB = Lb[2];
-      si0[0] = upwind_mac(Lx, Rb[0], P0.m_lo[0], eps);
-      si0[1] = upwind_mac(Ly, Rb[1], P0.m_lo[1], eps);
-      si0[2] = upwind_mac(Lzc, Rb[2], P0.m_lo[2], eps);
-      if (BC && k == kc) {
-        int w = bcw; asm volatile("" : "+v"(w));
-        if (w & 0xF00F) { FACE_BC(si0[0], w, 0, Lx, Rb[0], P0.s0, S_AT(kc, -8L)) FACE_BC(si0[1], w, 12, Ly, Rb[1], P0.s0, S_AT(kc, -F.s_row)) }
-        if ((zw & 15) && ing_ij) { FACE_BC(si0[2], zw, 0, Lzc, Rb[2], P0.s0, P1.s0) }
-      }
-      LS(lSI[buf]) = si0[1];                                   // read by the row below in the next iteration
-    }
-    // ---------------- stage C, plane kk-1 ----------------
-    double qc[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-    if (kk - 1 >= k0 - 1) {
-      const int k = kk - 1, kc = min(max(k, KB), KT);
-      const int zw = Z_WORD(k, kc);
-      double Lb[3] = { P1.Lb[0], P1.Lb[1], P1.Lb[2] }, Rb[3] = { P1.Rb[0], P1.Rb[1], P1.Rb[2] };
-      int wc = 0;
-      if (BC) {
-        wc = bcw; asm volatile("" : "+v"(wc));
-        if (wc & 0x770770) { PREMOD(Lb[0], Rb[0], wc, 4, 8, S_AT(kc, -8L), S_AT(kc, 8L)) PREMOD(Lb[1], Rb[1], wc, 16, 20, S_AT(kc, -F.s_row), S_AT(kc, F.s_row)) }
-        if (zw & 0x770) { PREMOD(Lb[2], Rb[2], zw, 4, 8, S_AT(kc - 1, 0L), S_AT(kc + 1, 0L)) }
-      }
-      const double su[3] = { lane_next(si1[0]), LP(lSI[buf ^ 1]), si0[2] };       // SI on the upper faces
-      double t[3];
-      t[0] = tvq(cons, F.tC[0], su[0], si1[0], P1.m_up[0], P1.m_lo[0]);
-      t[1] = tvq(cons, F.tC[1], su[1], si1[1], P1.m_up[1], P1.m_lo[1]);
-      t[2] = tvq(cons, F.tC[2], su[2], si1[2], P1.m_up[2], P1.m_lo[2]);
-      double VL[3][2], VR[3][2];
-      VL[0][0] = Lb[0] - t[1]; VR[0][0] = Rb[0] - t[1]; VL[0][1] = Lb[0] - t[2]; VR[0][1] = Rb[0] - t[2];
-      VL[1][0] = Lb[1] - t[0]; VR[1][0] = Rb[1] - t[0]; VL[1][1] = Lb[1] - t[2]; VR[1][1] = Rb[1] - t[2];
-      VL[2][0] = Lb[2] - t[0]; VR[2][0] = Rb[2] - t[0]; VL[2][1] = Lb[2] - t[1]; VR[2][1] = Rb[2] - t[1];
-      LS(lC[buf][0]) = VL[1][0]; LS(lC[buf][1]) = VL[1][1];
-      __syncthreads();
-      double Lx[2], Ly[2], Lzc[2];
-      Lx[0] = shfl_prev(VL[0][0]); Lx[1] = shfl_prev(VL[0][1]);
-      Ly[0] = LM(lC[buf][0]); Ly[1] = LM(lC[buf][1]);
-      Lzc[0] = LzC[0]; Lzc[1] = LzC[1];
-      LzC[0] = VL[2][0]; LzC[1] = VL[2][1];
-      qc[0] = upwind_mac(Lx[0], VR[0][0], P1.m_lo[0], eps); qc[1] = upwind_mac(Lx[1], VR[0][1], P1.m_lo[0], eps);
-      qc[2] = upwind_mac(Ly[0], VR[1][0], P1.m_lo[1], eps); qc[3] = upwind_mac(Ly[1], VR[1][1], P1.m_lo[1], eps);
-      qc[4] = upwind_mac(Lzc[0], VR[2][0], P1.m_lo[2], eps); qc[5] = upwind_mac(Lzc[1], VR[2][1], P1.m_lo[2], eps);
-      if (BC && k == kc) {
-        if (wc & 0xF00F) {
-          FACE_BC(qc[0], wc, 0, Lx[0], VR[0][0], P1.s0, S_AT(kc, -8L)) FACE_BC(qc[1], wc, 0, Lx[1], VR[0][1], P1.s0, S_AT(kc, -8L))
-          FACE_BC(qc[2], wc, 12, Ly[0], VR[1][0], P1.s0, S_AT(kc, -F.s_row)) FACE_BC(qc[3], wc, 12, Ly[1], VR[1][1], P1.s0, S_AT(kc, -F.s_row))
-        }
-        if ((zw & 15) && ing_ij) { FACE_BC(qc[4], zw, 0, Lzc[0], VR[2][0], P1.s0, P2.s0) FACE_BC(qc[5], zw, 0, Lzc[1], VR[2][1], P1.s0, P2.s0) }
-      }
-      LS(lSC[buf][0]) = qc[2]; LS(lSC[buf][1]) = qc[3];            // read by the row below in the next iteration
-    }
-    // ---------------- stage D, plane kk-2 ----------------
-    if (kk - 2 >= k0 - 1) {
-      const int k = kk - 2, kc = min(max(k, KB), KT);
-      const int zw = Z_WORD(k, kc);
-      const bool vz = k >= F.lo[2] && k <= F.hi[2];
-      const double (&m_lo)[3] = P2.m_lo, (&m_up)[3] = P2.m_up;
-      const double s0 = P2.s0;
-      const double ft = F.dt2 * P2.f, mt = F.dt2 * s0 * P2.mr;
-      double Lb[3] = { P2.Lb[0], P2.Lb[1], P2.Lb[2] }, Rb[3] = { P2.Rb[0], P2.Rb[1], P2.Rb[2] };
-      int wd = 0;
-      if (BC) {
-        wd = bcw; asm volatile("" : "+v"(wd));
-        if (wd & 0x770770) { PREMOD(Lb[0], Rb[0], wd, 4, 8, S_AT(kc, -8L), S_AT(kc, 8L)) PREMOD(Lb[1], Rb[1], wd, 16, 20, S_AT(kc, -F.s_row), S_AT(kc, F.s_row)) }
-        if (zw & 0x770) { PREMOD(Lb[2], Rb[2], zw, 4, 8, S_AT(kc - 1, 0L), S_AT(kc + 1, 0L)) }
-      }
-      // SC on the upper faces: x-faces from the next lane, y-faces from the next row (written in the previous iteration), z-faces from stage C above
-      const double q1[6] = { lane_next(qp[0]), lane_next(qp[1]), LP(lSC[buf ^ 1][0]), LP(lSC[buf ^ 1][1]), qc[4], qc[5] };
-      const double (&q0)[6] = qp;
-      double VL[3], VR[3];
-      const double a[3] = { F.aD[0] * s0 * (m_up[0] - m_lo[0]), F.aD[1] * s0 * (m_up[1] - m_lo[1]), F.aD[2] * s0 * (m_up[2] - m_lo[2]) };
-      #define CHAIN(Dd, T1, T2, n1, n2)                                                                    \
-        { const double t1 = tvq(cons, F.tD[T1], q1[n1], q0[n1], m_up[T1], m_lo[T1]);                         \
-          const double t2 = tvq(cons, F.tD[T2], q1[n2], q0[n2], m_up[T2], m_lo[T2]);                         \
-          double vl = Lb[Dd], vr = Rb[Dd];                                                                   \
-          vl = vl - t1; vr = vr - t1; vl = vl - t2; vr = vr - t2;                                            \
-          if (cons) { vl = vl + a[T1]; vr = vr + a[T1]; vl = vl + a[T2]; vr = vr + a[T2]; }                  \
-          if (!F.use_minion) { vl = vl + ft; vr = vr + ft; if (cons) { vl = vl - mt; vr = vr - mt; } }       \
-          VL[Dd] = vl; VR[Dd] = vr; }
-      CHAIN(0, 1, 2, 3, 5)
-      CHAIN(1, 0, 2, 1, 4)
-      CHAIN(2, 0, 1, 0, 2)
-      #undef CHAIN
-      LS(lD[buf]) = VL[1];
-      __syncthreads();
-      double L[3];
-      L[0] = shfl_prev(VL[0]); L[1] = LM(lD[buf]); L[2] = LzD; LzD = VL[2];
-      if (k >= k0) {
-        double e[3] = { 0.0, 0.0, 0.0 };
-        if (UPD || own_ij) {
-          e[0] = upwind_mac(L[0], VR[0], m_lo[0], eps); e[1] = upwind_mac(L[1], VR[1], m_lo[1], eps); e[2] = upwind_mac(L[2], VR[2], m_lo[2], eps);
-          if (BC) {
-            if (wd & 0xF00F) { FACE_BC(e[0], wd, 0, L[0], VR[0], s0, S_AT(kc, -8L)) FACE_BC(e[1], wd, 12, L[1], VR[1], s0, S_AT(kc, -F.s_row)) }
-            if (zw & 15) { FACE_BC(e[2], zw, 0, L[2], VR[2], s0, S_AT(kc - 1, 0L)) }
-          }
-        }
-        if (!UPD) {
-          if (own_ij) {
-            if (vy && vz) { std_(qex, 0u, e[0]); if (cons) std_(qfx, 0u, e[0] * m_lo[0]); }
-            if (vx && vz) { std_(qey, 0u, e[1]); if (cons) std_(qfy, 0u, e[1] * m_lo[1]); }
-            if (vx && vy) { std_(qez, 0u, e[2]); if (cons) std_(qfz, 0u, e[2] * m_lo[2]); }
-          }
-          qex += F.sq[0]; qfx += F.sq[0]; qey += F.sq[1]; qfy += F.sq[1]; qez += F.sq[2]; qfz += F.sq[2];
-        } else {
-          // what update_3d differences: fluxes of a conservative component (flux = sedge * umac, mkflux.f90:1969), edge states otherwise
-          const double ex = cons ? e[0] * m_lo[0] : e[0], ey = cons ? e[1] * m_lo[1] : e[1], ez = cons ? e[2] * m_lo[2] : e[2];
-          if (k - 1 >= k0) {                                           // finish plane k-1: its upper y face from the row above, its upper z face = ez
-            const double eyu = LP(lE[buf ^ 1]);
-            const double ty = cons ? DIVDX(eyu - c_e1, 1) : DIVDX(c_vbar * (eyu - c_e1), 1);
-            const double tz = cons ? DIVDX(ez - c_e2, 2) : DIVDX(c_wbar * (ez - c_e2), 2);
-            const double ug = c_tx + ty + tz;
-            const bool vzp = k - 1 >= F.lo[2] && k - 1 <= F.hi[2];
-            if (own_ij && vx && vy && vzp) std_(qn, 0u, c_so - F.dt * ug + F.dt * c_fu);
-            qn += F.sqn;
-          }
-          const double exu = lane_next(ex);                            // the upper x face: the next lane's lower one
-          c_tx = cons ? DIVDX(exu - ex, 0) : DIVDX((0.5 * (m_lo[0] + m_up[0])) * (exu - ex), 0);
-          c_vbar = 0.5 * (m_lo[1] + m_up[1]); c_wbar = 0.5 * (m_lo[2] + m_up[2]);
-          c_e1 = ey; c_e2 = ez; c_so = s0;
-          if (F.fmode == 0) c_fu = P2.f;
-          else {
-            const long po = (long)(kc - KB) * F.sp[5] + o_f;
-            c_fu = ldd(F.pfu[0] + po, 0u) + (F.lapu0 - ldd(F.pfu[1] + po, 0u)) / ldd(F.pfu[2] + po, 0u);
-          }
-          LS(lE[buf]) = ey;                                     // read by the row below in the next iteration
-        }
-      }
-    }
-    si1[0] = si0[0]; si1[1] = si0[1]; si1[2] = si0[2];
-    #pragma unroll
-    for (int n = 0; n < 6; n++) qp[n] = qc[n];
-  }
   #undef F_LOAD
   #undef F_ADVANCE
   #undef S_AT
@@ -1437,7 +828,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, bool ONEB = t
   #undef PREMOD
   #undef Z_WORD
 }
-template <bool BC = true, bool INL = true, bool UPD = false, bool PW2 = false, bool ONEB = true> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_m(FArgs F, Range3 r, int klen, const double *umax) {
+template <bool BC = true, bool INL = true, bool UPD = false, bool PW2 = false> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_m(FArgs F, Range3 r, int klen, const double *umax) {
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
   // a workgroup whose tile and k-chunk stay clear of every face that carries a rule runs the body without the boundary code (same values:
   // none of its cells is flagged); compiled into one kernel the lean path keeps its own register allocation (0.69 against 0.96 ms per launch)
@@ -1453,8 +844,8 @@ template <bool BC = true, bool INL = true, bool UPD = false, bool PW2 = false, b
     }
   }
   __shared__ FShared<UPD> S;
-  if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2, false, ONEB>(S, F, r, klen, umax, bx_, by_, bz_);
-  else mk_F_m_body<false, false, UPD, PW2, false, ONEB>(S, F, r, klen, umax, bx_, by_, bz_);
+  if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2>(S, F, r, klen, umax, bx_, by_, bz_);
+  else mk_F_m_body<false, false, UPD, PW2>(S, F, r, klen, umax, bx_, by_, bz_);
 }
 // The remainder column of a one-box level in narrow segments (round 5).  A row of 256 cells is four 62-cell tiles and 8 cells: the fifth tile column
 // marched 64 lanes for 8 cells (a fifth of all workgroups at 256^3).  With NCOL that column runs in segments of (cells + 2) lanes, 64 / W rows per wave
@@ -1568,8 +959,8 @@ __global__ void kk_velmax(FV u, Range3 r, double *out) {             // velpred.
 // The descriptors are read through the constant address space (scalar loads, never invalidated by the kernel's stores),
 // exactly like kernel arguments.
 // ====================================================================================================
-struct MkD { FV s, sl0, sl1, sl2, um, vm, wm, force, macrhs, SI, SC, sex, sey, sez, flx, fly, flz; GArgs A; Range3 rm, rg, rf; int klg, klf, gs[3], gm[3], gg[3], gf[3]; double *umax; };
-struct VpD { FV s, sl0, sl1, sl2, force, UI, XC, um, vm, wm;                                     GArgs A; Range3 rm, rg, rf; int klg, klf, gs[3], gm[3], gg[3], gf[3]; double *umax; };
+struct MkD { FV s, sl0, sl1, sl2, um, vm, wm, force, macrhs, sex, sey, sez, flx, fly, flz; GArgs A; Range3 rm, rg, rf; int gs[3], gm[3]; double *umax; };
+struct VpD { FV s, sl0, sl1, sl2, force, um, vm, wm;                              GArgs A; Range3 rm, rg, rf; int gs[3], gm[3]; double *umax; };
 DEVI int locate_box(const int *start, int nbox, int bid) {
   int lo = 0, hi = nbox - 1;
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (as_constant(start + mid) <= bid) lo = mid; else hi = mid - 1; }
@@ -1614,19 +1005,6 @@ __global__ void kk_velmax_b(const VpD *descs, const int *start, int nbox) {
     m = fmax(m, fmax(fmax(fabs(fv_get(q.s, i, j, k, 0)), fabs(fv_get(q.s, i, j, k, 1))), fabs(fv_get(q.s, i, j, k, 2))));
   block_atomic_max(q.umax, m);
 }
-template <int NC> __global__ void __launch_bounds__(64 * TNY) kk_mk_B_mb(const MkD *descs, const int *start, int nbox, int c0, int ns) {
-  BATCH_LOCATE(MkD, gg)
-  mk_B_m_body<NC, true, true>(q.s, q.sl0, q.sl1, q.sl2, q.um, q.vm, q.wm, q.force, q.macrhs, q.SI, q.A, q.rg, q.klg, q.umax, c0, ns, BX, BY, BZ);
-}
-template <int NC> __global__ void __launch_bounds__(64 * TNY) kk_mk_C_mb(const MkD *descs, const int *start, int nbox, int c0, int ns) {
-  BATCH_LOCATE(MkD, gg)
-  mk_C_m_body<NC, true, true>(q.s, q.sl0, q.sl1, q.sl2, q.um, q.vm, q.wm, q.force, q.macrhs, q.SI, q.SC, q.A, q.rg, q.klg, q.umax, c0, ns, BX, BY, BZ);
-}
-template <int NC> __global__ void __launch_bounds__(64 * TNY) kk_mk_D_mb(const MkD *descs, const int *start, int nbox, int c0, int ns) {
-  BATCH_LOCATE(MkD, gf)
-  mk_D_m_body<NC, true, false, true>(q.s, q.sl0, q.sl1, q.sl2, q.um, q.vm, q.wm, q.force, q.macrhs, q.SC, q.sex, q.sey, q.sez, q.flx, q.fly, q.flz, q.A, q.rf, q.klf, q.umax, c0, ns, BX, BY, BZ);
-}
-// host side of a batch: grids of the four launch shapes per box, their prefix sums, and the upload
 // the fused march for every box of a level in one launch (a descriptor per box and component; see kk_batched for the scheme)
 struct FBatchD { FArgs F; Range3 r; int klen; const double *umax; int g[3], sw; };      // sw: lanes of a row segment (NAR launches; seg_geo)
 template <bool INL, bool PW2 = false, bool NAR = false> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_mb(const FBatchD *descs, const int *start, int nbox) {
@@ -1665,17 +1043,17 @@ static void fused_grid_small(const Range3 &r, int &klen, int g[3], int &sw) {
   }
 }
 
+// host side of a batch: grids of the slope and the reduction launch per box, their prefix sums, and the upload
 template <class D> struct GodBatch {
-  std::vector<D> d; const D *dev = nullptr; const int *st[4] = { nullptr, nullptr, nullptr, nullptr }; int tot[4] = { 0, 0, 0, 0 };
+  std::vector<D> d; const D *dev = nullptr; const int *st[2] = { nullptr, nullptr }; int tot[2] = { 0, 0 };
   void finish() {
     const int nb = (int)d.size();
-    std::vector<int> start(4 * nb);
+    std::vector<int> start(2 * nb);
     for (int b = 0; b < nb; b++) {
       D &q = d[b];
       const dim3 gs = grid_for(q.rg), gm = reduce_grid(q.rm);
-      const dim3 gg = march_grid(q.rg, q.klg), gf = march_grid(q.rf, q.klf);
-      const dim3 *g[4] = { &gs, &gm, &gg, &gf }; int *o[4] = { q.gs, q.gm, q.gg, q.gf };
-      for (int t = 0; t < 4; t++) { o[t][0] = g[t]->x; o[t][1] = g[t]->y; o[t][2] = g[t]->z; start[t * nb + b] = tot[t]; tot[t] += (int)(g[t]->x * g[t]->y * g[t]->z); }
+      const dim3 *g[2] = { &gs, &gm }; int *o[2] = { q.gs, q.gm };
+      for (int t = 0; t < 2; t++) { o[t][0] = g[t]->x; o[t][1] = g[t]->y; o[t][2] = g[t]->z; start[t * nb + b] = tot[t]; tot[t] += (int)(g[t]->x * g[t]->y * g[t]->z); }
       // the slope launch: the plane flattened over the workgroup when that takes fewer workgroups (kk_slopes_b: gs[1] = 0)
       static const bool flat_on = !(vdn_env("VDN_BATCH_FLAT") && atoi(vdn_env("VDN_BATCH_FLAT")) == 0);
       const int pnx = q.rg.hi[0] - q.rg.lo[0] + 1, pny = q.rg.hi[1] - q.rg.lo[1] + 1;
@@ -1685,9 +1063,9 @@ template <class D> struct GodBatch {
         q.gs[0] = gfl; q.gs[1] = 0;
       }
     }
-    D *dd = (D *)desc_scratch(sizeof(D) * nb); int *ds = (int *)desc_scratch(sizeof(int) * 4 * nb);
-    upload_staged(dd, d.data(), sizeof(D) * nb); upload_staged(ds, start.data(), sizeof(int) * 4 * nb);
-    dev = dd; for (int t = 0; t < 4; t++) st[t] = ds + t * nb;
+    D *dd = (D *)desc_scratch(sizeof(D) * nb); int *ds = (int *)desc_scratch(sizeof(int) * 2 * nb);
+    upload_staged(dd, d.data(), sizeof(D) * nb); upload_staged(ds, start.data(), sizeof(int) * 2 * nb);
+    dev = dd; for (int t = 0; t < 2; t++) st[t] = ds + t * nb;
   }
 };
 
@@ -1750,13 +1128,16 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
   REQUIRE(ncomp <= 3, "mkflux: at most 3 components per window (got %d)", ncomp);
   REQUIRE(s->ng >= 3 && umac[0]->ng >= 1 && force->ng >= 1 && mac_rhs->ng >= 1, "mkflux: ghost widths");
   hipStream_t st = ctx().stream;
-  if (use_batched(s) && !plain_godunov()) {            // every stage once for all boxes of the level
+  if (use_batched(s) && !plain_godunov()) {            // every stage once for all boxes of the level: the slopes, then stages B + C + D in one march (mk_F_m_body)
     size_t mark = arena_mark();
     const int nb = s->nfabs();
     GodBatch<MkD> B; B.d.resize(nb);
     double *umax = (double *)arena_alloc(sizeof(double) * nb);
     HIPCHK(hipMemsetAsync(umax, 0, sizeof(double) * nb, st));
-    for (int ib = 0; ib < nb; ib++) {
+    std::vector<FBatchD> fd((size_t)nb * ncomp);
+    std::vector<int> fstart((size_t)nb * ncomp);
+    bool ok = true, inflow = false;
+    for (int ib = 0; ib < nb && ok; ib++) {
       MkD &q = B.d[ib];
       fill_gargs(q.A, s, ib, bct, bccomp, ncomp, dx, dt);
       q.A.is_vel = is_vel ? 1 : 0;
@@ -1764,72 +1145,50 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
       BoxP bp = make_boxp(s, ib, bct);
       FV w = work_fv(nullptr, bp, 0);
       const size_t fld = (size_t)w.sc * sizeof(double);
-      q.sl0 = q.sl1 = q.sl2 = q.SI = q.SC = w;
+      q.sl0 = q.sl1 = q.sl2 = w;
       q.sl0.p = (double *)arena_alloc(fld * ncomp); q.sl1.p = (double *)arena_alloc(fld * ncomp); q.sl2.p = (double *)arena_alloc(fld * ncomp);
-      q.SI.p = (double *)arena_alloc(fld * 3 * ncomp); q.SC.p = (double *)arena_alloc(fld * 6 * ncomp);
       for (int d = 0; d < 3; d++) { q.rg.lo[d] = q.A.lo[d] - 1; q.rg.hi[d] = q.A.hi[d] + 1; q.rf.lo[d] = q.A.lo[d]; q.rf.hi[d] = q.A.hi[d] + 1; }
       q.rm = q.rf;
       q.s = s->fabs[ib]; q.um = umac[0]->fabs[ib]; q.vm = umac[1]->fabs[ib]; q.wm = umac[2]->fabs[ib]; q.force = force->fabs[ib]; q.macrhs = mac_rhs->fabs[ib];
       q.sex = sedge[0]->fabs[ib]; q.sey = sedge[1]->fabs[ib]; q.sez = sedge[2]->fabs[ib]; q.flx = flux[0]->fabs[ib]; q.fly = flux[1]->fabs[ib]; q.flz = flux[2]->fabs[ib];
       q.umax = umax + ib;
-    }
-    B.finish();
-    const dim3 blk(64, TNY, 1);
-    hipLaunchKernelGGL(kk_macmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);
-    hipLaunchKernelGGL(kk_slopes_b<MkD>, dim3(B.tot[0]), dim3(64, 4, 1), 0, st, B.dev, B.st[0], nb, 7);
-    static const bool fused_env = !(vdn_env("VDN_GOD_FUSED") && atoi(vdn_env("VDN_GOD_FUSED")) == 0);
-    if (fused_env) {               // stages B + C + D in one march per box and component (mk_F_m_body)
-      std::vector<FBatchD> fd((size_t)nb * ncomp);
-      std::vector<int> fstart((size_t)nb * ncomp);
-      bool ok = true, inflow = false;
-      int tot = 0;
-      for (int ib = 0; ib < nb && ok; ib++) {
-        const MkD &q = B.d[ib];
-        const FV sl[3] = { q.sl0, q.sl1, q.sl2 };
-        for (int d = 0; d < 3; d++) inflow = inflow || q.A.phys[d][0] == VDN_INLET || q.A.phys[d][1] == VDN_INLET;
-        for (int c0 = 0; c0 < ncomp && ok; c0++) {
-          FBatchD &f = fd[(size_t)c0 * nb + ib];
-          ok = fused_args(f.F, q.A, c0, q.s, sl, q.um, q.vm, q.wm, q.force, q.macrhs, q.sex, q.sey, q.sez, q.flx, q.fly, q.flz);
-          f.r = q.rf; f.umax = q.umax;
-          fused_grid_small(f.r, f.klen, f.g, f.sw);
-        }
-      }
-      if (ok) {
-        // two launches: the boxes in full-width tiles, the narrow ones in row segments (seg_geo)
-        std::stable_partition(fd.begin(), fd.end(), [](const FBatchD &f) { return f.sw == 0; });
-        const size_t nwide = std::count_if(fd.begin(), fd.end(), [](const FBatchD &f) { return f.sw == 0; });
-        int totn = 0;
-        for (size_t t = 0; t < fd.size(); t++) { int &T = t < nwide ? tot : totn; fstart[t] = T; T += fd[t].g[0] * fd[t].g[1] * fd[t].g[2]; }
-        FBatchD *dd = (FBatchD *)desc_scratch(sizeof(FBatchD) * fd.size()); int *ds = (int *)desc_scratch(sizeof(int) * fstart.size());
-        upload_staged(dd, fd.data(), sizeof(FBatchD) * fd.size()); upload_staged(ds, fstart.data(), sizeof(int) * fstart.size());
-        const bool p2 = fd[0].F.p2 != 0;
-        if (nwide) {
-          if (inflow) hipLaunchKernelGGL(kk_mk_F_mb<true>, dim3(tot), blk, 0, st, dd, ds, (int)nwide);
-          else if (p2) hipLaunchKernelGGL((kk_mk_F_mb<false, true>), dim3(tot), blk, 0, st, dd, ds, (int)nwide);
-          else hipLaunchKernelGGL(kk_mk_F_mb<false>, dim3(tot), blk, 0, st, dd, ds, (int)nwide);
-        }
-        if (nwide < fd.size()) {
-          const int nn = (int)(fd.size() - nwide);
-          if (inflow) hipLaunchKernelGGL((kk_mk_F_mb<true, false, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
-          else if (p2) hipLaunchKernelGGL((kk_mk_F_mb<false, true, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
-          else hipLaunchKernelGGL((kk_mk_F_mb<false, false, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
-        }
-        arena_release(mark);
-        return false;
+      const FV sl[3] = { q.sl0, q.sl1, q.sl2 };
+      for (int d = 0; d < 3; d++) inflow = inflow || q.A.phys[d][0] == VDN_INLET || q.A.phys[d][1] == VDN_INLET;
+      for (int c0 = 0; c0 < ncomp && ok; c0++) {
+        FBatchD &f = fd[(size_t)c0 * nb + ib];
+        ok = fused_args(f.F, q.A, c0, q.s, sl, q.um, q.vm, q.wm, q.force, q.macrhs, q.sex, q.sey, q.sez, q.flx, q.fly, q.flz);
+        f.r = q.rf; f.umax = q.umax;
+        fused_grid_small(f.r, f.klen, f.g, f.sw);
       }
     }
-    const int split = ncomp >= 2 ? 4 : 0;
-    #define MKB_STAGE(K, t, bit)                                                                                               \
-      if ((split >> bit) & 1) { for (int c0 = 0; c0 < ncomp; c0++) hipLaunchKernelGGL(K<1>, dim3(B.tot[t]), blk, 0, st, B.dev, B.st[t], nb, c0, ncomp); } \
-      else if (ncomp == 3) hipLaunchKernelGGL(K<3>, dim3(B.tot[t]), blk, 0, st, B.dev, B.st[t], nb, 0, ncomp);                  \
-      else if (ncomp == 2) hipLaunchKernelGGL(K<2>, dim3(B.tot[t]), blk, 0, st, B.dev, B.st[t], nb, 0, ncomp);                  \
-      else hipLaunchKernelGGL(K<1>, dim3(B.tot[t]), blk, 0, st, B.dev, B.st[t], nb, 0, ncomp);
-    MKB_STAGE(kk_mk_B_mb, 2, 0)
-    MKB_STAGE(kk_mk_C_mb, 2, 1)
-    MKB_STAGE(kk_mk_D_mb, 3, 2)
-    #undef MKB_STAGE
-    arena_release(mark);
-    return false;
+    if (ok) {
+      B.finish();
+      const dim3 blk(64, TNY, 1);
+      hipLaunchKernelGGL(kk_macmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);
+      hipLaunchKernelGGL(kk_slopes_b<MkD>, dim3(B.tot[0]), dim3(64, 4, 1), 0, st, B.dev, B.st[0], nb, 7);
+      // two launches: the boxes in full-width tiles, the narrow ones in row segments (seg_geo)
+      std::stable_partition(fd.begin(), fd.end(), [](const FBatchD &f) { return f.sw == 0; });
+      const size_t nwide = std::count_if(fd.begin(), fd.end(), [](const FBatchD &f) { return f.sw == 0; });
+      int tot = 0, totn = 0;
+      for (size_t t = 0; t < fd.size(); t++) { int &T = t < nwide ? tot : totn; fstart[t] = T; T += fd[t].g[0] * fd[t].g[1] * fd[t].g[2]; }
+      FBatchD *dd = (FBatchD *)desc_scratch(sizeof(FBatchD) * fd.size()); int *ds = (int *)desc_scratch(sizeof(int) * fstart.size());
+      upload_staged(dd, fd.data(), sizeof(FBatchD) * fd.size()); upload_staged(ds, fstart.data(), sizeof(int) * fstart.size());
+      const bool p2 = fd[0].F.p2 != 0;
+      if (nwide) {
+        if (inflow) hipLaunchKernelGGL(kk_mk_F_mb<true>, dim3(tot), blk, 0, st, dd, ds, (int)nwide);
+        else if (p2) hipLaunchKernelGGL((kk_mk_F_mb<false, true>), dim3(tot), blk, 0, st, dd, ds, (int)nwide);
+        else hipLaunchKernelGGL(kk_mk_F_mb<false>, dim3(tot), blk, 0, st, dd, ds, (int)nwide);
+      }
+      if (nwide < fd.size()) {
+        const int nn = (int)(fd.size() - nwide);
+        if (inflow) hipLaunchKernelGGL((kk_mk_F_mb<true, false, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
+        else if (p2) hipLaunchKernelGGL((kk_mk_F_mb<false, true, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
+        else hipLaunchKernelGGL((kk_mk_F_mb<false, false, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
+      }
+      arena_release(mark);
+      return false;
+    }
+    arena_release(mark);                               // a box's layouts refused: the level runs box by box
   }
   for (int ib = 0; ib < s->nfabs(); ib++) {
     size_t mark = arena_mark();
@@ -1839,11 +1198,9 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
     BoxP bp = make_boxp(s, ib, bct);
     FV w = work_fv(nullptr, bp, 0);
     const size_t fld = (size_t)w.sc * sizeof(double);
-    FV sl[3], SI = w, SC = w;
+    FV sl[3];
     const bool cached = is_vel && ncomp == 3 && (int)ctx().slope_src.size() == s->nfabs() && ctx().slope_src[ib] == s->fabs[ib].p;
     for (int d = 0; d < 3; d++) { sl[d] = w; sl[d].p = cached ? ctx().slope_cache[d][ib] : (double *)arena_alloc(fld * ncomp); }
-    SI.p = (double *)arena_alloc(fld * 3 * ncomp);
-    SC.p = (double *)arena_alloc(fld * 6 * ncomp);
     Range3 rg, rf;
     for (int d = 0; d < 3; d++) { rg.lo[d] = A.lo[d] - 1; rg.hi[d] = A.hi[d] + 1; rf.lo[d] = A.lo[d]; rf.hi[d] = A.hi[d] + 1; }
     const FV &um = umac[0]->fabs[ib], &vm = umac[1]->fabs[ib], &wm = umac[2]->fabs[ib];
@@ -1855,93 +1212,53 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
       if (mm_keep) ctx().macmax_src[ib] = um.p;
     }
     if (!cached) launch_slopes(s->fabs[ib], sl, A, rg, ncomp, nullptr, st);
-    if (plain_godunov()) {
+    FArgs FA[3];
+    bool fused = !plain_godunov();
+    for (int c0 = 0; c0 < ncomp && fused; c0++)
+      fused = fused_args(FA[c0], A, c0, s->fabs[ib], sl, um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], sedge[0]->fabs[ib], sedge[1]->fabs[ib], sedge[2]->fabs[ib],
+                         flux[0]->fabs[ib], flux[1]->fabs[ib], flux[2]->fabs[ib]);
+    if (fused) {                   // stages B + C + D in one march per component, boundary rules inside (see mk_F_m_body)
+      static const bool upd_env = !(vdn_env("VDN_GOD_UPDATE") && atoi(vdn_env("VDN_GOD_UPDATE")) == 0);
+      bool do_upd = upd && upd_env;                  // (every box of a box-by-box level: the conditions are geometric and the same for all of them -- checked below)
+      for (int c0 = 0; c0 < ncomp && do_upd; c0++) do_upd = fused_update_args(FA[c0], A, c0, upd->snew->fabs[ib], force->fabs[ib], *upd, ib);
+      int klF;
+      const dim3 gF = fused_grid(rf, klF), blk(64, TNY, 1);
+      for (int c0 = 0; c0 < ncomp; c0++) {
+        bool inflow = false;
+        for (int d = 0; d < 3; d++) inflow = inflow || A.phys[d][0] == VDN_INLET || A.phys[d][1] == VDN_INLET;
+        bool any = false;
+        for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) any = any || bc_mode_host(A.phys[d][sd]);
+        if (do_upd) {
+          const bool p2 = FA[c0].p2 != 0;                              // (the inflow variants keep the division: fewer instantiations)
+          if (!any) { if (p2) hipLaunchKernelGGL((kk_mk_F_m<false, false, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); else hipLaunchKernelGGL((kk_mk_F_m<false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); }
+          else if (inflow) hipLaunchKernelGGL((kk_mk_F_m<true, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+          else if (p2) {
+            // full 62-cell tiles, then the remainder column in narrow segments (kk_mk_F_mc) where that saves workgroups
+            dim3 gM; int klM, full, segw;
+            if (fused_grid_cols(rf, gM, klM, full, segw)) {
+              hipLaunchKernelGGL((kk_mk_F_mc<true, false, true, true>), gM, blk, 0, st, FA[c0], rf, klM, umax, full, segw);
+            } else hipLaunchKernelGGL((kk_mk_F_m<true, false, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+          }
+          else hipLaunchKernelGGL((kk_mk_F_m<true, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+          continue;
+        }
+        const bool p2 = FA[c0].p2 != 0;
+        if (!any) { if (p2) hipLaunchKernelGGL((kk_mk_F_m<false, false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); else hipLaunchKernelGGL((kk_mk_F_m<false, false>), gF, blk, 0, st, FA[c0], rf, klF, umax); }      // no physical face on this box
+        else if (inflow) hipLaunchKernelGGL((kk_mk_F_m<true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+        else if (p2) hipLaunchKernelGGL((kk_mk_F_m<true, false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+        else hipLaunchKernelGGL((kk_mk_F_m<true, false>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+      }
+      REQUIRE(ib == 0 || updated == do_upd, "mkflux: the update would ride along on some boxes of the level only");
+      updated = do_upd;
+    } else {                       // the face-centred stages: VDN_GODUNOV_PLAIN, or field layouts the fused march refuses
+      REQUIRE(!updated, "mkflux: the update rode along on an earlier box of the level but cannot on box %d", ib);      // (every box or none)
+      FV SI = w, SC = w;
+      SI.p = (double *)arena_alloc(fld * 3 * ncomp);
+      SC.p = (double *)arena_alloc(fld * 6 * ncomp);
       hipLaunchKernelGGL(kk_mk_B, grid_for(rg), dim3(64, 4, 1), 0, st, s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SI, A, rg, umax);
       hipLaunchKernelGGL(kk_mk_C, grid_for(rg), dim3(64, 4, 1), 0, st, s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SI, SC, A, rg, umax);
       hipLaunchKernelGGL(kk_mk_D, grid_for(rf), dim3(64, 4, 1), 0, st, s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SC,
                          sedge[0]->fabs[ib], sedge[1]->fabs[ib], sedge[2]->fabs[ib], flux[0]->fabs[ib], flux[1]->fabs[ib], flux[2]->fabs[ib], A, rf, umax);
-    } else {
-      int klg, klf;
-      const dim3 gg = march_grid(rg, klg), gf = march_grid(rf, klf), blk(64, TNY, 1);
-      // components per launch: the 3-component stage D needs more than 256 VGPRs, so it runs one component at a time
-      #define MK_ARGS_B(c0) s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SI, A, rg, klg, umax, c0, ncomp
-      #define MK_ARGS_C(c0) s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SI, SC, A, rg, klg, umax, c0, ncomp
-      #define MK_ARGS_D(c0) s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SC, \
-                            sedge[0]->fabs[ib], sedge[1]->fabs[ib], sedge[2]->fabs[ib], flux[0]->fabs[ib], flux[1]->fabs[ib], flux[2]->fabs[ib], A, rf, klf, umax, c0, ncomp
-      // measured at 256^3: D fused <3> 3.18 ms (61 spilled VGPRs) vs 3 x <1> 2.3 ms; D <2> 1.66 ms vs 2 x <1> 1.55 ms; B and C are faster fused
-      const int split = ncomp >= 2 ? 4 : 0;          // bit 0: B, 1: C, 2: D per component
-      #define MK_STAGE(K, BCF, ARGS, g, bit)                                                                               \
-        if ((split >> bit) & 1) { for (int c0 = 0; c0 < ncomp; c0++) hipLaunchKernelGGL((K<1, BCF>), g, blk, 0, st, ARGS(c0)); } \
-        else if (ncomp == 3) hipLaunchKernelGGL((K<3, BCF>), g, blk, 0, st, ARGS(0));                                        \
-        else if (ncomp == 2) hipLaunchKernelGGL((K<2, BCF>), g, blk, 0, st, ARGS(0));                                        \
-        else hipLaunchKernelGGL((K<1, BCF>), g, blk, 0, st, ARGS(0));
-      #define MK_STAGE_D(BCF)                                                                                              \
-        if ((split >> 2) & 1) { for (int c0 = 0; c0 < ncomp; c0++) hipLaunchKernelGGL((kk_mk_D_m<1, false, BCF>), gf, blk, 0, st, MK_ARGS_D(c0)); } \
-        else if (ncomp == 3) hipLaunchKernelGGL((kk_mk_D_m<3, false, BCF>), gf, blk, 0, st, MK_ARGS_D(0));                     \
-        else if (ncomp == 2) hipLaunchKernelGGL((kk_mk_D_m<2, false, BCF>), gf, blk, 0, st, MK_ARGS_D(0));                     \
-        else hipLaunchKernelGGL((kk_mk_D_m<1, false, BCF>), gf, blk, 0, st, MK_ARGS_D(0));
-      static const bool fused_env = !(vdn_env("VDN_GOD_FUSED") && atoi(vdn_env("VDN_GOD_FUSED")) == 0);
-      FArgs FA[3];
-      bool fused = fused_env;
-      for (int c0 = 0; c0 < ncomp && fused; c0++)
-        fused = fused_args(FA[c0], A, c0, s->fabs[ib], sl, um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], sedge[0]->fabs[ib], sedge[1]->fabs[ib], sedge[2]->fabs[ib],
-                           flux[0]->fabs[ib], flux[1]->fabs[ib], flux[2]->fabs[ib]);
-      static const bool upd_env = !(vdn_env("VDN_GOD_UPDATE") && atoi(vdn_env("VDN_GOD_UPDATE")) == 0);
-      bool do_upd = fused && upd && upd_env;        // (every box of a box-by-box level: the conditions are geometric and the same for all of them -- checked below)
-      for (int c0 = 0; c0 < ncomp && do_upd; c0++) do_upd = fused_update_args(FA[c0], A, c0, upd->snew->fabs[ib], force->fabs[ib], *upd, ib);
-      if (fused) {                 // stages B + C + D in one march per component, boundary rules inside (see mk_F_m_body)
-        int klF;
-        const dim3 gF = fused_grid(rf, klF);
-        for (int c0 = 0; c0 < ncomp; c0++) {
-          bool inflow = false;
-          for (int d = 0; d < 3; d++) inflow = inflow || A.phys[d][0] == VDN_INLET || A.phys[d][1] == VDN_INLET;
-          bool any = false;
-          for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) any = any || bc_mode_host(A.phys[d][sd]);
-          if (do_upd) {
-            const bool p2 = FA[c0].p2 != 0;                              // (the inflow variants keep the division: fewer instantiations)
-            if (!any) { if (p2) hipLaunchKernelGGL((kk_mk_F_m<false, false, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); else hipLaunchKernelGGL((kk_mk_F_m<false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); }
-            else if (inflow) hipLaunchKernelGGL((kk_mk_F_m<true, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-            else if (p2 && !god_oneb()) hipLaunchKernelGGL((kk_mk_F_m<true, false, true, true, false>), gF, blk, 0, st, FA[c0], rf, klF, umax);     // the three-barrier loop, kept for the variants test
-            else if (p2) {
-              // full 62-cell tiles, then the remainder column in narrow segments (kk_mk_F_mn) where that saves workgroups
-              dim3 gM; int klM, full, segw;
-              if (fused_grid_cols(rf, gM, klM, full, segw)) {
-                hipLaunchKernelGGL((kk_mk_F_mc<true, false, true, true>), gM, blk, 0, st, FA[c0], rf, klM, umax, full, segw);
-              } else hipLaunchKernelGGL((kk_mk_F_m<true, false, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-            }
-            else hipLaunchKernelGGL((kk_mk_F_m<true, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-            continue;
-          }
-          const bool p2 = FA[c0].p2 != 0;
-          if (!any) { if (p2) hipLaunchKernelGGL((kk_mk_F_m<false, false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); else hipLaunchKernelGGL((kk_mk_F_m<false, false>), gF, blk, 0, st, FA[c0], rf, klF, umax); }      // no physical face on this box
-          else if (inflow) hipLaunchKernelGGL((kk_mk_F_m<true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-          else if (p2) hipLaunchKernelGGL((kk_mk_F_m<true, false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-          else hipLaunchKernelGGL((kk_mk_F_m<true, false>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-        }
-        REQUIRE(ib == 0 || updated == do_upd, "mkflux: the update would ride along on some boxes of the level only");
-        updated = do_upd;
-      } else if (slab_bc()) {      // interior marches, then the face-centred code on the boundary slabs (see kk_slabs)
-        REQUIRE(!updated, "mkflux: the update rode along on an earlier box of the level but cannot on box %d", ib);      // (every box or none)
-        const MkPlain P{ s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SI, SC,
-                         sedge[0]->fabs[ib], sedge[1]->fabs[ib], sedge[2]->fabs[ib], flux[0]->fabs[ib], flux[1]->fabs[ib], flux[2]->fabs[ib], A, umax };
-        const Slabs Sg = boundary_slabs(A, rg), Sf = boundary_slabs(A, rf);
-        MK_STAGE(kk_mk_B_m, false, MK_ARGS_B, gg, 0)
-        launch_slabs(Sg, MkBFix{ P }, st);
-        MK_STAGE(kk_mk_C_m, false, MK_ARGS_C, gg, 1)
-        launch_slabs(Sg, MkCFix{ P }, st);
-        MK_STAGE_D(false)
-        launch_slabs(Sf, MkDFix{ P }, st);
-      } else {
-        REQUIRE(!updated, "mkflux: the update rode along on an earlier box of the level but cannot on box %d", ib);
-        MK_STAGE(kk_mk_B_m, true, MK_ARGS_B, gg, 0)
-        MK_STAGE(kk_mk_C_m, true, MK_ARGS_C, gg, 1)
-        MK_STAGE_D(true)
-      }
-      #undef MK_STAGE_D
-      #undef MK_STAGE
-      #undef MK_ARGS_B
-      #undef MK_ARGS_C
-      #undef MK_ARGS_D
     }
     arena_release(mark);
   }
@@ -1957,7 +1274,6 @@ bool k_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, 
               const vdn_multifab *force, const vdn_multifab *mac_rhs, const double *dx, double dt,
               const vdn_bc_tower *bct, bool is_vel, const int *is_cons, const MkUpdate *upd) {
   Prof prof_("mkflux");
-  god_xcd_init();
   const int ncomp = s->nc, dm = ctx().prm.dm;
   const int bccomp = is_vel ? 0 : bct->dm;            // mkflux.f90:62-66
   if (ncomp <= 3) return mkflux_window(s, sedge, flux, umac, force, mac_rhs, dx, dt, bct, is_vel, bccomp, is_cons, upd);
@@ -2029,18 +1345,16 @@ template <int D> DEVI void vp_B_one(const GArgs &A, const FV &u, const FV &slp, 
     fv_at(UI, i, j, k, D * 3 + c) = out;
   }
 }
-struct VpPlain { FV u, sl0, sl1, sl2, force, UI, XC, um, vm, wm; GArgs A; const double *umax; };
-DEVI void vp_B_cell(const FV &u, const FV &sl0, const FV &sl1, const FV &sl2, const FV &force, const FV &UI, const GArgs &A, int i, int j, int k, double eps, int dmask = 7) {
-  if (dmask & 1) vp_B_one<0>(A, u, sl0, force, UI, i, j, k, eps);
-  if (dmask & 2) vp_B_one<1>(A, u, sl1, force, UI, i, j, k, eps);
-  if (dmask & 4) vp_B_one<2>(A, u, sl2, force, UI, i, j, k, eps);
+DEVI void vp_B_cell(const FV &u, const FV &sl0, const FV &sl1, const FV &sl2, const FV &force, const FV &UI, const GArgs &A, int i, int j, int k, double eps) {
+  vp_B_one<0>(A, u, sl0, force, UI, i, j, k, eps);
+  vp_B_one<1>(A, u, sl1, force, UI, i, j, k, eps);
+  vp_B_one<2>(A, u, sl2, force, UI, i, j, k, eps);
 }
 __global__ void __launch_bounds__(256) kk_vp_B(FV u, FV sl0, FV sl1, FV sl2, FV force, FV UI, GArgs A, Range3 r, const double *umax) {
   THREAD_IJK(r)
   if (!in_range) return;
   vp_B_cell(u, sl0, sl1, sl2, force, UI, A, i, j, k, eps_from(umax));
 }
-struct VpBFix { VpPlain P; __device__ void operator()(int i, int j, int k, int dmask) const { vp_B_cell(P.u, P.sl0, P.sl1, P.sl2, P.force, P.UI, P.A, i, j, k, eps_from(P.umax), dmask); } };
 
 // stage C: component C on D-faces corrected by the third direction O = 3-C-D
 // (uimhyz = (C=0,D=1) velpred.f90:2466-2503, wimhxy = (C=2,D=0) 2189-2229, ...)
@@ -2066,20 +1380,19 @@ template <int C, int D> DEVI void vp_C_one(const GArgs &A, const FV &u, const FV
   const double av = 0.5 * (L + R);
   fv_at(XC, i, j, k, xc_idx(C, D)) = (fabs(un) < eps) ? av : v;
 }
-DEVI void vp_C_cell(const FV &u, const FV &sl0, const FV &sl1, const FV &sl2, const FV &force, const FV &UI, const FV &XC, const GArgs &A, int i, int j, int k, double eps, int dmask = 7) {
-  if (dmask & 2) vp_C_one<0, 1>(A, u, sl1, force, UI, XC, i, j, k, eps);
-  if (dmask & 4) vp_C_one<0, 2>(A, u, sl2, force, UI, XC, i, j, k, eps);
-  if (dmask & 1) vp_C_one<1, 0>(A, u, sl0, force, UI, XC, i, j, k, eps);
-  if (dmask & 4) vp_C_one<1, 2>(A, u, sl2, force, UI, XC, i, j, k, eps);
-  if (dmask & 1) vp_C_one<2, 0>(A, u, sl0, force, UI, XC, i, j, k, eps);
-  if (dmask & 2) vp_C_one<2, 1>(A, u, sl1, force, UI, XC, i, j, k, eps);
+DEVI void vp_C_cell(const FV &u, const FV &sl0, const FV &sl1, const FV &sl2, const FV &force, const FV &UI, const FV &XC, const GArgs &A, int i, int j, int k, double eps) {
+  vp_C_one<0, 1>(A, u, sl1, force, UI, XC, i, j, k, eps);
+  vp_C_one<0, 2>(A, u, sl2, force, UI, XC, i, j, k, eps);
+  vp_C_one<1, 0>(A, u, sl0, force, UI, XC, i, j, k, eps);
+  vp_C_one<1, 2>(A, u, sl2, force, UI, XC, i, j, k, eps);
+  vp_C_one<2, 0>(A, u, sl0, force, UI, XC, i, j, k, eps);
+  vp_C_one<2, 1>(A, u, sl1, force, UI, XC, i, j, k, eps);
 }
 __global__ void __launch_bounds__(256) kk_vp_C(FV u, FV sl0, FV sl1, FV sl2, FV force, FV UI, FV XC, GArgs A, Range3 r, const double *umax) {
   THREAD_IJK(r)
   if (!in_range) return;
   vp_C_cell(u, sl0, sl1, sl2, force, UI, XC, A, i, j, k, eps_from(umax));
 }
-struct VpCFix { VpPlain P; __device__ void operator()(int i, int j, int k, int dmask) const { vp_C_cell(P.u, P.sl0, P.sl1, P.sl2, P.force, P.UI, P.XC, P.A, i, j, k, eps_from(P.umax), dmask); } };
 
 // stage D: the MAC velocity on valid D-faces (velpred.f90:2616-2660, 2666-2710, 2372-2416)
 template <int D> DEVI void vp_D_one(const GArgs &A, const FV &u, const FV &slp, const FV &force, const FV &UI, const FV &XC, const FV &umac,
@@ -2116,289 +1429,31 @@ template <int D> DEVI void vp_D_one(const GArgs &A, const FV &u, const FV &slp, 
   fv_at(umac, i, j, k) = v;
 }
 DEVI void vp_D_cell(const FV &u, const FV &sl0, const FV &sl1, const FV &sl2, const FV &force, const FV &UI, const FV &XC, const FV &um, const FV &vm, const FV &wm,
-                    const GArgs &A, int i, int j, int k, double eps, int dmask = 7) {
-  if (dmask & 1) vp_D_one<0>(A, u, sl0, force, UI, XC, um, i, j, k, eps);
-  if (dmask & 2) vp_D_one<1>(A, u, sl1, force, UI, XC, vm, i, j, k, eps);
-  if (dmask & 4) vp_D_one<2>(A, u, sl2, force, UI, XC, wm, i, j, k, eps);
+                    const GArgs &A, int i, int j, int k, double eps) {
+  vp_D_one<0>(A, u, sl0, force, UI, XC, um, i, j, k, eps);
+  vp_D_one<1>(A, u, sl1, force, UI, XC, vm, i, j, k, eps);
+  vp_D_one<2>(A, u, sl2, force, UI, XC, wm, i, j, k, eps);
 }
 __global__ void __launch_bounds__(256) kk_vp_D(FV u, FV sl0, FV sl1, FV sl2, FV force, FV UI, FV XC, FV um, FV vm, FV wm, GArgs A, Range3 r, const double *umax) {
   THREAD_IJK(r)
   if (!in_range) return;
   vp_D_cell(u, sl0, sl1, sl2, force, UI, XC, um, vm, wm, A, i, j, k, eps_from(umax));
 }
-struct VpDFix { VpPlain P; __device__ void operator()(int i, int j, int k, int dmask) const { vp_D_cell(P.u, P.sl0, P.sl1, P.sl2, P.force, P.UI, P.XC, P.um, P.vm, P.wm, P.A, i, j, k, eps_from(P.umax), dmask); } };
 
-// ---- velpred, cell-centred k-marching form -------------------------------------------------------------------------
-// predictor bases of all three velocity components in a cell along D (vp_pair split by side, no boundary rule)
-template <int D> DEVI void vp_bases(const GArgs &A, const double uc[3], const double sl[3], const double ft[3], double Lb[3], double Rb[3]) {
-  const double dt2 = 0.5 * A.dt;
-  double cfl_l;
-  if (D == 1) cfl_l = dt2 * fmax(0.0, uc[D] / A.dx[1]);       // velpred.f90:2108: division inside max()
-  else cfl_l = dt2 * fmax(0.0, uc[D]) / A.dx[D];
-  const double cfl_r = dt2 * fmin(0.0, uc[D]) / A.dx[D];
-  #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    Lb[c] = uc[c] + (0.5 - cfl_l) * sl[c];
-    Rb[c] = uc[c] - (0.5 + cfl_r) * sl[c];
-    if (A.use_minion) { Lb[c] = Lb[c] + ft[c]; Rb[c] = Rb[c] + ft[c]; }
-  }
-}
-// this cell's half of the boundary rule on component c of its D-bases
-template <int D> DEVI void vp_premod(const GArgs &A, const FV &u, int c, int i, int j, int k, double &Lb, double &Rb) {
-  const int q = coord<D>(i, j, k);
-  if (q == A.lo[D]) { double o = Rb; bc_pair(o, Rb, A.phys[D][0], 0, true, c == D, ld<D>(u, i, j, k, -1, c), false); }
-  if (q == A.hi[D]) { double o = Lb; bc_pair(Lb, o, A.phys[D][1], 1, true, c == D, ld<D>(u, i, j, k, 1, c), D == 0 && !A.outlet2d); }   // :2075 quirk
-}
-template <int D> DEVI void vp_face_bc(const GArgs &A, const FV &u, int c, bool normal, bool quirk_ok, int i, int j, int k, double uc, double &L, double &R) {
-  const int side = face_side<D>(A, i, j, k);
-  if (side >= 0) bc_pair(L, R, A.phys[D][side], side, true, normal, side == 0 ? ld<D>(u, i, j, k, -1, c) : uc, quirk_ok && D == 0 && side == 1 && !A.outlet2d);
-}
-template <int D> DEVI void vp_B_emit(const FV &UI, int i, int j, int k, const double L[3], const double R[3], double eps) {
-  const double uavg = 0.5 * (L[D] + R[D]);
-  const bool test = ((L[D] <= 0.0 && R[D] >= 0.0) || (fabs(L[D] + R[D]) < eps));
-  double un = (uavg > 0.0) ? L[D] : R[D];
-  un = test ? 0.0 : un;
-  #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    double out;
-    if (c == D) out = un;
-    else {
-      double v = (un > 0.0) ? L[c] : R[c];
-      double av = 0.5 * (L[c] + R[c]);
-      out = (fabs(un) < eps) ? av : v;
-    }
-    fv_at(UI, i, j, k, D * 3 + c) = out;
-  }
-}
-#define VP_LOAD_CELL                                                                                                    \
-    double uc[3], s0[3], s1[3], s2[3], ft[3] = { 0.0, 0.0, 0.0 };                                                         \
-    _Pragma("unroll") for (int c = 0; c < 3; c++) {                                                                      \
-      uc[c] = fv_get(u, ic, jc, kc, c); s0[c] = fv_get(sl0, ic, jc, kc, c); s1[c] = fv_get(sl1, ic, jc, kc, c); s2[c] = fv_get(sl2, ic, jc, kc, c); \
-    }
-
-template <bool R, bool BC> __device__ __forceinline__ void vp_B_m_body(typename Prm<FV, R>::type u, typename Prm<FV, R>::type sl0, typename Prm<FV, R>::type sl1, typename Prm<FV, R>::type sl2, typename Prm<FV, R>::type force, typename Prm<FV, R>::type UI, typename Prm<GArgs, R>::type A, typename Prm<Range3, R>::type r, int klen, const double *umax, const int BX, const int BY, const int BZ) {
-  __shared__ double ly[2][3][TNY][64];
-  MARCH_SETUP(r)
-  const double eps = eps_from(umax);
-  const double dt2 = 0.5 * A.dt;
-  double Lz[3] = { 0.0, 0.0, 0.0 };
-  for (int k = k0 - 1; k <= k1; k++) {
-    MARCH_PLANE
-    VP_LOAD_CELL
-    if (A.use_minion) {
-      #pragma unroll
-      for (int c = 0; c < 3; c++) ft[c] = dt2 * fv_get(force, ic, jc, kc, c);
-    }
-    double Lb[3][3], Rb[3][3];
-    vp_bases<0>(A, uc, s0, ft, Lb[0], Rb[0]);
-    vp_bases<1>(A, uc, s1, ft, Lb[1], Rb[1]);
-    vp_bases<2>(A, uc, s2, ft, Lb[2], Rb[2]);
-    #pragma unroll
-    for (int c = 0; c < 3; c++) ly[buf][c][row][lane] = Lb[1][c];
-    __syncthreads();
-    double Lx[3], Ly[3], Lzc[3];
-    #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      Lx[c] = shfl_prev(Lb[0][c]);
-      Ly[c] = ly[buf][c][row >= 1 ? row - 1 : 0][lane];
-      Lzc[c] = Lz[c]; Lz[c] = Lb[2][c];
-    }
-    if (emit) {
-      if (BC && edge) {
-        #pragma unroll
-        for (int c = 0; c < 3; c++) {
-          vp_face_bc<0>(A, u, c, c == 0, true, i, j, k, uc[c], Lx[c], Rb[0][c]);
-          vp_face_bc<1>(A, u, c, c == 1, true, i, j, k, uc[c], Ly[c], Rb[1][c]);
-          vp_face_bc<2>(A, u, c, c == 2, true, i, j, k, uc[c], Lzc[c], Rb[2][c]);
-        }
-      }
-      if (i >= A.lo[0]) vp_B_emit<0>(UI, i, j, k, Lx, Rb[0], eps);
-      if (j >= A.lo[1]) vp_B_emit<1>(UI, i, j, k, Ly, Rb[1], eps);
-      if (k >= A.lo[2]) vp_B_emit<2>(UI, i, j, k, Lzc, Rb[2], eps);
-    }
-  }
-}
-template <bool BC> __global__ void __launch_bounds__(64 * TNY) kk_vp_B_m(FV u, FV sl0, FV sl1, FV sl2, FV force, FV UI, GArgs A, Range3 r, int klen, const double *umax) {
-  int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
-  vp_B_m_body<false, BC>(u, sl0, sl1, sl2, force, UI, A, r, klen, umax, bx_, by_, bz_);
-}
-
-
-// stage C: XC(C,D) = component C on D-faces corrected by the third direction O
+// the upwinded state of stage C (vp_C_one) from the normal velocity un
 DEVI double vp_up(double un, double L, double R, double eps) {
   const double v = (un > 0.0) ? L : R;
   const double av = 0.5 * (L + R);
   return (fabs(un) < eps) ? av : v;
 }
-template <bool R, bool BC> __device__ __forceinline__ void vp_C_m_body(typename Prm<FV, R>::type u, typename Prm<FV, R>::type sl0, typename Prm<FV, R>::type sl1, typename Prm<FV, R>::type sl2, typename Prm<FV, R>::type force, typename Prm<FV, R>::type UI, typename Prm<FV, R>::type XC, typename Prm<GArgs, R>::type A, typename Prm<Range3, R>::type r, int klen, const double *umax, const int BX, const int BY, const int BZ) {
-  __shared__ double ly[2][2][TNY][64];
-  MARCH_SETUP(r)
-  const double eps = eps_from(umax);
-  const double dt2 = 0.5 * A.dt, dt6 = A.dt / 6.0;
-  double Lz[2] = { 0.0, 0.0 };
-  for (int k = k0 - 1; k <= k1; k++) {
-    MARCH_PLANE
-    VP_LOAD_CELL
-    // w0[O][c] / w1[O][c]: UI[O*3+c] at the cell's lower / upper O-face
-    double w0[3][3], w1[3][3];
-    #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      w0[0][c] = fv_get(UI, ic, jc, kc, 0 + c); w1[0][c] = fv_get(UI, ip, jc, kc, 0 + c);
-      w0[1][c] = fv_get(UI, ic, jc, kc, 3 + c); w1[1][c] = fv_get(UI, ic, jp, kc, 3 + c);
-      w0[2][c] = fv_get(UI, ic, jc, kc, 6 + c); w1[2][c] = fv_get(UI, ic, jc, kp, 6 + c);
-    }
-    if (A.use_minion) {
-      #pragma unroll
-      for (int c = 0; c < 3; c++) ft[c] = dt2 * fv_get(force, ic, jc, kc, c);
-    }
-    double Lb[3][3], Rb[3][3];
-    vp_bases<0>(A, uc, s0, ft, Lb[0], Rb[0]);
-    vp_bases<1>(A, uc, s1, ft, Lb[1], Rb[1]);
-    vp_bases<2>(A, uc, s2, ft, Lb[2], Rb[2]);
-    if (BC && edge) {
-      #pragma unroll
-      for (int c = 0; c < 3; c++) { vp_premod<0>(A, u, c, ic, jc, kc, Lb[0][c], Rb[0][c]); vp_premod<1>(A, u, c, ic, jc, kc, Lb[1][c], Rb[1][c]); vp_premod<2>(A, u, c, ic, jc, kc, Lb[2][c], Rb[2][c]); }
-    }
-    // t[C][O] = (dt6/dx_O) * (UI[OO](+) + UI[OO]) * (UI[OC](+) - UI[OC])
-    double t[3][3];
-    #pragma unroll
-    for (int O = 0; O < 3; O++) {
-      const double sm = w1[O][O] + w0[O][O];
-      #pragma unroll
-      for (int C = 0; C < 3; C++) t[C][O] = (dt6 / A.dx[O]) * sm * (w1[O][C] - w0[O][C]);
-    }
-    // VL[D][n], VR[D][n]: D = 0: C = 1, 2;  D = 1: C = 0, 2;  D = 2: C = 0, 1
-    double VL[3][2], VR[3][2];
-    VL[0][0] = Lb[0][1] - t[1][2]; VR[0][0] = Rb[0][1] - t[1][2];   // D=0 C=1 O=2
-    VL[0][1] = Lb[0][2] - t[2][1]; VR[0][1] = Rb[0][2] - t[2][1];   // D=0 C=2 O=1
-    VL[1][0] = Lb[1][0] - t[0][2]; VR[1][0] = Rb[1][0] - t[0][2];   // D=1 C=0 O=2
-    VL[1][1] = Lb[1][2] - t[2][0]; VR[1][1] = Rb[1][2] - t[2][0];   // D=1 C=2 O=0
-    VL[2][0] = Lb[2][0] - t[0][1]; VR[2][0] = Rb[2][0] - t[0][1];   // D=2 C=0 O=1
-    VL[2][1] = Lb[2][1] - t[1][0]; VR[2][1] = Rb[2][1] - t[1][0];   // D=2 C=1 O=0
-    ly[buf][0][row][lane] = VL[1][0]; ly[buf][1][row][lane] = VL[1][1];
-    __syncthreads();
-    double L[3][2];
-    L[0][0] = shfl_prev(VL[0][0]); L[0][1] = shfl_prev(VL[0][1]);
-    L[1][0] = ly[buf][0][row >= 1 ? row - 1 : 0][lane]; L[1][1] = ly[buf][1][row >= 1 ? row - 1 : 0][lane];
-    L[2][0] = Lz[0]; L[2][1] = Lz[1];
-    Lz[0] = VL[2][0]; Lz[1] = VL[2][1];
-    if (emit) {
-      if (BC && edge) {
-        vp_face_bc<0>(A, u, 1, false, false, i, j, k, uc[1], L[0][0], VR[0][0]); vp_face_bc<0>(A, u, 2, false, false, i, j, k, uc[2], L[0][1], VR[0][1]);
-        vp_face_bc<1>(A, u, 0, false, false, i, j, k, uc[0], L[1][0], VR[1][0]); vp_face_bc<1>(A, u, 2, false, false, i, j, k, uc[2], L[1][1], VR[1][1]);
-        vp_face_bc<2>(A, u, 0, false, false, i, j, k, uc[0], L[2][0], VR[2][0]); vp_face_bc<2>(A, u, 1, false, false, i, j, k, uc[1], L[2][1], VR[2][1]);
-      }
-      // the advecting normal velocity on the cell's lower faces: UI[DD] = w0[D][D]
-      if (i >= A.lo[0]) { if (vz) fv_at(XC, i, j, k, xc_idx(1, 0)) = vp_up(w0[0][0], L[0][0], VR[0][0], eps); if (vy) fv_at(XC, i, j, k, xc_idx(2, 0)) = vp_up(w0[0][0], L[0][1], VR[0][1], eps); }
-      if (j >= A.lo[1]) { if (vz) fv_at(XC, i, j, k, xc_idx(0, 1)) = vp_up(w0[1][1], L[1][0], VR[1][0], eps); if (vx) fv_at(XC, i, j, k, xc_idx(2, 1)) = vp_up(w0[1][1], L[1][1], VR[1][1], eps); }
-      if (k >= A.lo[2]) { if (vy) fv_at(XC, i, j, k, xc_idx(0, 2)) = vp_up(w0[2][2], L[2][0], VR[2][0], eps); if (vx) fv_at(XC, i, j, k, xc_idx(1, 2)) = vp_up(w0[2][2], L[2][1], VR[2][1], eps); }
-    }
-  }
-}
-template <bool BC> __global__ void __launch_bounds__(64 * TNY) kk_vp_C_m(FV u, FV sl0, FV sl1, FV sl2, FV force, FV UI, FV XC, GArgs A, Range3 r, int klen, const double *umax) {
-  int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
-  vp_C_m_body<false, BC>(u, sl0, sl1, sl2, force, UI, XC, A, r, klen, umax, bx_, by_, bz_);
-}
-
-
-// stage D: the MAC velocity on valid D-faces
-template <int D> DEVI double vp_D_face(const GArgs &A, const FV &u, int i, int j, int k, double ucD, double L, double R, double eps, bool edge) {
-  const double uavg = 0.5 * (L + R);
-  const bool test = ((L <= 0.0 && R >= 0.0) || (fabs(L + R) < eps));
-  double v = (uavg > 0.0) ? L : R;
-  v = test ? 0.0 : v;
-  if (edge) {
-    const int side = face_side<D>(A, i, j, k);
-    if (side >= 0) {                                   // velpred.f90:2642-2659
-      const int ph = A.phys[D][side];
-      if (ph == VDN_SLIP_WALL || ph == VDN_NO_SLIP_WALL) v = 0.0;
-      else if (ph == VDN_INLET) v = (side == 0) ? ld<D>(u, i, j, k, -1, D) : ucD;
-      else if (ph == VDN_OUTLET) v = (side == 0) ? fmin(R, 0.0) : fmax(L, 0.0);
-    }
-  }
-  return v;
-}
-template <bool R, bool BC> __device__ __forceinline__ void vp_D_m_body(typename Prm<FV, R>::type u, typename Prm<FV, R>::type sl0, typename Prm<FV, R>::type sl1, typename Prm<FV, R>::type sl2, typename Prm<FV, R>::type force, typename Prm<FV, R>::type UI, typename Prm<FV, R>::type XC, typename Prm<FV, R>::type um, typename Prm<FV, R>::type vm, typename Prm<FV, R>::type wm, typename Prm<GArgs, R>::type A, typename Prm<Range3, R>::type r, int klen, const double *umax, const int BX, const int BY, const int BZ) {
-  __shared__ double ly[2][TNY][64];
-  MARCH_SETUP(r)
-  const double eps = eps_from(umax);
-  const double dt2 = 0.5 * A.dt, dt4 = A.dt / 4.0;
-  double Lz = 0.0;
-  for (int k = k0 - 1; k <= k1; k++) {
-    MARCH_PLANE
-    double uc[3], sd[3], ft[3];
-    #pragma unroll
-    for (int c = 0; c < 3; c++) { uc[c] = fv_get(u, ic, jc, kc, c); ft[c] = dt2 * fv_get(force, ic, jc, kc, c); }
-    sd[0] = fv_get(sl0, ic, jc, kc, 0); sd[1] = fv_get(sl1, ic, jc, kc, 1); sd[2] = fv_get(sl2, ic, jc, kc, 2);
-    // g[T] = UI[TT](+) + UI[TT];  x0/x1[n]: XC component n at the lower / upper face of its direction
-    //   XC index C*2 + (D > C ? D-1 : D): n 0 = (C0,D1) 1 = (C0,D2) 2 = (C1,D0) 3 = (C1,D2) 4 = (C2,D0) 5 = (C2,D1)
-    double g[3];
-    g[0] = fv_get(UI, ip, jc, kc, 0) + fv_get(UI, ic, jc, kc, 0);
-    g[1] = fv_get(UI, ic, jp, kc, 4) + fv_get(UI, ic, jc, kc, 4);
-    g[2] = fv_get(UI, ic, jc, kp, 8) + fv_get(UI, ic, jc, kc, 8);
-    double x0[6], x1[6];
-    #pragma unroll
-    for (int n = 0; n < 6; n++) x0[n] = fv_get(XC, ic, jc, kc, n);
-    x1[0] = fv_get(XC, ic, jp, kc, 0); x1[1] = fv_get(XC, ic, jc, kp, 1); x1[2] = fv_get(XC, ip, jc, kc, 2);
-    x1[3] = fv_get(XC, ic, jc, kp, 3); x1[4] = fv_get(XC, ip, jc, kc, 4); x1[5] = fv_get(XC, ic, jp, kc, 5);
-    // base of the NORMAL component only (vp_pair component D along D)
-    double Lb[3], Rb[3];
-    #define NBASE(Dd)                                                                                              \
-      { double cl; if (Dd == 1) cl = dt2 * fmax(0.0, uc[Dd] / A.dx[1]); else cl = dt2 * fmax(0.0, uc[Dd]) / A.dx[Dd];  \
-        const double cr = dt2 * fmin(0.0, uc[Dd]) / A.dx[Dd];                                                        \
-        Lb[Dd] = uc[Dd] + (0.5 - cl) * sd[Dd]; Rb[Dd] = uc[Dd] - (0.5 + cr) * sd[Dd];                                \
-        if (A.use_minion) { Lb[Dd] = Lb[Dd] + ft[Dd]; Rb[Dd] = Rb[Dd] + ft[Dd]; } }
-    NBASE(0) NBASE(1) NBASE(2)
-    #undef NBASE
-    if (BC && edge) { vp_premod<0>(A, u, 0, ic, jc, kc, Lb[0], Rb[0]); vp_premod<1>(A, u, 1, ic, jc, kc, Lb[1], Rb[1]); vp_premod<2>(A, u, 2, ic, jc, kc, Lb[2], Rb[2]); }
-    double VL[3], VR[3];
-    {   // D = 0: T1 = 1 with XC(0,1) = n0,  T2 = 2 with XC(0,2) = n1
-      const double a1 = (dt4 / A.dx[1]) * g[1] * (x1[0] - x0[0]);
-      const double a2 = (dt4 / A.dx[2]) * g[2] * (x1[1] - x0[1]);
-      double vl = Lb[0] - a1 - a2, vr = Rb[0] - a1 - a2;
-      if (!A.use_minion) { vl = vl + ft[0]; vr = vr + ft[0]; }
-      VL[0] = vl; VR[0] = vr;
-    }
-    {   // D = 1: T1 = 0 with XC(1,0) = n2,  T2 = 2 with XC(1,2) = n3
-      const double a1 = (dt4 / A.dx[0]) * g[0] * (x1[2] - x0[2]);
-      const double a2 = (dt4 / A.dx[2]) * g[2] * (x1[3] - x0[3]);
-      double vl = Lb[1] - a1 - a2, vr = Rb[1] - a1 - a2;
-      if (!A.use_minion) { vl = vl + ft[1]; vr = vr + ft[1]; }
-      VL[1] = vl; VR[1] = vr;
-    }
-    {   // D = 2: T1 = 0 with XC(2,0) = n4,  T2 = 1 with XC(2,1) = n5
-      const double a1 = (dt4 / A.dx[0]) * g[0] * (x1[4] - x0[4]);
-      const double a2 = (dt4 / A.dx[1]) * g[1] * (x1[5] - x0[5]);
-      double vl = Lb[2] - a1 - a2, vr = Rb[2] - a1 - a2;
-      if (!A.use_minion) { vl = vl + ft[2]; vr = vr + ft[2]; }
-      VL[2] = vl; VR[2] = vr;
-    }
-    ly[buf][row][lane] = VL[1];
-    __syncthreads();
-    const double Lx = shfl_prev(VL[0]);
-    const double Ly = ly[buf][row >= 1 ? row - 1 : 0][lane];
-    const double Lzc = Lz;
-    Lz = VL[2];
-    if (emit) {
-      if (vy && vz) fv_at(um, i, j, k) = vp_D_face<0>(A, u, i, j, k, uc[0], Lx, VR[0], eps, BC && edge);
-      if (vx && vz) fv_at(vm, i, j, k) = vp_D_face<1>(A, u, i, j, k, uc[1], Ly, VR[1], eps, BC && edge);
-      if (vx && vy) fv_at(wm, i, j, k) = vp_D_face<2>(A, u, i, j, k, uc[2], Lzc, VR[2], eps, BC && edge);
-    }
-  }
-}
-template <bool BC> __global__ void __launch_bounds__(64 * TNY) kk_vp_D_m(FV u, FV sl0, FV sl1, FV sl2, FV force, FV UI, FV XC, FV um, FV vm, FV wm, GArgs A, Range3 r, int klen, const double *umax) {
-  int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
-  vp_D_m_body<false, BC>(u, sl0, sl1, sl2, force, UI, XC, um, vm, wm, A, r, klen, umax, bx_, by_, bz_);
-}
-
 
 // ---- velpred: stages B + C + D in one march (all three components; the scheme of mk_F_m_body) --------------------------------------------
 // Iteration kk loads plane kk (u, nine slopes, force) and runs stage B on plane kk (UI: the nine upwinded states on the cell's lower faces),
 // stage C on plane kk-1 (XC: six transverse-corrected states) and stage D on plane kk-2 (the MAC velocity on the lower faces).  UI and XC
 // stay in registers; upper-face values come from the next lane (DPP), the next row (LDS, written one iteration earlier) and, along z, from the
 // stage that ran earlier in the same iteration.  A cell carries its eighteen bases from stage B to stage C and the three normal ones on to
-// stage D (the separate stages recompute them: six f64 divisions per cell and stage).  Every expression is the one of vp_B_m_body /
-// vp_C_m_body / vp_D_m_body in the same order (tests/test_kernels_gpu.py::test_velpred, test_godunov_marching_equals_face_centred).
+// stage D (the face-centred stages recompute them: six f64 divisions per cell and stage).  Every expression is the one of vp_B_one /
+// vp_C_one / vp_D_one in the same order (tests/test_kernels_gpu.py::test_velpred, test_godunov_marching_equals_face_centred).
 // Boundary rules as packed per-thread codes (mk_F_m_body): bc_pair leaves L = R = v, v one of {ghost, 0, inner, clamped inner}; the
 // hi-x OUTLET quirk of velpred.f90:2075 (min instead of max on the normal component) is the code 4 in place of 5 in stages B / premod.
 struct VArgs {
@@ -2424,7 +1479,7 @@ DEVI int vp_code_D(int phys, int side) {
   if (phys == VDN_OUTLET) return side ? 5 : 4;
   return 0;
 }
-template <int D> DEVI void vpf_emit(double ui[3], const double L[3], const double R[3], double eps) {      // vp_B_emit into registers
+template <int D> DEVI void vpf_emit(double ui[3], const double L[3], const double R[3], double eps) {      // vp_B_one's upwinding into registers
   const double uavg = 0.5 * (L[D] + R[D]);
   const bool test = ((L[D] <= 0.0 && R[D] >= 0.0) || (fabs(L[D] + R[D]) < eps));
   double un = (uavg > 0.0) ? L[D] : R[D];
@@ -2439,7 +1494,7 @@ template <int D> DEVI void vpf_emit(double ui[3], const double L[3], const doubl
     }
   }
 }
-DEVI double vpf_riemann(double L, double R, double eps) {            // the state of vp_D_face before its boundary rule
+DEVI double vpf_riemann(double L, double R, double eps) {            // the state of vp_D_one before its boundary rule
   const double uavg = 0.5 * (L + R);
   const bool test = ((L <= 0.0 && R >= 0.0) || (fabs(L + R) < eps));
   const double v = (uavg > 0.0) ? L : R;
@@ -2992,89 +2047,64 @@ static void k2_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab 
   }
 }
 
-__global__ void __launch_bounds__(64 * TNY) kk_vp_B_mb(const VpD *descs, const int *start, int nbox) {
-  BATCH_LOCATE(VpD, gg)
-  vp_B_m_body<true, true>(q.s, q.sl0, q.sl1, q.sl2, q.force, q.UI, q.A, q.rg, q.klg, q.umax, BX, BY, BZ);
-}
-__global__ void __launch_bounds__(64 * TNY) kk_vp_C_mb(const VpD *descs, const int *start, int nbox) {
-  BATCH_LOCATE(VpD, gg)
-  vp_C_m_body<true, true>(q.s, q.sl0, q.sl1, q.sl2, q.force, q.UI, q.XC, q.A, q.rg, q.klg, q.umax, BX, BY, BZ);
-}
-__global__ void __launch_bounds__(64 * TNY) kk_vp_D_mb(const VpD *descs, const int *start, int nbox) {
-  BATCH_LOCATE(VpD, gf)
-  vp_D_m_body<true, true>(q.s, q.sl0, q.sl1, q.sl2, q.force, q.UI, q.XC, q.um, q.vm, q.wm, q.A, q.rf, q.klf, q.umax, BX, BY, BZ);
-}
 void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *force, const double *dx, double dt,
                const vdn_bc_tower *bct) {
   Prof prof_("velpred");
-  god_xcd_init();
   if (ctx().prm.dm == 2) { k2_velpred(u, umac, force, dx, dt, bct); return; }
   REQUIRE(u->nc == 3 && u->ng >= 3 && force->ng >= 1 && umac[0]->ng >= 1, "velpred: operand shapes");
   hipStream_t st = ctx().stream;
-  if (use_batched(u) && !plain_godunov()) {
+  if (use_batched(u) && !plain_godunov()) {            // the slopes, then stages B + C + D in one march per box (vp_F_m_body)
     size_t mark = arena_mark();
     const int nb = u->nfabs();
     GodBatch<VpD> B; B.d.resize(nb);
     double *umax = (double *)arena_alloc(sizeof(double) * nb);
     HIPCHK(hipMemsetAsync(umax, 0, sizeof(double) * nb, st));
-    for (int ib = 0; ib < nb; ib++) {
+    std::vector<VBatchD> fd(nb);
+    std::vector<int> fstart(nb);
+    bool ok = true, inflow = false, any = false;
+    for (int ib = 0; ib < nb && ok; ib++) {
       VpD &q = B.d[ib];
       fill_gargs(q.A, u, ib, bct, 0, 3, dx, dt);
       q.A.is_vel = 1;
       BoxP bp = make_boxp(u, ib, bct);
       FV w = work_fv(nullptr, bp, 0);
       const size_t fld = (size_t)w.sc * sizeof(double);
-      q.sl0 = q.sl1 = q.sl2 = q.UI = q.XC = w;
+      q.sl0 = q.sl1 = q.sl2 = w;
       q.sl0.p = (double *)arena_alloc(fld * 3); q.sl1.p = (double *)arena_alloc(fld * 3); q.sl2.p = (double *)arena_alloc(fld * 3);
-      q.UI.p = (double *)arena_alloc(fld * 9); q.XC.p = (double *)arena_alloc(fld * 6);
       for (int d = 0; d < 3; d++) { q.rm.lo[d] = q.A.lo[d]; q.rm.hi[d] = q.A.hi[d]; q.rg.lo[d] = q.A.lo[d] - 1; q.rg.hi[d] = q.A.hi[d] + 1; q.rf.lo[d] = q.A.lo[d]; q.rf.hi[d] = q.A.hi[d] + 1; }
       q.s = u->fabs[ib]; q.force = force->fabs[ib]; q.um = umac[0]->fabs[ib]; q.vm = umac[1]->fabs[ib]; q.wm = umac[2]->fabs[ib];
       q.umax = umax + ib;
+      const FV sl[3] = { q.sl0, q.sl1, q.sl2 };
+      for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) { inflow = inflow || q.A.phys[d][sd] == VDN_INLET; any = any || bc_mode_host(q.A.phys[d][sd]); }
+      ok = vfused_args(fd[ib].F, q.A, q.s, sl, q.force, q.um, q.vm, q.wm);
+      fd[ib].r = q.rf; fd[ib].umax = q.umax;
+      fused_grid_small(fd[ib].r, fd[ib].klen, fd[ib].g, fd[ib].sw);
     }
-    B.finish();
-    const dim3 blk(64, TNY, 1);
-    hipLaunchKernelGGL(kk_velmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);
-    hipLaunchKernelGGL(kk_slopes_b<VpD>, dim3(B.tot[0]), dim3(64, 4, 1), 0, st, B.dev, B.st[0], nb, 7);
-    static const bool fused_env = !(vdn_env("VDN_GOD_FUSED") && atoi(vdn_env("VDN_GOD_FUSED")) == 0);
-    if (fused_env) {               // stages B + C + D in one march per box (vp_F_m_body)
-      std::vector<VBatchD> fd(nb);
-      std::vector<int> fstart(nb);
-      bool ok = true, inflow = false, any = false;
-      int tot = 0;
-      for (int ib = 0; ib < nb && ok; ib++) {
-        const VpD &q = B.d[ib];
-        const FV sl[3] = { q.sl0, q.sl1, q.sl2 };
-        for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) { inflow = inflow || q.A.phys[d][sd] == VDN_INLET; any = any || bc_mode_host(q.A.phys[d][sd]); }
-        ok = vfused_args(fd[ib].F, q.A, q.s, sl, q.force, q.um, q.vm, q.wm);
-        fd[ib].r = q.rf; fd[ib].umax = q.umax;
-        fused_grid_small(fd[ib].r, fd[ib].klen, fd[ib].g, fd[ib].sw);
-      }
-      if (ok) {
-        // two launches: the boxes in full-width tiles, the narrow ones in row segments (seg_geo)
-        std::stable_partition(fd.begin(), fd.end(), [](const VBatchD &f) { return f.sw == 0; });
-        const int nwide = (int)std::count_if(fd.begin(), fd.end(), [](const VBatchD &f) { return f.sw == 0; });
-        int totn = 0;
-        for (int t = 0; t < nb; t++) { int &T = t < nwide ? tot : totn; fstart[t] = T; T += fd[t].g[0] * fd[t].g[1] * fd[t].g[2]; }
-        VBatchD *dd = (VBatchD *)desc_scratch(sizeof(VBatchD) * nb); int *ds = (int *)desc_scratch(sizeof(int) * nb);
-        upload_staged(dd, fd.data(), sizeof(VBatchD) * nb); upload_staged(ds, fstart.data(), sizeof(int) * nb);
-        const bool p2 = fd[0].F.p2 != 0;
-        #define VP_LAUNCH(NARROW, T, D0, S0, N)                                                                                                          \
-          if (!any) { if (p2) hipLaunchKernelGGL((kk_vp_F_mb<false, false, true, NARROW>), dim3(T), blk, 0, st, D0, S0, N); else hipLaunchKernelGGL((kk_vp_F_mb<false, false, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N); } \
-          else if (inflow) hipLaunchKernelGGL((kk_vp_F_mb<true, true, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N);                                      \
-          else if (p2) hipLaunchKernelGGL((kk_vp_F_mb<true, false, true, NARROW>), dim3(T), blk, 0, st, D0, S0, N);                                          \
-          else hipLaunchKernelGGL((kk_vp_F_mb<true, false, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N);
-        if (nwide) { VP_LAUNCH(false, tot, dd, ds, nwide) }
-        if (nwide < nb) { VP_LAUNCH(true, totn, dd + nwide, ds + nwide, nb - nwide) }
-        #undef VP_LAUNCH
-        arena_release(mark);
-        return;
-      }
+    if (ok) {
+      B.finish();
+      const dim3 blk(64, TNY, 1);
+      hipLaunchKernelGGL(kk_velmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);
+      hipLaunchKernelGGL(kk_slopes_b<VpD>, dim3(B.tot[0]), dim3(64, 4, 1), 0, st, B.dev, B.st[0], nb, 7);
+      // two launches: the boxes in full-width tiles, the narrow ones in row segments (seg_geo)
+      std::stable_partition(fd.begin(), fd.end(), [](const VBatchD &f) { return f.sw == 0; });
+      const int nwide = (int)std::count_if(fd.begin(), fd.end(), [](const VBatchD &f) { return f.sw == 0; });
+      int tot = 0, totn = 0;
+      for (int t = 0; t < nb; t++) { int &T = t < nwide ? tot : totn; fstart[t] = T; T += fd[t].g[0] * fd[t].g[1] * fd[t].g[2]; }
+      VBatchD *dd = (VBatchD *)desc_scratch(sizeof(VBatchD) * nb); int *ds = (int *)desc_scratch(sizeof(int) * nb);
+      upload_staged(dd, fd.data(), sizeof(VBatchD) * nb); upload_staged(ds, fstart.data(), sizeof(int) * nb);
+      const bool p2 = fd[0].F.p2 != 0;
+      #define VP_LAUNCH(NARROW, T, D0, S0, N)                                                                                                          \
+        if (!any) { if (p2) hipLaunchKernelGGL((kk_vp_F_mb<false, false, true, NARROW>), dim3(T), blk, 0, st, D0, S0, N); else hipLaunchKernelGGL((kk_vp_F_mb<false, false, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N); } \
+        else if (inflow) hipLaunchKernelGGL((kk_vp_F_mb<true, true, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N);                                      \
+        else if (p2) hipLaunchKernelGGL((kk_vp_F_mb<true, false, true, NARROW>), dim3(T), blk, 0, st, D0, S0, N);                                          \
+        else hipLaunchKernelGGL((kk_vp_F_mb<true, false, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N);
+      if (nwide) { VP_LAUNCH(false, tot, dd, ds, nwide) }
+      if (nwide < nb) { VP_LAUNCH(true, totn, dd + nwide, ds + nwide, nb - nwide) }
+      #undef VP_LAUNCH
+      arena_release(mark);
+      return;
     }
-    hipLaunchKernelGGL(kk_vp_B_mb, dim3(B.tot[2]), blk, 0, st, B.dev, B.st[2], nb);
-    hipLaunchKernelGGL(kk_vp_C_mb, dim3(B.tot[2]), blk, 0, st, B.dev, B.st[2], nb);
-    hipLaunchKernelGGL(kk_vp_D_mb, dim3(B.tot[3]), blk, 0, st, B.dev, B.st[3], nb);
-    arena_release(mark);
-    return;
+    arena_release(mark);                               // a box's layouts refused: the level runs box by box
   }
   for (int ib = 0; ib < u->nfabs(); ib++) {
     size_t mark = arena_mark();
@@ -3083,58 +2113,38 @@ void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *f
     BoxP bp = make_boxp(u, ib, bct);
     FV w = work_fv(nullptr, bp, 0);
     const size_t fld = (size_t)w.sc * sizeof(double);
-    FV sl[3], UI = w, XC = w;
+    FV sl[3];
     const bool keep = (int)ctx().slope_src.size() == u->nfabs();           // advance_timestep: mkflux(uold) reuses these slopes
     for (int d = 0; d < 3; d++) { sl[d] = w; sl[d].p = keep ? ctx().slope_cache[d][ib] : (double *)arena_alloc(fld * 3); }
     if (keep) ctx().slope_src[ib] = u->fabs[ib].p;
-    UI.p = (double *)arena_alloc(fld * 9);
-    XC.p = (double *)arena_alloc(fld * 6);
     double *umax = (double *)arena_alloc(256);
     HIPCHK(hipMemsetAsync(umax, 0, sizeof(double), st));
-    Range3 rv, rg, rf;
-    for (int d = 0; d < 3; d++) { rv.lo[d] = A.lo[d]; rv.hi[d] = A.hi[d]; rg.lo[d] = A.lo[d] - 1; rg.hi[d] = A.hi[d] + 1; rf.lo[d] = A.lo[d]; rf.hi[d] = A.hi[d] + 1; }
+    Range3 rg, rf;
+    for (int d = 0; d < 3; d++) { rg.lo[d] = A.lo[d] - 1; rg.hi[d] = A.hi[d] + 1; rf.lo[d] = A.lo[d]; rf.hi[d] = A.hi[d] + 1; }
     launch_slopes(u->fabs[ib], sl, A, rg, 3, umax, st);      // + max |u| (kk_velmax)
-    (void)rv;
-    if (plain_godunov()) {
+    VArgs VA;
+    if (!plain_godunov() && vfused_args(VA, A, u->fabs[ib], sl, force->fabs[ib], umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib])) {
+      int klF;                     // stages B + C + D in one march, boundary rules inside (see vp_F_m_body)
+      const dim3 gF = fused_grid(rf, klF), blk(64, TNY, 1);
+      bool any = false, inflow = false;
+      for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) { any = any || bc_mode_host(A.phys[d][sd]); inflow = inflow || A.phys[d][sd] == VDN_INLET; }
+      const bool p2 = VA.p2 != 0;
+      if (!any) { if (p2) hipLaunchKernelGGL((kk_vp_F_m<false, false, true>), gF, blk, 0, st, VA, rf, klF, umax); else hipLaunchKernelGGL((kk_vp_F_m<false, false>), gF, blk, 0, st, VA, rf, klF, umax); }
+      else if (inflow) hipLaunchKernelGGL((kk_vp_F_m<true, true>), gF, blk, 0, st, VA, rf, klF, umax);
+      else if (p2) {
+        dim3 gM; int klM, full, segw;
+        if (fused_grid_cols(rf, gM, klM, full, segw)) hipLaunchKernelGGL((kk_vp_F_mc<true, false, true>), gM, blk, 0, st, VA, rf, klM, umax, full, segw);
+        else hipLaunchKernelGGL((kk_vp_F_m<true, false, true>), gF, blk, 0, st, VA, rf, klF, umax);
+      }
+      else hipLaunchKernelGGL((kk_vp_F_m<true, false>), gF, blk, 0, st, VA, rf, klF, umax);
+    } else {                       // the face-centred stages: VDN_GODUNOV_PLAIN, or field layouts the fused march refuses
+      FV UI = w, XC = w;
+      UI.p = (double *)arena_alloc(fld * 9);
+      XC.p = (double *)arena_alloc(fld * 6);
       hipLaunchKernelGGL(kk_vp_B, grid_for(rg), dim3(64, 4, 1), 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, A, rg, umax);
       hipLaunchKernelGGL(kk_vp_C, grid_for(rg), dim3(64, 4, 1), 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC, A, rg, umax);
       hipLaunchKernelGGL(kk_vp_D, grid_for(rf), dim3(64, 4, 1), 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC,
                          umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib], A, rf, umax);
-    } else {
-      int klg, klf;
-      const dim3 gg = march_grid(rg, klg), gf = march_grid(rf, klf), blk(64, TNY, 1);
-      static const bool fused_env = !(vdn_env("VDN_GOD_FUSED") && atoi(vdn_env("VDN_GOD_FUSED")) == 0);
-      VArgs VA;
-      if (fused_env && vfused_args(VA, A, u->fabs[ib], sl, force->fabs[ib], umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib])) {
-        int klF;                   // stages B + C + D in one march, boundary rules inside (see vp_F_m_body)
-        const dim3 gF = fused_grid(rf, klF);
-        bool any = false, inflow = false;
-        for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) { any = any || bc_mode_host(A.phys[d][sd]); inflow = inflow || A.phys[d][sd] == VDN_INLET; }
-        const bool p2 = VA.p2 != 0;
-        if (!any) { if (p2) hipLaunchKernelGGL((kk_vp_F_m<false, false, true>), gF, blk, 0, st, VA, rf, klF, umax); else hipLaunchKernelGGL((kk_vp_F_m<false, false>), gF, blk, 0, st, VA, rf, klF, umax); }
-        else if (inflow) hipLaunchKernelGGL((kk_vp_F_m<true, true>), gF, blk, 0, st, VA, rf, klF, umax);
-        else if (p2) {
-          dim3 gM; int klM, full, segw;
-          if (fused_grid_cols(rf, gM, klM, full, segw)) hipLaunchKernelGGL((kk_vp_F_mc<true, false, true>), gM, blk, 0, st, VA, rf, klM, umax, full, segw);
-          else hipLaunchKernelGGL((kk_vp_F_m<true, false, true>), gF, blk, 0, st, VA, rf, klF, umax);
-        }
-        else hipLaunchKernelGGL((kk_vp_F_m<true, false>), gF, blk, 0, st, VA, rf, klF, umax);
-      } else if (slab_bc()) {      // interior marches, then the face-centred code on the boundary slabs (see kk_slabs)
-        const VpPlain P{ u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC, umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib], A, umax };
-        const Slabs Sg = boundary_slabs(A, rg), Sf = boundary_slabs(A, rf);
-        hipLaunchKernelGGL(kk_vp_B_m<false>, gg, blk, 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, A, rg, klg, umax);
-        launch_slabs(Sg, VpBFix{ P }, st);
-        hipLaunchKernelGGL(kk_vp_C_m<false>, gg, blk, 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC, A, rg, klg, umax);
-        launch_slabs(Sg, VpCFix{ P }, st);
-        hipLaunchKernelGGL(kk_vp_D_m<false>, gf, blk, 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC,
-                           umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib], A, rf, klf, umax);
-        launch_slabs(Sf, VpDFix{ P }, st);
-      } else {
-      hipLaunchKernelGGL(kk_vp_B_m<true>, gg, blk, 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, A, rg, klg, umax);
-      hipLaunchKernelGGL(kk_vp_C_m<true>, gg, blk, 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC, A, rg, klg, umax);
-      hipLaunchKernelGGL(kk_vp_D_m<true>, gf, blk, 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC,
-                         umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib], A, rf, klf, umax);
-      }
     }
     arena_release(mark);
   }

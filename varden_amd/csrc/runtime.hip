@@ -212,15 +212,12 @@ static const EnvSwitch g_switches[] = {
   { "VDN_NO_GRAPHS", "launch every multigrid cycle eagerly instead of replaying its hipGraph" },
   { "VDN_NO_SLOPE_CACHE", "velocity mkflux recomputes the slopes of uold that velpred computed in the same step" },
   { "VDN_NO_FORCE_REUSE", "1: every forcing term is computed where the reference computes it (advance_premac AND velocity_advance, ...)" },
-  { "VDN_SLOPES_Y", "0: the slopes march exchanges rows through LDS (kk_slopes_m) instead of reading the y-neighbours from memory (kk_slopes_my)" },
   { "VDN_SLOPES_MARCH", "0: the per-cell slopes kernel instead of the k-marching one" },
   { "VDN_GODUNOV_BATCH", "1: the descriptor (box-batched) Godunov kernels also on a level of one box" },
-  { "VDN_GOD_SLAB_BC", "0: (unfused marches) boundary rules inside the marches instead of the face-centred code on boundary slabs" },
-  { "VDN_GODUNOV_PLAIN", "the face-centred one-thread-per-cell Godunov kernels of round 1 (the marching kernels' bit-for-bit reference)" },
+  { "VDN_GODUNOV_PLAIN", "the face-centred one-thread-per-cell Godunov kernels of round 1 (the fused marches' bit-for-bit reference, and their fallback where they refuse the field layouts)" },
   { "VDN_GOD_SEGW", "0: the box-batched fused Godunov marches use full-width (64 x 8) tiles for every box" },
   { "VDN_GOD_P2", "0: the fused marches divide by dx also where every dx is a power of two (default there: scale by 1/dx, the same doubles)" },
   { "VDN_FUSED_KCHUNKS", "k-chunks of the fused marches (default: the count that fills the last round of workgroups best)" },
-  { "VDN_GOD_FUSED", "0: one march per Godunov stage (B, C, D) instead of the fused B+C+D march" },
   { "VDN_GOD_UPDATE", "0: update_3d as its own pass instead of inside the fused mkflux march" },
   { "VDN_GSRB_PAIR", "0: one cell per thread in the colour passes / residuals of wide levels instead of the 2 x 2 pair form" },
   { "VDN_MAC_SPLIT", "0: the finest level of macproject's one-level solve stays interleaved (kk_cc_gsrb_rho_pair) instead of stored by colour (kk_cc_gsrb_rho_split); 2: only the colour passes on the split arrays, the residual on the level array" },
@@ -251,7 +248,6 @@ static const EnvSwitch g_switches[] = {
   { "VDN_FB_FACES", "0: the ghost exchanges of the composite cell-centred solve fill edges and corners too" },
   { "VDN_MLCC_RHO", "0: the composite MAC solve reads stored face coefficients on its finest level too" },
   { "VDN_GOD_NARROW", "0: the remainder tile column of the fused mkflux + update march in full 64-lane tiles instead of narrow segments (kk_mk_F_mn)" },
-  { "VDN_GOD_1B", "0: the fused mkflux + update march of a one-box level with three workgroup barriers per plane (round 4) instead of one (godunov.hip, ONEB)" },
   { "VDN_KEEP_SETS", "0: the descriptor arrays of the inter-level operators and composite solves are rebuilt and uploaded at every call" },
   { "VDN_KEPT_BOUND", "n > 0: the kept descriptor tables hold at most n entries each (default 4096 / 64 / 512): the eviction paths in a test" },
   { "VDN_MLCC_GLUE", "0: the level-0 correction of the composite MAC solve stored and added in separate passes" },
