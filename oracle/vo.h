@@ -5,15 +5,15 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it, and only as
  * the checker / the reported CPU baseline.
  *
- * PARITY STATUS: **parity unpinned**.  The reference (BoxLib-Codes/VARDEN, pure Fortran 90) ships
- * no golden vectors, fixtures or known-answer tests for this path, and it
- * cannot be built here: it needs FBoxLib (external, absent, unpinned) and a generated
- * probin.f90.  Building it against hand-written stand-ins for those modules is not allowed
- * by this round's rules, so this restatement is checked only against (i) a line-by-line
- * reading of the reference sources it cites and (ii) the known-answer invariants listed in
- * SURVEY.md section 8(c) (tests/test_oracle_invariants.py).  Both multigrid solvers live in FBoxLib and
- * have NO reference text at all: oracle/vo_mg_cc.c and vo_mg_nd.c define the discrete systems
- *  and an algorithm of our own.
+ * PARITY STATUS: the pointwise kernels are pinned to the reference's own code, bit for bit: slope, velpred, mkflux, update,
+ * mkvelforce, mkscalforce, estdt, physbc, make_at_halftime, makevort, makemagvel, tag_boxes, 2-D and 3-D.  oracle/ref/ compiles
+ * the reference's array-level routines, unmodified, against stand-ins for the five declaration-only modules they use
+ * (oracle/_ref/libvref.so, built from the reference tree, never kept in git), and tests/test_reference_kernels_cpu.py compares
+ * every case with 0 ulp; tests/golden/reference_kernels.json keeps the hashes of the reference's results.
+ * Still unpinned: the two multigrids, the viscous solves, the inter-level operators and fill_boundary.  They are FBoxLib's and
+ * have NO reference text in the tree: oracle/vo_macproject.c, vo_hgproject.c and vo_amr.c define the discrete systems (SURVEY.md
+ * Appendix C) and algorithms of our own, held by the assembled-matrix tests and the known-answer invariants of SURVEY.md
+ * section 8(c) (tests/test_operators_assembled_*.py, tests/test_oracle_invariants.py) only.
  *
  * Arithmetic: IEEE f64, compiled with -ffp-contract=off so that expression order is the
  * only thing that determines the bits (the reference CPU build has no FMA contraction on

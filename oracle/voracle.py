@@ -1,7 +1,8 @@
 """ctypes loader + numpy helpers for the CPU oracle (oracle/libvoracle.so).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
-leg.  Nothing under varden_amd/ imports this module.  parity unpinned (see oracle/vo.h).
+leg.  Nothing under varden_amd/ imports this module.  Parity status: see oracle/vo.h (the pointwise kernels are held to the
+reference's own routines, ref_lib()).
 """
 import ctypes as C
 import os
@@ -116,6 +117,44 @@ def lib():
         _lib.vo_nd_solve.restype = C.c_int
         _lib.vo_estdt_g.restype = C.c_double
     return _lib
+
+
+REF_LIB = os.path.join(_HERE, "_ref", "libvref.so")
+# C entry points of oracle/ref/ref_capi.f90: p = pointer, i = int, d = double (by value), in argument order; "_2d" and "_3d" of each
+_REF_SIG = {
+    "vref_slope": ("ippppiiip",) * 2,
+    "vref_velpred": ("p" * 7 + "dppiiii", "p" * 8 + "dppiiii"),
+    "vref_mkflux": ("p" * 12 + "dippiiiiiiip", "p" * 15 + "dippiiiiiiip"),
+    "vref_update": ("p" * 11 + "iiiiiipdip", "p" * 14 + "iiiiiipdip"),
+    "vref_mkvelforce": ("pppppiiiiiidpp",) * 2,
+    "vref_mkscalforce": ("pppiiiidpp",) * 2,
+    "vref_estdt": ("pipipipipppp",) * 2,
+    "vref_physbc": ("pppipi",) * 2,
+    "vref_make_at_halftime": ("pppppii",) * 2,
+    "vref_makevort": ("ppppipp",) * 2,
+    "vref_makemagvel": ("ppppi",) * 2,
+    "vref_tag_boxes": ("ppppidi",) * 2,
+}
+_CT = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double}
+_ref = None
+
+
+def ref_lib():
+    """the reference's own array-level routines (oracle/ref/Makefile -> oracle/_ref/libvref.so) with typed signatures, or None when
+    the library has not been built (no reference tree or no flang at build time).  Arrays go in as addresses of Fortran-ordered data."""
+    global _ref
+    if _ref is None:
+        if not os.path.exists(REF_LIB):
+            return None
+        L = C.CDLL(REF_LIB)
+        for name, sigs in _REF_SIG.items():
+            for suffix, sig in zip(("_2d", "_3d"), sigs):
+                f = getattr(L, name + suffix)
+                f.argtypes, f.restype = [_CT[c] for c in sig], None
+        L.vref_set_probin.argtypes, L.vref_set_probin.restype = [_CT[c] for c in "iiiddiiippppp"], None
+        L.vref_errors.argtypes, L.vref_errors.restype = [], C.c_int
+        _ref = L
+    return _ref
 
 
 class Fab:

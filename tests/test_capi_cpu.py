@@ -86,14 +86,14 @@ def test_rejects_unimplemented_configurations():
 
 
 def test_product_does_not_reference_the_oracle():
-    """nothing under varden_amd/ may include, import or link anything under oracle/"""
+    """nothing under varden_amd/ may include, import or link anything under oracle/, the reference kernels of oracle/_ref/ (libvref.so) included"""
     bad = []
     for dp, _, fns in os.walk(os.path.join(ROOT, "varden_amd")):
         for fn in fns:
             if fn.endswith((".py", ".hip", ".h", ".cpp", ".f90", "Makefile")):
                 txt = open(os.path.join(dp, fn), errors="ignore").read()
                 for ln in txt.splitlines():
-                    if re.search(r"(#include|import|from|-l|-L).*(voracle|oracle/|vo\.h|libvoracle)", ln):
+                    if re.search(r"(#include|import|from|-l|-L).*(voracle|oracle/|vo\.h|libvoracle|_ref\b|libvref|vref_)", ln):
                         bad.append((fn, ln.strip()))
     assert not bad, bad
 
