@@ -116,7 +116,9 @@ int  vdn_init(const vdn_params *prm, int rank, int nranks, int device);
  * multigrid (VDN_ND_*, VDN_HG_FAST); composite solves (VDN_NDF_*, VDN_NDM_*, VDN_MLCC_*, VDN_FB_FACES); box-batched kernels (VDN_BATCH_*). */
 const char *vdn_debug_switches(void);
 /* "release": libvarden_amd.so -- reads NO environment variable (the switches are compiled out, RCCL is the only transport); "testing": libvarden_amd_testing.so,
- * the same objects with the switch table and the test-transport seam compiled in (the test suite, the A/B tools, the one-GPU transport rehearsal) */
+ * the same objects with the switch table and the test-transport seam compiled in (the test suite, the A/B tools, the one-GPU transport rehearsal).
+ * The testing build alone also exports `unsigned vdn_nd_prolong_fused_levels(void)`: bit l is set when level l of the last nodal solve took its coarse
+ * correction inside the first post-smoothing march (the read-back of tests/test_nd_prolong_fused_gpu.py; not part of the product's interface). */
 const char *vdn_build_flavour(void);
 int  vdn_finalize(void);
 const char *vdn_last_error(void);

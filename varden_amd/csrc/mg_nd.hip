@@ -219,8 +219,18 @@ __device__ int g_nd_dbg = 0;      // (probe of round 3, always 0 now: 1 = no ste
 struct NdPairGrid { int gxm, gy, gz, nmain, lwr, gyr, rev; };       // main tiles gxm x gy x gz (lw = 6), then gyr x gz remainder tiles of segment 2^lwr
 // (round 3, measured and rejected at 257^3: sigma and rhs loaded with the non-temporal hint 0.1392 -> 0.1420 ms; the kernel held to 128 VGPRs
 // -- four waves per SIMD, 116 bytes of scratch per lane -- 0.341 ms)
-template <int MODE, int ROWS>
-__global__ void __launch_bounds__(64 * ROWS) kk_nd_march_pair(NLev L, const double *__restrict__ phi, double *__restrict__ out, double omega, NdPairGrid G, double *nrm, int shell_later) {
+// PRO = 1 -- the first post-smoothing sweep of a V-cycle sweeps phi + P e, e the coarse level's correction (round 7): every phi value the march loads gets
+// kk_nd_prolong_m's update of the node it was loaded from before it enters q -- the same sums in the same order, the same mask (Dirichlet nodes and everything
+// outside 0..n keep the loaded value; the test is on the LOADED address iac / jc, so clamped and feed lanes hand on what the two-pass form would have read),
+// hence the same bits -- and the prolongation pass with its 16 B/node and its launch goes.  A lane keeps coarse column I = iac / 2 of the three coarse rows
+// (jc - 1) / 2 .. and of the coarse planes K = kp / 2 and K + 1 of the plane kp being loaded in a slot of LDS of its own (12 KB per workgroup; held in registers
+// they cost the march its third wave per SIMD: 180 VGPRs, or 44 bytes of scratch when held to 168); column I + 1 is the next lane's (DPP); plane K + 1 is loaded
+// when kp turns odd and is plane K one plane later: three 8-byte loads per lane every second plane, issued before the plane's own loads.
+struct NdCoarse { const double *phi; int PX, PY, n0; };
+// amdgpu_waves_per_eu(3) is there for PRO = 1 alone: on its own that instantiation takes 170 VGPRs (two waves per SIMD), under the hint 168 and no scratch -- exactly
+// the three-wave limit, so any edit of the PRO path must be followed by tools/check_scratch.sh.  The other two instantiations (154 / 150 VGPRs) come out the same with and without it.
+template <int MODE, int ROWS, int PRO = 0>
+__global__ void __launch_bounds__(64 * ROWS) __attribute__((amdgpu_waves_per_eu(3))) kk_nd_march_pair(NLev L, const double *__restrict__ phi, double *__restrict__ out, double omega, NdPairGrid G, double *nrm, int shell_later, NdCoarse C) {
   const int lane = threadIdx.x;
   const int id = (int)blockIdx.x;
   int lw, pair0, j, bz;
@@ -256,7 +266,61 @@ __global__ void __launch_bounds__(64 * ROWS) kk_nd_march_pair(NLev L, const doub
     #define EXCHP(pl) { _Pragma("unroll") for (int b = 0; b < 3; b++) { q[pl][b][0] = lane_prev(q[pl][b][2]); q[pl][b][3] = lane_next(q[pl][b][1]); } }
     #define LOADS(dk, off) { _Pragma("unroll") for (int dj = 0; dj < 2; dj++) { const double2 v = ld2(L.sig + (off) + (dj - 1) * sy); sg[dk][dj][1] = v.x; sg[dk][dj][2] = v.y; } }
     #define EXCHS(dk) { _Pragma("unroll") for (int dj = 0; dj < 2; dj++) sg[dk][dj][0] = lane_prev(sg[dk][dj][2]); }
+    // ---- PRO: the coarse correction of a loaded plane ----
+    // coarse column I of the rows Jlo .. Jlo + 2, coarse plane K in slot K & 1: every lane reads only what it wrote itself (no barrier)
+    __shared__ double pro_c[PRO ? 2 * 3 * 64 * ROWS : 1];
+    double *pc = pro_c + (PRO ? (int)threadIdx.y * 64 + lane : 0);
+    #define PC(K, r) pc[(((K) & 1) * 3 + (r)) * (64 * ROWS)]
+    unsigned coff = 0; long csy = 0, csz = 0;                            // this lane's (I, Jlo) in a coarse plane
+    bool pmA[3] = { false, false, false }, pmB[3] = { false, false, false };
+    const bool pj = jc & 1;                                              // fine rows jc - 1, jc, jc + 1 sit on coarse rows (0 | 0,1 | 1) for odd jc, (0,1 | 1 | 1,2) for even jc
+    if (PRO) {
+      csy = C.PX; csz = (long)C.PX * C.PY;
+      coff = (unsigned)((min(iac >> 1, C.n0 + 1) + 16) + C.PX * (((jc - 1) >> 1) + 1));      // (I, Jlo); rows Jlo + 2 <= n1 / 2 + 1 and planes K + 1 <= n2 / 2 + 1 exist (even extents)
+      const bool inA = iac >= 0 && iac <= L.n[0] && !((iac == 0 && L.dirlo[0]) || (iac == L.n[0] && L.dirhi[0]));
+      const bool inB = iac + 1 >= 0 && iac + 1 <= L.n[0] && !(iac + 1 == L.n[0] && L.dirhi[0]);
+      #pragma unroll
+      for (int b = 0; b < 3; b++) {
+        const int jr = jc - 1 + b;
+        const bool row = jr >= 0 && jr <= L.n[1] && !((jr == 0 && L.dirlo[1]) || (jr == L.n[1] && L.dirhi[1]));
+        pmA[b] = row && inA; pmB[b] = row && inB;
+      }
+      const int K0 = (k0 - 1) >> 1;
+      const double *cq = C.phi + csz * (K0 + 1) + coff;                  // plane K is the array's plane K + 1
+      #pragma unroll
+      for (int r = 0; r < 3; r++) { PC(K0, r) = cq[r * csy]; PC(K0 + 1, r) = cq[csz + r * csy]; }
+    }
+    // plane kp of phi, just loaded into q[pl][.][1..2]: kk_nd_prolong_m's `pe + s * w0` (even kp) / `po + t * w1` (odd kp) per node
+    #define PROP(pl, kpx) if (PRO) {                                                                                                        \
+      const int kp_ = (kpx);                                                                                                                \
+      const bool kin = kp_ >= 0 && kp_ <= L.n[2] && !((kp_ == 0 && L.dirlo[2]) || (kp_ == L.n[2] && L.dirhi[2]));                          \
+      const bool kodd = kp_ & 1;                                                                                                            \
+      double ca[3], cb[3], can[3], cbn[3];                                                                                                  \
+      _Pragma("unroll") for (int r = 0; r < 3; r++) { ca[r] = PC(kp_ >> 1, r); cb[r] = kodd ? PC((kp_ >> 1) + 1, r) : 0.0; }               \
+      _Pragma("unroll") for (int r = 0; r < 3; r++) { can[r] = lane_next(ca[r]); cbn[r] = kodd ? lane_next(cb[r]) : 0.0; }                 \
+      _Pragma("unroll") for (int b = 0; b < 3; b++) {                                                                                       \
+        const bool oj = (b == 1) ? pj : !pj;                                                                                                \
+        const int r0 = (b == 2) ? 1 : 0;                                        /* coarse row J of the fine row: r0 for odd jc, else r0 + (b == 1) */ \
+        const bool up = (b == 1) && !pj;                                                                                                    \
+        const double a00 = up ? ca[1] : ca[r0], a01 = up ? ca[2] : ca[r0 + 1], a10 = up ? can[1] : can[r0], a11 = up ? can[2] : can[r0 + 1]; \
+        double sA = 0.0, sB = 0.0;                                                                                                          \
+        sA = sA + a00; sA = oj ? sA + a01 : sA;                                                                                             \
+        sB = sB + a00; sB = sB + a10; sB = oj ? sB + a01 : sB; sB = oj ? sB + a11 : sB;                                                     \
+        double dA, dB;                                                          /* w0, w1 = 1 / ((1 + oi)(1 + oj)(1 + ok)): exact powers of two */ \
+        if (!kodd) { dA = sA * (oj ? 0.5 : 1.0); dB = sB * (oj ? 0.25 : 0.5); }                                                             \
+        else {                                                                                                                              \
+          const double b00 = up ? cb[1] : cb[r0], b01 = up ? cb[2] : cb[r0 + 1], b10 = up ? cbn[1] : cbn[r0], b11 = up ? cbn[2] : cbn[r0 + 1]; \
+          double tA = sA, tB = sB;                                                                                                          \
+          tA = tA + b00; tA = oj ? tA + b01 : tA;                                                                                           \
+          tB = tB + b00; tB = tB + b10; tB = oj ? tB + b01 : tB; tB = oj ? tB + b11 : tB;                                                   \
+          dA = tA * (oj ? 0.25 : 0.5); dB = tB * (oj ? 0.125 : 0.25);                                                                       \
+        }                                                                                                                                   \
+        if (kin && pmA[b]) q[pl][b][1] = q[pl][b][1] + dA;                                                                                            \
+        if (kin && pmB[b]) q[pl][b][2] = q[pl][b][2] + dB;                                                                                            \
+      } }
     LOADP(0, c - sz) LOADP(1, c) LOADS(0, c - sz)
+    PROP(0, k0 - 1)
+    PROP(1, k0)
     EXCHP(0) EXCHP(1) EXCHS(0)
     const bool dirj = (j == 0 && L.dirlo[1]) || (j == L.n[1] && L.dirhi[1]);
     const bool dirA_ij = dirj || (ia == 0 && L.dirlo[0]) || (ia == L.n[0] && L.dirhi[0]);
@@ -265,7 +329,11 @@ __global__ void __launch_bounds__(64 * ROWS) kk_nd_march_pair(NLev L, const doub
     const int dbg = g_nd_dbg;
     for (int k = k0; k <= k1; k++, c += sz, op += ostep) {
       double2 rhs = make_double2(1.0, 1.0);
+      if (PRO) {                                                         // the coarse planes of plane k + 1 (uniform over the workgroup)
+        if ((k + 1) & 1) { const int K1 = ((k + 1) >> 1) + 1; const double *cq = C.phi + csz * (K1 + 1) + coff; _Pragma("unroll") for (int r = 0; r < 3; r++) PC(K1, r) = cq[r * csy]; }
+      }
       if (!(dbg & 2)) { LOADP(2, c + sz) LOADS(1, c) rhs = ld2(L.b + c); }
+      PROP(2, k + 1)
       EXCHP(2) EXCHS(1)
       const bool dirk = (k == 0 && L.dirlo[2]) || (k == L.n[2] && L.dirhi[2]);
       double pa[3][3][3], pb[3][3][3], sa[2][2][2], sb[2][2][2];
@@ -313,6 +381,8 @@ __global__ void __launch_bounds__(64 * ROWS) kk_nd_march_pair(NLev L, const doub
     #undef EXCHP
     #undef LOADS
     #undef EXCHS
+    #undef PROP
+    #undef PC
   }
   if (MODE == 1 && nrm) block_atomic_max(nrm, rmax);
 }
@@ -963,7 +1033,8 @@ static NdPairGrid nd_pair_grid(const NLev &L, int rows, int nzu, bool use_rem, i
 // two warm-up planes (overhead 2/kchunk)
 // rev: the tiles in reverse order.  Consecutive marches of a level alternate (NDLev::rev): a sweep reads what the previous one wrote and the same sigma and
 // right-hand side, and the planes that one touched last are the ones still in the 256 MB Infinity Cache (same bits: a Jacobi sweep has no order)
-template <int MODE> static void nd_launch_march(const NLev &L, const double *phi, double *out, double *nrm, int shell_later = 0, int rev = 0) {
+// pro: the coarse level whose correction the sweep adds to phi as it loads it (MODE 0, paired levels only: nd_prolong_fusable)
+template <int MODE> static void nd_launch_march(const NLev &L, const double *phi, double *out, double *nrm, int shell_later = 0, int rev = 0, const NLev *pro = nullptr) {
   const int nzp = L.n[2] + 1;
   const int tiles = ((L.n[0] + 62) / 62) * ((L.n[1] + 4) / 4);
   int kchunk = nzp;
@@ -976,9 +1047,15 @@ template <int MODE> static void nd_launch_march(const NLev &L, const double *phi
     NdPairGrid G = nd_pair_grid(L, rows, nzp, use_rem, minwg, kc_env);
     static const bool flip = !(vdn_env("VDN_ND_REV") && atoi(vdn_env("VDN_ND_REV")) == 0);
     G.rev = flip ? rev : 0;
-    hipLaunchKernelGGL((kk_nd_march_pair<MODE, 4>), dim3(G.nmain + G.gyr * G.gz), NBLK, 0, ctx().stream, L, phi, out, nd_cur_omega(), G, nrm, shell_later);
+    if (MODE == 0 && pro) {
+      const NdCoarse C{ pro->phi, pro->PX, pro->PY, pro->n[0] };
+      hipLaunchKernelGGL((kk_nd_march_pair<0, 4, 1>), dim3(G.nmain + G.gyr * G.gz), NBLK, 0, ctx().stream, L, phi, out, nd_cur_omega(), G, nrm, shell_later, C);
+      return;
+    }
+    hipLaunchKernelGGL((kk_nd_march_pair<MODE, 4>), dim3(G.nmain + G.gyr * G.gz), NBLK, 0, ctx().stream, L, phi, out, nd_cur_omega(), G, nrm, shell_later, NdCoarse{ nullptr, 0, 0, 0 });
     return;
   }
+  REQUIRE(!pro, "nodal multigrid: the prolonging sweep is the paired march's");
   hipLaunchKernelGGL(kk_nd_march<MODE>, dim3((L.n[0] + 62) / 62, (L.n[1] + 4) / 4, nch), NBLK, 0, ctx().stream, L, phi, out, nd_cur_omega(), kchunk, nrm, shell_later);
 }
 
@@ -987,7 +1064,7 @@ struct NDLev { std::vector<NBox> boxes; XPlan *halo_A = nullptr, *halo_B = nullp
                int rev = 0; /* tile order of the next march (nd_launch_march) */
                bool res_restricted = false; /* the last residual pass left the x- and z-sums of the full weighting in res (kk_nd_march_pair_rst): nd_restrict_down finishes along y */ };
 struct NDMG {
-  std::vector<NDLev> dlev; std::vector<NLev> tail; int per[3]; double *d_nrm;
+  std::vector<NDLev> dlev; std::vector<NLev> tail; int per[3]; double *d_nrm; unsigned pro_levels = 0;
   std::vector<NGBox> gb; NGBox *d_gb = nullptr;
   double *sendbuf = nullptr, *recvbuf = nullptr; size_t cnt_nodes = 0, cnt_cells = 0;
   std::vector<long> loc_off_nodes, loc_off_cells;
@@ -1181,7 +1258,8 @@ static NdOm nd_om(bool pre, int nsweeps) {
   if (g_nd_iso && pre && nsweeps == 2 && P.hg_nu1 == 2 && P.hg_omega_pre1 > 0.0 && P.hg_omega_pre2 > 0.0) { o.om1 = P.hg_omega_pre1; o.om2 = P.hg_omega_pre2; o.nsp = 2; }
   return o;
 }
-static void nd_jacobi_d(NDLev &DL, int nsweeps, bool pre = false) {
+// pro: the first sweep adds the correction of this coarse level (nd_prolong_smooth)
+static void nd_jacobi_d(NDLev &DL, int nsweeps, bool pre = false, const NLev *pro = nullptr) {
   const NdOm om = nd_om(pre, nsweeps);
   NdOmegaScope scope_;
   if (DL.single_box && DL.boxes.size() == 1 && (long)(DL.ng[0] + 1) * (DL.ng[1] + 1) * (DL.ng[2] + 1) <= SMALL_LEVEL_NODES) {
@@ -1195,7 +1273,7 @@ static void nd_jacobi_d(NDLev &DL, int nsweeps, bool pre = false) {
   for (int s = 0; s < nsweeps; s++) {
     g_nd_omega_now = om.at(s);
     const bool ov = nd_halo_begin(DL);
-    for (NBox &B : DL.boxes) nd_launch_march<0>(B.L, B.L.phi, B.L.tmp, nullptr, 0, DL.rev);
+    for (NBox &B : DL.boxes) nd_launch_march<0>(B.L, B.L.phi, B.L.tmp, nullptr, 0, DL.rev, s == 0 ? pro : nullptr);
     DL.rev ^= 1;
     if (ov) {
       nd_halo_end();
@@ -1319,6 +1397,30 @@ static void nd_prolong_up(NDMG &M, int l) {
       nd_launch_prolong(B.L, M.tail[0], B.lo[0] / 2, B.lo[1] / 2, B.lo[2] / 2);
   }
 }
+// The coarse correction and the post-smoothing of level l.  On a wide one-box level (the conditions of the fused residual + restriction, nd_residual_d) the
+// correction rides in the first sweep (kk_nd_march_pair<0, 4, 1>): no prolongation pass.  Everything else -- several boxes, periodic axes, levels narrower than
+// 127 nodes, the nested iteration's interpolation -- keeps kk_nd_prolong_m.  Same omegas, same tile-order alternation, same phi / tmp flips either way.
+static bool nd_prolong_fusable(const NDMG &M, int l) {
+  static const bool fuse = !(vdn_env("VDN_ND_PROLONG_FUSED") && atoi(vdn_env("VDN_ND_PROLONG_FUSED")) == 0);
+  static const bool paired = !(vdn_env("VDN_ND_PAIR") && atoi(vdn_env("VDN_ND_PAIR")) == 0);
+  const NDLev &DL = M.dlev[l];
+  if (!(fuse && paired && DL.single_box && DL.boxes.size() == 1 && !DL.halo_A && !DL.halo_B && !(DL.per[0] || DL.per[1] || DL.per[2]))) return false;
+  if (l + 1 < (int)M.dlev.size() ? M.dlev[l + 1].boxes.size() != 1 : M.tail.empty()) return false;
+  const NBox &B = DL.boxes[0];
+  const NLev &L = B.L, &C = l + 1 < (int)M.dlev.size() ? M.dlev[l + 1].boxes[0].L : M.tail[0];
+  for (int d = 0; d < 3; d++) if (B.lo[d] != 0 || (L.n[d] & 1) || C.n[d] != L.n[d] / 2) return false;
+  return L.n[0] >= 127;
+}
+static unsigned g_nd_pro_levels = 0;      // the levels (bit l) whose coarse correction went into a prolonging march in the last nd_solve; the testing build hands it out (runtime.hip)
+unsigned nd_last_prolong_levels() { return g_nd_pro_levels; }
+static void nd_prolong_smooth(NDMG &M, int l) {
+  const int nu2 = ctx().prm.hg_nu2;
+  if (nu2 < 1 || !nd_prolong_fusable(M, l)) { nd_prolong_up(M, l); nd_jacobi_d(M.dlev[l], nu2); return; }
+  if (l + 1 < (int)M.dlev.size()) nd_halo_phi(M.dlev[l + 1]); else nd_fill_nodes(M.tail[0], M.tail[0].phi);      // the coarse level's ghost nodes, as nd_prolong_up
+  const NLev C = l + 1 < (int)M.dlev.size() ? M.dlev[l + 1].boxes[0].L : M.tail[0];
+  M.pro_levels |= 1u << l;                 // (kept in M: a replayed cycle installs the state its recording left, this bit included)
+  nd_jacobi_d(M.dlev[l], nu2, false, &C);
+}
 static int nd_bottom_sweeps_global(const NDLev &DL) {
   const int N = std::max(DL.ng[0], std::max(DL.ng[1], DL.ng[2]));
   return std::max(ctx().prm.hg_nub, 2 * N * N);
@@ -1372,8 +1474,7 @@ static void nd_vcycle_d(NDMG &M, int l) {
   nd_residual_d(M, DL, false);
   nd_restrict_down(M, l);
   if (last) nd_vcycle_t(M, 0); else nd_vcycle_d(M, l + 1);
-  nd_prolong_up(M, l);
-  nd_jacobi_d(DL, P.hg_nu2);
+  nd_prolong_smooth(M, l);
 }
 // ---- nested iteration for the initial guess (round 3; vdn_params.hg_fmg; the algorithm is stated with vo_nd_solve in oracle/vo_hgproject.c) ----
 // Only for a solve that starts from phi = 0.  Levels are counted globally: the distributed ones, then the replicated tail.  The right-hand side
@@ -1505,6 +1606,7 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
   const bool rebuild = !(keep && keep->built);
   if (rebuild) nd_build(M, coeffs, dx, bc);          // (of `coeffs` only the layout, the level and the boxes are used)
   NDLev &D0 = M.dlev[0];
+  M.pro_levels = 0; g_nd_pro_levels = 0;
   if (rebuild) {
   // sigma: level 0 from the (ghost-filled) coeffs multifab; coarser distributed levels by averaging + halo exchange
   for (size_t b = 0; b < D0.boxes.size(); b++) {
@@ -1578,8 +1680,7 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
       nd_residual_d(M, D, false);
       nd_restrict_down(M, 0);
       if (M.dlev.size() > 1) nd_vcycle_d(M, 1); else nd_vcycle_t(M, 0);
-      nd_prolong_up(M, 0);
-      nd_jacobi_d(D, P.hg_nu2);
+      nd_prolong_smooth(M, 0);
     });
     cyc++;
   }
@@ -1602,8 +1703,7 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
           NDLev &D = M.dlev[0];
           nd_restrict_down(M, 0);
           if (M.dlev.size() > 1) nd_vcycle_d(M, 1); else nd_vcycle_t(M, 0);
-          nd_prolong_up(M, 0);
-          nd_jacobi_d(D, P.hg_nu2);
+          nd_prolong_smooth(M, 0);
           nd_jacobi_d(D, P.hg_nu1, true);
           nd_residual_d(M, D, true, false);
           norm_hist_push(M.d_nrm);
@@ -1631,8 +1731,7 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
       NDLev &D = M.dlev[0];
       nd_restrict_down(M, 0);
       if (M.dlev.size() > 1) nd_vcycle_d(M, 1); else nd_vcycle_t(M, 0);
-      nd_prolong_up(M, 0);
-      nd_jacobi_d(D, P.hg_nu2);
+      nd_prolong_smooth(M, 0);
       nd_jacobi_d(D, P.hg_nu1, true);
       nd_residual_d(M, D, true);
     });
@@ -1650,6 +1749,7 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
     hipLaunchKernelGGL(kk_nd_store, ng3(L0.n[0] + 3, L0.n[1] + 3, L0.n[2] + 3), NBLK, 0, st, L0, phi->fabs[b], bx.lo[0], bx.lo[1], bx.lo[2]);
   }
   if (cycles) *cycles = cyc; if (res0) *res0 = bnorm; if (res) *res = rn;
+  g_nd_pro_levels = M.pro_levels;
   if (conv && fast && !fixed_cycles && !single && cyc >= 1) mg_predict_set(1, gn, cyc);
   if (!keep && !fast) arena_release(mark);  // with `keep` / `fast` the hierarchy stays in the caller's arena scope
   return conv ? 0 : 1;

@@ -240,6 +240,7 @@ static const EnvSwitch g_switches[] = {
   { "VDN_ND_PAIR", "0: one node per lane in the nodal march instead of the pair form" },
   { "VDN_ND_LEAN", "0: whole-array zero fills of the big nodal levels instead of shell-only" },
   { "VDN_ND_RESTRICT_FUSED", "0: nodal residual and full weighting as two passes" },
+  { "VDN_ND_PROLONG_FUSED", "0: nodal prolongation as a pass of its own instead of inside the first post-smoothing march" },
   { "VDN_NDF_SEGW", "0: the marches of the composite nodal solve use power-of-two lane segments per node row only" },
   { "VDN_NDF_PAIR", "0: one node per lane in the box-batched nodal march of the composite solve" },
   { "VDN_NDM_IFACE_FACES", "0: interface interpolation of the composite nodal solve over whole boxes instead of box faces" },
@@ -295,6 +296,11 @@ static void env_warn_unknown() {
 #endif
   }
 }
+#ifdef VDN_TESTING_BUILD
+// testing build only (tests/test_nd_prolong_fused_gpu.py): which levels of the last nodal solve took the prolonging march (mg_nd.hip)
+unsigned nd_last_prolong_levels();
+extern "C" unsigned vdn_nd_prolong_fused_levels(void) { return nd_last_prolong_levels(); }
+#endif
 extern "C" const char *vdn_debug_switches(void) {
   static std::string out;
 #ifndef VDN_TESTING_BUILD
