@@ -290,6 +290,31 @@ int vdn_make_new_grids(const vdn_multifab *s, int lev1, int buf_wid, int nest, d
 int vdn_make_vorticity(vdn_multifab *vort, int comp, vdn_multifab *u, const double *dx /*[dm]*/, const vdn_bc_tower *bct);
 int vdn_make_magvel(vdn_multifab *magvel, int comp, vdn_multifab *u);
 
+/* ---- plot files and checkpoints (FBoxLib's fabio_module and the reference's checkpoint_module) ------------------------------------------------------
+ * The files are the ones varden_amd/plotfile.py defines (Header, Level_NN/Cell_H with es27.17e3 numbers, Level_NN/Cell_D_00000 with a FAB line in front of
+ * every fab's doubles), byte for byte.  The valid points of every fab are packed on the device into a staging buffer of `staging_bytes` (<= 0: 256 MB; neither
+ * the device nor the pinned host buffer is made larger than the largest level), copied to the host and written, range by range; Cell_H's per-fab minima and
+ * maxima are exact and come out of the same pass (-0 sorts below +0).  ONE RANK: with nranks > 1 the writers and the reader fail ("several ranks: use the
+ * Python writer").  Every failed fopen / fwrite / short read / foreign FAB line fails the call with the path and strerror in vdn_last_error().
+ * vdn_fabio_ml_multifab_info, _boxes and vdn_checkpoint_info only parse text: they need neither vdn_init nor a GPU. */
+/* fabio_ml_multifab_write_d as src/varden.f90:568-573 and src/checkpoint.f90:45-48 call it: mfs[nlev] share components and nodal flags; rr[nlev-1] */
+int vdn_fabio_ml_multifab_write_d(const char *dirname, int nlev, vdn_multifab *const *mfs, const int *rr,
+        const char *const *names, const vdn_box *pd0, const double *prob_lo, const double *prob_hi,
+        double time, const double *dx0, long staging_bytes);   /* NULL names, pd0, prob_lo, prob_hi, dx0: the defaults plotfile.write_ml_multifab takes */
+/* what fabio_ml_multifab_read_d (src/checkpoint.f90:116-122) learns from the files before it builds its layout: levels, dimension, components, nodal flags,
+ * boxes per level (nboxes[nlev], at most 4), ratios (rr[nlev-1]), time.  Any output pointer may be NULL */
+int vdn_fabio_ml_multifab_info (const char *dirname, int *nlev, int *dm, int *ncomp, int nodal[3], int *nboxes, int *rr, double *time);
+/* the CELL boxes of one level, in the file's order (the boxarray fabio_ml_multifab_read_d builds its layout from) */
+int vdn_fabio_ml_multifab_boxes(const char *dirname, int lev, vdn_box *boxes, int maxboxes);
+/* the data part of fabio_ml_multifab_read_d (src/checkpoint.f90:116-122): mfs[lev] is built on the file's box list, in the file's order, with the file's nodal
+ * flags and at least its components; valid points are overwritten, ghost cells are not touched.  A mismatch fails naming the level and the box */
+int vdn_fabio_ml_multifab_read_d(const char *dirname, int nlev, vdn_multifab *const *mfs, long staging_bytes);
+/* checkpoint_write / checkpoint_read, src/checkpoint.f90:14-145: State, Pressure, Header (&CHKPOINT time, dt, nlevs; then the ratios) */
+int vdn_checkpoint_write(const char *dirname, int nlev, vdn_multifab *const *state, vdn_multifab *const *pressure,
+        const int *rr, double time, double dt, long staging_bytes);
+/* the namelist read of checkpoint_read (src/checkpoint.f90:100-112); State and Pressure are then read with vdn_fabio_ml_multifab_info / _boxes / _read_d */
+int vdn_checkpoint_info (const char *dirname, int *nlev, double *time, double *dt, int *rr);
+
 /* per-phase wall seconds of the last vdn_advance_timestep (reference prints them,
  * advance_timestep.f90:159-166): [0]=scalar [1]=velocity [2]=MAC [3]=HG [4]=total              */
 int  vdn_last_step_timing(double *sec5);

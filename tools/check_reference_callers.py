@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Compile the reference's OWN callers of the hot path against the product's Fortran surface -- syntax and semantics only, in the build container.
 
-    python tools/check_reference_callers.py [--out profiles/r06_reference_callers_syntax.txt]
+    python tools/check_reference_callers.py [--out profiles/reference_callers_syntax_io.txt]
 
 `flang -fsyntax-only -I varden_amd/fortran <file>` on files of /root/reference/src READ IN PLACE (nothing is copied; no object or module file of the
 reference is written -- with -fsyntax-only flang emits none, and the working directory is a scratch directory): src/advance_timestep.f90's callers
@@ -24,7 +24,7 @@ FDIR = os.path.join(ROOT, "varden_amd", "fortran")
 # the callers of the boundary (advance_timestep, estdt, hgproject, the containers) and the driver above them; advance_timestep.f90 itself is the routine the
 # library REPLACES -- it is listed to show which of its inner modules the boundary hides
 # (estdt.f90, makevort.f90, tag_boxes.f90, multifab_physbc.f90 ... sit BEHIND the boundary: their loops over host `dataptr` arrays are what the HIP kernels replace)
-FILES = ["main.f90", "varden.f90", "initialize.f90", "regrid.f90", "advance_timestep.f90"]
+FILES = ["main.f90", "varden.f90", "initialize.f90", "regrid.f90", "advance_timestep.f90", "checkpoint.f90", "restart.f90"]
 
 
 def flang():
@@ -37,7 +37,7 @@ def flang():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_reference_callers_syntax.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reference_callers_syntax_io.txt"))
     args = ap.parse_args()
     fc = flang()
     if not fc or not os.path.isdir(REF):

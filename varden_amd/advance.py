@@ -197,3 +197,60 @@ def ml_nodal_prolongation(fine, crse):
 def copy_layouts(dst, dcomp, src, scomp, nc):
     """multifab_copy_c between two multifabs of one level whose box lists differ (src/regrid.f90:333-337)"""
     check(capi.load().vdn_multifab_copy_layouts(dst.h, dcomp, src.h, scomp, nc))
+
+
+# ---- plot files and checkpoints inside the library (csrc/fabio.hip; one rank) ------------------------------------------------------------
+def _cbox(lo, hi):
+    b = capi.Box()
+    for d in range(3):
+        b.lo[d], b.hi[d] = int(lo[d]), int(hi[d])
+    return b
+
+
+def _dv(v):
+    return None if v is None else (C.c_double * max(3, len(v)))(*[float(x) for x in v])
+
+
+def _rr(rr):
+    return (C.c_int * max(1, len(rr)))(*[int(r) for r in rr])
+
+
+def fabio_ml_multifab_write_d(dirname, mfs, rr, names=None, pd=None, prob_lo=None, prob_hi=None, time=0.0, dx=None, staging_bytes=0):
+    """fabio_ml_multifab_write_d(mfs, rr, dirname, names, bounding_box, prob_lo, prob_hi, time, dx) of src/varden.f90:568-573: the files of
+    plotfile.write_ml_multifab, byte for byte; mfs: one multifab per level, rr: one ratio per pair of levels, pd: (lo, hi) of the level-0 domain"""
+    nm = None if names is None else (C.c_char_p * len(names))(*[str(n).encode() for n in names])
+    check(capi.load().vdn_fabio_ml_multifab_write_d(str(dirname).encode(), len(mfs), handle_array(mfs), _rr(rr), nm,
+                                                    None if pd is None else C.byref(_cbox(*pd)), _dv(prob_lo), _dv(prob_hi), float(time), _dv(dx), int(staging_bytes)))
+
+
+def fabio_ml_multifab_info(dirname):
+    """levels, dimension, components, nodal flags, boxes per level, ratios and time of a hierarchy on disk (text only: needs no GPU)"""
+    nl, dm, nc, t = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+    nodal, nb, rr = (C.c_int * 3)(), (C.c_int * 4)(), (C.c_int * 4)()
+    check(capi.load().vdn_fabio_ml_multifab_info(str(dirname).encode(), C.byref(nl), C.byref(dm), C.byref(nc), nodal, nb, rr, C.byref(t)))
+    return dict(nlevs=nl.value, dm=dm.value, ncomp=nc.value, nodal=tuple(nodal), nboxes=list(nb)[:nl.value], rr=list(rr)[:nl.value - 1], time=t.value)
+
+
+def fabio_ml_multifab_boxes(dirname, lev, nboxes):
+    """the cell boxes [(lo, hi)] of one level of a hierarchy on disk, in the file's order (text only)"""
+    arr = (capi.Box * max(1, int(nboxes)))()
+    check(capi.load().vdn_fabio_ml_multifab_boxes(str(dirname).encode(), int(lev), arr, int(nboxes)))
+    return [(tuple(arr[i].lo), tuple(arr[i].hi)) for i in range(int(nboxes))]
+
+
+def fabio_ml_multifab_read_d(dirname, mfs, staging_bytes=0):
+    """the data of a hierarchy on disk into multifabs built on its box lists (valid points; ghost cells keep their values)"""
+    check(capi.load().vdn_fabio_ml_multifab_read_d(str(dirname).encode(), len(mfs), handle_array(mfs), int(staging_bytes)))
+
+
+def checkpoint_write(dirname, state, pressure, rr, time, dt, staging_bytes=0):
+    """checkpoint_write(dirname, mfs, mfs_nodal, rrs, time, dt) of src/checkpoint.f90:14-86"""
+    check(capi.load().vdn_checkpoint_write(str(dirname).encode(), len(state), handle_array(state), handle_array(pressure), _rr(rr), float(time), float(dt),
+                                           int(staging_bytes)))
+
+
+def checkpoint_info(dirname):
+    """the namelist of a checkpoint's Header (src/checkpoint.f90:100-112) and the ratios behind it (text only)"""
+    nl, t, dt, rr = C.c_int(), C.c_double(), C.c_double(), (C.c_int * 4)()
+    check(capi.load().vdn_checkpoint_info(str(dirname).encode(), C.byref(nl), C.byref(t), C.byref(dt), rr))
+    return dict(nlevs=nl.value, time=t.value, dt=dt.value, rr=list(rr)[:nl.value - 1])

@@ -126,6 +126,12 @@ SIGNATURES = {
     "vdn_multifab_copy_layouts": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_int]),
     "vdn_tag_boxes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_ubyte)]),
     "vdn_make_new_grids": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Box), _PI, C.POINTER(C.c_long)]),
+    "vdn_fabio_ml_multifab_write_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PI, C.POINTER(C.c_char_p), C.POINTER(Box), _PD, _PD, C.c_double, _PD, C.c_long]),
+    "vdn_fabio_ml_multifab_info": (C.c_int, [C.c_char_p, _PI, _PI, _PI, _PI, _PI, _PI, _PD]),
+    "vdn_fabio_ml_multifab_boxes": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(Box), C.c_int]),
+    "vdn_fabio_ml_multifab_read_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, C.c_long]),
+    "vdn_checkpoint_write": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PVP, _PI, C.c_double, C.c_double, C.c_long]),
+    "vdn_checkpoint_info": (C.c_int, [C.c_char_p, _PI, _PD, _PD, _PI]),
     "vdn_last_step_timing": (C.c_int, [_PD]),
     "vdn_last_solver_stats": (C.c_int, [C.c_int, _PI, _PD, _PD]),
     "vdn_last_mac_level_form": (C.c_int, []),

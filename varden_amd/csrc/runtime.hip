@@ -488,7 +488,7 @@ extern "C" int vdn_finalize(void) {
   VDN_TRY
   VdnCtx &c = g_ctx;
   kept_purge(0);
-  arena_destroy(); field_pool_release();
+  arena_destroy(); field_pool_release(); fabio_release();
   graph_cache_clear();
   if (c.d_hist) { HIPCHK(hipFree(c.d_hist)); c.d_hist = nullptr; }
   if (c.d_scal) { HIPCHK(hipFree(c.d_scal)); c.d_scal = nullptr; HIPCHK(hipHostFree(c.h_scal)); c.h_scal = nullptr; c.h_scal_dev = nullptr; }

@@ -196,6 +196,7 @@ void  arena_release(size_t mark);
 vdn_multifab *mf_temp(const vdn_layout *la, int lev, int nc, int ng, int face_dir /* -1 cell, 0..2 face, 3 nodal */,
                       bool fill, double val);
 void mf_temp_free(vdn_multifab *mf);
+void fabio_release();      // fabio.hip: frees the pinned staging buffer of the file writers (vdn_finalize)
 
 // exchange.hip: ghost exchange plans and the RCCL transport
 struct XBoxInfo { FV fv; int vlo[3], vhi[3]; int owner; };      // valid POINT range (incl. nodal points); fv only if local

@@ -69,6 +69,7 @@ module varden_amd
   public :: advance_timestep, estdt, hgproject, macproject
   public :: ml_cc_restriction, ml_edge_restriction, multifab_fill_ghost_cells, create_umac_grown, ml_restrict_and_fill
   public :: fillpatch, ml_nodal_prolongation, multifab_copy_layouts, make_new_grids, make_vorticity, make_magvel
+  public :: fabio_ml_multifab_write_d, fabio_ml_multifab_info, fabio_ml_multifab_boxes, fabio_ml_multifab_read_d, checkpoint_write, checkpoint_info
 
   interface
      subroutine vdn_params_default(p) bind(C, name="vdn_params_default")
@@ -274,6 +275,52 @@ module varden_amd
        type(vdn_box), intent(out) :: boxes_out(*)
        integer(c_int), intent(out) :: nboxes_out
        integer(c_long), intent(out) :: ntagged
+     end function
+     ! plot files and checkpoints inside the library (include/varden_amd.h; csrc/fabio.hip); optional C arguments travel as addresses (c_null_ptr: the default)
+     integer(c_int) function vdn_fabio_ml_multifab_write_d(dirname, nlev, mfs, rr, names, pd0, prob_lo, prob_hi, time, dx0, staging_bytes) &
+                                                           bind(C, name="vdn_fabio_ml_multifab_write_d")
+       import :: c_int, c_ptr, c_char, c_double, c_long
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), value :: nlev
+       type(c_ptr), intent(in) :: mfs(*)
+       integer(c_int), intent(in) :: rr(*)
+       type(c_ptr), value :: names, pd0, prob_lo, prob_hi, dx0
+       real(c_double), value :: time
+       integer(c_long), value :: staging_bytes
+     end function
+     integer(c_int) function vdn_fabio_ml_multifab_info(dirname, nlev, dm, ncomp, nodal, nboxes, rr, time) bind(C, name="vdn_fabio_ml_multifab_info")
+       import :: c_int, c_char, c_double
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), intent(out) :: nlev, dm, ncomp, nodal(3), nboxes(*), rr(*)
+       real(c_double), intent(out) :: time
+     end function
+     integer(c_int) function vdn_fabio_ml_multifab_boxes(dirname, lev, boxes, maxboxes) bind(C, name="vdn_fabio_ml_multifab_boxes")
+       import :: c_int, c_char, vdn_box
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), value :: lev, maxboxes
+       type(vdn_box), intent(out) :: boxes(*)
+     end function
+     integer(c_int) function vdn_fabio_ml_multifab_read_d(dirname, nlev, mfs, staging_bytes) bind(C, name="vdn_fabio_ml_multifab_read_d")
+       import :: c_int, c_ptr, c_char, c_long
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), value :: nlev
+       type(c_ptr), intent(in) :: mfs(*)
+       integer(c_long), value :: staging_bytes
+     end function
+     integer(c_int) function vdn_checkpoint_write(dirname, nlev, state, pressure, rr, time, dt, staging_bytes) bind(C, name="vdn_checkpoint_write")
+       import :: c_int, c_ptr, c_char, c_double, c_long
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), value :: nlev
+       type(c_ptr), intent(in) :: state(*), pressure(*)
+       integer(c_int), intent(in) :: rr(*)
+       real(c_double), value :: time, dt
+       integer(c_long), value :: staging_bytes
+     end function
+     integer(c_int) function vdn_checkpoint_info(dirname, nlev, time, dt, rr) bind(C, name="vdn_checkpoint_info")
+       import :: c_int, c_char, c_double
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), intent(out) :: nlev, rr(*)
+       real(c_double), intent(out) :: time, dt
      end function
      integer(c_size_t) function c_strlen(s) bind(C, name="strlen")
        import :: c_ptr, c_size_t
@@ -644,6 +691,115 @@ contains
     nboxes = nb
     new_grid = nb > 0
   end subroutine make_new_grids
+
+  ! ---- plot files and checkpoints (FBoxLib's fabio_module, src/checkpoint.f90): written and read inside the library, one rank ------------------------
+  ! fabio_ml_multifab_write_d(mfs, rrs, dirname, names, bounding_box, prob_lo, prob_hi, time, dx)   (src/varden.f90:568-573, src/checkpoint.f90:45-48);
+  ! rr: one ratio per pair of levels; the optional arguments default as in fabio (names Var-i, the bounding box of level 1, the unit mesh)
+  subroutine fabio_ml_multifab_write_d(mfs, rr, dirname, names, bounding_box, prob_lo, prob_hi, time, dx, staging_bytes)
+    type(multifab)  , intent(in) :: mfs(:)
+    integer         , intent(in) :: rr(:)
+    character(len=*), intent(in) :: dirname
+    character(len=*), intent(in), optional :: names(:)
+    type(vdn_box)   , intent(in), optional :: bounding_box
+    real(dp_t)      , intent(in), optional :: prob_lo(:), prob_hi(:), time, dx(:)
+    integer(c_long) , intent(in), optional :: staging_bytes
+    character(kind=c_char), allocatable, target :: cbuf(:,:)
+    type(c_ptr), allocatable, target :: cp(:)
+    type(vdn_box), target :: pd
+    real(c_double), target :: plo(3), phi(3), dxc(3)
+    real(c_double) :: t
+    integer(c_int) :: rrc(max(1, size(rr)))
+    integer(c_long) :: sb
+    type(c_ptr) :: a_names, a_pd, a_lo, a_hi, a_dx
+    integer :: i, j, n
+    rrc = 2; rrc(1:size(rr)) = rr
+    a_names = c_null_ptr; a_pd = c_null_ptr; a_lo = c_null_ptr; a_hi = c_null_ptr; a_dx = c_null_ptr
+    if (present(names)) then
+       allocate(cbuf(len(names) + 1, size(names)), cp(size(names)))
+       do i = 1, size(names)
+          n = len_trim(names(i))
+          do j = 1, n
+             cbuf(j, i) = names(i)(j:j)
+          end do
+          cbuf(n + 1, i) = c_null_char
+          cp(i) = c_loc(cbuf(1, i))
+       end do
+       a_names = c_loc(cp(1))
+    end if
+    if (present(bounding_box)) then
+       pd = bounding_box; a_pd = c_loc(pd)
+    end if
+    plo = 0.d0; phi = 1.d0; dxc = 1.d0
+    if (present(prob_lo)) then
+       plo(1:size(prob_lo)) = prob_lo; a_lo = c_loc(plo(1))
+    end if
+    if (present(prob_hi)) then
+       phi(1:size(prob_hi)) = prob_hi; a_hi = c_loc(phi(1))
+    end if
+    if (present(dx)) then
+       dxc(1:size(dx)) = dx; a_dx = c_loc(dxc(1))
+    end if
+    t = 0.d0; if (present(time)) t = time
+    sb = 0; if (present(staging_bytes)) sb = staging_bytes
+    call chk(vdn_fabio_ml_multifab_write_d(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), rrc, a_names, a_pd, a_lo, a_hi, t, a_dx, sb), &
+             'fabio_ml_multifab_write_d')
+  end subroutine fabio_ml_multifab_write_d
+
+  ! what fabio_ml_multifab_read_d learns from the files before it builds its layout (text only: needs no GPU); nboxes(:) and rr(:) hold 4 entries at least
+  subroutine fabio_ml_multifab_info(dirname, nlev, dm, ncomp, nodal, nboxes, rr, time)
+    character(len=*), intent(in) :: dirname
+    integer, intent(out) :: nlev, dm, ncomp, nboxes(:), rr(:)
+    logical, intent(out) :: nodal(3)
+    real(dp_t), intent(out) :: time
+    integer(c_int) :: nl, d, nc, nd(3), nb(4), r(4)
+    nb = 0; r = 2
+    call chk(vdn_fabio_ml_multifab_info(trim(dirname) // c_null_char, nl, d, nc, nd, nb, r, time), 'fabio_ml_multifab_info')
+    nlev = nl; dm = d; ncomp = nc; nodal = nd /= 0
+    nboxes = 0; nboxes(1:nl) = nb(1:nl)
+    rr = 2; if (nl > 1) rr(1:nl - 1) = r(1:nl - 1)
+  end subroutine fabio_ml_multifab_info
+
+  ! the cell boxes of level lev (1-based) of a hierarchy on disk, in the file's order
+  subroutine fabio_ml_multifab_boxes(dirname, lev, boxes)
+    character(len=*), intent(in) :: dirname
+    integer, intent(in) :: lev
+    type(vdn_box), intent(out) :: boxes(:)
+    call chk(vdn_fabio_ml_multifab_boxes(trim(dirname) // c_null_char, int(lev - 1, c_int), boxes, int(size(boxes), c_int)), 'fabio_ml_multifab_boxes')
+  end subroutine fabio_ml_multifab_boxes
+
+  ! the data of fabio_ml_multifab_read_d (src/checkpoint.f90:130,134) into multifabs built on the file's box lists: valid points only
+  subroutine fabio_ml_multifab_read_d(mfs, dirname, staging_bytes)
+    type(multifab)  , intent(inout) :: mfs(:)
+    character(len=*), intent(in) :: dirname
+    integer(c_long) , intent(in), optional :: staging_bytes
+    integer(c_long) :: sb
+    sb = 0; if (present(staging_bytes)) sb = staging_bytes
+    call chk(vdn_fabio_ml_multifab_read_d(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), sb), 'fabio_ml_multifab_read_d')
+  end subroutine fabio_ml_multifab_read_d
+
+  ! checkpoint_write(nlevs, dirname, mfs, mfs_nodal, rrs, time, dt)   (src/checkpoint.f90:14-83): State, Pressure and the Header namelist
+  subroutine checkpoint_write(dirname, mfs, mfs_nodal, rr, time, dt)
+    character(len=*), intent(in) :: dirname
+    type(multifab)  , intent(in) :: mfs(:), mfs_nodal(:)
+    integer         , intent(in) :: rr(:)
+    real(dp_t)      , intent(in) :: time, dt
+    integer(c_int) :: rrc(max(1, size(rr)))
+    rrc = 2; rrc(1:size(rr)) = rr
+    call chk(vdn_checkpoint_write(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), handles(mfs_nodal), rrc, time, dt, 0_c_long), &
+             'checkpoint_write')
+  end subroutine checkpoint_write
+
+  ! the Header of checkpoint_read (src/checkpoint.f90:112-126): nlevs, time, dt and the ratios (rr(:) holds 4 entries at least)
+  subroutine checkpoint_info(dirname, nlev, time, dt, rr)
+    character(len=*), intent(in) :: dirname
+    integer, intent(out) :: nlev, rr(:)
+    real(dp_t), intent(out) :: time, dt
+    integer(c_int) :: nl, r(4)
+    r = 2
+    call chk(vdn_checkpoint_info(trim(dirname) // c_null_char, nl, time, dt, r), 'checkpoint_info')
+    nlev = nl
+    rr = 2; if (nl > 1) rr(1:nl - 1) = r(1:nl - 1)
+  end subroutine checkpoint_info
 
   function handles(mfs) result(h)
     type(multifab), intent(in) :: mfs(:)

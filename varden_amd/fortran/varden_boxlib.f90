@@ -17,7 +17,7 @@
 ! (tests/fortran/varden_loop.f90 is such a file: the time-loop body of src/varden.f90 as the reference spells it).  Every routine forwards to module varden_amd
 ! (varden_amd_mod.f90), i.e. to the C-ABI of include/varden_amd.h; all multifab data lives in HBM.
 !
-! What is NOT here: FBoxLib's host-side data access (dataptr returns a device address, see varden_amd_mod.f90), parallel I/O, fabio, the box calculus
+! What is NOT here: FBoxLib's host-side data access (dataptr returns a device address, see varden_amd_mod.f90), parallel I/O (fabio_module: varden_boxlib_ext.f90, one rank), the box calculus
 ! beyond what the hot path's callers use.  dm = 3.
 
 module bl_types

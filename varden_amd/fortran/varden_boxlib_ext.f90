@@ -13,9 +13,11 @@
 !   bl_IO_module        unit_new
 !   vort_module         make_vorticity(vort, comp, u, dx, bc) / make_magvel(magvel, comp, u)   (src/makevort.f90:16,58)
 !   fillpatch_module, ml_prolongation_module   fillpatch(fine, crse, ...) / ml_nodal_prolongation(fine, crse, ir)   (src/regrid.f90:279-280, 317-344)
+!   fabio_module        fabio_mkdir / fabio_ml_multifab_write_d(mfs, rrs, dirname[, names, bounding_box, prob_lo, prob_hi, time, dx]) / fabio_ml_multifab_read_d(mfs,
+!                       dirname)   (src/varden.f90:568-573, src/checkpoint.f90:40-48, 130-134): the library packs and writes (csrc/fabio.hip); one rank
 ! probin_module (varden_boxlib.f90) carries every entry of src/_parameters with its default, the &PROBIN namelist, probin_init and probin_close.
-! NOT here (listed by the report as the maintainer's remaining work): FBoxLib's host-side box calculus and I/O (list_box_module, box_util_module, fabio_module,
-! plotfile_module, checkpoint / restart, bl_mem_stat, bl_timer), layouts built one level at a time (layout_build_ba, make_new_grids_module, tag_boxes_module --
+! NOT here (listed by the report as the maintainer's remaining work): FBoxLib's host-side box calculus (list_box_module, box_util_module), plotfile_module,
+! bl_timer, layouts built one level at a time (layout_build_ba, make_new_grids_module, tag_boxes_module --
 ! the library builds whole hierarchies: vdn_make_new_grids), and the modules INSIDE advance_timestep (pre_advance_module, scalar_advance_module, ...): the
 ! boundary is advance_timestep itself, their kernels are the vdn_k_* hooks of include/varden_amd.h.
 
@@ -108,3 +110,105 @@ contains
     call vamd_nodal_prolongation(fine%v, crse%v)
   end subroutine ml_nodal_prolongation
 end module ml_prolongation_module
+
+module fabio_module
+  use iso_c_binding
+  use bl_types
+  use box_module
+  use ml_boxarray_module
+  use ml_layout_module
+  use multifab_module
+  use varden_amd, only: vamd_multifab => multifab, vamd_write_d => fabio_ml_multifab_write_d, vamd_info => fabio_ml_multifab_info, &
+                        vamd_boxes => fabio_ml_multifab_boxes, vamd_read_d => fabio_ml_multifab_read_d, vdn_box
+  implicit none
+  private
+  public :: fabio_mkdir, fabio_ml_multifab_write_d, fabio_ml_multifab_read_d
+  ! the hierarchies fabio_ml_multifab_read_d built its multifabs on: they live as long as the program (FBoxLib's read leaves its layouts to the caller's multifabs)
+  type(ml_layout), save, target :: read_mla(16)
+  integer, save :: nread = 0
+  interface
+     integer(c_int) function c_mkdir(path, mode) bind(C, name="mkdir")
+       import :: c_int, c_char
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_int), value :: mode
+     end function c_mkdir
+  end interface
+contains
+  ! fabio_mkdir(dirname)   (src/checkpoint.f90:40); an existing directory is kept
+  subroutine fabio_mkdir(dirname, stat)
+    character(len=*), intent(in) :: dirname
+    integer, intent(out), optional :: stat
+    integer(c_int) :: rc
+    rc = c_mkdir(trim(dirname) // c_null_char, int(o'777', c_int))
+    if (present(stat)) stat = 0
+  end subroutine fabio_mkdir
+
+  ! fabio_ml_multifab_write_d(mfs, rrs, dirname, names, bounding_box, prob_lo, prob_hi, time, dx)   (src/varden.f90:572, src/checkpoint.f90:45)
+  subroutine fabio_ml_multifab_write_d(mfs, rrs, dirname, names, bounding_box, prob_lo, prob_hi, time, dx)
+    type(multifab)  , intent(in) :: mfs(:)
+    integer         , intent(in) :: rrs(:)
+    character(len=*), intent(in) :: dirname
+    character(len=*), intent(in), optional :: names(:)
+    type(box)       , intent(in), optional :: bounding_box
+    real(dp_t)      , intent(in), optional :: prob_lo(:), prob_hi(:), time, dx(:)
+    type(vamd_multifab) :: v(size(mfs))
+    type(vdn_box) :: pd
+    integer :: n, nr
+    do n = 1, size(mfs)
+       v(n) = mfs(n)%v
+    end do
+    nr = min(size(rrs), size(mfs) - 1)
+    if (present(bounding_box)) then
+       pd%lo = 0; pd%hi = 0
+       pd%lo(1:bounding_box%dim) = bounding_box%lo(1:bounding_box%dim); pd%hi(1:bounding_box%dim) = bounding_box%hi(1:bounding_box%dim)
+       call vamd_write_d(v, rrs(1:nr), dirname, names, pd, prob_lo, prob_hi, time, dx)
+    else
+       call vamd_write_d(v, rrs(1:nr), dirname, names, prob_lo=prob_lo, prob_hi=prob_hi, time=time, dx=dx)
+    end if
+  end subroutine fabio_ml_multifab_write_d
+
+  ! fabio_ml_multifab_read_d(mfs, dirname)   (src/checkpoint.f90:130,134): allocates mfs(1:nlevs), builds the layout from the file's box lists (problem domain:
+  ! the bounding box of level 1, refined) and the multifabs with the file's components and nodal flags and no ghost cells, then reads the data
+  subroutine fabio_ml_multifab_read_d(mfs, dirname)
+    type(multifab), pointer :: mfs(:)
+    character(len=*), intent(in) :: dirname
+    type(ml_boxarray) :: mba
+    type(vdn_box), allocatable :: vb(:)
+    type(box), allocatable :: bxs(:)
+    type(vamd_multifab), allocatable :: v(:)
+    integer :: nlev, dm, nc, nb(4), rr(4), n, i
+    logical :: nodal(3)
+    real(dp_t) :: time
+    call vamd_info(dirname, nlev, dm, nc, nodal, nb, rr, time)
+    if (nread >= size(read_mla)) error stop 'fabio_ml_multifab_read_d: more than 16 hierarchies read in one run'
+    nread = nread + 1
+    call ml_boxarray_build_n(mba, nlev, dm)
+    do n = 1, nlev
+       allocate(vb(nb(n)), bxs(nb(n)))
+       call vamd_boxes(dirname, n, vb)
+       do i = 1, nb(n)
+          bxs(i)%dim = dm; bxs(i)%lo = vb(i)%lo; bxs(i)%hi = vb(i)%hi
+       end do
+       call boxarray_build_v(mba%bas(n), bxs)
+       if (n == 1) then
+          mba%pd(1)%dim = dm
+          do i = 1, 3
+             mba%pd(1)%lo(i) = minval(vb%lo(i)); mba%pd(1)%hi(i) = maxval(vb%hi(i))
+          end do
+       else
+          mba%rr(n - 1, :) = rr(n - 1)
+          mba%pd(n) = mba%pd(n - 1)
+          mba%pd(n)%lo(1:dm) = mba%pd(n - 1)%lo(1:dm) * rr(n - 1); mba%pd(n)%hi(1:dm) = (mba%pd(n - 1)%hi(1:dm) + 1) * rr(n - 1) - 1
+       end if
+       deallocate(vb, bxs)
+    end do
+    call ml_layout_build(read_mla(nread), mba)
+    call destroy(mba)
+    allocate(mfs(nlev), v(nlev))
+    do n = 1, nlev
+       call multifab_build(mfs(n), read_mla(nread)%la(n), nc, 0, nodal(1:dm))
+       v(n) = mfs(n)%v
+    end do
+    call vamd_read_d(v, dirname)
+  end subroutine fabio_ml_multifab_read_d
+end module fabio_module

@@ -7,8 +7,10 @@
 ! copies of the old data --, ghost fills, estdt over the levels, advance_timestep, new -> old) until max_step or stop_time.
 ! Scope: dim_in = 3, a cubic unit domain (every 3-D input of exec/test), prob_type 1 .. 4 (src/initdata.f90:190-306), one rank; dim_in = 2 (the four 2-D inputs of
 ! exec/test, all adaptive): the problem runs as its z-uniform copy -- n_cellx x n_celly x 16 cells of level 0, periodic along z, gravity along y, initdata_2d on every
-! plane, velpred_2d's outlet rule (vdn_set_extruded_2d; DESIGN.md section 13): plane k = 0 is the 2-D answer.  Plot and checkpoint files stay with the
-! Python mirror (varden_amd/plotfile.py).  The Python mirror of the same flow (varden_amd/inputs.py: run) sits on the same C-ABI: every step prints
+! plane, velpred_2d's outlet rule (vdn_set_extruded_2d; DESIGN.md section 13): plane k = 0 is the 2-D answer.  Plot files and checkpoints
+! (write_plotfile / write_checkfile, varden.f90:492-610) are written by the library (fabio_ml_multifab_write_d, checkpoint_write) at step 0 of a fresh run, after every
+! plot_int-th / chk_int-th step and once more after the last step (:207-221, 349-361, 374-377); restart = n takes box lists and state from <check_base_name>n and skips
+! the start-up sequence (initialize.f90:22-88, varden.f90:94-97); the files of an extruded copy are the 3-D copy's.  The Python mirror of the same flow (varden_amd/inputs.py: run) sits on the same C-ABI: every step prints
 ! time, dt, max|u| and the boxes per level with 17 significant digits and tests/test_fortran_gpu.py compares the two step for step.
 program varden_main
   use iso_c_binding
@@ -23,10 +25,12 @@ program varden_main
   real(dp_t) :: grav = 0.d0, stop_time = -1.d0, prob_hi_x = 1.d0, prob_hi_y = 1.d0, prob_hi_z = 1.d0, prob_lo_x = 0.d0, prob_lo_y = 0.d0, prob_lo_z = 0.d0
   real(dp_t) :: init_shrink = 1.d0, cflfac = 0.8d0, max_dt_growth = 1.1d0, visc_coef = 0.d0, diff_coef = 0.d0, fixed_dt = -1.d0, cluster_min_eff = 0.9d0
   real(dp_t) :: u_bc(3,2) = 0.d0, v_bc(3,2) = 0.d0, w_bc(3,2) = 0.d0, rho_bc(3,2) = 1.d0, trac_bc(3,2) = 0.d0
+  character(len=128) :: plot_base_name = 'plt', check_base_name = 'chk'
   namelist /probin/ dim_in, nscal, prob_type, boussinesq, max_step, max_levs, max_grid_size, regrid_int, amr_buf_width, n_cellx, n_celly, n_cellz, &
        init_iter, do_initial_projection, diffusion_type, slope_order, use_minion, stencil_order, verbose, mg_verbose, plot_int, chk_int, restart, ref_ratio, &
        bcx_lo, bcx_hi, bcy_lo, bcy_hi, bcz_lo, bcz_hi, cluster_min_width, cluster_blocking_factor, grav, stop_time, prob_hi_x, prob_hi_y, prob_hi_z, &
-       prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc
+       prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc, &
+       plot_base_name, check_base_name
 
   ! one hierarchy: box lists, layout, boundary tower and the four multifabs regridding carries (regrid.f90:60-75)
   type hier
@@ -49,7 +53,7 @@ program varden_main
   integer :: phys_bc(3, 2)
   real(dp_t) :: dx(MAXL, 3), dt, dtold, dtlev, time, umax
   type(vdn_box), allocatable :: newb(:)
-  integer :: nnew
+  integer :: nnew, last_plt = -1, last_chk = -1
   logical :: new_grid
 
   if (command_argument_count() < 1) stop 'usage: varden_main <inputs file> [max_step]'
@@ -64,6 +68,8 @@ program varden_main
      call get_command_argument(2, arg); read(arg, *) nsteps_arg
   end if
   if (nsteps_arg >= 0) max_step = nsteps_arg
+  if (dim_in == 2 .and. restart >= 0) &
+       stop "restart of a 2-D hierarchy (an extruded copy, DESIGN section 13): not in this round -- its checkpoint is the 3-D copy's"
   if (dim_in == 2) then                                         ! the z-uniform copy of the 2-D problem (see the header)
      if (prob_hi_x /= 1.d0 .or. abs(prob_hi_y / n_celly - prob_hi_x / n_cellx) > 1.d-15) stop 'varden_main: dim_in = 2: prob_hi_x = 1 and square cells'
      if (prob_type < 1 .or. prob_type > 3) stop 'varden_main: dim_in = 2: prob_type 1 .. 3 (src/initdata.f90:127-185)'
@@ -96,53 +102,66 @@ program varden_main
   end do
   allocate(newb(MAXB))
 
-  ! ---- grids: initialize_with_adaptive_grids (src/initialize.f90:152-342) ----
-  call base_boxes(H)
-  call alloc_state(H)
-  call init_level(H, 1)
-  do lev = 1, max_levs - 1
-     call make_new_grids(new_grid, H%sold(lev), lev, abw, merge(0, 2, lev == 1), mgs, newb, nnew)      ! (tag_boxes reads valid cells only)
-     if (.not. new_grid) exit
-     call grow_hierarchy(H, newb, nnew, carry=.true.)
-     call init_level(H, lev + 1)
-  end do
-  call make_temporaries()
-  do lev = 1, H%nlev                                              ! the data of every level from initdata (initialize.f90:326-333)
-     call init_level(H, lev)
-  end do
-  call fill_state_ghosts()
-
-  ! ---- start-up (varden.f90:126-199, 460-490) ----
-  time = 0.d0
-  if (do_initial_projection > 0) then
+  if (restart >= 0) then
+     ! ---- initialize_from_restart (src/initialize.f90:22-88): box lists, state, time and dt from the checkpoint; no start-up sequence ----
+     call restart_from_checkpoint()
+     call make_temporaries()
+     call fill_state_ghosts()
      do lev = 1, H%nlev
-        call multifab_build(rhohalf(lev), H%mla, lev, 1, 1)
-        call setval(rhohalf(lev), 1.d0, all=.true.)
+        call multifab_copy_c(unew(lev), 1, H%uold(lev), 1, dm, 3); call multifab_copy_c(snew(lev), 1, H%sold(lev), 1, nscal, 3)
      end do
-     call hgproject(initial_projection, H%mla, H%uold(1:H%nlev), H%uold(1:H%nlev), rhohalf(1:H%nlev), H%p(1:H%nlev), H%gp(1:H%nlev), &
-                    dx(1:H%nlev,:), 1.d0, H%bct, press_comp)
-     do lev = 1, H%nlev
-        call multifab_destroy(rhohalf(lev))
-        call setval(H%p(lev), 0.d0, all=.true.); call setval(H%gp(lev), 0.d0, all=.true.)
+     istep = restart
+  else
+     ! ---- grids: initialize_with_adaptive_grids (src/initialize.f90:152-342) ----
+     call base_boxes(H)
+     call alloc_state(H)
+     call init_level(H, 1)
+     do lev = 1, max_levs - 1
+        call make_new_grids(new_grid, H%sold(lev), lev, abw, merge(0, 2, lev == 1), mgs, newb, nnew)      ! (tag_boxes reads valid cells only)
+        if (.not. new_grid) exit
+        call grow_hierarchy(H, newb, nnew, carry=.true.)
+        call init_level(H, lev + 1)
+     end do
+     call make_temporaries()
+     do lev = 1, H%nlev                                              ! the data of every level from initdata (initialize.f90:326-333)
+        call init_level(H, lev)
      end do
      call fill_state_ghosts()
+
+     ! ---- start-up (varden.f90:126-199, 460-490) ----
+     time = 0.d0
+     if (do_initial_projection > 0) then
+        do lev = 1, H%nlev
+           call multifab_build(rhohalf(lev), H%mla, lev, 1, 1)
+           call setval(rhohalf(lev), 1.d0, all=.true.)
+        end do
+        call hgproject(initial_projection, H%mla, H%uold(1:H%nlev), H%uold(1:H%nlev), rhohalf(1:H%nlev), H%p(1:H%nlev), H%gp(1:H%nlev), &
+                       dx(1:H%nlev,:), 1.d0, H%bct, press_comp)
+        do lev = 1, H%nlev
+           call multifab_destroy(rhohalf(lev))
+           call setval(H%p(lev), 0.d0, all=.true.); call setval(H%gp(lev), 0.d0, all=.true.)
+        end do
+        call fill_state_ghosts()
+     end if
+     do lev = 1, H%nlev
+        call multifab_copy_c(unew(lev), 1, H%uold(lev), 1, dm, 3); call multifab_copy_c(snew(lev), 1, H%sold(lev), 1, nscal, 3)
+     end do
+     dt = 1.d20
+     do lev = 1, H%nlev
+        call estdt(lev, H%uold(lev), H%sold(lev), H%gp(lev), ext_vel_force(lev), dx(lev,:), 1.d20, dtlev)
+        dt = min(dt, dtlev)
+     end do
+     dt = limit_dt(dt * init_shrink, .true.)
+     do istep = 1, init_iter
+        call advance_timestep(istep, H%mla, H%sold(1:H%nlev), H%uold(1:H%nlev), snew(1:H%nlev), unew(1:H%nlev), H%gp(1:H%nlev), H%p(1:H%nlev), &
+                              ext_vel_force(1:H%nlev), ext_scal_force(1:H%nlev), H%bct, dt, time, dx(1:H%nlev,:), press_comp, pressure_iters)
+     end do
+     istep = 0
+     call dump(.false.)                                            ! varden.f90:207-221
   end if
-  do lev = 1, H%nlev
-     call multifab_copy_c(unew(lev), 1, H%uold(lev), 1, dm, 3); call multifab_copy_c(snew(lev), 1, H%sold(lev), 1, nscal, 3)
-  end do
-  dt = 1.d20
-  do lev = 1, H%nlev
-     call estdt(lev, H%uold(lev), H%sold(lev), H%gp(lev), ext_vel_force(lev), dx(lev,:), 1.d20, dtlev)
-     dt = min(dt, dtlev)
-  end do
-  dt = limit_dt(dt * init_shrink, .true.)
-  do istep = 1, init_iter
-     call advance_timestep(istep, H%mla, H%sold(1:H%nlev), H%uold(1:H%nlev), snew(1:H%nlev), unew(1:H%nlev), H%gp(1:H%nlev), H%p(1:H%nlev), &
-                           ext_vel_force(1:H%nlev), ext_scal_force(1:H%nlev), H%bct, dt, time, dx(1:H%nlev,:), press_comp, pressure_iters)
-  end do
 
   ! ---- time loop (varden.f90:237-345) ----
-  istep = 0; nregrids = 0
+  nregrids = 0
   do while (istep < max_step .and. (stop_time < 0.d0 .or. time < stop_time))
      istep = istep + 1
      if (max_levs > 1 .and. regrid_int > 0) then
@@ -168,7 +187,9 @@ program varden_main
      time = time + dt
      write(*, '(a,i5,a,es25.17,a,es25.17,a,es25.17,a,i2,a,4i6)') ' step ', istep, '  time ', time, '  dt ', dt, '  |u|max ', umax, &
           '  levels ', H%nlev, '  boxes ', H%nb
+     call dump(.false.)                                            ! varden.f90:349-361
   end do
+  if (istep > max(restart, 0)) call dump(.true.)                  ! varden.f90:374-377
   write(*, '(a,i4)') ' regrids: ', nregrids
 
   call free_temporaries()
@@ -176,6 +197,99 @@ program varden_main
   call varden_amd_finalize()
 
 contains
+
+  ! plot file and checkpoint after every plot_int-th / chk_int-th step; final: the last step once more if it has not been written
+  subroutine dump(final)
+    logical, intent(in) :: final
+    if (plot_int > 0) then
+       if ((mod(istep, plot_int) == 0 .or. final) .and. last_plt /= istep) then
+          call write_plotfile(); last_plt = istep
+       end if
+    end if
+    if (chk_int > 0) then
+       if ((mod(istep, chk_int) == 0 .or. final) .and. last_chk /= istep) then
+          call write_checkfile(); last_chk = istep
+       end if
+    end if
+  end subroutine dump
+
+  ! write_plotfile (src/varden.f90:492-585): velocity, scalars, |u|, vorticity, grad p of every level into <plot_base_name><istep>
+  subroutine write_plotfile()
+    type(multifab) :: plot(MAXL)
+    character(len=20) :: names(2 * dm + nscal + 2)
+    character(len=256) :: dir
+    type(vdn_box) :: pd
+    integer :: l, i, rr(MAXL)
+    names(1) = 'x_vel'; names(2) = 'y_vel'; names(3) = 'z_vel'; names(dm + 1) = 'density'      ! varden.f90:73-87
+    if (nscal > 1) names(dm + 2) = 'tracer'
+    do i = 3, nscal
+       write(names(dm + i), '(a,i0)') 'scalar_', i
+    end do
+    names(dm + nscal + 1) = 'magvel'; names(dm + nscal + 2) = 'vort'
+    names(dm + nscal + 3) = 'gpx'; names(dm + nscal + 4) = 'gpy'; names(dm + nscal + 5) = 'gpz'
+    do l = 1, H%nlev
+       call multifab_build(plot(l), H%mla, l, 2 * dm + nscal + 2, 0)
+       call multifab_copy_c(plot(l), 1, H%uold(l), 1, dm); call multifab_copy_c(plot(l), dm + 1, H%sold(l), 1, nscal)
+       call make_magvel(plot(l), dm + nscal + 1, H%uold(l))
+       call make_vorticity(plot(l), dm + nscal + 2, H%uold(l), dx(l,:), H%bct)
+       call multifab_copy_c(plot(l), dm + nscal + 3, H%gp(l), 1, dm)
+    end do
+    write(dir, '(a,i5.5)') trim(plot_base_name), istep
+    pd%lo = 0; pd%hi = nn - 1; rr = 2
+    call fabio_ml_multifab_write_d(plot(1:H%nlev), rr(1:H%nlev - 1), trim(dir), names, pd, (/ 0.d0, 0.d0, 0.d0 /), dx(1,:) * nn, time, dx(1,:))
+    do l = 1, H%nlev
+       call multifab_destroy(plot(l))
+    end do
+  end subroutine write_plotfile
+
+  ! write_checkfile (src/varden.f90:587-610) + checkpoint_write (src/checkpoint.f90:14-83): State = (uold, sold, gp), Pressure = p, Header
+  subroutine write_checkfile()
+    type(multifab) :: st(MAXL)
+    character(len=256) :: dir
+    integer :: l, rr(MAXL)
+    do l = 1, H%nlev
+       call multifab_build(st(l), H%mla, l, 2 * dm + nscal, 0)
+       call multifab_copy_c(st(l), 1, H%uold(l), 1, dm); call multifab_copy_c(st(l), dm + 1, H%sold(l), 1, nscal)
+       call multifab_copy_c(st(l), dm + nscal + 1, H%gp(l), 1, dm)
+    end do
+    write(dir, '(a,i5.5)') trim(check_base_name), istep
+    rr = 2
+    call checkpoint_write(trim(dir), st(1:H%nlev), H%p(1:H%nlev), rr(1:H%nlev - 1), time, dt)
+    do l = 1, H%nlev
+       call multifab_destroy(st(l))
+    end do
+  end subroutine write_checkfile
+
+  ! checkpoint_read + fill_restart_data + initialize_from_restart (src/checkpoint.f90:85-145, src/restart.f90:17-50, src/initialize.f90:22-88):
+  ! the hierarchy is built on the checkpoint's box lists, uold / sold / gp / p take its data, time and dt its Header's
+  subroutine restart_from_checkpoint()
+    type(multifab) :: st(MAXL)
+    character(len=256) :: dir
+    integer :: nl, fdm, fnc, nbx(MAXL), rr(MAXL), l
+    logical :: nd(3)
+    real(dp_t) :: t0
+    write(dir, '(a,i5.5)') trim(check_base_name), restart
+    call checkpoint_info(trim(dir), nl, time, dt, rr)
+    call fabio_ml_multifab_info(trim(dir) // '/State', nl, fdm, fnc, nd, nbx, rr, t0)
+    if (fdm /= dm .or. fnc /= 2 * dm + nscal .or. any(nd)) stop 'varden_main: restart: the State of the checkpoint is not (u, s, gp) of this run'
+    if (nl > MAXL .or. any(nbx(1:nl) > MAXB) .or. any(rr(1:nl - 1) /= 2)) stop 'varden_main: restart: too many levels or boxes, or a ratio other than 2'
+    if (.not. allocated(H%bx)) allocate(H%bx(MAXB, MAXL))
+    H%nlev = nl; H%nb = 0; H%nb(1:nl) = nbx(1:nl)
+    do l = 1, nl
+       call fabio_ml_multifab_boxes(trim(dir) // '/State', l, H%bx(1:nbx(l), l))
+    end do
+    call alloc_state(H)
+    do l = 1, nl
+       call multifab_build(st(l), H%mla, l, 2 * dm + nscal, 0)
+    end do
+    call fabio_ml_multifab_read_d(st(1:nl), trim(dir) // '/State')
+    do l = 1, nl
+       call multifab_copy_c(H%uold(l), 1, st(l), 1, dm); call multifab_copy_c(H%sold(l), 1, st(l), dm + 1, nscal)
+       call multifab_copy_c(H%gp(l), 1, st(l), dm + nscal + 1, dm)
+       call multifab_destroy(st(l))
+    end do
+    call fabio_ml_multifab_read_d(H%p(1:nl), trim(dir) // '/Pressure')
+  end subroutine restart_from_checkpoint
 
   ! fixed_dt and stop_time: varden.f90:196-199 (first step) and :318-326
   real(dp_t) function limit_dt(dtin, first)

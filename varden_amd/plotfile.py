@@ -13,7 +13,11 @@ fabio itself is not part of the reference tree (EXT): the layout above is writte
 Several ranks: every rank writes the fabs it owns into its own Cell_D_<rank:05d> of each level (FabOnDisk names the file, byte offsets
 follow from the box sizes alone, so no rank needs another's data), the per-fab minima / maxima are max-reduced over the ranks
 (vdn_comm_allreduce_max, which is also the barrier), rank 0 writes the text files.  One shared directory, i.e. one node or a
-shared file system."""
+shared file system.
+
+One rank: write_plotfile and write_checkfile hand their multifabs to the library (vdn_fabio_ml_multifab_write_d, vdn_checkpoint_write:
+csrc/fabio.hip), which packs the valid points on the device and writes the very same files; write_ml_multifab / _write_level stay the
+definition of the format, the several-rank path and what the tests hold the library's files against."""
 import os
 import re
 
@@ -236,6 +240,9 @@ def write_plotfile(sim, istep=None, base="plt", prob_lo=None, prob_hi=None):
     dm, ns = sim.dm, sim.nscal
     pd, nl = _domain(sim)
     ncomp = 2 * dm + ns + 2
+    name = "%s%05d" % (base, sim.istep if istep is None else istep)
+    dx0 = list(sim.dx[0][:dm])
+    hi = prob_hi if prob_hi is not None else [dx0[d] * (pd[1][d] + 1) for d in range(dm)]
     plot = [bl.MultiFab(sim.mla, n, ncomp, 0) for n in range(nl)]
     try:
         for n in range(nl):
@@ -244,14 +251,14 @@ def write_plotfile(sim, istep=None, base="plt", prob_lo=None, prob_hi=None):
             adv.make_magvel(plot[n], dm + ns, sim.uold[n])
             adv.make_vorticity(plot[n], dm + ns + 1, sim.uold[n], sim.dx[n], sim.bct)
             plot[n].copy_c(dm + ns + 2, sim.gp[n], 0, dm)
-        levels = _gather(sim, [plot])
+        if getattr(sim, "nranks", 1) == 1:              # one rank: packed on the device and written by the library (csrc/fabio.hip); the same files
+            adv.fabio_ml_multifab_write_d(name, plot, [2] * (nl - 1), plot_names(dm, ns), pd, prob_lo or [0.0] * dm, hi, sim.time, dx0)
+        else:
+            write_ml_multifab(name, _gather(sim, [plot]), [2] * (nl - 1), dm, plot_names(dm, ns), pd, prob_lo or [0.0] * dm, hi, sim.time, dx0, nc=ncomp,
+                              **_par(sim))
     finally:
         for m in plot:
             m.destroy()
-    name = "%s%05d" % (base, sim.istep if istep is None else istep)
-    dx0 = list(sim.dx[0][:dm])
-    hi = prob_hi if prob_hi is not None else [dx0[d] * (pd[1][d] + 1) for d in range(dm)]
-    write_ml_multifab(name, levels, [2] * (nl - 1), dm, plot_names(dm, ns), pd, prob_lo or [0.0] * dm, hi, sim.time, dx0, nc=ncomp, **_par(sim))
     if getattr(sim, "rank", 0) == 0:
         write_job_info(name, sim, getattr(sim, "inputs_text", None), getattr(sim, "job_name", ""), getattr(sim, "inputs_file", ""))   # varden.f90:583
     return name
@@ -324,6 +331,19 @@ def write_checkfile(sim, istep=None, base="chk"):
     Pressure = nodal p, Header = namelist &chkpoint (time, dt, nlevs) followed by the refinement ratios"""
     name = "%s%05d" % (base, sim.istep if istep is None else istep)
     pd, nl = _domain(sim)
+    if getattr(sim, "nranks", 1) == 1:                  # one rank: the library's checkpoint_write (csrc/fabio.hip); the same files
+        dm, ns = sim.dm, sim.nscal
+        state = [bl.MultiFab(sim.mla, n, 2 * dm + ns, 0) for n in range(nl)]
+        try:
+            for n in range(nl):                        # varden.f90:602-609
+                state[n].copy_c(0, sim.uold[n], 0, dm)
+                state[n].copy_c(dm, sim.sold[n], 0, ns)
+                state[n].copy_c(dm + ns, sim.gp[n], 0, dm)
+            adv.checkpoint_write(name, state, list(sim.p[:nl]), [2] * (nl - 1), sim.time, sim.dt)
+        finally:
+            for m in state:
+                m.destroy()
+        return name
     os.makedirs(name, exist_ok=True)
     write_ml_multifab(os.path.join(name, "State"), _gather(sim, [sim.uold, sim.sold, sim.gp]), [2] * (nl - 1), sim.dm, pd=pd,
                       nc=2 * sim.dm + sim.nscal, **_par(sim))
