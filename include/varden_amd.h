@@ -92,6 +92,24 @@ typedef struct vdn_params {
                                    * device and read in one go (one read-back -- at N > 1 one all-reduce -- instead of one per V-cycle).  The stopping cycle is
                                    * decided by the same norms: if the history shows an earlier cycle had already converged, the solve is REPEATED with a
                                    * read-back per cycle, so results never depend on the prediction; 0: read every cycle (rounds 1-3) */
+  /* Bottom solvers of the two multigrids (reference src/_parameters:55-57, handed to ml_cc_solve / ml_nd_solve in mac_multigrid.f90:56-58 and
+   * hg_multigrid.f90:99-100).  mg_bottom_solver governs EVERY cell-centred solve (the MAC projection, the viscous and the scalar diffusion solves: the
+   * reference routes them all through mac_multigrid), hg_bottom_solver the nodal one.  Values -- the numbering is FBoxLib's as published, which is not
+   * in the reference tree (EXT-UNVERIFIED):
+   *   -1 (default), 0, 4: the bottom sweeps -- max(mg_nub, N^2) red-black Gauss-Seidel / max(hg_nub, 2 N^2) Jacobi sweeps, N the bottom level's largest
+   *                 extent.  -1 is this library's default; 4 asks for an agglomerated multigrid at the bottom, which the replicated tail already is.
+   *   1, 3:         BiCGStab (3 is FBoxLib's communication-avoiding variant: it differs in communication only, and one workgroup has none).
+   *   2:            conjugate gradients.
+   *   anything else: vdn_init fails.
+   * Both Krylov methods are preconditioned by the operator's diagonal, start from zero, run in ONE workgroup, stop when the max-norm of the residual has
+   * fallen by *_bottom_solver_eps relative to the bottom right-hand side, and are capped at 12 N iterations.  A breakdown (rho or omega zero or not
+   * finite, p.Ap <= 0) leaves the last iterate, is counted (vdn_last_bottom_stats) and the V-cycle goes on.  They apply where one rank holds the whole
+   * bottom level: the last level of a one-box hierarchy and of the replicated tail (any boxes, any ranks; level 0 of a composite solve included).  A
+   * bottom level still distributed over boxes keeps its sweeps, and so does dm = 2.  With -1, 0 or 4 no launch and no bit differs from before. */
+  int    mg_bottom_solver, hg_bottom_solver;
+  int    max_mg_bottom_nlevels;   /* 1000 (src/_parameters:57): carried for the reference's namelist; NO effect (the levels under the bottom are the replicated tail) */
+  double mg_bottom_solver_eps;    /* 1e-3: mac_multigrid.f90:56 (bottom_solver_eps = 1.d-3) */
+  double hg_bottom_solver_eps;    /* 1e-3: OURS -- hg_multigrid.f90 passes none and FBoxLib's default is not in the reference tree */
 } vdn_params;
 
 /* fills *p with the reference defaults (src/_parameters) */
@@ -320,6 +338,10 @@ int vdn_checkpoint_info (const char *dirname, int *nlev, double *time, double *d
 int  vdn_last_step_timing(double *sec5);
 /* diagnostics of the last MAC / HG solves: cycles, initial and final residual norms             */
 int  vdn_last_solver_stats(int which /*0=MAC,1=HG*/, int *cycles, double *res0, double *res);
+/* Krylov bottom solvers (vdn_params.mg_bottom_solver / hg_bottom_solver = 1, 2, 3) of the last cell-centred (which = 0) / nodal (which = 1) solve: visits of
+ * the bottom level, iterations in all, the most in one visit, breakdowns.  All zero with the bottom sweeps.  A composite solve counts all its cycles on level 0.
+ * Reads four numbers back from the device (drains the launch stream); any pointer may be NULL. */
+int  vdn_last_bottom_stats(int which /*0=cell-centred,1=nodal*/, int *calls, int *iters, int *max_iters, int *breakdowns);
 /* how the last macproject solve on one box kept its finest level: 0 interleaved (the level array), 1 by colour (passes and residual on the
  * split arrays), 2 by colour for the passes only (VDN_MAC_SPLIT=2).  No reference counterpart: the tests use it to know which kernels they exercised. */
 int  vdn_last_mac_level_form(void);

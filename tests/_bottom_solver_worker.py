@@ -1,0 +1,52 @@
+"""one rank of tests/test_bottom_solver_gpu.py::test_two_ranks_reproduce_one_rank_bits_with_cg_bottoms: the bubble on (44, 22, 22) cells in two boxes of 22^3 with
+mg_bottom_solver = hg_bottom_solver = 2, two steps; ranks are processes on ONE GPU, the transport is the RCCL test double tests/fake_rccl (VDN_RCCL_LIB), the
+rendezvous a file.  argv: rank nranks idfile outprefix"""
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    rank, nranks, idfile, outprefix = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
+    from varden_amd import advance as adv
+    from varden_amd import boxlib as bl
+    from varden_amd import driver
+    from varden_amd.capi import default_params
+    prm = default_params(cflfac=0.9, mg_bottom_solver=2, hg_bottom_solver=2)
+    comm_id = None
+    if nranks > 1:
+        bl.initialize(prm, rank, nranks, 0)
+        if rank == 0:
+            cid = bl.comm_get_unique_id()
+            with open(idfile + ".tmp", "wb") as f:
+                f.write(cid)
+            os.rename(idfile + ".tmp", idfile)
+        t0 = time.time()
+        while not os.path.exists(idfile):
+            time.sleep(0.01)
+            assert time.time() - t0 < 120, "rendezvous timed out"
+        comm_id = open(idfile, "rb").read()
+    n, decomp = (44, 22, 22), (2, 1, 1)
+    h = 1.0 / max(n)
+    G = driver.Varden(n, [[bl.NO_SLIP_WALL] * 2] * 3, prm, prob_type=1, grav=-9.8, prob_hi=tuple(n[d] * h for d in range(3)), init_shrink=0.1, init_iter=1,
+                      device=0, decomp=decomp, rank=rank, nranks=nranks, comm_id=comm_id)
+    dts, mac, hg = [], [], []
+    for _ in range(2):
+        G.step()
+        dts.append(G.dt)
+        mac.append(adv.last_bottom_stats("mac")["iters"]); hg.append(adv.last_bottom_stats("hg")["iters"])
+    out = {"dt": np.array(dts), "mac_iters": np.array(mac), "hg_iters": np.array(hg)}
+    for li, gi in enumerate(G.local):
+        out["u%d" % gi] = G.unew[0].to_numpy(li)[3:-3, 3:-3, 3:-3]
+        out["s%d" % gi] = G.snew[0].to_numpy(li)[3:-3, 3:-3, 3:-3]
+        out["p%d" % gi] = G.p[0].to_numpy(li)[1:-1, 1:-1, 1:-1]
+    np.savez(outprefix + ".%d.npz" % rank, **out)
+    G.close()
+
+
+if __name__ == "__main__":
+    main()

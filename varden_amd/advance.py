@@ -60,6 +60,13 @@ def last_solver_stats(which):
     return cyc.value, r0.value, r.value
 
 
+def last_bottom_stats(which):
+    """Krylov bottom solver of the last cell-centred ("mac") / nodal ("hg") solve: dict(calls, iters, max_iters, breakdowns); zeros with the bottom sweeps"""
+    v = [C.c_int() for _ in range(4)]
+    check(capi.load().vdn_last_bottom_stats(0 if which == "mac" else 1, *[C.byref(x) for x in v]))
+    return dict(calls=v[0].value, iters=v[1].value, max_iters=v[2].value, breakdowns=v[3].value)
+
+
 # ---- per-kernel modules (single level) ------------------------------------------------------------
 def _iv(x):
     return (C.c_int * len(x))(*[int(v) for v in x])

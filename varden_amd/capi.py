@@ -29,6 +29,8 @@ class Params(C.Structure):
         ("hg_omega", C.c_double), ("mac_rel_eps", C.c_double), ("hg_rel_eps", C.c_double),
         ("abort_on_max_iter", C.c_int), ("hg_fmg", C.c_int), ("mac_fmg", C.c_int), ("hg_omega_pre1", C.c_double), ("hg_omega_pre2", C.c_double),
         ("hg_omega_fac1", C.c_double), ("hg_omega_fac2", C.c_double), ("hg_omega_fac3", C.c_double), ("mg_predict", C.c_int),
+        ("mg_bottom_solver", C.c_int), ("hg_bottom_solver", C.c_int), ("max_mg_bottom_nlevels", C.c_int),
+        ("mg_bottom_solver_eps", C.c_double), ("hg_bottom_solver_eps", C.c_double),
     ]
 
 
@@ -42,6 +44,8 @@ def default_params(**kw):
     p.mg_nu1 = 2; p.mg_nu2 = 2; p.mg_nub = 8; p.mg_max_iter = 100
     p.hg_max_iter = 100; p.hg_nu1 = 2; p.hg_nu2 = 1; p.hg_nub = 8; p.hg_omega = 0.9
     p.mac_rel_eps = 1.0e-10; p.hg_rel_eps = -1.0; p.abort_on_max_iter = 1; p.hg_fmg = 1; p.mac_fmg = 1; p.hg_omega_pre1 = 1.45; p.hg_omega_pre2 = 0.7; p.hg_omega_fac1 = 1.6; p.hg_omega_fac2 = 0.9; p.hg_omega_fac3 = 0.65; p.mg_predict = 1
+    p.mg_bottom_solver = -1; p.hg_bottom_solver = -1; p.max_mg_bottom_nlevels = 1000
+    p.mg_bottom_solver_eps = 1.0e-3; p.hg_bottom_solver_eps = 1.0e-3
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError("vdn_params has no field %r" % k)
@@ -134,6 +138,7 @@ SIGNATURES = {
     "vdn_checkpoint_info": (C.c_int, [C.c_char_p, _PI, _PD, _PD, _PI]),
     "vdn_last_step_timing": (C.c_int, [_PD]),
     "vdn_last_solver_stats": (C.c_int, [C.c_int, _PI, _PD, _PD]),
+    "vdn_last_bottom_stats": (C.c_int, [C.c_int, _PI, _PI, _PI, _PI]),
     "vdn_last_mac_level_form": (C.c_int, []),
     "vdn_k_slope": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP]),
     "vdn_k_velpred": (C.c_int, [_VP, _PVP, _VP, _PD, C.c_double, _VP]),

@@ -13,6 +13,7 @@
 // The smoother is the kernel the north-star roofline is quoted on: ALGORITHMIC traffic per colour
 // pass = 48 B/cell (phi r+w 16, rh 8, bx/by/bz 24), see DESIGN.md.
 #include "vdn_dev.h"
+#include "krylov_wg.h"
 #include <chrono>
 #include <tuple>
 #include <algorithm>
@@ -771,6 +772,45 @@ __global__ void __launch_bounds__(1024) kk_cc_tailcycle(CcTailArgs T) {
     if (l < T.nlev - 1) { wg_cc_up(T.L[l], T.L[l + 1]); wg_cc_gsrb(T.L[l], T.nu2, T.per); }
 }
 
+// ---- Krylov bottom solvers (vdn_params.mg_bottom_solver = 1, 2, 3; krylov_wg.h) ------------------------------------------------------------------
+// The coarsest level of a hierarchy whose extents are not powers of two is large (200 -> 100 -> 50 -> 25: 25^3 cells, max(8, N^2) = 625 red-black sweeps by one
+// workgroup in every V-cycle); CG or BiCGStab with the diagonal of cc_apply as preconditioner reaches the reference's bottom_solver_eps in under a hundred
+// iterations.  The level's operator, its periodic fill and its arrays are used as they are; the solve starts from phi = 0, as every bottom visit does.
+struct CcKrylovOp {
+  const CLev &L; const int *per; int sing;
+  DEVI int count() const { return L.n[0] * L.n[1] * L.n[2]; }
+  DEVI bool point(int t, long &c, int &i, int &j, int &k) const { i = t % L.n[0]; j = (t / L.n[0]) % L.n[1]; k = t / (L.n[0] * L.n[1]); c = cidx(L, i, j, k); return true; }
+  DEVI void apply(const double *v, long c, int, int, int, double &Av, double &diag) const { CLev Lv = L; Lv.phi = const_cast<double *>(v); cc_apply(Lv, c, Av, diag); }
+  DEVI void fill(double *v) const { CLev Lv = L; Lv.phi = v; wg_cc_periodic(Lv, per); }
+  DEVI long size() const { return L.sz; }
+  DEVI const double *rhs() const { return L.rh; }
+  DEVI double *x() const { return L.phi; }
+  DEVI bool singular() const { return sing != 0; }
+};
+template <int METHOD> DEVI void wg_cc_krylov(const CLev &L, const int per[3], int singular, const KrylovArgs &K) {
+  const CcKrylovOp op{ L, per, singular };
+  wg_krylov<METHOD>(op, K);
+}
+DEVI void wg_cc_krylov_any(int method, const CLev &L, const int per[3], int singular, const KrylovArgs &K) {      // method: uniform over the launch
+  if (method == VDN_KRYLOV_CG) wg_cc_krylov<VDN_KRYLOV_CG>(L, per, singular, K); else wg_cc_krylov<VDN_KRYLOV_BICGSTAB>(L, per, singular, K);
+}
+__global__ void __launch_bounds__(1024) kk_cc_bottom_krylov(CLev L, KrylovArgs K, int method, int singular, int per0, int per1, int per2) {
+  const int per[3] = { per0, per1, per2 };
+  wg_cc_krylov_any(method, L, per, singular, K);
+}
+// kk_cc_tailcycle with the Krylov solve in place of the nbot sweeps
+__global__ void __launch_bounds__(1024) kk_cc_tailcycle_krylov(CcTailArgs T, KrylovArgs K, int method, int singular) {
+  #pragma unroll
+  for (int l = 0; l < CC_TAIL_MAX - 1; l++)
+    if (l < T.nlev - 1) { wg_cc_gsrb(T.L[l], T.nu1, T.per); wg_cc_down(T.L[l], T.L[l + 1], T.per); }
+  #pragma unroll
+  for (int l = 0; l < CC_TAIL_MAX; l++)
+    if (l == T.nlev - 1) wg_cc_krylov_any(method, T.L[l], T.per, singular, K);
+  #pragma unroll
+  for (int l = CC_TAIL_MAX - 2; l >= 0; l--)
+    if (l < T.nlev - 1) { wg_cc_up(T.L[l], T.L[l + 1]); wg_cc_gsrb(T.L[l], T.nu2, T.per); }
+}
+
 // ---- levels of 16^3 .. 64^3 cells: one launch down, one launch up (round 3) ------------------------------------------------------------------
 // Below the 128^3 level a V-cycle is a chain of ~5 us launches: eleven per level and cycle (four colour passes, residual, restriction;
 // prolongation, four colour passes), each waiting for the one before -- ~300 launches per MAC solve on the 64^3, 32^3 and 16^3 levels of a 256^3
@@ -1136,6 +1176,8 @@ struct CCMG {
   std::vector<GBox> gb_rh, gb_b; GBox *d_gb_rh = nullptr, *d_gb_b = nullptr;
   double *sendbuf = nullptr, *recvbuf = nullptr; size_t cnt_rh = 0, cnt_b = 0;   // per-rank counts (doubles)
   std::vector<long> loc_off_rh, loc_off_b;                                       // offsets of my boxes inside my send buffer
+  // Krylov bottom solver (mg_bottom_solver = 1, 2, 3): its work arrays, of the bottom level's padded size; nullptr = the bottom sweeps
+  double *kry_w = nullptr; int kry_method = 0, kry_singular = 0, kry_maxit = 0;
 };
 
 static dim3 g3(int nx, int ny, int nz, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, nz); }
@@ -1296,6 +1338,7 @@ int mg_agglom(const vdn_layout *la, int lev) {
   return (all_local && !comm_active()) ? 128 : 64;
 }
 
+static int cc_krylov_method() { const int b = ctx().prm.mg_bottom_solver; return (b == 1 || b == 3) ? VDN_KRYLOV_BICGSTAB : (b == 2 ? VDN_KRYLOV_CG : 0); }
 static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const int bc[3][2], bool has_alpha) {
   Prof prof_("cc_build");
   const vdn_layout *la = rh->la; const int lev = rh->lev;
@@ -1400,7 +1443,20 @@ static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const in
     if (M.dlev.size() >= 31) break;
   }
   M.d_nrm = (double *)arena_alloc(256);
+  // Krylov bottom solver: where the coarsest level is held whole by this rank -- the last level of the replicated tail, or of a one-box hierarchy (a bottom level
+  // that is still distributed over boxes keeps its sweeps, cc_vcycle_d).  The work arrays come from the arena here, so their addresses repeat with the hierarchy's.
+  const int method = cc_krylov_method();
+  const CLev *bottom = !M.tail.empty() ? &M.tail.back() : ((M.dlev.size() > 1 && M.dlev.back().single_box && M.dlev.back().boxes.size() == 1) ? &M.dlev.back().boxes[0].L : nullptr);
+  if (method && bottom) {
+    M.kry_method = method;
+    M.kry_w = (double *)arena_alloc(sizeof(double) * bottom->sz * (method == VDN_KRYLOV_CG ? 4 : 7));
+    bool dir = false;
+    for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) if (bc[d][sd] == VDN_BC_DIR) dir = true;
+    M.kry_singular = (!has_alpha && !dir) ? 1 : 0;
+    M.kry_maxit = 12 * std::max(bottom->n[0], std::max(bottom->n[1], bottom->n[2]));
+  }
 }
+static KrylovArgs cc_krylov_args(const CCMG &M) { return KrylovArgs{ M.kry_w, bottom_stats_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry_maxit }; }
 
 static void cc_halo(CCMG &M, CDLev &DL) { if (DL.halo) xplan_run(DL.halo); }
 // levels of at most 8^3 cells held in ONE box are smoothed by a single workgroup in one launch (all sweeps, both
@@ -1521,6 +1577,7 @@ static void cc_gsrb_t(const CCMG &M, const CLev &L, int nsweeps) {
   }
 }
 static void cc_bottom_t(const CCMG &M, const CLev &L) {      // max(nub, N^2) sweeps, N = largest extent (same rule as the oracle)
+  if (M.kry_w) { hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, cc_krylov_args(M), M.kry_method, M.kry_singular, M.per[0], M.per[1], M.per[2]); return; }
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.mg_nub, N * N);
   hipLaunchKernelGGL(kk_cc_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, ns, M.per[0], M.per[1], M.per[2]);
@@ -1552,6 +1609,7 @@ static bool cc_small_end(const CCMG &M, int dl, int tl) {
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.mg_nu1; T.nu2 = P.mg_nu2; T.nbot = std::max(P.mg_nub, N * N);      // cc_bottom_t / cc_vcycle_d
   for (int d = 0; d < 3; d++) T.per[d] = M.per[d];
+  if (M.kry_w) { hipLaunchKernelGGL(kk_cc_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, cc_krylov_args(M), M.kry_method, M.kry_singular); return true; }
   hipLaunchKernelGGL(kk_cc_tailcycle, dim3(1), dim3(1024), 0, ctx().stream, T);
   return true;
 }
@@ -1725,6 +1783,10 @@ static void cc_vcycle_d(CCMG &M, int l) {
   const bool last = (l == (int)M.dlev.size() - 1);      // phi = 0 on entry: written by the restriction that feeds this level
   if (cc_small_end(M, l, 0)) return;
   if (last && M.tail.empty()) {         // nothing below: bottom sweeps on the distributed level itself
+    if (M.kry_w && DL.single_box && DL.boxes.size() == 1) {      // (one box: the Krylov bottom solver, when one is selected; several boxes keep the sweeps)
+      hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, DL.boxes[0].L, cc_krylov_args(M), M.kry_method, M.kry_singular, M.per[0], M.per[1], M.per[2]);
+      return;
+    }
     const int N = std::max(DL.ng[0], std::max(DL.ng[1], DL.ng[2]));     // largest GLOBAL extent, as in the oracle
     cc_gsrb_d(M, DL, std::max(P.mg_nub, N * N));
     return;
@@ -1855,6 +1917,7 @@ static unsigned long long cc_graph_key(const CCMG &M, int what) {
   }
   for (const CLev &L : M.tail) cc_key_lev(k, L);
   for (long o : M.loc_off_rh) k.put(o);
+  if (M.kry_w) { k.put(M.kry_w); k.put(M.kry_method); k.put(M.kry_singular); k.put(M.kry_maxit); k.put(P.mg_bottom_solver_eps); }
   return k.h;
 }
 static bool cc_graphable(const CCMG &M) {
@@ -2060,6 +2123,8 @@ int cc_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const dou
     // 24 ms of a 51 ms step on the stored-coefficient passes (56 B per cell and pass; by colour, without coefficient arrays: 20)
     else if (!keep && max_iter >= 0 && alpha && const_beta > 0.0 && cc_split_ok(M)) { cc_split_setup(M); g_mac_level_form = 1; }      // (phi goes over after the nested iteration, below)
   }
+  // the bottom statistics are those of one solve (a composite solve: of all the cycles it runs on its kept hierarchy)
+  if (M.kry_w && (max_iter >= 0 || !(keep && keep->built))) bottom_stats_reset(0);
   if (keep) keep->built = true;
   CDLev &D0 = M.dlev[0];
   const bool single = (M.dlev.size() == 1 && M.tail.empty());

@@ -12,6 +12,7 @@
 // (i + 16) + PX*((j+1) + PY*(k+1)), PX a multiple of 16 doubles (rows start on a 128-byte line).
 // Algorithmic traffic of one Jacobi sweep: phi read 8 + phi write 8 + rhs 8 + sigma 8 = 32 B/node.
 #include "vdn_dev.h"
+#include "krylov_wg.h"
 #include <tuple>
 #include <algorithm>
 
@@ -816,6 +817,50 @@ __global__ void __launch_bounds__(1024) kk_nd_tailcycle(NdTailArgs T) {
     if (l < T.nlev - 1) { wg_nd_up(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu2, T.omega); }
 }
 
+// ---- Krylov bottom solvers (vdn_params.hg_bottom_solver = 1, 2, 3; krylov_wg.h) ------------------------------------------------------------------
+// The 26^3-node bottom of a 200^3 problem takes max(hg_nub, 2 N^2) = 1250 Jacobi sweeps by one workgroup in every V-cycle.  K as nd_apply returns it has a positive
+// diagonal and is symmetric positive semi-definite, so CG applies with that diagonal as preconditioner.  Dirichlet (outflow) nodes are not unknowns; along a periodic
+// direction node n is the image of node 0, is written by wg_nd_fill only and is counted once.  The solve starts from phi = 0 and leaves its result in `phi` itself
+// (no ping-pong: the host's phi / tmp swap is that of zero sweeps).
+struct NdKrylovOp {
+  const NLev &L; double *phi;
+  DEVI int count() const { return (L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1); }
+  DEVI bool point(int t, long &c, int &i, int &j, int &k) const {
+    const int nx = L.n[0] + 1, ny = L.n[1] + 1;
+    i = t % nx; j = (t / nx) % ny; k = t / (nx * ny); c = nidx(L, i, j, k);
+    return !nd_is_dir(L, i, j, k) && !((L.per[0] && i == L.n[0]) || (L.per[1] && j == L.n[1]) || (L.per[2] && k == L.n[2]));
+  }
+  DEVI void apply(const double *v, long, int i, int j, int k, double &Av, double &diag) const { nd_apply(L, v, i, j, k, Av, diag); }
+  DEVI void fill(double *v) const { wg_nd_fill(L, v); }
+  DEVI long size() const { return L.sz; }
+  DEVI const double *rhs() const { return L.b; }
+  DEVI double *x() const { return phi; }
+  DEVI bool singular() const { return !(L.dirlo[0] || L.dirlo[1] || L.dirlo[2] || L.dirhi[0] || L.dirhi[1] || L.dirhi[2]); }
+};
+template <int METHOD> DEVI void wg_nd_krylov(const NLev &L, double *phi, const KrylovArgs &K) {
+  const NdKrylovOp op{ L, phi };
+  wg_krylov<METHOD>(op, K);
+}
+DEVI void wg_nd_krylov_any(int method, const NLev &L, double *phi, const KrylovArgs &K) {      // method: uniform over the launch
+  if (method == VDN_KRYLOV_CG) wg_nd_krylov<VDN_KRYLOV_CG>(L, phi, K); else wg_nd_krylov<VDN_KRYLOV_BICGSTAB>(L, phi, K);
+}
+__global__ void __launch_bounds__(1024) kk_nd_bottom_krylov(NLev L, double *phi, KrylovArgs K, int method) { wg_nd_krylov_any(method, L, phi, K); }
+// kk_nd_tailcycle with the Krylov solve in place of the nbot sweeps
+__global__ void __launch_bounds__(1024) kk_nd_tailcycle_krylov(NdTailArgs T, KrylovArgs K, int method) {
+  double *ph[ND_TAIL_MAX], *tm[ND_TAIL_MAX];
+  #pragma unroll
+  for (int l = 0; l < ND_TAIL_MAX; l++) { ph[l] = T.L[l].phi; tm[l] = T.L[l].tmp; }
+  #pragma unroll
+  for (int l = 0; l < ND_TAIL_MAX - 1; l++)
+    if (l < T.nlev - 1) { wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu1, T.omega, T.om1, T.om2, T.nsp); wg_nd_down(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); }
+  #pragma unroll
+  for (int l = 0; l < ND_TAIL_MAX; l++)
+    if (l == T.nlev - 1) wg_nd_krylov_any(method, T.L[l], ph[l], K);
+  #pragma unroll
+  for (int l = ND_TAIL_MAX - 2; l >= 0; l--)
+    if (l < T.nlev - 1) { wg_nd_up(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu2, T.omega); }
+}
+
 // (round 3, built, measured and removed: the 17^3 .. 65^3 levels as one LDS-tiled launch down -- two Jacobi sweeps on a 16^3 region around a
 // 10^3 tile, residual, full weighting -- and one up, the scheme of kk_cc_lds_down / kk_cc_lds_up in mg_cc.hip.  Bit-identical, and no faster:
 // 17-38 us down and 14-20 us up per level against six launches of 5-10 us; HG 15.75 ms either way.  The 27-point operator costs ~150 f64
@@ -1068,6 +1113,8 @@ struct NDMG {
   std::vector<NGBox> gb; NGBox *d_gb = nullptr;
   double *sendbuf = nullptr, *recvbuf = nullptr; size_t cnt_nodes = 0, cnt_cells = 0;
   std::vector<long> loc_off_nodes, loc_off_cells;
+  // Krylov bottom solver (hg_bottom_solver = 1, 2, 3): its work arrays, of the bottom level's padded size; nullptr = the bottom sweeps
+  double *kry_w = nullptr; int kry_method = 0, kry_maxit = 0;
 };
 
 struct NdHaloKey { unsigned long uid; const void *p0; int lev, l, which, per; unsigned long long sig; bool operator<(const NdHaloKey &o) const {
@@ -1217,7 +1264,17 @@ static void nd_build(NDMG &M, const vdn_multifab *coeffs, const double *dx, cons
     if (M.dlev.size() >= 31) break;
   }
   M.d_nrm = (double *)arena_alloc(256);
+  // Krylov bottom solver: where the coarsest level is held whole by this rank (mg_cc.hip, cc_build); a bottom level still distributed over boxes keeps its sweeps
+  const int hb = ctx().prm.hg_bottom_solver;
+  const int method = (hb == 1 || hb == 3) ? VDN_KRYLOV_BICGSTAB : (hb == 2 ? VDN_KRYLOV_CG : 0);
+  const NLev *bottom = !M.tail.empty() ? &M.tail.back() : ((M.dlev.size() > 1 && M.dlev.back().single_box && M.dlev.back().boxes.size() == 1) ? &M.dlev.back().boxes[0].L : nullptr);
+  if (method && bottom) {
+    M.kry_method = method;
+    M.kry_w = (double *)arena_alloc(sizeof(double) * bottom->sz * (method == VDN_KRYLOV_CG ? 4 : 7));
+    M.kry_maxit = 12 * (std::max(bottom->n[0], std::max(bottom->n[1], bottom->n[2])) + 1);
+  }
 }
+static KrylovArgs nd_krylov_args(const NDMG &M) { return KrylovArgs{ M.kry_w, bottom_stats_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry_maxit }; }
 
 // ---- distributed levels ------------------------------------------------------------------------------------------
 static void nd_halo_phi(NDLev &DL) { XPlan *P = DL.flip ? DL.halo_B : DL.halo_A; if (P) xplan_run(P); }
@@ -1336,7 +1393,8 @@ static void nd_jacobi_t(NLev &L, int nsweeps, bool pre = false) {
     std::swap(L.phi, L.tmp);
   }
 }
-static void nd_bottom_t(NLev &L) {          // max(nub, 2 N^2) sweeps (same rule as the oracle)
+static void nd_bottom_t(const NDMG &M, NLev &L) {          // max(nub, 2 N^2) sweeps (same rule as the oracle)
+  if (M.kry_w) { hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, L.phi, nd_krylov_args(M), M.kry_method); return; }
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.hg_nub, 2 * N * N);
   hipLaunchKernelGGL(kk_nd_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, L.phi, L.tmp, ns, ctx().prm.hg_omega);
@@ -1349,7 +1407,7 @@ static void nd_vcycle_t(NDMG &M, int l) {
   // phi = 0 on entry: deeper tail levels get it from kk_nd_restrict, the first one is filled by the generic gather/unpack
   if (l == 0) HIPCHK(hipMemsetAsync(L.phi, 0, sizeof(double) * L.sz, ctx().stream));
   if (nd_small_end(M, -1, l)) return;
-  if (l == (int)M.tail.size() - 1) { nd_bottom_t(L); return; }
+  if (l == (int)M.tail.size() - 1) { nd_bottom_t(M, L); return; }
   NLev &C = M.tail[l + 1];
   nd_jacobi_t(L, P.hg_nu1, true);
   nd_fill_nodes(L, L.phi);
@@ -1452,6 +1510,8 @@ static bool nd_small_end(NDMG &M, int dl, int tl) {
   const NLev &B = T.L[nl - 1];
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.hg_nu1; T.nu2 = P.hg_nu2; T.nbot = std::max(P.hg_nub, 2 * N * N); T.omega = P.hg_omega; { const NdOm o = nd_om(true, P.hg_nu1); T.om1 = o.om1; T.om2 = o.om2; T.nsp = o.nsp; }     // nd_bottom_t / nd_bottom_sweeps_global
+  if (M.kry_w) { hipLaunchKernelGGL(kk_nd_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, nd_krylov_args(M), M.kry_method); T.nbot = 0; /* no sweeps: no swap below */ }
+  else
   hipLaunchKernelGGL(kk_nd_tailcycle, dim3(1), dim3(1024), 0, ctx().stream, T);
   int m = 0;                                           // the ping-pong state the sweeps leave behind (nd_jacobi_d / nd_jacobi_t)
   if (dl >= 0) for (int q = dl; q < (int)M.dlev.size(); q++, m++) {
@@ -1469,6 +1529,13 @@ static void nd_vcycle_d(NDMG &M, int l) {
   NDLev &DL = M.dlev[l];                               // phi = 0 on entry: written by kk_nd_restrict
   if (nd_small_end(M, l, 0)) return;
   const bool last = (l == (int)M.dlev.size() - 1);
+  if (last && M.tail.empty() && M.kry_w && DL.single_box && DL.boxes.size() == 1) {      // one box: the Krylov bottom solver, when one is selected (several boxes keep the sweeps)
+    NBox &B = DL.boxes[0];
+    NLev Lp = B.L;                      // (as nd_jacobi_d: the kernel refreshes periodic images itself)
+    for (int d = 0; d < 3; d++) Lp.per[d] = DL.per[d];
+    hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, Lp, B.L.phi, nd_krylov_args(M), M.kry_method);
+    return;
+  }
   if (last && M.tail.empty()) { nd_jacobi_d(DL, nd_bottom_sweeps_global(DL)); return; }
   nd_jacobi_d(DL, P.hg_nu1, true);
   nd_residual_d(M, DL, false);
@@ -1560,6 +1627,7 @@ static unsigned long long nd_graph_key(const NDMG &M, int what) {
   }
   for (const NLev &L : M.tail) nd_key_lev(k, L);
   for (long o : M.loc_off_nodes) k.put(o);
+  if (M.kry_w) { k.put(M.kry_w); k.put(M.kry_method); k.put(M.kry_maxit); k.put(P.hg_bottom_solver_eps); }
   return k.h;
 }
 static std::map<unsigned long long, NDMG> g_nd_post;
@@ -1606,6 +1674,7 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
   const bool rebuild = !(keep && keep->built);
   if (rebuild) nd_build(M, coeffs, dx, bc);          // (of `coeffs` only the layout, the level and the boxes are used)
   NDLev &D0 = M.dlev[0];
+  if (M.kry_w && (max_iter >= 0 || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
   M.pro_levels = 0; g_nd_pro_levels = 0;
   if (rebuild) {
   // sigma: level 0 from the (ghost-filled) coeffs multifab; coarser distributed levels by averaging + halo exchange

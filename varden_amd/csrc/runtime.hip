@@ -165,6 +165,8 @@ extern "C" void vdn_params_default(vdn_params *p) {
   p->mg_nu1 = 2; p->mg_nu2 = 2; p->mg_nub = 8; p->mg_max_iter = 100;
   p->hg_max_iter = 100; p->hg_nu1 = 2; p->hg_nu2 = 1; p->hg_nub = 8; p->hg_omega = 0.9;     // hg_nub: 32 until round 3 -- the coarsest level (3^3 nodes under a 2^k box) gains nothing from more than max(8, 2 N^2) sweeps (same cycle counts), and each costs ~1.2 us of a one-workgroup launch
   p->mac_rel_eps = 1.0e-10; p->hg_rel_eps = -1.0; p->abort_on_max_iter = 1; p->hg_fmg = 1; p->mac_fmg = 1; p->hg_omega_pre1 = 1.45; p->hg_omega_pre2 = 0.7; p->hg_omega_fac1 = 1.6; p->hg_omega_fac2 = 0.9; p->hg_omega_fac3 = 0.65; p->mg_predict = 1;
+  p->mg_bottom_solver = -1; p->hg_bottom_solver = -1; p->max_mg_bottom_nlevels = 1000;      // src/_parameters:55-57
+  p->mg_bottom_solver_eps = 1.0e-3; p->hg_bottom_solver_eps = 1.0e-3;                       // mac_multigrid.f90:56; the nodal one is ours
 }
 
 // ---- roctx ranges ------------------------------------------------------------------------------------------------------------
@@ -458,6 +460,10 @@ extern "C" int vdn_init(const vdn_params *prm, int rank, int nranks, int device)
   REQUIRE(prm->visc_coef >= 0.0 && prm->diff_coef >= 0.0, "vdn_init: negative visc_coef / diff_coef");
   REQUIRE(prm->diffusion_type == 1 || prm->diffusion_type == 2, "BAD DIFFUSION TYPE");      // velocity_advance.f90:113
   REQUIRE(prm->slope_order == 0 || prm->slope_order == 2 || prm->slope_order == 4, "bad slope_order");
+  REQUIRE(prm->mg_bottom_solver >= -1 && prm->mg_bottom_solver <= 4, "vdn_init: bad mg_bottom_solver %d (-1, 0, 4: bottom sweeps; 1, 3: BiCGStab; 2: CG)", prm->mg_bottom_solver);
+  REQUIRE(prm->hg_bottom_solver >= -1 && prm->hg_bottom_solver <= 4, "vdn_init: bad hg_bottom_solver %d (-1, 0, 4: bottom sweeps; 1, 3: BiCGStab; 2: CG)", prm->hg_bottom_solver);
+  REQUIRE(prm->mg_bottom_solver_eps > 0.0 && prm->mg_bottom_solver_eps < 1.0 && prm->hg_bottom_solver_eps > 0.0 && prm->hg_bottom_solver_eps < 1.0,
+          "vdn_init: mg_bottom_solver_eps / hg_bottom_solver_eps must lie in (0, 1)");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   REQUIRE(ndev > 0, "vdn_init: no HIP device visible -- the product path has no CPU fallback");
@@ -480,6 +486,10 @@ extern "C" int vdn_init(const vdn_params *prm, int rank, int nranks, int device)
     HIPCHK(hipEventCreateWithFlags(&c.ev_halo, hipEventDisableTiming));
   }
   if (c.stream == 0) c.stream = c.own_stream;
+  // the counters of the Krylov bottom solvers exist only once one is selected: with the default bottom sweeps vdn_init allocates and launches what it always did
+  const bool krylov = (prm->mg_bottom_solver >= 1 && prm->mg_bottom_solver <= 3) || (prm->hg_bottom_solver >= 1 && prm->hg_bottom_solver <= 3);
+  if (krylov && !c.d_bstats) HIPCHK(hipMalloc((void **)&c.d_bstats, 8 * sizeof(double)));
+  if (krylov) HIPCHK(hipMemsetAsync(c.d_bstats, 0, 8 * sizeof(double), c.stream));
   prof_load();
   c.inited = true;
   VDN_CATCH
@@ -491,6 +501,7 @@ extern "C" int vdn_finalize(void) {
   arena_destroy(); field_pool_release(); fabio_release();
   graph_cache_clear();
   if (c.d_hist) { HIPCHK(hipFree(c.d_hist)); c.d_hist = nullptr; }
+  if (c.d_bstats) { HIPCHK(hipFree(c.d_bstats)); c.d_bstats = nullptr; }
   if (c.d_scal) { HIPCHK(hipFree(c.d_scal)); c.d_scal = nullptr; HIPCHK(hipHostFree(c.h_scal)); c.h_scal = nullptr; c.h_scal_dev = nullptr; }
   c.inited = false;
   VDN_CATCH
@@ -510,6 +521,18 @@ extern "C" int vdn_last_step_timing(double *s) { for (int i = 0; i < 5; i++) s[i
 extern "C" int vdn_last_solver_stats(int w, int *cyc, double *r0, double *r) {
   if (w < 0 || w > 1) return 1;
   *cyc = g_ctx.solver_cycles[w]; *r0 = g_ctx.solver_res0[w]; *r = g_ctx.solver_res[w]; return 0;
+}
+double *bottom_stats_dev(int which) { return g_ctx.d_bstats + 4 * which; }
+void bottom_stats_reset(int which) { HIPCHK(hipMemsetAsync(g_ctx.d_bstats + 4 * which, 0, 4 * sizeof(double), g_ctx.stream)); }
+extern "C" int vdn_last_bottom_stats(int which, int *calls, int *iters, int *max_iters, int *breakdowns) {
+  VDN_TRY
+  REQUIRE(which == 0 || which == 1, "vdn_last_bottom_stats: which must be 0 (cell-centred) or 1 (nodal)");
+  REQUIRE(g_ctx.inited, "vdn_last_bottom_stats: vdn_init first");
+  const int b = which == 0 ? g_ctx.prm.mg_bottom_solver : g_ctx.prm.hg_bottom_solver;
+  double v[4] = { 0.0, 0.0, 0.0, 0.0 };
+  if (b >= 1 && b <= 3 && g_ctx.d_bstats) { const double *h = read_scalars(g_ctx.d_bstats + 4 * which, 4); for (int q = 0; q < 4; q++) v[q] = h[q]; }      // (bottom sweeps: nothing to read)
+  if (calls) *calls = (int)v[0]; if (iters) *iters = (int)v[1]; if (max_iters) *max_iters = (int)v[2]; if (breakdowns) *breakdowns = (int)v[3];
+  VDN_CATCH
 }
 
 // ================================================================================================

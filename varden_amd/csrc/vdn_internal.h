@@ -89,6 +89,7 @@ struct VdnCtx {
   // small device scratch for reductions + pinned host mirror
   double *d_scal = nullptr; double *h_scal = nullptr;       // 64 doubles each
   double *h_scal_dev = nullptr;                             // device view of the pinned mirror (k_publish writes it)
+  double *d_bstats = nullptr;                               // statistics of the Krylov bottom solvers, 4 doubles per multigrid (0 cell-centred, 1 nodal): bottom_stats_*
   double *d_hist = nullptr;                                 // 64 norms of consecutive V-cycles + (slot 64, as an integer) their count: norm_hist_*
   double step_sec[5] = {0, 0, 0, 0, 0};
   int solver_cycles[2] = {0, 0}; double solver_res0[2] = {0, 0}, solver_res[2] = {0, 0};
@@ -144,6 +145,10 @@ const double *norm_hist_read(int n);
 int  mg_predict_get(int solver, const int n[3]);
 void mg_predict_set(int solver, const int n[3], int cycles);
 extern int g_mg_predict_off;          // > 0: inside the repeat of a solve whose prediction overshot
+// Krylov bottom solvers (krylov_wg.h): the device block the one-workgroup solver counts into -- bottom calls, total iterations, maximum iterations, breakdowns of the
+// solve in progress, as doubles -- for which = 0 (cell-centred) or 1 (nodal); bottom_stats_reset zeroes it on the launch stream at the start of a solve
+double *bottom_stats_dev(int which);
+void    bottom_stats_reset(int which);
 
 // ---- hipGraph replay of fixed launch sequences (one multigrid cycle = ~100 launches of 3-15 us) ---------------------------------------
 // Usage:  GraphKey k; k.put(...every value the launches depend on...);  if (!graph_replay(k.h)) { graph_begin(); body(); graph_end(k.h); }

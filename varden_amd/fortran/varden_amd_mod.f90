@@ -40,6 +40,8 @@ module varden_amd
      integer(c_int) :: abort_on_max_iter, hg_fmg, mac_fmg
      real(c_double) :: hg_omega_pre1, hg_omega_pre2, hg_omega_fac1, hg_omega_fac2, hg_omega_fac3
      integer(c_int) :: mg_predict
+     integer(c_int) :: mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels      ! src/_parameters:55-57 (-1, 0, 4: bottom sweeps; 1, 3: BiCGStab; 2: CG; max_mg_bottom_nlevels has no effect)
+     real(c_double) :: mg_bottom_solver_eps, hg_bottom_solver_eps                     ! 1e-3 (mac_multigrid.f90:56); the nodal one is ours
   end type vdn_params
 
   type, bind(C), public :: vdn_box

@@ -996,6 +996,7 @@ contains
     prm%dm = dim_in; prm%nscal = nscal; prm%prob_type = prob_type; prm%slope_order = slope_order; prm%verbose = verbose
     prm%use_minion = merge(1, 0, use_minion); prm%boussinesq = boussinesq; prm%stencil_order = stencil_order; prm%diffusion_type = diffusion_type
     prm%cflfac = cflfac; prm%max_dt_growth = max_dt_growth; prm%visc_coef = visc_coef; prm%diff_coef = diff_coef
+    prm%mg_bottom_solver = mg_bottom_solver; prm%hg_bottom_solver = hg_bottom_solver; prm%max_mg_bottom_nlevels = max_mg_bottom_nlevels      ! mac_multigrid.f90:57-58, hg_multigrid.f90:99-100
     prm%u_bc = transpose(u_bc); prm%v_bc = transpose(v_bc); prm%w_bc = transpose(w_bc); prm%rho_bc = transpose(rho_bc); prm%trac_bc = transpose(trac_bc)
     call varden_amd_initialize(prm, rank, nranks, device)
   end subroutine probin_to_library

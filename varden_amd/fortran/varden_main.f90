@@ -22,6 +22,7 @@ program varden_main
   integer :: n_cellx = 32, n_celly = 32, n_cellz = 32, init_iter = 4, do_initial_projection = 1, diffusion_type = 1, slope_order = 4
   integer :: use_minion = 0, stencil_order = 2, verbose = 0, mg_verbose = 0, plot_int = 0, chk_int = 0, restart = -1, ref_ratio = 2
   integer :: bcx_lo = 14, bcx_hi = 14, bcy_lo = 14, bcy_hi = 14, bcz_lo = 14, bcz_hi = 14, cluster_min_width = 4, cluster_blocking_factor = 4
+  integer :: mg_bottom_solver = -1, hg_bottom_solver = -1, max_mg_bottom_nlevels = 1000
   real(dp_t) :: grav = 0.d0, stop_time = -1.d0, prob_hi_x = 1.d0, prob_hi_y = 1.d0, prob_hi_z = 1.d0, prob_lo_x = 0.d0, prob_lo_y = 0.d0, prob_lo_z = 0.d0
   real(dp_t) :: init_shrink = 1.d0, cflfac = 0.8d0, max_dt_growth = 1.1d0, visc_coef = 0.d0, diff_coef = 0.d0, fixed_dt = -1.d0, cluster_min_eff = 0.9d0
   real(dp_t) :: u_bc(3,2) = 0.d0, v_bc(3,2) = 0.d0, w_bc(3,2) = 0.d0, rho_bc(3,2) = 1.d0, trac_bc(3,2) = 0.d0
@@ -30,7 +31,7 @@ program varden_main
        init_iter, do_initial_projection, diffusion_type, slope_order, use_minion, stencil_order, verbose, mg_verbose, plot_int, chk_int, restart, ref_ratio, &
        bcx_lo, bcx_hi, bcy_lo, bcy_hi, bcz_lo, bcz_hi, cluster_min_width, cluster_blocking_factor, grav, stop_time, prob_hi_x, prob_hi_y, prob_hi_z, &
        prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc, &
-       plot_base_name, check_base_name
+       plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels
 
   ! one hierarchy: box lists, layout, boundary tower and the four multifabs regridding carries (regrid.f90:60-75)
   type hier
@@ -88,6 +89,7 @@ program varden_main
   prm%dm = dim_in; prm%nscal = nscal; prm%slope_order = slope_order; prm%use_minion = use_minion; prm%boussinesq = boussinesq
   prm%stencil_order = stencil_order; prm%diffusion_type = diffusion_type; prm%verbose = verbose; prm%prob_type = prob_type
   prm%visc_coef = visc_coef; prm%diff_coef = diff_coef; prm%cflfac = cflfac; prm%max_dt_growth = max_dt_growth
+  prm%mg_bottom_solver = mg_bottom_solver; prm%hg_bottom_solver = hg_bottom_solver; prm%max_mg_bottom_nlevels = max_mg_bottom_nlevels
   prm%u_bc = transpose(u_bc); prm%v_bc = transpose(v_bc); prm%w_bc = transpose(w_bc); prm%rho_bc = transpose(rho_bc); prm%trac_bc = transpose(trac_bc)
   call varden_amd_initialize(prm, 0, 1, 0)
   if (extruded) call varden_amd_set_extruded_2d(.true.)

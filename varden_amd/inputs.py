@@ -15,6 +15,7 @@ DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step
                 regrid_int=-1, amr_buf_width=-1, n_cellx=32, n_celly=32, n_cellz=32, prob_hi_x=1.0, prob_hi_y=1.0, prob_hi_z=1.0,
                 init_iter=4, do_initial_projection=1, init_shrink=1.0, cflfac=0.8, max_dt_growth=1.1, visc_coef=0.0, diff_coef=0.0,
                 diffusion_type=1, slope_order=4, use_minion=0, stencil_order=2, verbose=0, mg_verbose=0,
+                mg_bottom_solver=-1, hg_bottom_solver=-1, max_mg_bottom_nlevels=1000,
                 bcx_lo=14, bcx_hi=14, bcy_lo=14, bcy_hi=14, bcz_lo=14, bcz_hi=14,
                 fixed_dt=-1.0, plot_int=0, chk_int=0, restart=-1, plot_base_name="plt", check_base_name="chk", grids_file_name="", job_name="", fixed_grids="")
 
@@ -41,16 +42,24 @@ def parse_namelist(text):
     return out
 
 
+def namelist_params(nl, dm=None):
+    """vdn_params for a namelist dictionary (DEFAULTS updated with parse_namelist's keys); dm: run it in this dimension instead of dim_in"""
+    prm = default_params(dm=int(nl["dim_in"]) if dm is None else dm, nscal=int(nl["nscal"]), slope_order=int(nl["slope_order"]), use_minion=int(nl["use_minion"]),
+                         boussinesq=int(nl["boussinesq"]), stencil_order=int(nl["stencil_order"]), diffusion_type=int(nl["diffusion_type"]),
+                         verbose=int(nl["verbose"]), prob_type=int(nl["prob_type"]), visc_coef=float(nl["visc_coef"]),
+                         diff_coef=float(nl["diff_coef"]), cflfac=float(nl["cflfac"]), max_dt_growth=float(nl["max_dt_growth"]),
+                         mg_bottom_solver=int(nl["mg_bottom_solver"]), hg_bottom_solver=int(nl["hg_bottom_solver"]),       # src/_parameters:55-57
+                         max_mg_bottom_nlevels=int(nl["max_mg_bottom_nlevels"]))
+    return prm
+
+
 def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, extrude_zbc=None):
     """the driver object for an inputs text: Varden (one level) or VardenAMR (max_levs > 1, grids from the tagged initial data);
     restart >= 0: grids and state from the checkpoint <outdir>/<check_base_name><restart:05d> (src/varden.f90:94-97)"""
     nl = dict(DEFAULTS)
     nl.update(parse_namelist(text))
     dm = int(nl["dim_in"])
-    prm = default_params(dm=dm, nscal=int(nl["nscal"]), slope_order=int(nl["slope_order"]), use_minion=int(nl["use_minion"]),
-                         boussinesq=int(nl["boussinesq"]), stencil_order=int(nl["stencil_order"]), diffusion_type=int(nl["diffusion_type"]),
-                         verbose=int(nl["verbose"]), prob_type=int(nl["prob_type"]), visc_coef=float(nl["visc_coef"]),
-                         diff_coef=float(nl["diff_coef"]), cflfac=float(nl["cflfac"]), max_dt_growth=float(nl["max_dt_growth"]))
+    prm = namelist_params(nl)
     for name in ("u_bc", "v_bc", "w_bc", "rho_bc", "trac_bc"):           # inflow data, probin.template:21-23: name(direction, side)
         for key, v in nl.items():
             m = re.fullmatch(name + r"\((\d),(\d)\)", key)
@@ -93,10 +102,7 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
         if prob_hi[0] != 1.0 or abs(prob_hi[1] / n[1] - prob_hi[0] / n[0]) > 1e-15:
             raise NotImplementedError("2-D hierarchies: prob_hi_x = 1 and square cells")
         nz = int(extrude_nz)                                  # cells of level 0 along the periodic z of the copy (a multiple of the blocking factor)
-        prm3 = default_params(dm=3, nscal=int(nl["nscal"]), slope_order=int(nl["slope_order"]), use_minion=int(nl["use_minion"]),
-                              boussinesq=int(nl["boussinesq"]), stencil_order=int(nl["stencil_order"]), diffusion_type=int(nl["diffusion_type"]),
-                              verbose=int(nl["verbose"]), prob_type=int(nl["prob_type"]), visc_coef=float(nl["visc_coef"]),
-                              diff_coef=float(nl["diff_coef"]), cflfac=float(nl["cflfac"]), max_dt_growth=float(nl["max_dt_growth"]))
+        prm3 = namelist_params(nl, dm=3)
         for name in ("u_bc", "v_bc", "rho_bc", "trac_bc"):
             for d in range(2):
                 for sd in range(2):
