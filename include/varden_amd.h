@@ -343,7 +343,7 @@ int  vdn_last_solver_stats(int which /*0=MAC,1=HG*/, int *cycles, double *res0, 
  * Reads four numbers back from the device (drains the launch stream); any pointer may be NULL. */
 int  vdn_last_bottom_stats(int which /*0=cell-centred,1=nodal*/, int *calls, int *iters, int *max_iters, int *breakdowns);
 /* how the last macproject solve on one box kept its finest level: 0 interleaved (the level array), 1 by colour (passes and residual on the
- * split arrays), 2 by colour for the passes only (VDN_MAC_SPLIT=2).  No reference counterpart: the tests use it to know which kernels they exercised. */
+ * split arrays).  No reference counterpart: the tests use it to know which kernels they exercised. */
 int  vdn_last_mac_level_form(void);
 
 /* ------------------------------------------------------------------------------------------- */

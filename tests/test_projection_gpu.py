@@ -115,12 +115,12 @@ def test_split_colour_level_matches_the_oracle_and_the_interleaved_level(gpu, or
     256^3 tests run it).  Here on 132 x 36 x 40 cells (VDN_MAC_SPLIT_MIN=0; 33 lane pairs: the clamped tail of a wave, one-sided y / z extents): the
     projected velocities against the oracle's in the worker, and the same bits (a) split, the passes and the residual time-skewed over slabs of 7 planes
     (cc_split_run; 40 planes: six slabs, the last a sliver), the second colour walking its planes downwards,
-    (b) split passes only, residual on the level array, both colours upwards, (c) interleaved.  260 cells: two waves per row, the second with one active lane pair
+    (b) split in whole-level launches, both colours upwards (the form a multi-box level runs), (c) interleaved.  260 cells: two waves per row, the second with one active lane pair
     (the lane that ends a wave inside the row reads its neighbour from memory).  tests/_split_worker.py."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out, form = [], []
-    for extra in ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "7"}, {"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SPLIT": "2", "VDN_MAC_KFLIP": "0"}, {"VDN_MAC_SPLIT": "0"}):
+    for extra in ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "7"}, {"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "0", "VDN_MAC_KFLIP": "0"}, {"VDN_MAC_SPLIT": "0"}):
         env = dict(os.environ)
         for k in ("VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_KFLIP", "VDN_MAC_SLAB"):
             env.pop(k, None)
@@ -129,7 +129,7 @@ def test_split_colour_level_matches_the_oracle_and_the_interleaved_level(gpu, or
         assert r.returncode == 0, r.stderr[-2000:]
         out.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0])
         form.append([ln for ln in r.stdout.splitlines() if ln.startswith("FORM")][0])
-    assert form == ["FORM 1", "FORM 2", "FORM 0"], form             # (vdn_last_mac_level_form: the three runs took the three paths)
+    assert form == ["FORM 1", "FORM 1", "FORM 0"], form             # (vdn_last_mac_level_form: two runs by colour, one interleaved)
     assert out[0] == out[1] == out[2], (bcname, out)
 
 
@@ -151,7 +151,7 @@ def test_split_colour_level_with_a_halo(gpu, oracle, bcname, n, nb):
         variants = (variants[0], variants[1], variants[3])
     for extra in variants:
         env = dict(os.environ)
-        for k in ("VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_KFLIP", "VDN_MAC_SLAB", "VDN_OVERLAP", "VDN_FORCE_PACKED", "VDN_MAC_SPLIT_HALO", "VDN_MG_AGGLOM"):
+        for k in ("VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_KFLIP", "VDN_MAC_SLAB", "VDN_OVERLAP", "VDN_FORCE_PACKED", "VDN_MG_AGGLOM"):
             env.pop(k, None)
         env.update(extra)
         env["VDN_MG_AGGLOM"] = "64"          # (boxes of 128 cells on ONE rank are gathered right below the finest level by default, mg_agglom: keep the second distributed level the split form asks for)

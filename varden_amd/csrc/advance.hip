@@ -26,7 +26,7 @@ static void restrict_and_fill(int nlev, vdn_multifab **mf, int icomp, int bcomp,
 // VDN_PHASE_HASH=1 (testing build; the hunt for the run-to-run differences of profiles/r06_determinism.txt): a checksum of whole multifabs (ghost cells included) at the
 // phase boundaries of a step, on stderr
 static void dbg_phase_hash(const char *tag, int nlevs, vdn_multifab **mfs, int per_level = 1, bool whole = false) {
-  static const bool on = vdn_env("VDN_PHASE_HASH") && atoi(vdn_env("VDN_PHASE_HASH")) != 0;
+  static const bool on = env_set("VDN_PHASE_HASH");
   if (!on) return;
   HIPCHK(hipStreamSynchronize(ctx().stream));
   unsigned long long h = 1469598103934665603ull;
@@ -131,7 +131,7 @@ extern "C" int vdn_advance_timestep(int istep, vdn_layout *mla, vdn_multifab **s
   // the same operands, at the top of velocity_advance (velocity_advance.f90:63-66; gp changes only in hgproject, sold and ext not at all; lapu is
   // zeroed in between only for diffusion_type = 2, advance_timestep.f90:116-120).  Unless that is the case the first one is kept for the
   // velocity mkflux (0.32 ms of a 41 ms step at 256^3): the same values, as with the limited slopes above.
-  static const bool force_reuse = !(vdn_env("VDN_NO_FORCE_REUSE") && atoi(vdn_env("VDN_NO_FORCE_REUSE")) != 0);
+  static const bool force_reuse = !(env_set("VDN_NO_FORCE_REUSE"));
   const bool keep_vel_force = force_reuse && !(viscous && P.diffusion_type == 2);
   vdn_multifab *vel_force0[VDN_MAXLEV] = { nullptr };
   if (keep_vel_force) for (int n = 0; n < nlevs; n++) vel_force0[n] = mf_temp(mla, n, dm, 1, -1, false, 0.0);
@@ -379,11 +379,15 @@ extern "C" int vdn_cc_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **
   HOOK_BEGIN(rh)
   int b[3][2]; bc_from_flat(bc, b);
   // nested iteration (vdn_params.mac_fmg) when phi comes in zero, ghost cells included -- the check costs a reduction here; macproject knows
-  int fmg = 0;
-  if (ctx().prm.mac_fmg && max_iter >= 0 && ctx().prm.dm == 3) fmg = mf_norm_inf_grown(phi, 0, 1, 1) == 0.0 ? 1 : 0;
-  int rc = cc_solve(rh, phi, beta, dx, b, rel_eps, abs_eps, max_iter, cycles, res0, res, nullptr, nullptr, nullptr, nullptr, fmg);
+  CcRequest q;
+  q.rh = rh; q.phi = phi; q.beta = beta; q.dx = dx; q.bc = b;
+  q.rel_eps = rel_eps; q.abs_eps = abs_eps; q.max_iter = max_iter;
+  q.fixed_cycles = max_iter < 0 ? -max_iter : 0;      // the C interface: a negative max_iter asks for exactly -max_iter cycles
+  if (ctx().prm.mac_fmg && max_iter >= 0 && ctx().prm.dm == 3) q.fmg = mf_norm_inf_grown(phi, 0, 1, 1) == 0.0;
+  const int rc = cc_solve(q);
+  if (cycles) *cycles = q.cycles; if (res0) *res0 = q.res0; if (res) *res = q.res;
   arena_reset();
-  if (rc != 0) vdn_fail("cc multigrid did not converge: %d cycles, residual %g (rhs %g)", *cycles, *res, *res0);
+  if (rc != 0) vdn_fail("cc multigrid did not converge: %d cycles, residual %g (rhs %g)", q.cycles, q.res, q.res0);
   HOOK_END
 }
 extern "C" int vdn_cc_smooth(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int *bc, int nsweeps) {
@@ -394,9 +398,14 @@ extern "C" int vdn_nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multi
                             int *cycles, double *res0, double *res) {
   HOOK_BEGIN(rh)
   int b[3][2]; bc_from_flat(bc, b);
-  int rc = nd_solve(rh, phi, coeffs, u, dx, b, rel_eps, abs_eps, max_iter, cycles, res0, res);
+  NdRequest q;
+  q.rh = rh; q.phi = phi; q.coeffs = coeffs; q.u = u; q.dx = dx; q.bc = b;
+  q.rel_eps = rel_eps; q.abs_eps = abs_eps; q.max_iter = max_iter;
+  q.fixed_cycles = max_iter < 0 ? -max_iter : 0;      // the C interface: a negative max_iter asks for exactly -max_iter cycles
+  const int rc = nd_solve(q);
+  if (cycles) *cycles = q.cycles; if (res0) *res0 = q.res0; if (res) *res = q.res;
   arena_reset();
-  if (rc != 0) vdn_fail("nodal multigrid did not converge: %d cycles, residual %g (rhs %g)", *cycles, *res, *res0);
+  if (rc != 0) vdn_fail("nodal multigrid did not converge: %d cycles, residual %g (rhs %g)", q.cycles, q.res, q.res0);
   HOOK_END
 }
 extern "C" int vdn_bench_cc_smoother(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const vdn_multifab *rho, const double *dx, const int *bc,

@@ -940,17 +940,19 @@ static void add_constant(vdn_multifab *mf, double v) {
 // rh, phi: [lev];  beta: [lev*3 + d];  dx: [lev*3 + d]
 // alpha: [lev] cell coefficients of (alpha - div beta grad), or nullptr.  The ghost cells of the incoming phi carry inhomogeneous
 // Dirichlet data (boundary-face values); they are moved into rh, which is modified
-int ml_cc_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vdn_multifab **beta, const double *dx, const vdn_bc_tower *bct, int bc_comp0,
-                double rel_eps, int max_iter, int *iters, double *res0, double *res, vdn_multifab **alpha, vdn_multifab **base_beta, const vdn_multifab *base_rho, const vdn_multifab *fine_rho,
-                double const_beta) {
+int ml_cc_solve(MlCcRequest &rq) {
+  vdn_layout *la = rq.la; vdn_multifab **rh = rq.rh, **phi = rq.phi, **beta = rq.beta, **alpha = rq.alpha;
+  const double *dx = rq.dx; const vdn_bc_tower *bct = rq.bct; const int bc_comp0 = rq.bc_comp0;
+  const double rel_eps = rq.rel_eps, const_beta = rq.const_beta;
+  REQUIRE(la && rh && phi && beta && dx && bct, "composite solve: la, rh, phi, beta, dx and bct");
   require_amr(la);
   hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
   const int L = la->nlev;
-  static const bool fuse_first_on = !(vdn_env("VDN_MLCC_FUSE1") && atoi(vdn_env("VDN_MLCC_FUSE1")) == 0);
-  static const bool rho_form = !(vdn_env("VDN_MLCC_RHO") && atoi(vdn_env("VDN_MLCC_RHO")) == 0);
+  static const bool fuse_first_on = env_on("VDN_MLCC_FUSE1");
+  static const bool rho_form = env_on("VDN_MLCC_RHO");
   const bool fuse_first = fuse_first_on && ctx().prm.mg_nu1 >= 1 && ctx().prm.mg_nu2 >= 1;
-  const vdn_multifab *frho = (rho_form && !alpha) ? fine_rho : nullptr;
+  const vdn_multifab *frho = (rho_form && !alpha) ? rq.fine_rho : nullptr;
   if (frho) REQUIRE(frho->ng >= 1 && frho->lev == L - 1, "composite solve: the finest level's density with a filled ghost cell expected");
   // everything the descriptor sets of this solve follow from: the key of the kept ones (vdn_internal.h)
   GraphKey key; key.put(0x7301); key.put(la->uid); key.put(L); key.put(bct->serial); key.put(bc_comp0); key.put(fuse_first); key.put((const void *)(frho ? frho->base : nullptr)); key.put(rho_form && const_beta > 0.0);
@@ -1040,10 +1042,10 @@ int ml_cc_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vdn_multi
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc0[d][s] = bct->ell_bc(0, 0, d, s, bc_comp0);
   while (!conv) {
     rn = composite_residual(S);
-    { static const bool trace = vdn_env("VDN_MLCC_TRACE") && atoi(vdn_env("VDN_MLCC_TRACE")) != 0;
+    { static const bool trace = env_set("VDN_MLCC_TRACE");
       if (trace) fprintf(stderr, "  ml_cc_solve: iteration %d, composite residual %.6e (right-hand side %.6e, target %.3e)\n", it, rn, bnorm, rel_eps * bnorm); }
     if (rn <= rel_eps * bnorm && bnorm < HUGE_VAL) { conv = true; break; }
-    if (it >= max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;
+    if (it >= rq.max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;
     // one V-cycle over the levels in correction form (oracle: vo_ml_cc_solve).  Down, finest level first: e_n = 0, nu1 sweeps, t = res_n - A_n e_n,
     // res_{n-1} := restriction of t under level n and the flux matching with e_n's fluxes next to it
     for (int n = 1; n < L; n++) {
@@ -1059,13 +1061,16 @@ int ml_cc_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vdn_multi
       S.vf_t[n].refresh(); S.rres_t[n].run(0, (double *)nullptr, st);
     }
     // coarse correction: ONE V-cycle of the single-level multigrid on the whole level 0
-    static const bool glue = !(vdn_env("VDN_MLCC_GLUE") && atoi(vdn_env("VDN_MLCC_GLUE")) == 0);
-    const bool zg = glue && it > 0;           // (the first call builds the kept hierarchy and loads phi as the generic solver does)
-    int cyc; double r0, rr;
+    static const bool glue = env_on("VDN_MLCC_GLUE");
     // (base_beta / base_rho, the MAC projection: the V-cycle runs on level 0's OWN coefficients 2/(rho_i + rho_i-1) -- `beta` carries the edge
     // restriction of the finer level's on the covered faces -- and so on the density-based kernels of the single-level solver; it is a
     // preconditioner, the composite residual above is formed with `beta`.  Oracle: beta_base of vo_ml_cc_solve)
-    cc_solve(S.res[0], S.e[0], base_beta ? base_beta : beta, dx, ebc0, 0.0, -1.0, -1, &cyc, &r0, &rr, alpha ? alpha[0] : nullptr, base_beta ? base_rho : nullptr, coarse_keep, nullptr, 0, zg, glue ? S.phi[0] : nullptr, const_beta);     // (no nested-iteration start here: it saves no FAC iteration, measured)
+    CcRequest c;
+    c.rh = S.res[0]; c.phi = S.e[0]; c.beta = rq.base_beta ? rq.base_beta : beta; c.alpha = alpha ? alpha[0] : nullptr; c.rho = rq.base_beta ? rq.base_rho : nullptr; c.const_beta = const_beta;
+    c.dx = dx; c.bc = ebc0; c.fixed_cycles = 1; c.keep = coarse_keep;      // (no nested-iteration start here: it saves no FAC iteration, measured)
+    c.zero_guess = glue && it > 0;                     // (the first call builds the kept hierarchy and loads phi as the generic solver does)
+    c.add_to = glue ? S.phi[0] : nullptr;
+    cc_solve(c);
     if (!glue) S.add[0].run(0, (double *)nullptr, st);     // (glue: phi_0 += e_0 was done where e_0 was stored)
     fill_e_ghosts(S, 0);
     // up, coarsest level first: e_n += P e_{n-1}, the interface ghost cells from e_{n-1}, nu2 sweeps, phi_n += e_n
@@ -1084,7 +1089,7 @@ int ml_cc_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vdn_multi
     it++;
   }
   fill_phi_ghosts(S);
-  if (iters) *iters = it; if (res0) *res0 = bnorm; if (res) *res = rn;
+  rq.cycles = it; rq.res0 = bnorm; rq.res = rn;
   for (int n = L - 1; n >= 0; n--) { if (S.mask[n]) mf_temp_free(S.mask[n]); if (S.t[n]) mf_temp_free(S.t[n]); mf_temp_free(S.e[n]); mf_temp_free(S.res[n]); }
   HIPCHK(hipStreamSynchronize(st));
   arena_release(mark);
@@ -1106,7 +1111,6 @@ void do_ml_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, 
   }
   for (int n = L - 1; n >= 1; n--) ml_cc_restriction(rh[n - 1], rh[n], 0, 1);     // 204-206
   for (int n = L - 1; n >= 1; n--) for (int d = 0; d < 3; d++) ml_edge_restriction(beta[3 * (n - 1) + d], beta[3 * n + d], d);       // 330-333
-  int it; double r0, rr;
   vdn_multifab *beta0[3];                    // level 0's own coefficients (the covered faces not overwritten): what the coarse correction's V-cycle runs on
   for (int d = 0; d < 3; d++) beta0[d] = mf_temp(mla, 0, 1, 0, d, false, 0.0);
   mac_level_coeffs(rho[0], beta0);
@@ -1114,10 +1118,14 @@ void do_ml_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, 
   // coefficients are 1 / (mean rho), the restricted ones a mean of 1 / rho; across a sharp density jump the softer operator makes the correction
   // overshoot -- 45 FAC iterations instead of 12 at a one-cell jump of 10 : 1, divergence at 100 : 1).  One reduction and read-back per solve.
   const bool own = mf_max_ratio3(beta, beta0) <= 1.25;
-  int rc = ml_cc_solve(mla, rh, phi, beta, dx, bct, bc_comp0, ctx().prm.mac_rel_eps, ctx().prm.mg_max_iter, &it, &r0, &rr, nullptr, own ? beta0 : nullptr, own ? rho[0] : nullptr, rho[L - 1]);
+  MlCcRequest q;
+  q.la = mla; q.rh = rh; q.phi = phi; q.beta = beta; q.dx = dx; q.bct = bct; q.bc_comp0 = bc_comp0;
+  q.base_beta = own ? beta0 : nullptr; q.base_rho = own ? rho[0] : nullptr; q.fine_rho = rho[L - 1];
+  q.rel_eps = ctx().prm.mac_rel_eps; q.max_iter = ctx().prm.mg_max_iter;
+  const int rc = ml_cc_solve(q);
   for (int d = 2; d >= 0; d--) mf_temp_free(beta0[d]);
-  ctx().solver_cycles[0] = it; ctx().solver_res0[0] = r0; ctx().solver_res[0] = rr;
-  solver_check(rc, "composite MAC solve", it, rr, r0);
+  ctx().solver_cycles[0] = q.cycles; ctx().solver_res0[0] = q.res0; ctx().solver_res[0] = q.res;
+  solver_check(rc, "composite MAC solve", q.cycles, q.res, q.res0);
   for (int n = 0; n < L; n++) mac_level_mkumac(umac + 3 * n, phi[n], beta + 3 * n, dx + 3 * n, bct, bc_comp0);   // 103
   for (int n = L - 1; n >= 1; n--) for (int d = 0; d < 3; d++) ml_edge_restriction(umac[3 * (n - 1) + d], umac[3 * n + d], d);       // 497-500
   for (int d = 0; d < 3; d++) mf_fill_boundary(umac[d]);

@@ -26,6 +26,7 @@
 // read or written here (nor moved by the ghost exchange, exchange.hip: xboxes_of).  vdn_multifab_copy_to/from_host present the
 // BoxLib 2-D layout p(lo1-ng:hi1+ng, lo2-ng:hi2+ng, nc).
 #include "vdn_dev.h"
+#include "mg_stop.h"
 #include <vector>
 #include <algorithm>
 
@@ -304,9 +305,6 @@ static void gather_level(double *base, long ndoubles) {
   if (ctx().nranks > 1) comm_allreduce_max_u8_dev((unsigned char *)base, (size_t)ndoubles * sizeof(double));
 }
 static dim3 g2(int nx, int ny) { return dim3((nx + 63) / 64, (ny + 3) / 4, 1); }
-static double read_scal(double *d) {
-  return read_scalar1(d);
-}
 struct CC2MG { std::vector<C2> lev; int per[2]; double *d_nrm; };
 static void c2_gsrb(const CC2MG &M, const C2 &L, int ns) {
   hipStream_t st = ctx().stream;
@@ -335,8 +333,9 @@ static void c2_vcycle(const CC2MG &M, int l) {
   hipLaunchKernelGGL(kk_c2_prolong, g2(L.n0, L.n1), B2, 0, ctx().stream, L, C);
   c2_gsrb(M, L, P.mg_nu2);
 }
-int cc2_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int bc[3][2], double rel_eps, double abs_eps, int max_iter,
-              int *cycles, double *res0, double *res, const vdn_multifab *alpha) {
+int cc2_solve(CcRequest &rq) {
+  vdn_multifab *rh = rq.rh, *phi = rq.phi, **beta = rq.beta; const vdn_multifab *alpha = rq.alpha;
+  const double *dx = rq.dx; const int (*bc)[2] = rq.bc; const int max_iter = rq.max_iter;
   require_2d(rh, "cc_solve");
   REQUIRE(phi->ng >= 1, "cc multigrid: phi needs one ghost cell");
   hipStream_t st = ctx().stream;
@@ -376,15 +375,15 @@ int cc2_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const do
   gather_level(L0.phi, sz0);
   comm_allreduce_max_dev(M.d_nrm, 1);
   for (size_t l = 1; l < M.lev.size(); l++) hipLaunchKernelGGL(kk_c2_coarsen, g2(M.lev[l].n0 + 1, M.lev[l].n1 + 1), B2, 0, st, M.lev[l - 1], M.lev[l]);
-  const double bnorm = read_scal(M.d_nrm);
+  const double bnorm = read_scalar1(M.d_nrm);
   const vdn_params &P = ctx().prm;
   int cyc = 0; bool conv = false; double rn = 0.0;
   if (bnorm == 0.0) conv = true;
   while (!conv && cyc <= max_iter) {
     c2_gsrb(M, L0, M.lev.size() == 1 ? c2_bottom(L0) : P.mg_nu1);
     c2_residual(M, L0, true);
-    rn = read_scal(M.d_nrm);
-    if ((rn <= rel_eps * bnorm && bnorm < HUGE_VAL) || rn <= abs_eps) { conv = true; break; }
+    rn = read_scalar1(M.d_nrm);
+    if (mg_converged(rn, bnorm, rq.rel_eps, rq.abs_eps)) { conv = true; break; }
     if (cyc == max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;
     if (M.lev.size() > 1) {
       hipLaunchKernelGGL(kk_c2_restrict, g2(M.lev[1].n0, M.lev[1].n1), B2, 0, st, L0, M.lev[1]);
@@ -402,7 +401,7 @@ int cc2_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const do
     vs.push_back(q);
   }
   launch_batched(vs, X, (double *)nullptr, 0, st);
-  if (cycles) *cycles = cyc; if (res0) *res0 = bnorm; if (res) *res = rn;
+  rq.cycles = cyc; rq.res0 = bnorm; rq.res = rn;
   HIPCHK(hipStreamSynchronize(st));
   arena_release(mark);
   return conv ? 0 : 1;
@@ -451,10 +450,11 @@ void do2_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vd
   run_cells(vd); run_cells(vc);
   int ebc[3][2];
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc[d][s] = d < 2 ? bct->ell_bc(0, 0, d, s, bc_comp0) : VDN_BC_INT;
-  int cyc; double r0, rr;
-  int rc = cc2_solve(rh, phi, beta, dx, ebc, ctx().prm.mac_rel_eps, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, nullptr);
-  ctx().solver_cycles[0] = cyc; ctx().solver_res0[0] = r0; ctx().solver_res[0] = rr;
-  solver_check(rc, "MAC multigrid (2-D)", cyc, rr, r0);
+  CcRequest q;
+  q.rh = rh; q.phi = phi; q.beta = beta; q.dx = dx; q.bc = ebc; q.rel_eps = ctx().prm.mac_rel_eps; q.max_iter = ctx().prm.mg_max_iter;
+  const int rc = cc2_solve(q);
+  ctx().solver_cycles[0] = q.cycles; ctx().solver_res0[0] = q.res0; ctx().solver_res[0] = q.res;
+  solver_check(rc, "MAC multigrid (2-D)", q.cycles, q.res, q.res0);
   // (phi's ghost layer came from the gathered solve: the neighbours' phi across a box face, the closure across a domain face)
   const vdn_box &pd = mla->pd[0];
   std::vector<std::pair<mkumac2_K, Range3>> vu;
@@ -536,8 +536,10 @@ void do2_visc_solve(vdn_layout *mla, vdn_multifab *unew, const vdn_multifab *lap
     run_cells(v);
     int ebc[3][2];
     for (int a = 0; a < 3; a++) for (int s = 0; s < 2; s++) ebc[a][s] = a < 2 ? bct->ell_bc(0, 0, a, s, d) : VDN_BC_INT;
-    int cyc; double r0, rr;
-    solver_check(cc2_solve(rh, phi, beta, dx, ebc, 1.e-12, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, alpha), "viscous solve (2-D)", cyc, rr, r0, d);
+    CcRequest q;
+    q.rh = rh; q.phi = phi; q.beta = beta; q.alpha = alpha; q.dx = dx; q.bc = ebc; q.rel_eps = 1.e-12; q.max_iter = ctx().prm.mg_max_iter;
+    const int rc = cc2_solve(q);
+    solver_check(rc, "viscous solve (2-D)", q.cycles, q.res, q.res0, d);
     mf_copy(unew, d, phi, 0, 1, 0);
   }
   mf_restrict_and_fill(unew, 0, 0, 2, false, bct);
@@ -559,8 +561,10 @@ void do2_diff_scalar_solve(vdn_layout *mla, vdn_multifab *snew, const vdn_multif
   run_cells(v);
   int ebc[3][2];
   for (int a = 0; a < 3; a++) for (int s = 0; s < 2; s++) ebc[a][s] = a < 2 ? bct->ell_bc(0, 0, a, s, bccomp0) : VDN_BC_INT;
-  int cyc; double r0, rr;
-  solver_check(cc2_solve(rh, phi, beta, dx, ebc, 1.e-12, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, alpha), "diffusive solve (2-D)", cyc, rr, r0);
+  CcRequest q;
+  q.rh = rh; q.phi = phi; q.beta = beta; q.alpha = alpha; q.dx = dx; q.bc = ebc; q.rel_eps = 1.e-12; q.max_iter = ctx().prm.mg_max_iter;
+  const int rc = cc2_solve(q);
+  solver_check(rc, "diffusive solve (2-D)", q.cycles, q.res, q.res0);
   mf_copy(snew, icomp, phi, 0, 1, 0);
   mf_restrict_and_fill(snew, icomp, bccomp0, 1, false, bct);
   mf_temp_free(beta[0]); mf_temp_free(beta[1]); mf_temp_free(alpha); mf_temp_free(phi); mf_temp_free(rh);
@@ -723,8 +727,9 @@ static void n2_vcycle(ND2MG &M, int l) {
   hipLaunchKernelGGL(kk_n2_prolong, g2(L.n0 + 1, L.n1 + 1), B2, 0, ctx().stream, L, C);
   n2_jacobi(M, L, P.hg_nu2);
 }
-int nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, const vdn_multifab *u, const double *dx, const int bc[3][2],
-              double rel_eps, double abs_eps, int max_iter, int *cycles, double *res0, double *res) {
+int nd2_solve(NdRequest &rq) {
+  vdn_multifab *rh = rq.rh, *phi = rq.phi; const vdn_multifab *coeffs = rq.coeffs, *u = rq.u;
+  const double *dx = rq.dx; const int (*bc)[2] = rq.bc; const int max_iter = rq.max_iter;
   require_2d(coeffs, "nd_solve");
   REQUIRE(phi->ng >= 1 && rh->ng >= 1 && coeffs->ng >= 1, "nodal multigrid: phi, rh, coeffs need one ghost layer");
   hipStream_t st = ctx().stream;
@@ -775,14 +780,14 @@ int nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, c
     hipLaunchKernelGGL(kk_n2_coarsen_sigma, g2(M.lev[l].n0, M.lev[l].n1), B2, 0, st, M.lev[l - 1], M.lev[l]);
     hipLaunchKernelGGL(kk_n2_fill_cells, g2(M.lev[l].n0 + 2, M.lev[l].n1 + 2), B2, 0, st, M.lev[l], M.per[0], M.per[1]);
   }
-  const double bnorm = read_scal(M.d_nrm);
+  const double bnorm = read_scalar1(M.d_nrm);
   const vdn_params &P = ctx().prm;
   int cyc = 0; bool conv = (bnorm == 0.0); double rn = 0.0;
   while (!conv) {
     n2_jacobi(M, L0, M.lev.size() == 1 ? n2_bottom(L0) : P.hg_nu1);
     n2_residual(M, L0, true);
-    rn = read_scal(M.d_nrm);
-    if ((rn <= rel_eps * bnorm && bnorm < HUGE_VAL) || rn <= abs_eps) { conv = true; break; }
+    rn = read_scalar1(M.d_nrm);
+    if (mg_converged(rn, bnorm, rq.rel_eps, rq.abs_eps)) { conv = true; break; }
     if (cyc >= max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;     // also: a NaN / inf norm (the reductions turn NaN into +inf)
     if (M.lev.size() > 1) {
       hipLaunchKernelGGL(kk_n2_restrict, g2(M.lev[1].n0 + 1, M.lev[1].n1 + 1), B2, 0, st, L0, M.lev[1]);
@@ -802,7 +807,7 @@ int nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, c
     vo.push_back(q);
   }
   launch_batched(vo, X, (double *)nullptr, 0, st);
-  if (cycles) *cycles = cyc; if (res0) *res0 = bnorm; if (res) *res = rn;
+  rq.cycles = cyc; rq.res0 = bnorm; rq.res = rn;
   HIPCHK(hipStreamSynchronize(st));
   arena_release(mark);
   return conv ? 0 : 1;
@@ -876,10 +881,11 @@ void do2_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_mult
   if (proj_type == VDN_INITIAL_PROJECTION && ctx().prm.prob_type == 4) abs_eps = 1.e-12;
   int ebc[3][2];
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc[d][s] = d < 2 ? bct->ell_bc(0, 0, d, s, press_comp0) : VDN_BC_INT;
-  int cyc; double r0, rr;
-  int rc = nd2_solve(rh, phi, coeffs, un, dx, ebc, rel, abs_eps, ctx().prm.hg_max_iter, &cyc, &r0, &rr);
-  ctx().solver_cycles[1] = cyc; ctx().solver_res0[1] = r0; ctx().solver_res[1] = rr;
-  solver_check(rc, "nodal multigrid (2-D)", cyc, rr, r0);
+  NdRequest q;
+  q.rh = rh; q.phi = phi; q.coeffs = coeffs; q.u = un; q.dx = dx; q.bc = ebc; q.rel_eps = rel; q.abs_eps = abs_eps; q.max_iter = ctx().prm.hg_max_iter;
+  const int rc = nd2_solve(q);
+  ctx().solver_cycles[1] = q.cycles; ctx().solver_res0[1] = q.res0; ctx().solver_res[1] = q.res;
+  solver_check(rc, "nodal multigrid (2-D)", q.cycles, q.res, q.res0);
   if (proj_type == VDN_INITIAL_PROJECTION || proj_type == VDN_DIVU_ITERS) { mf_setval(gpp, 0.0, 0, gpp->nc, true); mf_setval(pp, 0.0, 0, 1, true); }
   std::vector<std::pair<hg_update2_K, Range3>> vh;
   for (int b = 0; b < un->nfabs(); b++) {

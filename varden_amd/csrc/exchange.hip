@@ -213,19 +213,6 @@ __global__ void k_xpack(const PackDesc *descs, int nc, double *buf) {
     for (int c = 0; c < nc; c++) buf[D.off + c * tot + t] = fv_get(D.fv, i - D.sh[0], j - D.sh[1], k - D.sh[2], c);
   }
 }
-__global__ void k_xunpack(const PackDesc *descs, int nc, const double *buf) {
-  // XPACK_WG workgroups per descriptor, descriptor = blockIdx.x / XPACK_WG (gridDim.x may be 2^31 - 1; gridDim.z is capped at 65535,
-  // which a level of a few thousand boxes with periodic images exceeds)
-  const PackDesc &D = descs[blockIdx.x / XPACK_WG];
-  const int nx = D.hi[0] - D.lo[0] + 1, ny = D.hi[1] - D.lo[1] + 1, nz = D.hi[2] - D.lo[2] + 1;
-  const long tot = (long)nx * ny * nz;
-  for (long t = (long)(blockIdx.x % XPACK_WG) * blockDim.x + threadIdx.x; t < tot; t += (long)XPACK_WG * blockDim.x) {
-    const int i = D.lo[0] + (int)(t % nx), j = D.lo[1] + (int)((t / nx) % ny), k = D.lo[2] + (int)(t / ((long)nx * ny));
-    const bool inside = i >= D.vlo[0] && i <= D.vhi[0] && j >= D.vlo[1] && j <= D.vhi[1] && k >= D.vlo[2] && k <= D.vhi[2];
-    if (inside) continue;
-    for (int c = 0; c < nc; c++) fv_at(D.fv, i, j, k, c) = buf[D.off + c * tot + t];
-  }
-}
 
 // all peers in one launch (the descriptor names its peer's buffer): with seven peers per rank a launch per peer and direction put 14 small
 // kernels around every ncclGroup
@@ -619,7 +606,7 @@ void xplan_cache_purge(unsigned long uid) {
 // or one -- three quarters of the copy kernel's workgroups
 void mf_fill_boundary(vdn_multifab *mf, bool faces_only) {
   if (mf->ng == 0) return;
-  static const bool faces_ok = !(vdn_env("VDN_FB_FACES") && atoi(vdn_env("VDN_FB_FACES")) == 0);
+  static const bool faces_ok = env_on("VDN_FB_FACES");
   faces_only = faces_only && faces_ok;
   const int ndflags = mf->nodal[0] | (mf->nodal[1] << 1) | (mf->nodal[2] << 2);
   auto plan = [&](int variant, const int *trim) -> XPlan * {

@@ -167,7 +167,7 @@ template <int NC> __global__ void __launch_bounds__(256) kk_slopes_my(FV s, FV s
   if (vmax) block_atomic_max(vmax, m);
 }
 static void launch_slopes(const FV &s, const FV sl[3], const GArgs &A, const Range3 &rg, int ncomp, double *vmax, hipStream_t st) {
-  static const bool marching = !(vdn_env("VDN_SLOPES_MARCH") && atoi(vdn_env("VDN_SLOPES_MARCH")) == 0);
+  static const bool marching = env_on("VDN_SLOPES_MARCH");
   if (marching && (ncomp == 2 || ncomp == 3) && s.a0 <= A.lo[0] - 3 && s.a1 <= A.lo[1] - 3 && s.a2 <= A.lo[2] - 3) {
     const int nx = rg.hi[0] - rg.lo[0] + 1, ny = rg.hi[1] - rg.lo[1] + 1, nz = rg.hi[2] - rg.lo[2] + 1;
     const int tiles = ((nx + 59) / 60) * ((ny + 3) / 4);
@@ -378,7 +378,7 @@ __global__ void __launch_bounds__(256) kk_mk_D(FV s, FV sl0, FV sl1, FV sl2, FV 
 // the computable region produce values nobody uses), the rare boundary work sits in one branch after it.
 // VDN_GODUNOV_BATCH=1 launches the descriptor (box-batched) kernels also for a level of one box. Measured at 256^3: they need
 // fewer VGPRs (mk_D<1> 116 vs 174) yet run slower there (scalar 6.6 vs 5.6 ms, velocity 10.0 vs 8.2 ms), so one box keeps the by-value kernels
-static bool batch_always() { static const bool b = vdn_env("VDN_GODUNOV_BATCH") && atoi(vdn_env("VDN_GODUNOV_BATCH")) != 0; return b; }
+static bool batch_always() { static const bool b = env_set("VDN_GODUNOV_BATCH"); return b; }
 // one launch per stage for all boxes (descriptors) or one set of launches per box (arguments by value)?  A level of an adaptive
 // hierarchy (hundreds of 16^3 .. 32^3 boxes) is launch-bound box by box; a level of a few large boxes -- 512^3 cut into eight 256^3
 // boxes -- runs faster box by box: the by-value kernels need fewer registers (measured,
@@ -445,7 +445,7 @@ struct FCell { double m_lo[3], m_up[3], s0, f, mr, Lb[3], Rb[3]; };      // a ce
 // results included: both are the correctly rounded value of the same real number), so where every dx is a power of two -- the unit cube on
 // 2^n cells, every level of a hierarchy over it -- the P2 kernels multiply.  The ten f64 divisions per cell and plane of the fused march were a
 // third of its f64 instructions (v_div_scale x 2, v_rcp, eight fma, v_div_fmas, v_div_fixup each).  Other spacings keep the division.
-static bool no_p2() { static const bool off = vdn_env("VDN_GOD_P2") && atoi(vdn_env("VDN_GOD_P2")) == 0; return off; }      // (the variants test: division path on power-of-two grids)
+static bool no_p2() { static const bool off = !env_on("VDN_GOD_P2"); return off; }      // (the variants test: division path on power-of-two grids)
 static bool is_pow2(double x) { int e; return x > 0.0 && std::frexp(x, &e) == 0.5; }
 #define DIVDX(x, d) (PW2 ? (x) * F.idx[d] : (x) / F.dx[d])
 template <bool PW2> DEVI void f_bases(const FArgs &F, FCell &P, const double sl[3]) {
@@ -485,7 +485,7 @@ static dim3 fused_grid(const Range3 &r, int &klen) {
 // the grid of a fused march whose remainder tile column runs in narrow segments (kk_mk_F_mc, kk_vp_F_mc): `full` 62-cell tile columns + one column of
 // segments of segw lanes; false when the box has no remainder column worth it.  The chunk count is chosen for the workgroups that do work.
 static bool fused_grid_cols(const Range3 &rf, dim3 &g, int &klen, int &full, int &segw) {
-  static const bool narrow_env = !(vdn_env("VDN_GOD_NARROW") && atoi(vdn_env("VDN_GOD_NARROW")) == 0);
+  static const bool narrow_env = env_on("VDN_GOD_NARROW");
   const int nx = rf.hi[0] - rf.lo[0] + 1, ny = rf.hi[1] - rf.lo[1] + 1, nz = rf.hi[2] - rf.lo[2] + 1;
   full = nx / FNX;
   const int rem = nx - full * FNX;
@@ -1034,7 +1034,7 @@ static void fused_grid_small(const Range3 &r, int &klen, int g[3], int &sw) {
   klen = (nz + chunks - 1) / chunks;
   g[0] = (nx + FNX - 1) / FNX; g[1] = (ny + FNY - 1) / FNY; g[2] = (nz + klen - 1) / klen;
   sw = 0;
-  static const bool narrow_on = !(vdn_env("VDN_GOD_SEGW") && atoi(vdn_env("VDN_GOD_SEGW")) == 0);
+  static const bool narrow_on = env_on("VDN_GOD_SEGW");
   if (!narrow_on) return;
   int best = g[0] * g[1];
   for (int w = 6; w <= 32; w++) {
@@ -1055,7 +1055,7 @@ template <class D> struct GodBatch {
       const dim3 *g[2] = { &gs, &gm }; int *o[2] = { q.gs, q.gm };
       for (int t = 0; t < 2; t++) { o[t][0] = g[t]->x; o[t][1] = g[t]->y; o[t][2] = g[t]->z; start[t * nb + b] = tot[t]; tot[t] += (int)(g[t]->x * g[t]->y * g[t]->z); }
       // the slope launch: the plane flattened over the workgroup when that takes fewer workgroups (kk_slopes_b: gs[1] = 0)
-      static const bool flat_on = !(vdn_env("VDN_BATCH_FLAT") && atoi(vdn_env("VDN_BATCH_FLAT")) == 0);
+      static const bool flat_on = env_on("VDN_BATCH_FLAT");
       const int pnx = q.rg.hi[0] - q.rg.lo[0] + 1, pny = q.rg.hi[1] - q.rg.lo[1] + 1;
       if (flat_on && pnx > 0 && pny > 0 && (pnx * pny + 255) / 256 < (int)(gs.x * gs.y)) {
         const int gfl = (pnx * pny + 255) / 256;
@@ -1218,7 +1218,7 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
       fused = fused_args(FA[c0], A, c0, s->fabs[ib], sl, um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], sedge[0]->fabs[ib], sedge[1]->fabs[ib], sedge[2]->fabs[ib],
                          flux[0]->fabs[ib], flux[1]->fabs[ib], flux[2]->fabs[ib]);
     if (fused) {                   // stages B + C + D in one march per component, boundary rules inside (see mk_F_m_body)
-      static const bool upd_env = !(vdn_env("VDN_GOD_UPDATE") && atoi(vdn_env("VDN_GOD_UPDATE")) == 0);
+      static const bool upd_env = env_on("VDN_GOD_UPDATE");
       bool do_upd = upd && upd_env;                  // (every box of a box-by-box level: the conditions are geometric and the same for all of them -- checked below)
       for (int c0 = 0; c0 < ncomp && do_upd; c0++) do_upd = fused_update_args(FA[c0], A, c0, upd->snew->fabs[ib], force->fabs[ib], *upd, ib);
       int klF;

@@ -13,6 +13,7 @@
 // The smoother is the kernel the north-star roofline is quoted on: ALGORITHMIC traffic per colour
 // pass = 48 B/cell (phi r+w 16, rh 8, bx/by/bz 24), see DESIGN.md.
 #include "vdn_dev.h"
+#include "mg_stop.h"
 #include "krylov_wg.h"
 #include <chrono>
 #include <tuple>
@@ -485,15 +486,33 @@ static inline void launch_gsrb_shell(const CLev &L, int color, hipStream_t st, i
   if (L.rho) hipLaunchKernelGGL(kk_cc_gsrb_shell<true>, g, dim3(64, 4, 1), 0, st, L, color, hm);
   else hipLaunchKernelGGL(kk_cc_gsrb_shell<false>, g, dim3(64, 4, 1), 0, st, L, color, hm);
 }
-static bool mac_kflip() { static const bool b = !(vdn_env("VDN_MAC_KFLIP") && atoi(vdn_env("VDN_MAC_KFLIP")) == 0); return b; }
+// ---- the launch-form switches of this file (runtime.hip's table), each read here ----------------------------------------------------------
+static bool mac_kflip()         { static const bool b = env_on("VDN_MAC_KFLIP"); return b; }
+static bool gsrb_pair_on()      { static const bool b = env_on("VDN_GSRB_PAIR"); return b; }
+static bool restrict_fused_on() { static const bool b = env_on("VDN_MG_RESTRICT_FUSED"); return b; }
+static bool prolong_fused_on()  { static const bool b = env_on("VDN_MG_PROLONG_FUSED"); return b; }
+static bool mac_split_on()      { static const bool b = env_on("VDN_MAC_SPLIT"); return b; }      // 0: the finest level of a MAC solve stays interleaved
+static long mac_split_min()     { static const long n = env_int("VDN_MAC_SPLIT_MIN", 1 << 23); return n; }
+static int  mac_slab_env()      { static const int k = env_int("VDN_MAC_SLAB", -1); return k; }
+static bool mg_lds_on()         { static const bool b = env_on("VDN_MG_LDS"); return b; }
+static bool mg_tailcycle_on()   { static const bool b = env_on("VDN_MG_TAILCYCLE"); return b; }
+static int  overlap_env()       { static const int v = env_int("VDN_OVERLAP", -1); return v; }
+// the 7-point operator reads no edge or corner ghost cell: the halo of phi carries the face cells only (VDN_CC_HALO_FACES=0: the whole shell)
+static bool cc_faces_only()     { static const bool b = env_on("VDN_CC_HALO_FACES"); return b; }
+// VDN_MAC_STORED_BETA=1: the finest level reads the stored face coefficients like the others (the measured alternative of DESIGN.md section 4)
+static bool beta_from_rho()     { static const bool b = !env_set("VDN_MAC_STORED_BETA"); return b; }
+// ---- the launch forms a level's extents allow, each said here -------------------------------------------------------------------------------
+// the 2 x 2 pair kernels (colour passes, residual): even in x and y, at least two waves wide (VDN_GSRB_PAIR=0: one cell per thread)
+static bool cc_pair_level(const CLev &L) { return gsrb_pair_on() && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[0] >= 128; }
+// ... and even in z: the pair kernels that also write or read the next level (residual + restriction, the correction inside the first sweep, the level by colour)
+static bool cc_pair_level_z(const CLev &L) { return cc_pair_level(L) && L.n[2] % 2 == 0; }
 static inline void launch_gsrb(const CLev &L, int color, hipStream_t st, int interior_only = 0) {
   const dim3 blk(64, 4, 1), g((unsigned)(((L.n[0] + 1) / 2 + 63) / 64), (unsigned)((L.n[1] + 3) / 4), (unsigned)L.n[2]);
-  static const bool paired = !(vdn_env("VDN_GSRB_PAIR") && atoi(vdn_env("VDN_GSRB_PAIR")) == 0);
   const int kdown = (mac_kflip() && (color & 1)) ? 1 : 0;
-  if (L.rho && paired && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[0] >= 128)
+  if (L.rho && cc_pair_level(L))
     hipLaunchKernelGGL(kk_cc_gsrb_rho_pair, dim3((unsigned)((L.n[0] / 2 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)L.n[2]), blk, 0, st, L, color, interior_only, kdown);
   else if (L.rho) hipLaunchKernelGGL(kk_cc_gsrb_rho, g, blk, 0, st, L, color, interior_only);
-  else if (paired && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[0] >= 128)
+  else if (cc_pair_level(L))
     hipLaunchKernelGGL(kk_cc_gsrb_pair, dim3((unsigned)((L.n[0] / 2 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)L.n[2]), blk, 0, st, L, color, interior_only, kdown);
   else hipLaunchKernelGGL(kk_cc_gsrb, g, blk, 0, st, L, color, interior_only);
 }
@@ -1184,9 +1203,8 @@ static dim3 g3(int nx, int ny, int nz, dim3 b) { return dim3((nx + b.x - 1) / b.
 static const dim3 BLK(64, 4, 1);
 
 // ---- macproject's finest level by colour (kk_cc_gsrb_rho_split): host side --------------------------------------------------------------------
-// The level array keeps rhs and rho (level 1's coefficients, the nested iteration and the residual read them there); phi lives in the split arrays
-// from cc_to_split (after the nested iteration) to cc_from_split (before the residual pass, which reads the level array, and at the end of the solve).
-static bool mac_split_on() { static const bool b = !(vdn_env("VDN_MAC_SPLIT") && atoi(vdn_env("VDN_MAC_SPLIT")) == 0); return b; }
+// The level array keeps rhs and rho (level 1's coefficients and the nested iteration read them there); phi lives in the split arrays
+// from cc_to_split (after the nested iteration) to cc_from_split (at the end of the solve).
 // hm: the shell behind these faces is left to kk_cc_gsrb_split_shell (cc_gsrb_d's overlap of the exchange with the pass)
 template <int ADD> static inline void launch_gsrb_split(const CBox &B, int color, hipStream_t st, const CLev &C, int k0 = 0, int k1 = -1, int hm = 0) {
   const CLev &L = B.L;
@@ -1224,24 +1242,19 @@ static void split_halo(const CDLev &DL, int colour, hipStream_t st = nullptr) { 
 // and enough cells on this rank that the level does not live in the caches anyway.  Round 5 took one box without periodic faces only; round 6: any box list, periodic faces,
 // several ranks -- the ghost exchange runs on the split arrays themselves (cc_split_setup).
 static bool cc_split_ok(const CCMG &M) {
-  static const bool dflt = !(vdn_env("VDN_GSRB_PAIR") && atoi(vdn_env("VDN_GSRB_PAIR")) == 0) && !(vdn_env("VDN_MG_RESTRICT_FUSED") && atoi(vdn_env("VDN_MG_RESTRICT_FUSED")) == 0) &&
-                           !(vdn_env("VDN_MG_PROLONG_FUSED") && atoi(vdn_env("VDN_MG_PROLONG_FUSED")) == 0);
-  if (!mac_split_on() || !dflt || M.dlev.size() < 2 || ctx().prm.mg_nu1 < 1 || ctx().prm.mg_nu2 < 1) return false;
+  if (!mac_split_on() || !restrict_fused_on() || !prolong_fused_on() || M.dlev.size() < 2 || ctx().prm.mg_nu1 < 1 || ctx().prm.mg_nu2 < 1) return false;
   const CDLev &D0 = M.dlev[0];
   if (D0.boxes.empty() || D0.boxes.size() != M.dlev[1].boxes.size()) return false;
-  static const bool halo_ok = !(vdn_env("VDN_MAC_SPLIT_HALO") && atoi(vdn_env("VDN_MAC_SPLIT_HALO")) == 0);      // 0: round 5's rule (one box, no exchange)
-  if (D0.halo && !halo_ok) return false;
   long cells = 0;
   for (const CBox &B : D0.boxes) {
     const CLev &L = B.L;
-    if (!((L.rho || (L.cmu > 0.0 && L.alpha)) && L.n[0] % 4 == 0 && L.n[1] % 2 == 0 && L.n[2] % 2 == 0 && L.n[0] >= 128)) return false;
+    if (!((L.rho || (L.cmu > 0.0 && L.alpha)) && cc_pair_level_z(L) && L.n[0] % 4 == 0)) return false;
     for (int d = 0; d < 3; d++) if (B.lo[d] & 1) return false;
     cells += (long)L.n[0] * L.n[1] * L.n[2];
   }
   for (int d = 0; d < 3; d++) if (D0.ng[d] & 1) return false;
   // (128^3 stays interleaved: its arrays live in the caches, the conversions cost more than the passes gain -- 6.98 against 7.21 ms per step)
-  static const long nmin = vdn_env("VDN_MAC_SPLIT_MIN") ? atol(vdn_env("VDN_MAC_SPLIT_MIN")) : (1L << 23);
-  return cells >= nmin;
+  return cells >= mac_split_min();
 }
 static int g_mac_level_form = 0;
 extern "C" int vdn_last_mac_level_form(void) { return g_mac_level_form; }
@@ -1288,8 +1301,6 @@ static FV cc_phi_view(const CLev &L, const int lo[3]) {
   return f;
 }
 
-// the 7-point operator reads no edge or corner ghost cell: the halo of phi carries the face cells only (VDN_CC_HALO_FACES=0: the whole shell)
-static bool cc_faces_only() { static const bool f = !(vdn_env("VDN_CC_HALO_FACES") && atoi(vdn_env("VDN_CC_HALO_FACES")) == 0); return f; }
 // plans for the per-level phi halos are cached across solves: arena addresses repeat from step to step
 // sig: a hash of EVERY local box's phi address -- the plan bakes those addresses in, and two solves on one level that start at the same
 // arena offset but differ in layout (6 arrays per box without alpha, 7 with) agree on the first box only
@@ -1331,7 +1342,7 @@ static XPlan *cc_split_plan(const CDLev &D0, int colour, const int per[3]) {
 // The arithmetic is that of the single-box hierarchy wherever the cut is made (global colours, global bottom-sweep counts): tests/test_multirank_gpu.py compares ranks that
 // cut at 64 with one rank that cuts at 128, bit for bit.  VDN_MG_AGGLOM (testing build): a fixed value.
 int mg_agglom(const vdn_layout *la, int lev) {
-  static const int env = vdn_env("VDN_MG_AGGLOM") ? atoi(vdn_env("VDN_MG_AGGLOM")) : 0;
+  static const int env = env_int("VDN_MG_AGGLOM", 0);
   if (env > 0) return env;
   bool all_local = true;
   for (int o : la->owner[lev]) if (o != ctx().rank) all_local = false;
@@ -1471,7 +1482,7 @@ static void cc_gsrb_d(CCMG &M, CDLev &DL, int nsweeps) {
   // traffic -- pack kernels, the ncclSend / ncclRecv group, box-to-box copies, unpack kernels -- runs on ctx().halo_stream while the
   // launch stream updates the cells that read no ghost value; the one-cell shell follows when the halo has landed
   // Only where the pass is long enough to hide something: boxes of at least 2^20 cells (a 64^3 pass takes 5 us).
-  static const int ov_env = vdn_env("VDN_OVERLAP") ? atoi(vdn_env("VDN_OVERLAP")) : -1;
+  const int ov_env = overlap_env();
   static const long ov_min = 1L << 20;
   bool overlap = DL.halo && (ov_env == 1 || (ov_env != 0 && xplan_has_remote(DL.halo)));
   if (overlap) {
@@ -1516,28 +1527,22 @@ static void cc_residual_d(CCMG &M, CDLev &DL, bool norm, bool reduce = true) {  
   if (norm) HIPCHK(hipMemsetAsync(M.d_nrm, 0, sizeof(double), ctx().stream));
   DL.res_restricted = false;
   if (DL.split) {
-    static const bool split_res = !(vdn_env("VDN_MAC_SPLIT") && atoi(vdn_env("VDN_MAC_SPLIT")) == 2);      // 2: only the colour passes run on the split arrays
-    if (split_res) {
-      // the residual reads both colours' ghost entries: colour 0's were exchanged before the last pass (of colour 1) and have not changed since
-      split_halo(DL, 1);
-      for (size_t b = 0; b < DL.boxes.size(); b++) {
-        const CBox &B = DL.boxes[b]; const CLev &L = B.L;
-        launch_residual_split_rst(L, B.sp, norm ? M.d_nrm : nullptr, M.dlev[1].boxes[b].L, 0, L.n[2] / 2, ctx().stream);
-      }
-      DL.res_restricted = true;
-      if (norm && reduce) comm_allreduce_max_dev(M.d_nrm, 1);
-      return;
+    // the residual reads both colours' ghost entries: colour 0's were exchanged before the last pass (of colour 1) and have not changed since
+    split_halo(DL, 1);
+    for (size_t b = 0; b < DL.boxes.size(); b++) {
+      const CBox &B = DL.boxes[b]; const CLev &L = B.L;
+      launch_residual_split_rst(L, B.sp, norm ? M.d_nrm : nullptr, M.dlev[1].boxes[b].L, 0, L.n[2] / 2, ctx().stream);
     }
-    cc_from_split(DL);
+    DL.res_restricted = true;
+    if (norm && reduce) comm_allreduce_max_dev(M.d_nrm, 1);
+    return;
   }
   cc_halo(M, DL);
   {   // the finest level of a MAC solve in one box: residual and restriction in one pass (kk_cc_residual_rho_pair_rst); cc_restrict_down then skips
-    static const bool fuse = !(vdn_env("VDN_MG_RESTRICT_FUSED") && atoi(vdn_env("VDN_MG_RESTRICT_FUSED")) == 0);
-    static const bool paired0 = !(vdn_env("VDN_GSRB_PAIR") && atoi(vdn_env("VDN_GSRB_PAIR")) == 0);
     const size_t l = &DL - &M.dlev[0];
-    if (fuse && paired0 && DL.single_box && DL.boxes.size() == 1 && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
+    if (restrict_fused_on() && DL.single_box && DL.boxes.size() == 1 && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
       const CLev &L = DL.boxes[0].L;
-      if (L.rho && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[2] % 2 == 0 && L.n[0] >= 128) {
+      if (L.rho && cc_pair_level_z(L)) {
         const dim3 g((unsigned)((L.n[0] / 2 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)std::min(L.n[2] / 2, 16));
         hipLaunchKernelGGL(kk_cc_residual_rho_pair_rst, g, BLK, 0, ctx().stream, L, norm ? M.d_nrm : nullptr, M.dlev[l + 1].boxes[0].L);
         DL.res_restricted = true;
@@ -1548,16 +1553,12 @@ static void cc_residual_d(CCMG &M, CDLev &DL, bool norm, bool reduce = true) {  
   }
   for (const CBox &B : DL.boxes) {
     const dim3 g = g3(B.L.n[0], B.L.n[1], norm ? std::min(B.L.n[2], 16) : B.L.n[2], BLK);
-    static const bool paired = !(vdn_env("VDN_GSRB_PAIR") && atoi(vdn_env("VDN_GSRB_PAIR")) == 0);
-    if (B.L.rho && paired && B.L.n[0] % 2 == 0 && B.L.n[1] % 2 == 0 && B.L.n[0] >= 128)
+    if (B.L.rho && cc_pair_level(B.L))
       hipLaunchKernelGGL(kk_cc_residual_rho_pair, dim3((unsigned)((B.L.n[0] / 2 + 63) / 64), (unsigned)((B.L.n[1] / 2 + 3) / 4), g.z), BLK, 0, ctx().stream, B.L, norm ? M.d_nrm : nullptr);
     else if (B.L.rho) hipLaunchKernelGGL(kk_cc_residual_rho, g, BLK, 0, ctx().stream, B.L, norm ? M.d_nrm : nullptr);
     else hipLaunchKernelGGL(kk_cc_residual, g, BLK, 0, ctx().stream, B.L, norm ? M.d_nrm : nullptr);
   }
   if (norm && reduce) comm_allreduce_max_dev(M.d_nrm, 1);
-}
-static double read_scalar(double *d) {
-  return read_scalar1(d);
 }
 
 // ---- the replicated tail: single-box V-cycle --------------------------------------------------------------------
@@ -1585,8 +1586,7 @@ static void cc_bottom_t(const CCMG &M, const CLev &L) {      // max(nub, N^2) sw
 // The small end of the hierarchy in one launch (kk_cc_tailcycle): distributed levels dl .. end when they are one box of at most 8^3 cells
 // each (dl < 0: none), then the replicated tail levels tl .. end (one rank and one box: the gather between the two is the plain restriction).
 static bool cc_small_end(const CCMG &M, int dl, int tl) {
-  static const bool on = !(vdn_env("VDN_MG_TAILCYCLE") && atoi(vdn_env("VDN_MG_TAILCYCLE")) == 0);
-  if (!on) return false;
+  if (!mg_tailcycle_on()) return false;
   static const long tail_cells = SMALL_LEVEL_CELLS;     // largest level the one-workgroup cycle takes (measured: 16^3 no gain, MAC 15.33 -> 15.39 ms)
   const vdn_params &P = ctx().prm;
   CcTailArgs T; memset(&T, 0, sizeof T);
@@ -1616,9 +1616,8 @@ static bool cc_small_end(const CCMG &M, int dl, int tl) {
 // may tail level l run as kk_cc_lds_down / kk_cc_lds_up?  (round 6: the replicated levels of 16^3 .. 64^3 cells take the two-launch form of the one-box hierarchy too --
 // they were eleven launches per level and cycle; cc_lds_level's conditions)
 static bool cc_lds_tail_level(const CCMG &M, int l) {
-  static const bool on = !(vdn_env("VDN_MG_LDS") && atoi(vdn_env("VDN_MG_LDS")) == 0);
   const vdn_params &P = ctx().prm;
-  if (!on || l + 1 >= (int)M.tail.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
+  if (!mg_lds_on() || l + 1 >= (int)M.tail.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
   const CLev &L = M.tail[l], &C = M.tail[l + 1];
   if (L.rho) return false;
   for (int d = 0; d < 3; d++) if (L.n[d] % LT || L.n[d] < 2 * LT || L.n[d] > 64 || C.n[d] * 2 != L.n[d]) return false;
@@ -1693,11 +1692,8 @@ static void cc_prolong_smooth(CCMG &M, int l, int nsweeps) {
     if (nsweeps > 1) cc_gsrb_d(M, DL, nsweeps - 1);
     return;
   }
-  static const bool fuse = !(vdn_env("VDN_MG_PROLONG_FUSED") && atoi(vdn_env("VDN_MG_PROLONG_FUSED")) == 0);
-  static const bool paired = !(vdn_env("VDN_GSRB_PAIR") && atoi(vdn_env("VDN_GSRB_PAIR")) == 0);
-  const bool ok = fuse && paired && nsweeps >= 1 && DL.single_box && DL.boxes.size() == 1 && !DL.halo && l + 1 < (int)M.dlev.size() && M.dlev[l + 1].boxes.size() == 1 &&
-                  !(M.per[0] || M.per[1] || M.per[2]) && DL.boxes[0].L.rho &&
-                  DL.boxes[0].L.n[0] % 2 == 0 && DL.boxes[0].L.n[1] % 2 == 0 && DL.boxes[0].L.n[2] % 2 == 0 && DL.boxes[0].L.n[0] >= 128;
+  const bool ok = prolong_fused_on() && nsweeps >= 1 && DL.single_box && DL.boxes.size() == 1 && !DL.halo && l + 1 < (int)M.dlev.size() && M.dlev[l + 1].boxes.size() == 1 &&
+                  !(M.per[0] || M.per[1] || M.per[2]) && DL.boxes[0].L.rho && cc_pair_level_z(DL.boxes[0].L);
   if (!ok) { cc_prolong_up(M, l); cc_gsrb_d(M, DL, nsweeps); return; }
   const CLev &L = DL.boxes[0].L, &C = M.dlev[l + 1].boxes[0].L;
   const dim3 g((unsigned)((L.n[0] / 2 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)L.n[2]), blk(64, 4, 1);
@@ -1718,8 +1714,7 @@ static void cc_prolong_smooth(CCMG &M, int l, int nsweeps) {
 // the planes whose pass traffic (24 B per cell of the level) adds up to ~200 MB -- what stays in the cache between two passes over it; at most half the level.
 // 512^3 (plane = 6.3 MB; MAC solve per step): whole-level launches 69.8 ms; slabs of 16 / 24 / 28 / 32 / 40 / 64 / 256 planes 67.9 / 65.2 / 64.5 / 64.7 / 65.2 / 67.5 / 69.1 ms.
 static int mac_slab(const CLev &L) {
-  static const int k = vdn_env("VDN_MAC_SLAB") ? atoi(vdn_env("VDN_MAC_SLAB")) : -1;
-  if (k >= 0) return k;
+  if (mac_slab_env() >= 0) return mac_slab_env();
   const long fit = (long)(200.0e6 / (24.0 * L.n[0] * L.n[1]));
   return (int)std::max(8L, std::min((long)(L.n[2] + 1) / 2, fit));
 }
@@ -1756,19 +1751,17 @@ static void cc_split_run(CCMG &M, CDLev &DL, bool prolong, int nsweeps, bool res
 static void cc_fine_seq(CCMG &M, bool after_coarse, bool residual, bool norm, bool reduce = true) {
   const vdn_params &P = ctx().prm;
   CDLev &D0 = M.dlev[0];
-  static const bool split_res = !(vdn_env("VDN_MAC_SPLIT") && atoi(vdn_env("VDN_MAC_SPLIT")) == 2);
   // (the slab schedule: one box without an exchange between the passes)
-  if (D0.split && !D0.halo && D0.boxes.size() == 1 && mac_slab(D0.boxes[0].L) > 0 && split_res && residual) { cc_split_run(M, D0, after_coarse, (after_coarse ? P.mg_nu2 : 0) + P.mg_nu1, true, norm, reduce); return; }
+  if (D0.split && !D0.halo && D0.boxes.size() == 1 && mac_slab(D0.boxes[0].L) > 0 && residual) { cc_split_run(M, D0, after_coarse, (after_coarse ? P.mg_nu2 : 0) + P.mg_nu1, true, norm, reduce); return; }
   if (after_coarse) cc_prolong_smooth(M, 0, P.mg_nu2);
   cc_gsrb_d(M, D0, P.mg_nu1);
   if (residual) cc_residual_d(M, D0, norm, reduce);
 }
 // may level l >= 1 of a V-cycle run as kk_cc_lds_down / kk_cc_lds_up?  (VDN_MG_LDS=0: never; extents up to 64)
 static bool cc_lds_level(const CCMG &M, int l) {
-  static const bool on = !(vdn_env("VDN_MG_LDS") && atoi(vdn_env("VDN_MG_LDS")) == 0);
   static const int nmax_ = 64;                 // (measured in round 5: the 128^3 level of a 256^3 solve as LDS tiles too, MAC 8.98 -> 10.33 ms per step)
   const vdn_params &P = ctx().prm;
-  if (!on || l < 1 || l + 1 >= (int)M.dlev.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
+  if (!mg_lds_on() || l < 1 || l + 1 >= (int)M.dlev.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
   const CDLev &D = M.dlev[l], &DC = M.dlev[l + 1];
   if (!(D.single_box && D.boxes.size() == 1 && !D.halo && DC.single_box && DC.boxes.size() == 1)) return false;
   const CLev &L = D.boxes[0].L;
@@ -1920,12 +1913,8 @@ static unsigned long long cc_graph_key(const CCMG &M, int what) {
   if (M.kry_w) { k.put(M.kry_w); k.put(M.kry_method); k.put(M.kry_singular); k.put(M.kry_maxit); k.put(P.mg_bottom_solver_eps); }
   return k.h;
 }
-static bool cc_graphable(const CCMG &M) {
-  (void)M;
-  return graphs_enabled();
-}
 template <class Body> static void cc_run_cycle(CCMG &M, int what, Body body) {
-  if (!cc_graphable(M)) { body(); return; }
+  if (!graphs_enabled()) { body(); return; }
   const unsigned long long key = cc_graph_key(M, what);
   if (graph_replay(key)) return;
   graph_begin();
@@ -1939,25 +1928,63 @@ static int cc_fmg_what(const int bc[3][2]) {
   for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) code = code * 4 + (bc[d][sd] + 1);
   return 3 + 4 * code;
 }
-// VDN_MAC_STORED_BETA=1: the finest level reads the stored face coefficients like the others (the measured alternative of DESIGN.md section 4)
-static bool beta_from_rho() { static const bool b = !(vdn_env("VDN_MAC_STORED_BETA") && atoi(vdn_env("VDN_MAC_STORED_BETA")) != 0); return b; }
+// boundary folding only on faces that are DOMAIN faces: the boundary types of local box b of a level's multifab (VDN_BC_INT on the faces inside the domain)
+struct CcFaces { int e[3][2]; };
+static CcFaces cc_domain_faces(const vdn_multifab *mf, size_t b, const int bc[3][2]) {
+  const vdn_box &bx = mf->vbox[b], &pd = mf->la->pd[mf->lev];
+  CcFaces F;
+  for (int d = 0; d < 3; d++) {
+    F.e[d][0] = (bx.lo[d] == pd.lo[d]) ? bc[d][0] : VDN_BC_INT;
+    F.e[d][1] = (bx.hi[d] == pd.hi[d]) ? bc[d][1] : VDN_BC_INT;
+  }
+  return F;
+}
+// the coefficients of every level below the finest, from the finest level's: the distributed levels box by box (from_rho: level 1 from level 0's density), the first
+// tail level gathered from the last distributed one, the rest of the tail; with alpha: the 8-cell means of alpha alongside
+static void cc_coarsen_coeffs(CCMG &M, bool has_alpha, bool from_rho) {
+  for (size_t l = 1; l < M.dlev.size(); l++)
+    for (size_t b = 0; b < M.dlev[l].boxes.size(); b++) {
+      const CLev &F = M.dlev[l - 1].boxes[b].L, &C = M.dlev[l].boxes[b].L;
+      if (l == 1 && from_rho) hipLaunchKernelGGL(kk_cc_coarsen_b_rho, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, F, C);
+      else hipLaunchKernelGGL(kk_cc_coarsen_b, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, F, C);
+      if (has_alpha) hipLaunchKernelGGL(kk_cc_coarsen_cell, g3(C.n[0], C.n[1], C.n[2], BLK), BLK, 0, ctx().stream, F, (const double *)F.alpha, C, C.alpha);
+    }
+  if (M.tail.empty()) return;
+  CDLev &DL = M.dlev.back();
+  for (size_t b = 0; b < DL.boxes.size(); b++) {
+    const CLev &F = DL.boxes[b].L;
+    const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
+    hipLaunchKernelGGL(kk_cc_coarsen_b_pack, g3(nx + 1, ny + 1, nz + 1, BLK), BLK, 0, ctx().stream, F, M.sendbuf, M.loc_off_b[b], nx, ny, nz);
+  }
+  comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_b);
+  hipLaunchKernelGGL(kk_cc_unpack_b, dim3(4, 1, (unsigned)M.gb_b.size()), dim3(256), 0, ctx().stream, M.tail[0], M.recvbuf, M.d_gb_b);
+  if (has_alpha) {                   // alpha of the first tail level: per-box 8-cell means, gathered like the residual
+    for (size_t b = 0; b < DL.boxes.size(); b++) {
+      const CLev &F = DL.boxes[b].L;
+      const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
+      hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, ctx().stream, F, (const double *)F.alpha, M.sendbuf, M.loc_off_rh[b], nx, ny, nz);
+    }
+    comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_rh);
+    hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.gb_rh.size()), dim3(256), 0, ctx().stream, M.tail[0], M.tail[0].alpha, M.recvbuf, M.d_gb_rh);
+  }
+  for (size_t l = 1; l < M.tail.size(); l++) {
+    const CLev &C = M.tail[l];
+    hipLaunchKernelGGL(kk_cc_coarsen_b, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, M.tail[l - 1], C);
+    if (has_alpha) hipLaunchKernelGGL(kk_cc_coarsen_cell, g3(C.n[0], C.n[1], C.n[2], BLK), BLK, 0, ctx().stream, M.tail[l - 1], (const double *)M.tail[l - 1].alpha, C, C.alpha);
+  }
+}
 static void cc_setup(CCMG &M, vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *alpha, vdn_multifab **beta, const double *dx, const int bc[3][2],
                      const vdn_multifab *rho = nullptr, double const_beta = 0.0) {
   REQUIRE(phi->ng >= 1, "cc multigrid: phi needs one ghost cell");
   cc_build(M, rh, dx, bc, alpha != nullptr);
-  const vdn_layout *la = rh->la; const int lev = rh->lev;
   CDLev &D0 = M.dlev[0];
   // beta = 2 / (rho_i + rho_i-1) (the MAC projection): the finest level recomputes it from rho; not with the fused sweeps (they read b)
   const bool from_rho = rho && !alpha && beta_from_rho() && rho->ng >= 1;
   for (size_t b = 0; b < D0.boxes.size(); b++) {
     CLev &L0 = D0.boxes[b].L;
     const vdn_box &bx = rh->vbox[b];
-    // boundary folding only on faces that are DOMAIN faces
-    int e[3][2];
-    for (int d = 0; d < 3; d++) {
-      e[d][0] = (bx.lo[d] == la->pd[lev].lo[d]) ? bc[d][0] : VDN_BC_INT;
-      e[d][1] = (bx.hi[d] == la->pd[lev].hi[d]) ? bc[d][1] : VDN_BC_INT;
-    }
+    const CcFaces F = cc_domain_faces(rh, b, bc);
+    const auto &e = F.e;
     hipLaunchKernelGGL(kk_cc_load, g3(L0.n[0] + 1, L0.n[1] + 1, L0.n[2] + 1, BLK), BLK, 0, ctx().stream, L0, rh->fabs[b], phi->fabs[b],
                        alpha ? alpha->fabs[b] : rh->fabs[b], beta[0]->fabs[b], beta[1]->fabs[b], beta[2]->fabs[b], bx.lo[0], bx.lo[1], bx.lo[2],
                        e[0][0], e[0][1], e[1][0], e[1][1], e[2][0], e[2][1]);
@@ -1974,36 +2001,7 @@ static void cc_setup(CCMG &M, vdn_multifab *rh, vdn_multifab *phi, const vdn_mul
       for (int d = 0; d < 3; d++) { L0.fold[d][0] = e[d][0]; L0.fold[d][1] = e[d][1]; }
     }
   }
-  for (size_t l = 1; l < M.dlev.size(); l++)
-    for (size_t b = 0; b < M.dlev[l].boxes.size(); b++) {
-      const CLev &C = M.dlev[l].boxes[b].L;
-      hipLaunchKernelGGL(kk_cc_coarsen_b, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, M.dlev[l - 1].boxes[b].L, C);
-      if (alpha) hipLaunchKernelGGL(kk_cc_coarsen_cell, g3(C.n[0], C.n[1], C.n[2], BLK), BLK, 0, ctx().stream, M.dlev[l - 1].boxes[b].L, (const double *)M.dlev[l - 1].boxes[b].L.alpha, C, C.alpha);
-    }
-  if (!M.tail.empty()) {
-    CDLev &DL = M.dlev.back();
-    for (size_t b = 0; b < DL.boxes.size(); b++) {
-      const CLev &F = DL.boxes[b].L;
-      const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
-      hipLaunchKernelGGL(kk_cc_coarsen_b_pack, g3(nx + 1, ny + 1, nz + 1, BLK), BLK, 0, ctx().stream, F, M.sendbuf, M.loc_off_b[b], nx, ny, nz);
-    }
-    comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_b);
-    hipLaunchKernelGGL(kk_cc_unpack_b, dim3(4, 1, (unsigned)M.gb_b.size()), dim3(256), 0, ctx().stream, M.tail[0], M.recvbuf, M.d_gb_b);
-    if (alpha) {                       // alpha of the first tail level: per-box 8-cell means, gathered like the residual
-      for (size_t b = 0; b < DL.boxes.size(); b++) {
-        const CLev &F = DL.boxes[b].L;
-        const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
-        hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, ctx().stream, F, (const double *)F.alpha, M.sendbuf, M.loc_off_rh[b], nx, ny, nz);
-      }
-      comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_rh);
-      hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.gb_rh.size()), dim3(256), 0, ctx().stream, M.tail[0], M.tail[0].alpha, M.recvbuf, M.d_gb_rh);
-    }
-    for (size_t l = 1; l < M.tail.size(); l++) {
-      const CLev &C = M.tail[l];
-      hipLaunchKernelGGL(kk_cc_coarsen_b, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, M.tail[l - 1], C);
-      if (alpha) hipLaunchKernelGGL(kk_cc_coarsen_cell, g3(C.n[0], C.n[1], C.n[2], BLK), BLK, 0, ctx().stream, M.tail[l - 1], (const double *)M.tail[l - 1].alpha, C, C.alpha);
-    }
-  }
+  cc_coarsen_coeffs(M, alpha != nullptr, false);
 }
 // set-up of macproject's fast path: levels from the layout of rho, level 0 = rho + the right-hand side from the MAC field, level 1 from rho,
 // the rest as cc_setup; returns max |rh| (all ranks)
@@ -2011,17 +2009,13 @@ static double cc_setup_fast(CCMG &M, CcFast *fast, const double *dx, const int b
   const vdn_multifab *rho = fast->rho;
   cc_build(M, rho, dx, bc, false);
   REQUIRE(M.dlev.size() >= 2, "cc_setup_fast: needs a second distributed level");
-  const vdn_layout *la = rho->la; const int lev = rho->lev;
   CDLev &D0 = M.dlev[0];
   HIPCHK(hipMemsetAsync(M.d_nrm, 0, sizeof(double), ctx().stream));
   for (size_t b = 0; b < D0.boxes.size(); b++) {
     CLev &L0 = D0.boxes[b].L;
     const vdn_box &bx = rho->vbox[b];
-    int e[3][2];
-    for (int d = 0; d < 3; d++) {
-      e[d][0] = (bx.lo[d] == la->pd[lev].lo[d]) ? bc[d][0] : VDN_BC_INT;
-      e[d][1] = (bx.hi[d] == la->pd[lev].hi[d]) ? bc[d][1] : VDN_BC_INT;
-    }
+    const CcFaces F = cc_domain_faces(rho, b, bc);
+    const auto &e = F.e;
     double *r = (double *)arena_alloc(sizeof(double) * L0.sz);
     hipLaunchKernelGGL(kk_cc_load_rho, g3(L0.n[0] + 2, L0.n[1] + 2, L0.n[2] + 2, BLK), BLK, 0, ctx().stream, L0, r, rho->fabs[b], bx.lo[0], bx.lo[1], bx.lo[2]);
     L0.rho = r;
@@ -2031,40 +2025,17 @@ static double cc_setup_fast(CCMG &M, CcFast *fast, const double *dx, const int b
   }
   comm_allreduce_max_dev(M.d_nrm, 1);
   const double bnorm = read_scalar1(M.d_nrm);
-  for (size_t l = 1; l < M.dlev.size(); l++)
-    for (size_t b = 0; b < M.dlev[l].boxes.size(); b++) {
-      const CLev &C = M.dlev[l].boxes[b].L;
-      if (l == 1) hipLaunchKernelGGL(kk_cc_coarsen_b_rho, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, M.dlev[0].boxes[b].L, C);
-      else hipLaunchKernelGGL(kk_cc_coarsen_b, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, M.dlev[l - 1].boxes[b].L, C);
-    }
-  if (!M.tail.empty()) {
-    CDLev &DL = M.dlev.back();
-    for (size_t b = 0; b < DL.boxes.size(); b++) {
-      const CLev &F = DL.boxes[b].L;
-      const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
-      hipLaunchKernelGGL(kk_cc_coarsen_b_pack, g3(nx + 1, ny + 1, nz + 1, BLK), BLK, 0, ctx().stream, F, M.sendbuf, M.loc_off_b[b], nx, ny, nz);
-    }
-    comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_b);
-    hipLaunchKernelGGL(kk_cc_unpack_b, dim3(4, 1, (unsigned)M.gb_b.size()), dim3(256), 0, ctx().stream, M.tail[0], M.recvbuf, M.d_gb_b);
-    for (size_t l = 1; l < M.tail.size(); l++) {
-      const CLev &C = M.tail[l];
-      hipLaunchKernelGGL(kk_cc_coarsen_b, g3(C.n[0] + 1, C.n[1] + 1, C.n[2] + 1, BLK), BLK, 0, ctx().stream, M.tail[l - 1], C);
-    }
-  }
+  cc_coarsen_coeffs(M, false, true);
   return bnorm;
 }
 // a kept hierarchy (coefficients on every level stay): the finest level takes a new right-hand side and initial guess
 static void cc_reload(CCMG &M, vdn_multifab *rh, vdn_multifab *phi, const int bc[3][2], bool zero_guess = false) {
-  const vdn_layout *la = rh->la; const int lev = rh->lev;
   CDLev &D0 = M.dlev[0];
   for (size_t b = 0; b < D0.boxes.size(); b++) {
     CLev &L0 = D0.boxes[b].L;
     const vdn_box &bx = rh->vbox[b];
-    int e[3][2];
-    for (int d = 0; d < 3; d++) {
-      e[d][0] = (bx.lo[d] == la->pd[lev].lo[d]) ? bc[d][0] : VDN_BC_INT;
-      e[d][1] = (bx.hi[d] == la->pd[lev].hi[d]) ? bc[d][1] : VDN_BC_INT;
-    }
+    const CcFaces F = cc_domain_faces(rh, b, bc);
+    const auto &e = F.e;
     if (zero_guess) { if (!D0.split) HIPCHK(hipMemsetAsync(L0.phi, 0, sizeof(double) * L0.sz, ctx().stream)); }      // (the caller's phi is neither zero-filled nor read; by colour: the split arrays hold phi)
     else hipLaunchKernelGGL(kk_cc_load_phi, g3(L0.n[0], L0.n[1], L0.n[2], BLK), BLK, 0, ctx().stream, L0, phi->fabs[b], bx.lo[0], bx.lo[1], bx.lo[2]);
     hipLaunchKernelGGL(kk_cc_load_rh, g3(L0.n[0], L0.n[1], L0.n[2], BLK), BLK, 0, ctx().stream, L0, rh->fabs[b], phi->fabs[b],
@@ -2078,29 +2049,33 @@ static void cc_reload(CCMG &M, vdn_multifab *rh, vdn_multifab *phi, const int bc
 static void cc_store(CCMG &M, vdn_multifab *phi, const int bc[3][2], vdn_multifab *add_to = nullptr) {
   CDLev &D0 = M.dlev[0];
   cc_halo(M, D0);
-  const vdn_layout *la = phi->la; const int lev = phi->lev;
   for (size_t b = 0; b < D0.boxes.size(); b++) {
     const CLev &L0 = D0.boxes[b].L;
     const vdn_box &bx = phi->vbox[b];
-    int e[3][2];
-    for (int d = 0; d < 3; d++) {
-      e[d][0] = (bx.lo[d] == la->pd[lev].lo[d]) ? bc[d][0] : VDN_BC_INT;
-      e[d][1] = (bx.hi[d] == la->pd[lev].hi[d]) ? bc[d][1] : VDN_BC_INT;
-    }
+    const CcFaces F = cc_domain_faces(phi, b, bc);
+    const auto &e = F.e;
     hipLaunchKernelGGL(kk_cc_store, g3(L0.n[0] + 2, L0.n[1] + 2, L0.n[2] + 2, BLK), BLK, 0, ctx().stream, L0, phi->fabs[b],
                        bx.lo[0], bx.lo[1], bx.lo[2], e[0][0], e[0][1], e[1][0], e[1][1], e[2][0], e[2][1], add_to ? 1 : 0, add_to ? add_to->fabs[b] : phi->fabs[b]);
   }
 }
 
+// One V-cycle of a solve's hierarchy from its finest level down and up again: pre-smoothing and residual, the coarse correction, post-smoothing
+static void cc_coarse_correction(CCMG &M) {
+  cc_restrict_down(M, 0);
+  if (M.dlev.size() > 1) cc_vcycle_d(M, 1); else cc_vcycle_t(M, 0);
+}
 // fast: macproject's single-level call (CcFast in vdn_internal.h): rh, phi and beta are not used (may be null); phi comes back as views of the
 // finest level's array (ghost cells exchanged) and the level arrays stay allocated -- the CALLER releases the arena
-int cc_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int bc[3][2],
-             double rel_eps, double abs_eps, int max_iter, int *cycles, double *res0, double *res, const vdn_multifab *alpha, const vdn_multifab *rho, CcKeep *keep,
-             CcFast *fast, int fmg, bool zero_guess, vdn_multifab *add_to, double const_beta) {
+int cc_solve(CcRequest &q) {
   Prof prof_("mac_multigrid");
-  if (ctx().prm.dm == 2) return cc2_solve(rh, phi, beta, dx, bc, rel_eps, abs_eps, max_iter, cycles, res0, res, alpha);
+  if (ctx().prm.dm == 2) return cc2_solve(q);
   const vdn_params &P = ctx().prm;
-  if (fast) REQUIRE(!keep && !alpha && max_iter >= 0 && fast->rho && fast->rho->ng >= 1, "cc_solve: bad use of the fast path");
+  CcKeep *keep = q.keep; CcFast *fast = q.fast;
+  const bool fixed = q.fixed_cycles > 0;
+  // the legal combinations
+  REQUIRE(q.dx && q.bc && q.fixed_cycles >= 0, "cc_solve: dx, bc and fixed_cycles >= 0");
+  if (fast) REQUIRE(!keep && !q.alpha && !fixed && fast->rho && fast->rho->ng >= 1, "cc_solve: bad use of the fast path");
+  else REQUIRE(q.rh && q.phi && q.beta, "cc_solve: rh, phi and beta");
   size_t mark = arena_mark();
   // keep: the hierarchy (arrays in the caller's arena scope, coefficients on every level) survives the call; the next call with the
   // same `keep` loads only its right-hand side and phi (the composite solves: one V-cycle per FAC iteration on the same coefficients)
@@ -2108,108 +2083,78 @@ int cc_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const dou
   CCMG &M = keep ? keep->M : M_local;
   double bnorm_fast = 0.0;
   if (fast) {
-    bnorm_fast = cc_setup_fast(M, fast, dx, bc);
+    bnorm_fast = cc_setup_fast(M, fast, q.dx, q.bc);
     if (cc_split_ok(M)) cc_split_setup(M);
-    g_mac_level_form = !M.dlev[0].split ? 0 : (vdn_env("VDN_MAC_SPLIT") && atoi(vdn_env("VDN_MAC_SPLIT")) == 2) ? 2 : 1;
+    g_mac_level_form = M.dlev[0].split ? 1 : 0;
   }
-  else if (keep && keep->built) { cc_reload(M, rh, phi, bc, zero_guess); g_mac_level_form = M.dlev[0].split ? 1 : 0; }
+  else if (keep && keep->built) { cc_reload(M, q.rh, q.phi, q.bc, q.zero_guess); g_mac_level_form = M.dlev[0].split ? 1 : 0; }
   else {
-    cc_setup(M, rh, phi, alpha, beta, dx, bc, rho, const_beta);
+    cc_setup(M, q.rh, q.phi, q.alpha, q.beta, q.dx, q.bc, q.rho, q.const_beta);
     g_mac_level_form = 0;
     // round 6: the V-cycles a composite MAC solve runs on its level 0 (a kept hierarchy, one cycle per FAC iteration, the density form) take the level by colour
     // too -- for the tagged 256^3 hierarchies that is a whole 256^3 level, 23 cycles per step
-    if (keep && max_iter < 0 && (!alpha || const_beta > 0.0) && cc_split_ok(M)) { cc_split_setup(M); cc_to_split(M.dlev[0], 1); g_mac_level_form = 1; }      // (also the composite viscous solves: constant coefficients)
+    if (keep && fixed && (!q.alpha || q.const_beta > 0.0) && cc_split_ok(M)) { cc_split_setup(M); cc_to_split(M.dlev[0], 1); g_mac_level_form = 1; }      // (also the composite viscous solves: constant coefficients)
     // ... and the viscous / diffusive solves (constant face coefficients: the caller's const_beta): every 3-D input of exec/test runs three of them per step, at 256^3 they were
     // 24 ms of a 51 ms step on the stored-coefficient passes (56 B per cell and pass; by colour, without coefficient arrays: 20)
-    else if (!keep && max_iter >= 0 && alpha && const_beta > 0.0 && cc_split_ok(M)) { cc_split_setup(M); g_mac_level_form = 1; }      // (phi goes over after the nested iteration, below)
+    else if (!keep && !fixed && q.alpha && q.const_beta > 0.0 && cc_split_ok(M)) { cc_split_setup(M); g_mac_level_form = 1; }      // (phi goes over after the nested iteration, below)
   }
   // the bottom statistics are those of one solve (a composite solve: of all the cycles it runs on its kept hierarchy)
-  if (M.kry_w && (max_iter >= 0 || !(keep && keep->built))) bottom_stats_reset(0);
+  if (M.kry_w && (!fixed || !(keep && keep->built))) bottom_stats_reset(0);
   if (keep) keep->built = true;
   CDLev &D0 = M.dlev[0];
   const bool single = (M.dlev.size() == 1 && M.tail.empty());
-  // fmg: the caller's phi is zero, ghost cells included, and the solve starts from a nested iteration (not before a fixed number of cycles);
-  // the fast path: vdn_params.mac_fmg
-  if (fast) fmg = P.mac_fmg ? 1 : 0;
-  if (max_iter < 0) {            // exactly -max_iter V-cycles, no norms, no convergence test (the coarse correction of the composite solves)
-    for (int c = 0; c < -max_iter; c++) {
-      if (single) { const int N = std::max(D0.ng[0], std::max(D0.ng[1], D0.ng[2])); cc_gsrb_d(M, D0, std::max(P.mg_nub, N * N)); continue; }
+  const int nbot = std::max(P.mg_nub, std::max(D0.ng[0], std::max(D0.ng[1], D0.ng[2])) * std::max(D0.ng[0], std::max(D0.ng[1], D0.ng[2])));
+  if (fixed) {            // exactly fixed_cycles V-cycles, no norms, no convergence test (the coarse correction of the composite solves)
+    for (int c = 0; c < q.fixed_cycles; c++) {
+      if (single) { cc_gsrb_d(M, D0, nbot); continue; }
       cc_run_cycle(M, 2, [&] {
         const bool slabs = D0.split && !D0.halo && D0.boxes.size() == 1 && mac_slab(D0.boxes[0].L) > 0;
         if (slabs) cc_split_run(M, D0, false, P.mg_nu1, true, false, false);
         else { cc_gsrb_d(M, D0, P.mg_nu1); cc_residual_d(M, D0, false); }
-        cc_restrict_down(M, 0);
-        if (M.dlev.size() > 1) cc_vcycle_d(M, 1); else cc_vcycle_t(M, 0);
+        cc_coarse_correction(M);
         if (slabs) cc_split_run(M, D0, true, P.mg_nu2, false, false, false);
         else cc_prolong_smooth(M, 0, P.mg_nu2);
       });
     }
     if (D0.split) cc_from_split(D0);
-    cc_store(M, phi, bc, add_to);
-    if (cycles) *cycles = -max_iter; if (res0) *res0 = 0.0; if (res) *res = 0.0;
+    cc_store(M, q.phi, q.bc, q.add_to);
+    q.cycles = q.fixed_cycles; q.res0 = 0.0; q.res = 0.0;
     if (!keep) arena_release(mark);
     return 0;
   }
-  const double bnorm = fast ? bnorm_fast : mf_norm_inf(rh, 0, 1);
-  int cyc = 0; bool conv = (bnorm == 0.0); double rn = 0.0;
-  // pre-smoothing + residual, then per cycle: [coarse correction, post-smoothing, the next cycle's pre-smoothing, residual + norm] as ONE
-  // replayed graph and one 8-byte read-back -- the same launch sequence as testing the residual the cycle computes after pre-smoothing
-  const int nbot = std::max(P.mg_nub, std::max(D0.ng[0], std::max(D0.ng[1], D0.ng[2])) * std::max(D0.ng[0], std::max(D0.ng[1], D0.ng[2])));
-  if (fmg && !conv && !single && bnorm < HUGE_VAL) cc_run_cycle(M, cc_fmg_what(bc), [&] { cc_fmg(M, bc); });
+  const double bnorm = fast ? bnorm_fast : mf_norm_inf(q.rh, 0, 1);
+  // fmg: the caller's phi is zero, ghost cells included, and the solve starts from a nested iteration (not before a fixed number of cycles);
+  // the fast path: vdn_params.mac_fmg
+  const bool fmg = fast ? P.mac_fmg != 0 : q.fmg;
+  if (fmg && bnorm != 0.0 && !single && bnorm < HUGE_VAL) cc_run_cycle(M, cc_fmg_what(q.bc), [&] { cc_fmg(M, q.bc); });
   if (D0.split) cc_to_split(D0, 1);
-  // vdn_params.mg_predict (macproject's call: zero guess): see nd_solve in mg_nd.hip -- the norms of the cycles before the one the previous solve of this
-  // size stopped at, minus one, go into the device-side history and are read in one go; a history that shows an earlier stop repeats the solve
+  // the cycles (mg_stop.h); vdn_params.mg_predict on macproject's call (zero guess)
   const int gn[3] = { D0.ng[0], D0.ng[1], D0.ng[2] };
-  const int pred = (fast && !single && !conv && bnorm < HUGE_VAL) ? std::min(mg_predict_get(0, gn), std::min(max_iter, 63)) : 0;
-  if (!conv) {
-    if (single) cc_gsrb_d(M, D0, nbot); else cc_fine_seq(M, false, pred >= 2, true, false);
-    if (pred >= 2) {
-      norm_hist_reset(); norm_hist_push(M.d_nrm);
-      cc_run_cycle(M, 4 + 4 * pred, [&] {      // all blind cycles as ONE graph (ids: 1 and 2 the plain cycles, 3 + 4 code the nested iterations, multiples of 4 these)
-        for (int c = 1; c <= pred - 1; c++) {
-          cc_restrict_down(M, 0);
-          if (M.dlev.size() > 1) cc_vcycle_d(M, 1); else cc_vcycle_t(M, 0);
-          cc_fine_seq(M, true, true, true, false);
-          norm_hist_push(M.d_nrm);
-        }
+  const MgStop s = mg_stop_loop(0, gn, fast && !single && bnorm < HUGE_VAL, fast && !single, q, bnorm, M.d_nrm,
+    [&](bool blind) {
+      if (single) cc_gsrb_d(M, D0, nbot); else cc_fine_seq(M, false, blind, true, false);
+      if (!blind) cc_residual_d(M, D0, true);
+    },
+    [&] {
+      if (single) { cc_gsrb_d(M, D0, nbot); cc_residual_d(M, D0, true); }
+      else cc_run_cycle(M, 1, [&] { cc_coarse_correction(M); cc_fine_seq(M, true, true, true); });
+    },
+    [&](int n) {
+      cc_run_cycle(M, 8 + 4 * n, [&] {      // all blind cycles as ONE graph (ids: 1 and 2 the plain cycles, 3 + 4 code the nested iterations, multiples of 4 these)
+        for (int c = 0; c < n; c++) { cc_coarse_correction(M); cc_fine_seq(M, true, true, true, false); norm_hist_push(M.d_nrm); }
       });
-      const double *h = norm_hist_read(pred);
-      int first = -1;
-      for (int c = 0; c < pred && first < 0; c++)
-        if (((h[c] <= rel_eps * bnorm && bnorm < HUGE_VAL) || h[c] <= abs_eps) || !(h[c] < HUGE_VAL)) first = c;
-      if (first >= 0 && first < pred - 1) {                      // overshot: repeat without the prediction
-        arena_release(mark);
-        struct Off { Off() { g_mg_predict_off++; } ~Off() { g_mg_predict_off--; } } off_;
-        return cc_solve(rh, phi, beta, dx, bc, rel_eps, abs_eps, max_iter, cycles, res0, res, alpha, rho, keep, fast, fmg, zero_guess, add_to, const_beta);
-      }
-      cyc = pred - 1; rn = h[pred - 1];
-    } else {
-      cc_residual_d(M, D0, true); rn = read_scalar(M.d_nrm);
-    }
-  }
-  while (!conv) {
-    if ((rn <= rel_eps * bnorm && bnorm < HUGE_VAL) || rn <= abs_eps) { conv = true; break; }
-    if (cyc >= max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;     // also: a NaN / inf norm (the reductions turn NaN into +inf)
-    if (single) { cc_gsrb_d(M, D0, nbot); cc_residual_d(M, D0, true); }
-    else cc_run_cycle(M, 1, [&] {
-      cc_restrict_down(M, 0);
-      if (M.dlev.size() > 1) cc_vcycle_d(M, 1); else cc_vcycle_t(M, 0);
-      cc_fine_seq(M, true, true, true);
-    });
-    cyc++;
-    rn = read_scalar(M.d_nrm);
-  }
+    },
+    [&] { return read_scalar1(M.d_nrm); });
+  if (s.overshot) { arena_release(mark); return mg_repeat_unpredicted([&] { return cc_solve(q); }); }
+  if (D0.split) cc_from_split(D0);
   if (fast) {
-    CDLev &DF = M.dlev[0];
-    if (DF.split) cc_from_split(DF);
-    cc_halo(M, DF);
+    cc_halo(M, D0);
     fast->phi_view.clear();
-    for (size_t b = 0; b < DF.boxes.size(); b++) fast->phi_view.push_back(cc_phi_view(DF.boxes[b].L, fast->rho->vbox[b].lo));
-  } else { if (M.dlev[0].split) cc_from_split(M.dlev[0]); cc_store(M, phi, bc); }
-  if (cycles) *cycles = cyc; if (res0) *res0 = bnorm; if (res) *res = rn;
-  if (conv && fast && !single && cyc >= 1) mg_predict_set(0, gn, cyc);
+    for (size_t b = 0; b < D0.boxes.size(); b++) fast->phi_view.push_back(cc_phi_view(D0.boxes[b].L, fast->rho->vbox[b].lo));
+  } else cc_store(M, q.phi, q.bc);
+  q.cycles = s.cycles; q.res0 = bnorm; q.res = s.res;
   if (!keep && !fast) arena_release(mark);
-  return conv ? 0 : 1;
+  return s.conv ? 0 : 1;
 }
 
 void cc_smooth(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int bc[3][2], int nsweeps) {
@@ -2365,7 +2310,7 @@ static void mac_level_mkumac_rho(vdn_multifab **um, const std::vector<FV> &phi_v
     v.push_back({ mkumac_rho_K{ um[0]->fabs[i], um[1]->fabs[i], um[2]->fabs[i], phi_view[i], rho->fabs[i], A }, rf });
   }
   // advance_timestep on one level, one box: the step's cache of max |umac| (godunov.hip: macmax_cache) is filled here
-  static const bool fuse_max = !(vdn_env("VDN_MAC_UMAX") && atoi(vdn_env("VDN_MAC_UMAX")) == 0);
+  static const bool fuse_max = env_on("VDN_MAC_UMAX");
   VdnCtx &c = ctx();
   if (fuse_max && v.size() == 1 && rho->la->nlev == 1 && c.macmax_cache.size() == 1 && c.macmax_cache[0]) {
     HIPCHK(hipMemsetAsync(c.macmax_cache[0], 0, sizeof(double), c.stream));
@@ -2415,7 +2360,7 @@ void do_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn
   const int n = 0;
   size_t mark = arena_mark();
   {
-    static const bool fast_on = !(vdn_env("VDN_MAC_FAST") && atoi(vdn_env("VDN_MAC_FAST")) == 0);
+    static const bool fast_on = env_on("VDN_MAC_FAST");
     // the second level must exist (its coefficients come from the first level's rho): boxes that halve cleanly to >= 4 cells, as cc_build asks
     bool ok = fast_on && beta_from_rho() && rho[n]->ng >= 1;
     {   // cc_build's rule for a second DISTRIBUTED level: the domain coarsens, the boxes halve cleanly and stay at least min_dist wide
@@ -2429,10 +2374,12 @@ void do_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn
       int ebc[3][2];
       for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc[d][s] = bct->ell_bc(n, 0, d, s, bc_comp0);
       CcFast F; F.um = um; F.mac_rhs = mac_rhs[n]; F.rho = rho[n];
-      int cyc; double r0, rr;
-      int rc = cc_solve(nullptr, nullptr, nullptr, dx, ebc, ctx().prm.mac_rel_eps, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, nullptr, rho[n], nullptr, &F);
-      ctx().solver_cycles[0] = cyc; ctx().solver_res0[0] = r0; ctx().solver_res[0] = rr;
-      solver_check(rc, "MAC multigrid", cyc, rr, r0);
+      CcRequest q;
+      q.dx = dx; q.bc = ebc; q.rel_eps = ctx().prm.mac_rel_eps; q.max_iter = ctx().prm.mg_max_iter;
+      q.rho = rho[n]; q.fast = &F;
+      const int rc = cc_solve(q);
+      ctx().solver_cycles[0] = q.cycles; ctx().solver_res0[0] = q.res0; ctx().solver_res[0] = q.res;
+      solver_check(rc, "MAC multigrid", q.cycles, q.res, q.res0);
       mac_level_mkumac_rho(um, F.phi_view, rho[n], dx, bct, bc_comp0);
       for (int d = 0; d < 3; d++) mf_fill_boundary(um[d]);        // macproject.f90:115-119
       arena_release(mark);
@@ -2449,11 +2396,13 @@ void do_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn
   mac_level_coeffs(rho[n], beta);
   int ebc[3][2];
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc[d][s] = bct->ell_bc(n, 0, d, s, bc_comp0);   // grid 0 = whole domain
-  int cyc; double r0, rr;
-  int rc = cc_solve(rh, phi, beta, dx, ebc, ctx().prm.mac_rel_eps, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, nullptr, rho[n], nullptr, nullptr,
-                    ctx().prm.mac_fmg ? 1 : 0);   // macproject.f90:91-93 (phi was created zero above)
-  ctx().solver_cycles[0] = cyc; ctx().solver_res0[0] = r0; ctx().solver_res[0] = rr;
-  solver_check(rc, "MAC multigrid", cyc, rr, r0);
+  CcRequest q;
+  q.rh = rh; q.phi = phi; q.beta = beta; q.rho = rho[n]; q.dx = dx; q.bc = ebc;
+  q.rel_eps = ctx().prm.mac_rel_eps; q.max_iter = ctx().prm.mg_max_iter;      // macproject.f90:91-93
+  q.fmg = ctx().prm.mac_fmg != 0;                                              // (phi was created zero above)
+  const int rc = cc_solve(q);
+  ctx().solver_cycles[0] = q.cycles; ctx().solver_res0[0] = q.res0; ctx().solver_res[0] = q.res;
+  solver_check(rc, "MAC multigrid", q.cycles, q.res, q.res0);
   mac_level_mkumac(um, phi, beta, dx, bct, bc_comp0);
   for (int d = 0; d < 3; d++) mf_fill_boundary(um[d]);          // macproject.f90:115-119
   for (int d = 0; d < 3; d++) mf_temp_free(beta[d]);

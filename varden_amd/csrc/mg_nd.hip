@@ -12,6 +12,7 @@
 // (i + 16) + PX*((j+1) + PY*(k+1)), PX a multiple of 16 doubles (rows start on a 128-byte line).
 // Algorithmic traffic of one Jacobi sweep: phi read 8 + phi write 8 + rhs 8 + sigma 8 = 32 B/node.
 #include "vdn_dev.h"
+#include "mg_stop.h"
 #include "krylov_wg.h"
 #include <tuple>
 #include <algorithm>
@@ -623,15 +624,8 @@ DEVI double nd_interp8(const NLev &C, const double *__restrict__ cp, int I, int 
   s = (ok && oi && oj) ? s + v111 : s;
   return s * (1.0 / (double)((1 + oi) * (1 + oj) * (1 + ok)));
 }
-__global__ void kk_nd_prolong(NLev F, NLev C) {
-  NODE_IJK(F)
-  if (!in_range) return;
-  if (nd_is_dir(F, i, j, k)) return;
-  const long f = nidx(F, i, j, k);
-  F.phi[f] = F.phi[f] + nd_interp8(C, C.phi, i >> 1, j >> 1, k >> 1, i & 1, j & 1, k & 1);
-}
-// k-marching form of kk_nd_prolong / kk_nd_prolong_tail: a thread owns a fine (i,j) column of a slab of planes and keeps the four
-// coarse values of planes K and K+1 in registers -- 4 coarse loads per TWO fine planes instead of 8 per node; same sums, same order
+// phi_F += the interpolated phi_C (nd_interp8's sums, in its order), k-marching: a thread owns a fine (i,j) column of a slab of planes and keeps the four
+// coarse values of planes K and K+1 in registers -- 4 coarse loads per TWO fine planes instead of 8 per node.  c0: the coarse index of the box's node 0
 __global__ void __launch_bounds__(256) kk_nd_prolong_m(NLev F, NLev C, int c00, int c01, int c02, int kchunk) {
   const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y;
   const int k0 = (int)blockIdx.z * kchunk, k1 = min(k0 + kchunk - 1, F.n[2]);          // kchunk is even: k0 is even
@@ -1042,15 +1036,6 @@ __global__ void kk_nd_unpack(NLev T, double *dst, const double *buf, const NGBox
     dst[nidx(T, g.c0[0] + i, g.c0[1] + j, g.c0[2] + k)] = buf[g.off + t];
   }
 }
-__global__ void kk_nd_prolong_tail(NLev F, NLev T, int c00, int c01, int c02, int f00, int f01, int f02) {
-  NODE_IJK(F)
-  if (!in_range) return;
-  if (nd_is_dir(F, i, j, k)) return;
-  // global fine node = f0 + (i,j,k); the box origin is even, so parity and halving are local
-  (void)f00; (void)f01; (void)f02;
-  const long f = nidx(F, i, j, k);
-  F.phi[f] = F.phi[f] + nd_interp8(T, T.phi, c00 + (i >> 1), c01 + (j >> 1), c02 + (k >> 1), i & 1, j & 1, k & 1);
-}
 
 // ---- host ---------------------------------------------------------------------------------------------------
 static const dim3 NBLK(64, 4, 1);
@@ -1074,6 +1059,23 @@ static NdPairGrid nd_pair_grid(const NLev &L, int rows, int nzu, bool use_rem, i
   G.rev = 0;
   return G;
 }
+// ---- the launch-form switches of this file (runtime.hip's table), each read here ----------------------------------------------------------
+static bool nd_pair_on()           { static const bool b = env_on("VDN_ND_PAIR"); return b; }
+static bool nd_rev_on()            { static const bool b = env_on("VDN_ND_REV"); return b; }
+static bool nd_lean_on()           { static const bool b = env_on("VDN_ND_LEAN"); return b; }
+static bool nd_restrict_fused_on() { static const bool b = env_on("VDN_ND_RESTRICT_FUSED"); return b; }
+static bool nd_prolong_fused_on()  { static const bool b = env_on("VDN_ND_PROLONG_FUSED"); return b; }
+static bool nd_tailcycle_on()      { static const bool b = env_on("VDN_MG_TAILCYCLE"); return b; }
+static int  nd_overlap_env()       { static const int v = env_int("VDN_OVERLAP", -1); return v; }
+static bool hg_fast_on()           { static const bool b = env_on("VDN_HG_FAST"); return b; }
+static bool ndf_pair_on()          { static const bool b = env_on("VDN_NDF_PAIR"); return b; }
+static bool ndm_iface_faces_on()   { static const bool b = env_on("VDN_NDM_IFACE_FACES"); return b; }
+static bool ndm_prolong8_on()      { static const bool b = env_on("VDN_NDM_PROLONG8"); return b; }
+static bool ndm_neg_copy()         { static const bool b = env_set("VDN_NDM_NEG"); return b; }
+// the wide nodal level: the pair march (124 nodes per wave row; VDN_ND_PAIR=0: one node per lane)
+static bool nd_wide_level(const NLev &L) { return nd_pair_on() && L.n[0] >= 127; }
+// ... with even extents: the pair marches that also write or read the next level (residual + restriction, the correction inside the first sweep)
+static bool nd_wide_even_level(const NLev &L) { return nd_wide_level(L) && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[2] % 2 == 0; }
 // slab thickness: enough workgroups to fill 256 CUs several times over, yet long enough marches to amortise the
 // two warm-up planes (overhead 2/kchunk)
 // rev: the tiles in reverse order.  Consecutive marches of a level alternate (NDLev::rev): a sweep reads what the previous one wrote and the same sigma and
@@ -1085,13 +1087,11 @@ template <int MODE> static void nd_launch_march(const NLev &L, const double *phi
   int kchunk = nzp;
   while (kchunk > 8 && tiles * ((nzp + kchunk - 1) / kchunk) < 2048) kchunk = (kchunk + 1) / 2;
   const int nch = (nzp + kchunk - 1) / kchunk;
-  static const bool paired = !(vdn_env("VDN_ND_PAIR") && atoi(vdn_env("VDN_ND_PAIR")) == 0);
-  if (paired && L.n[0] >= 127) {                   // 124 nodes per wave row
+  if (nd_wide_level(L)) {
     const int rows = 4;                          // (measured: 8 rows per workgroup 17.1 -> 18.7 ms of HG per step, 16 rows spill)
     const bool use_rem = true; const int minwg = 2048, kc_env = 0;
     NdPairGrid G = nd_pair_grid(L, rows, nzp, use_rem, minwg, kc_env);
-    static const bool flip = !(vdn_env("VDN_ND_REV") && atoi(vdn_env("VDN_ND_REV")) == 0);
-    G.rev = flip ? rev : 0;
+    G.rev = nd_rev_on() ? rev : 0;
     if (MODE == 0 && pro) {
       const NdCoarse C{ pro->phi, pro->PX, pro->PY, pro->n[0] };
       hipLaunchKernelGGL((kk_nd_march_pair<0, 4, 1>), dim3(G.nmain + G.gyr * G.gz), NBLK, 0, ctx().stream, L, phi, out, nd_cur_omega(), G, nrm, shell_later, C);
@@ -1147,8 +1147,7 @@ static NLev nd_alloc_lev(const int n[3], const double h[3]) {
   // Row padding beyond the ghost nodes only ever reaches lanes whose results are discarded.
   // (The first version left sigma to its load as well -- true on the finest level only: the 129^3 level of a 257^3 solve then read
   // whatever the arena held beyond the walls, which happened to be zeros until hgproject stopped allocating its multifabs in front of it.)
-  static const bool lean_on = !(vdn_env("VDN_ND_LEAN") && atoi(vdn_env("VDN_ND_LEAN")) == 0);
-  if (lean_on && (long)(n[0] + 1) * (n[1] + 1) * (n[2] + 1) >= (1L << 21)) {
+  if (nd_lean_on() && (long)(n[0] + 1) * (n[1] + 1) * (n[2] + 1) >= (1L << 21)) {
     const int m = std::max(n[0], std::max(n[1], n[2])) + 3;
     hipLaunchKernelGGL(kk_nd_zero_shell, dim3((m + 63) / 64, (m + 3) / 4, 6), dim3(64, 4, 1), 0, ctx().stream, L, L.phi, L.tmp, L.res);
     HIPCHK(hipMemsetAsync(L.sig, 0, sizeof(double) * L.sz, ctx().stream));
@@ -1284,7 +1283,7 @@ static void nd_halo_phi(NDLev &DL) { XPlan *P = DL.flip ? DL.halo_B : DL.halo_A;
 static bool nd_halo_begin(NDLev &DL) {
   XPlan *P = DL.flip ? DL.halo_B : DL.halo_A;
   if (!P) return false;
-  static const int ov_env = vdn_env("VDN_OVERLAP") ? atoi(vdn_env("VDN_OVERLAP")) : -1;
+  const int ov_env = nd_overlap_env();
   static const long ov_min = 1L << 20;     // see cc_gsrb_d
   long nodes = 0;
   for (const NBox &B : DL.boxes) nodes = std::max(nodes, (long)B.L.n[0] * B.L.n[1] * B.L.n[2]);
@@ -1344,16 +1343,13 @@ static void nd_residual_d(NDMG &M, NDLev &DL, bool norm, bool reduce = true) {  
   if (norm) HIPCHK(hipMemsetAsync(M.d_nrm, 0, sizeof(double), ctx().stream));
   DL.res_restricted = false;
   {   // a wide one-box level without periodic images whose next level is one box too: residual and the x / z part of the restriction in one march
-    static const bool fuse = !(vdn_env("VDN_ND_RESTRICT_FUSED") && atoi(vdn_env("VDN_ND_RESTRICT_FUSED")) == 0);
-    static const bool paired = !(vdn_env("VDN_ND_PAIR") && atoi(vdn_env("VDN_ND_PAIR")) == 0);
     const size_t l = &DL - &M.dlev[0];
-    if (fuse && paired && DL.single_box && DL.boxes.size() == 1 && !DL.halo_res && !(DL.per[0] || DL.per[1] || DL.per[2]) && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
+    if (nd_restrict_fused_on() && DL.single_box && DL.boxes.size() == 1 && !DL.halo_res && !(DL.per[0] || DL.per[1] || DL.per[2]) && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
       const NLev &L = DL.boxes[0].L;
-      if (L.n[0] >= 127 && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[2] % 2 == 0) {
+      if (nd_wide_even_level(L)) {
         nd_halo_phi(DL);                                                  // (no neighbour, no image: nothing to exchange; kept for symmetry with the plain path)
         NdPairGrid G = nd_pair_grid(L, 4, L.n[2] / 2 + 1, true, 2048, 0);
-        static const bool flip = !(vdn_env("VDN_ND_REV") && atoi(vdn_env("VDN_ND_REV")) == 0);
-        G.rev = flip ? DL.rev : 0; DL.rev ^= 1;
+        G.rev = nd_rev_on() ? DL.rev : 0; DL.rev ^= 1;
         hipLaunchKernelGGL((kk_nd_march_pair_rst<4>), dim3(G.nmain + G.gyr * G.gz), NBLK, 0, ctx().stream, L, (const double *)L.phi, L.res, G, norm ? M.d_nrm : nullptr);
         DL.res_restricted = true;
         if (norm && reduce) comm_allreduce_max_dev(M.d_nrm, 1);
@@ -1459,15 +1455,13 @@ static void nd_prolong_up(NDMG &M, int l) {
 // correction rides in the first sweep (kk_nd_march_pair<0, 4, 1>): no prolongation pass.  Everything else -- several boxes, periodic axes, levels narrower than
 // 127 nodes, the nested iteration's interpolation -- keeps kk_nd_prolong_m.  Same omegas, same tile-order alternation, same phi / tmp flips either way.
 static bool nd_prolong_fusable(const NDMG &M, int l) {
-  static const bool fuse = !(vdn_env("VDN_ND_PROLONG_FUSED") && atoi(vdn_env("VDN_ND_PROLONG_FUSED")) == 0);
-  static const bool paired = !(vdn_env("VDN_ND_PAIR") && atoi(vdn_env("VDN_ND_PAIR")) == 0);
   const NDLev &DL = M.dlev[l];
-  if (!(fuse && paired && DL.single_box && DL.boxes.size() == 1 && !DL.halo_A && !DL.halo_B && !(DL.per[0] || DL.per[1] || DL.per[2]))) return false;
+  if (!(nd_prolong_fused_on() && DL.single_box && DL.boxes.size() == 1 && !DL.halo_A && !DL.halo_B && !(DL.per[0] || DL.per[1] || DL.per[2]))) return false;
   if (l + 1 < (int)M.dlev.size() ? M.dlev[l + 1].boxes.size() != 1 : M.tail.empty()) return false;
   const NBox &B = DL.boxes[0];
   const NLev &L = B.L, &C = l + 1 < (int)M.dlev.size() ? M.dlev[l + 1].boxes[0].L : M.tail[0];
-  for (int d = 0; d < 3; d++) if (B.lo[d] != 0 || (L.n[d] & 1) || C.n[d] != L.n[d] / 2) return false;
-  return L.n[0] >= 127;
+  for (int d = 0; d < 3; d++) if (B.lo[d] != 0 || C.n[d] != L.n[d] / 2) return false;
+  return nd_wide_even_level(L);
 }
 static unsigned g_nd_pro_levels = 0;      // the levels (bit l) whose coarse correction went into a prolonging march in the last nd_solve; the testing build hands it out (runtime.hip)
 unsigned nd_last_prolong_levels() { return g_nd_pro_levels; }
@@ -1486,8 +1480,7 @@ static int nd_bottom_sweeps_global(const NDLev &DL) {
 // The small end of the hierarchy in one launch (kk_nd_tailcycle): distributed levels dl .. end when they are one box of at most 9^3 nodes
 // each (dl < 0: none), then the replicated tail levels tl .. end (one rank and one box: the gather between the two is the plain restriction).
 static bool nd_small_end(NDMG &M, int dl, int tl) {
-  static const bool on = !(vdn_env("VDN_MG_TAILCYCLE") && atoi(vdn_env("VDN_MG_TAILCYCLE")) == 0);
-  if (!on) return false;
+  if (!nd_tailcycle_on()) return false;
   static const long tail_nodes = SMALL_LEVEL_NODES;    // largest level the one-workgroup cycle takes (measured: 17^3 is slower, HG 16.9 -> 17.6 ms)
   const vdn_params &P = ctx().prm;
   NdTailArgs T; memset(&T, 0, sizeof T);
@@ -1646,10 +1639,6 @@ template <class Body> static void nd_run_cycle(NDMG &M, int what, Body body) {
   g_nd_post[key] = M;
 }
 
-static double nd_read(double *d) {
-  return read_scalar1(d);
-}
-
 // keep: the level hierarchy (arrays in the caller's arena scope, sigma on every level) survives the call and the next call with the same
 // `keep` only loads its right-hand side and phi -- the composite solves run one V-cycle of this solver per FAC iteration on the same
 // coefficients (19 iterations per step on the tagged 256^3 hierarchy: 19 set-ups of 0.6 ms each before)
@@ -1659,22 +1648,29 @@ void nd_keep_free(NdKeep *k) { delete k; }
 // fast: hgproject's single-level call (NdFast in vdn_internal.h) -- rh and phi are known to be zero and are not touched (may be null), sigma comes
 // from fast->rhohalf (coeffs may be null), and instead of storing phi into a multifab the call returns views of the finest level's phi
 // (ghost nodes exchanged) in fast->phi_view; the level arrays then stay allocated: the CALLER releases the arena (mark taken before the call)
-int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, const vdn_multifab *u, const double *dx,
-             const int bc[3][2], double rel_eps, double abs_eps, int max_iter, int *cycles, double *res0, double *res, NdKeep *keep, NdFast *fast, bool fmg_start, bool rh_is_b, vdn_multifab *add_to) {
+int nd_solve(NdRequest &q) {
   Prof prof_("hg_multigrid");
-  if (ctx().prm.dm == 2) return nd2_solve(rh, phi, coeffs, u, dx, bc, rel_eps, abs_eps, max_iter, cycles, res0, res);
+  if (ctx().prm.dm == 2) return nd2_solve(q);
   const vdn_params &P = ctx().prm;
+  vdn_multifab *rh = q.rh, *phi = q.phi, *add_to = q.add_to; const vdn_multifab *u = q.u; const double *dx = q.dx;
+  NdKeep *keep = q.keep; NdFast *fast = q.fast;
+  const bool fixed_cycles = q.fixed_cycles > 0;     // exactly that many V-cycles, no norms, no convergence test (composite coarse correction)
+  // the legal combinations
+  REQUIRE(dx && q.bc && q.fixed_cycles >= 0, "nodal multigrid: dx, bc and fixed_cycles >= 0");
+  if (fast) REQUIRE(fast->rhohalf && u && u->ng >= 1 && u->nc >= 3 && !keep && !fixed_cycles, "nodal multigrid: the fast path needs rhohalf and u with a ghost cell");      // (rhohalf is read on valid cells only: no ghost layer needed)
+  else REQUIRE(rh && phi && q.coeffs && rh->ng >= 1 && phi->ng >= 1 && q.coeffs->ng >= 1, "nodal multigrid: rh, phi, coeffs need one ghost layer");
+  if (u && !fast) REQUIRE(u->ng >= 1 && u->nc >= 3, "nodal multigrid: u needs a ghost cell");
+  if (q.rh_is_b) REQUIRE(fixed_cycles && !u && !fast, "nodal multigrid: rh_is_b is the fixed-cycle correction solve's");
+  const vdn_multifab *coeffs = fast ? fast->rhohalf : q.coeffs;
   g_nd_iso = nd_isotropic(dx);
-  if (fast) { REQUIRE(fast->rhohalf && u && !keep, "nodal multigrid: the fast path needs rhohalf and u"); /* rhohalf is read on valid cells only: no ghost layer needed */ coeffs = fast->rhohalf; }
-  else REQUIRE(rh->ng >= 1 && phi->ng >= 1 && coeffs->ng >= 1, "nodal multigrid: rh, phi, coeffs need one ghost layer");
   hipStream_t st = ctx().stream;
   size_t mark = arena_mark();
   NDMG M_local;
   NDMG &M = keep ? keep->M : M_local;
   const bool rebuild = !(keep && keep->built);
-  if (rebuild) nd_build(M, coeffs, dx, bc);          // (of `coeffs` only the layout, the level and the boxes are used)
+  if (rebuild) nd_build(M, coeffs, dx, q.bc);          // (of `coeffs` only the layout, the level and the boxes are used)
   NDLev &D0 = M.dlev[0];
-  if (M.kry_w && (max_iter >= 0 || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
+  if (M.kry_w && (!fixed_cycles || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
   M.pro_levels = 0; g_nd_pro_levels = 0;
   if (rebuild) {
   // sigma: level 0 from the (ghost-filled) coeffs multifab; coarser distributed levels by averaging + halo exchange
@@ -1712,7 +1708,6 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
   }
   if (keep) keep->built = true;
   if (u && !fast) {                                         // add_divu = .true., hg_multigrid.f90:96
-    REQUIRE(u->ng >= 1 && u->nc >= 3, "nodal multigrid: u needs a ghost cell");
     std::vector<std::pair<nd_divu_K, Range3>> v;
     for (size_t b = 0; b < D0.boxes.size(); b++) {
       const vdn_box &bx = coeffs->vbox[b];
@@ -1725,87 +1720,51 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
   for (size_t b = 0; b < D0.boxes.size(); b++) {
     NLev &L0 = D0.boxes[b].L; const vdn_box &bx = coeffs->vbox[b];
     if (fast) {
-      REQUIRE(u->ng >= 1 && u->nc >= 3, "nodal multigrid: u needs a ghost cell");
       hipLaunchKernelGGL(kk_nd_load_divu, ng3(L0.n[0] + 1, L0.n[1] + 1, std::min(L0.n[2] + 1, 16)), NBLK, 0, st, L0, u->fabs[b], 0.25 / dx[0], 0.25 / dx[1], 0.25 / dx[2],
                          bx.lo[0], bx.lo[1], bx.lo[2], M.d_nrm);
-    } else if (rh_is_b) {
-      REQUIRE(max_iter < 0 && !u && ctx().prm.dm == 3, "nodal multigrid: rh_is_b is the fixed-cycle correction solve's");
+    } else if (q.rh_is_b) {
       hipLaunchKernelGGL(kk_nd_load_b, ng3(L0.n[0] + 1, L0.n[1] + 1, std::min(L0.n[2] + 1, 16)), NBLK, 0, st, L0, rh->fabs[b], bx.lo[0], bx.lo[1], bx.lo[2]);
     } else
     hipLaunchKernelGGL(kk_nd_load, ng3(L0.n[0] + 1, L0.n[1] + 1, std::min(L0.n[2] + 1, 16)), NBLK, 0, st, L0, rh->fabs[b], phi->fabs[b], bx.lo[0], bx.lo[1], bx.lo[2], M.d_nrm);
   }
   comm_allreduce_max_dev(M.d_nrm, 2);
   const bool single = (M.dlev.size() == 1 && M.tail.empty());
-  const bool fixed_cycles = max_iter < 0;     // exactly -max_iter V-cycles, no norms, no convergence test (composite coarse correction)
   double bnorm = 1.0, p0max = 1.0;
   if (!fixed_cycles) { const double *sc = read_scalars(M.d_nrm, 2); bnorm = sc[0]; p0max = sc[1]; }
-  int cyc = 0; bool conv = (bnorm == 0.0); double rn = 0.0;
-  if (P.hg_fmg && !conv && !single && (fixed_cycles ? fmg_start : (p0max == 0.0 && bnorm < HUGE_VAL))) nd_fmg(M);
-  for (int c = 0; fixed_cycles && c < -max_iter; c++) {
-    if (single) { nd_jacobi_d(M.dlev[0], nd_bottom_sweeps_global(M.dlev[0])); continue; }
-    nd_run_cycle(M, 2, [&] {
-      NDLev &D = M.dlev[0];
-      nd_jacobi_d(D, P.hg_nu1, true);
-      nd_residual_d(M, D, false);
-      nd_restrict_down(M, 0);
-      if (M.dlev.size() > 1) nd_vcycle_d(M, 1); else nd_vcycle_t(M, 0);
-      nd_prolong_smooth(M, 0);
-    });
-    cyc++;
-  }
-  if (fixed_cycles) conv = true;
-  // pre-smoothing + residual, then per cycle [coarse correction, post-smoothing, next pre-smoothing, residual + norm] as one replayed
-  // graph and one read-back: the same launch sequence as testing the residual the cycle computes after its pre-smoothing
-  // vdn_params.mg_predict (hgproject's call, zero guess): the previous solve of this size stopped after `pred` cycles, so the norms of the cycles
-  // before pred - 1 are not waited for -- they go into the device-side history and are read in one go after cycle pred - 1.  Should the history show
-  // that an earlier cycle had already met the tolerance, this solve is thrown away and repeated with a read-back per cycle (rare: the count
-  // dropped by two or more from one solve to the next), so the result is the one the plain loop gives, whatever the prediction was.
-  int gn[3] = { M.dlev[0].ng[0], M.dlev[0].ng[1], M.dlev[0].ng[2] };
-  int pred = (fast && !fixed_cycles && !single && !conv && p0max == 0.0) ? std::min(mg_predict_get(1, gn), std::min(max_iter, 63)) : 0;
-  if (!conv) {
-    nd_jacobi_d(M.dlev[0], single ? nd_bottom_sweeps_global(M.dlev[0]) : P.hg_nu1, !single);
-    if (pred >= 2) {
-      nd_residual_d(M, M.dlev[0], true, false);
-      norm_hist_reset(); norm_hist_push(M.d_nrm);
-      nd_run_cycle(M, 4 + 4 * pred, [&] {                  // all blind cycles as ONE graph (ids 1, 2: the plain cycles; nothing else is a multiple of 4)
-        for (int c = 1; c <= pred - 1; c++) {
-          NDLev &D = M.dlev[0];
-          nd_restrict_down(M, 0);
-          if (M.dlev.size() > 1) nd_vcycle_d(M, 1); else nd_vcycle_t(M, 0);
-          nd_prolong_smooth(M, 0);
-          nd_jacobi_d(D, P.hg_nu1, true);
-          nd_residual_d(M, D, true, false);
-          norm_hist_push(M.d_nrm);
-        }
-      });
-      const double *h = norm_hist_read(pred);
-      int first = -1;                                            // the first cycle count at which the plain loop would have stopped
-      for (int c = 0; c < pred && first < 0; c++)
-        if (((h[c] <= rel_eps * bnorm && bnorm < HUGE_VAL) || h[c] <= abs_eps) || !(h[c] < HUGE_VAL)) first = c;
-      if (first >= 0 && first < pred - 1) {                      // overshot: repeat without the prediction
-        arena_release(mark);
-        struct Off { Off() { g_mg_predict_off++; } ~Off() { g_mg_predict_off--; } } off_;
-        return nd_solve(rh, phi, nullptr, u, dx, bc, rel_eps, abs_eps, max_iter, cycles, res0, res, keep, fast, fmg_start, rh_is_b, add_to);
-      }
-      cyc = pred - 1; rn = h[pred - 1];
-    } else {
-      nd_residual_d(M, M.dlev[0], true); rn = nd_read(M.d_nrm);
+  if (P.hg_fmg && bnorm != 0.0 && !single && (fixed_cycles ? q.fmg_start : (p0max == 0.0 && bnorm < HUGE_VAL))) nd_fmg(M);
+  // the coarse correction of a cycle and what follows it on the finest level
+  auto correct = [&] {
+    nd_restrict_down(M, 0);
+    if (M.dlev.size() > 1) nd_vcycle_d(M, 1); else nd_vcycle_t(M, 0);
+    nd_prolong_smooth(M, 0);
+  };
+  MgStop s;
+  if (fixed_cycles) {
+    for (int c = 0; c < q.fixed_cycles; c++) {
+      if (single) { nd_jacobi_d(M.dlev[0], nd_bottom_sweeps_global(M.dlev[0])); continue; }
+      nd_run_cycle(M, 2, [&] { nd_jacobi_d(M.dlev[0], P.hg_nu1, true); nd_residual_d(M, M.dlev[0], false); correct(); });
+      s.cycles++;
     }
-  }
-  while (!conv) {
-    if ((rn <= rel_eps * bnorm && bnorm < HUGE_VAL) || rn <= abs_eps) { conv = true; break; }
-    if (cyc >= max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;     // also: a NaN / inf norm (the reductions turn NaN into +inf)
-    if (single) { nd_jacobi_d(M.dlev[0], nd_bottom_sweeps_global(M.dlev[0])); nd_residual_d(M, M.dlev[0], true); }
-    else nd_run_cycle(M, 1, [&] {
-      NDLev &D = M.dlev[0];
-      nd_restrict_down(M, 0);
-      if (M.dlev.size() > 1) nd_vcycle_d(M, 1); else nd_vcycle_t(M, 0);
-      nd_prolong_smooth(M, 0);
-      nd_jacobi_d(D, P.hg_nu1, true);
-      nd_residual_d(M, D, true);
-    });
-    cyc++;
-    rn = nd_read(M.d_nrm);
+    s.conv = true;
+  } else {
+    // the cycles (mg_stop.h); vdn_params.mg_predict on hgproject's call (zero guess)
+    const int gn[3] = { M.dlev[0].ng[0], M.dlev[0].ng[1], M.dlev[0].ng[2] };
+    s = mg_stop_loop(1, gn, fast && !single && p0max == 0.0, fast && !single, q, bnorm, M.d_nrm,
+      [&](bool blind) {
+        nd_jacobi_d(M.dlev[0], single ? nd_bottom_sweeps_global(M.dlev[0]) : P.hg_nu1, !single);
+        nd_residual_d(M, M.dlev[0], true, !blind);
+      },
+      [&] {
+        if (single) { nd_jacobi_d(M.dlev[0], nd_bottom_sweeps_global(M.dlev[0])); nd_residual_d(M, M.dlev[0], true); }
+        else nd_run_cycle(M, 1, [&] { correct(); nd_jacobi_d(M.dlev[0], P.hg_nu1, true); nd_residual_d(M, M.dlev[0], true); });
+      },
+      [&](int n) {
+        nd_run_cycle(M, 8 + 4 * n, [&] {                  // all blind cycles as ONE graph (ids 1, 2: the plain cycles; nothing else is a multiple of 4)
+          for (int c = 0; c < n; c++) { correct(); nd_jacobi_d(M.dlev[0], P.hg_nu1, true); nd_residual_d(M, M.dlev[0], true, false); norm_hist_push(M.d_nrm); }
+        });
+      },
+      [&] { return read_scalar1(M.d_nrm); });
+    if (s.overshot) { arena_release(mark); return mg_repeat_unpredicted([&] { return nd_solve(q); }); }
   }
   NDLev &DF = M.dlev[0];                    // (a replayed cycle re-assigns M: take the reference afresh)
   nd_halo_phi(DF);
@@ -1817,11 +1776,10 @@ int nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, co
     else
     hipLaunchKernelGGL(kk_nd_store, ng3(L0.n[0] + 3, L0.n[1] + 3, L0.n[2] + 3), NBLK, 0, st, L0, phi->fabs[b], bx.lo[0], bx.lo[1], bx.lo[2]);
   }
-  if (cycles) *cycles = cyc; if (res0) *res0 = bnorm; if (res) *res = rn;
+  q.cycles = s.cycles; q.res0 = bnorm; q.res = s.res;
   g_nd_pro_levels = M.pro_levels;
-  if (conv && fast && !fixed_cycles && !single && cyc >= 1) mg_predict_set(1, gn, cyc);
   if (!keep && !fast) arena_release(mark);  // with `keep` / `fast` the hierarchy stays in the caller's arena scope
-  return conv ? 0 : 1;
+  return s.conv ? 0 : 1;
 }
 
 // ====================================================================================================
@@ -1944,17 +1902,18 @@ void do_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_multi
   if (proj_type == VDN_INITIAL_PROJECTION && ctx().prm.prob_type == 4) abs_eps = 1.e-12;   // 125-127
   int ebc[3][2];
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc[d][s] = bct->ell_bc(n, 0, d, s, press_comp0);
-  int cyc; double r0, rr;
+  NdRequest q;
+  q.u = un; q.dx = dx; q.bc = ebc; q.rel_eps = rel; q.abs_eps = abs_eps; q.max_iter = ctx().prm.hg_max_iter;
   // Round 3: rh, phi and coeffs (hgproject.f90:70-76, hg_multigrid.f90:68-80) exist only to carry zeros, D u and 1 / rhohalf into the solver
   // and phi out of it: the solver takes sigma from rhohalf, forms b = -D u while it loads, and hg_update reads phi from the level array
   // (0.5 ms of fills, copies and passes per 256^3 projection; VDN_HG_FAST=0: the multifabs as the reference has them -- same values)
-  static const bool fast_on = !(vdn_env("VDN_HG_FAST") && atoi(vdn_env("VDN_HG_FAST")) == 0);
-  if (fast_on) {
+  if (hg_fast_on()) {
     hg_level_pre(proj_type, un, uo, rhh, gpp, nullptr, dt, bct);
     NdFast F; F.rhohalf = rhh;
-    int rc = nd_solve(nullptr, nullptr, nullptr, un, dx, ebc, rel, abs_eps, ctx().prm.hg_max_iter, &cyc, &r0, &rr, nullptr, &F);
-    ctx().solver_cycles[1] = cyc; ctx().solver_res0[1] = r0; ctx().solver_res[1] = rr;
-    solver_check(rc, "nodal multigrid", cyc, rr, r0);
+    q.fast = &F;
+    const int rc = nd_solve(q);
+    ctx().solver_cycles[1] = q.cycles; ctx().solver_res0[1] = q.res0; ctx().solver_res[1] = q.res;
+    solver_check(rc, "nodal multigrid", q.cycles, q.res, q.res0);
     hg_level_post(proj_type, un, uo, rhh, gpp, pp, nullptr, nullptr, dx, dt, &F.phi_view);
     mf_fill_boundary(gpp); mf_fill_boundary(pp);                      // hgproject.f90:359-362
     arena_release(mark);
@@ -1965,9 +1924,10 @@ void do_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_multi
   vdn_multifab *gphi = mf_temp(mla, n, 3, 0, -1, false, 0.0);
   vdn_multifab *coeffs = mf_temp(mla, n, 1, 1, -1, true, 0.0);        // ghosts 0: hg_multigrid.f90:73
   hg_level_pre(proj_type, un, uo, rhh, gpp, coeffs, dt, bct);
-  int rc = nd_solve(rh, phi, coeffs, un, dx, ebc, rel, abs_eps, ctx().prm.hg_max_iter, &cyc, &r0, &rr);
-  ctx().solver_cycles[1] = cyc; ctx().solver_res0[1] = r0; ctx().solver_res[1] = rr;
-  solver_check(rc, "nodal multigrid", cyc, rr, r0);
+  q.rh = rh; q.phi = phi; q.coeffs = coeffs;
+  const int rc = nd_solve(q);
+  ctx().solver_cycles[1] = q.cycles; ctx().solver_res0[1] = q.res0; ctx().solver_res[1] = q.res;
+  solver_check(rc, "nodal multigrid", q.cycles, q.res, q.res0);
   hg_level_post(proj_type, un, uo, rhh, gpp, pp, gphi, phi, dx, dt);
   mf_fill_boundary(gpp); mf_fill_boundary(pp);                        // hgproject.f90:359-362
   mf_temp_free(coeffs); mf_temp_free(gphi); mf_temp_free(phi); mf_temp_free(rh);
@@ -1979,23 +1939,6 @@ void do_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_multi
 // =====================================================================================================================
 // Works directly on the multifab fabs (nodal, one ghost layer).  This round: one fine box (the coarse level may be any
 // decomposition the single-level multigrid accepts), single rank.
-DEVI void ndf_apply(const FV &phi, const FV &sig, const double f[3], int i, int j, int k, double &Kp, double &diag) {
-  const NdW W = nd_weights(f);
-  double p[3][3][3], sg[2][2][2];
-  #pragma unroll
-  for (int c = 0; c < 3; c++)
-    #pragma unroll
-    for (int b = 0; b < 3; b++)
-      #pragma unroll
-      for (int a = 0; a < 3; a++) p[c][b][a] = fv_get(phi, i + a - 1, j + b - 1, k + c - 1);
-  #pragma unroll
-  for (int c = 0; c < 2; c++)
-    #pragma unroll
-    for (int b = 0; b < 2; b++)
-      #pragma unroll
-      for (int a = 0; a < 2; a++) sg[c][b][a] = fv_get(sig, i + a - 1, j + b - 1, k + c - 1);
-  nd_stencil(W, p, sg, Kp, diag);
-}
 struct NdfArgs { double f[3]; int lo[3], hi[3]; int dirlo[3], dirhi[3]; int cflo[3], cfhi[3]; int ilo[3], ihi[3]; };
 DEVI bool ndf_pdir(const NdfArgs &A, int i, int j, int k) {
   return (i == A.lo[0] && A.dirlo[0]) || (i == A.hi[0] && A.dirhi[0]) || (j == A.lo[1] && A.dirlo[1]) || (j == A.hi[1] && A.dirhi[1]) ||
@@ -2005,33 +1948,8 @@ DEVI bool ndf_cf(const NdfArgs &A, int i, int j, int k) {          // node on a 
   return (i == A.lo[0] && A.cflo[0]) || (i == A.hi[0] && A.cfhi[0]) || (j == A.lo[1] && A.cflo[1]) || (j == A.hi[1] && A.cfhi[1]) ||
          (k == A.lo[2] && A.cflo[2]) || (k == A.hi[2] && A.cfhi[2]);
 }
-// A.lo/hi: node range of the box.  excl: 0 none, 1 exclude interface nodes from the norm (fine), 2 exclude coarse nodes strictly
-// inside the fine box (A.ilo/ihi, coarse node indices)
-__global__ void kk_ndf_residual(FV b, FV phi, FV sig, FV res, NdfArgs A, int excl, Range3 r, double *nrm) {
-  REDUCE_IJ(r)
-  double rmax = 0.0;
-  if (in_ij) REDUCE_KLOOP(r) {
-    double rr = 0.0;
-    if (!ndf_pdir(A, i, j, k)) { double Kp, diag; ndf_apply(phi, sig, A.f, i, j, k, Kp, diag); rr = fv_get(b, i, j, k) - Kp; }
-    fv_at(res, i, j, k) = rr;
-    bool skip = false;
-    if (excl == 1) skip = ndf_cf(A, i, j, k) && !ndf_pdir(A, i, j, k);
-    if (excl == 2) skip = i > A.ilo[0] && i < A.ihi[0] && j > A.ilo[1] && j < A.ihi[1] && k > A.ilo[2] && k < A.ihi[2];
-    if (!skip) rmax = nmax(rmax, fabs(rr));
-  }
-  if (nrm) block_atomic_max(nrm, rmax);
-}
-__global__ void kk_ndf_jacobi(FV ein, FV eout, FV rb, FV sig, NdfArgs A, double omega, Range3 r) {
-  THREAD_IJK(r)
-  if (!in_range) return;
-  const double p0 = fv_get(ein, i, j, k);
-  double v = p0;
-  if (!ndf_pdir(A, i, j, k) && !ndf_cf(A, i, j, k)) { double Kp, diag; ndf_apply(ein, sig, A.f, i, j, k, Kp, diag); if (diag != 0.0) v = p0 + omega * ((fv_get(rb, i, j, k) - Kp) / diag); }
-  fv_at(eout, i, j, k) = v;
-}
-
-// k-marching forms of kk_ndf_jacobi / kk_ndf_residual (same structure as kk_nd_march: own-column loads, i-1 / i+1 columns by wave
-// shuffles, three phi planes and two sigma planes in registers).  r: the node range of the box; tiles of 62 nodes along i.
+// The sweep and the residual of the composite solve's boxes, k-marching (same structure as kk_nd_march: own-column loads, i-1 / i+1 columns by wave
+// shuffles, three phi planes and two sigma planes in registers).  A.lo/hi, r: the node range of the box; tiles of 62 nodes along i.
 // MODE 0: eout = ein + omega (rb - K ein)/diag on free nodes;  MODE 1: res = b - K phi (0 on physical Dirichlet nodes), max-norm
 // over the nodes that are not interface nodes (excl = 1) / all nodes (excl = 0)
 struct MarchB { FV phi, out, rb, sig, slave; int has_slave; NdfArgs A; Range3 r; int g[3], kchunk, sw; };      // sw: lanes of the segment that carries one node row (4 .. 64)
@@ -2231,14 +2149,11 @@ static MarchSet ndf_build_march(std::vector<MarchB> &v) {
   for (size_t b = 0; b < v.size(); b++) {
     MarchB &B = v[b];
     const int nx = B.r.hi[0] - B.r.lo[0] + 1, ny = B.r.hi[1] - B.r.lo[1] + 1, nz = B.r.hi[2] - B.r.lo[2] + 1;
-    static const bool paired = !(vdn_env("VDN_NDF_PAIR") && atoi(vdn_env("VDN_NDF_PAIR")) == 0);
     // the segment width that needs the fewest waves per node row (kk_ndf_march2: a lane carries two nodes): tiles along x / rows per wave; a box of
     // 33 nodes takes 19 lanes (17 pairs + the two feeding lanes), three rows per wave, where the power-of-two segments of round 3 gave it 32 and two
-    static const bool any_width = !(vdn_env("VDN_NDF_SEGW") && atoi(vdn_env("VDN_NDF_SEGW")) == 0);
-    const int per_lane = paired ? 2 : 1;
+    const int per_lane = ndf_pair_on() ? 2 : 1;
     int best = 64; double best_cost = 1e30;
     for (int sw = 4; sw <= 64; sw++) {
-      if (!any_width && (sw & (sw - 1))) continue;
       const double cost = (double)((nx + per_lane * (sw - 2) - 1) / (per_lane * (sw - 2))) / (double)(64 / sw);
       if (cost < best_cost - 1e-12) { best_cost = cost; best = sw; }
     }
@@ -2259,12 +2174,10 @@ static MarchSet ndf_build_march(std::vector<MarchB> &v) {
 }
 template <int MODE> static void ndf_run_march(const MarchSet &S, double omega, int excl, double *nrm) {
   if (S.nbox == 0) return;
-  static const bool paired = !(vdn_env("VDN_NDF_PAIR") && atoi(vdn_env("VDN_NDF_PAIR")) == 0);
-  if (paired) hipLaunchKernelGGL(kk_ndf_march2<MODE>, dim3(S.tot), NBLK, 0, ctx().stream, (const MarchB *)S.d_args, (const int *)S.d_start, S.nbox, omega, excl, nrm);
+  if (ndf_pair_on()) hipLaunchKernelGGL(kk_ndf_march2<MODE>, dim3(S.tot), NBLK, 0, ctx().stream, (const MarchB *)S.d_args, (const int *)S.d_start, S.nbox, omega, excl, nrm);
   else hipLaunchKernelGGL(kk_ndf_march<MODE>, dim3(S.tot), NBLK, 0, ctx().stream, (const MarchB *)S.d_args, (const int *)S.d_start, S.nbox, omega, excl, nrm);
 }
 
-static double ndf_read(double *d) { return read_scalar1(d); }
 // ---- composite nodal solve on arbitrary unions of boxes: node masks instead of per-face flags ----------------------------------
 // (batched kernels: one launch per operation and level, vdn_dev.h)
 // cell mask -> node mask.  mode 0 ("slave"): 1 on the nodes that are not physical Dirichlet nodes and touch a cell INSIDE the
@@ -2436,7 +2349,7 @@ void mlnd_kept_purge(unsigned long uid) {
 }
 // mode 0: slaves of level n <- P phi_{n-1};  mode 1: dst_n += P src_{n-1};  mode 2: dst_n = P src_{n-1} (dst zeroed first by the caller)
 static void ml_nd_prolong(MLND &S, int n, vdn_multifab *dst, vdn_multifab *src, int mode) {
-  static const bool faces_only = !(vdn_env("VDN_NDM_IFACE_FACES") && atoi(vdn_env("VDN_NDM_IFACE_FACES")) == 0);
+  const bool faces_only = ndm_iface_faces_on();
   const auto key = std::make_tuple(n, (const void *)dst, (const void *)src, mode == 0 ? 0 : 1);
   auto hit = S.pro.find(key);
   if (hit != S.pro.end()) { hit->second.Cv.refresh(); hit->second.s.run(mode, (double *)nullptr, ctx().stream); hit->second.s8.run(mode, (double *)nullptr, ctx().stream); return; }
@@ -2452,7 +2365,7 @@ static void ml_nd_prolong(MLND &S, int n, vdn_multifab *dst, vdn_multifab *src, 
     if (itk != g_ndpro_kept.end()) { PS.s = itk->second->s; PS.s8 = itk->second->s8; PS.s.run(mode, (double *)nullptr, ctx().stream); PS.s8.run(mode, (double *)nullptr, ctx().stream); return; }
     kept = new NdProKept; kept->uid = S.la->uid;     // (the table is bounded at the entry of ml_nd_solve: sets already bound to this solve must not be freed here)
   }
-  static const bool by_parent = !(vdn_env("VDN_NDM_PROLONG8") && atoi(vdn_env("VDN_NDM_PROLONG8")) == 0);
+  const bool by_parent = ndm_prolong8_on();
   std::vector<NdmProlongB> v; std::vector<NdmProlong8B> v8;
   const BoxBins cb(Cv.vbox, &Cv.have);
   for (size_t f = 0; f < S.A[n].size(); f++) {
@@ -2528,11 +2441,14 @@ static double ml_nd_residual(MLND &S, bool zero_field = false) {
     S.amax[n].run(0, S.d_nrm, st);
   }
   comm_allreduce_max_dev(S.d_nrm, 1);
-  return ndf_read(S.d_nrm);
+  return read_scalar1(S.d_nrm);
 }
 // rh, phi: nodal ng 1 per level; coeffs: cells ng 1 (ghost 0 outside the level); u: cells (>= 1 ghost); dx: [lev*3+d]
-static int ml_nd_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vdn_multifab **coeffs, vdn_multifab **u, const double *dx,
-                       const vdn_bc_tower *bct, int press_comp0, double rel_eps, double abs_eps, int max_iter, int *iters, double *res0, double *res) {
+struct MlNdRequest : MgRequest { vdn_layout *la = nullptr; vdn_multifab **rh = nullptr, **phi = nullptr, **coeffs = nullptr, **u = nullptr; const vdn_bc_tower *bct = nullptr; int press_comp0 = 0; };
+static int ml_nd_solve(MlNdRequest &rq) {
+  vdn_layout *la = rq.la; vdn_multifab **rh = rq.rh, **phi = rq.phi, **coeffs = rq.coeffs, **u = rq.u;
+  const double *dx = rq.dx; const vdn_bc_tower *bct = rq.bct; const int press_comp0 = rq.press_comp0;
+  REQUIRE(la && rh && phi && coeffs && u && dx && bct, "composite nodal solve: la, rh, phi, coeffs, u, dx and bct");
   const int L = la->nlev;
   REQUIRE(L >= 2 && L <= VDN_MAXLEV, "composite nodal solve: 2..%d levels", VDN_MAXLEV);
   g_nd_iso = nd_isotropic(dx);                         // (the ratio of the spacings is the same on every level)
@@ -2700,15 +2616,17 @@ static int ml_nd_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vd
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc0[d][s] = bct->ell_bc(0, 0, d, s, press_comp0);
   int it = 0; bool conv = (bnorm == 0.0); double rn = 0.0;
   NdKeep coarse_keep;                        // the level-0 multigrid hierarchy is built once for all FAC iterations
-  static const bool neg_copy = vdn_env("VDN_NDM_NEG") && atoi(vdn_env("VDN_NDM_NEG")) != 0;
+  const bool neg_copy = ndm_neg_copy();
   while (!conv) {
     rn = ml_nd_residual(S);
-    if ((rn <= rel_eps * bnorm && bnorm < HUGE_VAL) || rn <= abs_eps) { conv = true; break; }
-    if (it >= max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;
+    if (mg_converged(rn, bnorm, rq.rel_eps, rq.abs_eps)) { conv = true; break; }
+    if (it >= rq.max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;
     // coarse correction K_0 e = r_0: one V-cycle of the single-level solver from e = 0, the composite residual loaded as its b
     // (VDN_NDM_NEG=1: through a negated copy and a zero-filled e, as rounds 2 built it -- same bits)
-    int cyc; double r0, rr;
-    if (!neg_copy) nd_solve(S.res[0], ee, coeffs[0], nullptr, dx, ebc0, 0.0, -1.0, -1, &cyc, &r0, &rr, &coarse_keep, nullptr, it == 0, true, S.phi[0]);
+    NdRequest c;
+    c.phi = ee; c.coeffs = coeffs[0]; c.dx = dx; c.bc = ebc0; c.fixed_cycles = 1; c.keep = &coarse_keep;
+    c.fmg_start = it == 0;                              // (first correction: from the nested iteration, hg_fmg)
+    if (!neg_copy) { c.rh = S.res[0]; c.rh_is_b = true; c.add_to = S.phi[0]; nd_solve(c); }
     else {
       mf_setval(ee, 0.0, 0, 1, true);                   // (er: every node is overwritten below, its ghost nodes are never written and stay zero)
       std::vector<NdfNegB> v;
@@ -2717,7 +2635,7 @@ static int ml_nd_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vd
         v.push_back(q);
       }
       launch_batched(v, 0, (double *)nullptr, 0, st);
-      nd_solve(er, ee, coeffs[0], nullptr, dx, ebc0, 0.0, -1.0, -1, &cyc, &r0, &rr, &coarse_keep, nullptr, it == 0);     // (first correction: from the nested iteration, hg_fmg)
+      c.rh = er; nd_solve(c);
     }
     if (neg_copy) ml_nd_add(S, 0, S.phi[0], ee);           // (otherwise phi_0 += e_0 was done where e_0 was stored)
     // the finer levels, coarsest first, in correction form (oracle: vo_ml_nd_solve): e_n = P e_{n-1} (trilinear, not on physical Dirichlet nodes),
@@ -2742,7 +2660,7 @@ static int ml_nd_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vd
   }
   if (S.multi[0]) mf_fill_boundary(S.phi[0]);
   for (int n = 1; n < L; n++) ml_nd_interface(S, n);
-  if (iters) *iters = it; if (res0) *res0 = bnorm; if (res) *res = rn;
+  rq.cycles = it; rq.res0 = bnorm; rq.res = rn;
   HIPCHK(hipStreamSynchronize(st));
   for (size_t i = temps.size(); i-- > 0;) mf_temp_free(temps[i]);
   arena_release(mark);
@@ -2767,10 +2685,12 @@ static void do_ml_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew,
   double rel = ctx().prm.hg_rel_eps > 0.0 ? ctx().prm.hg_rel_eps : (L == 2 ? 1.e-11 : 1.e-10);
   double abs_eps = -1.0;
   if (proj_type == VDN_INITIAL_PROJECTION && ctx().prm.prob_type == 4) abs_eps = 1.e-12;
-  int it; double r0, rr;
-  int rc = ml_nd_solve(mla, rh, phi, coeffs, unew, dx, bct, press_comp0, rel, abs_eps, ctx().prm.hg_max_iter, &it, &r0, &rr);
-  ctx().solver_cycles[1] = it; ctx().solver_res0[1] = r0; ctx().solver_res[1] = rr;
-  solver_check(rc, "composite nodal solve", it, rr, r0);
+  MlNdRequest q;
+  q.la = mla; q.rh = rh; q.phi = phi; q.coeffs = coeffs; q.u = unew; q.dx = dx; q.bct = bct; q.press_comp0 = press_comp0;
+  q.rel_eps = rel; q.abs_eps = abs_eps; q.max_iter = ctx().prm.hg_max_iter;
+  const int rc = ml_nd_solve(q);
+  ctx().solver_cycles[1] = q.cycles; ctx().solver_res0[1] = q.res0; ctx().solver_res[1] = q.res;
+  solver_check(rc, "composite nodal solve", q.cycles, q.res, q.res0);
   for (int n = 0; n < L; n++) hg_level_post(proj_type, unew[n], uold[n], rhohalf[n], gp[n], p[n], gphi[n], phi[n], dx + 3 * n, dt);
   for (int n = L - 1; n >= 1; n--) ml_cc_restriction(gp[n - 1], gp[n], 0, 3);      // hgproject.f90:355-357
   for (int n = 0; n < L; n++) { mf_fill_boundary(gp[n]); mf_fill_boundary(p[n]); }

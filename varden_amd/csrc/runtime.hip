@@ -26,7 +26,7 @@ void vdn_fail(const char *fmt, ...) {
 
 // also drops the pointers advance_timestep keeps INTO the arena (limited slopes of uold, max |umac|): a step that ended in an exception
 // (solver_check throws by default) must not leave them dangling for the next stand-alone vdn_k_mkflux / vdn_k_velpred
-static bool arena_poison() { static const bool p = vdn_env("VDN_ARENA_POISON") && atoi(vdn_env("VDN_ARENA_POISON")) != 0; return p; }
+static bool arena_poison() { static const bool p = env_set("VDN_ARENA_POISON"); return p; }
 // the descriptors of arena temporaries (mf_temp) that nobody freed: they die with the arena contents they describe
 static std::vector<vdn_multifab *> g_temp_mfs;
 void arena_reset() {
@@ -93,7 +93,7 @@ static void arena_destroy() {
 // the fields of a ONE-level layout, which are created once: the one-box 512^3 step runs 3 % slower on chunk-backed fields than on hipMalloc blocks (7 % on 1 GB chunks;
 // a per-field offset into the chunk did not change that: profiles/r06_allocator_ab.txt) -- the boxes of a hierarchy are small and show no difference.
 static size_t field_chunk() { static const size_t v = env_mb("VDN_FIELD_CHUNK_MB", 64); return v; }
-static size_t field_small() { static const size_t v = vdn_env("VDN_FIELD_VMM") && atoi(vdn_env("VDN_FIELD_VMM")) == 0 ? ~(size_t)0 : (size_t)32 << 20; return v; }
+static size_t field_small() { static const size_t v = !env_on("VDN_FIELD_VMM") ? ~(size_t)0 : (size_t)32 << 20; return v; }
 #define FIELD_CHUNK field_chunk()
 #define FIELD_SMALL field_small()
 struct FieldAlloc { void *va; size_t va_bytes; std::vector<hipMemGenericAllocationHandle_t> chunks; };
@@ -222,9 +222,8 @@ static const EnvSwitch g_switches[] = {
   { "VDN_FUSED_KCHUNKS", "k-chunks of the fused marches (default: the count that fills the last round of workgroups best)" },
   { "VDN_GOD_UPDATE", "0: update_3d as its own pass instead of inside the fused mkflux march" },
   { "VDN_GSRB_PAIR", "0: one cell per thread in the colour passes / residuals of wide levels instead of the 2 x 2 pair form" },
-  { "VDN_MAC_SPLIT", "0: the finest level of macproject's one-level solve stays interleaved (kk_cc_gsrb_rho_pair) instead of stored by colour (kk_cc_gsrb_rho_split); 2: only the colour passes on the split arrays, the residual on the level array" },
+  { "VDN_MAC_SPLIT", "0: the finest level of macproject's one-level solve stays interleaved (kk_cc_gsrb_rho_pair) instead of stored by colour (kk_cc_gsrb_rho_split)" },
   { "VDN_MAC_SPLIT_MIN", "fewest cells (of this rank's boxes together) of a level stored by colour (default 2^23)" },
-  { "VDN_MAC_SPLIT_HALO", "0: only a one-box level without periodic faces is stored by colour (round 5); default: any box list, periodic faces and several ranks too, the ghost exchange on the split arrays" },
   { "VDN_ND_REV", "0: every march of a nodal level walks its tiles in the same order (default: consecutive marches alternate)" },
   { "VDN_MAC_SLAB", "planes per slab of the time-skewed schedule of the split level's passes (cc_split_run; default: ~200 MB of pass traffic, at most half the level); 0: whole-level launches" },
   { "VDN_MAC_UMAX", "0: max |umac| by its own pass (kk_macmax) instead of inside macproject's velocity update (kk_mkumac_rho_max)" },
@@ -243,7 +242,6 @@ static const EnvSwitch g_switches[] = {
   { "VDN_ND_LEAN", "0: whole-array zero fills of the big nodal levels instead of shell-only" },
   { "VDN_ND_RESTRICT_FUSED", "0: nodal residual and full weighting as two passes" },
   { "VDN_ND_PROLONG_FUSED", "0: nodal prolongation as a pass of its own instead of inside the first post-smoothing march" },
-  { "VDN_NDF_SEGW", "0: the marches of the composite nodal solve use power-of-two lane segments per node row only" },
   { "VDN_NDF_PAIR", "0: one node per lane in the box-batched nodal march of the composite solve" },
   { "VDN_NDM_IFACE_FACES", "0: interface interpolation of the composite nodal solve over whole boxes instead of box faces" },
   { "VDN_NDM_PROLONG8", "0: correction interpolation with a thread per fine node instead of per coarse node" },
@@ -329,7 +327,7 @@ const double *read_scalars(const double *dev, int n) {
   static unsigned long long seq = 0;
   // VDN_POLL: 1 = spin, 0 = synchronise always; unset: spin on a one-rank run, synchronise when several ranks run (each rank's spinning thread would
   // take a core from RCCL's proxy threads and from the other ranks of an oversubscribed host)
-  static const int poll_env = vdn_env("VDN_POLL") ? atoi(vdn_env("VDN_POLL")) : -1;
+  static const int poll_env = env_int("VDN_POLL", -1);
   const bool poll = poll_env >= 0 ? poll_env != 0 : c.nranks == 1;
   ++seq;
   dbg_sync(8);
@@ -713,7 +711,7 @@ vdn_multifab *mf_temp(const vdn_layout *la, int lev, int nc, int ng, int face_di
   mf->base = (double *)arena_alloc(mf->bytes);
   for (auto &f : mf->fabs) f.p = (double *)((char *)mf->base + (uintptr_t)f.p);
   {   // (VDN_PHASE_HASH: every temporary starts from zeros, so that entries nobody writes -- and nobody reads -- do not differ from process to process in the checksums)
-    static const bool clr = vdn_env("VDN_PHASE_HASH") && atoi(vdn_env("VDN_PHASE_HASH")) != 0;
+    static const bool clr = env_set("VDN_PHASE_HASH");
     if (clr) HIPCHK(hipMemsetAsync(mf->base, 0, mf->bytes, g_ctx.stream));
   }
   if (fill) mf_setval(mf, val, 0, nc, true);
@@ -728,10 +726,10 @@ void mf_temp_free(vdn_multifab *mf) {
 
 // descriptor sets kept across calls (vdn_internal.h)
 static std::map<unsigned long long, KeptSet> g_kept;
-bool kept_sets_enabled() { static const bool on = !(vdn_env("VDN_KEEP_SETS") && atoi(vdn_env("VDN_KEEP_SETS")) == 0); return on; }
+bool kept_sets_enabled() { static const bool on = env_on("VDN_KEEP_SETS"); return on; }
 // VDN_KEEP_OFF: a mask of families switched off one by one (1 the generic launch_batched_kept sets, 2 create_umac_grown, 4 the composite cell-centred solve, 8 the nodal prolongation)
-void dbg_sync(int bit) { static const int m = vdn_env("VDN_SYNC_POINTS") ? atoi(vdn_env("VDN_SYNC_POINTS")) : 0; if (m & bit) HIPCHK(hipDeviceSynchronize()); }
-bool kept_family_enabled(int fam) { static const int off = vdn_env("VDN_KEEP_OFF") ? atoi(vdn_env("VDN_KEEP_OFF")) : 0; return kept_sets_enabled() && !(off & fam); }
+void dbg_sync(int bit) { static const int m = env_int("VDN_SYNC_POINTS", 0); if (m & bit) HIPCHK(hipDeviceSynchronize()); }
+bool kept_family_enabled(int fam) { static const int off = env_int("VDN_KEEP_OFF", 0); return kept_sets_enabled() && !(off & fam); }
 KeptSet *kept_find(unsigned long long key) { auto it = g_kept.find(key); return it == g_kept.end() ? nullptr : &it->second; }
 static void kept_free(KeptSet &k) { if (k.d_args) HIPCHK(hipFree(k.d_args)); if (k.d_start) HIPCHK(hipFree(k.d_start)); k.d_args = nullptr; k.d_start = nullptr; }
 static KeeperMem *g_keeper = nullptr;
@@ -758,7 +756,7 @@ void kept_purge(unsigned long uid) {
 }
 // the size bounds of the three tables (plain sets here, the groups of the composite solves in amr.hip / mg_nd.hip); VDN_KEPT_BOUND shrinks them for
 // the eviction test (tests/test_amr_gpu.py)
-int kept_bound(int dflt) { static const int env = vdn_env("VDN_KEPT_BOUND") ? atoi(vdn_env("VDN_KEPT_BOUND")) : 0; return env > 0 ? env : dflt; }
+int kept_bound(int dflt) { static const int env = env_int("VDN_KEPT_BOUND", 0); return env > 0 ? env : dflt; }
 KeptSet *kept_store(unsigned long long key, unsigned long uid, const void *args, size_t arg_bytes, const int *start, int nbox, int tot) {
   // Bounded (temporaries that wander through the arena), rebuilt on demand.  This runs INSIDE the composite solves (launch_batched_kept), whose own
   // groups (MLCCKept, NdProKept) are bound to the running solve: the bound drops the plain entries only -- nobody holds a KeptSet across a store --
@@ -1020,12 +1018,6 @@ DEVI void physbc_cell(const FV &f, const PhysArgs &A, int b1, int b2) {
     q[A.d] = edge - in * g;
     fv_at(f, q[0], q[1], q[2], A.comp) = v;
   }
-}
-__global__ void k_physbc(FV f, PhysArgs A) {
-  int b1 = A.r1lo + (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  int b2 = A.r2lo + (int)(blockIdx.y * blockDim.y + threadIdx.y);
-  if (b1 > A.r1hi || b2 > A.r2hi) return;
-  physbc_cell(f, A, b1, b2);
 }
 // one box: the faces of one direction (two sides x the components) in ONE launch, descriptors as kernel arguments, blockIdx.z = face
 constexpr int PHYS_MULTI = 8;

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdarg>
 #include <cstring>
+#include <cstdlib>
 #include <stdexcept>
 #include <cmath>
 #include "../../include/varden_amd.h"
@@ -103,6 +104,9 @@ VdnCtx &ctx();
 
 // the one way the library reads its environment: getenv for a name declared in the switch table of runtime.hip (fails for any other name)
 const char *vdn_env(const char *name);
+inline bool env_on(const char *name) { const char *e = vdn_env(name); return !(e && atoi(e) == 0); }           // on unless "0"
+inline bool env_set(const char *name) { const char *e = vdn_env(name); return e && atoi(e) != 0; }            // off unless non-zero
+inline int  env_int(const char *name, int dflt) { const char *e = vdn_env(name); return e ? atoi(e) : dflt; } // an integer with a default
 // error handling: C-ABI functions wrap their body in VDN_TRY/VDN_CATCH
 void vdn_set_error(const char *fmt, ...);
 struct VdnErr : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -329,11 +333,31 @@ void do_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn
                    const vdn_bc_tower *bct, int bc_comp0);
 // cc_solve's fast path for macproject on one level (mg_cc.hip): right-hand side from the MAC field, coefficients from rho, phi handed back as views
 struct CcFast { vdn_multifab **um = nullptr; const vdn_multifab *mac_rhs = nullptr, *rho = nullptr; std::vector<FV> phi_view; };
-int  cc_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int bc[3][2],
-              double rel_eps, double abs_eps, int max_iter, int *cycles, double *res0, double *res,
-              const vdn_multifab *alpha = nullptr, const vdn_multifab *rho = nullptr,    // rho: beta = 2/(rho_i + rho_i-1), recomputed on the finest level
-              struct CcKeep *keep = nullptr, CcFast *fast = nullptr, int fmg = 0, bool zero_guess = false, vdn_multifab *add_to = nullptr,
-              double const_beta = 0.0);      // const_beta > 0 (with alpha): every face coefficient of `beta` is this constant (visc_solve, diff_scalar_solve) -- the finest level may then live by colour without coefficient arrays   // fmg: the caller's phi is zero and max_iter >= 0: start from the nested iteration (cc_fmg); zero_guess (a kept hierarchy's later calls, max_iter < 0): phi is not read, the guess is zero; add_to += the solution on the valid cells          // keep: see mg_cc.hip (hierarchy kept between the calls of a composite solve)
+// ---- solve requests: what a multigrid solve is asked to do, and what it did.  Plain argument records: the callers name the fields they set, the solvers check the
+// combination at their top and read it; nothing else lives here.
+struct MgRequest {                         // what every solver takes
+  const double *dx = nullptr;
+  const int (*bc)[2] = nullptr;            // bc[3][2]: the elliptic boundary types of the domain faces
+  double rel_eps = 0.0, abs_eps = -1.0;    // converged when |res| <= rel_eps |rhs| or |res| <= abs_eps
+  int max_iter = 0;                        // most V-cycles (FAC iterations) of a solve that tests its residual
+  int cycles = 0;                          // results: cycles run, ...
+  double res0 = 0.0, res = 0.0;            // ... the norm of the right-hand side and of the last residual
+};
+struct MgLevelRequest : MgRequest {        // ... and the two single-level solvers
+  int fixed_cycles = 0;                    // > 0: exactly this many V-cycles, no norms, no convergence test (the coarse correction of the composite solves)
+  vdn_multifab *add_to = nullptr;          // += the solution on the valid cells / nodes
+};
+struct CcRequest : MgLevelRequest {
+  vdn_multifab *rh = nullptr, *phi = nullptr, **beta = nullptr;
+  const vdn_multifab *alpha = nullptr;
+  const vdn_multifab *rho = nullptr;       // beta = 2 / (rho_i + rho_i-1), recomputed on the finest level
+  double const_beta = 0.0;                 // > 0 (with alpha): every face coefficient of `beta` is this constant (visc_solve, diff_scalar_solve) -- the finest level may then live by colour without coefficient arrays
+  struct CcKeep *keep = nullptr;           // see mg_cc.hip (hierarchy kept between the calls of a composite solve)
+  CcFast *fast = nullptr;
+  bool fmg = false;                        // the caller's phi is zero and the solve tests its residual: start from the nested iteration (cc_fmg)
+  bool zero_guess = false;                 // a kept hierarchy's later calls (fixed_cycles): phi is not read, the guess is zero
+};
+int  cc_solve(CcRequest &q);
 struct CcKeep *cc_keep_new(); void cc_keep_free(struct CcKeep *k);
 int  mg_agglom(const vdn_layout *la, int lev);     // box width below which a multi-box multigrid level is gathered into one box (mg_cc.hip)
 void cc_smooth(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int bc[3][2], int nsweeps);
@@ -350,9 +374,15 @@ void do_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_multi
                   vdn_multifab **p, vdn_multifab **gp, const double *dx, double dt, const vdn_bc_tower *bct, int press_comp0);
 // nd_solve's fast path for hgproject on one level (mg_nd.hip): sigma = 1 / rhohalf, rh = phi = 0 on entry, phi handed back as views
 struct NdFast { const vdn_multifab *rhohalf = nullptr; std::vector<FV> phi_view; };
-int  nd_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, const vdn_multifab *u, const double *dx,
-              const int bc[3][2], double rel_eps, double abs_eps, int max_iter, int *cycles, double *res0, double *res, struct NdKeep *keep = nullptr,
-              NdFast *fast = nullptr, bool fmg_start = false, bool rh_is_b = false, vdn_multifab *add_to = nullptr);      // fmg_start: nested iteration before a FIXED number of cycles (max_iter < 0; the caller's phi is zero); rh_is_b: `rh` holds b = -rh and phi is not read (zero guess; max_iter < 0); add_to += the solution on the valid nodes
+struct NdRequest : MgLevelRequest {
+  vdn_multifab *rh = nullptr, *phi = nullptr;
+  const vdn_multifab *coeffs = nullptr, *u = nullptr;
+  struct NdKeep *keep = nullptr;
+  NdFast *fast = nullptr;
+  bool fmg_start = false;                  // nested iteration before a FIXED number of cycles (the caller's phi is zero)
+  bool rh_is_b = false;                    // `rh` holds b = -rh and phi is not read (zero guess; fixed_cycles)
+};
+int  nd_solve(NdRequest &q);
 
 // dim2.hip: the dm = 2 path (one level, one box)
 void k2_mkvelforce(vdn_multifab *vf, const vdn_multifab *ext, const vdn_multifab *s, const vdn_multifab *gp, const vdn_multifab *lapu, double visc_fac);
@@ -360,15 +390,13 @@ void k2_mkscalforce(vdn_multifab *sf, const vdn_multifab *ext, const vdn_multifa
 void k2_update(const vdn_multifab *sold, vdn_multifab **umac, vdn_multifab **sedge, vdn_multifab **flux, const vdn_multifab *force, vdn_multifab *snew,
                const double *dx, double dt, bool is_vel, const int *is_cons);
 void k2_estdt_max(const vdn_multifab *u, const vdn_multifab *s, const vdn_multifab *gp, const vdn_multifab *ext, double out6[6]);
-int  cc2_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int bc[3][2], double rel_eps, double abs_eps, int max_iter,
-               int *cycles, double *res0, double *res, const vdn_multifab *alpha);
+int  cc2_solve(CcRequest &q);
 void do2_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn_multifab **mac_rhs, const double *dx, const vdn_bc_tower *bct, int bc_comp0);
 void k2_explicit_diffusive_term(vdn_multifab *lap, const vdn_multifab *data, int comp, int bccomp0, const double *dx, const vdn_bc_tower *bct);
 void do2_visc_solve(vdn_layout *mla, vdn_multifab *unew, const vdn_multifab *lapu, const vdn_multifab *rho, const vdn_multifab *mac_rhs,
                     const double *dx, double mu, const vdn_bc_tower *bct);
 void do2_diff_scalar_solve(vdn_layout *mla, vdn_multifab *snew, const vdn_multifab *laps, const double *dx, double mu, const vdn_bc_tower *bct, int icomp, int bccomp0);
-int  nd2_solve(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *coeffs, const vdn_multifab *u, const double *dx, const int bc[3][2],
-               double rel_eps, double abs_eps, int max_iter, int *cycles, double *res0, double *res);
+int  nd2_solve(NdRequest &q);
 void do2_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_multifab **uold, vdn_multifab **rhohalf, vdn_multifab **p, vdn_multifab **gp,
                    const double *dx, double dt, const vdn_bc_tower *bct, int press_comp0);
 
@@ -381,9 +409,14 @@ void ml_edge_restriction(vdn_multifab *crse, const vdn_multifab *fine, int dir, 
 void ml_fill_ghost_cells(vdn_multifab *fine, const vdn_multifab *crse, int icomp, int nc);
 void ml_create_umac_grown(vdn_multifab *fine, const vdn_multifab *crse, int dir);
 void ml_restrict_and_fill(int nlev, vdn_multifab **mf, int icomp, int bcomp, int nc, bool same_boundary, const vdn_bc_tower *bct);
-int ml_cc_solve(vdn_layout *la, vdn_multifab **rh, vdn_multifab **phi, vdn_multifab **beta, const double *dx, const vdn_bc_tower *bct, int bc_comp0,
-                double rel_eps, int max_iter, int *iters, double *res0, double *res, vdn_multifab **alpha, vdn_multifab **base_beta = nullptr, const vdn_multifab *base_rho = nullptr, const vdn_multifab *fine_rho = nullptr,
-                double const_beta = 0.0);      // const_beta > 0: every face coefficient on every level is this constant (the viscous / diffusive solves): handed to level 0's V-cycles
+struct MlCcRequest : MgRequest {           // the composite cell-centred solve: one multifab per level
+  vdn_layout *la = nullptr;
+  vdn_multifab **rh = nullptr, **phi = nullptr, **beta = nullptr, **alpha = nullptr;
+  const vdn_bc_tower *bct = nullptr; int bc_comp0 = 0;
+  vdn_multifab **base_beta = nullptr; const vdn_multifab *base_rho = nullptr, *fine_rho = nullptr;
+  double const_beta = 0.0;                 // > 0: every face coefficient on every level is this constant (the viscous / diffusive solves): handed to level 0's V-cycles
+};
+int ml_cc_solve(MlCcRequest &q);
 void do_ml_visc_solve(vdn_layout *mla, vdn_multifab **unew, vdn_multifab **lapu, vdn_multifab **rho, vdn_multifab **mac_rhs,
                       const double *dx, double mu, const vdn_bc_tower *bct);
 void do_ml_diff_scalar_solve(vdn_layout *mla, vdn_multifab **snew, vdn_multifab **laps, const double *dx, double mu,

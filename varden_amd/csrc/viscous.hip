@@ -108,9 +108,11 @@ void do_visc_solve(vdn_layout *mla, vdn_multifab *unew, const vdn_multifab *lapu
   for (int d = 0; d < 3; d++) {
     visc_rhs_level(rh, phi, unew, lapu, rho, mac_rhs, d, mu, dx[d], visc_mu_dt);
     int ebc[3][2]; ell_of(bct, n, d, ebc);                                             // bc_comp = d, viscsolve.f90:99
-    int cyc; double r0, rr;
-    int rc = cc_solve(rh, phi, beta, dx, ebc, 1.e-12, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, alpha, nullptr, nullptr, nullptr, 0, false, nullptr, mu);   // viscsolve.f90:88-89 (beta = mu on every face)
-    solver_check(rc, "viscous solve", cyc, rr, r0, d);
+    CcRequest q;
+    q.rh = rh; q.phi = phi; q.alpha = alpha; q.beta = beta; q.const_beta = mu;         // viscsolve.f90:88-89 (beta = mu on every face)
+    q.dx = dx; q.bc = ebc; q.rel_eps = 1.e-12; q.max_iter = ctx().prm.mg_max_iter;
+    const int rc = cc_solve(q);
+    solver_check(rc, "viscous solve", q.cycles, q.res, q.res0, d);
     mf_copy(unew, d, phi, 0, 1, 0);                                                    // viscsolve.f90:103
   }
   mf_restrict_and_fill(unew, 0, 0, 3, false, bct);                                     // viscsolve.f90:106
@@ -134,9 +136,12 @@ void do_ml_visc_solve(vdn_layout *mla, vdn_multifab **unew, vdn_multifab **lapu,
   const double visc_mu_dt = (ctx().prm.diffusion_type == 1) ? 2.0 * mu : mu;
   for (int d = 0; d < 3; d++) {
     for (int n = 0; n < L; n++) visc_rhs_level(rh[n], phi[n], unew[n], lapu[n], rho[n], mac_rhs[n], d, mu, dx[3 * n + d], visc_mu_dt);
-    int it; double r0, rr;
-    int rc = ml_cc_solve(mla, rh, phi, beta, dx, bct, d, 1.e-12, ctx().prm.mg_max_iter, &it, &r0, &rr, alpha, nullptr, nullptr, nullptr, mu);      // bc_comp = d, viscsolve.f90:88-99
-    solver_check(rc, "composite viscous solve", it, rr, r0, d);
+    MlCcRequest q;
+    q.la = mla; q.rh = rh; q.phi = phi; q.alpha = alpha; q.beta = beta; q.const_beta = mu;
+    q.dx = dx; q.bct = bct; q.bc_comp0 = d;                                                       // bc_comp = d, viscsolve.f90:88-99
+    q.rel_eps = 1.e-12; q.max_iter = ctx().prm.mg_max_iter;
+    const int rc = ml_cc_solve(q);
+    solver_check(rc, "composite viscous solve", q.cycles, q.res, q.res0, d);
     for (int n = 0; n < L; n++) mf_copy(unew[n], d, phi[n], 0, 1, 0);                            // viscsolve.f90:103
   }
   ml_restrict_and_fill(L, unew, 0, 0, 3, false, bct);                                            // viscsolve.f90:106
@@ -156,9 +161,11 @@ void do_diff_scalar_solve(vdn_layout *mla, vdn_multifab *snew, const vdn_multifa
   for (int d = 0; d < 3; d++) beta[d] = mf_temp(mla, n, 1, 0, d, true, mu);
   diff_rhs_level(rh, phi, snew, laps, icomp, mu);
   int ebc[3][2]; ell_of(bct, n, bccomp0, ebc);
-  int cyc; double r0, rr;
-  int rc = cc_solve(rh, phi, beta, dx, ebc, 1.e-12, -1.0, ctx().prm.mg_max_iter, &cyc, &r0, &rr, alpha, nullptr, nullptr, nullptr, 0, false, nullptr, mu);
-  solver_check(rc, "diffusive solve", cyc, rr, r0);
+  CcRequest q;
+  q.rh = rh; q.phi = phi; q.alpha = alpha; q.beta = beta; q.const_beta = mu;
+  q.dx = dx; q.bc = ebc; q.rel_eps = 1.e-12; q.max_iter = ctx().prm.mg_max_iter;
+  const int rc = cc_solve(q);
+  solver_check(rc, "diffusive solve", q.cycles, q.res, q.res0);
   mf_copy(snew, icomp, phi, 0, 1, 0);                                                  // viscsolve.f90:374
   mf_fill_boundary(snew);                                                              // 378-381 (all comps: a superset of fill_boundary_c)
   mf_physbc(snew, icomp, bccomp0, 1, bct, false);
@@ -178,9 +185,11 @@ void do_ml_diff_scalar_solve(vdn_layout *mla, vdn_multifab **snew, vdn_multifab 
     for (int d = 0; d < 3; d++) beta[3 * n + d] = mf_temp(mla, n, 1, 0, d, true, mu);
     diff_rhs_level(rh[n], phi[n], snew[n], laps[n], icomp, mu);
   }
-  int it; double r0, rr;
-  int rc = ml_cc_solve(mla, rh, phi, beta, dx, bct, bccomp0, 1.e-12, ctx().prm.mg_max_iter, &it, &r0, &rr, alpha, nullptr, nullptr, nullptr, mu);
-  solver_check(rc, "composite diffusive solve", it, rr, r0);
+  MlCcRequest q;
+  q.la = mla; q.rh = rh; q.phi = phi; q.alpha = alpha; q.beta = beta; q.const_beta = mu;
+  q.dx = dx; q.bct = bct; q.bc_comp0 = bccomp0; q.rel_eps = 1.e-12; q.max_iter = ctx().prm.mg_max_iter;
+  const int rc = ml_cc_solve(q);
+  solver_check(rc, "composite diffusive solve", q.cycles, q.res, q.res0);
   for (int n = 0; n < L; n++) mf_copy(snew[n], icomp, phi[n], 0, 1, 0);                          // viscsolve.f90:374
   ml_restrict_and_fill(L, snew, icomp, bccomp0, 1, false, bct);                                  // 378-381
   for (int n = L - 1; n >= 0; n--) { for (int d = 2; d >= 0; d--) mf_temp_free(beta[3 * n + d]); mf_temp_free(alpha[n]); mf_temp_free(phi[n]); mf_temp_free(rh[n]); }
