@@ -125,8 +125,8 @@ typedef struct vdn_bc_tower vdn_bc_tower;  /* define_bc_module::bc_tower        
 /* runtime                                                                                     */
 /* ------------------------------------------------------------------------------------------- */
 int  vdn_init(const vdn_params *prm, int rank, int nranks, int device);
-/* Debug / measurement switches.  The library reads environment variables VDN_* only through one table (varden_amd/csrc/runtime.hip, g_switches): each
- * selects between launch forms that the test suite holds bit-for-bit equal, or is a probe; none changes a result, none is needed in production.  This call
+/* Debug / measurement switches.  The library reads environment variables VDN_* only through one list (varden_amd/csrc/vdn_switches.h: name, reading rule, default
+ * and meaning of each, read once per process into one struct): each selects between launch forms that the test suite holds bit-for-bit equal, or is a probe; none changes a result, none is needed in production.  This call
  * returns the table as text -- one line per switch: name, current value, what it does.  vdn_init warns on stderr about VDN_* variables that are not in it.
  * Groups: transport rehearsal (VDN_FORCE_PACKED, VDN_RCCL_LIB + VDN_TESTING); runtime (VDN_ARENA_POISON, VDN_POLL, VDN_NO_GRAPHS,
  * VDN_NO_ROCTX, VDN_KEEP_SETS, VDN_KEPT_BOUND); advance (VDN_NO_SLOPE_CACHE, VDN_NO_FORCE_REUSE); Godunov launch forms (VDN_GOD_*, VDN_GODUNOV_*, VDN_SLOPES_MARCH,

@@ -3,11 +3,11 @@ mg_bottom_solver = hg_bottom_solver = 2, two steps; ranks are processes on ONE G
 rendezvous a file.  argv: rank nranks idfile outprefix"""
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests.children import rendezvous, save_rank  # noqa: E402
 
 
 def main():
@@ -17,19 +17,7 @@ def main():
     from varden_amd import driver
     from varden_amd.capi import default_params
     prm = default_params(cflfac=0.9, mg_bottom_solver=2, hg_bottom_solver=2)
-    comm_id = None
-    if nranks > 1:
-        bl.initialize(prm, rank, nranks, 0)
-        if rank == 0:
-            cid = bl.comm_get_unique_id()
-            with open(idfile + ".tmp", "wb") as f:
-                f.write(cid)
-            os.rename(idfile + ".tmp", idfile)
-        t0 = time.time()
-        while not os.path.exists(idfile):
-            time.sleep(0.01)
-            assert time.time() - t0 < 120, "rendezvous timed out"
-        comm_id = open(idfile, "rb").read()
+    comm_id = rendezvous(bl, prm, rank, nranks, idfile)
     n, decomp = (44, 22, 22), (2, 1, 1)
     h = 1.0 / max(n)
     G = driver.Varden(n, [[bl.NO_SLIP_WALL] * 2] * 3, prm, prob_type=1, grav=-9.8, prob_hi=tuple(n[d] * h for d in range(3)), init_shrink=0.1, init_iter=1,
@@ -44,7 +32,7 @@ def main():
         out["u%d" % gi] = G.unew[0].to_numpy(li)[3:-3, 3:-3, 3:-3]
         out["s%d" % gi] = G.snew[0].to_numpy(li)[3:-3, 3:-3, 3:-3]
         out["p%d" % gi] = G.p[0].to_numpy(li)[1:-1, 1:-1, 1:-1]
-    np.savez(outprefix + ".%d.npz" % rank, **out)
+    save_rank(outprefix, rank, out)
     G.close()
 
 

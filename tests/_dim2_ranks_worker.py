@@ -3,11 +3,11 @@ the transport is the RCCL test double tests/fake_rccl (VDN_RCCL_LIB), the rendez
 argv: rank nranks idfile outprefix bx by n nsteps bcname"""
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests.children import rendezvous, save_rank  # noqa: E402
 
 BCS = {"walls": [[15, 15], [15, 15]], "periodic": [[-1, -1], [15, 15]]}
 
@@ -19,19 +19,7 @@ def main():
     from varden_amd import boxlib as bl, driver
     from varden_amd.capi import default_params
     prm = default_params(dm=2, cflfac=0.9, visc_coef=0.001)
-    comm_id = None
-    if nranks > 1:
-        bl.initialize(prm, rank, nranks, 0)
-        if rank == 0:
-            cid = bl.comm_get_unique_id()
-            with open(idfile + ".tmp", "wb") as f:
-                f.write(cid)
-            os.rename(idfile + ".tmp", idfile)
-        t0 = time.time()
-        while not os.path.exists(idfile):
-            time.sleep(0.01)
-            assert time.time() - t0 < 120, "rendezvous timed out"
-        comm_id = open(idfile, "rb").read()
+    comm_id = rendezvous(bl, prm, rank, nranks, idfile)
     G = driver.Varden(n, [bc[0], bc[1], [0, 0]], prm, prob_type=1, init_shrink=0.1, init_iter=1, decomp=decomp, rank=rank, nranks=nranks, comm_id=comm_id)
     dts = []
     for _ in range(nsteps):
@@ -43,7 +31,7 @@ def main():
         out["s%d" % gi] = G.sold[0].to_numpy(li)[3:-3, 3:-3]
         out["gp%d" % gi] = G.gp[0].to_numpy(li)[1:-1, 1:-1]
         out["p%d" % gi] = G.p[0].to_numpy(li)[1:-1, 1:-1]
-    np.savez(outprefix + ".%d.npz" % rank, **out)
+    save_rank(outprefix, rank, out)
     G.close()
 
 

@@ -2,11 +2,11 @@
 three-level fixed hierarchy whose boxes are dealt to the ranks by cell count.  argv: rank[,rank...] nranks idfile outprefix nlev visc [tagged | restart <checkpoint>]"""
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests.children import rendezvous, save_rank  # noqa: E402
 
 
 def main():
@@ -22,18 +22,7 @@ def one_rank(rank, nranks, pkg):
     restart = len(sys.argv) > 7 and sys.argv[7] == "restart"          # continue from the checkpoint <argv[8]> written by a "tagged" run
     bl, driver, plotfile = pkg.boxlib, pkg.driver, pkg.plotfile
     prm = pkg.capi.default_params(cflfac=0.9, visc_coef=visc)
-    comm_id = None
-    if nranks > 1:
-        bl.initialize(prm, rank, nranks, 0)
-        if rank == 0:
-            with open(idfile + ".tmp", "wb") as f:
-                f.write(bl.comm_get_unique_id())
-            os.rename(idfile + ".tmp", idfile)
-        t0 = time.time()
-        while not os.path.exists(idfile):
-            time.sleep(0.01)
-            assert time.time() - t0 < 120, "rendezvous timed out"
-        comm_id = open(idfile, "rb").read()
+    comm_id = rendezvous(bl, prm, rank, nranks, idfile)
     walls = [[bl.NO_SLIP_WALL] * 2] * 3
     base = [((0, 0, 0), (7, 7, 15)), ((8, 0, 0), (15, 7, 15)), ((0, 8, 0), (7, 15, 15)), ((8, 8, 0), (15, 15, 15))]    # level 0 in four equal boxes (the single-level multigrid wants equal boxes)
     fine = [((8, 8, 8), (15, 23, 23)), ((16, 8, 8), (23, 15, 23)), ((16, 16, 8), (23, 23, 23))]          # partial shared faces
@@ -63,7 +52,7 @@ def one_rank(rank, nranks, pkg):
     if tagged and not restart:                             # plot and checkpoint files, every rank its own Cell_D file
         plotfile.write_plotfile(G, base=outprefix + "_plt")
         plotfile.write_checkfile(G, base=outprefix + "_chk")
-    np.savez(outprefix + ".%d.npz" % rank, **out)
+    save_rank(outprefix, rank, out)
     G.close()
 
 

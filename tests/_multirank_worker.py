@@ -4,11 +4,11 @@ transport is the RCCL test double tests/fake_rccl (VDN_RCCL_LIB), the rendezvous
 argv: rank[,rank...] nranks idfile outprefix bx by bz nx ny nz nsteps periodic"""
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests.children import rendezvous, save_rank  # noqa: E402
 
 
 def main():
@@ -25,19 +25,7 @@ def one_rank(rank, nranks, pkg):
     bl, driver = pkg.boxlib, pkg.driver
     prm = pkg.capi.default_params(cflfac=0.9)
     dev = rank if os.environ.get("VDN_WORKER_DEVICE_PER_RANK") == "1" else 0     # real RCCL: one GPU per rank
-    comm_id = None
-    if nranks > 1:
-        bl.initialize(prm, rank, nranks, dev)
-        if rank == 0:
-            cid = bl.comm_get_unique_id()
-            with open(idfile + ".tmp", "wb") as f:
-                f.write(cid)
-            os.rename(idfile + ".tmp", idfile)
-        t0 = time.time()
-        while not os.path.exists(idfile):
-            time.sleep(0.01)
-            assert time.time() - t0 < 120, "rendezvous timed out"
-        comm_id = open(idfile, "rb").read()
+    comm_id = rendezvous(bl, prm, rank, nranks, idfile, dev)
     walls = [[bl.NO_SLIP_WALL] * 2] * 3
     if periodic:
         walls = [[bl.PERIODIC] * 2] + [[bl.NO_SLIP_WALL] * 2] * 2
@@ -53,7 +41,7 @@ def one_rank(rank, nranks, pkg):
         out["u%d" % gi] = G.unew[0].to_numpy(li)[3:-3, 3:-3, 3:-3]
         out["s%d" % gi] = G.snew[0].to_numpy(li)[3:-3, 3:-3, 3:-3]
         out["p%d" % gi] = G.p[0].to_numpy(li)[1:-1, 1:-1, 1:-1]
-    np.savez(outprefix + ".%d.npz" % rank, **out)
+    save_rank(outprefix, rank, out)
     with open(outprefix + ".%d.form" % rank, "w") as f:        # how the last MAC solve kept its finest level (vdn_last_mac_level_form)
         f.write("%d\n" % pkg.capi.load().vdn_last_mac_level_form())
     G.close()

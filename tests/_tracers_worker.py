@@ -3,11 +3,11 @@ multi-rank hierarchy run with nscal = 5 on ONE GPU (tests/test_tracers_gpu.py::t
 argv: rank[,rank...] nranks idfile outprefix fixed|tagged"""
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests.children import rendezvous, save_rank  # noqa: E402
 
 
 def tracer_value(m, X, Y, Z):
@@ -69,18 +69,7 @@ def one_rank(rank, nranks, pkg):
     idfile, outprefix, mode = sys.argv[3], sys.argv[4], sys.argv[5]
     bl, driver = pkg.boxlib, pkg.driver
     prm = pkg.capi.default_params(cflfac=0.9, visc_coef=0.001, diff_coef=0.001, nscal=5)
-    comm_id = None
-    if nranks > 1:
-        bl.initialize(prm, rank, nranks, 0)
-        if rank == 0:
-            with open(idfile + ".tmp", "wb") as f:
-                f.write(bl.comm_get_unique_id())
-            os.rename(idfile + ".tmp", idfile)
-        t0 = time.time()
-        while not os.path.exists(idfile):
-            time.sleep(0.01)
-            assert time.time() - t0 < 120, "rendezvous timed out"
-        comm_id = open(idfile, "rb").read()
+    comm_id = rendezvous(bl, prm, rank, nranks, idfile)
     walls = [[bl.NO_SLIP_WALL] * 2] * 3
     init = init_with_tracers(FIVE[:4], initdata=driver.initdata_numpy)
     if mode == "tagged":     # grids from the tagged bubble on a 32^3 base in four boxes, regridding every second step
@@ -105,7 +94,7 @@ def one_rank(rank, nranks, pkg):
             out["u%d_%d" % (n, gi)] = G.unew[n].to_numpy(li)[3:-3, 3:-3, 3:-3]
             out["s%d_%d" % (n, gi)] = G.snew[n].to_numpy(li)[3:-3, 3:-3, 3:-3]
             out["p%d_%d" % (n, gi)] = G.p[n].to_numpy(li)[1:-1, 1:-1, 1:-1]
-    np.savez(outprefix + ".%d.npz" % rank, **out)
+    save_rank(outprefix, rank, out)
     G.close()
 
 

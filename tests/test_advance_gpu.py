@@ -3,9 +3,12 @@ src/varden.f90 drives it) against the CPU oracle on the bubble problem of exec/t
 (inviscid), plus size-independent properties at a larger size.
 Tolerance: rel L-inf 1e-9 on u and rho after several steps; in practice the two paths
 agree to ~1e-13 because they run the same algorithm in the same expression order."""
+import os
+
 import numpy as np
 import pytest
 
+from tests.children import ROOT, line, run_variants
 from tests.util import WALLS, PER, INOUT, params_for
 
 pytestmark = pytest.mark.gpu
@@ -216,17 +219,8 @@ def test_viscous_solves_by_colour(gpu, oracle, bcname, n, diff):
     projections, dt bit for bit) and the same state hash (a) by colour with slabs of 7 planes, (b) by colour, whole-level launches, (c) interleaved.  Dirichlet walls (no-slip: every
     component), mixed (slip walls: the normal component Dirichlet, the tangential ones Neumann -- the folding differs per component), periodic x (ghost entries exchanged), inflow /
     outflow (inhomogeneous Dirichlet data in the right-hand side), 260 cells (two waves per row)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out, form = [], []
-    for extra in ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "7"}, {"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "0", "VDN_WORKER_ORACLE": "0"}, {"VDN_MAC_SPLIT": "0", "VDN_WORKER_ORACLE": "0"}):
-        env = dict(os.environ)
-        for k in ("VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_KFLIP", "VDN_MAC_SLAB"):
-            env.pop(k, None)
-        env.update(extra)
-        r = subprocess.run([sys.executable, os.path.join(root, "tests", "_visc_split_worker.py"), bcname] + [str(v) for v in n] + [str(diff)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0])
-        form.append([ln for ln in r.stdout.splitlines() if ln.startswith("FORM")][0])
+    variants = ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "7"}, {"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "0", "VDN_WORKER_ORACLE": "0"}, {"VDN_MAC_SPLIT": "0", "VDN_WORKER_ORACLE": "0"})
+    runs = run_variants((os.path.join(ROOT, "tests", "_visc_split_worker.py"), bcname) + n + (diff,), variants, 600)
+    out, form = [line(r, "HASH") for r in runs], [line(r, "FORM") for r in runs]
     assert form[0].split()[1] == "1" and form[1].split()[1] == "1" and form[2].split()[1] == "0", form       # (the start-up's last cell-centred solve: a viscous one)
     assert out[0] == out[1] == out[2], (bcname, out)

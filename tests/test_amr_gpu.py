@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.children import ROOT, line, run_variants
 from tests.util import assert_bits
 
 pytestmark = pytest.mark.gpu
@@ -923,39 +924,25 @@ def test_composite_launch_variants_agree_bit_for_bit(gpu):
     plane per workgroup (VDN_BATCH_PPW=1), the interpolation over whole boxes (VDN_NDM_IFACE_FACES=0) and the negated copy + zero-filled
     correction of round 2 (VDN_NDM_NEG=1), and (c) with the defaults and the kept descriptor tables bounded to two entries (VDN_KEPT_BOUND=2).  The switches are
     read once per process, hence the child processes."""
-    import os, subprocess, sys, textwrap
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import textwrap
     code = textwrap.dedent("""
-        import sys, hashlib
+        import sys
         sys.path.insert(0, %r)
-        import numpy as np
         from varden_amd import driver
         from varden_amd.capi import default_params
+        from tests.util import state_hash
         walls = [[15, 15]] * 3
         prm = default_params(cflfac=0.9)
         levels = driver.VardenAMR.tagged_grids(32, walls, prm, max_levs=3, max_grid_size=32)
         G = driver.VardenAMR(32, levels[0], walls, params=prm, finer_levels=levels[1:], init_iter=1, do_initial_projection=1)
         for _ in range(2):
             G.step()
-        h = hashlib.sha256()
-        for n in range(3):
-            for m in (G.uold[n], G.sold[n], G.p[n], G.gp[n]):
-                for f in range(m.nfabs()):
-                    h.update(np.ascontiguousarray(m.to_numpy(f)).tobytes())
-        print("HASH", h.hexdigest(), G.dt)
-    """ % root)
-    switches = ("VDN_BATCH_PPW", "VDN_NDM_IFACE_FACES", "VDN_NDM_NEG", "VDN_BATCH_YZ", "VDN_NDF_PAIR", "VDN_BATCH_CHUNK", "VDN_MLCC_FUSE1", "VDN_MLCC_GLUE", "VDN_MLCC_RHO", "VDN_FB_FACES", "VDN_GOD_SEGW", "VDN_KEEP_SETS", "VDN_BATCH_FLAT", "VDN_NDM_PROLONG8", "VDN_KEPT_BOUND")
-    out = []
+        print("HASH", state_hash(G, 3), G.dt)
+    """ % ROOT)
     # third run: the kept descriptor tables bounded to two entries each, so that every bound is hit in the MIDDLE of the composite solves of a three-level
     # step (ADVICE r4: an eviction there must not free the sets the running solve is bound to)
-    for extra in ({}, {"VDN_KEPT_BOUND": "2"}, {"VDN_BATCH_PPW": "1", "VDN_NDM_IFACE_FACES": "0", "VDN_NDM_NEG": "1", "VDN_BATCH_YZ": "0", "VDN_NDF_PAIR": "0", "VDN_BATCH_CHUNK": "0", "VDN_MLCC_FUSE1": "0", "VDN_MLCC_GLUE": "0", "VDN_MLCC_RHO": "0", "VDN_FB_FACES": "0", "VDN_GOD_SEGW": "0", "VDN_KEEP_SETS": "0", "VDN_BATCH_FLAT": "0", "VDN_NDM_PROLONG8": "0"}):
-        env = dict(os.environ)
-        for k in switches:
-            env.pop(k, None)
-        env.update(extra)
-        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0])
+    variants = ({}, {"VDN_KEPT_BOUND": "2"}, {"VDN_BATCH_PPW": "1", "VDN_NDM_IFACE_FACES": "0", "VDN_NDM_NEG": "1", "VDN_BATCH_YZ": "0", "VDN_NDF_PAIR": "0", "VDN_BATCH_CHUNK": "0", "VDN_MLCC_FUSE1": "0", "VDN_MLCC_GLUE": "0", "VDN_MLCC_RHO": "0", "VDN_FB_FACES": "0", "VDN_GOD_SEGW": "0", "VDN_KEEP_SETS": "0", "VDN_BATCH_FLAT": "0", "VDN_NDM_PROLONG8": "0"})
+    out = [line(r, "HASH") for r in run_variants(("-c", code), variants, 600)]
     assert out[0] == out[1] == out[2], out
 
 
@@ -1011,34 +998,21 @@ def test_level0_cycles_of_composite_solves_by_colour_agree_bit_for_bit(gpu):
     """round 6: the V-cycle a composite solve runs on level 0 in every FAC iteration takes the level by colour -- the MAC projection's (the density form) and, with viscosity, the three
     velocity solves' (constant face coefficients) -- from 2^23 cells (the 256^3 base of configs[3] / [4]).  Here a 128^3 base with one refined box, visc_coef = 0.001, start-up + one
     step, VDN_MAC_SPLIT_MIN=0 (slabs of 16 planes) against VDN_MAC_SPLIT=0: the same state, bit for bit, and the by-colour form did run."""
-    import os, subprocess, sys, textwrap
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import textwrap
     code = textwrap.dedent("""
-        import sys, hashlib
+        import sys
         sys.path.insert(0, %r)
-        import numpy as np
         from varden_amd import driver, capi
         from varden_amd.capi import default_params
+        from tests.util import state_hash
         G = driver.VardenAMR(128, [((48, 48, 40), (111, 111, 103))], [[15, 15]] * 3, params=default_params(cflfac=0.9, visc_coef=0.001), init_shrink=0.1, init_iter=1, do_initial_projection=1)
         G.step()
-        h = hashlib.sha256()
-        for n in range(2):
-            for m in (G.uold[n], G.sold[n], G.p[n], G.gp[n]):
-                for f in range(m.nfabs()):
-                    h.update(np.ascontiguousarray(m.to_numpy(f)).tobytes())
-        print("HASH", h.hexdigest(), G.dt, "FORM", capi.load().vdn_last_mac_level_form())
+        print("HASH", state_hash(G, 2), G.dt, "FORM", capi.load().vdn_last_mac_level_form())
         G.close()
-    """ % root)
-    out = []
+    """ % ROOT)
     # third run: the refined levels' sweeps and residuals READ the face coefficients (VDN_MLCC_RHO=0) instead of forming them from the density (MAC) or taking
     # the constant mu (viscous solves: use_rho == 2 of amr.hip) -- the same bits again
-    for extra in ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "16"}, {"VDN_MAC_SPLIT": "0"}, {"VDN_MAC_SPLIT": "0", "VDN_MLCC_RHO": "0"}):
-        env = dict(os.environ)
-        for k in ("VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_SLAB", "VDN_MLCC_RHO"):
-            env.pop(k, None)
-        env.update(extra)
-        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0].split())
+    variants = ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "16"}, {"VDN_MAC_SPLIT": "0"}, {"VDN_MAC_SPLIT": "0", "VDN_MLCC_RHO": "0"})
+    out = [r["HASH"][0] for r in run_variants(("-c", code), variants, 600)]
     assert out[0][1] == out[1][1] == out[2][1] and out[0][2] == out[1][2] == out[2][2], out
     assert out[0][4] == "1" and out[1][4] == "0", out          # (the last cell-centred solve of the step: a viscous composite one; its level-0 cycles by colour / interleaved)

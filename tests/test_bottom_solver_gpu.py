@@ -9,13 +9,12 @@ tests/test_operators_assembled_gpu.py holds the default bottom sweeps: the same 
 """
 import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import assembled as asm
+from tests.children import launch_ranks
 from tests.test_operators_assembled_cpu import smooth
 from tests.test_operators_assembled_gpu import ELL_OF
 from tests.util import BC_SETS, WALLS, Case, assert_bits
@@ -252,33 +251,8 @@ def test_a_two_level_hierarchy_with_cg_bottoms_matches_the_default(gpu):
         assert scale > 0 and err <= 1e-9 * scale, "%s differs by %.3e (scale %.3e)" % (nm, err, scale)
 
 
-FAKE = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
-
-
 def run_ranks(tmp_path, tag, nranks):
-    if nranks > 1 and not os.path.exists(FAKE):
-        subprocess.check_call(["make", "-s", "-C", os.path.dirname(FAKE)])
-    idfile, prefix = str(tmp_path / (tag + ".id")), str(tmp_path / tag)
-    env = dict(os.environ, VDN_RCCL_LIB=FAKE, VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path), VDN_OVERLAP=os.environ.get("VDN_OVERLAP", "1"))
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_bottom_solver_worker.py"), str(r), str(nranks), idfile, prefix], env=env, cwd=ROOT)
-             for r in range(nranks)]
-    try:
-        rcs = [p.wait(timeout=300) for p in procs]
-    finally:
-        for p in procs:                      # exact PIDs of the children this test started
-            if p.poll() is None:
-                p.kill()
-    assert rcs == [0] * len(procs), rcs
-    out = {}
-    for r in range(nranks):
-        with np.load(prefix + ".%d.npz" % r) as z:
-            for k in z.files:
-                if k in ("dt", "mac_iters", "hg_iters"):
-                    out.setdefault(k, z[k])
-                    assert np.array_equal(out[k], z[k]), "ranks disagree on %s" % k
-                else:
-                    out[k] = z[k]
-    return out
+    return launch_ranks("_bottom_solver_worker.py", nranks, tmp_path, tag, (), agree=("dt", "mac_iters", "hg_iters"), timeout=300)
 
 
 def test_two_ranks_reproduce_one_rank_bits_with_cg_bottoms(gpu, tmp_path):

@@ -2,15 +2,14 @@
 level, so their answer does not depend on the decomposition at all (bit for bit); whole steps differ from the one-box run only through the
 reference's per-box dead band of velpred_2d / mkflux_2d (velpred.f90:215-226); several ranks reproduce one rank on the same boxes bit for bit."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.children import launch_ranks
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
 INP = os.path.join(ROOT, "tests", "golden", "inputs")
 
 BC2 = {"walls": [[15, 15], [15, 15]], "periodic": [[-1, -1], [-1, -1]], "periodic-x": [[-1, -1], [15, 15]], "inout": [[11, 12], [14, 15]]}
@@ -289,29 +288,7 @@ def test_boxes_reproduce_the_extruded_copy_on_the_same_boxes(gpu, name, bc, prob
 
 # ---- several ranks -------------------------------------------------------------------------------------------------------------------------
 def run_ranks(tmp_path, tag, nranks, decomp, n, nsteps, bcname):
-    if nranks > 1 and not os.path.exists(FAKE):
-        subprocess.check_call(["make", "-s", "-C", os.path.dirname(FAKE)])
-    idfile, prefix = str(tmp_path / (tag + ".id")), str(tmp_path / tag)
-    env = dict(os.environ, VDN_RCCL_LIB=FAKE, VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path))
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_dim2_ranks_worker.py"), str(r), str(nranks), idfile, prefix,
-                               str(decomp[0]), str(decomp[1]), str(n), str(nsteps), bcname], env=env, cwd=ROOT) for r in range(nranks)]
-    try:
-        rcs = [p.wait(timeout=400) for p in procs]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    assert rcs == [0] * len(procs), rcs
-    out = {}
-    for r in range(nranks):
-        with np.load(prefix + ".%d.npz" % r) as z:
-            for k in z.files:
-                if k == "dt":
-                    out.setdefault("dt", z[k])
-                    assert np.array_equal(out["dt"], z[k]), "ranks disagree on dt"
-                else:
-                    out[k] = z[k]
-    return out
+    return launch_ranks("_dim2_ranks_worker.py", nranks, tmp_path, tag, (decomp[0], decomp[1], n, nsteps, bcname), overlap=None)
 
 
 @pytest.mark.parametrize("nranks,decomp,bcname", [(2, (2, 2), "walls"), (4, (2, 2), "periodic"), (2, (4, 1), "periodic"), (4, (4, 1), "walls")])

@@ -3,10 +3,12 @@ seeded inputs and for every boundary-condition family the reference handles.  Th
 Godunov / streaming kernels is BIT-EXACT: the HIP kernels keep the reference's expression order and are
 built with fp-contract off (tolerance 0 ulp)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
+from tests.children import ROOT, line, run_variant
 from tests.util import BC_SETS, Case, assert_bits
 
 pytestmark = pytest.mark.gpu
@@ -228,7 +230,7 @@ def test_godunov_marching_equals_face_centred(gpu, shape):
     and falls back to the face-centred kernels, box by box, also where the level would take the box-batched march (VDN_GODUNOV_BATCH=1).
     Only the valid faces are hashed.  The switches are read at the first launch of a process, hence the child processes.  The second shape spans
     two x-tiles, three y-tiles and several k-chunks of the fused march; the faces carry all four boundary rules."""
-    import os, subprocess, sys, textwrap
+    import textwrap
     code = textwrap.dedent("""
         import sys, hashlib
         sys.path.insert(0, %r)
@@ -264,27 +266,16 @@ def test_godunov_marching_equals_face_centred(gpu, shape):
         for m in umac + ue + se + [sf[d] for d in range(3)]:
             h.update(np.ascontiguousarray(valid(m)).tobytes())
         print("HASH", h.hexdigest())
-    """ % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), max(shape), shape[0], shape[1], shape[2]))
+    """ % (ROOT, max(shape), shape[0], shape[1], shape[2]))
     out = []
     for extra, fg in (({}, 0), ({"VDN_GODUNOV_PLAIN": "1", "VDN_SLOPES_MARCH": "0"}, 0), ({"VDN_FUSED_KCHUNKS": "5"}, 0), ({}, 1), ({"VDN_GODUNOV_BATCH": "1"}, 1)):
-        env = dict(os.environ)
-        for k in ("VDN_GODUNOV_PLAIN", "VDN_FUSED_KCHUNKS", "VDN_SLOPES_MARCH", "VDN_GODUNOV_BATCH"):
-            env.pop(k, None)
-        env.update(extra)
-        r = subprocess.run([sys.executable, "-c", code, str(fg)], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out.append([l for l in r.stdout.splitlines() if l.startswith("HASH")][0])
+        out.append(line(run_variant(("-c", code, fg), extra, 300), "HASH"))
     assert all(o == out[0] for o in out), out
 
 
 def _pair_run(tmp_path, tag, decomp, pair):
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = str(tmp_path / (tag + ".npz"))
-    env = dict(os.environ, VDN_GSRB_PAIR=str(pair))
-    subprocess.check_call([sys.executable, os.path.join(root, "tests", "_pair_worker.py")] + [str(d) for d in decomp] + [out], env=env, cwd=root, timeout=300)
+    run_variant((os.path.join(ROOT, "tests", "_pair_worker.py"),) + tuple(decomp) + (out,), {"VDN_GSRB_PAIR": str(pair)}, 300)
     return np.load(out)
 
 

@@ -10,49 +10,13 @@ import sys
 import numpy as np
 import pytest
 
+from tests.children import ROOT, fake_rccl, launch_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
 
 
-def rank_groups(nranks, per_proc):
-    """the ranks each worker process hosts: a GPU box admits six processes on its card, so eight ranks run as four processes of two rank
-    threads (tests/_rank_threads.py: one private copy of the library per rank)"""
-    return [",".join(str(r) for r in range(a, min(a + per_proc, nranks))) for a in range(0, nranks, per_proc)]
-
-
-def run_ranks(tmp_path, tag, nranks, decomp, n, nsteps, periodic, real_rccl=False, per_proc=1):
-    if nranks > 1 and not os.path.exists(FAKE):
-        subprocess.check_call(["make", "-s", "-C", os.path.dirname(FAKE)])
-    idfile, prefix = str(tmp_path / (tag + ".id")), str(tmp_path / tag)
-    if real_rccl:                                # one GPU per rank, the RCCL torch ships (dlopen of librccl.so.1)
-        env = dict(os.environ, VDN_WORKER_DEVICE_PER_RANK="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        env.pop("VDN_RCCL_LIB", None)
-    else:
-        # VDN_OVERLAP=1: halo exchange on the second stream + shell kernels on every level (by default only boxes of >= 2^20 cells do)
-        env = dict(os.environ, VDN_RCCL_LIB=FAKE, VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path), VDN_OVERLAP=os.environ.get("VDN_OVERLAP", "1"))
-        if nranks >= 8:
-            env["FAKE_RCCL_MAXMSG_MB"] = "8"     # 64 mailboxes: keep the memory-mapped file small (the messages of 32^3 boxes are a few hundred KB)
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_multirank_worker.py"), g, str(nranks), idfile, prefix]
-                              + [str(x) for x in decomp] + [str(x) for x in n] + [str(nsteps), str(int(periodic))], env=env, cwd=ROOT)
-             for g in rank_groups(nranks, per_proc)]
-    try:
-        rcs = [p.wait(timeout=400) for p in procs]
-    finally:
-        for p in procs:                      # exact PIDs of the children this test started
-            if p.poll() is None:
-                p.kill()
-    assert rcs == [0] * len(procs), rcs
-    out = {}
-    for r in range(nranks):
-        with np.load(prefix + ".%d.npz" % r) as z:
-            for k in z.files:
-                if k == "dt":
-                    out.setdefault("dt", z[k])
-                    assert np.array_equal(out["dt"], z[k]), "ranks disagree on dt"
-                else:
-                    out[k] = z[k]
-    return out
+def run_ranks(tmp_path, tag, nranks, decomp, n, nsteps, periodic, real_rccl=False, per_proc=1, switches=None):
+    return launch_ranks("_multirank_worker.py", nranks, tmp_path, tag, tuple(decomp) + tuple(n) + (nsteps, int(periodic)), per_proc=per_proc, real_rccl=real_rccl, switches=switches)
 
 
 @pytest.mark.parametrize("nranks,decomp,n,periodic", [(2, (2, 1, 1), (64, 32, 32), False), (2, (2, 1, 1), (64, 32, 32), True),
@@ -92,29 +56,25 @@ def test_two_rank_threads_in_one_process_equal_two_processes(gpu, tmp_path):
         assert np.array_equal(a[k], b[k]), k
 
 
-def test_two_ranks_of_128_cubed_with_the_default_overlap_rule(gpu, tmp_path, monkeypatch):
+def test_two_ranks_of_128_cubed_with_the_default_overlap_rule(gpu, tmp_path):
     """boxes of 2^21 cells: large enough for the default rule (VDN_OVERLAP unset) to put the halo traffic of the finest multigrid level on the
     second stream and finish its face cells in the shell kernels, for the paired density pass of the MAC solve (n >= 128) and for the fused
     Godunov marches with interior box faces; the coarser levels take the serial path.  One step, against the single-rank bits."""
-    monkeypatch.setenv("VDN_OVERLAP", "-1")                 # run_ranks passes it on: -1 = the library's own rule
-    ref = run_ranks(tmp_path, "ref", 1, (2, 1, 1), (256, 128, 128), 1, False)
-    got = run_ranks(tmp_path, "mr", 2, (2, 1, 1), (256, 128, 128), 1, False)
+    own_rule = {"VDN_OVERLAP": "-1"}                        # -1 = the library's own rule
+    ref = run_ranks(tmp_path, "ref", 1, (2, 1, 1), (256, 128, 128), 1, False, switches=own_rule)
+    got = run_ranks(tmp_path, "mr", 2, (2, 1, 1), (256, 128, 128), 1, False, switches=own_rule)
     assert np.array_equal(ref["dt"], got["dt"]), (ref["dt"], got["dt"])
     for k in sorted(ref):
         assert np.array_equal(ref[k], got[k]), "%s differs: max %.3e" % (k, np.abs(ref[k] - got[k]).max())
 
 
-def test_two_ranks_with_the_finest_mac_level_by_colour(gpu, tmp_path, monkeypatch):
+def test_two_ranks_with_the_finest_mac_level_by_colour(gpu, tmp_path):
     """round 6: macproject's finest level stored by colour on two ranks (VDN_MAC_SPLIT_MIN=0: from any size; by default from 2^23 cells per rank, i.e. configs[2]'s
     256^3 box per GPU): the ghost entries of one colour travel through the packed buffers of the split arrays' own plan, on the halo stream next to the interior
     cells, the shell kernel behind them (the library's own overlap rule), the coarse correction inside the first sweep, residual + restriction per box.
     One step of two 128^3 boxes against ONE rank with the level interleaved (round 5's form): the same bits."""
-    monkeypatch.setenv("VDN_OVERLAP", "-1")
-    monkeypatch.setenv("VDN_MAC_SPLIT", "0")
-    ref = run_ranks(tmp_path, "ref", 1, (2, 1, 1), (256, 128, 128), 1, False)
-    monkeypatch.delenv("VDN_MAC_SPLIT")
-    monkeypatch.setenv("VDN_MAC_SPLIT_MIN", "0")
-    got = run_ranks(tmp_path, "mr", 2, (2, 1, 1), (256, 128, 128), 1, False)
+    ref = run_ranks(tmp_path, "ref", 1, (2, 1, 1), (256, 128, 128), 1, False, switches={"VDN_OVERLAP": "-1", "VDN_MAC_SPLIT": "0"})
+    got = run_ranks(tmp_path, "mr", 2, (2, 1, 1), (256, 128, 128), 1, False, switches={"VDN_OVERLAP": "-1", "VDN_MAC_SPLIT_MIN": "0"})
     assert np.array_equal(ref["dt"], got["dt"]), (ref["dt"], got["dt"])
     for k in sorted(ref):
         assert np.array_equal(ref[k], got[k]), "%s differs: max %.3e" % (k, np.abs(ref[k] - got[k]).max())
@@ -157,9 +117,7 @@ def test_bench_spawns_its_own_ranks(gpu, tmp_path, extra):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     if _ngpus() < 2:
-        if not os.path.exists(FAKE):
-            subprocess.check_call(["make", "-s", "-C", os.path.dirname(FAKE)])
-        env.update(VDN_BENCH_ONE_DEVICE="1", VDN_RCCL_LIB=FAKE, VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path))
+        env.update(VDN_BENCH_ONE_DEVICE="1", VDN_RCCL_LIB=fake_rccl(), VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path))
     line = _bench_line(["--gpus", "2", "--steps", "2", "--warmup", "1", "--box", "32", "--skip-cpu"] + extra, env)
     assert line["n_gpus"] == 2 and line["rccl_nranks"] == 2 and line["value"] > 0
     assert line["scaling"] == ("weak" if not extra else "strong")
@@ -174,31 +132,7 @@ def test_bench_spawns_its_own_ranks(gpu, tmp_path, extra):
 
 
 def run_amr_ranks(tmp_path, tag, nranks, nlev, visc, mode="fixed", extra=(), per_proc=1):
-    if nranks > 1 and not os.path.exists(FAKE):
-        subprocess.check_call(["make", "-s", "-C", os.path.dirname(FAKE)])
-    idfile, prefix = str(tmp_path / (tag + ".id")), str(tmp_path / tag)
-    env = dict(os.environ, VDN_RCCL_LIB=FAKE, VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path), VDN_OVERLAP=os.environ.get("VDN_OVERLAP", "1"))
-    if nranks >= 8:
-        env["FAKE_RCCL_MAXMSG_MB"] = "8"
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_multirank_amr_worker.py"), g, str(nranks), idfile, prefix, str(nlev), str(visc), mode] + list(extra),
-                              env=env, cwd=ROOT) for g in rank_groups(nranks, per_proc)]
-    try:
-        rcs = [p.wait(timeout=400) for p in procs]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    assert rcs == [0] * len(procs), rcs
-    out = {}
-    for r in range(nranks):
-        with np.load(prefix + ".%d.npz" % r) as z:
-            for k in z.files:
-                if k in ("dt", "nboxes", "nregrids"):
-                    out.setdefault(k, z[k])
-                    assert np.array_equal(out[k], z[k]), "ranks disagree on " + k
-                else:
-                    out[k] = z[k]
-    return out
+    return launch_ranks("_multirank_amr_worker.py", nranks, tmp_path, tag, (nlev, visc, mode) + tuple(extra), per_proc=per_proc, agree=("dt", "nboxes", "nregrids"))
 
 
 def test_tagged_grids_and_regrid_on_two_ranks(gpu, tmp_path):
@@ -251,7 +185,7 @@ def test_amr_ranks_reproduce_single_rank(gpu, tmp_path, nranks, nlev, visc):
     reproduce the single-rank run on the same boxes bit for bit.  Five ranks: more ranks than boxes on every level (4, 3, 2 boxes), so
     some ranks own nothing on a level and still take part in every collective.  Transport: the RCCL test double (see the module docstring)."""
     ref = run_amr_ranks(tmp_path, "aref", 1, nlev, visc)
-    got = run_amr_ranks(tmp_path, "amr", nranks, nlev, visc)
+    got = run_amr_ranks(tmp_path, "amr", nranks, nlev, visc, per_proc=2 if nranks > 4 else 1)      # (five ranks: 2 + 2 + 1 rank threads, launch_ranks starts at most four processes)
     assert sorted(ref) == sorted(got)
     assert np.array_equal(ref["dt"], got["dt"]), (ref["dt"], got["dt"])
     for k in sorted(ref):

@@ -10,10 +10,10 @@ Shapes that are paired on the finest level and thin elsewhere:
 Each with walls on all faces and with an outlet on one x, one y and one z face in turn (the Dirichlet skip on each axis); sigma is the bubble's 1 / rho.
 The switches are read once per process: one child process per launch form runs every case (tests/_nd_prolong_worker.py), once for the module."""
 import os
-import subprocess
-import sys
 
 import pytest
+
+from tests.children import ROOT, run_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -25,17 +25,10 @@ FORMS = {"fused": {}, "fused-nographs": {"VDN_NO_GRAPHS": "1"}, "two-launch": {"
 
 @pytest.fixture(scope="module")
 def runs(gpu):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = {}
-    for form, extra in FORMS.items():
-        env = dict(os.environ)
-        for k in ("VDN_ND_PROLONG_FUSED", "VDN_NO_GRAPHS", "VDN_ND_PAIR", "VDN_ND_REV", "VDN_ND_RESTRICT_FUSED"):
-            env.pop(k, None)
-        env.update(extra)
-        cmd = [sys.executable, os.path.join(root, "tests", "_nd_prolong_worker.py")] + (["oracle"] if form == "fused" else [])
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
-        assert r.returncode == 0, (form, r.stderr[-2000:])
-        out[form] = {ln.split()[1]: ln.split()[2:] for ln in r.stdout.splitlines() if ln.startswith("CASE ")}
+    for form, extra in FORMS.items():      # (in this order: a form that fails ends the fixture, none is started after it)
+        r = run_variant([os.path.join(ROOT, "tests", "_nd_prolong_worker.py")] + (["oracle"] if form == "fused" else []), extra, 300)
+        out[form] = {tok[1]: tok[2:] for tok in r["CASE"]}
     return out
 
 

@@ -4,13 +4,16 @@ order; the only order-dependent reduction is a max-norm, so the results are expe
 Tolerance written here: bit-exact for the smoother; 1e-11 relative (L-inf) for the converged solves
 (tolerance-limited quantities: the reference itself stops at 1e-10 / 1e-12 relative residual)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
+from tests.children import ROOT, line, run_variant, run_variants
 from tests.util import BC_SETS, Case, assert_bits
 
 pytestmark = pytest.mark.gpu
+SPLIT_WORKER = os.path.join(ROOT, "tests", "_split_worker.py")
 
 
 def face_fabs(case, ng, nc, val=0.0):
@@ -117,20 +120,18 @@ def test_split_colour_level_matches_the_oracle_and_the_interleaved_level(gpu, or
     (cc_split_run; 40 planes: six slabs, the last a sliver), the second colour walking its planes downwards,
     (b) split in whole-level launches, both colours upwards (the form a multi-box level runs), (c) interleaved.  260 cells: two waves per row, the second with one active lane pair
     (the lane that ends a wave inside the row reads its neighbour from memory).  tests/_split_worker.py."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out, form = [], []
-    for extra in ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "7"}, {"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "0", "VDN_MAC_KFLIP": "0"}, {"VDN_MAC_SPLIT": "0"}):
-        env = dict(os.environ)
-        for k in ("VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_KFLIP", "VDN_MAC_SLAB"):
-            env.pop(k, None)
-        env.update(extra)
-        r = subprocess.run([sys.executable, os.path.join(root, "tests", "_split_worker.py"), bcname] + [str(v) for v in n], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0])
-        form.append([ln for ln in r.stdout.splitlines() if ln.startswith("FORM")][0])
+    runs = run_variants((SPLIT_WORKER, bcname) + n, ({"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "7"}, {"VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_SLAB": "0", "VDN_MAC_KFLIP": "0"}, {"VDN_MAC_SPLIT": "0"}), 600)
+    out, form = [line(r, "HASH") for r in runs], [line(r, "FORM") for r in runs]
     assert form == ["FORM 1", "FORM 1", "FORM 0"], form             # (vdn_last_mac_level_form: two runs by colour, one interleaved)
     assert out[0] == out[1] == out[2], (bcname, out)
+
+
+def test_a_variant_child_sees_no_switch_of_the_outer_environment(gpu, oracle, monkeypatch):
+    """tests/children.py: a launch-form switch that the shell which started pytest had set does not reach a variant's child.  VDN_MAC_SPLIT=0 outside, the
+    variant VDN_MAC_SPLIT_MIN=0 on the smallest split-colour shape above: the level by colour did run."""
+    monkeypatch.setenv("VDN_MAC_SPLIT", "0")
+    r = run_variant((SPLIT_WORKER, "walls", 132, 36, 40), {"VDN_MAC_SPLIT_MIN": "0"}, 600)
+    assert line(r, "FORM") == "FORM 1", r
 
 
 @pytest.mark.parametrize("bcname,n,nb", [("periodic", (132, 36, 40), (1, 1, 1)), ("periodicyz", (132, 36, 40), (1, 1, 1)), ("walls", (264, 128, 128), (2, 1, 1)),
@@ -142,23 +143,13 @@ def test_split_colour_level_with_a_halo(gpu, oracle, bcname, n, nb):
     coarse level's ghost cells exchanged, residual + restriction per box.  Against the oracle in the first run; the same bits (a) split, (b) split with the exchange on
     the halo stream next to the interior cells and the shell kernel behind it (VDN_OVERLAP=1), (c) split through the packed per-peer buffers (VDN_FORCE_PACKED=1: the
     path to another rank), (d) interleaved (round 5's form of these levels).  Boxes of 132 x 128 x 128 cells: the smallest that keep a second distributed level."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out, form = [], []
     variants = ({"VDN_MAC_SPLIT_MIN": "0"}, {"VDN_MAC_SPLIT_MIN": "0", "VDN_OVERLAP": "1", "VDN_WORKER_ORACLE": "0"},
                 {"VDN_MAC_SPLIT_MIN": "0", "VDN_FORCE_PACKED": "1", "VDN_WORKER_ORACLE": "0"}, {"VDN_MAC_SPLIT": "0", "VDN_WORKER_ORACLE": "0"})
     if nb[0] == 1 and nb != (1, 1, 1):          # (the y / z decompositions: split with the overlap path against interleaved -- the packed path's descriptors do not depend on the direction)
         variants = (variants[0], variants[1], variants[3])
-    for extra in variants:
-        env = dict(os.environ)
-        for k in ("VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_KFLIP", "VDN_MAC_SLAB", "VDN_OVERLAP", "VDN_FORCE_PACKED", "VDN_MG_AGGLOM"):
-            env.pop(k, None)
-        env.update(extra)
-        env["VDN_MG_AGGLOM"] = "64"          # (boxes of 128 cells on ONE rank are gathered right below the finest level by default, mg_agglom: keep the second distributed level the split form asks for)
-        r = subprocess.run([sys.executable, os.path.join(root, "tests", "_split_worker.py"), bcname] + [str(v) for v in n + nb], env=env, capture_output=True, text=True, timeout=900, cwd=root)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0])
-        form.append([ln for ln in r.stdout.splitlines() if ln.startswith("FORM")][0])
+    # VDN_MG_AGGLOM=64: boxes of 128 cells on ONE rank are gathered right below the finest level by default (mg_agglom); keep the second distributed level the split form asks for
+    runs = run_variants((SPLIT_WORKER, bcname) + n + nb, [dict(extra, VDN_MG_AGGLOM="64") for extra in variants], 900)
+    out, form = [line(r, "HASH") for r in runs], [line(r, "FORM") for r in runs]
     assert form == ["FORM 1"] * (len(variants) - 1) + ["FORM 0"], form
     assert len(set(out)) == 1, (bcname, out)
 
@@ -266,39 +257,26 @@ def test_multigrid_launch_variants_agree_bit_for_bit(gpu):
     (VDN_ND_LEAN=0), every forcing term computed where the reference computes it (VDN_NO_FORCE_REUSE=1) and the Godunov marches dividing by dx where the
     default scales by 1 / dx on these power-of-two grids (VDN_GOD_P2=0); and a viscous 64^3 run the same way (the alpha form of the cell-centred kernels: three visc_solves per step).
     The switches are read once per process, hence the child processes."""
-    import hashlib, os, subprocess, sys, textwrap
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import textwrap
     code = textwrap.dedent("""
-        import sys, hashlib
+        import sys
         sys.path.insert(0, %r)
-        import numpy as np
         from varden_amd import driver
+        from tests.util import state_hash
         from varden_amd.capi import default_params
         n, visc = int(sys.argv[1]), float(sys.argv[2])
         G = driver.VardenAMR(n, [], [[15, 15]] * 3, params=default_params(visc_coef=visc, diff_coef=visc), init_iter=1, do_initial_projection=1)
         for _ in range(2):
             G.step()
-        h = hashlib.sha256()
-        for m in (G.uold[0], G.sold[0], G.p[0], G.gp[0]):
-            h.update(np.ascontiguousarray(m.to_numpy()).tobytes())
-        print("HASH", h.hexdigest(), G.dt)
-    """ % root)
-    switches = ("VDN_MG_PROLONG_FUSED", "VDN_MG_RESTRICT_FUSED", "VDN_MG_TAILCYCLE", "VDN_MG_LDS", "VDN_NO_GRAPHS", "VDN_HG_FAST", "VDN_MAC_FAST", "VDN_ND_LEAN", "VDN_NO_FORCE_REUSE", "VDN_GOD_UPDATE", "VDN_GOD_P2", "VDN_ND_RESTRICT_FUSED", "VDN_GOD_NARROW", "VDN_MAC_SPLIT", "VDN_MAC_SPLIT_MIN", "VDN_MAC_KFLIP", "VDN_ND_REV", "VDN_MAC_SLAB",
-                "VDN_MAC_UMAX", "VDN_ND_PAIR", "VDN_MAC_STORED_BETA", "VDN_NO_SLOPE_CACHE", "VDN_CC_HALO_FACES", "VDN_GODUNOV_BATCH")
+        print("HASH", state_hash(G, 1), G.dt)
+    """ % ROOT)
     for n, visc in ((128, 0.0), (64, 0.01)):
-        out = []
         # second run (round 5): the remainder tile column of the fused mkflux + update march in full 64-lane tiles (VDN_GOD_NARROW=0) against narrow segments
         # round 5 also: the first two runs keep the finest MAC level by colour (VDN_MAC_SPLIT_MIN=0: from any size), the third interleaved; the second and third
         # walk every colour pass / nodal march in the same order (VDN_MAC_KFLIP=0, VDN_ND_REV=0); the first in two plane slabs (cc_split_run), the second in whole-level launches
-        for extra in ({"VDN_MAC_SPLIT_MIN": "0"}, {"VDN_GOD_NARROW": "0", "VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_KFLIP": "0", "VDN_ND_REV": "0", "VDN_MAC_SLAB": "0", "VDN_NO_GRAPHS": "1"},
+        variants = ({"VDN_MAC_SPLIT_MIN": "0"}, {"VDN_GOD_NARROW": "0", "VDN_MAC_SPLIT_MIN": "0", "VDN_MAC_KFLIP": "0", "VDN_ND_REV": "0", "VDN_MAC_SLAB": "0", "VDN_NO_GRAPHS": "1"},
                       {"VDN_MAC_KFLIP": "0", "VDN_ND_REV": "0", "VDN_MAC_SPLIT": "0", "VDN_MAC_UMAX": "0", "VDN_ND_PAIR": "0", "VDN_MAC_STORED_BETA": "1", "VDN_NO_SLOPE_CACHE": "1", "VDN_CC_HALO_FACES": "0",
                        "VDN_GODUNOV_BATCH": "1", "VDN_MG_PROLONG_FUSED": "0", "VDN_MG_RESTRICT_FUSED": "0", "VDN_MG_TAILCYCLE": "0", "VDN_MG_LDS": "0", "VDN_NO_GRAPHS": "1",
-                          "VDN_HG_FAST": "0", "VDN_MAC_FAST": "0", "VDN_ND_LEAN": "0", "VDN_NO_FORCE_REUSE": "1", "VDN_GOD_UPDATE": "0", "VDN_GOD_P2": "0", "VDN_ND_RESTRICT_FUSED": "0"}):
-            env = dict(os.environ)
-            for k in switches:
-                env.pop(k, None)
-            env.update(extra)
-            r = subprocess.run([sys.executable, "-c", code, str(n), str(visc)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-            assert r.returncode == 0, r.stderr[-2000:]
-            out.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0])
+                          "VDN_HG_FAST": "0", "VDN_MAC_FAST": "0", "VDN_ND_LEAN": "0", "VDN_NO_FORCE_REUSE": "1", "VDN_GOD_UPDATE": "0", "VDN_GOD_P2": "0", "VDN_ND_RESTRICT_FUSED": "0"})
+        out = [line(r, "HASH") for r in run_variants(("-c", code, n, visc), variants, 600)]
         assert out[0] == out[1] == out[2], (n, visc, out)

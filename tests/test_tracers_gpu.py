@@ -6,11 +6,11 @@ import os
 import re
 import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.children import launch_ranks
 from tests._tracers_worker import FIVE, init_with_tracers, set_tracers
 from tests.util import INOUT, PER, WALLS, assert_bits, params_for
 
@@ -228,34 +228,8 @@ def test_four_scalars_on_a_tagged_hierarchy_against_the_box_list_oracle(gpu, ora
 
 
 # ---- 4. several ranks ----------------------------------------------------------------------------------------------------------------------------------
-FAKE = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
-
-
 def _run_ranks(tmp_path, tag, nranks, mode):
-    if nranks > 1 and not os.path.exists(FAKE):
-        subprocess.check_call(["make", "-s", "-C", os.path.dirname(FAKE)])
-    idfile, prefix = str(tmp_path / (tag + ".id")), str(tmp_path / tag)
-    env = dict(os.environ, VDN_RCCL_LIB=FAKE, VDN_TESTING="1", FAKE_RCCL_DIR=str(tmp_path), VDN_OVERLAP=os.environ.get("VDN_OVERLAP", "1"))
-    groups = [",".join(str(r) for r in range(a, min(a + 2, nranks))) for a in range(0, nranks, 2)]      # two rank threads per process: at most two children
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_tracers_worker.py"), g, str(nranks), idfile, prefix, mode], env=env, cwd=ROOT)
-             for g in groups]
-    try:
-        rcs = [p.wait(timeout=400) for p in procs]
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    assert rcs == [0] * len(procs), rcs
-    out = {}
-    for r in range(nranks):
-        with np.load(prefix + ".%d.npz" % r) as z:
-            for k in z.files:
-                if k in ("dt", "nboxes", "nregrids"):
-                    out.setdefault(k, z[k])
-                    assert np.array_equal(out[k], z[k]), "ranks disagree on " + k
-                else:
-                    out[k] = z[k]
-    return out
+    return launch_ranks("_tracers_worker.py", nranks, tmp_path, tag, (mode,), per_proc=2, agree=("dt", "nboxes", "nregrids"))      # two rank threads per process: at most two children
 
 
 @pytest.mark.parametrize("mode", ["fixed", "tagged"])

@@ -1,5 +1,6 @@
 """shared helpers for the parity tests: seeded smooth fields on one box, oracle <-> HIP plumbing"""
 import ctypes as C
+import hashlib
 
 import numpy as np
 
@@ -110,3 +111,14 @@ def assert_bits(a, b, what, region=None):
         idx = np.unravel_index(np.nanargmax(d), d.shape)
         raise AssertionError("%s: not bit-identical; max |diff| = %.3e at %r (a=%r b=%r), %d mismatches"
                              % (what, np.nanmax(d), idx, a[idx], b[idx], int((a != b).sum())))
+
+
+def state_hash(G, nlev):
+    """sha256 over uold, sold, p and gp (ghost cells included) of every local box of the first `nlev` levels of a driver: what the variant tests'
+    child processes print, equal between two runs exactly when the states are the same bits"""
+    h = hashlib.sha256()
+    for n in range(nlev):
+        for m in (G.uold[n], G.sold[n], G.p[n], G.gp[n]):
+            for f in range(m.nfabs()):
+                h.update(np.ascontiguousarray(m.to_numpy(f)).tobytes())
+    return h.hexdigest()

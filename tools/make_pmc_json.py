@@ -1,4 +1,4 @@
-"""profiles/r05_smoother_split_pmc.json (or, with a third argument `pair`, r05_smoother_rho_pmc.json: VDN_MAC_SPLIT=0 runs) from the summary tools/pmc_summary.py wrote for `tools/smoother_probe.py 256 20` (tools/final_profiles_r05.sh):
+"""profiles/r05_smoother_split_pmc.json (or, with a third argument `pair`, r05_smoother_rho_pmc.json: VDN_MAC_SPLIT=0 runs) from the summary tools/pmc_summary.py wrote for `tools/smoother_probe.py 256 20` (the passes listed in profiles/r05_smoother_split_pmc.json's _comment):
 HBM bytes per launch of the roofline kernel = 2 x FETCH_SIZE (gfx950 reports half of a coalesced streaming read, MI355X_MICROARCH.md, checked on
 the k_copy line of the same run) + WRITE_SIZE.  usage: make_pmc_json.py <smoother_pmc_summary.txt> <out.json>"""
 import json, sys
@@ -17,7 +17,7 @@ k, c = row(kname), row("k_copy")
 n = 256
 out = {
     "_comment": "rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE / TA_BUSY_avr TA_BUSY_max / TCC_HIT_sum TCC_MISS_sum / VALUBusy MemUnitBusy, separate runs, "
-                "--kernel-trace, csv; tools/final_profiles_r05.sh) of `python3 tools/smoother_probe.py 256 20` on MI355X, round 5; per-launch means over %d dispatches of "
+                "--kernel-trace, csv) of `python3 tools/smoother_probe.py 256 20` on MI355X, round 5; per-launch means over %d dispatches of "
                 "the kernel at 256^3, the colour pass macproject runs on its finest level (kk_cc_gsrb_rho_split: the level stored by colour, round 5; "
                 "kk_cc_gsrb_rho_pair: the interleaved level, VDN_MAC_SPLIT=0 and every multi-box run).  Sizes in KB.  FETCH_SIZE is doubled per MI355X_MICROARCH.md; "
                 "the k_copy calibration of the same run (134217728 B read and written per launch) is alongside." % k["calls"],

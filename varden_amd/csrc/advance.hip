@@ -26,8 +26,7 @@ static void restrict_and_fill(int nlev, vdn_multifab **mf, int icomp, int bcomp,
 // VDN_PHASE_HASH=1 (testing build; the hunt for the run-to-run differences of profiles/r06_determinism.txt): a checksum of whole multifabs (ghost cells included) at the
 // phase boundaries of a step, on stderr
 static void dbg_phase_hash(const char *tag, int nlevs, vdn_multifab **mfs, int per_level = 1, bool whole = false) {
-  static const bool on = env_set("VDN_PHASE_HASH");
-  if (!on) return;
+  if (!sw().phase_hash) return;
   HIPCHK(hipStreamSynchronize(ctx().stream));
   unsigned long long h = 1469598103934665603ull;
   for (int n = 0; n < nlevs; n++) for (int q = 0; q < per_level; q++) {
@@ -113,7 +112,7 @@ extern "C" int vdn_advance_timestep(int istep, vdn_layout *mla, vdn_multifab **s
   // velpred (advance_premac) and the velocity mkflux (velocity_advance) both start from the limited slopes of the same uold: the
   // reference computes them twice (velpred.f90:1985-1990, mkflux.f90:1207-1212); one level of one box keeps velpred's for mkflux
   ctx().drop_step_caches();
-  if (nlevs == 1 && dm == 3 && god_per_box(uold[0]) && !vdn_env("VDN_NO_SLOPE_CACHE")) {
+  if (nlevs == 1 && dm == 3 && god_per_box(uold[0]) && !sw().no_slope_cache) {
     const int nb = uold[0]->nfabs();
     for (int d = 0; d < 3; d++) ctx().slope_cache[d].assign(nb, nullptr);
     ctx().slope_src.assign(nb, nullptr); ctx().macmax_cache.assign(nb, nullptr); ctx().macmax_src.assign(nb, nullptr);
@@ -131,7 +130,7 @@ extern "C" int vdn_advance_timestep(int istep, vdn_layout *mla, vdn_multifab **s
   // the same operands, at the top of velocity_advance (velocity_advance.f90:63-66; gp changes only in hgproject, sold and ext not at all; lapu is
   // zeroed in between only for diffusion_type = 2, advance_timestep.f90:116-120).  Unless that is the case the first one is kept for the
   // velocity mkflux (0.32 ms of a 41 ms step at 256^3): the same values, as with the limited slopes above.
-  static const bool force_reuse = !(env_set("VDN_NO_FORCE_REUSE"));
+  const bool force_reuse = !sw().no_force_reuse;
   const bool keep_vel_force = force_reuse && !(viscous && P.diffusion_type == 2);
   vdn_multifab *vel_force0[VDN_MAXLEV] = { nullptr };
   if (keep_vel_force) for (int n = 0; n < nlevs; n++) vel_force0[n] = mf_temp(mla, n, dm, 1, -1, false, 0.0);

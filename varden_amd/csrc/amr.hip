@@ -949,9 +949,8 @@ int ml_cc_solve(MlCcRequest &rq) {
   hipStream_t st = ctx().stream;
   const size_t mark = arena_mark();
   const int L = la->nlev;
-  static const bool fuse_first_on = env_on("VDN_MLCC_FUSE1");
-  static const bool rho_form = env_on("VDN_MLCC_RHO");
-  const bool fuse_first = fuse_first_on && ctx().prm.mg_nu1 >= 1 && ctx().prm.mg_nu2 >= 1;
+  const bool rho_form = sw().mlcc_rho;
+  const bool fuse_first = sw().mlcc_fuse1 && ctx().prm.mg_nu1 >= 1 && ctx().prm.mg_nu2 >= 1;
   const vdn_multifab *frho = (rho_form && !alpha) ? rq.fine_rho : nullptr;
   if (frho) REQUIRE(frho->ng >= 1 && frho->lev == L - 1, "composite solve: the finest level's density with a filled ghost cell expected");
   // everything the descriptor sets of this solve follow from: the key of the kept ones (vdn_internal.h)
@@ -1042,8 +1041,7 @@ int ml_cc_solve(MlCcRequest &rq) {
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc0[d][s] = bct->ell_bc(0, 0, d, s, bc_comp0);
   while (!conv) {
     rn = composite_residual(S);
-    { static const bool trace = env_set("VDN_MLCC_TRACE");
-      if (trace) fprintf(stderr, "  ml_cc_solve: iteration %d, composite residual %.6e (right-hand side %.6e, target %.3e)\n", it, rn, bnorm, rel_eps * bnorm); }
+    if (sw().mlcc_trace) fprintf(stderr, "  ml_cc_solve: iteration %d, composite residual %.6e (right-hand side %.6e, target %.3e)\n", it, rn, bnorm, rel_eps * bnorm);
     if (rn <= rel_eps * bnorm && bnorm < HUGE_VAL) { conv = true; break; }
     if (it >= rq.max_iter || !(rn < HUGE_VAL) || !(bnorm < HUGE_VAL)) break;
     // one V-cycle over the levels in correction form (oracle: vo_ml_cc_solve).  Down, finest level first: e_n = 0, nu1 sweeps, t = res_n - A_n e_n,
@@ -1061,7 +1059,7 @@ int ml_cc_solve(MlCcRequest &rq) {
       S.vf_t[n].refresh(); S.rres_t[n].run(0, (double *)nullptr, st);
     }
     // coarse correction: ONE V-cycle of the single-level multigrid on the whole level 0
-    static const bool glue = env_on("VDN_MLCC_GLUE");
+    const bool glue = sw().mlcc_glue;
     // (base_beta / base_rho, the MAC projection: the V-cycle runs on level 0's OWN coefficients 2/(rho_i + rho_i-1) -- `beta` carries the edge
     // restriction of the finer level's on the covered faces -- and so on the density-based kernels of the single-level solver; it is a
     // preconditioner, the composite residual above is formed with `beta`.  Oracle: beta_base of vo_ml_cc_solve)

@@ -49,7 +49,7 @@ struct Rccl {
   bool test_double = false;
 };
 static Rccl g_rccl;
-static int packed_mode() { const char *e = vdn_env("VDN_FORCE_PACKED"); return e ? atoi(e) : 0; }
+static int packed_mode() { return sw_live().force_packed; }      // (read at every call: tests/test_multibox_gpu.py sets it between calls)
 #define NCCLCHK(x) do { int r_ = (x); if (r_ != ncclSuccess) vdn_fail("%s failed: %s", #x, g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "?"); } while (0)
 
 static void rccl_load() {
@@ -59,7 +59,7 @@ static void rccl_load() {
   // is honoured only together with VDN_TESTING=1 AND a library that identifies itself through vdn_test_transport_magic(); anything else
   // named there fails the call.  vdn_comm_transport() says which one is in use (bench.py prints it).
 #ifdef VDN_TESTING_BUILD
-  const char *forced = vdn_env("VDN_RCCL_LIB");
+  const char *forced = sw().rccl_lib;
 #else
   const char *forced = nullptr;            // the release build has no seam for another transport: RCCL by name, nothing else
 #endif
@@ -68,12 +68,12 @@ static void rccl_load() {
   Rccl R;
   struct Closer { void *&h; bool armed = true; ~Closer() { if (armed && h) { dlclose(h); h = nullptr; } } } closer{ R.h };
   if (forced && *forced) {
-    const char *t = vdn_env("VDN_TESTING");
-    REQUIRE(t && atoi(t) == 1, "VDN_RCCL_LIB is set but VDN_TESTING=1 is not: the transport of this library is RCCL; only the test suite may replace it");
+    const char *t = sw().testing;
+    REQUIRE(t && atoi(t) == 1, "the variable VDN_RCCL_LIB is set but VDN_TESTING=1 is not: the transport of this library is RCCL; only the test suite may replace it");
     R.h = dlopen(forced, RTLD_NOW | RTLD_LOCAL);
     REQUIRE(R.h, "cannot dlopen the test transport %s: %s", forced, dlerror());
     long (*magic)() = nullptr; *(void **)(&magic) = dlsym(R.h, "vdn_test_transport_magic");
-    REQUIRE(magic && magic() == 0x76646e74657374L, "VDN_RCCL_LIB names %s, which is not the test double of tests/fake_rccl", forced);
+    REQUIRE(magic && magic() == 0x76646e74657374L, "the variable VDN_RCCL_LIB names %s, which is not the test double of tests/fake_rccl", forced);
     R.test_double = true;
     fprintf(stderr, "varden_amd: TEST TRANSPORT %s in place of RCCL (VDN_TESTING=1)\n", forced);
   }
@@ -606,8 +606,7 @@ void xplan_cache_purge(unsigned long uid) {
 // or one -- three quarters of the copy kernel's workgroups
 void mf_fill_boundary(vdn_multifab *mf, bool faces_only) {
   if (mf->ng == 0) return;
-  static const bool faces_ok = env_on("VDN_FB_FACES");
-  faces_only = faces_only && faces_ok;
+  faces_only = faces_only && sw().fb_faces;
   const int ndflags = mf->nodal[0] | (mf->nodal[1] << 1) | (mf->nodal[2] << 2);
   auto plan = [&](int variant, const int *trim) -> XPlan * {
     FbKey key{ mf->la->uid, mf->base, mf->lev, mf->nc, mf->ng, ndflags + (faces_only ? 8 : 0) + 16 * variant };

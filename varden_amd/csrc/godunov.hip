@@ -167,8 +167,7 @@ template <int NC> __global__ void __launch_bounds__(256) kk_slopes_my(FV s, FV s
   if (vmax) block_atomic_max(vmax, m);
 }
 static void launch_slopes(const FV &s, const FV sl[3], const GArgs &A, const Range3 &rg, int ncomp, double *vmax, hipStream_t st) {
-  static const bool marching = env_on("VDN_SLOPES_MARCH");
-  if (marching && (ncomp == 2 || ncomp == 3) && s.a0 <= A.lo[0] - 3 && s.a1 <= A.lo[1] - 3 && s.a2 <= A.lo[2] - 3) {
+  if (sw().slopes_march && (ncomp == 2 || ncomp == 3) && s.a0 <= A.lo[0] - 3 && s.a1 <= A.lo[1] - 3 && s.a2 <= A.lo[2] - 3) {
     const int nx = rg.hi[0] - rg.lo[0] + 1, ny = rg.hi[1] - rg.lo[1] + 1, nz = rg.hi[2] - rg.lo[2] + 1;
     const int tiles = ((nx + 59) / 60) * ((ny + 3) / 4);
     int chunks = std::max(1, std::min(nz / 8, (32 * 256 + tiles - 1) / tiles));      // (measured at 256^3, three / two components: 4 x 256 workgroups 0.741 / 0.477 ms, 8 x 0.667 / 0.418, 16 x 0.661 / 0.406, 32 x 0.645 / 0.384)
@@ -378,21 +377,19 @@ __global__ void __launch_bounds__(256) kk_mk_D(FV s, FV sl0, FV sl1, FV sl2, FV 
 // the computable region produce values nobody uses), the rare boundary work sits in one branch after it.
 // VDN_GODUNOV_BATCH=1 launches the descriptor (box-batched) kernels also for a level of one box. Measured at 256^3: they need
 // fewer VGPRs (mk_D<1> 116 vs 174) yet run slower there (scalar 6.6 vs 5.6 ms, velocity 10.0 vs 8.2 ms), so one box keeps the by-value kernels
-static bool batch_always() { static const bool b = env_set("VDN_GODUNOV_BATCH"); return b; }
 // one launch per stage for all boxes (descriptors) or one set of launches per box (arguments by value)?  A level of an adaptive
 // hierarchy (hundreds of 16^3 .. 32^3 boxes) is launch-bound box by box; a level of a few large boxes -- 512^3 cut into eight 256^3
 // boxes -- runs faster box by box: the by-value kernels need fewer registers (measured,
 // eight 256^3 boxes on one GPU: scalar 52 -> 42 ms, velocity 76 -> 54 ms per step).  VDN_GODUNOV_BATCH=1 forces the descriptors.
 static bool use_batched(const vdn_multifab *s) {
   if (s->nfabs() == 0) return false;
-  if (batch_always()) return true;
+  if (sw().godunov_batch) return true;
   if (s->nfabs() == 1) return false;
   long cells = 0;
   for (int b = 0; b < s->nfabs(); b++) cells += (long)(s->vbox[b].hi[0] - s->vbox[b].lo[0] + 1) * (s->vbox[b].hi[1] - s->vbox[b].lo[1] + 1) * (s->vbox[b].hi[2] - s->vbox[b].lo[2] + 1);
   return !(s->nfabs() <= 16 && cells / s->nfabs() >= 96L * 96 * 96);
 }
 bool god_per_box(const vdn_multifab *s) { return s->nfabs() >= 1 && !use_batched(s); }
-static bool plain_godunov() { static const bool p = vdn_env("VDN_GODUNOV_PLAIN") != nullptr; return p; }
 // tile order of the marching kernels: XCD-aware (vdn_dev.h xcd_tile)
 __constant__ int g_god_xcd = 1;
 DEVI void xcd_remap(int &bx, int &by, int &bz) { if (g_god_xcd) xcd_tile(bx, by, bz); else { bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z; } }
@@ -445,7 +442,6 @@ struct FCell { double m_lo[3], m_up[3], s0, f, mr, Lb[3], Rb[3]; };      // a ce
 // results included: both are the correctly rounded value of the same real number), so where every dx is a power of two -- the unit cube on
 // 2^n cells, every level of a hierarchy over it -- the P2 kernels multiply.  The ten f64 divisions per cell and plane of the fused march were a
 // third of its f64 instructions (v_div_scale x 2, v_rcp, eight fma, v_div_fmas, v_div_fixup each).  Other spacings keep the division.
-static bool no_p2() { static const bool off = !env_on("VDN_GOD_P2"); return off; }      // (the variants test: division path on power-of-two grids)
 static bool is_pow2(double x) { int e; return x > 0.0 && std::frexp(x, &e) == 0.5; }
 #define DIVDX(x, d) (PW2 ? (x) * F.idx[d] : (x) / F.dx[d])
 template <bool PW2> DEVI void f_bases(const FArgs &F, FCell &P, const double sl[3]) {
@@ -471,7 +467,7 @@ static dim3 fused_grid(const Range3 &r, int &klen) {
   // one 512-thread workgroup per CU at a time: the chunk count is the one that fills the last round of workgroups best
   const int nx = r.hi[0] - r.lo[0] + 1, ny = r.hi[1] - r.lo[1] + 1, nz = r.hi[2] - r.lo[2] + 1;
   const int tiles = ((nx + FNX - 1) / FNX) * ((ny + FNY - 1) / FNY);
-  static const int env = vdn_env("VDN_FUSED_KCHUNKS") ? std::max(1, atoi(vdn_env("VDN_FUSED_KCHUNKS"))) : 0;
+  const int env = sw().fused_kchunks;
   int best = 1; double best_cost = 1e300;
   for (int ch = 1; ch <= 16 && ch <= nz; ch++) {
     const int kl = (nz + ch - 1) / ch, nch = (nz + kl - 1) / kl;
@@ -485,7 +481,7 @@ static dim3 fused_grid(const Range3 &r, int &klen) {
 // the grid of a fused march whose remainder tile column runs in narrow segments (kk_mk_F_mc, kk_vp_F_mc): `full` 62-cell tile columns + one column of
 // segments of segw lanes; false when the box has no remainder column worth it.  The chunk count is chosen for the workgroups that do work.
 static bool fused_grid_cols(const Range3 &rf, dim3 &g, int &klen, int &full, int &segw) {
-  static const bool narrow_env = env_on("VDN_GOD_NARROW");
+  const bool narrow_env = sw().god_narrow;
   const int nx = rf.hi[0] - rf.lo[0] + 1, ny = rf.hi[1] - rf.lo[1] + 1, nz = rf.hi[2] - rf.lo[2] + 1;
   full = nx / FNX;
   const int rem = nx - full * FNX;
@@ -911,7 +907,7 @@ static bool fused_args(FArgs &F, const GArgs &A, int c, const FV &s, const FV sl
     F.lo[d] = A.lo[d]; F.hi[d] = A.hi[d]; F.phys[d][0] = A.phys[d][0]; F.phys[d][1] = A.phys[d][1];
   }
   F.cons = cons ? 1 : 0; F.use_minion = A.use_minion; F.is_vel = A.is_vel; F.c = c;
-  F.p2 = (is_pow2(A.dx[0]) && is_pow2(A.dx[1]) && is_pow2(A.dx[2]) && !no_p2()) ? 1 : 0;
+  F.p2 = (is_pow2(A.dx[0]) && is_pow2(A.dx[1]) && is_pow2(A.dx[2]) && sw().god_p2) ? 1 : 0;
   F.qn = nullptr; F.sqn = 0; F.hn = FGeo{ 0, 0, 0 }; F.pfu[0] = F.pfu[1] = F.pfu[2] = nullptr; F.fmode = 0; F.dt = A.dt; F.lapu0 = 0.0;
   return true;
 }
@@ -1034,8 +1030,7 @@ static void fused_grid_small(const Range3 &r, int &klen, int g[3], int &sw) {
   klen = (nz + chunks - 1) / chunks;
   g[0] = (nx + FNX - 1) / FNX; g[1] = (ny + FNY - 1) / FNY; g[2] = (nz + klen - 1) / klen;
   sw = 0;
-  static const bool narrow_on = env_on("VDN_GOD_SEGW");
-  if (!narrow_on) return;
+  if (!::sw().god_segw) return;      // (the global accessor: sw is the segment width here)
   int best = g[0] * g[1];
   for (int w = 6; w <= 32; w++) {
     const int ox = w - 2, oy = TNY * (64 / w) - 2, c = ((nx + ox - 1) / ox) * ((ny + oy - 1) / oy);
@@ -1055,9 +1050,8 @@ template <class D> struct GodBatch {
       const dim3 *g[2] = { &gs, &gm }; int *o[2] = { q.gs, q.gm };
       for (int t = 0; t < 2; t++) { o[t][0] = g[t]->x; o[t][1] = g[t]->y; o[t][2] = g[t]->z; start[t * nb + b] = tot[t]; tot[t] += (int)(g[t]->x * g[t]->y * g[t]->z); }
       // the slope launch: the plane flattened over the workgroup when that takes fewer workgroups (kk_slopes_b: gs[1] = 0)
-      static const bool flat_on = env_on("VDN_BATCH_FLAT");
       const int pnx = q.rg.hi[0] - q.rg.lo[0] + 1, pny = q.rg.hi[1] - q.rg.lo[1] + 1;
-      if (flat_on && pnx > 0 && pny > 0 && (pnx * pny + 255) / 256 < (int)(gs.x * gs.y)) {
+      if (sw().batch_flat && pnx > 0 && pny > 0 && (pnx * pny + 255) / 256 < (int)(gs.x * gs.y)) {
         const int gfl = (pnx * pny + 255) / 256;
         tot[0] += (gfl - (int)(gs.x * gs.y)) * (int)gs.z;
         q.gs[0] = gfl; q.gs[1] = 0;
@@ -1128,7 +1122,7 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
   REQUIRE(ncomp <= 3, "mkflux: at most 3 components per window (got %d)", ncomp);
   REQUIRE(s->ng >= 3 && umac[0]->ng >= 1 && force->ng >= 1 && mac_rhs->ng >= 1, "mkflux: ghost widths");
   hipStream_t st = ctx().stream;
-  if (use_batched(s) && !plain_godunov()) {            // every stage once for all boxes of the level: the slopes, then stages B + C + D in one march (mk_F_m_body)
+  if (use_batched(s) && !sw().godunov_plain) {            // every stage once for all boxes of the level: the slopes, then stages B + C + D in one march (mk_F_m_body)
     size_t mark = arena_mark();
     const int nb = s->nfabs();
     GodBatch<MkD> B; B.d.resize(nb);
@@ -1213,13 +1207,12 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
     }
     if (!cached) launch_slopes(s->fabs[ib], sl, A, rg, ncomp, nullptr, st);
     FArgs FA[3];
-    bool fused = !plain_godunov();
+    bool fused = !sw().godunov_plain;
     for (int c0 = 0; c0 < ncomp && fused; c0++)
       fused = fused_args(FA[c0], A, c0, s->fabs[ib], sl, um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], sedge[0]->fabs[ib], sedge[1]->fabs[ib], sedge[2]->fabs[ib],
                          flux[0]->fabs[ib], flux[1]->fabs[ib], flux[2]->fabs[ib]);
     if (fused) {                   // stages B + C + D in one march per component, boundary rules inside (see mk_F_m_body)
-      static const bool upd_env = env_on("VDN_GOD_UPDATE");
-      bool do_upd = upd && upd_env;                  // (every box of a box-by-box level: the conditions are geometric and the same for all of them -- checked below)
+      bool do_upd = upd && sw().god_update;                  // (every box of a box-by-box level: the conditions are geometric and the same for all of them -- checked below)
       for (int c0 = 0; c0 < ncomp && do_upd; c0++) do_upd = fused_update_args(FA[c0], A, c0, upd->snew->fabs[ib], force->fabs[ib], *upd, ib);
       int klF;
       const dim3 gF = fused_grid(rf, klF), blk(64, TNY, 1);
@@ -1820,7 +1813,7 @@ static bool vfused_args(VArgs &F, const GArgs &A, const FV &u, const FV sl[3], c
     F.lo[d] = A.lo[d]; F.hi[d] = A.hi[d]; F.phys[d][0] = A.phys[d][0]; F.phys[d][1] = A.phys[d][1];
   }
   F.use_minion = A.use_minion; F.outlet2d = A.outlet2d;
-  F.p2 = (is_pow2(A.dx[0]) && is_pow2(A.dx[1]) && is_pow2(A.dx[2]) && !no_p2()) ? 1 : 0;
+  F.p2 = (is_pow2(A.dx[0]) && is_pow2(A.dx[1]) && is_pow2(A.dx[2]) && sw().god_p2) ? 1 : 0;
   return true;
 }
 
@@ -2053,7 +2046,7 @@ void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *f
   if (ctx().prm.dm == 2) { k2_velpred(u, umac, force, dx, dt, bct); return; }
   REQUIRE(u->nc == 3 && u->ng >= 3 && force->ng >= 1 && umac[0]->ng >= 1, "velpred: operand shapes");
   hipStream_t st = ctx().stream;
-  if (use_batched(u) && !plain_godunov()) {            // the slopes, then stages B + C + D in one march per box (vp_F_m_body)
+  if (use_batched(u) && !sw().godunov_plain) {            // the slopes, then stages B + C + D in one march per box (vp_F_m_body)
     size_t mark = arena_mark();
     const int nb = u->nfabs();
     GodBatch<VpD> B; B.d.resize(nb);
@@ -2123,7 +2116,7 @@ void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *f
     for (int d = 0; d < 3; d++) { rg.lo[d] = A.lo[d] - 1; rg.hi[d] = A.hi[d] + 1; rf.lo[d] = A.lo[d]; rf.hi[d] = A.hi[d] + 1; }
     launch_slopes(u->fabs[ib], sl, A, rg, 3, umax, st);      // + max |u| (kk_velmax)
     VArgs VA;
-    if (!plain_godunov() && vfused_args(VA, A, u->fabs[ib], sl, force->fabs[ib], umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib])) {
+    if (!sw().godunov_plain && vfused_args(VA, A, u->fabs[ib], sl, force->fabs[ib], umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib])) {
       int klF;                     // stages B + C + D in one march, boundary rules inside (see vp_F_m_body)
       const dim3 gF = fused_grid(rf, klF), blk(64, TNY, 1);
       bool any = false, inflow = false;

@@ -486,29 +486,14 @@ static inline void launch_gsrb_shell(const CLev &L, int color, hipStream_t st, i
   if (L.rho) hipLaunchKernelGGL(kk_cc_gsrb_shell<true>, g, dim3(64, 4, 1), 0, st, L, color, hm);
   else hipLaunchKernelGGL(kk_cc_gsrb_shell<false>, g, dim3(64, 4, 1), 0, st, L, color, hm);
 }
-// ---- the launch-form switches of this file (runtime.hip's table), each read here ----------------------------------------------------------
-static bool mac_kflip()         { static const bool b = env_on("VDN_MAC_KFLIP"); return b; }
-static bool gsrb_pair_on()      { static const bool b = env_on("VDN_GSRB_PAIR"); return b; }
-static bool restrict_fused_on() { static const bool b = env_on("VDN_MG_RESTRICT_FUSED"); return b; }
-static bool prolong_fused_on()  { static const bool b = env_on("VDN_MG_PROLONG_FUSED"); return b; }
-static bool mac_split_on()      { static const bool b = env_on("VDN_MAC_SPLIT"); return b; }      // 0: the finest level of a MAC solve stays interleaved
-static long mac_split_min()     { static const long n = env_int("VDN_MAC_SPLIT_MIN", 1 << 23); return n; }
-static int  mac_slab_env()      { static const int k = env_int("VDN_MAC_SLAB", -1); return k; }
-static bool mg_lds_on()         { static const bool b = env_on("VDN_MG_LDS"); return b; }
-static bool mg_tailcycle_on()   { static const bool b = env_on("VDN_MG_TAILCYCLE"); return b; }
-static int  overlap_env()       { static const int v = env_int("VDN_OVERLAP", -1); return v; }
-// the 7-point operator reads no edge or corner ghost cell: the halo of phi carries the face cells only (VDN_CC_HALO_FACES=0: the whole shell)
-static bool cc_faces_only()     { static const bool b = env_on("VDN_CC_HALO_FACES"); return b; }
-// VDN_MAC_STORED_BETA=1: the finest level reads the stored face coefficients like the others (the measured alternative of DESIGN.md section 4)
-static bool beta_from_rho()     { static const bool b = !env_set("VDN_MAC_STORED_BETA"); return b; }
 // ---- the launch forms a level's extents allow, each said here -------------------------------------------------------------------------------
 // the 2 x 2 pair kernels (colour passes, residual): even in x and y, at least two waves wide (VDN_GSRB_PAIR=0: one cell per thread)
-static bool cc_pair_level(const CLev &L) { return gsrb_pair_on() && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[0] >= 128; }
+static bool cc_pair_level(const CLev &L) { return sw().gsrb_pair && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[0] >= 128; }
 // ... and even in z: the pair kernels that also write or read the next level (residual + restriction, the correction inside the first sweep, the level by colour)
 static bool cc_pair_level_z(const CLev &L) { return cc_pair_level(L) && L.n[2] % 2 == 0; }
 static inline void launch_gsrb(const CLev &L, int color, hipStream_t st, int interior_only = 0) {
   const dim3 blk(64, 4, 1), g((unsigned)(((L.n[0] + 1) / 2 + 63) / 64), (unsigned)((L.n[1] + 3) / 4), (unsigned)L.n[2]);
-  const int kdown = (mac_kflip() && (color & 1)) ? 1 : 0;
+  const int kdown = (sw().mac_kflip && (color & 1)) ? 1 : 0;
   if (L.rho && cc_pair_level(L))
     hipLaunchKernelGGL(kk_cc_gsrb_rho_pair, dim3((unsigned)((L.n[0] / 2 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)L.n[2]), blk, 0, st, L, color, interior_only, kdown);
   else if (L.rho) hipLaunchKernelGGL(kk_cc_gsrb_rho, g, blk, 0, st, L, color, interior_only);
@@ -1211,8 +1196,8 @@ template <int ADD> static inline void launch_gsrb_split(const CBox &B, int color
   if (k1 < 0) k1 = L.n[2];
   const dim3 g((unsigned)((L.n[0] / 4 + 63) / 64), (unsigned)((L.n[1] + 7) / 8), (unsigned)(k1 - k0));
   // the second colour walks the planes downwards: what the first colour's pass touched last is what it reads first (Infinity Cache; VDN_MAC_KFLIP=0: both upwards)
-  if (L.cmu > 0.0) hipLaunchKernelGGL((kk_cc_gsrb_rho_split<ADD, true>), g, dim3(64, 8, 1), 0, st, L, B.sp, color, C, (mac_kflip() && color) ? 1 : 0, k0, hm);
-  else hipLaunchKernelGGL((kk_cc_gsrb_rho_split<ADD, false>), g, dim3(64, 8, 1), 0, st, L, B.sp, color, C, (mac_kflip() && color) ? 1 : 0, k0, hm);
+  if (L.cmu > 0.0) hipLaunchKernelGGL((kk_cc_gsrb_rho_split<ADD, true>), g, dim3(64, 8, 1), 0, st, L, B.sp, color, C, (sw().mac_kflip && color) ? 1 : 0, k0, hm);
+  else hipLaunchKernelGGL((kk_cc_gsrb_rho_split<ADD, false>), g, dim3(64, 8, 1), 0, st, L, B.sp, color, C, (sw().mac_kflip && color) ? 1 : 0, k0, hm);
 }
 static inline void launch_residual_split_rst(const CLev &L, const CSplit &S, double *nrm, const CLev &C, int Ka, int Kb, hipStream_t st) {
   const dim3 g((unsigned)((L.n[0] / 4 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)std::min(Kb - Ka, 16));
@@ -1242,7 +1227,7 @@ static void split_halo(const CDLev &DL, int colour, hipStream_t st = nullptr) { 
 // and enough cells on this rank that the level does not live in the caches anyway.  Round 5 took one box without periodic faces only; round 6: any box list, periodic faces,
 // several ranks -- the ghost exchange runs on the split arrays themselves (cc_split_setup).
 static bool cc_split_ok(const CCMG &M) {
-  if (!mac_split_on() || !restrict_fused_on() || !prolong_fused_on() || M.dlev.size() < 2 || ctx().prm.mg_nu1 < 1 || ctx().prm.mg_nu2 < 1) return false;
+  if (!sw().mac_split || !sw().mg_restrict_fused || !sw().mg_prolong_fused || M.dlev.size() < 2 || ctx().prm.mg_nu1 < 1 || ctx().prm.mg_nu2 < 1) return false;
   const CDLev &D0 = M.dlev[0];
   if (D0.boxes.empty() || D0.boxes.size() != M.dlev[1].boxes.size()) return false;
   long cells = 0;
@@ -1254,7 +1239,7 @@ static bool cc_split_ok(const CCMG &M) {
   }
   for (int d = 0; d < 3; d++) if (D0.ng[d] & 1) return false;
   // (128^3 stays interleaved: its arrays live in the caches, the conversions cost more than the passes gain -- 6.98 against 7.21 ms per step)
-  return cells >= mac_split_min();
+  return cells >= sw().mac_split_min;
 }
 static int g_mac_level_form = 0;
 extern "C" int vdn_last_mac_level_form(void) { return g_mac_level_form; }
@@ -1331,7 +1316,7 @@ static XPlan *cc_split_plan(const CDLev &D0, int colour, const int per[3]) {
   vdn_box lpd = D0.lpd; lpd.hi[0] = (lpd.hi[0] + 1) / 2 - 1;
   HaloKey key{ D0.la_uid, (const void *)D0.boxes[0].sp.phi[colour], D0.la_lev, 1000 + colour, per[0] | (per[1] << 1) | (per[2] << 2), hk.h };
   auto it = g_halo_cache.find(key);
-  if (it == g_halo_cache.end()) { XPlan *P = xplan_build(xb, lpd, per, 1, 1, cc_faces_only()); halo_cache_register(D0.la_uid, P); it = g_halo_cache.emplace(key, P).first; }
+  if (it == g_halo_cache.end()) { XPlan *P = xplan_build(xb, lpd, per, 1, 1, sw().cc_halo_faces); halo_cache_register(D0.la_uid, P); it = g_halo_cache.emplace(key, P).first; }
   return it->second;
 }
 
@@ -1342,8 +1327,7 @@ static XPlan *cc_split_plan(const CDLev &D0, int colour, const int per[3]) {
 // The arithmetic is that of the single-box hierarchy wherever the cut is made (global colours, global bottom-sweep counts): tests/test_multirank_gpu.py compares ranks that
 // cut at 64 with one rank that cuts at 128, bit for bit.  VDN_MG_AGGLOM (testing build): a fixed value.
 int mg_agglom(const vdn_layout *la, int lev) {
-  static const int env = env_int("VDN_MG_AGGLOM", 0);
-  if (env > 0) return env;
+  if (sw().mg_agglom > 0) return sw().mg_agglom;
   bool all_local = true;
   for (int o : la->owner[lev]) if (o != ctx().rank) all_local = false;
   return (all_local && !comm_active()) ? 128 : 64;
@@ -1397,7 +1381,7 @@ static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const in
       GraphKey hk; for (const CBox &B : DL.boxes) { hk.put(B.L.phi); hk.put(B.L.sz); }
       HaloKey key{ la->uid, DL.boxes.empty() ? nullptr : (const void *)DL.boxes[0].L.phi, lev, (int)M.dlev.size(), M.per[0] | (M.per[1] << 1) | (M.per[2] << 2), hk.h };
       auto it = g_halo_cache.find(key);
-      if (it == g_halo_cache.end()) { XPlan *P = xplan_build(xb, lpd, M.per, 1, 1, cc_faces_only()); halo_cache_register(la->uid, P); it = g_halo_cache.emplace(key, P).first; }
+      if (it == g_halo_cache.end()) { XPlan *P = xplan_build(xb, lpd, M.per, 1, 1, sw().cc_halo_faces); halo_cache_register(la->uid, P); it = g_halo_cache.emplace(key, P).first; }
       DL.halo = it->second;
     }
     DL.single_box = (nb == 1);
@@ -1482,7 +1466,7 @@ static void cc_gsrb_d(CCMG &M, CDLev &DL, int nsweeps) {
   // traffic -- pack kernels, the ncclSend / ncclRecv group, box-to-box copies, unpack kernels -- runs on ctx().halo_stream while the
   // launch stream updates the cells that read no ghost value; the one-cell shell follows when the halo has landed
   // Only where the pass is long enough to hide something: boxes of at least 2^20 cells (a 64^3 pass takes 5 us).
-  const int ov_env = overlap_env();
+  const int ov_env = sw().overlap;
   static const long ov_min = 1L << 20;
   bool overlap = DL.halo && (ov_env == 1 || (ov_env != 0 && xplan_has_remote(DL.halo)));
   if (overlap) {
@@ -1540,7 +1524,7 @@ static void cc_residual_d(CCMG &M, CDLev &DL, bool norm, bool reduce = true) {  
   cc_halo(M, DL);
   {   // the finest level of a MAC solve in one box: residual and restriction in one pass (kk_cc_residual_rho_pair_rst); cc_restrict_down then skips
     const size_t l = &DL - &M.dlev[0];
-    if (restrict_fused_on() && DL.single_box && DL.boxes.size() == 1 && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
+    if (sw().mg_restrict_fused && DL.single_box && DL.boxes.size() == 1 && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
       const CLev &L = DL.boxes[0].L;
       if (L.rho && cc_pair_level_z(L)) {
         const dim3 g((unsigned)((L.n[0] / 2 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)std::min(L.n[2] / 2, 16));
@@ -1586,7 +1570,7 @@ static void cc_bottom_t(const CCMG &M, const CLev &L) {      // max(nub, N^2) sw
 // The small end of the hierarchy in one launch (kk_cc_tailcycle): distributed levels dl .. end when they are one box of at most 8^3 cells
 // each (dl < 0: none), then the replicated tail levels tl .. end (one rank and one box: the gather between the two is the plain restriction).
 static bool cc_small_end(const CCMG &M, int dl, int tl) {
-  if (!mg_tailcycle_on()) return false;
+  if (!sw().mg_tailcycle) return false;
   static const long tail_cells = SMALL_LEVEL_CELLS;     // largest level the one-workgroup cycle takes (measured: 16^3 no gain, MAC 15.33 -> 15.39 ms)
   const vdn_params &P = ctx().prm;
   CcTailArgs T; memset(&T, 0, sizeof T);
@@ -1617,7 +1601,7 @@ static bool cc_small_end(const CCMG &M, int dl, int tl) {
 // they were eleven launches per level and cycle; cc_lds_level's conditions)
 static bool cc_lds_tail_level(const CCMG &M, int l) {
   const vdn_params &P = ctx().prm;
-  if (!mg_lds_on() || l + 1 >= (int)M.tail.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
+  if (!sw().mg_lds || l + 1 >= (int)M.tail.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
   const CLev &L = M.tail[l], &C = M.tail[l + 1];
   if (L.rho) return false;
   for (int d = 0; d < 3; d++) if (L.n[d] % LT || L.n[d] < 2 * LT || L.n[d] > 64 || C.n[d] * 2 != L.n[d]) return false;
@@ -1692,13 +1676,13 @@ static void cc_prolong_smooth(CCMG &M, int l, int nsweeps) {
     if (nsweeps > 1) cc_gsrb_d(M, DL, nsweeps - 1);
     return;
   }
-  const bool ok = prolong_fused_on() && nsweeps >= 1 && DL.single_box && DL.boxes.size() == 1 && !DL.halo && l + 1 < (int)M.dlev.size() && M.dlev[l + 1].boxes.size() == 1 &&
+  const bool ok = sw().mg_prolong_fused && nsweeps >= 1 && DL.single_box && DL.boxes.size() == 1 && !DL.halo && l + 1 < (int)M.dlev.size() && M.dlev[l + 1].boxes.size() == 1 &&
                   !(M.per[0] || M.per[1] || M.per[2]) && DL.boxes[0].L.rho && cc_pair_level_z(DL.boxes[0].L);
   if (!ok) { cc_prolong_up(M, l); cc_gsrb_d(M, DL, nsweeps); return; }
   const CLev &L = DL.boxes[0].L, &C = M.dlev[l + 1].boxes[0].L;
   const dim3 g((unsigned)((L.n[0] / 2 + 63) / 64), (unsigned)((L.n[1] / 2 + 3) / 4), (unsigned)L.n[2]), blk(64, 4, 1);
   hipLaunchKernelGGL(kk_cc_gsrb_rho_pair_t<1>, g, blk, 0, ctx().stream, L, 0, 0, C, 0);
-  hipLaunchKernelGGL(kk_cc_gsrb_rho_pair_t<2>, g, blk, 0, ctx().stream, L, 1, 0, C, mac_kflip() ? 1 : 0);
+  hipLaunchKernelGGL(kk_cc_gsrb_rho_pair_t<2>, g, blk, 0, ctx().stream, L, 1, 0, C, sw().mac_kflip ? 1 : 0);
   if (nsweeps > 1) cc_gsrb_d(M, DL, nsweeps - 1);
 }
 // The finest level's part of a cycle -- [prolongation inside the first sweep,] nsweeps red-black sweeps, residual + restriction -- on the SPLIT level in plane
@@ -1714,7 +1698,7 @@ static void cc_prolong_smooth(CCMG &M, int l, int nsweeps) {
 // the planes whose pass traffic (24 B per cell of the level) adds up to ~200 MB -- what stays in the cache between two passes over it; at most half the level.
 // 512^3 (plane = 6.3 MB; MAC solve per step): whole-level launches 69.8 ms; slabs of 16 / 24 / 28 / 32 / 40 / 64 / 256 planes 67.9 / 65.2 / 64.5 / 64.7 / 65.2 / 67.5 / 69.1 ms.
 static int mac_slab(const CLev &L) {
-  if (mac_slab_env() >= 0) return mac_slab_env();
+  if (sw().mac_slab >= 0) return sw().mac_slab;
   const long fit = (long)(200.0e6 / (24.0 * L.n[0] * L.n[1]));
   return (int)std::max(8L, std::min((long)(L.n[2] + 1) / 2, fit));
 }
@@ -1761,7 +1745,7 @@ static void cc_fine_seq(CCMG &M, bool after_coarse, bool residual, bool norm, bo
 static bool cc_lds_level(const CCMG &M, int l) {
   static const int nmax_ = 64;                 // (measured in round 5: the 128^3 level of a 256^3 solve as LDS tiles too, MAC 8.98 -> 10.33 ms per step)
   const vdn_params &P = ctx().prm;
-  if (!mg_lds_on() || l < 1 || l + 1 >= (int)M.dlev.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
+  if (!sw().mg_lds || l < 1 || l + 1 >= (int)M.dlev.size() || P.mg_nu1 != 2 || P.mg_nu2 != 2 || M.per[0] || M.per[1] || M.per[2]) return false;
   const CDLev &D = M.dlev[l], &DC = M.dlev[l + 1];
   if (!(D.single_box && D.boxes.size() == 1 && !D.halo && DC.single_box && DC.boxes.size() == 1)) return false;
   const CLev &L = D.boxes[0].L;
@@ -1979,7 +1963,7 @@ static void cc_setup(CCMG &M, vdn_multifab *rh, vdn_multifab *phi, const vdn_mul
   cc_build(M, rh, dx, bc, alpha != nullptr);
   CDLev &D0 = M.dlev[0];
   // beta = 2 / (rho_i + rho_i-1) (the MAC projection): the finest level recomputes it from rho; not with the fused sweeps (they read b)
-  const bool from_rho = rho && !alpha && beta_from_rho() && rho->ng >= 1;
+  const bool from_rho = rho && !alpha && !sw().mac_stored_beta && rho->ng >= 1;
   for (size_t b = 0; b < D0.boxes.size(); b++) {
     CLev &L0 = D0.boxes[b].L;
     const vdn_box &bx = rh->vbox[b];
@@ -2310,9 +2294,8 @@ static void mac_level_mkumac_rho(vdn_multifab **um, const std::vector<FV> &phi_v
     v.push_back({ mkumac_rho_K{ um[0]->fabs[i], um[1]->fabs[i], um[2]->fabs[i], phi_view[i], rho->fabs[i], A }, rf });
   }
   // advance_timestep on one level, one box: the step's cache of max |umac| (godunov.hip: macmax_cache) is filled here
-  static const bool fuse_max = env_on("VDN_MAC_UMAX");
   VdnCtx &c = ctx();
-  if (fuse_max && v.size() == 1 && rho->la->nlev == 1 && c.macmax_cache.size() == 1 && c.macmax_cache[0]) {
+  if (sw().mac_umax && v.size() == 1 && rho->la->nlev == 1 && c.macmax_cache.size() == 1 && c.macmax_cache[0]) {
     HIPCHK(hipMemsetAsync(c.macmax_cache[0], 0, sizeof(double), c.stream));
     dim3 g = grid_for(v[0].second, dim3(64, 4, 1));
     if (g.z > 64) g.z = 64;                                       // (one atomic per workgroup, each walking its share of the planes; 8 / 32 / 64 / 258 chunks: MAC 9.085 / 9.062 / 9.051 / 9.13 ms.
@@ -2360,9 +2343,8 @@ void do_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn
   const int n = 0;
   size_t mark = arena_mark();
   {
-    static const bool fast_on = env_on("VDN_MAC_FAST");
     // the second level must exist (its coefficients come from the first level's rho): boxes that halve cleanly to >= 4 cells, as cc_build asks
-    bool ok = fast_on && beta_from_rho() && rho[n]->ng >= 1;
+    bool ok = sw().mac_fast && !sw().mac_stored_beta && rho[n]->ng >= 1;
     {   // cc_build's rule for a second DISTRIBUTED level: the domain coarsens, the boxes halve cleanly and stay at least min_dist wide
       const int agglom = mg_agglom(mla, n);
       const int min_dist = mla->boxes[n].size() > 1 ? agglom : 4;

@@ -1059,21 +1059,8 @@ static NdPairGrid nd_pair_grid(const NLev &L, int rows, int nzu, bool use_rem, i
   G.rev = 0;
   return G;
 }
-// ---- the launch-form switches of this file (runtime.hip's table), each read here ----------------------------------------------------------
-static bool nd_pair_on()           { static const bool b = env_on("VDN_ND_PAIR"); return b; }
-static bool nd_rev_on()            { static const bool b = env_on("VDN_ND_REV"); return b; }
-static bool nd_lean_on()           { static const bool b = env_on("VDN_ND_LEAN"); return b; }
-static bool nd_restrict_fused_on() { static const bool b = env_on("VDN_ND_RESTRICT_FUSED"); return b; }
-static bool nd_prolong_fused_on()  { static const bool b = env_on("VDN_ND_PROLONG_FUSED"); return b; }
-static bool nd_tailcycle_on()      { static const bool b = env_on("VDN_MG_TAILCYCLE"); return b; }
-static int  nd_overlap_env()       { static const int v = env_int("VDN_OVERLAP", -1); return v; }
-static bool hg_fast_on()           { static const bool b = env_on("VDN_HG_FAST"); return b; }
-static bool ndf_pair_on()          { static const bool b = env_on("VDN_NDF_PAIR"); return b; }
-static bool ndm_iface_faces_on()   { static const bool b = env_on("VDN_NDM_IFACE_FACES"); return b; }
-static bool ndm_prolong8_on()      { static const bool b = env_on("VDN_NDM_PROLONG8"); return b; }
-static bool ndm_neg_copy()         { static const bool b = env_set("VDN_NDM_NEG"); return b; }
 // the wide nodal level: the pair march (124 nodes per wave row; VDN_ND_PAIR=0: one node per lane)
-static bool nd_wide_level(const NLev &L) { return nd_pair_on() && L.n[0] >= 127; }
+static bool nd_wide_level(const NLev &L) { return sw().nd_pair && L.n[0] >= 127; }
 // ... with even extents: the pair marches that also write or read the next level (residual + restriction, the correction inside the first sweep)
 static bool nd_wide_even_level(const NLev &L) { return nd_wide_level(L) && L.n[0] % 2 == 0 && L.n[1] % 2 == 0 && L.n[2] % 2 == 0; }
 // slab thickness: enough workgroups to fill 256 CUs several times over, yet long enough marches to amortise the
@@ -1091,7 +1078,7 @@ template <int MODE> static void nd_launch_march(const NLev &L, const double *phi
     const int rows = 4;                          // (measured: 8 rows per workgroup 17.1 -> 18.7 ms of HG per step, 16 rows spill)
     const bool use_rem = true; const int minwg = 2048, kc_env = 0;
     NdPairGrid G = nd_pair_grid(L, rows, nzp, use_rem, minwg, kc_env);
-    G.rev = nd_rev_on() ? rev : 0;
+    G.rev = sw().nd_rev ? rev : 0;
     if (MODE == 0 && pro) {
       const NdCoarse C{ pro->phi, pro->PX, pro->PY, pro->n[0] };
       hipLaunchKernelGGL((kk_nd_march_pair<0, 4, 1>), dim3(G.nmain + G.gyr * G.gz), NBLK, 0, ctx().stream, L, phi, out, nd_cur_omega(), G, nrm, shell_later, C);
@@ -1147,7 +1134,7 @@ static NLev nd_alloc_lev(const int n[3], const double h[3]) {
   // Row padding beyond the ghost nodes only ever reaches lanes whose results are discarded.
   // (The first version left sigma to its load as well -- true on the finest level only: the 129^3 level of a 257^3 solve then read
   // whatever the arena held beyond the walls, which happened to be zeros until hgproject stopped allocating its multifabs in front of it.)
-  if (nd_lean_on() && (long)(n[0] + 1) * (n[1] + 1) * (n[2] + 1) >= (1L << 21)) {
+  if (sw().nd_lean && (long)(n[0] + 1) * (n[1] + 1) * (n[2] + 1) >= (1L << 21)) {
     const int m = std::max(n[0], std::max(n[1], n[2])) + 3;
     hipLaunchKernelGGL(kk_nd_zero_shell, dim3((m + 63) / 64, (m + 3) / 4, 6), dim3(64, 4, 1), 0, ctx().stream, L, L.phi, L.tmp, L.res);
     HIPCHK(hipMemsetAsync(L.sig, 0, sizeof(double) * L.sz, ctx().stream));
@@ -1283,7 +1270,7 @@ static void nd_halo_phi(NDLev &DL) { XPlan *P = DL.flip ? DL.halo_B : DL.halo_A;
 static bool nd_halo_begin(NDLev &DL) {
   XPlan *P = DL.flip ? DL.halo_B : DL.halo_A;
   if (!P) return false;
-  const int ov_env = nd_overlap_env();
+  const int ov_env = sw().overlap;
   static const long ov_min = 1L << 20;     // see cc_gsrb_d
   long nodes = 0;
   for (const NBox &B : DL.boxes) nodes = std::max(nodes, (long)B.L.n[0] * B.L.n[1] * B.L.n[2]);
@@ -1344,12 +1331,12 @@ static void nd_residual_d(NDMG &M, NDLev &DL, bool norm, bool reduce = true) {  
   DL.res_restricted = false;
   {   // a wide one-box level without periodic images whose next level is one box too: residual and the x / z part of the restriction in one march
     const size_t l = &DL - &M.dlev[0];
-    if (nd_restrict_fused_on() && DL.single_box && DL.boxes.size() == 1 && !DL.halo_res && !(DL.per[0] || DL.per[1] || DL.per[2]) && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
+    if (sw().nd_restrict_fused && DL.single_box && DL.boxes.size() == 1 && !DL.halo_res && !(DL.per[0] || DL.per[1] || DL.per[2]) && l + 1 < M.dlev.size() && M.dlev[l + 1].boxes.size() == 1) {
       const NLev &L = DL.boxes[0].L;
       if (nd_wide_even_level(L)) {
         nd_halo_phi(DL);                                                  // (no neighbour, no image: nothing to exchange; kept for symmetry with the plain path)
         NdPairGrid G = nd_pair_grid(L, 4, L.n[2] / 2 + 1, true, 2048, 0);
-        G.rev = nd_rev_on() ? DL.rev : 0; DL.rev ^= 1;
+        G.rev = sw().nd_rev ? DL.rev : 0; DL.rev ^= 1;
         hipLaunchKernelGGL((kk_nd_march_pair_rst<4>), dim3(G.nmain + G.gyr * G.gz), NBLK, 0, ctx().stream, L, (const double *)L.phi, L.res, G, norm ? M.d_nrm : nullptr);
         DL.res_restricted = true;
         if (norm && reduce) comm_allreduce_max_dev(M.d_nrm, 1);
@@ -1456,7 +1443,7 @@ static void nd_prolong_up(NDMG &M, int l) {
 // 127 nodes, the nested iteration's interpolation -- keeps kk_nd_prolong_m.  Same omegas, same tile-order alternation, same phi / tmp flips either way.
 static bool nd_prolong_fusable(const NDMG &M, int l) {
   const NDLev &DL = M.dlev[l];
-  if (!(nd_prolong_fused_on() && DL.single_box && DL.boxes.size() == 1 && !DL.halo_A && !DL.halo_B && !(DL.per[0] || DL.per[1] || DL.per[2]))) return false;
+  if (!(sw().nd_prolong_fused && DL.single_box && DL.boxes.size() == 1 && !DL.halo_A && !DL.halo_B && !(DL.per[0] || DL.per[1] || DL.per[2]))) return false;
   if (l + 1 < (int)M.dlev.size() ? M.dlev[l + 1].boxes.size() != 1 : M.tail.empty()) return false;
   const NBox &B = DL.boxes[0];
   const NLev &L = B.L, &C = l + 1 < (int)M.dlev.size() ? M.dlev[l + 1].boxes[0].L : M.tail[0];
@@ -1480,7 +1467,7 @@ static int nd_bottom_sweeps_global(const NDLev &DL) {
 // The small end of the hierarchy in one launch (kk_nd_tailcycle): distributed levels dl .. end when they are one box of at most 9^3 nodes
 // each (dl < 0: none), then the replicated tail levels tl .. end (one rank and one box: the gather between the two is the plain restriction).
 static bool nd_small_end(NDMG &M, int dl, int tl) {
-  if (!nd_tailcycle_on()) return false;
+  if (!sw().mg_tailcycle) return false;
   static const long tail_nodes = SMALL_LEVEL_NODES;    // largest level the one-workgroup cycle takes (measured: 17^3 is slower, HG 16.9 -> 17.6 ms)
   const vdn_params &P = ctx().prm;
   NdTailArgs T; memset(&T, 0, sizeof T);
@@ -1907,7 +1894,7 @@ void do_hgproject(int proj_type, vdn_layout *mla, vdn_multifab **unew, vdn_multi
   // Round 3: rh, phi and coeffs (hgproject.f90:70-76, hg_multigrid.f90:68-80) exist only to carry zeros, D u and 1 / rhohalf into the solver
   // and phi out of it: the solver takes sigma from rhohalf, forms b = -D u while it loads, and hg_update reads phi from the level array
   // (0.5 ms of fills, copies and passes per 256^3 projection; VDN_HG_FAST=0: the multifabs as the reference has them -- same values)
-  if (hg_fast_on()) {
+  if (sw().hg_fast) {
     hg_level_pre(proj_type, un, uo, rhh, gpp, nullptr, dt, bct);
     NdFast F; F.rhohalf = rhh;
     q.fast = &F;
@@ -2151,7 +2138,7 @@ static MarchSet ndf_build_march(std::vector<MarchB> &v) {
     const int nx = B.r.hi[0] - B.r.lo[0] + 1, ny = B.r.hi[1] - B.r.lo[1] + 1, nz = B.r.hi[2] - B.r.lo[2] + 1;
     // the segment width that needs the fewest waves per node row (kk_ndf_march2: a lane carries two nodes): tiles along x / rows per wave; a box of
     // 33 nodes takes 19 lanes (17 pairs + the two feeding lanes), three rows per wave, where the power-of-two segments of round 3 gave it 32 and two
-    const int per_lane = ndf_pair_on() ? 2 : 1;
+    const int per_lane = sw().ndf_pair ? 2 : 1;
     int best = 64; double best_cost = 1e30;
     for (int sw = 4; sw <= 64; sw++) {
       const double cost = (double)((nx + per_lane * (sw - 2) - 1) / (per_lane * (sw - 2))) / (double)(64 / sw);
@@ -2174,7 +2161,7 @@ static MarchSet ndf_build_march(std::vector<MarchB> &v) {
 }
 template <int MODE> static void ndf_run_march(const MarchSet &S, double omega, int excl, double *nrm) {
   if (S.nbox == 0) return;
-  if (ndf_pair_on()) hipLaunchKernelGGL(kk_ndf_march2<MODE>, dim3(S.tot), NBLK, 0, ctx().stream, (const MarchB *)S.d_args, (const int *)S.d_start, S.nbox, omega, excl, nrm);
+  if (sw().ndf_pair) hipLaunchKernelGGL(kk_ndf_march2<MODE>, dim3(S.tot), NBLK, 0, ctx().stream, (const MarchB *)S.d_args, (const int *)S.d_start, S.nbox, omega, excl, nrm);
   else hipLaunchKernelGGL(kk_ndf_march<MODE>, dim3(S.tot), NBLK, 0, ctx().stream, (const MarchB *)S.d_args, (const int *)S.d_start, S.nbox, omega, excl, nrm);
 }
 
@@ -2349,7 +2336,7 @@ void mlnd_kept_purge(unsigned long uid) {
 }
 // mode 0: slaves of level n <- P phi_{n-1};  mode 1: dst_n += P src_{n-1};  mode 2: dst_n = P src_{n-1} (dst zeroed first by the caller)
 static void ml_nd_prolong(MLND &S, int n, vdn_multifab *dst, vdn_multifab *src, int mode) {
-  const bool faces_only = ndm_iface_faces_on();
+  const bool faces_only = sw().ndm_iface_faces;
   const auto key = std::make_tuple(n, (const void *)dst, (const void *)src, mode == 0 ? 0 : 1);
   auto hit = S.pro.find(key);
   if (hit != S.pro.end()) { hit->second.Cv.refresh(); hit->second.s.run(mode, (double *)nullptr, ctx().stream); hit->second.s8.run(mode, (double *)nullptr, ctx().stream); return; }
@@ -2365,7 +2352,7 @@ static void ml_nd_prolong(MLND &S, int n, vdn_multifab *dst, vdn_multifab *src, 
     if (itk != g_ndpro_kept.end()) { PS.s = itk->second->s; PS.s8 = itk->second->s8; PS.s.run(mode, (double *)nullptr, ctx().stream); PS.s8.run(mode, (double *)nullptr, ctx().stream); return; }
     kept = new NdProKept; kept->uid = S.la->uid;     // (the table is bounded at the entry of ml_nd_solve: sets already bound to this solve must not be freed here)
   }
-  const bool by_parent = ndm_prolong8_on();
+  const bool by_parent = sw().ndm_prolong8;
   std::vector<NdmProlongB> v; std::vector<NdmProlong8B> v8;
   const BoxBins cb(Cv.vbox, &Cv.have);
   for (size_t f = 0; f < S.A[n].size(); f++) {
@@ -2616,7 +2603,7 @@ static int ml_nd_solve(MlNdRequest &rq) {
   for (int d = 0; d < 3; d++) for (int s = 0; s < 2; s++) ebc0[d][s] = bct->ell_bc(0, 0, d, s, press_comp0);
   int it = 0; bool conv = (bnorm == 0.0); double rn = 0.0;
   NdKeep coarse_keep;                        // the level-0 multigrid hierarchy is built once for all FAC iterations
-  const bool neg_copy = ndm_neg_copy();
+  const bool neg_copy = sw().ndm_neg;
   while (!conv) {
     rn = ml_nd_residual(S);
     if (mg_converged(rn, bnorm, rq.rel_eps, rq.abs_eps)) { conv = true; break; }

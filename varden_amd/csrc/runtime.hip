@@ -26,14 +26,13 @@ void vdn_fail(const char *fmt, ...) {
 
 // also drops the pointers advance_timestep keeps INTO the arena (limited slopes of uold, max |umac|): a step that ended in an exception
 // (solver_check throws by default) must not leave them dangling for the next stand-alone vdn_k_mkflux / vdn_k_velpred
-static bool arena_poison() { static const bool p = env_set("VDN_ARENA_POISON"); return p; }
 // the descriptors of arena temporaries (mf_temp) that nobody freed: they die with the arena contents they describe
 static std::vector<vdn_multifab *> g_temp_mfs;
 void arena_reset() {
   dbg_sync(16);
   for (vdn_multifab *m : g_temp_mfs) delete m;
   g_temp_mfs.clear();
-  if (arena_poison() && g_ctx.arena && g_ctx.arena_peak > 0) HIPCHK(hipMemsetAsync(g_ctx.arena, 0xFF, std::min(g_ctx.arena_peak + (size_t)(64 << 20), g_ctx.arena_bytes), g_ctx.stream));
+  if (sw().arena_poison && g_ctx.arena && g_ctx.arena_peak > 0) HIPCHK(hipMemsetAsync(g_ctx.arena, 0xFF, std::min(g_ctx.arena_peak + (size_t)(64 << 20), g_ctx.arena_bytes), g_ctx.stream));
   g_ctx.arena_off = 0;
   g_ctx.drop_step_caches();
 }
@@ -42,9 +41,7 @@ void arena_reset() {
 // sized it up front -- 150 ghosted fields of the layout, 120 GB for the three-level 256^3 hierarchy -- with one hipMalloc, and a regrid that needed more freed it
 // and allocated again: 3-7 SECONDS per hipMalloc beyond some 30 GB on this card (profiles/r06_regrid_cost.txt), every kept descriptor set and graph dropped because
 // the base moved.  Now the base never moves, nothing is guessed, and only what a step touches is backed by memory.
-static size_t env_mb(const char *name, size_t dflt_mb) { const char *e = vdn_env(name); const long v = e ? atol(e) : 0; return (size_t)(v > 0 ? v : (long)dflt_mb) << 20; }
-static size_t arena_chunk() { static const size_t v = env_mb("VDN_ARENA_CHUNK_MB", 1024); return v; }
-#define ARENA_CHUNK arena_chunk()
+#define ARENA_CHUNK sw().arena_chunk
 static std::vector<hipMemGenericAllocationHandle_t> g_arena_chunks;
 static size_t g_arena_va = 0;
 static void arena_map_to(size_t bytes) {                   // c.arena_bytes (= mapped bytes) >= bytes afterwards
@@ -73,7 +70,7 @@ static void arena_map_to(size_t bytes) {                   // c.arena_bytes (= m
     g_arena_chunks.push_back(h);
     // fresh device memory holds whatever its last owner left: a temporary that is read where nobody wrote (a ghost entry multiplied by a zero coefficient ...) would make
     // a run differ from process to process.  Zeros -- or, under VDN_ARENA_POISON, the NaNs that released arena bytes get, so that such a read fails loudly
-    HIPCHK(hipMemsetAsync(c.arena + c.arena_bytes, arena_poison() ? 0xFF : 0x00, ARENA_CHUNK, c.stream));
+    HIPCHK(hipMemsetAsync(c.arena + c.arena_bytes, sw().arena_poison ? 0xFF : 0x00, ARENA_CHUNK, c.stream));
     c.arena_bytes += ARENA_CHUNK;
   }
 }
@@ -92,9 +89,8 @@ static void arena_destroy() {
 // the pool cost the mapping calls, some 10 us each.  Fields below 32 MB are plain hipMalloc blocks (a chunk each would waste the card on the small cases), and so are
 // the fields of a ONE-level layout, which are created once: the one-box 512^3 step runs 3 % slower on chunk-backed fields than on hipMalloc blocks (7 % on 1 GB chunks;
 // a per-field offset into the chunk did not change that: profiles/r06_allocator_ab.txt) -- the boxes of a hierarchy are small and show no difference.
-static size_t field_chunk() { static const size_t v = env_mb("VDN_FIELD_CHUNK_MB", 64); return v; }
-static size_t field_small() { static const size_t v = !env_on("VDN_FIELD_VMM") ? ~(size_t)0 : (size_t)32 << 20; return v; }
-#define FIELD_CHUNK field_chunk()
+static size_t field_small() { return !sw().field_vmm ? ~(size_t)0 : (size_t)32 << 20; }
+#define FIELD_CHUNK sw().field_chunk
 #define FIELD_SMALL field_small()
 struct FieldAlloc { void *va; size_t va_bytes; std::vector<hipMemGenericAllocationHandle_t> chunks; };
 static std::map<void *, FieldAlloc> g_field_allocs;
@@ -143,9 +139,9 @@ void arena_reserve_for(const vdn_layout *) {}
 size_t arena_mark() { return g_ctx.arena_off; }
 // VDN_ARENA_POISON=1 (debugging): whatever is handed back to the arena is overwritten with NaNs (all-ones bytes), so that a kernel which reads
 // an entry nobody wrote -- and only worked because the last tenant of that address left zeros there -- meets a NaN; the norms turn it into a
-// failed solve.  The GPU suite is run once per round this way (tools/r3_poison.sh).
+// failed solve.
 void arena_release(size_t mark) {
-  if (arena_poison() && g_ctx.arena && g_ctx.arena_off > mark) HIPCHK(hipMemsetAsync(g_ctx.arena + mark, 0xFF, g_ctx.arena_off - mark, g_ctx.stream));
+  if (sw().arena_poison && g_ctx.arena && g_ctx.arena_off > mark) HIPCHK(hipMemsetAsync(g_ctx.arena + mark, 0xFF, g_ctx.arena_off - mark, g_ctx.stream));
   g_ctx.arena_off = mark;
 }
 void *arena_alloc(size_t bytes) {
@@ -178,7 +174,7 @@ void prof_load() {
   static bool tried = false;
   if (tried) return;
   tried = true;
-  if (vdn_env("VDN_NO_ROCTX")) return;
+  if (sw().no_roctx) return;
   for (const char *n : { "librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so" }) {
     void *h = dlopen(n, RTLD_NOW | RTLD_LOCAL);
     if (!h) continue;
@@ -192,91 +188,17 @@ Prof::Prof(const char *name) : on(g_roctx_push != nullptr) { if (on) g_roctx_pus
 Prof::~Prof() { if (on) g_roctx_pop(); }
 
 // ---- debug / measurement switches ------------------------------------------------------------------------------------------------
-// Every environment variable the library reads, with what it does.  None changes a result: they select between launch forms that the tests hold bit-for-bit
-// equal (tests/test_projection_gpu.py::test_multigrid_launch_variants_agree_bit_for_bit, test_kernels_gpu.py, test_amr_gpu.py) or are probes.  vdn_env() is the
-// only way the library reads the environment: a name missing from this table fails the call, and vdn_init warns about VDN_* variables it does not know
+// vdn_switches.h declares them, once each; the struct is filled here on first use, and vdn_init warns about VDN_* variables the table does not know
 // (a misspelt switch would otherwise be silently ignored).  vdn_debug_switches() hands the table out (include/varden_amd.h).
-struct EnvSwitch { const char *name, *doc; };
-static const EnvSwitch g_switches[] = {
-  { "VDN_TESTING", "1: allows VDN_RCCL_LIB (the test transport of tests/fake_rccl); nothing else" },
-  { "VDN_RCCL_LIB", "path of a library that stands in for librccl -- honoured only with VDN_TESTING=1 and the test double's handshake" },
-  { "VDN_FORCE_PACKED", "1: box-to-box copies of one rank go through the packed per-peer buffers (device memcpy for send/recv); 2: through a 1-rank RCCL communicator (one-GPU rehearsal of the N > 1 transport)" },
-  { "VDN_ARENA_POISON", "1: every byte handed back to the arena is overwritten with NaNs (a read of an entry nobody wrote fails the next solve)" },
-  { "VDN_ARENA_CHUNK_MB", "size of the physical chunks mapped into the arena's address range (default 1024)" },
-  { "VDN_FIELD_CHUNK_MB", "size of the pooled physical chunks behind the state fields (default 64)" },
-  { "VDN_FIELD_VMM", "0: every state field is one hipMalloc block (rounds 1-5) instead of pooled chunks mapped into its own address range" },
-  { "VDN_MLCC_TRACE", "1: the composite cell-centred solve prints its residual at every FAC iteration (stderr)" },
-  { "VDN_KEEP_OFF", "mask of kept-descriptor families rebuilt at every call: 1 generic sets, 2 create_umac_grown, 4 composite cell-centred solve, 8 nodal prolongation" },
-  { "VDN_SYNC_POINTS", "mask of points that synchronise the device (race hunting): 1 after every batched launch, 2 after every staged upload, 4 after every exchange, 8 before a scalar read-back, 16 at arena_reset, 32 after launch_cells" },
-  { "VDN_PHASE_HASH", "1: advance_timestep prints a checksum of its fields at every phase boundary (stderr)" },
-  { "VDN_NO_ROCTX", "do not bind the roctx library (no bl_prof ranges)" },
-  { "VDN_POLL", "scalar read-back: 1 spin on the pinned sequence number, 0 hipStreamSynchronize; default: spin on one rank, synchronise on several" },
-  { "VDN_NO_GRAPHS", "launch every multigrid cycle eagerly instead of replaying its hipGraph" },
-  { "VDN_NO_SLOPE_CACHE", "velocity mkflux recomputes the slopes of uold that velpred computed in the same step" },
-  { "VDN_NO_FORCE_REUSE", "1: every forcing term is computed where the reference computes it (advance_premac AND velocity_advance, ...)" },
-  { "VDN_SLOPES_MARCH", "0: the per-cell slopes kernel instead of the k-marching one" },
-  { "VDN_GODUNOV_BATCH", "1: the descriptor (box-batched) Godunov kernels also on a level of one box" },
-  { "VDN_GODUNOV_PLAIN", "the face-centred one-thread-per-cell Godunov kernels of round 1 (the fused marches' bit-for-bit reference, and their fallback where they refuse the field layouts)" },
-  { "VDN_GOD_SEGW", "0: the box-batched fused Godunov marches use full-width (64 x 8) tiles for every box" },
-  { "VDN_GOD_P2", "0: the fused marches divide by dx also where every dx is a power of two (default there: scale by 1/dx, the same doubles)" },
-  { "VDN_FUSED_KCHUNKS", "k-chunks of the fused marches (default: the count that fills the last round of workgroups best)" },
-  { "VDN_GOD_UPDATE", "0: update_3d as its own pass instead of inside the fused mkflux march" },
-  { "VDN_GSRB_PAIR", "0: one cell per thread in the colour passes / residuals of wide levels instead of the 2 x 2 pair form" },
-  { "VDN_MAC_SPLIT", "0: the finest level of macproject's one-level solve stays interleaved (kk_cc_gsrb_rho_pair) instead of stored by colour (kk_cc_gsrb_rho_split)" },
-  { "VDN_MAC_SPLIT_MIN", "fewest cells (of this rank's boxes together) of a level stored by colour (default 2^23)" },
-  { "VDN_ND_REV", "0: every march of a nodal level walks its tiles in the same order (default: consecutive marches alternate)" },
-  { "VDN_MAC_SLAB", "planes per slab of the time-skewed schedule of the split level's passes (cc_split_run; default: ~200 MB of pass traffic, at most half the level); 0: whole-level launches" },
-  { "VDN_MAC_UMAX", "0: max |umac| by its own pass (kk_macmax) instead of inside macproject's velocity update (kk_mkumac_rho_max)" },
-  { "VDN_MAC_KFLIP", "0: both colour passes of a sweep walk the planes upwards (default: the second colour downwards; paired and split passes of the cell-centred multigrid)" },
-  { "VDN_CC_HALO_FACES", "0: the cell-centred multigrid exchanges the whole ghost shell instead of the faces only" },
-  { "VDN_OVERLAP", "halo exchange of multigrid passes next to interior work: 1 always, 0 never, default: when a plan has a remote peer and the box is large" },
-  { "VDN_MG_AGGLOM", "box width below which a multi-box multigrid level is gathered into one box (default: 64 across ranks, 128 where every box is this rank's)" },
-  { "VDN_MG_RESTRICT_FUSED", "0: cell-centred residual and restriction as two passes" },
-  { "VDN_MG_TAILCYCLE", "0: the smallest levels launch by launch instead of one single-workgroup cycle" },
-  { "VDN_MG_PROLONG_FUSED", "0: cell-centred prolongation as its own pass instead of inside the first post-smoothing colour pass" },
-  { "VDN_MG_LDS", "0: the 16^3..64^3 cell-centred levels launch by launch instead of the LDS-tiled down / up kernels" },
-  { "VDN_MAC_STORED_BETA", "1: the finest MAC level reads stored face coefficients instead of recomputing them from rho" },
-  { "VDN_MAC_FAST", "0: macproject with its rh / phi / beta multifabs as the reference has them" },
-  { "VDN_HG_FAST", "0: hgproject with its rh / phi / coeffs multifabs as the reference has them" },
-  { "VDN_ND_PAIR", "0: one node per lane in the nodal march instead of the pair form" },
-  { "VDN_ND_LEAN", "0: whole-array zero fills of the big nodal levels instead of shell-only" },
-  { "VDN_ND_RESTRICT_FUSED", "0: nodal residual and full weighting as two passes" },
-  { "VDN_ND_PROLONG_FUSED", "0: nodal prolongation as a pass of its own instead of inside the first post-smoothing march" },
-  { "VDN_NDF_PAIR", "0: one node per lane in the box-batched nodal march of the composite solve" },
-  { "VDN_NDM_IFACE_FACES", "0: interface interpolation of the composite nodal solve over whole boxes instead of box faces" },
-  { "VDN_NDM_PROLONG8", "0: correction interpolation with a thread per fine node instead of per coarse node" },
-  { "VDN_NDM_NEG", "1: the composite nodal solve copies -res into the correction's right-hand side instead of loading it directly" },
-  { "VDN_FB_FACES", "0: the ghost exchanges of the composite cell-centred solve fill edges and corners too" },
-  { "VDN_MLCC_RHO", "0: the composite MAC solve reads stored face coefficients on its finest level too" },
-  { "VDN_GOD_NARROW", "0: the remainder tile column of the fused mkflux + update march in full 64-lane tiles instead of narrow segments (kk_mk_F_mn)" },
-  { "VDN_KEEP_SETS", "0: the descriptor arrays of the inter-level operators and composite solves are rebuilt and uploaded at every call" },
-  { "VDN_KEPT_BOUND", "n > 0: the kept descriptor tables hold at most n entries each (default 4096 / 64 / 512): the eviction paths in a test" },
-  { "VDN_MLCC_GLUE", "0: the level-0 correction of the composite MAC solve stored and added in separate passes" },
-  { "VDN_MLCC_FUSE1", "0: the composite MAC solve's finest-level residual and first colour pass as two launches" },
-  { "VDN_BATCH_YZ", "0: no (j,k) / (i,k) tiles for thin ranges in the box-batched kernels" },
-  { "VDN_BATCH_PPW", "planes per workgroup of the light box-batched kernels (default 8)" },
-  { "VDN_BATCH_FLAT", "0: no flattened (i,j) plane mapping for badly filling tiles" },
-  { "VDN_BATCH_CHUNK", "0: box-batched workgroups take strided instead of contiguous plane chunks" }
-};
-// Round 6: the switches exist in the TESTING build only (libvarden_amd_testing.so: -DVDN_TESTING_BUILD on this file and exchange.hip; the suite, the A/B tools and
-// the one-GPU transport rehearsal load it -- VDN_LIB_FLAVOUR=testing in the Python mirror).  The shipped libvarden_amd.so reads NO environment variable: every launch
-// form is the default one, every choice that matters is a field of vdn_params; vdn_init says so once if VDN_* switches are set.
+static Switches g_sw;
+const Switches &sw() { static const bool filled = (switches_read(g_sw), true); (void)filled; return g_sw; }
+const Switches &sw_live() { sw(); switches_read(g_sw, true); return g_sw; }
 extern "C" const char *vdn_build_flavour(void) {
 #ifdef VDN_TESTING_BUILD
   return "testing";
 #else
   return "release";
 #endif
-}
-const char *vdn_env(const char *name) {
-  for (const EnvSwitch &e : g_switches) if (!strcmp(e.name, name)) {
-#ifdef VDN_TESTING_BUILD
-    return getenv(name);
-#else
-    return nullptr;
-#endif
-  }
-  vdn_fail("internal: the switch %s is not declared in the table of runtime.hip", name);
 }
 extern char **environ;
 static void env_warn_unknown() {
@@ -288,7 +210,7 @@ static void env_warn_unknown() {
     const char *eq = strchr(*e, '=');
     const size_t len = eq ? (size_t)(eq - *e) : strlen(*e);
     bool known = false;
-    for (const EnvSwitch &s : g_switches) if (strlen(s.name) == len && !strncmp(s.name, *e, len)) known = true;
+    for (const SwitchInfo &s : switch_table) if (strlen(s.name) == len && !strncmp(s.name, *e, len)) known = true;
     if (!strncmp(*e, "VDN_LIB_FLAVOUR", 15)) continue;                  // (read by the Python mirror: which of the two libraries to load)
     if (!known) fprintf(stderr, "varden_amd: warning: environment variable %.*s is not a switch of this library (vdn_debug_switches lists them)\n", (int)len, *e);
 #ifndef VDN_TESTING_BUILD
@@ -306,7 +228,7 @@ extern "C" const char *vdn_debug_switches(void) {
 #ifndef VDN_TESTING_BUILD
   if (out.empty()) out = "release build: the switches below are compiled out, every launch form is the default one (libvarden_amd_testing.so reads them)\n";
 #endif
-  if (out.find("VDN_TESTING ") == std::string::npos) for (const EnvSwitch &s : g_switches) { const char *v = getenv(s.name); out += s.name; out += v ? std::string(" = ") + v : std::string(" (unset)"); out += ": "; out += s.doc; out += "\n"; }
+  if (out.find(std::string(switch_table[0].name) + " ") == std::string::npos) for (const SwitchInfo &s : switch_table) { const char *v = switch_raw(s); out += s.name; out += v ? std::string(" = ") + v : std::string(" (unset)"); out += ": "; out += s.doc; out += "\n"; }
   return out.c_str();
 }
 
@@ -327,8 +249,7 @@ const double *read_scalars(const double *dev, int n) {
   static unsigned long long seq = 0;
   // VDN_POLL: 1 = spin, 0 = synchronise always; unset: spin on a one-rank run, synchronise when several ranks run (each rank's spinning thread would
   // take a core from RCCL's proxy threads and from the other ranks of an oversubscribed host)
-  static const int poll_env = env_int("VDN_POLL", -1);
-  const bool poll = poll_env >= 0 ? poll_env != 0 : c.nranks == 1;
+  const bool poll = sw().poll >= 0 ? sw().poll != 0 : c.nranks == 1;
   ++seq;
   dbg_sync(8);
   hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, c.stream, c.h_scal_dev, dev, n, seq);
@@ -378,8 +299,7 @@ static std::map<unsigned long long, hipGraphExec_t> g_graphs;
 static bool g_capturing = false;
 bool g_capturing_now() { return g_capturing; }
 bool graphs_enabled() {
-  static const bool off = vdn_env("VDN_NO_GRAPHS") != nullptr;
-  return !off && !comm_active() && g_ctx.stream != 0 && !g_capturing;
+  return !sw().no_graphs && !comm_active() && g_ctx.stream != 0 && !g_capturing;
 }
 // `generation` counts the clears: solvers that keep host state next to a graph (mg_nd.hip: the ping-pong state a cycle leaves behind)
 // drop it when the generation has moved on
@@ -711,8 +631,7 @@ vdn_multifab *mf_temp(const vdn_layout *la, int lev, int nc, int ng, int face_di
   mf->base = (double *)arena_alloc(mf->bytes);
   for (auto &f : mf->fabs) f.p = (double *)((char *)mf->base + (uintptr_t)f.p);
   {   // (VDN_PHASE_HASH: every temporary starts from zeros, so that entries nobody writes -- and nobody reads -- do not differ from process to process in the checksums)
-    static const bool clr = env_set("VDN_PHASE_HASH");
-    if (clr) HIPCHK(hipMemsetAsync(mf->base, 0, mf->bytes, g_ctx.stream));
+    if (sw().phase_hash) HIPCHK(hipMemsetAsync(mf->base, 0, mf->bytes, g_ctx.stream));
   }
   if (fill) mf_setval(mf, val, 0, nc, true);
   g_temp_mfs.push_back(mf);
@@ -726,10 +645,9 @@ void mf_temp_free(vdn_multifab *mf) {
 
 // descriptor sets kept across calls (vdn_internal.h)
 static std::map<unsigned long long, KeptSet> g_kept;
-bool kept_sets_enabled() { static const bool on = env_on("VDN_KEEP_SETS"); return on; }
 // VDN_KEEP_OFF: a mask of families switched off one by one (1 the generic launch_batched_kept sets, 2 create_umac_grown, 4 the composite cell-centred solve, 8 the nodal prolongation)
-void dbg_sync(int bit) { static const int m = env_int("VDN_SYNC_POINTS", 0); if (m & bit) HIPCHK(hipDeviceSynchronize()); }
-bool kept_family_enabled(int fam) { static const int off = env_int("VDN_KEEP_OFF", 0); return kept_sets_enabled() && !(off & fam); }
+void dbg_sync(int bit) { if (sw().sync_points & bit) HIPCHK(hipDeviceSynchronize()); }
+bool kept_family_enabled(int fam) { return sw().keep_sets && !(sw().keep_off & fam); }
 KeptSet *kept_find(unsigned long long key) { auto it = g_kept.find(key); return it == g_kept.end() ? nullptr : &it->second; }
 static void kept_free(KeptSet &k) { if (k.d_args) HIPCHK(hipFree(k.d_args)); if (k.d_start) HIPCHK(hipFree(k.d_start)); k.d_args = nullptr; k.d_start = nullptr; }
 static KeeperMem *g_keeper = nullptr;
@@ -756,7 +674,7 @@ void kept_purge(unsigned long uid) {
 }
 // the size bounds of the three tables (plain sets here, the groups of the composite solves in amr.hip / mg_nd.hip); VDN_KEPT_BOUND shrinks them for
 // the eviction test (tests/test_amr_gpu.py)
-int kept_bound(int dflt) { static const int env = env_int("VDN_KEPT_BOUND", 0); return env > 0 ? env : dflt; }
+int kept_bound(int dflt) { return sw().kept_bound > 0 ? sw().kept_bound : dflt; }
 KeptSet *kept_store(unsigned long long key, unsigned long uid, const void *args, size_t arg_bytes, const int *start, int nbox, int tot) {
   // Bounded (temporaries that wander through the arena), rebuilt on demand.  This runs INSIDE the composite solves (launch_batched_kept), whose own
   // groups (MLCCKept, NdProKept) are bound to the running solve: the bound drops the plain entries only -- nobody holds a KeptSet across a store --

@@ -18,6 +18,7 @@
 #include <stdexcept>
 #include <cmath>
 #include "../../include/varden_amd.h"
+#include "vdn_switches.h"
 
 // ---- device-visible views ---------------------------------------------------------------------
 // one fab: p(alo0:, alo1:, alo2:, 0:nc-1), x fastest.  alo = valid lo - ng.
@@ -102,11 +103,9 @@ struct VdnCtx {
 };
 VdnCtx &ctx();
 
-// the one way the library reads its environment: getenv for a name declared in the switch table of runtime.hip (fails for any other name)
-const char *vdn_env(const char *name);
-inline bool env_on(const char *name) { const char *e = vdn_env(name); return !(e && atoi(e) == 0); }           // on unless "0"
-inline bool env_set(const char *name) { const char *e = vdn_env(name); return e && atoi(e) != 0; }            // off unless non-zero
-inline int  env_int(const char *name, int dflt) { const char *e = vdn_env(name); return e ? atoi(e) : dflt; } // an integer with a default
+// the launch-form switches: one field per entry of vdn_switches.h, filled on first use (runtime.hip); sw_live() reads the LIVE entries again
+const Switches &sw();
+const Switches &sw_live();
 // error handling: C-ABI functions wrap their body in VDN_TRY/VDN_CATCH
 void vdn_set_error(const char *fmt, ...);
 struct VdnErr : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -171,7 +170,6 @@ struct GraphKey {
 // pointers, components, ...) and dropped with the layout (xplan_cache_purge) or when the table outgrows its bound.  VDN_KEEP_SETS=0: rebuilt every call.
 struct GraphKey;
 struct KeptSet { void *d_args = nullptr; int *d_start = nullptr; int nbox = 0, tot = 0; unsigned long uid = 0; };
-bool     kept_sets_enabled();
 bool     kept_family_enabled(int fam);
 void     dbg_sync(int bit);          // VDN_SYNC_POINTS (testing build): hipDeviceSynchronize at the points whose bit is set -- the search for a host / device race
 KeptSet *kept_find(unsigned long long key);
