@@ -332,6 +332,28 @@ int vdn_checkpoint_write(const char *dirname, int nlev, vdn_multifab *const *sta
         const int *rr, double time, double dt, long staging_bytes);
 /* the namelist read of checkpoint_read (src/checkpoint.f90:100-112); State and Pressure are then read with vdn_fabio_ml_multifab_info / _boxes / _read_d */
 int vdn_checkpoint_info (const char *dirname, int *nlev, double *time, double *dt, int *rr);
+/* ---- the same files for a 2-D problem that runs as its z-uniform 3-D copy (vdn_set_extruded_2d): dm = 2 files of plane k = 0 ----------
+ * write_plane_d: the arguments of vdn_fabio_ml_multifab_write_d, then comps[ncomp] = the source component of every file component (any order, need not be
+ * contiguous; names[ncomp]); pd0, prob_lo, prob_hi, dx0 give their two in-plane entries.  The file boxes of a level are the (x, y) footprints of the boxes
+ * that contain plane k = 0 (the node plane k = 0 of a multifab nodal in z), in the multifab's box order; those footprints must be pairwise disjoint and every
+ * other box of the level must have exactly one of them, else the call fails naming the level and the box before anything is launched.  The files are what
+ * plotfile.write_ml_multifab(dm = 2) writes for the plane arrays, byte for byte.
+ * defect (NULL: not asked for) receives two figures over everything written: [0] the largest |f(i,j,k) - f(i,j,0)| over the listed components of all boxes,
+ * measured against the plane that goes to the file; [1] the largest |value| over the components vanish[nvanish] (w, gpz), all boxes.  Reported, never judged.
+ * read_plane_d: a dm = 2 file into 3-D multifabs cut along z in any way: every box's footprint must equal exactly one file box (else: level and box named),
+ * the file's nodal flags are the multifab's in-plane ones, the file holds ncomp components; component c of the file goes to EVERY valid z-plane of comps[c]
+ * (nz, or nz + 1 when nodal in z).  Ghost cells and unlisted components are not touched. */
+int vdn_fabio_ml_multifab_write_plane_d(const char *dirname, int nlev, vdn_multifab *const *mfs, const int *rr,
+        const char *const *names, const vdn_box *pd0, const double *prob_lo, const double *prob_hi,
+        double time, const double *dx0, long staging_bytes, int ncomp, const int *comps, int nvanish, const int *vanish, double *defect /*[2]*/);
+int vdn_fabio_ml_multifab_read_plane_d(const char *dirname, int nlev, vdn_multifab *const *mfs, long staging_bytes, int ncomp, const int *comps);
+/* vdn_checkpoint_write through the plane writer: State = comps[ncomp] of state, Pressure = component 0 of pressure (nodal (1,1) in the file), the same Header.
+ * defect: [0] over State and Pressure, [1] over vanish[nvanish] of state */
+int vdn_checkpoint_write_plane(const char *dirname, int nlev, vdn_multifab *const *state, vdn_multifab *const *pressure,
+        const int *rr, double time, double dt, long staging_bytes, int ncomp, const int *comps, int nvanish, const int *vanish, double *defect /*[2]*/);
+/* makevort_2d's rule (src/makevort.f90:93-156: the signed v_x - u_y, one-sided forms over dx next to inflow, slip and no-slip faces) on every plane of a
+ * 3-D copy; the ghost fill of u is vdn_make_vorticity's.  dx: the two in-plane spacings */
+int vdn_make_vorticity_plane(vdn_multifab *vort, int comp, vdn_multifab *u, const double *dx /*[2]*/, const vdn_bc_tower *bct);
 
 /* per-phase wall seconds of the last vdn_advance_timestep (reference prints them,
  * advance_timestep.f90:159-166): [0]=scalar [1]=velocity [2]=MAC [3]=HG [4]=total              */

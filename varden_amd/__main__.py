@@ -1,5 +1,6 @@
-"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D]: the reference executable's command line (src/main.f90
-reads the inputs file named by the first argument and calls varden()).  Plot and checkpoint files go under --outdir."""
+"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D] [--files plane|copy]: the reference executable's command line (src/main.f90
+reads the inputs file named by the first argument and calls varden()).  Plot and checkpoint files go under --outdir; a 2-D hierarchy writes the 2-D run's own
+dm = 2 files (--files copy: those of the 3-D copy it runs as)."""
 import argparse
 import os
 import time
@@ -14,6 +15,7 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="override max_step")
     ap.add_argument("--outdir", default=".")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--files", choices=["plane", "copy"], default="plane", help="files of a 2-D hierarchy: the 2-D run's (plane k = 0, dm = 2) or the 3-D copy's")
     a = ap.parse_args()
     os.makedirs(a.outdir, exist_ok=True)
 
@@ -22,7 +24,7 @@ def main():
                                                                                adv.last_solver_stats("hg")[0]), flush=True)
 
     t0 = time.time()
-    nl, G = inputs.run(open(a.inputs_file).read(), a.steps, report, device=a.device, outdir=a.outdir)
+    nl, G = inputs.run(open(a.inputs_file).read(), a.steps, report, device=a.device, outdir=a.outdir, files=a.files)
     print("Total Run time (s) = %.3f" % (time.time() - t0))
     for f in G.files_written:
         print("wrote", f)

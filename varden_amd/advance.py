@@ -192,6 +192,12 @@ def make_vorticity(vort, comp, u, dx, bct):
     check(capi.load().vdn_make_vorticity(vort.h, comp, u.h, d, bct.h))
 
 
+def make_vorticity_plane(vort, comp, u, dx, bct):
+    """makevort_2d's rule (src/makevort.f90:93-156) on every plane of a z-uniform 3-D copy; dx: the two in-plane spacings"""
+    d = (C.c_double * 3)(*(list(dx[:2]) + [1.0]))
+    check(capi.load().vdn_make_vorticity_plane(vort.h, comp, u.h, d, bct.h))
+
+
 def make_magvel(magvel, comp, u):
     """make_magvel(magvel, comp, u) of src/makevort.f90:59-91"""
     check(capi.load().vdn_make_magvel(magvel.h, comp, u.h))
@@ -261,3 +267,33 @@ def checkpoint_info(dirname):
     nl, t, dt, rr = C.c_int(), C.c_double(), C.c_double(), (C.c_int * 4)()
     check(capi.load().vdn_checkpoint_info(str(dirname).encode(), C.byref(nl), C.byref(t), C.byref(dt), rr))
     return dict(nlevs=nl.value, time=t.value, dt=dt.value, rr=list(rr)[:nl.value - 1])
+
+
+# ---- the same files for a 2-D problem run as its z-uniform 3-D copy: dm = 2 files of plane k = 0 ------------------------------------------
+def _iv(v):
+    return (C.c_int * max(1, len(v)))(*[int(x) for x in v])
+
+
+def fabio_ml_multifab_write_plane_d(dirname, mfs, rr, comps, names=None, pd=None, prob_lo=None, prob_hi=None, time=0.0, dx=None, staging_bytes=0, vanish=(), defect=True):
+    """plane k = 0 of the 3-D multifabs of a z-uniform copy as a dm = 2 hierarchy: file component c = source component comps[c]; the files of
+    plotfile.write_ml_multifab(dm=2) for the plane arrays, byte for byte.  Returns (largest |f(i,j,k) - f(i,j,0)| over the listed components of all
+    boxes, largest |value| of the components `vanish`), or None with defect=False"""
+    nm = None if names is None else (C.c_char_p * len(names))(*[str(n).encode() for n in names])
+    out = (C.c_double * 2)()
+    check(capi.load().vdn_fabio_ml_multifab_write_plane_d(str(dirname).encode(), len(mfs), handle_array(mfs), _rr(rr), nm, None if pd is None else C.byref(_cbox(*pd)),
+                                                          _dv(prob_lo), _dv(prob_hi), float(time), _dv(dx), int(staging_bytes), len(comps), _iv(comps), len(vanish),
+                                                          _iv(vanish), out if defect else None))
+    return (out[0], out[1]) if defect else None
+
+
+def fabio_ml_multifab_read_plane_d(dirname, mfs, comps, staging_bytes=0):
+    """a dm = 2 hierarchy on disk into the 3-D multifabs of a copy (cut along z in any way): file component c to every valid z-plane of comps[c]"""
+    check(capi.load().vdn_fabio_ml_multifab_read_plane_d(str(dirname).encode(), len(mfs), handle_array(mfs), int(staging_bytes), len(comps), _iv(comps)))
+
+
+def checkpoint_write_plane(dirname, state, pressure, rr, time, dt, comps, vanish=(), staging_bytes=0):
+    """checkpoint_write of a z-uniform copy: State = components comps of state, Pressure nodal (1,1); returns the z-uniformity figures of the plane writer"""
+    out = (C.c_double * 2)()
+    check(capi.load().vdn_checkpoint_write_plane(str(dirname).encode(), len(state), handle_array(state), handle_array(pressure), _rr(rr), float(time), float(dt),
+                                                 int(staging_bytes), len(comps), _iv(comps), len(vanish), _iv(vanish), out))
+    return out[0], out[1]

@@ -136,6 +136,11 @@ SIGNATURES = {
     "vdn_fabio_ml_multifab_read_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, C.c_long]),
     "vdn_checkpoint_write": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PVP, _PI, C.c_double, C.c_double, C.c_long]),
     "vdn_checkpoint_info": (C.c_int, [C.c_char_p, _PI, _PD, _PD, _PI]),
+    "vdn_fabio_ml_multifab_write_plane_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PI, C.POINTER(C.c_char_p), C.POINTER(Box), _PD, _PD, C.c_double, _PD, C.c_long,
+                                                      C.c_int, _PI, C.c_int, _PI, _PD]),
+    "vdn_fabio_ml_multifab_read_plane_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, C.c_long, C.c_int, _PI]),
+    "vdn_checkpoint_write_plane": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PVP, _PI, C.c_double, C.c_double, C.c_long, C.c_int, _PI, C.c_int, _PI, _PD]),
+    "vdn_make_vorticity_plane": (C.c_int, [_VP, C.c_int, _VP, C.POINTER(C.c_double), _VP]),
     "vdn_last_step_timing": (C.c_int, [_PD]),
     "vdn_last_solver_stats": (C.c_int, [C.c_int, _PI, _PD, _PD]),
     "vdn_last_bottom_stats": (C.c_int, [C.c_int, _PI, _PI, _PI, _PI]),

@@ -287,18 +287,18 @@ DEVI bool vort_fix2(int p) { return p == VDN_INLET || p == VDN_SLIP_WALL || p ==
 struct vort_K { FV vort, u; VortArgs A;
   __device__ void cell(int i, int j, int k) const {
     if (A.dm == 2) {
-      // makevort_2d (makevort.f90:93-156): one-sided forms over dx (not 3 dx), slip walls included; the y-face loops run last and
+      // makevort_2d (makevort.f90:93-156; k = 0 in a dm = 2 run, every plane of a z-uniform copy for make_vorticity_plane): one-sided forms over dx (not 3 dx), slip walls included; the y-face loops run last and
       // overwrite, so at a corner the x derivative is the centred one
-      double vx = (fv_get(u, i + 1, j, 0, 1) - fv_get(u, i - 1, j, 0, 1)) / (2.0 * A.dx[0]);
-      double uy = (fv_get(u, i, j + 1, 0, 0) - fv_get(u, i, j - 1, 0, 0)) / (2.0 * A.dx[1]);
+      double vx = (fv_get(u, i + 1, j, k, 1) - fv_get(u, i - 1, j, k, 1)) / (2.0 * A.dx[0]);
+      double uy = (fv_get(u, i, j + 1, k, 0) - fv_get(u, i, j - 1, k, 0)) / (2.0 * A.dx[1]);
       const bool ylo = j == A.lo[1] && vort_fix2(A.phys[1][0]), yhi = j == A.hi[1] && vort_fix2(A.phys[1][1]);
       if (!(ylo || yhi)) {
-        if (i == A.lo[0] && vort_fix2(A.phys[0][0])) vx = (fv_get(u, i + 1, j, 0, 1) + 3.0 * fv_get(u, i, j, 0, 1) - 4.0 * fv_get(u, i - 1, j, 0, 1)) / A.dx[0];
-        if (i == A.hi[0] && vort_fix2(A.phys[0][1])) vx = -(fv_get(u, i - 1, j, 0, 1) + 3.0 * fv_get(u, i, j, 0, 1) - 4.0 * fv_get(u, i + 1, j, 0, 1)) / A.dx[0];
+        if (i == A.lo[0] && vort_fix2(A.phys[0][0])) vx = (fv_get(u, i + 1, j, k, 1) + 3.0 * fv_get(u, i, j, k, 1) - 4.0 * fv_get(u, i - 1, j, k, 1)) / A.dx[0];
+        if (i == A.hi[0] && vort_fix2(A.phys[0][1])) vx = -(fv_get(u, i - 1, j, k, 1) + 3.0 * fv_get(u, i, j, k, 1) - 4.0 * fv_get(u, i + 1, j, k, 1)) / A.dx[0];
       }
-      if (ylo) uy = (fv_get(u, i, j + 1, 0, 0) + 3.0 * fv_get(u, i, j, 0, 0) - 4.0 * fv_get(u, i, j - 1, 0, 0)) / A.dx[1];
-      if (yhi) uy = -(fv_get(u, i, j - 1, 0, 0) + 3.0 * fv_get(u, i, j, 0, 0) - 4.0 * fv_get(u, i, j + 1, 0, 0)) / A.dx[1];
-      fv_at(vort, i, j, 0, A.comp) = vx - uy;
+      if (ylo) uy = (fv_get(u, i, j + 1, k, 0) + 3.0 * fv_get(u, i, j, k, 0) - 4.0 * fv_get(u, i, j - 1, k, 0)) / A.dx[1];
+      if (yhi) uy = -(fv_get(u, i, j - 1, k, 0) + 3.0 * fv_get(u, i, j, k, 0) - 4.0 * fv_get(u, i, j + 1, k, 0)) / A.dx[1];
+      fv_at(vort, i, j, k, A.comp) = vx - uy;
       return;
     }
     // makevort_3d (makevort.f90:158-682): faces, edges and corners follow one rule per direction
@@ -322,17 +322,19 @@ struct magvel_K { FV mv, u; int comp, dm;
     fv_at(mv, i, j, k, comp) = sqrt(s);
   } };
 // make_vorticity(vort, comp, u, dx, bc): fills the ghost cells of u (fill_boundary + physbc, makevort.f90:34-38) and writes component comp
-void k_make_vorticity(vdn_multifab *vort, int comp, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct) {
-  const int dm = ctx().prm.dm;
+// plane: makevort_2d's rule on every plane of a 3-D copy (dx: the two in-plane spacings)
+void k_make_vorticity(vdn_multifab *vort, int comp, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct, bool plane = false) {
+  const int dm = ctx().prm.dm, rule = plane ? 2 : dm;
+  REQUIRE(!plane || dm == 3, "make_vorticity_plane: the run is not a 3-D copy (dm = %d)", dm);
   REQUIRE(u->ng >= 1 && u->nc >= dm && comp >= 0 && comp < vort->nc && vort->nfabs() == u->nfabs(), "make_vorticity: operand shapes");
   mf_fill_boundary(u);
   mf_physbc(u, 0, 0, dm, bct, false);
   std::vector<std::pair<vort_K, Range3>> v;
   for (int i = 0; i < u->nfabs(); i++) {
     VortArgs A; Range3 r; BoxP bp = make_boxp(u, i, bct);
-    for (int d = 0; d < 3; d++) { A.lo[d] = r.lo[d] = bp.lo[d]; A.hi[d] = r.hi[d] = bp.hi[d]; A.dx[d] = d < dm ? dx[d] : 1.0;
+    for (int d = 0; d < 3; d++) { A.lo[d] = r.lo[d] = bp.lo[d]; A.hi[d] = r.hi[d] = bp.hi[d]; A.dx[d] = d < rule ? dx[d] : 1.0;
       for (int s = 0; s < 2; s++) A.phys[d][s] = bp.phys[d][s]; }
-    A.comp = comp; A.dm = dm;
+    A.comp = comp; A.dm = rule;
     v.push_back({ vort_K{ vort->fabs[i], u->fabs[i], A }, r });
   }
   launch_cells(v, ctx().stream);
@@ -350,6 +352,9 @@ void k_make_magvel(vdn_multifab *mv, int comp, vdn_multifab *u) {
 }
 extern "C" int vdn_make_vorticity(vdn_multifab *vort, int comp, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct) {
   VDN_TRY REQUIRE(ctx().inited, "vdn_init has not been called"); k_make_vorticity(vort, comp, u, dx, bct); VDN_CATCH
+}
+extern "C" int vdn_make_vorticity_plane(vdn_multifab *vort, int comp, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct) {
+  VDN_TRY REQUIRE(ctx().inited, "vdn_init has not been called"); k_make_vorticity(vort, comp, u, dx, bct, true); VDN_CATCH
 }
 extern "C" int vdn_make_magvel(vdn_multifab *magvel, int comp, vdn_multifab *u) {
   VDN_TRY REQUIRE(ctx().inited, "vdn_init has not been called"); k_make_magvel(magvel, comp, u); VDN_CATCH

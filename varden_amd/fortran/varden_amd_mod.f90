@@ -72,6 +72,7 @@ module varden_amd
   public :: ml_cc_restriction, ml_edge_restriction, multifab_fill_ghost_cells, create_umac_grown, ml_restrict_and_fill
   public :: fillpatch, ml_nodal_prolongation, multifab_copy_layouts, make_new_grids, make_vorticity, make_magvel
   public :: fabio_ml_multifab_write_d, fabio_ml_multifab_info, fabio_ml_multifab_boxes, fabio_ml_multifab_read_d, checkpoint_write, checkpoint_info
+  public :: fabio_ml_multifab_write_plane_d, fabio_ml_multifab_read_plane_d, checkpoint_write_plane, make_vorticity_plane
 
   interface
      subroutine vdn_params_default(p) bind(C, name="vdn_params_default")
@@ -323,6 +324,43 @@ module varden_amd
        character(kind=c_char), intent(in) :: dirname(*)
        integer(c_int), intent(out) :: nlev, rr(*)
        real(c_double), intent(out) :: time, dt
+     end function
+     ! the same files for a 2-D problem run as its z-uniform 3-D copy: plane k = 0 as a dm = 2 hierarchy (include/varden_amd.h)
+     integer(c_int) function vdn_fabio_ml_multifab_write_plane_d(dirname, nlev, mfs, rr, names, pd0, prob_lo, prob_hi, time, dx0, staging_bytes, ncomp, comps, &
+                                                                 nvanish, vanish, defect) bind(C, name="vdn_fabio_ml_multifab_write_plane_d")
+       import :: c_int, c_ptr, c_char, c_double, c_long
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), value :: nlev, ncomp, nvanish
+       type(c_ptr), intent(in) :: mfs(*)
+       integer(c_int), intent(in) :: rr(*), comps(*), vanish(*)
+       type(c_ptr), value :: names, pd0, prob_lo, prob_hi, dx0, defect
+       real(c_double), value :: time
+       integer(c_long), value :: staging_bytes
+     end function
+     integer(c_int) function vdn_fabio_ml_multifab_read_plane_d(dirname, nlev, mfs, staging_bytes, ncomp, comps) bind(C, name="vdn_fabio_ml_multifab_read_plane_d")
+       import :: c_int, c_ptr, c_char, c_long
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), value :: nlev, ncomp
+       type(c_ptr), intent(in) :: mfs(*)
+       integer(c_long), value :: staging_bytes
+       integer(c_int), intent(in) :: comps(*)
+     end function
+     integer(c_int) function vdn_checkpoint_write_plane(dirname, nlev, state, pressure, rr, time, dt, staging_bytes, ncomp, comps, nvanish, vanish, defect) &
+                                                        bind(C, name="vdn_checkpoint_write_plane")
+       import :: c_int, c_ptr, c_char, c_double, c_long
+       character(kind=c_char), intent(in) :: dirname(*)
+       integer(c_int), value :: nlev, ncomp, nvanish
+       type(c_ptr), intent(in) :: state(*), pressure(*)
+       integer(c_int), intent(in) :: rr(*), comps(*), vanish(*)
+       real(c_double), value :: time, dt
+       integer(c_long), value :: staging_bytes
+       real(c_double), intent(out) :: defect(2)
+     end function
+     integer(c_int) function vdn_make_vorticity_plane(vort, comp, u, dx, bct) bind(C, name="vdn_make_vorticity_plane")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: vort, u, bct
+       integer(c_int), value :: comp
+       real(c_double), intent(in) :: dx(*)
      end function
      integer(c_size_t) function c_strlen(s) bind(C, name="strlen")
        import :: c_ptr, c_size_t
@@ -664,6 +702,16 @@ contains
     d = 1.0_c_double; d(1:size(dx)) = dx
     call chk(vdn_make_vorticity(vort%h, int(comp - 1, c_int), u%h, d, the_bc_tower%h), 'make_vorticity')
   end subroutine make_vorticity
+  ! makevort_2d's rule (src/makevort.f90:93-156) on every plane of a z-uniform 3-D copy; dx: the two in-plane spacings
+  subroutine make_vorticity_plane(vort, comp, u, dx, the_bc_tower)
+    type(multifab), intent(inout) :: vort, u
+    integer       , intent(in   ) :: comp
+    real(dp_t)    , intent(in   ) :: dx(:)
+    type(bc_tower), intent(in   ) :: the_bc_tower
+    real(c_double) :: d(3)
+    d = 1.0_c_double; d(1:2) = dx(1:2)
+    call chk(vdn_make_vorticity_plane(vort%h, int(comp - 1, c_int), u%h, d, the_bc_tower%h), 'make_vorticity_plane')
+  end subroutine make_vorticity_plane
   subroutine make_magvel(magvel, comp, u)
     type(multifab), intent(inout) :: magvel, u
     integer       , intent(in   ) :: comp
@@ -705,6 +753,36 @@ contains
     type(vdn_box)   , intent(in), optional :: bounding_box
     real(dp_t)      , intent(in), optional :: prob_lo(:), prob_hi(:), time, dx(:)
     integer(c_long) , intent(in), optional :: staging_bytes
+    call fabio_write_any(mfs, rr, dirname, names, bounding_box, prob_lo, prob_hi, time, dx, staging_bytes)
+  end subroutine fabio_ml_multifab_write_d
+  ! plane k = 0 of the 3-D multifabs of a z-uniform copy as a dm = 2 hierarchy: file component c = component comps(c) (1-based); bounding_box, prob_lo, prob_hi
+  ! and dx give their two in-plane entries.  defect: largest |f(i,j,k) - f(i,j,0)| over the listed components, largest |value| of the components vanish(:)
+  subroutine fabio_ml_multifab_write_plane_d(mfs, rr, dirname, comps, names, bounding_box, prob_lo, prob_hi, time, dx, staging_bytes, vanish, defect)
+    type(multifab)  , intent(in) :: mfs(:)
+    integer         , intent(in) :: rr(:), comps(:)
+    character(len=*), intent(in) :: dirname
+    character(len=*), intent(in), optional :: names(:)
+    type(vdn_box)   , intent(in), optional :: bounding_box
+    real(dp_t)      , intent(in), optional :: prob_lo(:), prob_hi(:), time, dx(:)
+    integer(c_long) , intent(in), optional :: staging_bytes
+    integer         , intent(in), optional :: vanish(:)
+    real(dp_t)      , intent(out), optional :: defect(2)
+    call fabio_write_any(mfs, rr, dirname, names, bounding_box, prob_lo, prob_hi, time, dx, staging_bytes, comps, vanish, defect)
+  end subroutine fabio_ml_multifab_write_plane_d
+  subroutine fabio_write_any(mfs, rr, dirname, names, bounding_box, prob_lo, prob_hi, time, dx, staging_bytes, comps, vanish, defect)
+    type(multifab)  , intent(in) :: mfs(:)
+    integer         , intent(in) :: rr(:)
+    character(len=*), intent(in) :: dirname
+    character(len=*), intent(in), optional :: names(:)
+    type(vdn_box)   , intent(in), optional :: bounding_box
+    real(dp_t)      , intent(in), optional :: prob_lo(:), prob_hi(:), time, dx(:)
+    integer(c_long) , intent(in), optional :: staging_bytes
+    integer         , intent(in), optional :: comps(:), vanish(:)
+    real(dp_t)      , intent(out), optional :: defect(2)
+    integer(c_int), allocatable :: cc(:), vc(:)
+    real(c_double), target :: dfc(2)
+    type(c_ptr) :: a_def
+    integer :: nv
     character(kind=c_char), allocatable, target :: cbuf(:,:)
     type(c_ptr), allocatable, target :: cp(:)
     type(vdn_box), target :: pd
@@ -743,9 +821,21 @@ contains
     end if
     t = 0.d0; if (present(time)) t = time
     sb = 0; if (present(staging_bytes)) sb = staging_bytes
-    call chk(vdn_fabio_ml_multifab_write_d(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), rrc, a_names, a_pd, a_lo, a_hi, t, a_dx, sb), &
-             'fabio_ml_multifab_write_d')
-  end subroutine fabio_ml_multifab_write_d
+    if (.not. present(comps)) then
+       call chk(vdn_fabio_ml_multifab_write_d(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), rrc, a_names, a_pd, a_lo, a_hi, t, a_dx, sb), &
+                'fabio_ml_multifab_write_d')
+       return
+    end if
+    allocate(cc(size(comps))); cc = int(comps - 1, c_int)
+    nv = 0; if (present(vanish)) nv = size(vanish)
+    allocate(vc(max(1, nv))); vc = 0
+    if (nv > 0) vc(1:nv) = int(vanish - 1, c_int)
+    a_def = c_null_ptr; if (present(defect)) a_def = c_loc(dfc(1))
+    call chk(vdn_fabio_ml_multifab_write_plane_d(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), rrc, a_names, a_pd, a_lo, a_hi, t, a_dx, sb, &
+                                                 int(size(comps), c_int), cc, int(nv, c_int), vc, a_def), &
+             'fabio_ml_multifab_write_plane_d')
+    if (present(defect)) defect = dfc
+  end subroutine fabio_write_any
 
   ! what fabio_ml_multifab_read_d learns from the files before it builds its layout (text only: needs no GPU); nboxes(:) and rr(:) hold 4 entries at least
   subroutine fabio_ml_multifab_info(dirname, nlev, dm, ncomp, nodal, nboxes, rr, time)
@@ -778,6 +868,34 @@ contains
     sb = 0; if (present(staging_bytes)) sb = staging_bytes
     call chk(vdn_fabio_ml_multifab_read_d(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), sb), 'fabio_ml_multifab_read_d')
   end subroutine fabio_ml_multifab_read_d
+
+  ! a dm = 2 hierarchy on disk into the 3-D multifabs of a copy (cut along z in any way): file component c to every valid z-plane of comps(c) (1-based)
+  subroutine fabio_ml_multifab_read_plane_d(mfs, dirname, comps, staging_bytes)
+    type(multifab)  , intent(inout) :: mfs(:)
+    character(len=*), intent(in) :: dirname
+    integer         , intent(in) :: comps(:)
+    integer(c_long) , intent(in), optional :: staging_bytes
+    integer(c_long) :: sb
+    integer(c_int) :: cc(size(comps))
+    sb = 0; if (present(staging_bytes)) sb = staging_bytes
+    cc = int(comps - 1, c_int)
+    call chk(vdn_fabio_ml_multifab_read_plane_d(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), sb, int(size(comps), c_int), cc), &
+             'fabio_ml_multifab_read_plane_d')
+  end subroutine fabio_ml_multifab_read_plane_d
+
+  ! checkpoint_write of a z-uniform copy: State = the components comps(:) of mfs, Pressure = mfs_nodal (nodal (1,1) in the file); defect as above
+  subroutine checkpoint_write_plane(dirname, mfs, mfs_nodal, rr, time, dt, comps, vanish, defect)
+    character(len=*), intent(in) :: dirname
+    type(multifab)  , intent(in) :: mfs(:), mfs_nodal(:)
+    integer         , intent(in) :: rr(:), comps(:), vanish(:)
+    real(dp_t)      , intent(in) :: time, dt
+    real(dp_t)      , intent(out) :: defect(2)
+    integer(c_int) :: rrc(max(1, size(rr))), cc(size(comps)), vc(max(1, size(vanish)))
+    rrc = 2; rrc(1:size(rr)) = rr
+    cc = int(comps - 1, c_int); vc = 0; vc(1:size(vanish)) = int(vanish - 1, c_int)
+    call chk(vdn_checkpoint_write_plane(trim(dirname) // c_null_char, int(size(mfs), c_int), handles(mfs), handles(mfs_nodal), rrc, time, dt, 0_c_long, &
+                                        int(size(comps), c_int), cc, int(size(vanish), c_int), vc, defect), 'checkpoint_write_plane')
+  end subroutine checkpoint_write_plane
 
   ! checkpoint_write(nlevs, dirname, mfs, mfs_nodal, rrs, time, dt)   (src/checkpoint.f90:14-83): State, Pressure and the Header namelist
   subroutine checkpoint_write(dirname, mfs, mfs_nodal, rr, time, dt)

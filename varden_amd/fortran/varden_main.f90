@@ -10,7 +10,9 @@
 ! plane, velpred_2d's outlet rule (vdn_set_extruded_2d; DESIGN.md section 13): plane k = 0 is the 2-D answer.  Plot files and checkpoints
 ! (write_plotfile / write_checkfile, varden.f90:492-610) are written by the library (fabio_ml_multifab_write_d, checkpoint_write) at step 0 of a fresh run, after every
 ! plot_int-th / chk_int-th step and once more after the last step (:207-221, 349-361, 374-377); restart = n takes box lists and state from <check_base_name>n and skips
-! the start-up sequence (initialize.f90:22-88, varden.f90:94-97); the files of an extruded copy are the 3-D copy's.  The Python mirror of the same flow (varden_amd/inputs.py: run) sits on the same C-ABI: every step prints
+! the start-up sequence (initialize.f90:22-88, varden.f90:94-97).  An extruded copy writes the 2-D run's own files -- plane k = 0 with dm = 2, the vorticity by
+! makevort_2d's rule (fabio_ml_multifab_write_plane_d, checkpoint_write_plane, make_vorticity_plane) -- and restarts from them: the file's boxes extruded over z and cut by
+! max_grid_size (the rule of plotfile.extrude_boxes), the file's plane on every plane, w = gpz = 0.  The Python mirror of the same flow (varden_amd/inputs.py: run) sits on the same C-ABI: every step prints
 ! time, dt, max|u| and the boxes per level with 17 significant digits and tests/test_fortran_gpu.py compares the two step for step.
 program varden_main
   use iso_c_binding
@@ -55,6 +57,7 @@ program varden_main
   real(dp_t) :: dx(MAXL, 3), dt, dtold, dtlev, time, umax
   type(vdn_box), allocatable :: newb(:)
   integer :: nnew, last_plt = -1, last_chk = -1
+  real(dp_t) :: copy_defect(2) = 0.d0                             ! z-uniformity of an extruded copy as the last plane writer measured it
   logical :: new_grid
 
   if (command_argument_count() < 1) stop 'usage: varden_main <inputs file> [max_step]'
@@ -69,8 +72,6 @@ program varden_main
      call get_command_argument(2, arg); read(arg, *) nsteps_arg
   end if
   if (nsteps_arg >= 0) max_step = nsteps_arg
-  if (dim_in == 2 .and. restart >= 0) &
-       stop "restart of a 2-D hierarchy (an extruded copy, DESIGN section 13): not in this round -- its checkpoint is the 3-D copy's"
   if (dim_in == 2) then                                         ! the z-uniform copy of the 2-D problem (see the header)
      if (prob_hi_x /= 1.d0 .or. abs(prob_hi_y / n_celly - prob_hi_x / n_cellx) > 1.d-15) stop 'varden_main: dim_in = 2: prob_hi_x = 1 and square cells'
      if (prob_type < 1 .or. prob_type > 3) stop 'varden_main: dim_in = 2: prob_type 1 .. 3 (src/initdata.f90:127-185)'
@@ -222,6 +223,7 @@ contains
     character(len=256) :: dir
     type(vdn_box) :: pd
     integer :: l, i, rr(MAXL)
+    integer, allocatable :: comps(:)
     names(1) = 'x_vel'; names(2) = 'y_vel'; names(3) = 'z_vel'; names(dm + 1) = 'density'      ! varden.f90:73-87
     if (nscal > 1) names(dm + 2) = 'tracer'
     do i = 3, nscal
@@ -233,12 +235,24 @@ contains
        call multifab_build(plot(l), H%mla, l, 2 * dm + nscal + 2, 0)
        call multifab_copy_c(plot(l), 1, H%uold(l), 1, dm); call multifab_copy_c(plot(l), dm + 1, H%sold(l), 1, nscal)
        call make_magvel(plot(l), dm + nscal + 1, H%uold(l))
-       call make_vorticity(plot(l), dm + nscal + 2, H%uold(l), dx(l,:), H%bct)
+       if (extruded) then
+          call make_vorticity_plane(plot(l), dm + nscal + 2, H%uold(l), dx(l,1:2), H%bct)
+       else
+          call make_vorticity(plot(l), dm + nscal + 2, H%uold(l), dx(l,:), H%bct)
+       end if
        call multifab_copy_c(plot(l), dm + nscal + 3, H%gp(l), 1, dm)
     end do
     write(dir, '(a,i5.5)') trim(plot_base_name), istep
     pd%lo = 0; pd%hi = nn - 1; rr = 2
-    call fabio_ml_multifab_write_d(plot(1:H%nlev), rr(1:H%nlev - 1), trim(dir), names, pd, (/ 0.d0, 0.d0, 0.d0 /), dx(1,:) * nn, time, dx(1,:))
+    if (extruded) then                                             ! u, v, scalars, magvel, vort, gpx, gpy of plane k = 0; w and gpz stay behind
+       allocate(comps(nscal + 6))
+       comps = (/ 1, 2, (dm + i, i = 1, nscal), dm + nscal + 1, dm + nscal + 2, dm + nscal + 3, dm + nscal + 4 /)
+       pd%hi(3) = 0
+       call fabio_ml_multifab_write_plane_d(plot(1:H%nlev), rr(1:H%nlev - 1), trim(dir), comps, names(comps), pd, (/ 0.d0, 0.d0 /), dx(1,1:2) * nn(1:2), time, dx(1,1:2), &
+                                            vanish=(/ 3, dm + nscal + 5 /), defect=copy_defect)
+    else
+       call fabio_ml_multifab_write_d(plot(1:H%nlev), rr(1:H%nlev - 1), trim(dir), names, pd, (/ 0.d0, 0.d0, 0.d0 /), dx(1,:) * nn, time, dx(1,:))
+    end if
     do l = 1, H%nlev
        call multifab_destroy(plot(l))
     end do
@@ -248,7 +262,7 @@ contains
   subroutine write_checkfile()
     type(multifab) :: st(MAXL)
     character(len=256) :: dir
-    integer :: l, rr(MAXL)
+    integer :: l, i, rr(MAXL)
     do l = 1, H%nlev
        call multifab_build(st(l), H%mla, l, 2 * dm + nscal, 0)
        call multifab_copy_c(st(l), 1, H%uold(l), 1, dm); call multifab_copy_c(st(l), dm + 1, H%sold(l), 1, nscal)
@@ -256,7 +270,12 @@ contains
     end do
     write(dir, '(a,i5.5)') trim(check_base_name), istep
     rr = 2
-    call checkpoint_write(trim(dir), st(1:H%nlev), H%p(1:H%nlev), rr(1:H%nlev - 1), time, dt)
+    if (extruded) then                                             ! State = u, v, scalars, gpx, gpy of plane k = 0
+       call checkpoint_write_plane(trim(dir), st(1:H%nlev), H%p(1:H%nlev), rr(1:H%nlev - 1), time, dt, &
+                                   (/ 1, 2, (dm + i, i = 1, nscal), dm + nscal + 1, dm + nscal + 2 /), (/ 3, 2 * dm + nscal /), copy_defect)
+    else
+       call checkpoint_write(trim(dir), st(1:H%nlev), H%p(1:H%nlev), rr(1:H%nlev - 1), time, dt)
+    end if
     do l = 1, H%nlev
        call multifab_destroy(st(l))
     end do
@@ -273,6 +292,10 @@ contains
     write(dir, '(a,i5.5)') trim(check_base_name), restart
     call checkpoint_info(trim(dir), nl, time, dt, rr)
     call fabio_ml_multifab_info(trim(dir) // '/State', nl, fdm, fnc, nd, nbx, rr, t0)
+    if (extruded) then
+       call restart_copy_from_planes(trim(dir), nl, fdm, fnc, nd, nbx, rr)
+       return
+    end if
     if (fdm /= dm .or. fnc /= 2 * dm + nscal .or. any(nd)) stop 'varden_main: restart: the State of the checkpoint is not (u, s, gp) of this run'
     if (nl > MAXL .or. any(nbx(1:nl) > MAXB) .or. any(rr(1:nl - 1) /= 2)) stop 'varden_main: restart: too many levels or boxes, or a ratio other than 2'
     if (.not. allocated(H%bx)) allocate(H%bx(MAXB, MAXL))
@@ -292,6 +315,54 @@ contains
     end do
     call fabio_ml_multifab_read_d(H%p(1:nl), trim(dir) // '/Pressure')
   end subroutine restart_from_checkpoint
+
+  ! ... of an extruded copy from the 2-D run's checkpoint: every box of the file spans z = 0 .. NZ_EXT 2**(l-1) - 1, cut into the fewest equal chunks no longer than
+  ! max_grid_size, the chunks in ascending z and the file's box order inside a chunk (plotfile.extrude_boxes); the file's plane goes to every plane, w = gpz = 0
+  subroutine restart_copy_from_planes(dir, nl, fdm, fnc, nd, nbx, rr)
+    character(len=*), intent(in) :: dir
+    integer, intent(in) :: nl, fdm, fnc, nbx(MAXL), rr(MAXL)
+    logical, intent(in) :: nd(3)
+    type(multifab) :: st(MAXL)
+    type(vdn_box), allocatable :: fb(:)
+    integer :: l, i, k, q, nz, nchunk, w
+    if (fdm /= 2) stop 'varden_main: restart of a 2-D hierarchy: the checkpoint is not a dm = 2 one (a 3-D copy''s own files are not read back)'
+    if (fnc /= nscal + 4 .or. any(nd)) stop 'varden_main: restart: the State of the checkpoint is not (u, v, s, gpx, gpy) of this run'
+    if (nl > MAXL .or. any(rr(1:nl - 1) /= 2)) stop 'varden_main: restart: too many levels, or a ratio other than 2'
+    if (.not. allocated(H%bx)) allocate(H%bx(MAXB, MAXL))
+    allocate(fb(MAXB))
+    H%nlev = nl; H%nb = 0
+    do l = 1, nl
+       nz = NZ_EXT * 2**(l - 1)
+       nchunk = (nz + mgs - 1) / mgs
+       do while (mod(nz, nchunk) /= 0)
+          nchunk = nchunk + 1
+       end do
+       w = nz / nchunk
+       if (nbx(l) * nchunk > MAXB) stop 'varden_main: restart: too many boxes'
+       call fabio_ml_multifab_boxes(dir // '/State', l, fb(1:nbx(l)))
+       q = 0
+       do k = 0, nchunk - 1
+          do i = 1, nbx(l)
+             q = q + 1
+             H%bx(q, l) = fb(i)
+             H%bx(q, l)%lo(3) = k * w; H%bx(q, l)%hi(3) = (k + 1) * w - 1
+          end do
+       end do
+       H%nb(l) = q
+    end do
+    call alloc_state(H)
+    do l = 1, nl
+       call multifab_build(st(l), H%mla, l, 2 * dm + nscal, 0)
+    end do
+    call fabio_ml_multifab_read_plane_d(st(1:nl), dir // '/State', (/ 1, 2, (dm + i, i = 1, nscal), dm + nscal + 1, dm + nscal + 2 /))
+    do l = 1, nl
+       call setval(H%uold(l), 0.d0, all=.true.); call setval(H%gp(l), 0.d0, all=.true.)
+       call multifab_copy_c(H%uold(l), 1, st(l), 1, 2); call multifab_copy_c(H%sold(l), 1, st(l), dm + 1, nscal)
+       call multifab_copy_c(H%gp(l), 1, st(l), dm + nscal + 1, 2)
+       call multifab_destroy(st(l))
+    end do
+    call fabio_ml_multifab_read_plane_d(H%p(1:nl), dir // '/Pressure', (/ 1 /))
+  end subroutine restart_copy_from_planes
 
   ! fixed_dt and stop_time: varden.f90:196-199 (first step) and :318-326
   real(dp_t) function limit_dt(dtin, first)

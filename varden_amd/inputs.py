@@ -53,9 +53,11 @@ def namelist_params(nl, dm=None):
     return prm
 
 
-def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, extrude_zbc=None):
+def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, extrude_zbc=None, files="plane"):
     """the driver object for an inputs text: Varden (one level) or VardenAMR (max_levs > 1, grids from the tagged initial data);
-    restart >= 0: grids and state from the checkpoint <outdir>/<check_base_name><restart:05d> (src/varden.f90:94-97)"""
+    restart >= 0: grids and state from the checkpoint <outdir>/<check_base_name><restart:05d> (src/varden.f90:94-97).
+    files: what a 2-D hierarchy (run as its z-uniform 3-D copy) writes and restarts from -- "plane": the 2-D run's own dm = 2 files, "copy": the 3-D copy's"""
+    assert files in ("plane", "copy"), files
     nl = dict(DEFAULTS)
     nl.update(parse_namelist(text))
     dm = int(nl["dim_in"])
@@ -74,18 +76,43 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
                   init_iter=int(nl["init_iter"]), do_initial_projection=int(nl["do_initial_projection"]), device=device,
                   fixed_dt=float(nl["fixed_dt"]), stop_time=float(nl["stop_time"]))
     decomp = tuple(max(1, -(-n[d] // mgs)) for d in range(dm)) + (1,) * (3 - dm)
+
+    def copy_of_2d(boxes2d, **kw):
+        """a 2-D hierarchy on the box lists of a dm = 2 checkpoint or grids file, as the z-uniform copy: plotfile.extrude_boxes, extrude_nz << n cells along z on level n"""
+        if prob_hi[0] != 1.0 or abs(prob_hi[1] / n[1] - prob_hi[0] / n[0]) > 1e-15:
+            raise NotImplementedError("2-D hierarchies: prob_hi_x = 1 and square cells")
+        b3 = [plotfile.extrude_boxes(b, int(extrude_nz) << lev, mgs) for lev, b in enumerate(boxes2d)]
+        G = VardenAMR(n, b3[1], phys, params=params_of_copy(), finer_levels=b3[2:], base_boxes=b3[0], regrid_int=int(nl["regrid_int"]), amr_buf_width=abw,
+                      max_levs=max(int(nl["max_levs"]), len(b3)), max_grid_size=mgs, extrude2d=int(extrude_nz), extrude_zbc=extrude_zbc, **common, **kw)
+        G.files_copy = files == "copy"
+        return G
+
+    def params_of_copy():
+        prm3 = namelist_params(nl, dm=3)
+        for name in ("u_bc", "v_bc", "rho_bc", "trac_bc"):
+            for d in range(2):
+                for sd in range(2):
+                    getattr(prm3, name)[d][sd] = getattr(prm, name)[d][sd]
+        return prm3
     if int(nl["restart"]) >= 0:
         chk = plotfile.read_checkfile(os.path.join(outdir, "%s%05d" % (nl["check_base_name"], int(nl["restart"]))))
         rs = dict(restart=chk, restart_step=int(nl["restart"]))
         if chk["nlevs"] == 1:
             return nl, Varden(n, phys, prm, prob_hi=prob_hi, decomp=decomp, **common, **rs)
         if dm == 2:
-            raise NotImplementedError("restart of a 2-D hierarchy (an extruded copy, DESIGN section 13): not in this round -- its checkpoint is the 3-D copy's")
+            if chk["dm"] != 2:
+                raise NotImplementedError("restart of a 2-D hierarchy from %s: that checkpoint is a 3-D copy's (dm = %d, written with files=\"copy\"); only dm = 2 "
+                                          "checkpoints are read back" % (chk["name"], chk["dm"]))
+            return nl, copy_of_2d(chk["boxes"], **rs)
         return nl, VardenAMR(n[0], chk["boxes"][1], phys, params=prm, finer_levels=chk["boxes"][2:], base_boxes=chk["boxes"][0],
                              regrid_int=int(nl["regrid_int"]), amr_buf_width=abw, max_levs=int(nl["max_levs"]), max_grid_size=mgs, **common, **rs)
     if nl["fixed_grids"]:                                   # initialize_with_fixed_grids, src/initialize.f90:93-150
-        if dm == 2:
-            raise NotImplementedError("fixed_grids with dim_in = 2: not in this round (adaptive 2-D hierarchies run as extruded copies)")
+        if dm == 2:                                         # (a grids file of write_grids: the footprints, dm = 2)
+            domains, boxes = plotfile.read_grids(os.path.join(outdir, str(nl["fixed_grids"])))
+            assert domains[0] == ((0, 0, 0), (n[0] - 1, n[1] - 1, 0)), "fixed_grids: level-0 domain differs from n_cell"
+            if len(boxes) == 1:
+                raise NotImplementedError("fixed_grids with one level: use max_grid_size")
+            return nl, copy_of_2d(boxes)
         if dm != 3 or len(set(n)) != 1 or any(p != 1.0 for p in prob_hi):
             raise NotImplementedError("hierarchies: 3-D, cubic unit domain in this round")
         domains, boxes = plotfile.read_grids(os.path.join(outdir, str(nl["fixed_grids"])))
@@ -98,15 +125,11 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
         return nl, Varden(n, phys, prm, prob_hi=prob_hi, decomp=decomp, **common)
     if dm == 2:
         # the 2-D inputs of exec/test (all four adaptive): the hierarchy runs as the z-uniform, z-periodic 3-D copy of the problem (driver.VardenAMR: extrude2d) --
-        # plane k = 0 of every field is the 2-D answer, plot files are those of the 3-D copy
+        # plane k = 0 of every field is the 2-D answer and what the plot files and checkpoints hold (plotfile.py; files="copy": the 3-D copy's own files)
         if prob_hi[0] != 1.0 or abs(prob_hi[1] / n[1] - prob_hi[0] / n[0]) > 1e-15:
             raise NotImplementedError("2-D hierarchies: prob_hi_x = 1 and square cells")
         nz = int(extrude_nz)                                  # cells of level 0 along the periodic z of the copy (a multiple of the blocking factor)
-        prm3 = namelist_params(nl, dm=3)
-        for name in ("u_bc", "v_bc", "rho_bc", "trac_bc"):
-            for d in range(2):
-                for sd in range(2):
-                    getattr(prm3, name)[d][sd] = getattr(prm, name)[d][sd]
+        prm3 = params_of_copy()
         base = None
         if any(dc > 1 for dc in decomp[:2]) or nz > mgs:
             bs = [n[0] // decomp[0], n[1] // decomp[1], min(nz, mgs)]
@@ -116,8 +139,10 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
                                         base_boxes=base, extrude2d=nz)
         if not levels:
             return nl, Varden(n, phys, prm, prob_hi=prob_hi, decomp=decomp, **common)
-        return nl, VardenAMR(n, levels[0], phys, params=prm3, finer_levels=levels[1:], regrid_int=int(nl["regrid_int"]), amr_buf_width=abw,
-                             max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, extrude2d=nz, extrude_zbc=extrude_zbc, **common)
+        G = VardenAMR(n, levels[0], phys, params=prm3, finer_levels=levels[1:], regrid_int=int(nl["regrid_int"]), amr_buf_width=abw,
+                      max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, extrude2d=nz, extrude_zbc=extrude_zbc, **common)
+        G.files_copy = files == "copy"
+        return nl, G
     if len(set(n)) != 1 or any(p != 1.0 for p in prob_hi):
         raise NotImplementedError("adaptive hierarchies: cubic unit domain in this round")
     # level 0 is cut by max_grid_size like every other level (boxarray_maxsize, src/initialize.f90:204-206)
@@ -134,10 +159,10 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
                          max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, **common)
 
 
-def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16):
+def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane"):
     """the time loop of src/varden.f90:237-371 for max_step steps (or until stop_time); plot / checkpoint files at step 0 of a fresh
     run and after every plot_int-th / chk_int-th step (:207-221, :349-361) under outdir"""
-    nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz)
+    nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz, files=files)
     max_step = int(nl["max_step"]) if nsteps is None else nsteps
     stop_time = float(nl["stop_time"])
     plot_int, chk_int = int(nl["plot_int"]), int(nl["chk_int"])

@@ -17,7 +17,12 @@ shared file system.
 
 One rank: write_plotfile and write_checkfile hand their multifabs to the library (vdn_fabio_ml_multifab_write_d, vdn_checkpoint_write:
 csrc/fabio.hip), which packs the valid points on the device and writes the very same files; write_ml_multifab / _write_level stay the
-definition of the format, the several-rank path and what the tests hold the library's files against."""
+definition of the format, the several-rank path and what the tests hold the library's files against.
+
+A 2-D hierarchy runs as its z-uniform 3-D copy (driver.VardenAMR: extrude2d).  Its files are the 2-D run's: plane k = 0 written with dm = 2 by the library's plane
+writer (vdn_fabio_ml_multifab_write_plane_d, vdn_checkpoint_write_plane), the vorticity by makevort_2d's rule (vdn_make_vorticity_plane); `footprints` maps the copy's
+boxes to the file's, `extrude_boxes` rebuilds a copy's boxes from a file's, load_restart spreads the file's plane over every plane (vdn_fabio_ml_multifab_read_plane_d).
+sim.files_copy = True keeps the 3-D copy's own files."""
 import os
 import re
 
@@ -228,6 +233,73 @@ def plot_names(dm, nscal):
     return names + ["magvel", "vort", "gpx", "gpy"] + (["gpz"] if dm > 2 else [])
 
 
+def footprints(boxes3d):
+    """the dm = 2 file boxes of one level of a z-uniform copy: the (x, y) footprints of the boxes that hold plane k = 0, in list order, padded with 0 in z as
+    read_ml_multifab pads a dm = 2 file's; and for every 3-D box the index of its file box.  Those footprints must be pairwise disjoint and every other box must
+    have exactly one of them (the rule of vdn_fabio_ml_multifab_write_plane_d); ValueError otherwise"""
+    fp = lambda b: ((int(b[0][0]), int(b[0][1]), 0), (int(b[1][0]), int(b[1][1]), 0))   # noqa: E731
+    boxes2d = [fp(b) for b in boxes3d if b[0][2] <= 0 <= b[1][2]]
+    for g, a in enumerate(boxes2d):
+        for h in range(g):
+            b = boxes2d[h]
+            if not (a[0][0] > b[1][0] or b[0][0] > a[1][0] or a[0][1] > b[1][1] or b[0][1] > a[1][1]):
+                raise ValueError("footprints: %s and %s overlap and both hold plane k = 0" % (a, b))
+    where = {b: g for g, b in enumerate(boxes2d)}
+    index = []
+    for i, b in enumerate(boxes3d):
+        if fp(b) not in where:
+            raise ValueError("footprints: box %d, %s: its footprint is not that of any box that holds plane k = 0" % (i, (tuple(b[0]), tuple(b[1]))))
+        index.append(where[fp(b)])
+    return boxes2d, index
+
+
+def extrude_boxes(boxes2d, nz_level, max_grid_size):
+    """3-D boxes of a z-uniform copy from the boxes of a dm = 2 file: every footprint spans [0, nz_level), cut into the fewest equal chunks no longer than
+    max_grid_size; the chunks in ascending z, the file's box order inside a chunk -- so that footprints(extrude_boxes(b, ...))[0] == b.  (A layout takes no box
+    narrower than 4 cells: nz_level is a multiple of the blocking factor in practice.)"""
+    nz, mgs = int(nz_level), int(max_grid_size)
+    assert nz >= 1 and mgs >= 1
+    nchunk = -(-nz // mgs)
+    while nz % nchunk:
+        nchunk += 1
+    w = nz // nchunk
+    return [((int(lo[0]), int(lo[1]), k * w), (int(hi[0]), int(hi[1]), (k + 1) * w - 1)) for k in range(nchunk) for lo, hi in boxes2d]
+
+
+def _plane_files(sim):
+    """the sim is the z-uniform copy of a 2-D problem and writes that problem's files (one rank: the library's I/O; several ranks keep the copy's own files)"""
+    return bool(getattr(sim, "extrude2d", None)) and not getattr(sim, "files_copy", False) and getattr(sim, "nranks", 1) == 1
+
+
+def _plane_domain(sim):
+    return ((0, 0, 0), (int(sim.ncs[0]) - 1, int(sim.ncs[1]) - 1, 0))
+
+
+def _write_plane_plotfile(sim, name, prob_lo, prob_hi):
+    """write_plotfile of a 2-D hierarchy run as its copy: u, v, scalars, magvel, vort (makevort_2d's rule), gpx, gpy of plane k = 0, dm = 2"""
+    ns, nl = sim.nscal, len(sim.boxes)
+    pd = _plane_domain(sim)
+    dx0 = list(sim.dx[0][:2])
+    hi = prob_hi if prob_hi is not None else [dx0[d] * (pd[1][d] + 1) for d in range(2)]
+    comps = [0, 1] + list(range(3, 3 + ns)) + [3 + ns, 4 + ns, 5 + ns, 6 + ns]           # (w and gpz stay behind)
+    plot = [bl.MultiFab(sim.mla, n, 8 + ns, 0) for n in range(nl)]
+    try:
+        for n in range(nl):
+            plot[n].copy_c(0, sim.uold[n], 0, 3)
+            plot[n].copy_c(3, sim.sold[n], 0, ns)
+            adv.make_magvel(plot[n], 3 + ns, sim.uold[n])
+            adv.make_vorticity_plane(plot[n], 4 + ns, sim.uold[n], sim.dx[n][:2], sim.bct)
+            plot[n].copy_c(5 + ns, sim.gp[n], 0, 3)
+        # the z-uniformity of the copy as the writer measured it: (largest |f(i,j,k) - f(i,j,0)|, largest |w|, |gpz|)
+        sim.last_copy_defect = adv.fabio_ml_multifab_write_plane_d(name, plot, [2] * (nl - 1), comps, plot_names(2, ns), pd, (prob_lo or [0.0] * 2)[:2], hi[:2], sim.time, dx0,
+                                                                   vanish=[2, 7 + ns])
+    finally:
+        for m in plot:
+            m.destroy()
+    write_job_info(name, sim, getattr(sim, "inputs_text", None), getattr(sim, "job_name", ""), getattr(sim, "inputs_file", ""), dm=2)
+    return name
+
+
 def _domain(sim):
     lv = _sim_levels(sim)
     n = sim.n if hasattr(sim, "n") else getattr(sim, "ncs", None) or (sim.nc,) * 3
@@ -241,6 +313,8 @@ def write_plotfile(sim, istep=None, base="plt", prob_lo=None, prob_hi=None):
     pd, nl = _domain(sim)
     ncomp = 2 * dm + ns + 2
     name = "%s%05d" % (base, sim.istep if istep is None else istep)
+    if _plane_files(sim):
+        return _write_plane_plotfile(sim, name, prob_lo, prob_hi)
     dx0 = list(sim.dx[0][:dm])
     hi = prob_hi if prob_hi is not None else [dx0[d] * (pd[1][d] + 1) for d in range(dm)]
     plot = [bl.MultiFab(sim.mla, n, ncomp, 0) for n in range(nl)]
@@ -267,13 +341,16 @@ def write_plotfile(sim, istep=None, base="plt", prob_lo=None, prob_hi=None):
 BC_NAMES = {-1: "periodic", 0: "interior", 11: "inlet", 12: "outlet", 13: "symmetry", 14: "slip wall", 15: "no slip wall"}
 
 
-def write_job_info(dirname, sim, inputs_text=None, job_name="", inputs_file=""):
+def write_job_info(dirname, sim, inputs_text=None, job_name="", inputs_file="", dm=None):
     """job_info in a plot directory (src/write_job_info.f90): job, output, grid and boundary-condition sections; the build section
     names this library instead of the Fortran tool chain; the run-time parameters are the namelist the run was started from"""
     import datetime
     bar = "=" * 79
     lv = _sim_levels(sim)
     pd, _ = _domain(sim)
+    dm = sim.dm if dm is None else dm                    # (2: the files of a 2-D hierarchy run as its copy list two directions and the file's boxes)
+    if dm < sim.dm:
+        lv = [(footprints(boxes)[0], None) for boxes, _ in lv]
     with open(os.path.join(dirname, "job_info"), "w") as f:
         f.write("%s\n Job Information\n%s\njob name:    %s\ninputs file: %s\n \n" % (bar, bar, job_name, inputs_file))
         f.write("number of MPI processes %6d\nnumber of threads       %6d\n \n \n" % (getattr(sim, "nranks", 1), 1))
@@ -283,10 +360,10 @@ def write_job_info(dirname, sim, inputs_text=None, job_name="", inputs_file=""):
         f.write("%s\n Build Information\n%s\nvarden_amd (MI355X, HIP): %s\n \n \n" % (bar, bar, os.path.dirname(os.path.abspath(__file__))))
         f.write("%s\n Grid Information\n%s\n" % (bar, bar))
         for n, (boxes, _) in enumerate(lv):
-            ext = [(pd[1][d] + 1) << n for d in range(sim.dm)]
+            ext = [(pd[1][d] + 1) << n for d in range(dm)]
             f.write(" level: %d\n    number of boxes = %d\n    maximum zones   = %s\n" % (n + 1, len(boxes), " ".join(str(e) for e in ext)))
         f.write(" \n Boundary Conditions\n")
-        for d in range(sim.dm):
+        for d in range(dm):
             f.write("   -%s: %s\n   +%s: %s\n \n" % ("xyz"[d], BC_NAMES.get(sim.phys[d][0], str(sim.phys[d][0])), "xyz"[d], BC_NAMES.get(sim.phys[d][1], str(sim.phys[d][1]))))
         f.write(" \n%s\n Runtime Parameter Information\n%s\n%s\n" % (bar, bar, (inputs_text or "").strip()))
 
@@ -296,6 +373,8 @@ def write_grids(grids_file_name, sim, nstep):
     lv = _sim_levels(sim)
     pd, _ = _domain(sim)
     dm = sim.dm
+    if _plane_files(sim):                                # a 2-D hierarchy run as its copy: the footprints, dm = 2
+        lv, dm = [(footprints(boxes)[0], None) for boxes, _ in lv], 2
     fmt = lambda lo, hi: "((%s) (%s) (%s))" % (", ".join(str(int(x)) for x in lo[:dm]), ", ".join(str(int(x)) for x in hi[:dm]), ",".join("0" for _ in range(dm)))   # noqa: E731
     if getattr(sim, "rank", 0) != 0:
         return
@@ -331,6 +410,19 @@ def write_checkfile(sim, istep=None, base="chk"):
     Pressure = nodal p, Header = namelist &chkpoint (time, dt, nlevs) followed by the refinement ratios"""
     name = "%s%05d" % (base, sim.istep if istep is None else istep)
     pd, nl = _domain(sim)
+    if _plane_files(sim):                               # State = u, v, scalars, gpx, gpy of plane k = 0; Pressure nodal (1,1)
+        ns = sim.nscal
+        state = [bl.MultiFab(sim.mla, n, 6 + ns, 0) for n in range(nl)]
+        try:
+            for n in range(nl):
+                state[n].copy_c(0, sim.uold[n], 0, 3)
+                state[n].copy_c(3, sim.sold[n], 0, ns)
+                state[n].copy_c(3 + ns, sim.gp[n], 0, 3)
+            sim.last_copy_defect = adv.checkpoint_write_plane(name, state, list(sim.p[:nl]), [2] * (nl - 1), sim.time, sim.dt, [0, 1] + list(range(3, 5 + ns)), vanish=[2, 5 + ns])
+        finally:
+            for m in state:
+                m.destroy()
+        return name
     if getattr(sim, "nranks", 1) == 1:                  # one rank: the library's checkpoint_write (csrc/fabio.hip); the same files
         dm, ns = sim.dm, sim.nscal
         state = [bl.MultiFab(sim.mla, n, 2 * dm + ns, 0) for n in range(nl)]
@@ -368,7 +460,7 @@ def read_checkfile(name):
     state, press = read_ml_multifab(os.path.join(name, "State")), read_ml_multifab(os.path.join(name, "Pressure"))
     assert state["nlevs"] == nl and press["nlevs"] == nl
     return dict(nlevs=nl, time=float(nml["time"].lower().replace("d", "e")), dt=float(nml["dt"].lower().replace("d", "e")),
-                rr=[int(x) for x in tail[:nl - 1]], dm=state["dm"], pd=state["pd"],
+                rr=[int(x) for x in tail[:nl - 1]], dm=state["dm"], pd=state["pd"], name=name,
                 boxes=[L["boxes"] for L in state["levels"]], state=[L["fabs"] for L in state["levels"]],
                 pressure=[L["fabs"] for L in press["levels"]])
 
@@ -376,6 +468,23 @@ def read_checkfile(name):
 def load_restart(sim, chk):
     """initialize_from_restart (src/initialize.f90:52-57): uold, sold, gp, p <- the checkpoint; the sim was built on chk['boxes']"""
     dm, ns = sim.dm, sim.nscal
+    if getattr(sim, "extrude2d", None) and chk["dm"] == 2:      # a 2-D checkpoint into the copy: the file's plane to every plane (the library checks the footprints), w = gpz = 0
+        nl = len(sim.boxes)
+        state = [bl.MultiFab(sim.mla, n, 6 + ns, 0) for n in range(nl)]
+        try:
+            adv.fabio_ml_multifab_read_plane_d(os.path.join(chk["name"], "State"), state, [0, 1] + list(range(3, 5 + ns)))
+            for n in range(nl):
+                sim.uold[n].setval(0.0, 2, 1, all=True)
+                sim.gp[n].setval(0.0, 2, 1, all=True)
+                sim.uold[n].copy_c(0, state[n], 0, 2)
+                sim.sold[n].copy_c(0, state[n], 3, ns)
+                sim.gp[n].copy_c(0, state[n], 3 + ns, 2)
+        finally:
+            for m in state:
+                m.destroy()
+        adv.fabio_ml_multifab_read_plane_d(os.path.join(chk["name"], "Pressure"), list(sim.p[:nl]), [0])
+        sim.time, sim.dt = chk["time"], chk["dt"]
+        return
     for n, (boxes, local) in enumerate(_sim_levels(sim)):
         assert [tuple(map(tuple, b)) for b in boxes] == [tuple(map(tuple, b)) for b in chk["boxes"][n]], "restart: box lists differ"
         for li, gi in enumerate(local):
