@@ -17,6 +17,7 @@
 // device memory by the next kernel (no host round trip).
 #include "vdn_dev.h"
 #include <algorithm>
+#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------------
 struct GArgs {
@@ -444,16 +445,16 @@ struct FCell { double m_lo[3], m_up[3], s0, f, mr, Lb[3], Rb[3]; };      // a ce
 // third of its f64 instructions (v_div_scale x 2, v_rcp, eight fma, v_div_fmas, v_div_fixup each).  Other spacings keep the division.
 static bool is_pow2(double x) { int e; return x > 0.0 && std::frexp(x, &e) == 0.5; }
 #define DIVDX(x, d) (PW2 ? (x) * F.idx[d] : (x) / F.dx[d])
-template <bool PW2> DEVI void f_bases(const FArgs &F, FCell &P, const double sl[3]) {
+template <bool PW2> DEVI void f_bases(const FArgs &F, FCell &P, const double sl[3], const bool minion, const bool cons) {
   double ft = 0.0, mt = 0.0;
-  if (F.use_minion) { ft = F.dt2 * P.f; mt = F.dt2 * P.s0 * P.mr; }
+  if (minion) { ft = F.dt2 * P.f; mt = F.dt2 * P.s0 * P.mr; }
   #pragma unroll
   for (int d = 0; d < 3; d++) {
     double Lb = P.s0 + (0.5 - DIVDX(F.dt2 * P.m_up[d], d)) * sl[d];
     double Rb = P.s0 - (0.5 + DIVDX(F.dt2 * P.m_lo[d], d)) * sl[d];
-    if (F.use_minion) {
+    if (minion) {
       Lb = Lb + ft; Rb = Rb + ft;
-      if (F.cons) { Lb = Lb - mt; Rb = Rb - mt; }
+      if (cons) { Lb = Lb - mt; Rb = Rb - mt; }
     }
     P.Lb[d] = Lb; P.Rb[d] = Rb;
   }
@@ -463,6 +464,11 @@ DEVI double tvq(bool cons, double q, double sp, double s0, double mp, double m0)
   return q * (mp + m0) * (sp - s0);
 }
 constexpr int FNX = 62, FNY = TNY - 2;      // cells a tile owns per row / rows it owns
+// SP: the launch-uniform flags of a one-box march as a template argument -- cons, use_minion and (UPD) the update's forcing mode compiled in, so that
+// neither arm of a flag nor the copies around it stay in the plane loop (f_bases, tvq, the stage-D chains, the update); SP_RT: read from FArgs at run
+// time (the box-batched launches, whose descriptors differ in them, and the rarely taken forms).  vp_F_m_body: use_minion only.
+constexpr int SP_RT = -1, SP_CONS = 1, SP_MINION = 2, SP_FMODE1 = 4;
+constexpr int PH_EDGE = 0, PH_STEADY = 1;   // phases of a march's plane function
 static dim3 fused_grid(const Range3 &r, int &klen) {
   // one 512-thread workgroup per CU at a time: the chunk count is the one that fills the last round of workgroups best
   const int nx = r.hi[0] - r.lo[0] + 1, ny = r.hi[1] - r.lo[1] + 1, nz = r.hi[2] - r.lo[2] + 1;
@@ -556,7 +562,7 @@ template <bool NAR> DEVI SegGeo seg_geo(int W_) {
 // passed barrier kk reads buffer kk & 1 and last iteration's lSI / lSC / lE while the fastest wave writes buffer (kk + 1) & 1 and this iteration's.
 // the y-exchange arrays of the march, ONE allocation per kernel shared by the bodies inlined into it (boundary / lean, full-width / narrow)
 template <bool UPD> struct FShared { double lB[2][TNY][64], lSI[2][TNY][64], lC[2][2][TNY][64], lSC[2][2][TNY][64], lD[2][TNY][64], lE[UPD ? 2 : 1][UPD ? TNY : 1][64]; };
-template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __forceinline__ void mk_F_m_body(FShared<UPD> &S, const FArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
+template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, int SP = SP_RT, bool PEEL = false> __device__ __forceinline__ void mk_F_m_body(FShared<UPD> &S, const FArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
   double (&lB)[2][TNY][64] = S.lB, (&lSI)[2][TNY][64] = S.lSI, (&lC)[2][2][TNY][64] = S.lC, (&lSC)[2][2][TNY][64] = S.lSC, (&lD)[2][TNY][64] = S.lD;
   double (&lE)[UPD ? 2 : 1][UPD ? TNY : 1][64] = S.lE;
   const SegGeo G = seg_geo<NAR>(segw);
@@ -571,7 +577,8 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
   const int k0 = r.lo[2] + BZ * klen, k1 = min(k0 + klen - 1, r.hi[2]);
   const int KB = F.lo[2] - 1, KT = F.hi[2] + 1;                       // the planes loads are clamped to
   const double eps = eps_from(umax);
-  const bool cons = F.cons != 0;
+  const bool cons = SP != SP_RT ? (SP & SP_CONS) != 0 : F.cons != 0, minion = SP != SP_RT ? (SP & SP_MINION) != 0 : F.use_minion != 0;
+  const int fmode = SP != SP_RT ? ((SP & SP_FMODE1) ? 1 : 0) : F.fmode;
   // the thread's column in every field layout
   const unsigned o_s = fg_off(F.g[0], ic, jc), o_sl = fg_off(F.g[1], ic, jc), o_um = fg_off(F.g[2], ic, jc), o_vm = fg_off(F.g[3], ic, jc), o_wm = fg_off(F.g[4], ic, jc);
   const unsigned o_f = fg_off(F.g[5], ic, jc), o_mr = fg_off(F.g[6], ic, jc);
@@ -631,7 +638,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
   #define PREMOD(Lb_, Rb_, w, shlo, shhi, gl_expr, gh_expr) { const int a_ = ((w) >> (shlo)) & 7; if (a_) { double o_; BC_V(o_, a_, Rb_, gl_expr) Rb_ = o_; }  \
                                                               const int b_ = ((w) >> (shhi)) & 7; if (b_) { double o_; BC_V(o_, b_, Lb_, gh_expr) Lb_ = o_; } }
   // the word of the z direction for stage plane k (clamped kc): uniform
-  #define Z_WORD(k, kc) (BC ? ((((k) == (kc) && (k) == F.lo[2]) ? cd[2][0] : 0) | (((k) == (kc) && (k) == KT && cd[2][1]) ? (cd[2][1] | 8) : 0) | \
+  #define Z_WORD(k, kc) (BCP ? ((((k) == (kc) && (k) == F.lo[2]) ? cd[2][0] : 0) | (((k) == (kc) && (k) == KT && cd[2][1]) ? (cd[2][1] | 8) : 0) | \
                                 (((kc) == F.lo[2]) ? cd[2][0] << 4 : 0) | (((kc) == F.hi[2]) ? cd[2][1] << 8 : 0)) : 0)
   // a plane's twelve loads are issued one iteration ahead (N): at two waves per SIMD nothing else hides their latency, and an iteration's
   // arithmetic (~500 VALU instructions per wave) is longer than the round trip
@@ -647,7 +654,10 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
       if (kc_ != kcur) { ps += F.sp[0]; psl0 += F.sp[1]; psl1 += F.sp[1]; psl2 += F.sp[1]; pum += F.sp[2]; pvm += F.sp[3]; pwm += F.sp[4]; pf += F.sp[5]; pmr += F.sp[6]; kcur = kc_; } }
   F_LOAD
   F_ADVANCE(k0 - 1)
-  for (int kk = k0 - 2; kk <= k1 + 2 + (UPD ? 1 : 0); kk++) {
+  // one plane of the march.  PH_EDGE: the warm-up and run-out conditions tested per plane; PH_STEADY: all of them known true (see the loop below);
+  // bcp: with the boundary code (a body with BC may run a plane without it)
+  auto plane = [&](auto ph, auto bcp, const int kk) __attribute__((always_inline)) {
+    constexpr bool STEADY = decltype(ph)::value == PH_STEADY, BCP = BC && decltype(bcp)::value;
     const int buf = kk & 1;
     P2 = P1; P1 = P0;
     {
@@ -655,10 +665,10 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
       for (int d = 0; d < 3; d++) { P0.m_lo[d] = N.m_lo[d]; P0.m_up[d] = N.m_up[d]; }
       P0.s0 = N.s0; P0.f = N.f; P0.mr = N.mr;
       const double sl[3] = { N.sl[0], N.sl[1], N.sl[2] };
-      if (kk < k1 + 2) { F_LOAD  F_ADVANCE(kk + 2) }
-      f_bases<PW2>(F, P0, sl);
+      if (STEADY || kk < k1 + 2) { F_LOAD  F_ADVANCE(kk + 2) }
+      f_bases<PW2>(F, P0, sl, minion, cons);
     }
-    const bool doC = kk - 1 >= k0 - 1, doD = kk - 2 >= k0 - 1;
+    const bool doC = STEADY || kk - 1 >= k0 - 1, doD = STEADY || kk - 2 >= k0 - 1;
     // ================= in front of the barrier: the three LDS writes and every upwind that reads no LDS value =================
     // ---- stage B, plane kk: x and z faces
     double si0[3];
@@ -671,7 +681,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
       LzB = P0.Lb[2];
       si0[0] = upwind_mac(LxB, P0.Rb[0], P0.m_lo[0], eps);
       si0[2] = upwind_mac(Lzc, P0.Rb[2], P0.m_lo[2], eps);
-      if (BC && kB == kcB) {
+      if (BCP && kB == kcB) {
         int w = bcw; asm volatile("" : "+v"(w));
         if (w & 0xF) { FACE_BC(si0[0], w, 0, LxB, P0.Rb[0], P0.s0, S_AT(kcB, -8L)) }
         if ((zwB & 15) && ing_ij) { FACE_BC(si0[2], zwB, 0, Lzc, P0.Rb[2], P0.s0, P1.s0) }
@@ -685,7 +695,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
     if (doC) {
       #pragma unroll
       for (int d = 0; d < 3; d++) { cLb[d] = P1.Lb[d]; cRb[d] = P1.Rb[d]; }
-      if (BC) {
+      if (BCP) {
         wc = bcw; asm volatile("" : "+v"(wc));
         if (wc & 0x770770) { PREMOD(cLb[0], cRb[0], wc, 4, 8, S_AT(kcC, -8L), S_AT(kcC, 8L)) PREMOD(cLb[1], cRb[1], wc, 16, 20, S_AT(kcC, -F.s_row), S_AT(kcC, F.s_row)) }
         if (zwC & 0x770) { PREMOD(cLb[2], cRb[2], zwC, 4, 8, S_AT(kcC - 1, 0L), S_AT(kcC + 1, 0L)) }
@@ -699,7 +709,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
       LzC[0] = VL20;
       qc[1] = upwind_mac(Lx1, VR01, P1.m_lo[0], eps);
       qc[4] = upwind_mac(Lz0, VR20, P1.m_lo[2], eps);
-      if (BC && kC == kcC) {
+      if (BCP && kC == kcC) {
         if (wc & 0xF) { FACE_BC(qc[1], wc, 0, Lx1, VR01, P1.s0, S_AT(kcC, -8L)) }
         if ((zwC & 15) && ing_ij) { FACE_BC(qc[4], zwC, 0, Lz0, VR20, P1.s0, P2.s0) }
       }
@@ -714,13 +724,13 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
           double vl = dLb[Dd], vr = dRb[Dd];                                                                     \
           vl = vl - t1; vr = vr - t1; vl = vl - t2; vr = vr - t2;                                                \
           if (cons) { vl = vl + da[T1]; vr = vr + da[T1]; vl = vl + da[T2]; vr = vr + da[T2]; }                  \
-          if (!F.use_minion) { vl = vl + dft; vr = vr + dft; if (cons) { vl = vl - dmt; vr = vr - dmt; } }       \
+          if (!minion) { vl = vl + dft; vr = vr + dft; if (cons) { vl = vl - dmt; vr = vr - dmt; } }             \
           vl_ = vl; vr_ = vr; }
     if (doD) {
       dft = F.dt2 * P2.f; dmt = F.dt2 * P2.s0 * P2.mr;
       #pragma unroll
       for (int d = 0; d < 3; d++) { dLb[d] = P2.Lb[d]; dRb[d] = P2.Rb[d]; da[d] = F.aD[d] * P2.s0 * (P2.m_up[d] - P2.m_lo[d]); }
-      if (BC) {
+      if (BCP) {
         wd = bcw; asm volatile("" : "+v"(wd));
         if (wd & 0x770770) { PREMOD(dLb[0], dRb[0], wd, 4, 8, S_AT(kcD, -8L), S_AT(kcD, 8L)) PREMOD(dLb[1], dRb[1], wd, 16, 20, S_AT(kcD, -F.s_row), S_AT(kcD, F.s_row)) }
         if (zwD & 0x770) { PREMOD(dLb[2], dRb[2], zwD, 4, 8, S_AT(kcD - 1, 0L), S_AT(kcD + 1, 0L)) }
@@ -735,7 +745,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
     {
       const double Ly = LM(lB[buf]);
       si0[1] = upwind_mac(Ly, P0.Rb[1], P0.m_lo[1], eps);
-      if (BC && kB == kcB) {
+      if (BCP && kB == kcB) {
         int w = bcw; asm volatile("" : "+v"(w));
         if (w & 0xF000) { FACE_BC(si0[1], w, 12, Ly, P0.Rb[1], P0.s0, S_AT(kcB, -F.s_row)) }
       }
@@ -750,7 +760,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
       qc[0] = upwind_mac(Lx0, VR00, P1.m_lo[0], eps);
       qc[2] = upwind_mac(Ly0, VR10, P1.m_lo[1], eps); qc[3] = upwind_mac(Ly1, VR11, P1.m_lo[1], eps);
       qc[5] = upwind_mac(cLz1, VR21, P1.m_lo[2], eps);
-      if (BC && kC == kcC) {
+      if (BCP && kC == kcC) {
         if (wc & 0xF00F) {
           FACE_BC(qc[0], wc, 0, Lx0, VR00, P1.s0, S_AT(kcC, -8L))
           FACE_BC(qc[2], wc, 12, Ly0, VR10, P1.s0, S_AT(kcC, -F.s_row)) FACE_BC(qc[3], wc, 12, Ly1, VR11, P1.s0, S_AT(kcC, -F.s_row))
@@ -771,11 +781,11 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
       CHAIN1(VL[2], VR[2], 2, 0, 1, lane_next(qp[0]), qp[0], LP(lSC[buf ^ 1][0]), qp[2])
       double L[3];
       L[0] = shfl_prev(VL[0]); L[1] = LM(lD[buf]); L[2] = LzD; LzD = VL[2];
-      if (k >= k0) {
+      if (STEADY || k >= k0) {
         double e[3] = { 0.0, 0.0, 0.0 };
         if (UPD || own_ij) {
           e[0] = upwind_mac(L[0], VR[0], m_lo[0], eps); e[1] = upwind_mac(L[1], VR[1], m_lo[1], eps); e[2] = upwind_mac(L[2], VR[2], m_lo[2], eps);
-          if (BC) {
+          if (BCP) {
             if (wd & 0xF00F) { FACE_BC(e[0], wd, 0, L[0], VR[0], s0, S_AT(kc, -8L)) FACE_BC(e[1], wd, 12, L[1], VR[1], s0, S_AT(kc, -F.s_row)) }
             if (zw & 15) { FACE_BC(e[2], zw, 0, L[2], VR[2], s0, S_AT(kc - 1, 0L)) }
           }
@@ -789,7 +799,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
           qex += F.sq[0]; qfx += F.sq[0]; qey += F.sq[1]; qfy += F.sq[1]; qez += F.sq[2]; qfz += F.sq[2];
         } else {
           const double ex = cons ? e[0] * m_lo[0] : e[0], ey = cons ? e[1] * m_lo[1] : e[1], ez = cons ? e[2] * m_lo[2] : e[2];
-          if (k - 1 >= k0) {                                           // finish plane k-1: its upper y face from the row above, its upper z face = ez
+          if (STEADY || k - 1 >= k0) {                                 // finish plane k-1: its upper y face from the row above, its upper z face = ez
             const double eyu = LP(lE[buf ^ 1]);
             const double ty = cons ? DIVDX(eyu - c_e1, 1) : DIVDX(c_vbar * (eyu - c_e1), 1);
             const double tz = cons ? DIVDX(ez - c_e2, 2) : DIVDX(c_wbar * (ez - c_e2), 2);
@@ -802,7 +812,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
           c_tx = cons ? DIVDX(exu - ex, 0) : DIVDX((0.5 * (m_lo[0] + m_up[0])) * (exu - ex), 0);
           c_vbar = 0.5 * (m_lo[1] + m_up[1]); c_wbar = 0.5 * (m_lo[2] + m_up[2]);
           c_e1 = ey; c_e2 = ez; c_so = s0;
-          if (F.fmode == 0) c_fu = P2.f;
+          if (fmode == 0) c_fu = P2.f;
           else {
             const long po = (long)(kc - KB) * F.sp[5] + o_f;
             c_fu = ldd(F.pfu[0] + po, 0u) + (F.lapu0 - ldd(F.pfu[1] + po, 0u)) / ldd(F.pfu[2] + po, 0u);
@@ -811,11 +821,31 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
         }
       }
     }
-    #undef CHAIN1
     si1[0] = si0[0]; si1[1] = si0[1]; si1[2] = si0[2];
     #pragma unroll
     for (int n = 0; n < 6; n++) qp[n] = qc[n];
+  };
+  #undef CHAIN1
+  // The march over ONE plane function in two forms.  Stage C starts at kk = k0, stage D at k0 + 1, the stores at k0 + 2, the update's finishing half
+  // at k0 + 3, and loads stop at k1 + 2: all five conditions hold for kk in [k0 + 3, k1 + 1], and there the plane runs with them compiled in (no uniform
+  // branches, no PHI copies around them, unconditional loads) -- the steady form; the five planes before and the one or two after test them as before.
+  // The steady form carries no boundary code: in a workgroup that runs the boundary body it takes the planes whose three stage planes (kk, kk - 1,
+  // kk - 2) stay clear of the z faces when the tile touches no x / y face with a rule (no cell of such a plane is flagged: it is what an unflagged
+  // workgroup executes); every other plane of that workgroup runs the tested form with the boundary code.  Same expressions, one barrier per plane in
+  // every form; a chunk of at most 3 planes has no steady plane.  Three loops one after the other: the same planes in one loop that chooses the form
+  // per plane made every kernel spill (300 to 480 bytes of scratch per lane).
+  bool xy_face = false;                                               // the tile comes within one cell of an x / y face that carries a rule (uniform)
+  if (BC) {
+    const int t0[2] = { r.lo[0] - 1 + BX * ownx, r.lo[1] - 1 + BY * owny }, t1[2] = { t0[0] + G.W - 1, t0[1] + G.ROWS - 1 };
+    #pragma unroll
+    for (int d = 0; d < 2; d++) xy_face = xy_face || (mode[d][0] && t0[d] <= F.lo[d] + 1) || (mode[d][1] && t1[d] >= F.hi[d] - 1);
   }
+  const int kend = k1 + 2 + (UPD ? 1 : 0);
+  const int ks0 = BC ? max(k0 + 3, F.lo[2] + 3) : k0 + 3, ks1 = (BC && xy_face) ? ks0 - 1 : (BC ? min(k1 + 1, F.hi[2] - 1) : k1 + 1);
+  int kk = k0 - 2;
+  for (; kk <= (PEEL ? min(ks0 - 1, kend) : kend); kk++) plane(std::integral_constant<int, PH_EDGE>{}, std::true_type{}, kk);
+  if (PEEL) for (; kk <= ks1; kk++) plane(std::integral_constant<int, PH_STEADY>{}, std::false_type{}, kk);
+  if (PEEL) for (; kk <= kend; kk++) plane(std::integral_constant<int, PH_EDGE>{}, std::true_type{}, kk);
   #undef F_LOAD
   #undef F_ADVANCE
   #undef S_AT
@@ -824,7 +854,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false> __device__ __
   #undef PREMOD
   #undef Z_WORD
 }
-template <bool BC = true, bool INL = true, bool UPD = false, bool PW2 = false> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_m(FArgs F, Range3 r, int klen, const double *umax) {
+template <bool BC = true, bool INL = true, bool UPD = false, bool PW2 = false, int SP = SP_RT> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_m(FArgs F, Range3 r, int klen, const double *umax) {
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
   // a workgroup whose tile and k-chunk stay clear of every face that carries a rule runs the body without the boundary code (same values:
   // none of its cells is flagged); compiled into one kernel the lean path keeps its own register allocation (0.69 against 0.96 ms per launch)
@@ -840,15 +870,16 @@ template <bool BC = true, bool INL = true, bool UPD = false, bool PW2 = false> _
     }
   }
   __shared__ FShared<UPD> S;
-  if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2>(S, F, r, klen, umax, bx_, by_, bz_);
-  else mk_F_m_body<false, false, UPD, PW2>(S, F, r, klen, umax, bx_, by_, bz_);
+  constexpr bool PEEL = SP != SP_RT || !UPD;       // (the update forms with run-time flags stay unpeeled: peeled, the inflow one needs scratch -- profiles/godunov_phases_ab.txt)
+  if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2, false, SP, PEEL>(S, F, r, klen, umax, bx_, by_, bz_);
+  else mk_F_m_body<false, false, UPD, PW2, false, SP, PEEL>(S, F, r, klen, umax, bx_, by_, bz_);
 }
 // The remainder column of a one-box level in narrow segments (round 5).  A row of 256 cells is four 62-cell tiles and 8 cells: the fifth tile column
 // marched 64 lanes for 8 cells (a fifth of all workgroups at 256^3).  With NCOL that column runs in segments of (cells + 2) lanes, 64 / W rows per wave
 // (NAR, see seg_geo): 10 lanes x 6 rows, a workgroup 48 rows of which 46 own cells -- 6 workgroups per k-chunk instead of 43; the other workgroups of the
 // column's grid slots leave at once.  ONE launch (as a second launch the 42 workgroups were a round of their own: measured, slower than the full tiles).
 // Same body, same values; the update rides along as in the full-width tiles (the shared arrays are addressed flat).
-template <bool BC, bool INL, bool UPD, bool PW2> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_mc(FArgs F, Range3 r, int klen, const double *umax, int full, int segw) {
+template <bool BC, bool INL, bool UPD, bool PW2, int SP = SP_RT> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_mc(FArgs F, Range3 r, int klen, const double *umax, int full, int segw) {
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
   const bool narrow = bx_ == full;
   Range3 rr = r;
@@ -871,14 +902,31 @@ template <bool BC, bool INL, bool UPD, bool PW2> __global__ void __launch_bounds
     }
   }
   __shared__ FShared<UPD> S;
+  constexpr bool PEEL = SP != SP_RT;               // (as in kk_mk_F_m)
   if (narrow) {
-    if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2, true>(S, F, rr, klen, umax, bx_, by_, bz_, segw);
-    else mk_F_m_body<false, false, UPD, PW2, true>(S, F, rr, klen, umax, bx_, by_, bz_, segw);
+    if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2, true, SP, PEEL>(S, F, rr, klen, umax, bx_, by_, bz_, segw);
+    else mk_F_m_body<false, false, UPD, PW2, true, SP, PEEL>(S, F, rr, klen, umax, bx_, by_, bz_, segw);
   } else {
-    if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2>(S, F, rr, klen, umax, bx_, by_, bz_);
-    else mk_F_m_body<false, false, UPD, PW2>(S, F, rr, klen, umax, bx_, by_, bz_);
+    if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2, false, SP, PEEL>(S, F, rr, klen, umax, bx_, by_, bz_);
+    else mk_F_m_body<false, false, UPD, PW2, false, SP, PEEL>(S, F, rr, klen, umax, bx_, by_, bz_);
   }
 }
+// The update-carrying power-of-two marches of a one-box level (what a step on 2^n cells runs) with the launch's flags compiled in: the combinations
+// that occur -- a conservative or a convective scalar with the force of the call, a velocity component with the forcing term formed in place, each
+// with and without use_minion; anything else takes the run-time form.  (uses blk and st of the caller)
+static int mk_sp(const FArgs &F) {
+  if (F.cons && F.fmode) return SP_RT;
+  return (F.cons ? SP_CONS : 0) | (F.use_minion ? SP_MINION : 0) | (F.fmode == 1 ? SP_FMODE1 : 0);
+}
+#define MK_LAUNCH_SP_(K, BC_, SP_, G_, ...) hipLaunchKernelGGL((K<BC_, false, true, true, SP_>), G_, blk, 0, st, __VA_ARGS__)
+#define MK_LAUNCH_SP(K, BC_, F_, G_, ...) switch (mk_sp(F_)) {                                                                \
+    case 0: MK_LAUNCH_SP_(K, BC_, 0, G_, __VA_ARGS__); break;                                                                  \
+    case SP_CONS: MK_LAUNCH_SP_(K, BC_, SP_CONS, G_, __VA_ARGS__); break;                                                      \
+    case SP_MINION: MK_LAUNCH_SP_(K, BC_, SP_MINION, G_, __VA_ARGS__); break;                                                  \
+    case SP_CONS | SP_MINION: MK_LAUNCH_SP_(K, BC_, SP_CONS | SP_MINION, G_, __VA_ARGS__); break;                              \
+    case SP_FMODE1: MK_LAUNCH_SP_(K, BC_, SP_FMODE1, G_, __VA_ARGS__); break;                                                  \
+    case SP_FMODE1 | SP_MINION: MK_LAUNCH_SP_(K, BC_, SP_FMODE1 | SP_MINION, G_, __VA_ARGS__); break;                          \
+    default: MK_LAUNCH_SP_(K, BC_, SP_RT, G_, __VA_ARGS__); }
 // the launch arguments of the fused march for component c; false when the field layouts do not allow the shared offsets
 static bool fused_args(FArgs &F, const GArgs &A, int c, const FV &s, const FV sl[3], const FV &um, const FV &vm, const FV &wm, const FV &force, const FV &macrhs,
                        const FV &sex, const FV &sey, const FV &sez, const FV &flx, const FV &fly, const FV &flz) {
@@ -1223,14 +1271,14 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
         for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) any = any || bc_mode_host(A.phys[d][sd]);
         if (do_upd) {
           const bool p2 = FA[c0].p2 != 0;                              // (the inflow variants keep the division: fewer instantiations)
-          if (!any) { if (p2) hipLaunchKernelGGL((kk_mk_F_m<false, false, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); else hipLaunchKernelGGL((kk_mk_F_m<false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); }
+          if (!any) { if (p2) { MK_LAUNCH_SP(kk_mk_F_m, false, FA[c0], gF, FA[c0], rf, klF, umax) } else hipLaunchKernelGGL((kk_mk_F_m<false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); }
           else if (inflow) hipLaunchKernelGGL((kk_mk_F_m<true, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
           else if (p2) {
             // full 62-cell tiles, then the remainder column in narrow segments (kk_mk_F_mc) where that saves workgroups
             dim3 gM; int klM, full, segw;
             if (fused_grid_cols(rf, gM, klM, full, segw)) {
-              hipLaunchKernelGGL((kk_mk_F_mc<true, false, true, true>), gM, blk, 0, st, FA[c0], rf, klM, umax, full, segw);
-            } else hipLaunchKernelGGL((kk_mk_F_m<true, false, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+              MK_LAUNCH_SP(kk_mk_F_mc, true, FA[c0], gM, FA[c0], rf, klM, umax, full, segw)
+            } else { MK_LAUNCH_SP(kk_mk_F_m, true, FA[c0], gF, FA[c0], rf, klF, umax) }
           }
           else hipLaunchKernelGGL((kk_mk_F_m<true, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
           continue;
@@ -1493,7 +1541,7 @@ DEVI double vpf_riemann(double L, double R, double eps) {            // the stat
   const double v = (uavg > 0.0) ? L : R;
   return test ? 0.0 : v;
 }
-template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinline__ void vp_F_m_body(const VArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
+template <bool BC, bool INL, bool PW2, bool NAR = false, int SP = SP_RT> __device__ __forceinline__ void vp_F_m_body(const VArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
   __shared__ double lB[3][TNY][64], lUI[3][TNY][64], lC[2][TNY][64], lXC[2][TNY][64], lD[TNY][64];
   const SegGeo G = seg_geo<NAR>(segw);
   const int lane = G.lane, row = G.row;
@@ -1567,7 +1615,10 @@ template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinlin
   #define V_ADVANCE(kn) { const int kc_ = min(max((kn), KB), KT);                                                 \
       if (kc_ != kcur) { pu += F.sp_u; ps0 += F.sp_sl; ps1 += F.sp_sl; ps2 += F.sp_sl; pf += F.sp_f; kcur = kc_; } }
   double fa[3] = { 0.0, 0.0, 0.0 }, fb[3] = { 0.0, 0.0, 0.0 };       // dt/2 force of planes kk-1, kk-2 (stage D adds it when !use_minion)
-  for (int kk = k0 - 2; kk <= k1 + 2; kk++) {
+  const bool minion = SP != SP_RT ? (SP & SP_MINION) != 0 : F.use_minion != 0;
+  // one plane of the march (see mk_F_m_body).  PH_EDGE: stages C and D and the stores tested per plane; PH_STEADY: all of them known to run
+  auto plane = [&](auto ph, const int kk) __attribute__((always_inline)) {
+    constexpr bool STEADY = decltype(ph)::value == PH_STEADY;
     // ---------------- plane kk: loads, bases ----------------
     double uc[3], Lb[3][3], Rb[3][3], ft[3];
     {
@@ -1585,7 +1636,7 @@ template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinlin
         for (int c = 0; c < 3; c++) {
           Lb[d][c] = uc[c] + (0.5 - cfl_l) * sl[d][c];
           Rb[d][c] = uc[c] - (0.5 + cfl_r) * sl[d][c];
-          if (F.use_minion) { Lb[d][c] = Lb[d][c] + ft[c]; Rb[d][c] = Rb[d][c] + ft[c]; }
+          if (minion) { Lb[d][c] = Lb[d][c] + ft[c]; Rb[d][c] = Rb[d][c] + ft[c]; }
         }
       }
     }
@@ -1628,7 +1679,7 @@ template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinlin
     }
     // ---------------- stage C, plane kk-1 ----------------
     double xc1[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, sm1[3] = { 0.0, 0.0, 0.0 };
-    if (kk - 1 >= k0 - 1) {
+    if (STEADY || kk - 1 >= k0 - 1) {
       const int k = kk - 1, kc = min(max(k, KB), KT);
       unsigned zf, zp; ZF_WORD(k, kc, zf) ZP_WORD(kc, zp)
       // w0[O][c] = ui1[O][c]; w1[O][c]: the upper O-face
@@ -1694,7 +1745,7 @@ template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinlin
       __syncthreads();                                              // keeps lB / lUI single-buffered while stage C is idle (start of a chunk)
     }
     // ---------------- stage D, plane kk-2 ----------------
-    if (kk - 2 >= k0 - 1) {
+    if (STEADY || kk - 2 >= k0 - 1) {
       const int k = kk - 2, kc = min(max(k, KB), KT);
       unsigned zf, zp; ZF_WORD(k, kc, zf) ZP_WORD(kc, zp)
       const bool vz = k >= F.lo[2] && k <= F.hi[2];
@@ -1718,28 +1769,28 @@ template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinlin
         const double a1 = F.tD[1] * g[1] * (x1[0] - x0[0]);
         const double a2 = F.tD[2] * g[2] * (x1[1] - x0[1]);
         double vl = Ld[0] - a1 - a2, vr = Rd[0] - a1 - a2;
-        if (!F.use_minion) { vl = vl + fb[0]; vr = vr + fb[0]; }
+        if (!minion) { vl = vl + fb[0]; vr = vr + fb[0]; }
         VL[0] = vl; VR[0] = vr;
       }
       {   // D = 1: T1 = 0 with XC(1,0) = n2,  T2 = 2 with XC(1,2) = n3
         const double a1 = F.tD[0] * g[0] * (x1[2] - x0[2]);
         const double a2 = F.tD[2] * g[2] * (x1[3] - x0[3]);
         double vl = Ld[1] - a1 - a2, vr = Rd[1] - a1 - a2;
-        if (!F.use_minion) { vl = vl + fb[1]; vr = vr + fb[1]; }
+        if (!minion) { vl = vl + fb[1]; vr = vr + fb[1]; }
         VL[1] = vl; VR[1] = vr;
       }
       {   // D = 2: T1 = 0 with XC(2,0) = n4,  T2 = 1 with XC(2,1) = n5
         const double a1 = F.tD[0] * g[0] * (x1[4] - x0[4]);
         const double a2 = F.tD[1] * g[1] * (x1[5] - x0[5]);
         double vl = Ld[2] - a1 - a2, vr = Rd[2] - a1 - a2;
-        if (!F.use_minion) { vl = vl + fb[2]; vr = vr + fb[2]; }
+        if (!minion) { vl = vl + fb[2]; vr = vr + fb[2]; }
         VL[2] = vl; VR[2] = vr;
       }
       LS(lD) = VL[1];
       __syncthreads();
       const double Lx = shfl_prev(VL[0]), Ly = LM(lD), Lzc = LzD;
       LzD = VL[2];
-      if (k >= k0) {
+      if (STEADY || k >= k0) {
         if (own_ij) {
           double e0 = vpf_riemann(Lx, VR[0], eps), e1 = vpf_riemann(Ly, VR[1], eps), e2 = vpf_riemann(Lzc, VR[2], eps);
           if (BC) {
@@ -1762,7 +1813,12 @@ template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinlin
     for (int n = 0; n < 6; n++) xc2[n] = xc1[n];
     #pragma unroll
     for (int d = 0; d < 3; d++) for (int c = 0; c < 3; c++) { Lb1[d][c] = Lb[d][c]; Rb1[d][c] = Rb[d][c]; ui1[d][c] = ui0[d][c]; }
-  }
+  };
+  // Stage C starts at kk = k0, stage D at k0 + 1 and the stores at k0 + 2 (loads never stop): the four warm-up planes test that, every later plane runs
+  // with all three compiled in.  Three barriers per plane in both forms -- the idle stages of the warm-up planes keep theirs.
+  int kk = k0 - 2;
+  for (; kk <= k0 + 1; kk++) plane(std::integral_constant<int, PH_EDGE>{}, kk);
+  for (; kk <= k1 + 2; kk++) plane(std::integral_constant<int, PH_STEADY>{}, kk);
   #undef U_AT
   #undef BC_V
   #undef PAIR_BC
@@ -1774,21 +1830,21 @@ template <bool BC, bool INL, bool PW2, bool NAR = false> __device__ __forceinlin
   #undef V_ADVANCE
 }
 // (the interior / boundary workgroup dispatch of kk_mk_F_m was measured here too: 1.198 -> 1.227 ms, not kept)
-template <bool BC = true, bool INL = true, bool PW2 = false> __global__ void __launch_bounds__(64 * TNY) kk_vp_F_m(VArgs F, Range3 r, int klen, const double *umax) {
+template <bool BC = true, bool INL = true, bool PW2 = false, int SP = SP_RT> __global__ void __launch_bounds__(64 * TNY) kk_vp_F_m(VArgs F, Range3 r, int klen, const double *umax) {
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
-  vp_F_m_body<BC, INL, PW2>(F, r, klen, umax, bx_, by_, bz_);
+  vp_F_m_body<BC, INL, PW2, false, SP>(F, r, klen, umax, bx_, by_, bz_);
 }
 // the remainder tile column in narrow segments inside the same launch (see kk_mk_F_mc)
-template <bool BC, bool INL, bool PW2> __global__ void __launch_bounds__(64 * TNY) kk_vp_F_mc(VArgs F, Range3 r, int klen, const double *umax, int full, int segw) {
+template <bool BC, bool INL, bool PW2, int SP = SP_RT> __global__ void __launch_bounds__(64 * TNY) kk_vp_F_mc(VArgs F, Range3 r, int klen, const double *umax, int full, int segw) {
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
   Range3 rr = r;
   if (bx_ == full) {
     rr.lo[0] = r.lo[0] + full * FNX;
     if (by_ * (TNY * (64 / segw) - 2) > r.hi[1] - r.lo[1]) return;
-    vp_F_m_body<BC, INL, PW2, true>(F, rr, klen, umax, 0, by_, bz_, segw);
+    vp_F_m_body<BC, INL, PW2, true, SP>(F, rr, klen, umax, 0, by_, bz_, segw);
   } else {
     rr.hi[0] = r.lo[0] + full * FNX - 1;
-    vp_F_m_body<BC, INL, PW2>(F, rr, klen, umax, bx_, by_, bz_);
+    vp_F_m_body<BC, INL, PW2, false, SP>(F, rr, klen, umax, bx_, by_, bz_);
   }
 }
 static bool vfused_args(VArgs &F, const GArgs &A, const FV &u, const FV sl[3], const FV &force, const FV &um, const FV &vm, const FV &wm) {
@@ -2122,14 +2178,18 @@ void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *f
       bool any = false, inflow = false;
       for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) { any = any || bc_mode_host(A.phys[d][sd]); inflow = inflow || A.phys[d][sd] == VDN_INLET; }
       const bool p2 = VA.p2 != 0;
-      if (!any) { if (p2) hipLaunchKernelGGL((kk_vp_F_m<false, false, true>), gF, blk, 0, st, VA, rf, klF, umax); else hipLaunchKernelGGL((kk_vp_F_m<false, false>), gF, blk, 0, st, VA, rf, klF, umax); }
+      // (the power-of-two forms with use_minion compiled in: SP of vp_F_m_body)
+      #define VP_LAUNCH_SP(K, BC_, G_, ...) { if (VA.use_minion) hipLaunchKernelGGL((K<BC_, false, true, SP_MINION>), G_, blk, 0, st, __VA_ARGS__); \
+                                              else hipLaunchKernelGGL((K<BC_, false, true, 0>), G_, blk, 0, st, __VA_ARGS__); }
+      if (!any) { if (p2) VP_LAUNCH_SP(kk_vp_F_m, false, gF, VA, rf, klF, umax) else hipLaunchKernelGGL((kk_vp_F_m<false, false>), gF, blk, 0, st, VA, rf, klF, umax); }
       else if (inflow) hipLaunchKernelGGL((kk_vp_F_m<true, true>), gF, blk, 0, st, VA, rf, klF, umax);
       else if (p2) {
         dim3 gM; int klM, full, segw;
-        if (fused_grid_cols(rf, gM, klM, full, segw)) hipLaunchKernelGGL((kk_vp_F_mc<true, false, true>), gM, blk, 0, st, VA, rf, klM, umax, full, segw);
-        else hipLaunchKernelGGL((kk_vp_F_m<true, false, true>), gF, blk, 0, st, VA, rf, klF, umax);
+        if (fused_grid_cols(rf, gM, klM, full, segw)) VP_LAUNCH_SP(kk_vp_F_mc, true, gM, VA, rf, klM, umax, full, segw)
+        else VP_LAUNCH_SP(kk_vp_F_m, true, gF, VA, rf, klF, umax)
       }
       else hipLaunchKernelGGL((kk_vp_F_m<true, false>), gF, blk, 0, st, VA, rf, klF, umax);
+      #undef VP_LAUNCH_SP
     } else {                       // the face-centred stages: VDN_GODUNOV_PLAIN, or field layouts the fused march refuses
       FV UI = w, XC = w;
       UI.p = (double *)arena_alloc(fld * 9);
