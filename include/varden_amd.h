@@ -104,8 +104,10 @@ typedef struct vdn_params {
    * Both Krylov methods are preconditioned by the operator's diagonal, start from zero, run in ONE workgroup, stop when the max-norm of the residual has
    * fallen by *_bottom_solver_eps relative to the bottom right-hand side, and are capped at 12 N iterations.  A breakdown (rho or omega zero or not
    * finite, p.Ap <= 0) leaves the last iterate, is counted (vdn_last_bottom_stats) and the V-cycle goes on.  They apply where one rank holds the whole
-   * bottom level: the last level of a one-box hierarchy and of the replicated tail (any boxes, any ranks; level 0 of a composite solve included).  A
-   * bottom level still distributed over boxes keeps its sweeps, and so does dm = 2.  With -1, 0 or 4 no launch and no bit differs from before. */
+   * bottom level: the last level of a one-box hierarchy and of the replicated tail (any boxes, any ranks; level 0 of a composite solve included), and
+   * the last level of both dm = 2 multigrids (any boxes, any ranks: they work on a gathered level that every rank holds whole).  A bottom level still
+   * distributed over boxes keeps its sweeps, and so does a hierarchy of ONE level (an odd extent on the finest level, in dm = 2 and dm = 3 alike), which
+   * reports zero statistics.  With -1, 0 or 4 no launch and no bit differs from before. */
   int    mg_bottom_solver, hg_bottom_solver;
   int    max_mg_bottom_nlevels;   /* 1000 (src/_parameters:57): carried for the reference's namelist; NO effect (the levels under the bottom are the replicated tail) */
   double mg_bottom_solver_eps;    /* 1e-3: mac_multigrid.f90:56 (bottom_solver_eps = 1.d-3) */
@@ -401,6 +403,11 @@ int  vdn_k_make_at_halftime(vdn_multifab *rhohalf, const vdn_multifab *sold, con
 int  vdn_cc_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx,
                   const int *bc /*[3][2]*/, double rel_eps, double abs_eps, int max_iter,
                   int *cycles, double *res0, double *res);
+/* the same with the alpha term: (alpha - div beta grad) phi = rh, alpha a cell multifab (ng = 0) -- the solve of visc_solve and
+ * diff_scalar_solve (src/viscsolve.f90), which mac_multigrid routes through ml_cc_solve too; max_iter >= 0                        */
+int  vdn_cc_solve_alpha(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *alpha, vdn_multifab **beta, const double *dx,
+                        const int *bc /*[3][2]*/, double rel_eps, double abs_eps, int max_iter,
+                        int *cycles, double *res0, double *res);
 /* one red-black Gauss-Seidel sweep pair (nsweeps times) of that operator on the finest level --
  * the kernel the smoother roofline is quoted on                                                   */
 int  vdn_cc_smooth(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx,

@@ -102,9 +102,14 @@ def make_at_halftime(rhohalf, sold, snew, in_comp, out_comp, bct):
     check(capi.load().vdn_k_make_at_halftime(rhohalf.h, sold.h, snew.h, in_comp, out_comp, bct.h))
 
 
-def cc_solve(rh, phi, beta, dx, bc, rel_eps, abs_eps=-1.0, max_iter=100):
+def cc_solve(rh, phi, beta, dx, bc, rel_eps, abs_eps=-1.0, max_iter=100, alpha=None):
+    """alpha: a cell multifab -- (alpha - div beta grad) phi = rh, the solve of the viscous and diffusive steps"""
     cyc, r0, r = C.c_int(), C.c_double(), C.c_double()
     flat = _iv([bc[d][s] for d in range(3) for s in range(2)])
+    if alpha is not None:
+        check(capi.load().vdn_cc_solve_alpha(rh.h, phi.h, alpha.h, handle_array(beta), _dx(dx), flat, rel_eps, abs_eps, max_iter,
+                                             C.byref(cyc), C.byref(r0), C.byref(r)))
+        return cyc.value, r0.value, r.value
     check(capi.load().vdn_cc_solve(rh.h, phi.h, handle_array(beta), _dx(dx), flat, rel_eps, abs_eps, max_iter,
                                    C.byref(cyc), C.byref(r0), C.byref(r)))
     return cyc.value, r0.value, r.value

@@ -153,6 +153,7 @@ SIGNATURES = {
     "vdn_k_mkscalforce": (C.c_int, [_VP, _VP, _VP, C.c_double, _VP]),
     "vdn_k_make_at_halftime": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP]),
     "vdn_cc_solve": (C.c_int, [_VP, _VP, _PVP, _PD, _PI, C.c_double, C.c_double, C.c_int, _PI, _PD, _PD]),
+    "vdn_cc_solve_alpha": (C.c_int, [_VP, _VP, _VP, _PVP, _PD, _PI, C.c_double, C.c_double, C.c_int, _PI, _PD, _PD]),
     "vdn_cc_smooth": (C.c_int, [_VP, _VP, _PVP, _PD, _PI, C.c_int]),
     "vdn_nd_solve": (C.c_int, [_VP, _VP, _VP, _VP, _PD, _PI, C.c_double, C.c_double, C.c_int, _PI, _PD, _PD]),
     "vdn_bench_cc_smoother": (C.c_int, [_VP, _VP, _PVP, _VP, _PD, _PI, C.c_int, _PD, C.POINTER(C.c_long)]),

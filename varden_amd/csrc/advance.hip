@@ -389,6 +389,21 @@ extern "C" int vdn_cc_solve(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **
   if (rc != 0) vdn_fail("cc multigrid did not converge: %d cycles, residual %g (rhs %g)", q.cycles, q.res, q.res0);
   HOOK_END
 }
+// vdn_cc_solve with the alpha term of the viscous and diffusive solves: (alpha - div beta grad) phi = rh.  No nested iteration (those solves start from unew / snew).
+extern "C" int vdn_cc_solve_alpha(vdn_multifab *rh, vdn_multifab *phi, const vdn_multifab *alpha, vdn_multifab **beta, const double *dx, const int *bc,
+                                  double rel_eps, double abs_eps, int max_iter, int *cycles, double *res0, double *res) {
+  HOOK_BEGIN(rh)
+  REQUIRE(alpha && max_iter >= 0, "vdn_cc_solve_alpha: needs alpha and max_iter >= 0");
+  int b[3][2]; bc_from_flat(bc, b);
+  CcRequest q;
+  q.rh = rh; q.phi = phi; q.beta = beta; q.alpha = alpha; q.dx = dx; q.bc = b;
+  q.rel_eps = rel_eps; q.abs_eps = abs_eps; q.max_iter = max_iter;
+  const int rc = cc_solve(q);
+  if (cycles) *cycles = q.cycles; if (res0) *res0 = q.res0; if (res) *res = q.res;
+  arena_reset();
+  if (rc != 0) vdn_fail("cc multigrid (alpha) did not converge: %d cycles, residual %g (rhs %g)", q.cycles, q.res, q.res0);
+  HOOK_END
+}
 extern "C" int vdn_cc_smooth(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int *bc, int nsweeps) {
   HOOK_BEGIN(rh) int b[3][2]; bc_from_flat(bc, b); cc_smooth(rh, phi, beta, dx, b, nsweeps); HOOK_END
 }

@@ -27,6 +27,7 @@
 // BoxLib 2-D layout p(lo1-ng:hi1+ng, lo2-ng:hi2+ng, nc).
 #include "vdn_dev.h"
 #include "mg_stop.h"
+#include "krylov_wg.h"
 #include <vector>
 #include <algorithm>
 
@@ -237,6 +238,38 @@ __global__ void kk_c2_periodic(C2 L, int per0, int per1) {
   if (j < 0) { g = true; if (per1) sj = j + L.n1; else ok = false; } else if (j >= L.n1) { g = true; if (per1) sj = j - L.n1; else ok = false; }
   if (g && ok) L.phi[c2i(L, i, j)] = L.phi[c2i(L, si, sj)];
 }
+// ---- Krylov bottom solver (vdn_params.mg_bottom_solver = 1, 2, 3; krylov_wg.h) -- the 2-D counterpart of mg_cc.hip's CcKrylovOp ----
+// The V-cycles stop where an extent turns odd (200 -> 100 -> 50 -> 25) and there is no one-workgroup sweep kernel in this file: the 25^2 bottom takes
+// max(mg_nub, N^2) = 625 red-black sweeps of two to four launches each.  CG or BiCGStab by ONE workgroup in ONE launch takes their place.  c2_apply and the
+// level's arrays are used as they are; the Neumann / Dirichlet closures sit in bx / by and rely on ghost entries that read as zero (wg_krylov zeroes its
+// work arrays of the padded size c2_size; the periodic fill writes ghosts only along a periodic direction).
+DEVI void wg_c2_periodic(const C2 &L, int per0, int per1) {      // kk_c2_periodic by one workgroup; nothing without a periodic direction, else ends in a barrier
+  if (!per0 && !per1) return;
+  const int nx = L.n0 + 2, np = nx * (L.n1 + 2);
+  for (int t = threadIdx.x; t < np; t += blockDim.x) {
+    const int i = t % nx - 1, j = t / nx - 1;
+    int si = i, sj = j; bool g = false, ok = true;
+    if (i < 0) { g = true; if (per0) si = i + L.n0; else ok = false; } else if (i >= L.n0) { g = true; if (per0) si = i - L.n0; else ok = false; }
+    if (j < 0) { g = true; if (per1) sj = j + L.n1; else ok = false; } else if (j >= L.n1) { g = true; if (per1) sj = j - L.n1; else ok = false; }
+    if (g && ok) L.phi[c2i(L, i, j)] = L.phi[c2i(L, si, sj)];      // (the source is a cell of the level, never a ghost: no thread reads what another writes)
+  }
+  __syncthreads();
+}
+struct C2KrylovOp {
+  const C2 &L; int per0, per1, sing;
+  DEVI int count() const { return L.n0 * L.n1; }
+  DEVI bool point(int t, long &c, int &i, int &j, int &k) const { i = t % L.n0; j = t / L.n0; k = 0; c = c2i(L, i, j); return true; }
+  DEVI void apply(const double *v, long, int i, int j, int, double &Av, double &diag) const { C2 Lv = L; Lv.phi = const_cast<double *>(v); c2_apply(Lv, i, j, Av, diag); }
+  DEVI void fill(double *v) const { C2 Lv = L; Lv.phi = v; wg_c2_periodic(Lv, per0, per1); }
+  DEVI long size() const { return (long)(L.n0 + 2) * (L.n1 + 2); }
+  DEVI const double *rhs() const { return L.rh; }
+  DEVI double *x() const { return L.phi; }
+  DEVI bool singular() const { return sing != 0; }
+};
+__global__ void __launch_bounds__(1024) kk_c2_bottom_krylov(C2 L, KrylovArgs K, int method, int singular, int per0, int per1) {      // method: uniform over the launch
+  const C2KrylovOp op{ L, per0, per1, singular };
+  if (method == VDN_KRYLOV_CG) wg_krylov<VDN_KRYLOV_CG>(op, K); else wg_krylov<VDN_KRYLOV_BICGSTAB>(op, K);
+}
 struct C2Bc { int e[2][2]; int lo[2]; };               // elliptic boundary codes of the DOMAIN faces; lo: the domain's first cell
 struct C2Gx { C2 L; C2Bc B; int has_alpha; };           // what every box's load / store launch shares (kk_batched's `extra`)
 // The per-box descriptors of the gathered level (vdn_dev.h: kk_batched).  r: the points THIS box writes -- each point of the domain
@@ -305,7 +338,9 @@ static void gather_level(double *base, long ndoubles) {
   if (ctx().nranks > 1) comm_allreduce_max_u8_dev((unsigned char *)base, (size_t)ndoubles * sizeof(double));
 }
 static dim3 g2(int nx, int ny) { return dim3((nx + 63) / 64, (ny + 3) / 4, 1); }
-struct CC2MG { std::vector<C2> lev; int per[2]; double *d_nrm; };
+struct CC2MG { std::vector<C2> lev; int per[2]; double *d_nrm;
+  double *kry_w = nullptr; int kry_method = 0, kry_singular = 0, kry_maxit = 0; };      // Krylov bottom solver: its work arrays (nullptr = the bottom sweeps)
+static int krylov_method_of(int b) { return (b == 1 || b == 3) ? VDN_KRYLOV_BICGSTAB : (b == 2 ? VDN_KRYLOV_CG : 0); }
 static void c2_gsrb(const CC2MG &M, const C2 &L, int ns) {
   hipStream_t st = ctx().stream;
   for (int s = 0; s < ns; s++) for (int col = 0; col < 2; col++) {
@@ -324,7 +359,13 @@ static void c2_vcycle(const CC2MG &M, int l) {
   const vdn_params &P = ctx().prm;
   const C2 &L = M.lev[l];
   HIPCHK(hipMemsetAsync(L.phi, 0, sizeof(double) * c2_size(L.n0, L.n1), ctx().stream));
-  if (l == (int)M.lev.size() - 1) { c2_gsrb(M, L, c2_bottom(L)); return; }
+  if (l == (int)M.lev.size() - 1) {
+    if (M.kry_w) {
+      const KrylovArgs K{ M.kry_w, bottom_stats_dev(0), P.mg_bottom_solver_eps, M.kry_maxit };
+      hipLaunchKernelGGL(kk_c2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry_method, M.kry_singular, M.per[0], M.per[1]);
+    } else c2_gsrb(M, L, c2_bottom(L));
+    return;
+  }
   const C2 &C = M.lev[l + 1];
   c2_gsrb(M, L, P.mg_nu1);
   c2_residual(M, L, false);
@@ -355,6 +396,19 @@ int cc2_solve(CcRequest &rq) {
     M.lev.push_back(L);
     if ((n0 & 1) || (n1 & 1) || n0 <= 2 || n1 <= 2 || M.lev.size() >= 31) break;
     n0 /= 2; n1 /= 2; h0 *= 2.0; h1 *= 2.0;
+  }
+  // Krylov bottom solver: on the last level of a hierarchy of more than one level (a one-level hierarchy -- an odd extent on the finest level -- keeps its sweeps);
+  // the statistics are those of this solve
+  const int method = krylov_method_of(ctx().prm.mg_bottom_solver);
+  if (method) bottom_stats_reset(0);
+  if (method && M.lev.size() > 1) {
+    const C2 &B = M.lev.back();
+    M.kry_method = method;
+    M.kry_w = (double *)arena_alloc(sizeof(double) * c2_size(B.n0, B.n1) * (method == VDN_KRYLOV_CG ? 4 : 7));
+    bool dir = false;
+    for (int d = 0; d < 2; d++) for (int sd = 0; sd < 2; sd++) if (bc[d][sd] == VDN_BC_DIR) dir = true;
+    M.kry_singular = (!alpha && !dir) ? 1 : 0;
+    M.kry_maxit = 12 * std::max(B.n0, B.n1);
   }
   C2Gx X; X.L = M.lev[0]; X.has_alpha = alpha ? 1 : 0;
   for (int d = 0; d < 2; d++) { X.B.lo[d] = pd.lo[d]; for (int s = 0; s < 2; s++) X.B.e[d][s] = bc[d][s]; }
@@ -665,6 +719,41 @@ __global__ void kk_n2_coarsen_sigma(N2 F, N2 C) {
   for (int b = 0; b < 2; b++) for (int a = 0; a < 2; a++) s = s + F.sig[s2i(F, 2 * i + a, 2 * j + b)];
   C.sig[s2i(C, i, j)] = s * 0.25;
 }
+// ---- Krylov bottom solver (vdn_params.hg_bottom_solver = 1, 2, 3; krylov_wg.h) -- the 2-D counterpart of mg_nd.hip's NdKrylovOp ----
+// The 26^2-node bottom of a 200^2 problem takes max(hg_nub, 2 N^2) = 1250 Jacobi sweeps of two launches each.  K as n2_apply returns it is symmetric positive
+// semi-definite with a positive diagonal.  Dirichlet (outflow) nodes are not unknowns; along a periodic direction node n is the image of node 0, written by the
+// fill only and counted once.  The sigma = 0 ring beyond a physical face is the wall closure and the node ring there reads as zero (the fill writes it).  The
+// solve starts from phi = 0 and leaves its result in the array L.phi names at the launch (no ping-pong: the host's phi / tmp swap is that of zero sweeps).
+DEVI void wg_n2_fill_nodes(const N2 &L, double *a, int per0, int per1) {      // kk_n2_fill_nodes by one workgroup; ends in a barrier
+  const int nx = L.n0 + 3, np = nx * (L.n1 + 3);
+  for (int t = threadIdx.x; t < np; t += blockDim.x) {
+    const int i = t % nx - 1, j = t / nx - 1;
+    int si = i, sj = j; bool g = false, zero = false;
+    if (per0) { if (i < 0) { si = i + L.n0; g = true; } else if (i >= L.n0) { si = i - L.n0; g = true; } } else if (i < 0 || i > L.n0) { g = true; zero = true; }
+    if (per1) { if (j < 0) { sj = j + L.n1; g = true; } else if (j >= L.n1) { sj = j - L.n1; g = true; } } else if (j < 0 || j > L.n1) { g = true; zero = true; }
+    if (g) a[n2i(L, i, j)] = zero ? 0.0 : a[n2i(L, si, sj)];      // (the source is a node no thread writes: below n along a periodic direction, on the level along the other)
+  }
+  __syncthreads();
+}
+struct N2KrylovOp {
+  const N2 &L; int per0, per1;
+  DEVI int count() const { return (L.n0 + 1) * (L.n1 + 1); }
+  DEVI bool point(int t, long &c, int &i, int &j, int &k) const {
+    const int nx = L.n0 + 1;
+    i = t % nx; j = t / nx; k = 0; c = n2i(L, i, j);
+    return !n2_dir(L, i, j) && !((per0 && i == L.n0) || (per1 && j == L.n1));
+  }
+  DEVI void apply(const double *v, long, int i, int j, int, double &Av, double &diag) const { n2_apply(L, v, i, j, Av, diag); }
+  DEVI void fill(double *v) const { wg_n2_fill_nodes(L, v, per0, per1); }
+  DEVI long size() const { return (long)(L.n0 + 3) * (L.n1 + 3); }
+  DEVI const double *rhs() const { return L.b; }
+  DEVI double *x() const { return L.phi; }
+  DEVI bool singular() const { return !(L.dirlo[0] || L.dirlo[1] || L.dirhi[0] || L.dirhi[1]); }
+};
+__global__ void __launch_bounds__(1024) kk_n2_bottom_krylov(N2 L, KrylovArgs K, int method, int per0, int per1) {      // method: uniform over the launch
+  const N2KrylovOp op{ L, per0, per1 };
+  if (method == VDN_KRYLOV_CG) wg_krylov<VDN_KRYLOV_CG>(op, K); else wg_krylov<VDN_KRYLOV_BICGSTAB>(op, K);
+}
 struct N2Gx { N2 L; int lo[2]; };                      // lo: the domain's first cell / node
 // gathered level (see cc2_solve): sigma on the box's cells, grown by the ghost cell at the domain's sides (the ring the smoother reads there)
 struct N2LoadSig { Range3 r; int g[3]; FV coeffs;
@@ -696,7 +785,8 @@ struct nd_divu2_K { FV u, rh; double gx, gy;
     const double duy = (G2(u, i, j, 1) + G2(u, i - 1, j, 1)) - (G2(u, i, j - 1, 1) + G2(u, i - 1, j - 1, 1));
     P2(rh, i, j, 0) = G2(rh, i, j, 0) + (dux * gx + duy * gy);
   } };
-struct ND2MG { std::vector<N2> lev; int per[2]; double *d_nrm; };
+struct ND2MG { std::vector<N2> lev; int per[2]; double *d_nrm;
+  double *kry_w = nullptr; int kry_method = 0, kry_maxit = 0; };      // Krylov bottom solver: its work arrays (nullptr = the bottom sweeps)
 static long n2_nsize(int n0, int n1) { return (long)(n0 + 3) * (n1 + 3); }
 static void n2_fill(const ND2MG &M, const N2 &L, double *a) { hipLaunchKernelGGL(kk_n2_fill_nodes, g2(L.n0 + 3, L.n1 + 3), B2, 0, ctx().stream, L, a, M.per[0], M.per[1]); }
 static void n2_jacobi(const ND2MG &M, N2 &L, int ns) {
@@ -717,7 +807,13 @@ static void n2_vcycle(ND2MG &M, int l) {
   const vdn_params &P = ctx().prm;
   N2 &L = M.lev[l];
   HIPCHK(hipMemsetAsync(L.phi, 0, sizeof(double) * n2_nsize(L.n0, L.n1), ctx().stream));
-  if (l == (int)M.lev.size() - 1) { n2_jacobi(M, L, n2_bottom(L)); return; }
+  if (l == (int)M.lev.size() - 1) {
+    if (M.kry_w) {      // (L.phi as it stands now: the sweeps above this level may have swapped phi and tmp, the Krylov solve swaps nothing)
+      const KrylovArgs K{ M.kry_w, bottom_stats_dev(1), P.hg_bottom_solver_eps, M.kry_maxit };
+      hipLaunchKernelGGL(kk_n2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry_method, M.per[0], M.per[1]);
+    } else n2_jacobi(M, L, n2_bottom(L));
+    return;
+  }
   N2 &C = M.lev[l + 1];
   n2_jacobi(M, L, P.hg_nu1);
   n2_residual(M, L, false);
@@ -750,6 +846,15 @@ int nd2_solve(NdRequest &rq) {
     M.lev.push_back(L);
     if ((n0 & 1) || (n1 & 1) || n0 <= 2 || n1 <= 2 || M.lev.size() >= 31) break;
     n0 /= 2; n1 /= 2; h0 *= 2.0; h1 *= 2.0;
+  }
+  // Krylov bottom solver: as in cc2_solve (more than one level; the statistics are those of this solve)
+  const int method = krylov_method_of(ctx().prm.hg_bottom_solver);
+  if (method) bottom_stats_reset(1);
+  if (method && M.lev.size() > 1) {
+    const N2 &B = M.lev.back();
+    M.kry_method = method;
+    M.kry_w = (double *)arena_alloc(sizeof(double) * n2_nsize(B.n0, B.n1) * (method == VDN_KRYLOV_CG ? 4 : 7));
+    M.kry_maxit = 12 * (std::max(B.n0, B.n1) + 1);
   }
   N2 &L0 = M.lev[0];
   N2Gx X; X.L = L0; X.lo[0] = pd.lo[0]; X.lo[1] = pd.lo[1];
