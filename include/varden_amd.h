@@ -101,8 +101,11 @@ typedef struct vdn_params {
    *   1, 3:         BiCGStab (3 is FBoxLib's communication-avoiding variant: it differs in communication only, and one workgroup has none).
    *   2:            conjugate gradients.
    *   anything else: vdn_init fails.
-   * Both Krylov methods are preconditioned by the operator's diagonal, start from zero, run in ONE workgroup, stop when the max-norm of the residual has
-   * fallen by *_bottom_solver_eps relative to the bottom right-hand side, and are capped at 12 N iterations.  A breakdown (rho or omega zero or not
+   * Both Krylov methods are preconditioned by the operator's diagonal, start from zero, stop when the max-norm of the residual has fallen by
+   * *_bottom_solver_eps relative to the bottom right-hand side, and are capped at 12 N iterations.  A bottom level of fewer than 4913 = 17^3 points (cells, or
+   * nodes) is solved by ONE workgroup in one launch (csrc/krylov_wg.h); a larger one -- 75^3 cells under n_cell = 150 or 300, 125^3 under 250 or 500 -- by
+   * the whole GPU, the same iteration as a fixed sequence of plain launches per visit (csrc/krylov_grid.h; dm = 3 only; vdn_last_bottom_form tells which).
+   * A breakdown (rho or omega zero or not
    * finite, p.Ap <= 0) leaves the last iterate, is counted (vdn_last_bottom_stats) and the V-cycle goes on.  They apply where one rank holds the whole
    * bottom level: the last level of a one-box hierarchy and of the replicated tail (any boxes, any ranks; level 0 of a composite solve included), and
    * the last level of both dm = 2 multigrids (any boxes, any ranks: they work on a gathered level that every rank holds whole).  A bottom level still
@@ -366,6 +369,10 @@ int  vdn_last_solver_stats(int which /*0=MAC,1=HG*/, int *cycles, double *res0, 
  * the bottom level, iterations in all, the most in one visit, breakdowns.  All zero with the bottom sweeps.  A composite solve counts all its cycles on level 0.
  * Reads four numbers back from the device (drains the launch stream); any pointer may be NULL. */
 int  vdn_last_bottom_stats(int which /*0=cell-centred,1=nodal*/, int *calls, int *iters, int *max_iters, int *breakdowns);
+/* what the last cell-centred (which = 0) / nodal (which = 1) solve ran at its bottom level: 0 the bottom sweeps, 1 a Krylov solver in one workgroup
+ * (csrc/krylov_wg.h), 2 the same solver over the whole GPU (csrc/krylov_grid.h: bottom levels of 4913 points and more).  -1: which is neither 0 nor 1.
+ * vdn_last_bottom_stats counts either form.  No reference counterpart. */
+int  vdn_last_bottom_form(int which /*0=cell-centred,1=nodal*/);
 /* how the last macproject solve on one box kept its finest level: 0 interleaved (the level array), 1 by colour (passes and residual on the
  * split arrays).  No reference counterpart: the tests use it to know which kernels they exercised. */
 int  vdn_last_mac_level_form(void);

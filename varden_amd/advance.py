@@ -67,6 +67,11 @@ def last_bottom_stats(which):
     return dict(calls=v[0].value, iters=v[1].value, max_iters=v[2].value, breakdowns=v[3].value)
 
 
+def last_bottom_form(which):
+    """what the last cell-centred ("mac") / nodal ("hg") solve ran at its bottom level: 0 the sweeps, 1 a Krylov solver in one workgroup, 2 over the whole GPU"""
+    return int(capi.load().vdn_last_bottom_form(0 if which == "mac" else 1))
+
+
 # ---- per-kernel modules (single level) ------------------------------------------------------------
 def _iv(x):
     return (C.c_int * len(x))(*[int(v) for v in x])

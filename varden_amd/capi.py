@@ -144,6 +144,7 @@ SIGNATURES = {
     "vdn_last_step_timing": (C.c_int, [_PD]),
     "vdn_last_solver_stats": (C.c_int, [C.c_int, _PI, _PD, _PD]),
     "vdn_last_bottom_stats": (C.c_int, [C.c_int, _PI, _PI, _PI, _PI]),
+    "vdn_last_bottom_form": (C.c_int, [C.c_int]),
     "vdn_last_mac_level_form": (C.c_int, []),
     "vdn_k_slope": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP]),
     "vdn_k_velpred": (C.c_int, [_VP, _PVP, _VP, _PD, C.c_double, _VP]),

@@ -401,6 +401,7 @@ int cc2_solve(CcRequest &rq) {
   // the statistics are those of this solve
   const int method = krylov_method_of(ctx().prm.mg_bottom_solver);
   if (method) bottom_stats_reset(0);
+  bottom_form_set(0, (method && M.lev.size() > 1) ? 1 : 0);      // dm = 2: always one workgroup (a 75^2 bottom is 5625 cells)
   if (method && M.lev.size() > 1) {
     const C2 &B = M.lev.back();
     M.kry_method = method;
@@ -850,6 +851,7 @@ int nd2_solve(NdRequest &rq) {
   // Krylov bottom solver: as in cc2_solve (more than one level; the statistics are those of this solve)
   const int method = krylov_method_of(ctx().prm.hg_bottom_solver);
   if (method) bottom_stats_reset(1);
+  bottom_form_set(1, (method && M.lev.size() > 1) ? 1 : 0);
   if (method && M.lev.size() > 1) {
     const N2 &B = M.lev.back();
     M.kry_method = method;

@@ -15,6 +15,7 @@
 #include "vdn_dev.h"
 #include "mg_stop.h"
 #include "krylov_wg.h"
+#include "krylov_grid.h"
 #include <chrono>
 #include <tuple>
 #include <algorithm>
@@ -699,20 +700,28 @@ __global__ void __launch_bounds__(1024) kk_cc_bottom(CLev L, int nsweeps, int pe
 // kk_cc_bottom / cc_residual_body / kk_cc_restrict / kk_cc_prolong in the same order with barriers where the launches ended.
 #define CC_TAIL_MAX 4
 struct CcTailArgs { CLev L[CC_TAIL_MAX]; int nlev, nu1, nu2, nbot, per[3]; };
+// the periodic images of phi, one at a time: entry t of 6 faces of m x m, m the largest extent (wg_cc_periodic here, kg_fill in krylov_grid.h)
+DEVI int cc_periodic_count(const CLev &L, const int per[3]) {
+  if (!(per[0] || per[1] || per[2])) return 0;
+  const int m = max(L.n[0], max(L.n[1], L.n[2]));
+  return 6 * m * m;
+}
+DEVI void cc_periodic_point(const CLev &L, const int per[3], int t) {
+  const int m = max(L.n[0], max(L.n[1], L.n[2]));
+  const int face = t / (m * m), a = (t / m) % m, b = t % m;
+  const int d = face >> 1, sd = face & 1;
+  const int t1 = (d == 0) ? 1 : 0, t2 = (d == 2) ? 1 : 2;
+  if (per[d] && a < L.n[t1] && b < L.n[t2]) {
+    int g[3], q[3];
+    g[t1] = q[t1] = a; g[t2] = q[t2] = b;
+    g[d] = sd ? L.n[d] : -1; q[d] = sd ? 0 : L.n[d] - 1;
+    L.phi[cidx(L, g[0], g[1], g[2])] = L.phi[cidx(L, q[0], q[1], q[2])];
+  }
+}
 DEVI void wg_cc_periodic(const CLev &L, const int per[3]) {
   if (!(per[0] || per[1] || per[2])) return;
-  const int m = max(L.n[0], max(L.n[1], L.n[2]));
-  for (int t = threadIdx.x; t < 6 * m * m; t += blockDim.x) {
-    const int face = t / (m * m), a = (t / m) % m, b = t % m;
-    const int d = face >> 1, sd = face & 1;
-    const int t1 = (d == 0) ? 1 : 0, t2 = (d == 2) ? 1 : 2;
-    if (per[d] && a < L.n[t1] && b < L.n[t2]) {
-      int g[3], q[3];
-      g[t1] = q[t1] = a; g[t2] = q[t2] = b;
-      g[d] = sd ? L.n[d] : -1; q[d] = sd ? 0 : L.n[d] - 1;
-      L.phi[cidx(L, g[0], g[1], g[2])] = L.phi[cidx(L, q[0], q[1], q[2])];
-    }
-  }
+  const int nt = cc_periodic_count(L, per);
+  for (int t = threadIdx.x; t < nt; t += blockDim.x) cc_periodic_point(L, per, t);
   __syncthreads();
 }
 DEVI void wg_cc_gsrb(const CLev &L, int nsweeps, const int per[3]) {
@@ -786,6 +795,8 @@ struct CcKrylovOp {
   DEVI bool point(int t, long &c, int &i, int &j, int &k) const { i = t % L.n[0]; j = (t / L.n[0]) % L.n[1]; k = t / (L.n[0] * L.n[1]); c = cidx(L, i, j, k); return true; }
   DEVI void apply(const double *v, long c, int, int, int, double &Av, double &diag) const { CLev Lv = L; Lv.phi = const_cast<double *>(v); cc_apply(Lv, c, Av, diag); }
   DEVI void fill(double *v) const { CLev Lv = L; Lv.phi = v; wg_cc_periodic(Lv, per); }
+  DEVI int fill_count() const { return cc_periodic_count(L, per); }
+  DEVI void fill_point(double *v, int t) const { CLev Lv = L; Lv.phi = v; cc_periodic_point(Lv, per, t); }
   DEVI long size() const { return L.sz; }
   DEVI const double *rhs() const { return L.rh; }
   DEVI double *x() const { return L.phi; }
@@ -802,6 +813,11 @@ __global__ void __launch_bounds__(1024) kk_cc_bottom_krylov(CLev L, KrylovArgs K
   const int per[3] = { per0, per1, per2 };
   wg_cc_krylov_any(method, L, per, singular, K);
 }
+// the level as the grid-wide form takes it (krylov_grid.h): by value, for bottom levels of VDN_KRYLOV_GRID_MIN_POINTS cells and more
+struct CcKrylovLevel {
+  CLev L; int per[3]; int sing;
+  DEVI CcKrylovOp op() const { return CcKrylovOp{ L, per, sing }; }
+};
 // kk_cc_tailcycle with the Krylov solve in place of the nbot sweeps
 __global__ void __launch_bounds__(1024) kk_cc_tailcycle_krylov(CcTailArgs T, KrylovArgs K, int method, int singular) {
   #pragma unroll
@@ -1182,6 +1198,8 @@ struct CCMG {
   std::vector<long> loc_off_rh, loc_off_b;                                       // offsets of my boxes inside my send buffer
   // Krylov bottom solver (mg_bottom_solver = 1, 2, 3): its work arrays, of the bottom level's padded size; nullptr = the bottom sweeps
   double *kry_w = nullptr; int kry_method = 0, kry_singular = 0, kry_maxit = 0;
+  // ... its grid-wide form (krylov_grid.h) on a bottom level of VDN_KRYLOV_GRID_MIN_POINTS cells or more: partial sums and state blocks; the iterations a visit launches
+  double *kry_part = nullptr; int kry_budget = 0; unsigned long long kry_kind = 0;
 };
 
 static dim3 g3(int nx, int ny, int nz, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, nz); }
@@ -1449,9 +1467,26 @@ static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const in
     for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) if (bc[d][sd] == VDN_BC_DIR) dir = true;
     M.kry_singular = (!has_alpha && !dir) ? 1 : 0;
     M.kry_maxit = 12 * std::max(bottom->n[0], std::max(bottom->n[1], bottom->n[2]));
+    if ((long)bottom->n[0] * bottom->n[1] * bottom->n[2] >= VDN_KRYLOV_GRID_MIN_POINTS) {
+      M.kry_part = (double *)arena_alloc(sizeof(double) * KG_DOUBLES);
+      GraphKey k; k.put(0); k.put(method); k.put(bottom->n); k.put(has_alpha); k.put(M.kry_singular); k.put(ctx().prm.mg_bottom_solver_eps);
+      M.kry_kind = k.h | 1ull;
+      M.kry_budget = M.kry_maxit;
+    }
   }
 }
 static KrylovArgs cc_krylov_args(const CCMG &M) { return KrylovArgs{ M.kry_w, bottom_stats_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry_maxit }; }
+// one visit of the bottom level L by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU
+static void cc_krylov_visit(const CCMG &M, const CLev &L) {
+  if (!M.kry_part) { hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, cc_krylov_args(M), M.kry_method, M.kry_singular, M.per[0], M.per[1], M.per[2]); return; }
+  const CcKrylovLevel lv{ L, { M.per[0], M.per[1], M.per[2] }, M.kry_singular };
+  const KrylovGridArgs K{ M.kry_w, M.kry_part, bottom_stats_dev(0), bottom_exhausted_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry_maxit };
+  const long np = (long)L.n[0] * L.n[1] * L.n[2];
+  const long m = std::max(L.n[0], std::max(L.n[1], L.n[2]));
+  const long nfill = (M.per[0] || M.per[1] || M.per[2]) ? 6 * m * m : 0;
+  if (M.kry_method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry_budget, ctx().stream);
+  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry_budget, ctx().stream);
+}
 
 static void cc_halo(CCMG &M, CDLev &DL) { if (DL.halo) xplan_run(DL.halo); }
 // levels of at most 8^3 cells held in ONE box are smoothed by a single workgroup in one launch (all sweeps, both
@@ -1562,7 +1597,7 @@ static void cc_gsrb_t(const CCMG &M, const CLev &L, int nsweeps) {
   }
 }
 static void cc_bottom_t(const CCMG &M, const CLev &L) {      // max(nub, N^2) sweeps, N = largest extent (same rule as the oracle)
-  if (M.kry_w) { hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, cc_krylov_args(M), M.kry_method, M.kry_singular, M.per[0], M.per[1], M.per[2]); return; }
+  if (M.kry_w) { cc_krylov_visit(M, L); return; }
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.mg_nub, N * N);
   hipLaunchKernelGGL(kk_cc_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, ns, M.per[0], M.per[1], M.per[2]);
@@ -1761,7 +1796,7 @@ static void cc_vcycle_d(CCMG &M, int l) {
   if (cc_small_end(M, l, 0)) return;
   if (last && M.tail.empty()) {         // nothing below: bottom sweeps on the distributed level itself
     if (M.kry_w && DL.single_box && DL.boxes.size() == 1) {      // (one box: the Krylov bottom solver, when one is selected; several boxes keep the sweeps)
-      hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, DL.boxes[0].L, cc_krylov_args(M), M.kry_method, M.kry_singular, M.per[0], M.per[1], M.per[2]);
+      cc_krylov_visit(M, DL.boxes[0].L);
       return;
     }
     const int N = std::max(DL.ng[0], std::max(DL.ng[1], DL.ng[2]));     // largest GLOBAL extent, as in the oracle
@@ -1895,6 +1930,7 @@ static unsigned long long cc_graph_key(const CCMG &M, int what) {
   for (const CLev &L : M.tail) cc_key_lev(k, L);
   for (long o : M.loc_off_rh) k.put(o);
   if (M.kry_w) { k.put(M.kry_w); k.put(M.kry_method); k.put(M.kry_singular); k.put(M.kry_maxit); k.put(P.mg_bottom_solver_eps); }
+  if (M.kry_part) { k.put(M.kry_part); k.put(M.kry_budget); }
   return k.h;
 }
 template <class Body> static void cc_run_cycle(CCMG &M, int what, Body body) {
@@ -2083,7 +2119,10 @@ int cc_solve(CcRequest &q) {
     else if (!keep && !fixed && q.alpha && q.const_beta > 0.0 && cc_split_ok(M)) { cc_split_setup(M); g_mac_level_form = 1; }      // (phi goes over after the nested iteration, below)
   }
   // the bottom statistics are those of one solve (a composite solve: of all the cycles it runs on its kept hierarchy)
-  if (M.kry_w && (!fixed || !(keep && keep->built))) bottom_stats_reset(0);
+  if (!fixed || !(keep && keep->built)) {
+    bottom_form_set(0, M.kry_w ? (M.kry_part ? 2 : 1) : 0);
+    if (M.kry_w) { const int budget = bottom_budget_begin(0, M.kry_kind, M.kry_maxit); if (M.kry_part) M.kry_budget = budget; bottom_stats_reset(0); }
+  }
   if (keep) keep->built = true;
   CDLev &D0 = M.dlev[0];
   const bool single = (M.dlev.size() == 1 && M.tail.empty());

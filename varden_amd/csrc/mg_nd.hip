@@ -14,6 +14,7 @@
 #include "vdn_dev.h"
 #include "mg_stop.h"
 #include "krylov_wg.h"
+#include "krylov_grid.h"
 #include <tuple>
 #include <algorithm>
 
@@ -723,19 +724,22 @@ __global__ void __launch_bounds__(1024) kk_nd_bottom(NLev L, double *a, double *
 // L[0] is entered like any level of nd_vcycle_d (b set, phi = 0) and left with its correction in the array the host's swap parity names.
 #define ND_TAIL_MAX 4
 struct NdTailArgs { NLev L[ND_TAIL_MAX]; int nlev, nu1, nu2, nbot; double omega, om1, om2; int nsp; };      // om1, om2, nsp: the pre-smoothing sweeps' damping (NdOm)
-DEVI void wg_nd_fill(const NLev &L, double *a) {                     // nd_fill_nodes; ghost nodes outside a physical face stay zero
-  if (!(L.per[0] || L.per[1] || L.per[2])) return;
-  const int ex = L.n[0] + 3, ey = L.n[1] + 3, ez = L.n[2] + 3;
-  for (int t = threadIdx.x; t < ex * ey * ez; t += blockDim.x) {
-    const int i = t % ex - 1, j = (t / ex) % ey - 1, k = t / (ex * ey) - 1;
-    int q[3] = { i, j, k }, sidx[3] = { i, j, k }; bool g = false, zero = false;
-    for (int d = 0; d < 3; d++) {
-      if (L.per[d]) { if (q[d] < 0) { sidx[d] = q[d] + L.n[d]; g = true; } else if (q[d] >= L.n[d]) { sidx[d] = q[d] - L.n[d]; g = true; } }
-      else if (q[d] < 0 || q[d] > L.n[d]) { g = true; zero = true; }
-    }
-    if (g) a[nidx(L, i, j, k)] = zero ? 0.0 : a[nidx(L, sidx[0], sidx[1], sidx[2])];
+// nd_fill_nodes one entry at a time: entry t of the node array grown by one (wg_nd_fill here, kg_fill in krylov_grid.h)
+DEVI int nd_fill_count(const NLev &L) { return (L.per[0] || L.per[1] || L.per[2]) ? (L.n[0] + 3) * (L.n[1] + 3) * (L.n[2] + 3) : 0; }
+DEVI void nd_fill_point(const NLev &L, double *a, int t) {
+  const int ex = L.n[0] + 3, ey = L.n[1] + 3;
+  const int i = t % ex - 1, j = (t / ex) % ey - 1, k = t / (ex * ey) - 1;
+  int q[3] = { i, j, k }, sidx[3] = { i, j, k }; bool g = false, zero = false;
+  for (int d = 0; d < 3; d++) {
+    if (L.per[d]) { if (q[d] < 0) { sidx[d] = q[d] + L.n[d]; g = true; } else if (q[d] >= L.n[d]) { sidx[d] = q[d] - L.n[d]; g = true; } }
+    else if (q[d] < 0 || q[d] > L.n[d]) { g = true; zero = true; }
   }
-  __syncthreads();
+  if (g) a[nidx(L, i, j, k)] = zero ? 0.0 : a[nidx(L, sidx[0], sidx[1], sidx[2])];
+}
+DEVI void wg_nd_fill(const NLev &L, double *a) {                     // nd_fill_nodes; ghost nodes outside a physical face stay zero
+  const int nt = nd_fill_count(L);
+  for (int t = threadIdx.x; t < nt; t += blockDim.x) nd_fill_point(L, a, t);
+  if (nt) __syncthreads();
 }
 DEVI void wg_nd_jacobi(const NLev &L, double *&src, double *&dst, int nsweeps, double omega, double om1 = 0.0, double om2 = 0.0, int nsp = 0) {
   const int nx = L.n[0] + 1, ny = L.n[1] + 1, nz = L.n[2] + 1;
@@ -826,6 +830,8 @@ struct NdKrylovOp {
   }
   DEVI void apply(const double *v, long, int i, int j, int k, double &Av, double &diag) const { nd_apply(L, v, i, j, k, Av, diag); }
   DEVI void fill(double *v) const { wg_nd_fill(L, v); }
+  DEVI int fill_count() const { return nd_fill_count(L); }
+  DEVI void fill_point(double *v, int t) const { nd_fill_point(L, v, t); }
   DEVI long size() const { return L.sz; }
   DEVI const double *rhs() const { return L.b; }
   DEVI double *x() const { return phi; }
@@ -839,6 +845,11 @@ DEVI void wg_nd_krylov_any(int method, const NLev &L, double *phi, const KrylovA
   if (method == VDN_KRYLOV_CG) wg_nd_krylov<VDN_KRYLOV_CG>(L, phi, K); else wg_nd_krylov<VDN_KRYLOV_BICGSTAB>(L, phi, K);
 }
 __global__ void __launch_bounds__(1024) kk_nd_bottom_krylov(NLev L, double *phi, KrylovArgs K, int method) { wg_nd_krylov_any(method, L, phi, K); }
+// the level as the grid-wide form takes it (krylov_grid.h): by value, for bottom levels of VDN_KRYLOV_GRID_MIN_POINTS nodes and more
+struct NdKrylovLevel {
+  NLev L; double *phi;
+  DEVI NdKrylovOp op() const { return NdKrylovOp{ L, phi }; }
+};
 // kk_nd_tailcycle with the Krylov solve in place of the nbot sweeps
 __global__ void __launch_bounds__(1024) kk_nd_tailcycle_krylov(NdTailArgs T, KrylovArgs K, int method) {
   double *ph[ND_TAIL_MAX], *tm[ND_TAIL_MAX];
@@ -1102,6 +1113,8 @@ struct NDMG {
   std::vector<long> loc_off_nodes, loc_off_cells;
   // Krylov bottom solver (hg_bottom_solver = 1, 2, 3): its work arrays, of the bottom level's padded size; nullptr = the bottom sweeps
   double *kry_w = nullptr; int kry_method = 0, kry_maxit = 0;
+  // ... its grid-wide form (krylov_grid.h) on a bottom level of VDN_KRYLOV_GRID_MIN_POINTS nodes or more: partial sums and state blocks; the iterations a visit launches
+  double *kry_part = nullptr; int kry_budget = 0; unsigned long long kry_kind = 0;
 };
 
 struct NdHaloKey { unsigned long uid; const void *p0; int lev, l, which, per; unsigned long long sig; bool operator<(const NdHaloKey &o) const {
@@ -1258,9 +1271,26 @@ static void nd_build(NDMG &M, const vdn_multifab *coeffs, const double *dx, cons
     M.kry_method = method;
     M.kry_w = (double *)arena_alloc(sizeof(double) * bottom->sz * (method == VDN_KRYLOV_CG ? 4 : 7));
     M.kry_maxit = 12 * (std::max(bottom->n[0], std::max(bottom->n[1], bottom->n[2])) + 1);
+    if ((long)(bottom->n[0] + 1) * (bottom->n[1] + 1) * (bottom->n[2] + 1) >= VDN_KRYLOV_GRID_MIN_POINTS) {
+      M.kry_part = (double *)arena_alloc(sizeof(double) * KG_DOUBLES);
+      GraphKey k; k.put(1); k.put(method); k.put(bottom->n); k.put(bottom->dirlo); k.put(bottom->dirhi); k.put(ctx().prm.hg_bottom_solver_eps);
+      M.kry_kind = k.h | 1ull;
+      M.kry_budget = M.kry_maxit;
+    }
   }
 }
 static KrylovArgs nd_krylov_args(const NDMG &M) { return KrylovArgs{ M.kry_w, bottom_stats_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry_maxit }; }
+// one visit of the bottom level L (its periodic flags set) by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU; the result is left in phi
+static void nd_krylov_visit(const NDMG &M, const NLev &L, double *phi) {
+  if (!M.kry_part) { hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, phi, nd_krylov_args(M), M.kry_method); return; }
+  const NdKrylovLevel lv{ L, phi };
+  const KrylovGridArgs K{ M.kry_w, M.kry_part, bottom_stats_dev(1), bottom_exhausted_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry_maxit };
+  const long np = (long)(L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1);
+  const long nfill = (L.per[0] || L.per[1] || L.per[2]) ? (long)(L.n[0] + 3) * (L.n[1] + 3) * (L.n[2] + 3) : 0;
+  const bool singular = !(L.dirlo[0] || L.dirlo[1] || L.dirlo[2] || L.dirhi[0] || L.dirhi[1] || L.dirhi[2]);
+  if (M.kry_method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, singular, M.kry_budget, ctx().stream);
+  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, singular, M.kry_budget, ctx().stream);
+}
 
 // ---- distributed levels ------------------------------------------------------------------------------------------
 static void nd_halo_phi(NDLev &DL) { XPlan *P = DL.flip ? DL.halo_B : DL.halo_A; if (P) xplan_run(P); }
@@ -1377,7 +1407,7 @@ static void nd_jacobi_t(NLev &L, int nsweeps, bool pre = false) {
   }
 }
 static void nd_bottom_t(const NDMG &M, NLev &L) {          // max(nub, 2 N^2) sweeps (same rule as the oracle)
-  if (M.kry_w) { hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, L.phi, nd_krylov_args(M), M.kry_method); return; }
+  if (M.kry_w) { nd_krylov_visit(M, L, L.phi); return; }
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.hg_nub, 2 * N * N);
   hipLaunchKernelGGL(kk_nd_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, L.phi, L.tmp, ns, ctx().prm.hg_omega);
@@ -1513,7 +1543,7 @@ static void nd_vcycle_d(NDMG &M, int l) {
     NBox &B = DL.boxes[0];
     NLev Lp = B.L;                      // (as nd_jacobi_d: the kernel refreshes periodic images itself)
     for (int d = 0; d < 3; d++) Lp.per[d] = DL.per[d];
-    hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, Lp, B.L.phi, nd_krylov_args(M), M.kry_method);
+    nd_krylov_visit(M, Lp, B.L.phi);
     return;
   }
   if (last && M.tail.empty()) { nd_jacobi_d(DL, nd_bottom_sweeps_global(DL)); return; }
@@ -1608,6 +1638,7 @@ static unsigned long long nd_graph_key(const NDMG &M, int what) {
   for (const NLev &L : M.tail) nd_key_lev(k, L);
   for (long o : M.loc_off_nodes) k.put(o);
   if (M.kry_w) { k.put(M.kry_w); k.put(M.kry_method); k.put(M.kry_maxit); k.put(P.hg_bottom_solver_eps); }
+  if (M.kry_part) { k.put(M.kry_part); k.put(M.kry_budget); }
   return k.h;
 }
 static std::map<unsigned long long, NDMG> g_nd_post;
@@ -1657,6 +1688,10 @@ int nd_solve(NdRequest &q) {
   const bool rebuild = !(keep && keep->built);
   if (rebuild) nd_build(M, coeffs, dx, q.bc);          // (of `coeffs` only the layout, the level and the boxes are used)
   NDLev &D0 = M.dlev[0];
+  if (!fixed_cycles || rebuild) {
+    bottom_form_set(1, M.kry_w ? (M.kry_part ? 2 : 1) : 0);
+    if (M.kry_w) { const int budget = bottom_budget_begin(1, M.kry_kind, M.kry_maxit); if (M.kry_part) M.kry_budget = budget; }
+  }
   if (M.kry_w && (!fixed_cycles || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
   M.pro_levels = 0; g_nd_pro_levels = 0;
   if (rebuild) {

@@ -9,6 +9,7 @@
 #include "vdn_dev.h"
 #include <algorithm>
 #include <chrono>
+#include <map>
 #include <tuple>
 
 // ================================================================================================
@@ -367,6 +368,11 @@ void vdn_note_stale_error(hipError_t e) {
 }
 extern "C" int vdn_last_stale_hip_error(int clear) { const int e = g_stale_hip_error; if (clear) g_stale_hip_error = 0; return e; }
 
+// what the last solve of each multigrid ran at its bottom (vdn_last_bottom_form) and the iteration budgets of the grid-wide Krylov form (bottom_budget_begin)
+static int g_bottom_form[2] = { 0, 0 };
+static std::map<unsigned long long, int> g_bb_table;
+static unsigned long long g_bb_last[2] = { 0, 0 };
+static int g_bb_last_budget[2] = { 0, 0 };
 extern "C" int vdn_init(const vdn_params *prm, int rank, int nranks, int device) {
   VDN_TRY
   env_warn_unknown();
@@ -406,8 +412,9 @@ extern "C" int vdn_init(const vdn_params *prm, int rank, int nranks, int device)
   if (c.stream == 0) c.stream = c.own_stream;
   // the counters of the Krylov bottom solvers exist only once one is selected: with the default bottom sweeps vdn_init allocates and launches what it always did
   const bool krylov = (prm->mg_bottom_solver >= 1 && prm->mg_bottom_solver <= 3) || (prm->hg_bottom_solver >= 1 && prm->hg_bottom_solver <= 3);
-  if (krylov && !c.d_bstats) HIPCHK(hipMalloc((void **)&c.d_bstats, 8 * sizeof(double)));
-  if (krylov) HIPCHK(hipMemsetAsync(c.d_bstats, 0, 8 * sizeof(double), c.stream));
+  if (krylov && !c.d_bstats) HIPCHK(hipMalloc((void **)&c.d_bstats, 10 * sizeof(double)));
+  if (krylov) HIPCHK(hipMemsetAsync(c.d_bstats, 0, 10 * sizeof(double), c.stream));
+  g_bb_last[0] = g_bb_last[1] = 0; g_bottom_form[0] = g_bottom_form[1] = 0;
   prof_load();
   c.inited = true;
   VDN_CATCH
@@ -441,7 +448,35 @@ extern "C" int vdn_last_solver_stats(int w, int *cyc, double *r0, double *r) {
   *cyc = g_ctx.solver_cycles[w]; *r0 = g_ctx.solver_res0[w]; *r = g_ctx.solver_res[w]; return 0;
 }
 double *bottom_stats_dev(int which) { return g_ctx.d_bstats + 4 * which; }
-void bottom_stats_reset(int which) { HIPCHK(hipMemsetAsync(g_ctx.d_bstats + 4 * which, 0, 4 * sizeof(double), g_ctx.stream)); }
+double *bottom_exhausted_dev(int which) { return g_ctx.d_bstats + 8 + which; }
+void bottom_stats_reset(int which) {
+  HIPCHK(hipMemsetAsync(g_ctx.d_bstats + 4 * which, 0, 4 * sizeof(double), g_ctx.stream));
+  HIPCHK(hipMemsetAsync(g_ctx.d_bstats + 8 + which, 0, sizeof(double), g_ctx.stream));
+}
+void bottom_form_set(int which, int form) { g_bottom_form[which] = form; }
+extern "C" int vdn_last_bottom_form(int which) { return (which == 0 || which == 1) ? g_bottom_form[which] : -1; }
+// The iterations one visit of a grid-wide Krylov bottom solve launches (krylov_grid.h).  A cycle is captured into a hipGraph and nothing is read back inside
+// it, so the count is fixed before the solve: the cap on the first solve of a kind (`kind`: multigrid, method, bottom extents, alpha term, singular, eps),
+// afterwards 1.5 x the largest count a visit of the previous solve of that kind took, + 8, rounded up to a multiple of 32 (few distinct graphs); twice the
+// budget after a solve in which a visit ran out of it; never more than the cap.  Called where a solve resets its statistics: it first reads those of the previous
+// solve of this multigrid (one read-back, only when that solve was grid-wide).  kind = 0: this solve is not grid-wide.
+int bottom_budget_begin(int which, unsigned long long kind, int cap) {
+  if (g_bb_last[which]) {
+    double v[4], ex;
+    { const double *h = read_scalars(g_ctx.d_bstats + 4 * which, 4); for (int q = 0; q < 4; q++) v[q] = h[q]; }
+    ex = read_scalar1(g_ctx.d_bstats + 8 + which);
+    if (v[0] > 0.0) {
+      const int mx = (int)v[2];
+      g_bb_table[g_bb_last[which]] = ex > 0.0 ? 2 * g_bb_last_budget[which] : 32 * ((mx + mx / 2 + 8 + 31) / 32);
+    }
+    g_bb_last[which] = 0;
+  }
+  if (!kind) return 0;
+  const auto it = g_bb_table.find(kind);
+  const int b = it == g_bb_table.end() ? cap : std::min(cap, it->second);
+  g_bb_last[which] = kind; g_bb_last_budget[which] = b;
+  return b;
+}
 extern "C" int vdn_last_bottom_stats(int which, int *calls, int *iters, int *max_iters, int *breakdowns) {
   VDN_TRY
   REQUIRE(which == 0 || which == 1, "vdn_last_bottom_stats: which must be 0 (cell-centred) or 1 (nodal)");

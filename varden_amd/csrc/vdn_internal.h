@@ -91,7 +91,7 @@ struct VdnCtx {
   // small device scratch for reductions + pinned host mirror
   double *d_scal = nullptr; double *h_scal = nullptr;       // 64 doubles each
   double *h_scal_dev = nullptr;                             // device view of the pinned mirror (k_publish writes it)
-  double *d_bstats = nullptr;                               // statistics of the Krylov bottom solvers, 4 doubles per multigrid (0 cell-centred, 1 nodal): bottom_stats_*
+  double *d_bstats = nullptr;                               // statistics of the Krylov bottom solvers, 4 doubles per multigrid (0 cell-centred, 1 nodal), then one each for the visits out of budget: bottom_stats_*
   double *d_hist = nullptr;                                 // 64 norms of consecutive V-cycles + (slot 64, as an integer) their count: norm_hist_*
   double step_sec[5] = {0, 0, 0, 0, 0};
   int solver_cycles[2] = {0, 0}; double solver_res0[2] = {0, 0}, solver_res[2] = {0, 0};
@@ -152,6 +152,11 @@ extern int g_mg_predict_off;          // > 0: inside the repeat of a solve whose
 // solve in progress, as doubles -- for which = 0 (cell-centred) or 1 (nodal); bottom_stats_reset zeroes it on the launch stream at the start of a solve
 double *bottom_stats_dev(int which);
 void    bottom_stats_reset(int which);
+// ... the grid-wide form (krylov_grid.h): the count of visits that ran out of their iteration budget, the budget of the solve about to start (runtime.hip), and
+// what vdn_last_bottom_form reports: 0 sweeps, 1 one workgroup, 2 grid-wide
+double *bottom_exhausted_dev(int which);
+int     bottom_budget_begin(int which, unsigned long long kind, int cap);
+void    bottom_form_set(int which, int form);
 
 // ---- hipGraph replay of fixed launch sequences (one multigrid cycle = ~100 launches of 3-15 us) ---------------------------------------
 // Usage:  GraphKey k; k.put(...every value the launches depend on...);  if (!graph_replay(k.h)) { graph_begin(); body(); graph_end(k.h); }

@@ -362,6 +362,10 @@ module varden_amd
        integer(c_int), value :: comp
        real(c_double), intent(in) :: dx(*)
      end function
+     integer(c_int) function vdn_last_bottom_form(which) bind(C, name="vdn_last_bottom_form")   ! 0 bottom sweeps, 1 Krylov in one workgroup, 2 Krylov over the whole GPU
+       import :: c_int
+       integer(c_int), value :: which
+     end function
      integer(c_size_t) function c_strlen(s) bind(C, name="strlen")
        import :: c_ptr, c_size_t
        type(c_ptr), value :: s
