@@ -340,7 +340,6 @@ static void gather_level(double *base, long ndoubles) {
 static dim3 g2(int nx, int ny) { return dim3((nx + 63) / 64, (ny + 3) / 4, 1); }
 struct CC2MG { std::vector<C2> lev; int per[2]; double *d_nrm;
   double *kry_w = nullptr; int kry_method = 0, kry_singular = 0, kry_maxit = 0; };      // Krylov bottom solver: its work arrays (nullptr = the bottom sweeps)
-static int krylov_method_of(int b) { return (b == 1 || b == 3) ? VDN_KRYLOV_BICGSTAB : (b == 2 ? VDN_KRYLOV_CG : 0); }
 static void c2_gsrb(const CC2MG &M, const C2 &L, int ns) {
   hipStream_t st = ctx().stream;
   for (int s = 0; s < ns; s++) for (int col = 0; col < 2; col++) {
@@ -399,7 +398,7 @@ int cc2_solve(CcRequest &rq) {
   }
   // Krylov bottom solver: on the last level of a hierarchy of more than one level (a one-level hierarchy -- an odd extent on the finest level -- keeps its sweeps);
   // the statistics are those of this solve
-  const int method = krylov_method_of(ctx().prm.mg_bottom_solver);
+  const int method = mg_krylov_method(ctx().prm.mg_bottom_solver);
   if (method) bottom_stats_reset(0);
   bottom_form_set(0, (method && M.lev.size() > 1) ? 1 : 0);      // dm = 2: always one workgroup (a 75^2 bottom is 5625 cells)
   if (method && M.lev.size() > 1) {
@@ -849,7 +848,7 @@ int nd2_solve(NdRequest &rq) {
     n0 /= 2; n1 /= 2; h0 *= 2.0; h1 *= 2.0;
   }
   // Krylov bottom solver: as in cc2_solve (more than one level; the statistics are those of this solve)
-  const int method = krylov_method_of(ctx().prm.hg_bottom_solver);
+  const int method = mg_krylov_method(ctx().prm.hg_bottom_solver);
   if (method) bottom_stats_reset(1);
   bottom_form_set(1, (method && M.lev.size() > 1) ? 1 : 0);
   if (method && M.lev.size() > 1) {

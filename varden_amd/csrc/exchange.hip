@@ -22,8 +22,6 @@
 #include <tuple>
 #include <array>
 
-void mg_halo_cache_purge(unsigned long uid);   // mg_cc.hip / mg_nd.hip keep key -> plan maps; they drop the keys
-
 // ====================================================================================================
 // RCCL through dlopen
 // ====================================================================================================
@@ -587,17 +585,22 @@ std::vector<XBoxInfo> xboxes_of(const vdn_multifab *mf) {
 struct FbKey { unsigned long uid; const void *base; int lev, nc, ng, nd; bool operator<(const FbKey &o) const {
   return std::tie(uid, base, lev, nc, ng, nd) < std::tie(o.uid, o.base, o.lev, o.nc, o.ng, o.nd); } };
 static std::map<FbKey, XPlan *> g_fb_cache;
-static std::multimap<unsigned long, XPlan *> g_halo_owned;     // multigrid halo plans, by layout uid
-void halo_cache_register(unsigned long uid, XPlan *P) { g_halo_owned.emplace(uid, P); }
+static bool operator<(const MgHaloKey &a, const MgHaloKey &o) { return std::tie(a.uid, a.p0, a.lev, a.l, a.which, a.per, a.sig) < std::tie(o.uid, o.p0, o.lev, o.l, o.which, o.per, o.sig); }
+static std::map<MgHaloKey, XPlan *> g_mg_halo_cache;
+XPlan *mg_halo_plan(const MgHaloKey &key, const std::vector<XBoxInfo> &boxes, const vdn_box &pd, const int pmask[3], bool faces_only) {
+  auto it = g_mg_halo_cache.find(key);
+  if (it == g_mg_halo_cache.end()) it = g_mg_halo_cache.emplace(key, xplan_build(boxes, pd, pmask, 1, 1, faces_only)).first;
+  return it->second;
+}
+static void mg_halo_cache_purge(unsigned long uid) {
+  for (auto it = g_mg_halo_cache.begin(); it != g_mg_halo_cache.end();) { if (it->first.uid == uid) { xplan_free(it->second); it = g_mg_halo_cache.erase(it); } else ++it; }
+}
 void xplan_cache_purge(unsigned long uid) {
   kept_purge(uid);                              // descriptor sets hold pointers into the views' windows
   view_cache_purge(uid);
   for (auto it = g_fb_cache.begin(); it != g_fb_cache.end();) {
     if (it->first.uid == uid) { xplan_free(it->second); it = g_fb_cache.erase(it); } else ++it;
   }
-  auto rng = g_halo_owned.equal_range(uid);
-  for (auto it = rng.first; it != rng.second; ++it) xplan_free(it->second);
-  g_halo_owned.erase(rng.first, rng.second);
   mg_halo_cache_purge(uid);
 }
 

@@ -57,6 +57,23 @@ struct KrylovGridArgs {
   DEVI double *st(int b) const { return part + KG_NPART * KG_MAXWG + b * KG_NST; }
 };
 
+// What a 3-D hierarchy (CCMG, NDMG) keeps of its Krylov bottom solver.  w: the work arrays, of the bottom level's padded size (nullptr = the bottom sweeps);
+// part: the grid-wide form's partial sums and state blocks, on a bottom level of VDN_KRYLOV_GRID_MIN_POINTS points (cells, or nodes) or more; budget: the
+// iterations a visit of that form launches; kind: its key in bottom_budget_begin.
+struct MgKrylov { double *w = nullptr; int method = 0, maxit = 0; double *part = nullptr; int budget = 0; unsigned long long kind = 0; };
+// The set-up both builds share.  The arrays come from the arena here, so their addresses repeat with the hierarchy's.  sz: the bottom level's padded size;
+// N: its largest extent in points; np: its points; kind: what tells one solver's bottom systems apart (solver, method, extents, boundary, tolerance)
+inline void mg_krylov_setup(MgKrylov &K, int method, long sz, int N, long np, const GraphKey &kind) {
+  K.method = method;
+  K.w = (double *)arena_alloc(sizeof(double) * sz * (method == VDN_KRYLOV_CG ? 4 : 7));
+  K.maxit = 12 * N;
+  if (np >= VDN_KRYLOV_GRID_MIN_POINTS) {
+    K.part = (double *)arena_alloc(sizeof(double) * KG_DOUBLES);
+    K.kind = kind.h | 1ull;
+    K.budget = K.maxit;
+  }
+}
+
 DEVI double kg_sum(const double *p, int n) { double a = p[0]; for (int g = 1; g < n; g++) a = a + p[g]; return a; }
 DEVI double kg_max(const double *p, int n) { double a = p[0]; for (int g = 1; g < n; g++) a = nmax(a, p[g]); return a; }
 DEVI bool kg_first() { return blockIdx.x == 0 && threadIdx.x == 0; }

@@ -25,10 +25,8 @@
 // Work arrays, each of the level's padded size: CG 4 (r, p, q, 1/diag), BiCGStab 7 (r -- which also holds s --, r0, p, v, t, the preconditioned
 // vector, 1/diag).  The workgroup zeroes them on entry (ghost entries outside a physical face must read as zero).
 #pragma once
-#include "vdn_dev.h"
+#include "vdn_dev.h"      // (METHOD: VDN_KRYLOV_BICGSTAB, VDN_KRYLOV_CG of mg_plan.h)
 
-#define VDN_KRYLOV_BICGSTAB 1
-#define VDN_KRYLOV_CG 2
 struct KrylovArgs {
   double *w;          // 4 (CG) or 7 (BiCGStab) arrays of the bottom level's padded size, from the arena
   double *stats;      // 4 counters kept as doubles: bottom calls, total iterations, maximum iterations, breakdowns

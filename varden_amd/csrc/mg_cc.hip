@@ -1097,7 +1097,7 @@ __global__ void kk_cc_store(CLev L, FV phi, int lo0, int lo1, int lo2, int ebc00
 // distributing over xGMI.  Each rank restricts its boxes' residuals into a packed buffer, one all-gather makes
 // every rank's buffer visible everywhere, and an unpack kernel assembles the global coarse right-hand side.
 // The face coefficients of the tail's first level travel the same way once per solve.
-struct GBox { int c0[3]; int n[3]; long off; };     // where a box's coarse cells sit in the tail level / in the buffer
+// (GBox, mg_plan.h: where a box's coarse cells sit in the tail level / in the buffer)
 
 __global__ void kk_cc_restrict_pack(CLev F, const double *r, double *buf, long off, int nx, int ny, int nz) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1193,13 +1193,9 @@ struct CCMG {
   int per[3];
   double *d_nrm;
   // gather machinery
-  std::vector<GBox> gb_rh, gb_b; GBox *d_gb_rh = nullptr, *d_gb_b = nullptr;
-  double *sendbuf = nullptr, *recvbuf = nullptr; size_t cnt_rh = 0, cnt_b = 0;   // per-rank counts (doubles)
-  std::vector<long> loc_off_rh, loc_off_b;                                       // offsets of my boxes inside my send buffer
-  // Krylov bottom solver (mg_bottom_solver = 1, 2, 3): its work arrays, of the bottom level's padded size; nullptr = the bottom sweeps
-  double *kry_w = nullptr; int kry_method = 0, kry_singular = 0, kry_maxit = 0;
-  // ... its grid-wide form (krylov_grid.h) on a bottom level of VDN_KRYLOV_GRID_MIN_POINTS cells or more: partial sums and state blocks; the iterations a visit launches
-  double *kry_part = nullptr; int kry_budget = 0; unsigned long long kry_kind = 0;
+  MgGather g_rh, g_b; GBox *d_gb_rh = nullptr, *d_gb_b = nullptr;                // cells (rhs, alpha) and face coefficients (mg_plan.h)
+  double *sendbuf = nullptr, *recvbuf = nullptr;
+  MgKrylov kry; int kry_singular = 0;      // Krylov bottom solver (mg_bottom_solver = 1, 2, 3; krylov_grid.h)
 };
 
 static dim3 g3(int nx, int ny, int nz, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, nz); }
@@ -1304,14 +1300,10 @@ static FV cc_phi_view(const CLev &L, const int lo[3]) {
   return f;
 }
 
-// plans for the per-level phi halos are cached across solves: arena addresses repeat from step to step
+// plans for the per-level phi halos are cached across solves (mg_halo_plan, exchange.hip): arena addresses repeat from step to step
 // sig: a hash of EVERY local box's phi address -- the plan bakes those addresses in, and two solves on one level that start at the same
 // arena offset but differ in layout (6 arrays per box without alpha, 7 with) agree on the first box only
-struct HaloKey { unsigned long uid; const void *p0; int lev, l, per; unsigned long long sig; bool operator<(const HaloKey &o) const { return std::tie(uid, p0, lev, l, per, sig) < std::tie(o.uid, o.p0, o.lev, o.l, o.per, o.sig); } };
-static std::map<HaloKey, XPlan *> g_halo_cache;
-void cc_halo_cache_purge(unsigned long uid) {        // the plans themselves are freed by exchange.hip (halo_cache_register)
-  for (auto it = g_halo_cache.begin(); it != g_halo_cache.end();) { if (it->first.uid == uid) it = g_halo_cache.erase(it); else ++it; }
-}
+static const int CC_HALO = 4;      // MgHaloKey::which of this file's plans (0..3: the nodal arrays)
 
 // the exchange of phi[colour] in the index space (ih, j, k) of the split arrays: boxes and domain halved along x.  Extents and corner indices are even (cc_split_ok), so a
 // row has the same parity on both sides of a box face or a periodic image: entry ih of a ghost row / plane is entry ih of the neighbour's row / plane, the ghost entry -1 (nh)
@@ -1332,18 +1324,15 @@ static XPlan *cc_split_plan(const CDLev &D0, int colour, const int per[3]) {
     }
   }
   vdn_box lpd = D0.lpd; lpd.hi[0] = (lpd.hi[0] + 1) / 2 - 1;
-  HaloKey key{ D0.la_uid, (const void *)D0.boxes[0].sp.phi[colour], D0.la_lev, 1000 + colour, per[0] | (per[1] << 1) | (per[2] << 2), hk.h };
-  auto it = g_halo_cache.find(key);
-  if (it == g_halo_cache.end()) { XPlan *P = xplan_build(xb, lpd, per, 1, 1, sw().cc_halo_faces); halo_cache_register(D0.la_uid, P); it = g_halo_cache.emplace(key, P).first; }
-  return it->second;
+  const MgHaloKey key{ D0.la_uid, (const void *)D0.boxes[0].sp.phi[colour], D0.la_lev, 1000 + colour, CC_HALO, per[0] | (per[1] << 1) | (per[2] << 2), hk.h };
+  return mg_halo_plan(key, xb, lpd, per, sw().cc_halo_faces);
 }
 
-// Several boxes: a level stays distributed box by box while its boxes, halved, are at least this wide; below that the level of the WHOLE domain is gathered and every rank
-// runs the rest of the hierarchy on one box.  64 where the boxes live on several ranks: every level that stays distributed costs ~10 latency-bound halo exchanges per V-cycle,
-// the replicated levels below 64^3 per box cost microseconds per pass.  Round 6: 128 where every box of the level is this rank's and no transport is up (configs[2] on one GPU):
-// eight 64^3 boxes are eight 5-us launches and a ghost-copy kernel per pass -- three times the ONE pass over the gathered 128^3 level -- and the gather is a device copy.
-// The arithmetic is that of the single-box hierarchy wherever the cut is made (global colours, global bottom-sweep counts): tests/test_multirank_gpu.py compares ranks that
-// cut at 64 with one rank that cuts at 128, bit for bit.  VDN_MG_AGGLOM (testing build): a fixed value.
+// The box width the hierarchy rule (mg_plan.h) cuts a level of several boxes at.  64 where the boxes live on several ranks: every level that stays distributed costs ~10
+// latency-bound halo exchanges per V-cycle, the replicated levels below 64^3 per box cost microseconds per pass.  128 where every box of the level is this rank's and no
+// transport is up (configs[2] on one GPU): eight 64^3 boxes are eight 5-us launches and a ghost-copy kernel per pass -- three times the ONE pass over the gathered 128^3
+// level -- and the gather is a device copy.  The result does not depend on the cut (global colours, global bottom-sweep counts): tests/test_multirank_gpu.py compares
+// ranks that cut at 64 with one rank that cuts at 128, bit for bit.  VDN_MG_AGGLOM (testing build): a fixed value.
 int mg_agglom(const vdn_layout *la, int lev) {
   if (sw().mg_agglom > 0) return sw().mg_agglom;
   bool all_local = true;
@@ -1351,33 +1340,27 @@ int mg_agglom(const vdn_layout *la, int lev) {
   return (all_local && !comm_active()) ? 128 : 64;
 }
 
-static int cc_krylov_method() { const int b = ctx().prm.mg_bottom_solver; return (b == 1 || b == 3) ? VDN_KRYLOV_BICGSTAB : (b == 2 ? VDN_KRYLOV_CG : 0); }
+// the hierarchy (mg_plan.h) both single-level multigrids build on one level of a layout
+MgPlan mg_plan_of(const vdn_layout *la, int lev) {
+  return mg_plan(la->boxes[lev].data(), la->owner[lev].data(), (int)la->boxes[lev].size(), la->pd[lev], ctx().nranks, ctx().rank, mg_agglom(la, lev));
+}
 static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const int bc[3][2], bool has_alpha) {
   Prof prof_("cc_build");
   const vdn_layout *la = rh->la; const int lev = rh->lev;
-  const auto &gboxes = la->boxes[lev];
-  const int nb = (int)gboxes.size();
+  const int nb = (int)la->boxes[lev].size();
   for (int d = 0; d < 3; d++) M.per[d] = (bc[d][0] == VDN_BC_PER);
-  // all boxes must share one size and be aligned to it (2x2x2-style decompositions); the general case needs
-  // per-box gather sizes and is left for the AMR round
-  int bn[3]; for (int d = 0; d < 3; d++) bn[d] = gboxes[0].hi[d] - gboxes[0].lo[d] + 1;
-  for (const auto &b : gboxes) for (int d = 0; d < 3; d++) {
-    REQUIRE(b.hi[d] - b.lo[d] + 1 == bn[d], "cc multigrid: all boxes of a level must have the same size");
-    REQUIRE((b.lo[d] - la->pd[lev].lo[d]) % bn[d] == 0, "cc multigrid: boxes must be aligned to their size");
-  }
-  std::vector<int> nloc_of(ctx().nranks, 0);
-  for (int g = 0; g < nb; g++) nloc_of[la->owner[lev][g]]++;
-  int maxloc = 0; for (int r = 0; r < ctx().nranks; r++) maxloc = std::max(maxloc, nloc_of[r]);
-  // ---- distributed levels: while every extent of the boxes is even and >= 4 --------------------------------
-  int n[3] = { bn[0], bn[1], bn[2] }; double h[3] = { dx[0], dx[1], dx[2] };
-  int scale = 1;
-  for (;;) {
+  const MgPlan P = mg_plan_of(la, lev);
+  REQUIRE(P.err.empty(), "cc multigrid: %s", P.err.c_str());
+  // ---- distributed levels ---------------------------------------------------------------------------------
+  double h[3] = { dx[0], dx[1], dx[2] };
+  for (const MgDistLevel &PL : P.dist) {
+    const int *n = PL.n;
     CDLev DL;
     std::vector<XBoxInfo> xb;
     for (int g = 0; g < nb; g++) {
       XBoxInfo x; memset(&x, 0, sizeof x);
-      int lo[3];
-      for (int d = 0; d < 3; d++) { lo[d] = (gboxes[g].lo[d] - la->pd[lev].lo[d]) / scale; x.vlo[d] = lo[d]; x.vhi[d] = lo[d] + n[d] - 1; }
+      const int *lo = PL.lo[g].data();
+      for (int d = 0; d < 3; d++) { x.vlo[d] = lo[d]; x.vhi[d] = lo[d] + n[d] - 1; }
       x.owner = la->owner[lev][g];
       if (x.owner == ctx().rank) {
         CBox B; B.L = cc_alloc_lev(n, h, has_alpha); B.gidx = g;
@@ -1387,7 +1370,7 @@ static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const in
       }
       xb.push_back(x);
     }
-    vdn_box lpd; for (int d = 0; d < 3; d++) { lpd.lo[d] = 0; lpd.hi[d] = (la->pd[lev].hi[d] - la->pd[lev].lo[d] + 1) / scale - 1; DL.ng[d] = lpd.hi[d] + 1; }
+    vdn_box lpd; for (int d = 0; d < 3; d++) { lpd.lo[d] = 0; lpd.hi[d] = PL.ng[d] - 1; DL.ng[d] = PL.ng[d]; }
     for (CBox &B : DL.boxes) {
       B.hmask = 0;
       for (int d = 0; d < 3; d++) {
@@ -1397,95 +1380,53 @@ static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const in
     }
     if (nb > 1 || M.per[0] || M.per[1] || M.per[2]) {
       GraphKey hk; for (const CBox &B : DL.boxes) { hk.put(B.L.phi); hk.put(B.L.sz); }
-      HaloKey key{ la->uid, DL.boxes.empty() ? nullptr : (const void *)DL.boxes[0].L.phi, lev, (int)M.dlev.size(), M.per[0] | (M.per[1] << 1) | (M.per[2] << 2), hk.h };
-      auto it = g_halo_cache.find(key);
-      if (it == g_halo_cache.end()) { XPlan *P = xplan_build(xb, lpd, M.per, 1, 1, sw().cc_halo_faces); halo_cache_register(la->uid, P); it = g_halo_cache.emplace(key, P).first; }
-      DL.halo = it->second;
+      const MgHaloKey key{ la->uid, DL.boxes.empty() ? nullptr : (const void *)DL.boxes[0].L.phi, lev, (int)M.dlev.size(), CC_HALO, M.per[0] | (M.per[1] << 1) | (M.per[2] << 2), hk.h };
+      DL.halo = mg_halo_plan(key, xb, lpd, M.per, sw().cc_halo_faces);
     }
     DL.single_box = (nb == 1);
     DL.xb = xb; DL.lpd = lpd; DL.la_uid = la->uid; DL.la_lev = lev;
     M.dlev.push_back(DL);
-    // the hierarchy of GLOBAL levels is the single-box one (oracle rule: coarsen while every global extent is
-    // even and > 2); a level stays distributed while the boxes halve cleanly to extents >= 4
-    bool can = true, next_dist = true;
-    for (int d = 0; d < 3; d++) {
-      const int N = lpd.hi[d] + 1;
-      if ((N & 1) || N <= 2) can = false;
+    for (int d = 0; d < 3; d++) h[d] *= 2.0;
+  }
+  if (!P.tail.empty()) {
+    // ---- agglomerated tail starting at the half of the last distributed level ------------------------------------
+    for (const auto &tn : P.tail) {
+      M.tail.push_back(cc_alloc_lev(tn.data(), h, has_alpha));
+      for (int d = 0; d < 3; d++) h[d] *= 2.0;
     }
-    if (can) for (int d = 0; d < 3; d++) REQUIRE(!(n[d] & 1), "cc multigrid: box extent %d is odd while the domain can still be coarsened", n[d]);
-    // several boxes: stop exchanging halos once the boxes get small (below 64 cells) -- every level that stays distributed costs
-    // ~10 latency-bound halo exchanges per V-cycle, the replicated tail below a 64^3-per-box level costs microseconds per pass
-    const int agglom = mg_agglom(la, lev);
-    const int min_dist = nb > 1 ? agglom : 4;
-    for (int d = 0; d < 3; d++) if (n[d] / 2 < min_dist || ((n[d] / 2) & 1)) next_dist = false;
-    if (!can) break;                                   // the domain cannot be coarsened: this level is the bottom
-    if (!next_dist) {
-      // ---- agglomerated tail starting at the half of this level ---------------------------------------------
-      int tn[3]; double th[3]; int cn[3];
-      for (int d = 0; d < 3; d++) { cn[d] = n[d] / 2; tn[d] = (lpd.hi[d] + 1) / 2; th[d] = h[d] * 2.0; }
-      for (;;) {
-        M.tail.push_back(cc_alloc_lev(tn, th, has_alpha));
-        bool c2 = true;
-        for (int d = 0; d < 3; d++) if ((tn[d] & 1) || tn[d] <= 2) c2 = false;
-        if (!c2 || M.tail.size() >= 31) break;
-        for (int d = 0; d < 3; d++) { tn[d] /= 2; th[d] *= 2.0; }
-      }
-      // gather descriptors: rank r's buffer holds its boxes in local order, padded to maxloc boxes
-      const long per_rh = (long)cn[0] * cn[1] * cn[2];
-      const long per_b = (long)(cn[0] + 1) * cn[1] * cn[2] + (long)cn[0] * (cn[1] + 1) * cn[2] + (long)cn[0] * cn[1] * (cn[2] + 1);
-      M.cnt_rh = (size_t)per_rh * maxloc; M.cnt_b = (size_t)per_b * maxloc;
-      std::vector<int> seen(ctx().nranks, 0);
-      for (int g = 0; g < nb; g++) {
-        const int r = la->owner[lev][g], l = seen[r]++;
-        GBox a, b2;
-        for (int d = 0; d < 3; d++) { a.c0[d] = b2.c0[d] = (gboxes[g].lo[d] - la->pd[lev].lo[d]) / scale / 2; a.n[d] = b2.n[d] = cn[d]; }
-        a.off = (long)r * M.cnt_rh + (long)l * per_rh; b2.off = (long)r * M.cnt_b + (long)l * per_b;
-        M.gb_rh.push_back(a); M.gb_b.push_back(b2);
-        if (r == ctx().rank) { M.loc_off_rh.push_back((long)l * per_rh); M.loc_off_b.push_back((long)l * per_b); }
-      }
-      M.d_gb_rh = (GBox *)arena_alloc(nb * sizeof(GBox)); M.d_gb_b = (GBox *)arena_alloc(nb * sizeof(GBox));
-      HIPCHK(hipMemcpyAsync(M.d_gb_rh, M.gb_rh.data(), nb * sizeof(GBox), hipMemcpyHostToDevice, ctx().stream));
-      HIPCHK(hipMemcpyAsync(M.d_gb_b, M.gb_b.data(), nb * sizeof(GBox), hipMemcpyHostToDevice, ctx().stream));
-      HIPCHK(hipStreamSynchronize(ctx().stream));     // the host vectors above are read by the copies
-      M.sendbuf = (double *)arena_alloc(sizeof(double) * M.cnt_b);
-      M.recvbuf = (double *)arena_alloc(sizeof(double) * M.cnt_b * ctx().nranks);
-      break;
-    }
-    for (int d = 0; d < 3; d++) { n[d] /= 2; h[d] *= 2.0; }
-    scale *= 2;
-    if (M.dlev.size() >= 31) break;
+    const int *cn = P.cn;
+    M.g_rh = P.gather((long)cn[0] * cn[1] * cn[2]);
+    M.g_b = P.gather((long)(cn[0] + 1) * cn[1] * cn[2] + (long)cn[0] * (cn[1] + 1) * cn[2] + (long)cn[0] * cn[1] * (cn[2] + 1));
+    M.d_gb_rh = (GBox *)arena_alloc(nb * sizeof(GBox)); M.d_gb_b = (GBox *)arena_alloc(nb * sizeof(GBox));
+    HIPCHK(hipMemcpyAsync(M.d_gb_rh, M.g_rh.gb.data(), nb * sizeof(GBox), hipMemcpyHostToDevice, ctx().stream));
+    HIPCHK(hipMemcpyAsync(M.d_gb_b, M.g_b.gb.data(), nb * sizeof(GBox), hipMemcpyHostToDevice, ctx().stream));
+    HIPCHK(hipStreamSynchronize(ctx().stream));     // the host vectors above are read by the copies
+    M.sendbuf = (double *)arena_alloc(sizeof(double) * M.g_b.cnt);
+    M.recvbuf = (double *)arena_alloc(sizeof(double) * M.g_b.cnt * ctx().nranks);
   }
   M.d_nrm = (double *)arena_alloc(256);
-  // Krylov bottom solver: where the coarsest level is held whole by this rank -- the last level of the replicated tail, or of a one-box hierarchy (a bottom level
-  // that is still distributed over boxes keeps its sweeps, cc_vcycle_d).  The work arrays come from the arena here, so their addresses repeat with the hierarchy's.
-  const int method = cc_krylov_method();
-  const CLev *bottom = !M.tail.empty() ? &M.tail.back() : ((M.dlev.size() > 1 && M.dlev.back().single_box && M.dlev.back().boxes.size() == 1) ? &M.dlev.back().boxes[0].L : nullptr);
-  if (method && bottom) {
-    M.kry_method = method;
-    M.kry_w = (double *)arena_alloc(sizeof(double) * bottom->sz * (method == VDN_KRYLOV_CG ? 4 : 7));
+  // Krylov bottom solver: where this rank holds the coarsest level whole (a bottom level that is still distributed over boxes keeps its sweeps, cc_vcycle_d)
+  const int method = mg_krylov_method(ctx().prm.mg_bottom_solver);
+  if (method && P.whole_bottom) {
+    const CLev &B = !M.tail.empty() ? M.tail.back() : M.dlev.back().boxes[0].L;
     bool dir = false;
     for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) if (bc[d][sd] == VDN_BC_DIR) dir = true;
     M.kry_singular = (!has_alpha && !dir) ? 1 : 0;
-    M.kry_maxit = 12 * std::max(bottom->n[0], std::max(bottom->n[1], bottom->n[2]));
-    if ((long)bottom->n[0] * bottom->n[1] * bottom->n[2] >= VDN_KRYLOV_GRID_MIN_POINTS) {
-      M.kry_part = (double *)arena_alloc(sizeof(double) * KG_DOUBLES);
-      GraphKey k; k.put(0); k.put(method); k.put(bottom->n); k.put(has_alpha); k.put(M.kry_singular); k.put(ctx().prm.mg_bottom_solver_eps);
-      M.kry_kind = k.h | 1ull;
-      M.kry_budget = M.kry_maxit;
-    }
+    GraphKey k; k.put(0); k.put(method); k.put(B.n); k.put(has_alpha); k.put(M.kry_singular); k.put(ctx().prm.mg_bottom_solver_eps);
+    mg_krylov_setup(M.kry, method, B.sz, std::max(B.n[0], std::max(B.n[1], B.n[2])), (long)B.n[0] * B.n[1] * B.n[2], k);
   }
 }
-static KrylovArgs cc_krylov_args(const CCMG &M) { return KrylovArgs{ M.kry_w, bottom_stats_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry_maxit }; }
+static KrylovArgs cc_krylov_args(const CCMG &M) { return KrylovArgs{ M.kry.w, bottom_stats_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry.maxit }; }
 // one visit of the bottom level L by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU
 static void cc_krylov_visit(const CCMG &M, const CLev &L) {
-  if (!M.kry_part) { hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, cc_krylov_args(M), M.kry_method, M.kry_singular, M.per[0], M.per[1], M.per[2]); return; }
+  if (!M.kry.part) { hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, cc_krylov_args(M), M.kry.method, M.kry_singular, M.per[0], M.per[1], M.per[2]); return; }
   const CcKrylovLevel lv{ L, { M.per[0], M.per[1], M.per[2] }, M.kry_singular };
-  const KrylovGridArgs K{ M.kry_w, M.kry_part, bottom_stats_dev(0), bottom_exhausted_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry_maxit };
+  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(0), bottom_exhausted_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry.maxit };
   const long np = (long)L.n[0] * L.n[1] * L.n[2];
   const long m = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const long nfill = (M.per[0] || M.per[1] || M.per[2]) ? 6 * m * m : 0;
-  if (M.kry_method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry_budget, ctx().stream);
-  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry_budget, ctx().stream);
+  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
+  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
 }
 
 static void cc_halo(CCMG &M, CDLev &DL) { if (DL.halo) xplan_run(DL.halo); }
@@ -1597,7 +1538,7 @@ static void cc_gsrb_t(const CCMG &M, const CLev &L, int nsweeps) {
   }
 }
 static void cc_bottom_t(const CCMG &M, const CLev &L) {      // max(nub, N^2) sweeps, N = largest extent (same rule as the oracle)
-  if (M.kry_w) { cc_krylov_visit(M, L); return; }
+  if (M.kry.w) { cc_krylov_visit(M, L); return; }
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.mg_nub, N * N);
   hipLaunchKernelGGL(kk_cc_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, ns, M.per[0], M.per[1], M.per[2]);
@@ -1628,7 +1569,7 @@ static bool cc_small_end(const CCMG &M, int dl, int tl) {
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.mg_nu1; T.nu2 = P.mg_nu2; T.nbot = std::max(P.mg_nub, N * N);      // cc_bottom_t / cc_vcycle_d
   for (int d = 0; d < 3; d++) T.per[d] = M.per[d];
-  if (M.kry_w) { hipLaunchKernelGGL(kk_cc_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, cc_krylov_args(M), M.kry_method, M.kry_singular); return true; }
+  if (M.kry.w) { hipLaunchKernelGGL(kk_cc_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, cc_krylov_args(M), M.kry.method, M.kry_singular); return true; }
   hipLaunchKernelGGL(kk_cc_tailcycle, dim3(1), dim3(1024), 0, ctx().stream, T);
   return true;
 }
@@ -1681,10 +1622,10 @@ static void cc_restrict_down(CCMG &M, int l) {
     for (size_t b = 0; b < DL.boxes.size(); b++) {
       const CLev &F = DL.boxes[b].L;
       const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
-      hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, ctx().stream, F, (const double *)F.res, M.sendbuf, M.loc_off_rh[b], nx, ny, nz);
+      hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, ctx().stream, F, (const double *)F.res, M.sendbuf, M.g_rh.loc_off[b], nx, ny, nz);
     }
-    comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_rh);
-    hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.gb_rh.size()), dim3(256), 0, ctx().stream, T, T.rh, M.recvbuf, M.d_gb_rh);
+    comm_allgather_dev(M.sendbuf, M.recvbuf, M.g_rh.cnt);
+    hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.g_rh.gb.size()), dim3(256), 0, ctx().stream, T, T.rh, M.recvbuf, M.d_gb_rh);
   }
 }
 static void cc_prolong_up(CCMG &M, int l) {
@@ -1795,7 +1736,7 @@ static void cc_vcycle_d(CCMG &M, int l) {
   const bool last = (l == (int)M.dlev.size() - 1);      // phi = 0 on entry: written by the restriction that feeds this level
   if (cc_small_end(M, l, 0)) return;
   if (last && M.tail.empty()) {         // nothing below: bottom sweeps on the distributed level itself
-    if (M.kry_w && DL.single_box && DL.boxes.size() == 1) {      // (one box: the Krylov bottom solver, when one is selected; several boxes keep the sweeps)
+    if (M.kry.w && DL.single_box && DL.boxes.size() == 1) {      // (one box: the Krylov bottom solver, when one is selected; several boxes keep the sweeps)
       cc_krylov_visit(M, DL.boxes[0].L);
       return;
     }
@@ -1868,10 +1809,10 @@ static void cc_fmg(CCMG &M, const int bc[3][2]) {
       for (size_t b = 0; b < DL.boxes.size(); b++) {
         const CLev &F = DL.boxes[b].L;
         const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
-        hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, st, F, (const double *)F.rh, M.sendbuf, M.loc_off_rh[b], nx, ny, nz);
+        hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, st, F, (const double *)F.rh, M.sendbuf, M.g_rh.loc_off[b], nx, ny, nz);
       }
-      comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_rh);
-      hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.gb_rh.size()), dim3(256), 0, st, T, T.rh, M.recvbuf, M.d_gb_rh);
+      comm_allgather_dev(M.sendbuf, M.recvbuf, M.g_rh.cnt);
+      hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.g_rh.gb.size()), dim3(256), 0, st, T, T.rh, M.recvbuf, M.d_gb_rh);
     } else {
       CLev F = M.tail[g - nd]; F.res = F.rh;
       const CLev &C = M.tail[g - nd + 1];
@@ -1921,16 +1862,16 @@ static void cc_key_lev(GraphKey &k, const CLev &L) {
 static unsigned long long cc_graph_key(const CCMG &M, int what) {
   const vdn_params &P = ctx().prm;
   GraphKey k; k.put(what); k.put(P.mg_nu1); k.put(P.mg_nu2); k.put(P.mg_nub); k.put(M.per); k.put(M.d_nrm);
-  k.put(M.sendbuf); k.put(M.recvbuf); k.put(M.d_gb_rh); k.put(M.d_gb_b); k.put(M.cnt_rh); k.put(M.cnt_b);
+  k.put(M.sendbuf); k.put(M.recvbuf); k.put(M.d_gb_rh); k.put(M.d_gb_b); k.put(M.g_rh.cnt); k.put(M.g_b.cnt);
   for (const CDLev &DL : M.dlev) {
     k.put(xplan_serial(DL.halo)); k.put(DL.ng); k.put(DL.single_box); k.put(DL.res_restricted);
     k.put(DL.split); k.put(xplan_serial(DL.shalo[0])); k.put(xplan_serial(DL.shalo[1]));
     for (const CBox &B : DL.boxes) { cc_key_lev(k, B.L); k.put(B.lo); if (DL.split) { k.put(B.sp.PXH); k.put(B.sp.off); k.put(B.sp.phi); k.put(B.sp.rh); k.put(B.sp.rho); } }
   }
   for (const CLev &L : M.tail) cc_key_lev(k, L);
-  for (long o : M.loc_off_rh) k.put(o);
-  if (M.kry_w) { k.put(M.kry_w); k.put(M.kry_method); k.put(M.kry_singular); k.put(M.kry_maxit); k.put(P.mg_bottom_solver_eps); }
-  if (M.kry_part) { k.put(M.kry_part); k.put(M.kry_budget); }
+  for (long o : M.g_rh.loc_off) k.put(o);
+  if (M.kry.w) { k.put(M.kry.w); k.put(M.kry.method); k.put(M.kry_singular); k.put(M.kry.maxit); k.put(P.mg_bottom_solver_eps); }
+  if (M.kry.part) { k.put(M.kry.part); k.put(M.kry.budget); }
   return k.h;
 }
 template <class Body> static void cc_run_cycle(CCMG &M, int what, Body body) {
@@ -1974,18 +1915,18 @@ static void cc_coarsen_coeffs(CCMG &M, bool has_alpha, bool from_rho) {
   for (size_t b = 0; b < DL.boxes.size(); b++) {
     const CLev &F = DL.boxes[b].L;
     const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
-    hipLaunchKernelGGL(kk_cc_coarsen_b_pack, g3(nx + 1, ny + 1, nz + 1, BLK), BLK, 0, ctx().stream, F, M.sendbuf, M.loc_off_b[b], nx, ny, nz);
+    hipLaunchKernelGGL(kk_cc_coarsen_b_pack, g3(nx + 1, ny + 1, nz + 1, BLK), BLK, 0, ctx().stream, F, M.sendbuf, M.g_b.loc_off[b], nx, ny, nz);
   }
-  comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_b);
-  hipLaunchKernelGGL(kk_cc_unpack_b, dim3(4, 1, (unsigned)M.gb_b.size()), dim3(256), 0, ctx().stream, M.tail[0], M.recvbuf, M.d_gb_b);
+  comm_allgather_dev(M.sendbuf, M.recvbuf, M.g_b.cnt);
+  hipLaunchKernelGGL(kk_cc_unpack_b, dim3(4, 1, (unsigned)M.g_b.gb.size()), dim3(256), 0, ctx().stream, M.tail[0], M.recvbuf, M.d_gb_b);
   if (has_alpha) {                   // alpha of the first tail level: per-box 8-cell means, gathered like the residual
     for (size_t b = 0; b < DL.boxes.size(); b++) {
       const CLev &F = DL.boxes[b].L;
       const int nx = F.n[0] / 2, ny = F.n[1] / 2, nz = F.n[2] / 2;
-      hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, ctx().stream, F, (const double *)F.alpha, M.sendbuf, M.loc_off_rh[b], nx, ny, nz);
+      hipLaunchKernelGGL(kk_cc_restrict_pack, g3(nx, ny, nz, BLK), BLK, 0, ctx().stream, F, (const double *)F.alpha, M.sendbuf, M.g_rh.loc_off[b], nx, ny, nz);
     }
-    comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_rh);
-    hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.gb_rh.size()), dim3(256), 0, ctx().stream, M.tail[0], M.tail[0].alpha, M.recvbuf, M.d_gb_rh);
+    comm_allgather_dev(M.sendbuf, M.recvbuf, M.g_rh.cnt);
+    hipLaunchKernelGGL(kk_cc_unpack_rh, dim3(4, 1, (unsigned)M.g_rh.gb.size()), dim3(256), 0, ctx().stream, M.tail[0], M.tail[0].alpha, M.recvbuf, M.d_gb_rh);
   }
   for (size_t l = 1; l < M.tail.size(); l++) {
     const CLev &C = M.tail[l];
@@ -2120,8 +2061,8 @@ int cc_solve(CcRequest &q) {
   }
   // the bottom statistics are those of one solve (a composite solve: of all the cycles it runs on its kept hierarchy)
   if (!fixed || !(keep && keep->built)) {
-    bottom_form_set(0, M.kry_w ? (M.kry_part ? 2 : 1) : 0);
-    if (M.kry_w) { const int budget = bottom_budget_begin(0, M.kry_kind, M.kry_maxit); if (M.kry_part) M.kry_budget = budget; bottom_stats_reset(0); }
+    bottom_form_set(0, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
+    if (M.kry.w) { const int budget = bottom_budget_begin(0, M.kry.kind, M.kry.maxit); if (M.kry.part) M.kry.budget = budget; bottom_stats_reset(0); }
   }
   if (keep) keep->built = true;
   CDLev &D0 = M.dlev[0];
@@ -2382,14 +2323,8 @@ void do_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab **rho, vdn
   const int n = 0;
   size_t mark = arena_mark();
   {
-    // the second level must exist (its coefficients come from the first level's rho): boxes that halve cleanly to >= 4 cells, as cc_build asks
-    bool ok = sw().mac_fast && !sw().mac_stored_beta && rho[n]->ng >= 1;
-    {   // cc_build's rule for a second DISTRIBUTED level: the domain coarsens, the boxes halve cleanly and stay at least min_dist wide
-      const int agglom = mg_agglom(mla, n);
-      const int min_dist = mla->boxes[n].size() > 1 ? agglom : 4;
-      for (const vdn_box &b : mla->boxes[n]) for (int d = 0; d < 3; d++) { const int w = b.hi[d] - b.lo[d] + 1; if ((w & 1) || w / 2 < min_dist || ((w / 2) & 1)) ok = false; }
-      for (int d = 0; d < 3; d++) { const int N = mla->pd[n].hi[d] - mla->pd[n].lo[d] + 1; if ((N & 1) || N <= 2) ok = false; }
-    }
+    // a second DISTRIBUTED level must exist: its coefficients come from the first level's rho
+    const bool ok = sw().mac_fast && !sw().mac_stored_beta && rho[n]->ng >= 1 && mg_plan_of(mla, n).second_dist_level();
     if (ok) {
       vdn_multifab *um[3] = { umac[0], umac[1], umac[2] };
       int ebc[3][2];

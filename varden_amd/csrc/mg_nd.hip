@@ -18,10 +18,6 @@
 #include <tuple>
 #include <algorithm>
 
-void cc_halo_cache_purge(unsigned long uid);
-void nd_halo_cache_purge(unsigned long uid);
-void mg_halo_cache_purge(unsigned long uid) { cc_halo_cache_purge(uid); nd_halo_cache_purge(uid); }
-
 struct NLev {
   int n[3]; int PX, PY; long sz;
   double f[3];                    // 1/(36 h^2)
@@ -1009,7 +1005,6 @@ __global__ void __launch_bounds__(256) kk_nd_load_divu(NLev L, FV u, double fx, 
 }
 
 // ---- gather of the first agglomerated level (see mg_cc.hip: same scheme, nodes instead of cells) --------------------
-struct NGBox { int c0[3]; int n[3]; long off; };     // n = coarse CELLS of the box; nodes are n+1
 
 __global__ void kk_nd_restrict_pack(NLev F, NLev Cf /* flags + extents of the coarse box */, double *buf, long off) {
   NODE_IJK(Cf)
@@ -1038,8 +1033,8 @@ __global__ void kk_nd_coarsen_sigma_pack(NLev F, double *buf, long off, int nx, 
       for (int a = 0; a < 2; a++) s = s + F.sig[f + a + b * sy + c * sz];
   buf[off + i + (long)nx * (j + (long)ny * k)] = s * 0.125;
 }
-__global__ void kk_nd_unpack(NLev T, double *dst, const double *buf, const NGBox *gb, int nodal) {
-  const NGBox g = gb[blockIdx.z];
+__global__ void kk_nd_unpack(NLev T, double *dst, const double *buf, const GBox *gb, int nodal) {
+  const GBox g = gb[blockIdx.z];
   const int ex = g.n[0] + nodal, ey = g.n[1] + nodal, ez = g.n[2] + nodal;
   const int tot = ex * ey * ez;
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < tot; t += gridDim.x * blockDim.x) {
@@ -1108,21 +1103,10 @@ struct NDLev { std::vector<NBox> boxes; XPlan *halo_A = nullptr, *halo_B = nullp
                bool res_restricted = false; /* the last residual pass left the x- and z-sums of the full weighting in res (kk_nd_march_pair_rst): nd_restrict_down finishes along y */ };
 struct NDMG {
   std::vector<NDLev> dlev; std::vector<NLev> tail; int per[3]; double *d_nrm; unsigned pro_levels = 0;
-  std::vector<NGBox> gb; NGBox *d_gb = nullptr;
-  double *sendbuf = nullptr, *recvbuf = nullptr; size_t cnt_nodes = 0, cnt_cells = 0;
-  std::vector<long> loc_off_nodes, loc_off_cells;
-  // Krylov bottom solver (hg_bottom_solver = 1, 2, 3): its work arrays, of the bottom level's padded size; nullptr = the bottom sweeps
-  double *kry_w = nullptr; int kry_method = 0, kry_maxit = 0;
-  // ... its grid-wide form (krylov_grid.h) on a bottom level of VDN_KRYLOV_GRID_MIN_POINTS nodes or more: partial sums and state blocks; the iterations a visit launches
-  double *kry_part = nullptr; int kry_budget = 0; unsigned long long kry_kind = 0;
+  MgGather g_nodes, g_cells; GBox *d_gb = nullptr;      // (mg_plan.h; d_gb: [nodes... | cells...])
+  double *sendbuf = nullptr, *recvbuf = nullptr;
+  MgKrylov kry;      // Krylov bottom solver (hg_bottom_solver = 1, 2, 3; krylov_grid.h)
 };
-
-struct NdHaloKey { unsigned long uid; const void *p0; int lev, l, which, per; unsigned long long sig; bool operator<(const NdHaloKey &o) const {
-  return std::tie(uid, p0, lev, l, which, per, sig) < std::tie(o.uid, o.p0, o.lev, o.l, o.which, o.per, o.sig); } };      // sig: every local box's address (see mg_cc.hip HaloKey)
-static std::map<NdHaloKey, XPlan *> g_nd_halo_cache;
-void nd_halo_cache_purge(unsigned long uid) {
-  for (auto it = g_nd_halo_cache.begin(); it != g_nd_halo_cache.end();) { if (it->first.uid == uid) it = g_nd_halo_cache.erase(it); else ++it; }
-}
 
 // ghost nodes (index -1 or n+1 in some direction) of up to three node arrays := 0
 __global__ void kk_nd_zero_shell(NLev L, double *a0, double *a1, double *a2) {
@@ -1162,28 +1146,21 @@ static FV nd_view(const NLev &L, double *p, const int lo[3], int extra /* 3 for 
 static void nd_build(NDMG &M, const vdn_multifab *coeffs, const double *dx, const int bc[3][2]) {
   Prof prof_("nd_build");
   const vdn_layout *la = coeffs->la; const int lev = coeffs->lev;
-  const auto &gboxes = la->boxes[lev];
-  const int nb = (int)gboxes.size();
+  const int nb = (int)la->boxes[lev].size();
   for (int d = 0; d < 3; d++) M.per[d] = (bc[d][0] == VDN_BC_PER);
-  int bn[3]; for (int d = 0; d < 3; d++) bn[d] = gboxes[0].hi[d] - gboxes[0].lo[d] + 1;
-  for (const auto &b : gboxes) for (int d = 0; d < 3; d++) {
-    REQUIRE(b.hi[d] - b.lo[d] + 1 == bn[d], "nodal multigrid: all boxes of a level must have the same size");
-    REQUIRE((b.lo[d] - la->pd[lev].lo[d]) % bn[d] == 0, "nodal multigrid: boxes must be aligned to their size");
-  }
-  std::vector<int> nloc_of(ctx().nranks, 0);
-  for (int g = 0; g < nb; g++) nloc_of[la->owner[lev][g]]++;
-  int maxloc = 0; for (int r = 0; r < ctx().nranks; r++) maxloc = std::max(maxloc, nloc_of[r]);
+  const MgPlan P = mg_plan_of(la, lev);
+  REQUIRE(P.err.empty(), "nodal multigrid: %s", P.err.c_str());
   const int perbits = M.per[0] | (M.per[1] << 1) | (M.per[2] << 2);
-  int n[3] = { bn[0], bn[1], bn[2] }; double h[3] = { dx[0], dx[1], dx[2] };
-  int scale = 1;
-  for (;;) {
+  double h[3] = { dx[0], dx[1], dx[2] };
+  for (const MgDistLevel &PL : P.dist) {
+    const int *n = PL.n;
     NDLev DL;
     std::vector<XBoxInfo> xa, xb2, xr, xs;
-    vdn_box lpd; for (int d = 0; d < 3; d++) { lpd.lo[d] = 0; lpd.hi[d] = (la->pd[lev].hi[d] - la->pd[lev].lo[d] + 1) / scale - 1; DL.ng[d] = lpd.hi[d] + 1; }
+    vdn_box lpd; for (int d = 0; d < 3; d++) { lpd.lo[d] = 0; lpd.hi[d] = PL.ng[d] - 1; DL.ng[d] = PL.ng[d]; }
     for (int g = 0; g < nb; g++) {
       XBoxInfo x; memset(&x, 0, sizeof x);
-      int lo[3];
-      for (int d = 0; d < 3; d++) { lo[d] = (gboxes[g].lo[d] - la->pd[lev].lo[d]) / scale; x.vlo[d] = lo[d]; x.vhi[d] = lo[d] + n[d]; }   // nodes lo..lo+n
+      const int *lo = PL.lo[g].data();
+      for (int d = 0; d < 3; d++) { x.vlo[d] = lo[d]; x.vhi[d] = lo[d] + n[d]; }   // nodes lo..lo+n
       x.owner = la->owner[lev][g];
       XBoxInfo xc = x; for (int d = 0; d < 3; d++) xc.vhi[d] = lo[d] + n[d] - 1;                                                   // cells
       XBoxInfo xA = x, xB = x, xR = x;
@@ -1206,90 +1183,49 @@ static void nd_build(NDMG &M, const vdn_multifab *coeffs, const double *dx, cons
     if (nb > 1 || perbits) {
       const void *p0 = DL.boxes.empty() ? nullptr : (const void *)DL.boxes[0].A;
       GraphKey hk; for (const NBox &B : DL.boxes) { hk.put(B.A); hk.put(B.L.sz); }
-      auto get = [&](int which, const std::vector<XBoxInfo> &xv, const vdn_box &pdm) {
-        NdHaloKey key{ la->uid, p0, lev, (int)M.dlev.size(), which, perbits, hk.h };
-        auto it = g_nd_halo_cache.find(key);
-        if (it == g_nd_halo_cache.end()) { XPlan *P = xplan_build(xv, pdm, M.per, 1, 1); halo_cache_register(la->uid, P); it = g_nd_halo_cache.emplace(key, P).first; }
-        return it->second;
-      };
-      // the node "domain" for periodic shifts has the CELL period (node n is node 0): use the cell domain box
-      DL.halo_A = get(0, xa, lpd); DL.halo_B = get(1, xb2, lpd); DL.halo_res = get(2, xr, lpd); DL.halo_sig = get(3, xs, lpd);
+      auto get = [&](int which, const std::vector<XBoxInfo> &xv) { return mg_halo_plan(MgHaloKey{ la->uid, p0, lev, (int)M.dlev.size(), which, perbits, hk.h }, xv, lpd, M.per, false); };
+      // the node "domain" for periodic shifts has the CELL period (node n is node 0): the cell domain box
+      DL.halo_A = get(0, xa); DL.halo_B = get(1, xb2); DL.halo_res = get(2, xr); DL.halo_sig = get(3, xs);
     }
     DL.single_box = (nb == 1); for (int d = 0; d < 3; d++) DL.per[d] = M.per[d];
     M.dlev.push_back(DL);
-    bool can = true, next_dist = true;
-    for (int d = 0; d < 3; d++) { const int N = lpd.hi[d] + 1; if ((N & 1) || N <= 2) can = false; }
-    if (can) for (int d = 0; d < 3; d++) REQUIRE(!(n[d] & 1), "nodal multigrid: box extent %d is odd while the domain can still be coarsened", n[d]);
-    // several boxes: stop exchanging halos once the boxes get small (below 64 cells) -- every level that stays distributed costs
-    // ~10 latency-bound halo exchanges per V-cycle, the replicated tail below a 64^3-per-box level costs microseconds per pass
-    const int agglom = mg_agglom(la, lev);            // (mg_cc.hip: 64 across ranks, 128 where every box is this rank's)
-    const int min_dist = nb > 1 ? agglom : 4;
-    for (int d = 0; d < 3; d++) if (n[d] / 2 < min_dist || ((n[d] / 2) & 1)) next_dist = false;
-    if (!can) break;
-    if (!next_dist) {
-      int tn[3]; double th[3]; int cn[3];
-      for (int d = 0; d < 3; d++) { cn[d] = n[d] / 2; tn[d] = (lpd.hi[d] + 1) / 2; th[d] = h[d] * 2.0; }
-      for (;;) {
-        NLev T = nd_alloc_lev(tn, th);
-        for (int d = 0; d < 3; d++) { T.dirlo[d] = (bc[d][0] == VDN_BC_DIR); T.dirhi[d] = (bc[d][1] == VDN_BC_DIR); T.per[d] = M.per[d]; }
-        M.tail.push_back(T);
-        bool c2 = true;
-        for (int d = 0; d < 3; d++) if ((tn[d] & 1) || tn[d] <= 2) c2 = false;
-        if (!c2 || M.tail.size() >= 31) break;
-        for (int d = 0; d < 3; d++) { tn[d] /= 2; th[d] *= 2.0; }
-      }
-      const long per_nodes = (long)(cn[0] + 1) * (cn[1] + 1) * (cn[2] + 1), per_cells = (long)cn[0] * cn[1] * cn[2];
-      M.cnt_nodes = (size_t)per_nodes * maxloc; M.cnt_cells = (size_t)per_cells * maxloc;
-      std::vector<int> seen(ctx().nranks, 0);
-      std::vector<NGBox> gbn, gbc;
-      for (int g = 0; g < nb; g++) {
-        const int r = la->owner[lev][g], l = seen[r]++;
-        NGBox a, c;
-        for (int d = 0; d < 3; d++) { a.c0[d] = c.c0[d] = (gboxes[g].lo[d] - la->pd[lev].lo[d]) / scale / 2; a.n[d] = c.n[d] = cn[d]; }
-        a.off = (long)r * M.cnt_nodes + (long)l * per_nodes; c.off = (long)r * M.cnt_cells + (long)l * per_cells;
-        gbn.push_back(a); gbc.push_back(c);
-        if (r == ctx().rank) { M.loc_off_nodes.push_back((long)l * per_nodes); M.loc_off_cells.push_back((long)l * per_cells); }
-      }
-      M.gb = gbn; M.gb.insert(M.gb.end(), gbc.begin(), gbc.end());      // [nodes... | cells...]
-      M.d_gb = (NGBox *)arena_alloc(2 * nb * sizeof(NGBox));
-      HIPCHK(hipMemcpyAsync(M.d_gb, M.gb.data(), 2 * nb * sizeof(NGBox), hipMemcpyHostToDevice, ctx().stream));
-      HIPCHK(hipStreamSynchronize(ctx().stream));
-      M.sendbuf = (double *)arena_alloc(sizeof(double) * M.cnt_nodes);
-      M.recvbuf = (double *)arena_alloc(sizeof(double) * M.cnt_nodes * ctx().nranks);
-      break;
+    for (int d = 0; d < 3; d++) h[d] *= 2.0;
+  }
+  if (!P.tail.empty()) {
+    for (const auto &tn : P.tail) {
+      NLev T = nd_alloc_lev(tn.data(), h);
+      for (int d = 0; d < 3; d++) { T.dirlo[d] = (bc[d][0] == VDN_BC_DIR); T.dirhi[d] = (bc[d][1] == VDN_BC_DIR); T.per[d] = M.per[d]; h[d] *= 2.0; }
+      M.tail.push_back(T);
     }
-    for (int d = 0; d < 3; d++) { n[d] /= 2; h[d] *= 2.0; }
-    scale *= 2;
-    if (M.dlev.size() >= 31) break;
+    const int *cn = P.cn;
+    M.g_nodes = P.gather((long)(cn[0] + 1) * (cn[1] + 1) * (cn[2] + 1)); M.g_cells = P.gather((long)cn[0] * cn[1] * cn[2]);
+    std::vector<GBox> gb = M.g_nodes.gb; gb.insert(gb.end(), M.g_cells.gb.begin(), M.g_cells.gb.end());      // [nodes... | cells...]
+    M.d_gb = (GBox *)arena_alloc(2 * nb * sizeof(GBox));
+    HIPCHK(hipMemcpyAsync(M.d_gb, gb.data(), 2 * nb * sizeof(GBox), hipMemcpyHostToDevice, ctx().stream));
+    HIPCHK(hipStreamSynchronize(ctx().stream));      // gb is read by the copy
+    M.sendbuf = (double *)arena_alloc(sizeof(double) * M.g_nodes.cnt);
+    M.recvbuf = (double *)arena_alloc(sizeof(double) * M.g_nodes.cnt * ctx().nranks);
   }
   M.d_nrm = (double *)arena_alloc(256);
-  // Krylov bottom solver: where the coarsest level is held whole by this rank (mg_cc.hip, cc_build); a bottom level still distributed over boxes keeps its sweeps
-  const int hb = ctx().prm.hg_bottom_solver;
-  const int method = (hb == 1 || hb == 3) ? VDN_KRYLOV_BICGSTAB : (hb == 2 ? VDN_KRYLOV_CG : 0);
-  const NLev *bottom = !M.tail.empty() ? &M.tail.back() : ((M.dlev.size() > 1 && M.dlev.back().single_box && M.dlev.back().boxes.size() == 1) ? &M.dlev.back().boxes[0].L : nullptr);
-  if (method && bottom) {
-    M.kry_method = method;
-    M.kry_w = (double *)arena_alloc(sizeof(double) * bottom->sz * (method == VDN_KRYLOV_CG ? 4 : 7));
-    M.kry_maxit = 12 * (std::max(bottom->n[0], std::max(bottom->n[1], bottom->n[2])) + 1);
-    if ((long)(bottom->n[0] + 1) * (bottom->n[1] + 1) * (bottom->n[2] + 1) >= VDN_KRYLOV_GRID_MIN_POINTS) {
-      M.kry_part = (double *)arena_alloc(sizeof(double) * KG_DOUBLES);
-      GraphKey k; k.put(1); k.put(method); k.put(bottom->n); k.put(bottom->dirlo); k.put(bottom->dirhi); k.put(ctx().prm.hg_bottom_solver_eps);
-      M.kry_kind = k.h | 1ull;
-      M.kry_budget = M.kry_maxit;
-    }
+  // Krylov bottom solver: where this rank holds the coarsest level whole (a bottom level still distributed over boxes keeps its sweeps)
+  const int method = mg_krylov_method(ctx().prm.hg_bottom_solver);
+  if (method && P.whole_bottom) {
+    const NLev &B = !M.tail.empty() ? M.tail.back() : M.dlev.back().boxes[0].L;
+    GraphKey k; k.put(1); k.put(method); k.put(B.n); k.put(B.dirlo); k.put(B.dirhi); k.put(ctx().prm.hg_bottom_solver_eps);
+    mg_krylov_setup(M.kry, method, B.sz, std::max(B.n[0], std::max(B.n[1], B.n[2])) + 1, (long)(B.n[0] + 1) * (B.n[1] + 1) * (B.n[2] + 1), k);
   }
 }
-static KrylovArgs nd_krylov_args(const NDMG &M) { return KrylovArgs{ M.kry_w, bottom_stats_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry_maxit }; }
+static KrylovArgs nd_krylov_args(const NDMG &M) { return KrylovArgs{ M.kry.w, bottom_stats_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry.maxit }; }
 // one visit of the bottom level L (its periodic flags set) by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU; the result is left in phi
 static void nd_krylov_visit(const NDMG &M, const NLev &L, double *phi) {
-  if (!M.kry_part) { hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, phi, nd_krylov_args(M), M.kry_method); return; }
+  if (!M.kry.part) { hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, phi, nd_krylov_args(M), M.kry.method); return; }
   const NdKrylovLevel lv{ L, phi };
-  const KrylovGridArgs K{ M.kry_w, M.kry_part, bottom_stats_dev(1), bottom_exhausted_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry_maxit };
+  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(1), bottom_exhausted_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry.maxit };
   const long np = (long)(L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1);
   const long nfill = (L.per[0] || L.per[1] || L.per[2]) ? (long)(L.n[0] + 3) * (L.n[1] + 3) * (L.n[2] + 3) : 0;
   const bool singular = !(L.dirlo[0] || L.dirlo[1] || L.dirlo[2] || L.dirhi[0] || L.dirhi[1] || L.dirhi[2]);
-  if (M.kry_method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, singular, M.kry_budget, ctx().stream);
-  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, singular, M.kry_budget, ctx().stream);
+  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, singular, M.kry.budget, ctx().stream);
+  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, singular, M.kry.budget, ctx().stream);
 }
 
 // ---- distributed levels ------------------------------------------------------------------------------------------
@@ -1407,7 +1343,7 @@ static void nd_jacobi_t(NLev &L, int nsweeps, bool pre = false) {
   }
 }
 static void nd_bottom_t(const NDMG &M, NLev &L) {          // max(nub, 2 N^2) sweeps (same rule as the oracle)
-  if (M.kry_w) { nd_krylov_visit(M, L, L.phi); return; }
+  if (M.kry.w) { nd_krylov_visit(M, L, L.phi); return; }
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.hg_nub, 2 * N * N);
   hipLaunchKernelGGL(kk_nd_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, L.phi, L.tmp, ns, ctx().prm.hg_omega);
@@ -1445,14 +1381,14 @@ static void nd_restrict_down(NDMG &M, int l) {
     DL.res_restricted = false;
   } else {
     NLev &T = M.tail[0];
-    const int nb = (int)M.gb.size() / 2;
+    const int nb = (int)M.g_nodes.gb.size();
     for (size_t b = 0; b < DL.boxes.size(); b++) {
       const NLev &F = DL.boxes[b].L;
       NLev Cf = F;                       // extents + Dirichlet flags of the coarse box
       for (int d = 0; d < 3; d++) Cf.n[d] = F.n[d] / 2;
-      hipLaunchKernelGGL(kk_nd_restrict_pack, ng3(Cf.n[0] + 1, Cf.n[1] + 1, Cf.n[2] + 1), NBLK, 0, ctx().stream, F, Cf, M.sendbuf, M.loc_off_nodes[b]);
+      hipLaunchKernelGGL(kk_nd_restrict_pack, ng3(Cf.n[0] + 1, Cf.n[1] + 1, Cf.n[2] + 1), NBLK, 0, ctx().stream, F, Cf, M.sendbuf, M.g_nodes.loc_off[b]);
     }
-    comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_nodes);
+    comm_allgather_dev(M.sendbuf, M.recvbuf, M.g_nodes.cnt);
     hipLaunchKernelGGL(kk_nd_unpack, dim3(4, 1, (unsigned)nb), dim3(256), 0, ctx().stream, T, T.b, M.recvbuf, M.d_gb, 1);
   }
 }
@@ -1520,7 +1456,7 @@ static bool nd_small_end(NDMG &M, int dl, int tl) {
   const NLev &B = T.L[nl - 1];
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.hg_nu1; T.nu2 = P.hg_nu2; T.nbot = std::max(P.hg_nub, 2 * N * N); T.omega = P.hg_omega; { const NdOm o = nd_om(true, P.hg_nu1); T.om1 = o.om1; T.om2 = o.om2; T.nsp = o.nsp; }     // nd_bottom_t / nd_bottom_sweeps_global
-  if (M.kry_w) { hipLaunchKernelGGL(kk_nd_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, nd_krylov_args(M), M.kry_method); T.nbot = 0; /* no sweeps: no swap below */ }
+  if (M.kry.w) { hipLaunchKernelGGL(kk_nd_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, nd_krylov_args(M), M.kry.method); T.nbot = 0; /* no sweeps: no swap below */ }
   else
   hipLaunchKernelGGL(kk_nd_tailcycle, dim3(1), dim3(1024), 0, ctx().stream, T);
   int m = 0;                                           // the ping-pong state the sweeps leave behind (nd_jacobi_d / nd_jacobi_t)
@@ -1539,7 +1475,7 @@ static void nd_vcycle_d(NDMG &M, int l) {
   NDLev &DL = M.dlev[l];                               // phi = 0 on entry: written by kk_nd_restrict
   if (nd_small_end(M, l, 0)) return;
   const bool last = (l == (int)M.dlev.size() - 1);
-  if (last && M.tail.empty() && M.kry_w && DL.single_box && DL.boxes.size() == 1) {      // one box: the Krylov bottom solver, when one is selected (several boxes keep the sweeps)
+  if (last && M.tail.empty() && M.kry.w && DL.single_box && DL.boxes.size() == 1) {      // one box: the Krylov bottom solver, when one is selected (several boxes keep the sweeps)
     NBox &B = DL.boxes[0];
     NLev Lp = B.L;                      // (as nd_jacobi_d: the kernel refreshes periodic images itself)
     for (int d = 0; d < 3; d++) Lp.per[d] = DL.per[d];
@@ -1630,15 +1566,15 @@ static void nd_key_lev(GraphKey &k, const NLev &L) {
 static unsigned long long nd_graph_key(const NDMG &M, int what) {
   const vdn_params &P = ctx().prm;
   GraphKey k; k.put(what); k.put(P.hg_nu1); k.put(P.hg_nu2); k.put(P.hg_nub); k.put(P.hg_omega); k.put(P.hg_omega_pre1); k.put(P.hg_omega_pre2); k.put(M.per); k.put(M.d_nrm);
-  k.put(M.sendbuf); k.put(M.recvbuf); k.put(M.d_gb); k.put(M.cnt_nodes); k.put(M.cnt_cells);
+  k.put(M.sendbuf); k.put(M.recvbuf); k.put(M.d_gb); k.put(M.g_nodes.cnt); k.put(M.g_cells.cnt);
   for (const NDLev &DL : M.dlev) {
     k.put(xplan_serial(DL.halo_A)); k.put(xplan_serial(DL.halo_B)); k.put(xplan_serial(DL.halo_res)); k.put(xplan_serial(DL.halo_sig)); k.put(DL.ng); k.put(DL.flip); k.put(DL.single_box); k.put(DL.per); k.put(DL.res_restricted);
     for (const NBox &B : DL.boxes) { nd_key_lev(k, B.L); k.put(B.lo); k.put(B.A); k.put(B.B); k.put(B.hmask); k.put(xplan_serial(B.hA)); k.put(xplan_serial(B.hB)); }
   }
   for (const NLev &L : M.tail) nd_key_lev(k, L);
-  for (long o : M.loc_off_nodes) k.put(o);
-  if (M.kry_w) { k.put(M.kry_w); k.put(M.kry_method); k.put(M.kry_maxit); k.put(P.hg_bottom_solver_eps); }
-  if (M.kry_part) { k.put(M.kry_part); k.put(M.kry_budget); }
+  for (long o : M.g_nodes.loc_off) k.put(o);
+  if (M.kry.w) { k.put(M.kry.w); k.put(M.kry.method); k.put(M.kry.maxit); k.put(P.hg_bottom_solver_eps); }
+  if (M.kry.part) { k.put(M.kry.part); k.put(M.kry.budget); }
   return k.h;
 }
 static std::map<unsigned long long, NDMG> g_nd_post;
@@ -1689,10 +1625,10 @@ int nd_solve(NdRequest &q) {
   if (rebuild) nd_build(M, coeffs, dx, q.bc);          // (of `coeffs` only the layout, the level and the boxes are used)
   NDLev &D0 = M.dlev[0];
   if (!fixed_cycles || rebuild) {
-    bottom_form_set(1, M.kry_w ? (M.kry_part ? 2 : 1) : 0);
-    if (M.kry_w) { const int budget = bottom_budget_begin(1, M.kry_kind, M.kry_maxit); if (M.kry_part) M.kry_budget = budget; }
+    bottom_form_set(1, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
+    if (M.kry.w) { const int budget = bottom_budget_begin(1, M.kry.kind, M.kry.maxit); if (M.kry.part) M.kry.budget = budget; }
   }
-  if (M.kry_w && (!fixed_cycles || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
+  if (M.kry.w && (!fixed_cycles || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
   M.pro_levels = 0; g_nd_pro_levels = 0;
   if (rebuild) {
   // sigma: level 0 from the (ghost-filled) coeffs multifab; coarser distributed levels by averaging + halo exchange
@@ -1713,12 +1649,12 @@ int nd_solve(NdRequest &q) {
   }
   if (!M.tail.empty()) {
     NDLev &DL = M.dlev.back();
-    const int nb = (int)M.gb.size() / 2;
+    const int nb = (int)M.g_nodes.gb.size();
     for (size_t b = 0; b < DL.boxes.size(); b++) {
       const NLev &F = DL.boxes[b].L;
-      hipLaunchKernelGGL(kk_nd_coarsen_sigma_pack, ng3(F.n[0] / 2, F.n[1] / 2, F.n[2] / 2), NBLK, 0, st, F, M.sendbuf, M.loc_off_cells[b], F.n[0] / 2, F.n[1] / 2, F.n[2] / 2);
+      hipLaunchKernelGGL(kk_nd_coarsen_sigma_pack, ng3(F.n[0] / 2, F.n[1] / 2, F.n[2] / 2), NBLK, 0, st, F, M.sendbuf, M.g_cells.loc_off[b], F.n[0] / 2, F.n[1] / 2, F.n[2] / 2);
     }
-    comm_allgather_dev(M.sendbuf, M.recvbuf, M.cnt_cells);
+    comm_allgather_dev(M.sendbuf, M.recvbuf, M.g_cells.cnt);
     hipLaunchKernelGGL(kk_nd_unpack, dim3(4, 1, (unsigned)nb), dim3(256), 0, st, M.tail[0], M.tail[0].sig, M.recvbuf, M.d_gb + nb, 0);
     hipLaunchKernelGGL(kk_nd_fill_cells, ng3(M.tail[0].n[0] + 2, M.tail[0].n[1] + 2, M.tail[0].n[2] + 2), NBLK, 0, st, M.tail[0], M.tail[0].sig);
     for (size_t l = 1; l < M.tail.size(); l++) {

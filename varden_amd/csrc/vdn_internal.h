@@ -19,6 +19,7 @@
 #include <cmath>
 #include "../../include/varden_amd.h"
 #include "vdn_switches.h"
+#include "mg_plan.h"
 
 // ---- device-visible views ---------------------------------------------------------------------
 // one fab: p(alo0:, alo1:, alo2:, 0:nc-1), x fastest.  alo = valid lo - ng.
@@ -219,7 +220,9 @@ bool   xplan_has_remote(const XPlan *P);                  // some of the traffic
 void   xplan_free(XPlan *P);
 unsigned long xplan_serial(const XPlan *P);
 void   xplan_cache_purge(unsigned long layout_uid);   // drop every cached plan built for that layout
-void   halo_cache_register(unsigned long layout_uid, XPlan *P);
+// the multigrids' halo plans, cached across solves and dropped with their layout.  l: the multigrid level; which: the array (mg_cc.hip, mg_nd.hip); sig: every local box's address
+struct MgHaloKey { unsigned long uid; const void *p0; int lev, l, which, per; unsigned long long sig; };
+XPlan *mg_halo_plan(const MgHaloKey &key, const std::vector<XBoxInfo> &boxes, const vdn_box &pd, const int pmask[3], bool faces_only);
 std::vector<XBoxInfo> xboxes_of(const vdn_multifab *mf);
 // ---- views of another level's (or another box list's) data, for the inter-level operators on several ranks -----------------------
 // For every GLOBAL box j of `src`'s level: an FV that holds the part of box j (valid + ghost points) this rank's destination boxes
@@ -363,6 +366,7 @@ struct CcRequest : MgLevelRequest {
 int  cc_solve(CcRequest &q);
 struct CcKeep *cc_keep_new(); void cc_keep_free(struct CcKeep *k);
 int  mg_agglom(const vdn_layout *la, int lev);     // box width below which a multi-box multigrid level is gathered into one box (mg_cc.hip)
+MgPlan mg_plan_of(const vdn_layout *la, int lev);  // the shape of the single-level multigrid hierarchies on that level (mg_plan.h; mg_cc.hip)
 void cc_smooth(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const double *dx, const int bc[3][2], int nsweeps);
 void cc_bench_smoother(vdn_multifab *rh, vdn_multifab *phi, vdn_multifab **beta, const vdn_multifab *rho, const double *dx, const int bc[3][2],
                        int nlaunch, double *avg_ms, long *cells, int slab_sweeps = 0);
