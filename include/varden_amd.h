@@ -136,12 +136,13 @@ int  vdn_init(const vdn_params *prm, int rank, int nranks, int device);
  * Groups: transport rehearsal (VDN_FORCE_PACKED, VDN_RCCL_LIB + VDN_TESTING); runtime (VDN_ARENA_POISON, VDN_POLL, VDN_NO_GRAPHS,
  * VDN_NO_ROCTX, VDN_KEEP_SETS, VDN_KEPT_BOUND); advance (VDN_NO_SLOPE_CACHE, VDN_NO_FORCE_REUSE); Godunov launch forms (VDN_GOD_*, VDN_GODUNOV_*, VDN_SLOPES_MARCH,
  * VDN_FUSED_KCHUNKS); cell-centred multigrid (VDN_GSRB_PAIR, VDN_CC_HALO_FACES, VDN_MG_*, VDN_MAC_*, VDN_OVERLAP*); nodal
- * multigrid (VDN_ND_*, VDN_HG_FAST); composite solves (VDN_NDF_*, VDN_NDM_*, VDN_MLCC_*, VDN_FB_FACES); box-batched kernels (VDN_BATCH_*). */
+ * multigrid (VDN_ND_*, VDN_HG_FAST, and VDN_MG_LDS, which both multigrids read: their 16^3..64^3-cell levels launch by launch); composite solves (VDN_NDF_*, VDN_NDM_*, VDN_MLCC_*, VDN_FB_FACES); box-batched kernels (VDN_BATCH_*). */
 const char *vdn_debug_switches(void);
 /* "release": libvarden_amd.so -- reads NO environment variable (the switches are compiled out, RCCL is the only transport); "testing": libvarden_amd_testing.so,
  * the same objects with the switch table and the test-transport seam compiled in (the test suite, the A/B tools, the one-GPU transport rehearsal).
  * The testing build alone also exports `unsigned vdn_nd_prolong_fused_levels(void)`: bit l is set when level l of the last nodal solve took its coarse
- * correction inside the first post-smoothing march (the read-back of tests/test_nd_prolong_fused_gpu.py; not part of the product's interface). */
+ * correction inside the first post-smoothing march (the read-back of tests/test_nd_prolong_fused_gpu.py; not part of the product's interface), and
+ * `unsigned vdn_nd_lds_levels(void)`: bit l is set when level l of the last nodal solve ran as one launch down and one up (tests/test_nd_lds_levels_gpu.py). */
 const char *vdn_build_flavour(void);
 int  vdn_finalize(void);
 const char *vdn_last_error(void);

@@ -15,6 +15,7 @@
 #include "mg_stop.h"
 #include "krylov_wg.h"
 #include "krylov_grid.h"
+#include "nd_lds_plan.h"
 #include <tuple>
 #include <algorithm>
 
@@ -661,6 +662,162 @@ static void nd_launch_prolong(const NLev &F, const NLev &C, int c00, int c01, in
   const int kchunk = nzp > 64 ? 16 : (nzp > 16 ? 8 : 2);
   hipLaunchKernelGGL(kk_nd_prolong_m, dim3((F.n[0] + 64) / 64, (F.n[1] + 4) / 4, (nzp + kchunk - 1) / kchunk), dim3(64, 4, 1), 0, ctx().stream, F, C, c00, c01, c02, kchunk);
 }
+// ---- 17^3 .. 65^3 nodes: a level's way down in one launch and its way up in another (nd_lds_plan.h; the cell-centred pair is kk_cc_lds_down / _up) ----------
+// These levels took six dependent launches of 5-9 us per visit -- two pre-smoothing marches, the residual march, kk_nd_restrict, kk_nd_prolong_m, the
+// post-smoothing march -- for about a microsecond of work.  Here a workgroup owns an 8^3 tile of nodes and does the halo work of its neighbours again instead of
+// waiting for them: phi is zero on entry (nd_vcycle_d), so both pre-smoothing sweeps and the residual need only b and sigma, which nobody writes meanwhile.
+// Per node the code of the separate launches: nd_stencil on the same operands, the `!dir && diag != 0` update, nd_fw27's order, nd_interp8's sums -- same bits.
+// LDS of the down kernel: two phi boxes of 13^3 (ping-pong; the first holds the residual in the end) and sigma on 14^3 cells: 57 KB of the 64 KB a workgroup may take.
+#define ND_LDS_NT 1024
+DEVI void nd_lds_gather(const double *__restrict__ ph, int e, int c, const double *__restrict__ sgb, int se, int sc, double p[3][3][3], double sg[2][2][2]) {
+  #pragma unroll
+  for (int k = 0; k < 3; k++)
+    #pragma unroll
+    for (int j = 0; j < 3; j++)
+      #pragma unroll
+      for (int i = 0; i < 3; i++) p[k][j][i] = ph[c + (i - 1) + (j - 1) * e + (k - 1) * e * e];
+  #pragma unroll
+  for (int k = 0; k < 2; k++)
+    #pragma unroll
+    for (int j = 0; j < 2; j++)
+      #pragma unroll
+      for (int i = 0; i < 2; i++) sg[k][j][i] = sgb[sc + i + j * se + k * se * se];
+}
+__global__ void __launch_bounds__(ND_LDS_NT) kk_nd_lds_down(NLev L, NLev C, double om1, double om2) {
+  constexpr int E = ND_LDS_BOX, E3 = E * E * E, S = ND_LDS_SIG, S3 = S * S * S;
+  __shared__ double pa[E3], pb[E3], sgb[S3];
+  const int ta[3] = { (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z };
+  const int x0 = nd_lds_box_lo(ta[0]), y0 = nd_lds_box_lo(ta[1]), z0 = nd_lds_box_lo(ta[2]);          // the sigma box starts one cell below
+  const int tid = threadIdx.x;
+  for (int t = tid; t < S3; t += ND_LDS_NT) {                            // sigma, zero outside the level's cells (as the arrays hold it)
+    const int i = x0 - 1 + t % S, j = y0 - 1 + (t / S) % S, k = z0 - 1 + t / (S * S);
+    const bool in = i >= 0 && i < L.n[0] && j >= 0 && j < L.n[1] && k >= 0 && k < L.n[2];
+    sgb[t] = in ? L.sig[nidx(L, i, j, k)] : 0.0;
+  }
+  for (int t = tid; t < E3; t += ND_LDS_NT) pb[t] = 0.0;                  // sweep 2 writes its region only: the nodes around it are outside the level or unread
+  const NdW W = nd_weights(L.f);
+  __syncthreads();
+  // sweep 1 on the whole box, from phi = 0: the generic code on zeros
+  for (int t = tid; t < E3; t += ND_LDS_NT) {
+    const int bi = t % E, bj = (t / E) % E, bk = t / (E * E);
+    const int i = x0 + bi, j = y0 + bj, k = z0 + bk;
+    double v = 0.0;
+    if (i >= 0 && i <= L.n[0] && j >= 0 && j <= L.n[1] && k >= 0 && k <= L.n[2]) {
+      double p[3][3][3], sg[2][2][2];
+      #pragma unroll
+      for (int c = 0; c < 3; c++)
+        #pragma unroll
+        for (int b = 0; b < 3; b++)
+          #pragma unroll
+          for (int a = 0; a < 3; a++) p[c][b][a] = 0.0;
+      #pragma unroll
+      for (int c = 0; c < 2; c++)
+        #pragma unroll
+        for (int b = 0; b < 2; b++)
+          #pragma unroll
+          for (int a = 0; a < 2; a++) sg[c][b][a] = sgb[(bi + a) + (bj + b) * S + (bk + c) * S * S];
+      const double p0 = p[1][1][1];
+      double Kp, diag; nd_stencil(W, p, sg, Kp, diag);
+      if (!nd_is_dir(L, i, j, k) && diag != 0.0) v = p0 + om1 * ((L.b[nidx(L, i, j, k)] - Kp) / diag);
+    }
+    pa[t] = v;
+  }
+  __syncthreads();
+  // sweep 2 on the box shrunk by one; the owned nodes go to the array that holds phi after two plain sweeps
+  {
+    constexpr int R = E - 2;
+    const NdLdsRange ox = nd_lds_own_fine(L.n[0], ta[0]), oy = nd_lds_own_fine(L.n[1], ta[1]), oz = nd_lds_own_fine(L.n[2], ta[2]);
+    for (int t = tid; t < R * R * R; t += ND_LDS_NT) {
+      const int bi = 1 + t % R, bj = 1 + (t / R) % R, bk = 1 + t / (R * R);
+      const int i = x0 + bi, j = y0 + bj, k = z0 + bk;
+      if (!(i >= 0 && i <= L.n[0] && j >= 0 && j <= L.n[1] && k >= 0 && k <= L.n[2])) continue;
+      double p[3][3][3], sg[2][2][2];
+      const int c = bi + bj * E + bk * E * E;
+      nd_lds_gather(pa, E, c, sgb, S, bi + bj * S + bk * S * S, p, sg);
+      const double p0 = p[1][1][1];
+      const long g = nidx(L, i, j, k);
+      double Kp, diag; nd_stencil(W, p, sg, Kp, diag);
+      double v = p0;
+      if (!nd_is_dir(L, i, j, k) && diag != 0.0) v = p0 + om2 * ((L.b[g] - Kp) / diag);
+      pb[c] = v;
+      if (i >= ox.lo && i <= ox.hi && j >= oy.lo && j <= oy.hi && k >= oz.lo && k <= oz.hi) L.phi[g] = v;
+    }
+  }
+  __syncthreads();
+  // the residual where the full weighting of the owned coarse nodes reads it, zero elsewhere (outside the level; Dirichlet nodes), into the first box
+  {
+    constexpr int R = E - 2;
+    const NdLdsRange rx = nd_lds_resid(L.n[0], ta[0]), ry = nd_lds_resid(L.n[1], ta[1]), rz = nd_lds_resid(L.n[2], ta[2]);
+    for (int t = tid; t < R * R * R; t += ND_LDS_NT) {
+      const int bi = 2 + t % R, bj = 2 + (t / R) % R, bk = 2 + t / (R * R);
+      const int i = x0 + bi, j = y0 + bj, k = z0 + bk;
+      const int c = bi + bj * E + bk * E * E;
+      double r = 0.0;
+      if (i >= 0 && i <= min(L.n[0], rx.hi) && j >= 0 && j <= min(L.n[1], ry.hi) && k >= 0 && k <= min(L.n[2], rz.hi) && !nd_is_dir(L, i, j, k)) {
+        double p[3][3][3], sg[2][2][2];
+        nd_lds_gather(pb, E, c, sgb, S, bi + bj * S + bk * S * S, p, sg);
+        double Kp, diag; nd_stencil(W, p, sg, Kp, diag);
+        r = L.b[nidx(L, i, j, k)] - Kp;
+      }
+      pa[c] = r;
+    }
+  }
+  __syncthreads();
+  // full weighting of the owned coarse nodes (kk_nd_restrict)
+  {
+    const NdLdsRange cx = nd_lds_own_coarse(L.n[0], ta[0]), cy = nd_lds_own_coarse(L.n[1], ta[1]), cz = nd_lds_own_coarse(L.n[2], ta[2]);
+    constexpr int Q = ND_LDS_T / 2 + 1;
+    for (int t = tid; t < Q * Q * Q; t += ND_LDS_NT) {
+      const int qi = t % Q, qj = (t / Q) % Q, qk = t / (Q * Q);
+      const int i = cx.lo + qi, j = cy.lo + qj, k = cz.lo + qk;
+      if (i > cx.hi || j > cy.hi || k > cz.hi) continue;
+      double s = 0.0;
+      if (!nd_is_dir(C, i, j, k)) s = nd_fw27(pa + (3 + 2 * qi) + (3 + 2 * qj) * E + (3 + 2 * qk) * E * E, E, E * E);
+      const long cn = nidx(C, i, j, k);
+      C.b[cn] = s * 0.125;
+      C.phi[cn] = 0.0;
+    }
+  }
+}
+// phi + the trilinear correction on the tile grown by one, one post-smoothing sweep on the owned nodes: L.phi -> L.tmp (the host swaps, as for any sweep)
+__global__ void __launch_bounds__(ND_LDS_NT) kk_nd_lds_up(NLev L, NLev C, double omega) {
+  constexpr int E = ND_LDS_UBOX, E3 = E * E * E, S = ND_LDS_USIG, S3 = S * S * S;
+  __shared__ double ph[E3], sgb[S3];
+  const int ta[3] = { (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z };
+  const int x0 = nd_lds_ubox_lo(ta[0]), y0 = nd_lds_ubox_lo(ta[1]), z0 = nd_lds_ubox_lo(ta[2]);       // the sigma box starts at the same index
+  const int tid = threadIdx.x;
+  for (int t = tid; t < S3; t += ND_LDS_NT) {
+    const int i = x0 + t % S, j = y0 + (t / S) % S, k = z0 + t / (S * S);
+    const bool in = i >= 0 && i < L.n[0] && j >= 0 && j < L.n[1] && k >= 0 && k < L.n[2];
+    sgb[t] = in ? L.sig[nidx(L, i, j, k)] : 0.0;
+  }
+  for (int t = tid; t < E3; t += ND_LDS_NT) {                            // kk_nd_prolong_m's update of the node as it is loaded
+    const int i = x0 + t % E, j = y0 + (t / E) % E, k = z0 + t / (E * E);
+    double v = 0.0;
+    if (i >= 0 && i <= L.n[0] && j >= 0 && j <= L.n[1] && k >= 0 && k <= L.n[2]) {
+      v = L.phi[nidx(L, i, j, k)];
+      if (!nd_is_dir(L, i, j, k)) v = v + nd_interp8(C, C.phi, i >> 1, j >> 1, k >> 1, i & 1, j & 1, k & 1);
+    }
+    ph[t] = v;
+  }
+  const NdW W = nd_weights(L.f);
+  __syncthreads();
+  const NdLdsRange ox = nd_lds_own_fine(L.n[0], ta[0]), oy = nd_lds_own_fine(L.n[1], ta[1]), oz = nd_lds_own_fine(L.n[2], ta[2]);
+  constexpr int R = ND_LDS_T + 1;
+  for (int t = tid; t < R * R * R; t += ND_LDS_NT) {
+    const int bi = 1 + t % R, bj = 1 + (t / R) % R, bk = 1 + t / (R * R);
+    const int i = x0 + bi, j = y0 + bj, k = z0 + bk;
+    if (i > ox.hi || j > oy.hi || k > oz.hi) continue;
+    double p[3][3][3], sg[2][2][2];
+    nd_lds_gather(ph, E, bi + bj * E + bk * E * E, sgb, S, (bi - 1) + (bj - 1) * S + (bk - 1) * S * S, p, sg);
+    const double p0 = p[1][1][1];
+    const long g = nidx(L, i, j, k);
+    double Kp, diag; nd_stencil(W, p, sg, Kp, diag);
+    double v = p0;
+    if (!nd_is_dir(L, i, j, k) && diag != 0.0) v = p0 + omega * ((L.b[g] - Kp) / diag);
+    L.tmp[g] = v;
+  }
+}
 __global__ void kk_nd_coarsen_sigma(NLev F, NLev C) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
@@ -1102,7 +1259,7 @@ struct NDLev { std::vector<NBox> boxes; XPlan *halo_A = nullptr, *halo_B = nullp
                int rev = 0; /* tile order of the next march (nd_launch_march) */
                bool res_restricted = false; /* the last residual pass left the x- and z-sums of the full weighting in res (kk_nd_march_pair_rst): nd_restrict_down finishes along y */ };
 struct NDMG {
-  std::vector<NDLev> dlev; std::vector<NLev> tail; int per[3]; double *d_nrm; unsigned pro_levels = 0;
+  std::vector<NDLev> dlev; std::vector<NLev> tail; int per[3]; double *d_nrm; unsigned pro_levels = 0, lds_levels = 0;
   MgGather g_nodes, g_cells; GBox *d_gb = nullptr;      // (mg_plan.h; d_gb: [nodes... | cells...])
   double *sendbuf = nullptr, *recvbuf = nullptr;
   MgKrylov kry;      // Krylov bottom solver (hg_bottom_solver = 1, 2, 3; krylov_grid.h)
@@ -1470,6 +1627,18 @@ static bool nd_small_end(NDMG &M, int dl, int tl) {
   }
   return true;
 }
+// may level l >= 1 of a V-cycle run as kk_nd_lds_down / kk_nd_lds_up?  (cc_lds_level's conditions; VDN_MG_LDS=0: never; the extents: nd_lds_plan.h)
+static bool nd_lds_level(const NDMG &M, int l) {
+  const vdn_params &P = ctx().prm;
+  if (!sw().mg_lds || l < 1 || l + 1 >= (int)M.dlev.size() || ctx().nranks != 1 || P.hg_nu1 != 2 || P.hg_nu2 != 1 || M.per[0] || M.per[1] || M.per[2]) return false;
+  const NDLev &D = M.dlev[l], &DC = M.dlev[l + 1];
+  if (!(D.single_box && D.boxes.size() == 1 && !D.halo_A && !D.halo_B && !D.halo_res && !(D.per[0] || D.per[1] || D.per[2]) && DC.single_box && DC.boxes.size() == 1)) return false;
+  const NBox &B = D.boxes[0];
+  for (int d = 0; d < 3; d++) if (!nd_lds_extent_ok(B.L.n[d]) || B.lo[d] != 0 || DC.boxes[0].L.n[d] * 2 != B.L.n[d]) return false;
+  return true;
+}
+static unsigned g_nd_lds_levels = 0;      // the levels (bit l) that ran as kk_nd_lds_down / _up in the last nd_solve; the testing build hands it out (runtime.hip)
+unsigned nd_last_lds_levels() { return g_nd_lds_levels; }
 static void nd_vcycle_d(NDMG &M, int l) {
   const vdn_params &P = ctx().prm;
   NDLev &DL = M.dlev[l];                               // phi = 0 on entry: written by kk_nd_restrict
@@ -1483,6 +1652,19 @@ static void nd_vcycle_d(NDMG &M, int l) {
     return;
   }
   if (last && M.tail.empty()) { nd_jacobi_d(DL, nd_bottom_sweeps_global(DL)); return; }
+  if (nd_lds_level(M, l)) {                 // 17^3 .. 65^3 nodes: sweeps + residual + restriction in one launch, prolongation + sweep in another
+    const dim3 g((unsigned)nd_lds_tiles(DL.boxes[0].L.n[0]), (unsigned)nd_lds_tiles(DL.boxes[0].L.n[1]), (unsigned)nd_lds_tiles(DL.boxes[0].L.n[2]));
+    const NdOm om = nd_om(true, P.hg_nu1);
+    hipLaunchKernelGGL(kk_nd_lds_down, g, dim3(ND_LDS_NT), 0, ctx().stream, DL.boxes[0].L, M.dlev[l + 1].boxes[0].L, om.at(0), om.at(1));
+    M.lds_levels |= 1u << l;                // (kept in M, as pro_levels)
+    nd_vcycle_d(M, l + 1);
+    nd_halo_phi(M.dlev[l + 1]);             // the coarse level's ghost nodes, as nd_prolong_smooth (one box, no periodic axis: nothing to exchange)
+    NDLev &D = M.dlev[l];                   // (the levels below swapped their phi / tmp: take both afresh)
+    hipLaunchKernelGGL(kk_nd_lds_up, g, dim3(ND_LDS_NT), 0, ctx().stream, D.boxes[0].L, M.dlev[l + 1].boxes[0].L, P.hg_omega);
+    std::swap(D.boxes[0].L.phi, D.boxes[0].L.tmp);      // one sweep, as nd_jacobi_d leaves it
+    D.flip = !D.flip;
+    return;
+  }
   nd_jacobi_d(DL, P.hg_nu1, true);
   nd_residual_d(M, DL, false);
   nd_restrict_down(M, l);
@@ -1630,6 +1812,7 @@ int nd_solve(NdRequest &q) {
   }
   if (M.kry.w && (!fixed_cycles || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
   M.pro_levels = 0; g_nd_pro_levels = 0;
+  M.lds_levels = 0; g_nd_lds_levels = 0;
   if (rebuild) {
   // sigma: level 0 from the (ghost-filled) coeffs multifab; coarser distributed levels by averaging + halo exchange
   for (size_t b = 0; b < D0.boxes.size(); b++) {
@@ -1736,6 +1919,7 @@ int nd_solve(NdRequest &q) {
   }
   q.cycles = s.cycles; q.res0 = bnorm; q.res = s.res;
   g_nd_pro_levels = M.pro_levels;
+  g_nd_lds_levels = M.lds_levels;
   if (!keep && !fast) arena_release(mark);  // with `keep` / `fast` the hierarchy stays in the caller's arena scope
   return s.conv ? 0 : 1;
 }

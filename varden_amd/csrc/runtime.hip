@@ -223,6 +223,9 @@ static void env_warn_unknown() {
 // testing build only (tests/test_nd_prolong_fused_gpu.py): which levels of the last nodal solve took the prolonging march (mg_nd.hip)
 unsigned nd_last_prolong_levels();
 extern "C" unsigned vdn_nd_prolong_fused_levels(void) { return nd_last_prolong_levels(); }
+// ... and which ran as kk_nd_lds_down / kk_nd_lds_up (tests/test_nd_lds_levels_gpu.py)
+unsigned nd_last_lds_levels();
+extern "C" unsigned vdn_nd_lds_levels(void) { return nd_last_lds_levels(); }
 #endif
 extern "C" const char *vdn_debug_switches(void) {
   static std::string out;

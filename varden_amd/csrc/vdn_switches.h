@@ -62,7 +62,7 @@
   X(mg_restrict_fused, "VDN_MG_RESTRICT_FUSED", ON, true, "0: cell-centred residual and restriction as two passes") \
   X(mg_tailcycle, "VDN_MG_TAILCYCLE", ON, true, "0: the smallest levels launch by launch instead of one single-workgroup cycle") \
   X(mg_prolong_fused, "VDN_MG_PROLONG_FUSED", ON, true, "0: cell-centred prolongation as its own pass instead of inside the first post-smoothing colour pass") \
-  X(mg_lds, "VDN_MG_LDS", ON, true, "0: the 16^3..64^3 cell-centred levels launch by launch instead of the LDS-tiled down / up kernels") \
+  X(mg_lds, "VDN_MG_LDS", ON, true, "0: the 16^3..64^3-cell levels of both multigrids (cell-centred and nodal) launch by launch instead of the LDS-tiled down / up kernels") \
   X(mac_stored_beta, "VDN_MAC_STORED_BETA", SET, false, "1: the finest MAC level reads stored face coefficients instead of recomputing them from rho") \
   X(mac_fast, "VDN_MAC_FAST", ON, true, "0: macproject with its rh / phi / beta multifabs as the reference has them") \
   X(hg_fast, "VDN_HG_FAST", ON, true, "0: hgproject with its rh / phi / coeffs multifabs as the reference has them") \
