@@ -9,6 +9,9 @@ Large bottom levels (profiles/bottom_solver_probe_wide.txt): sizes 150 and 300 (
 max(8, N^2) = 5625 sweeps of 75^3 cells per V-cycle there, minutes per step.  The crossover between the two Krylov forms: sizes 34, 50, 66, 90 (bottoms 17^3,
 25^3, 33^3, 45^3 cells), rows = cg, once with a library built with -DVDN_KRYLOV_GRID_MIN_POINTS=1073741824 (always one workgroup) and once with
 -DVDN_KRYLOV_GRID_MIN_POINTS=0 (always the whole GPU); `lib` names the library to load instead of the package's.
+Large bottom levels, dm = 2 (profiles/bottom_solver_probe_2d_wide.txt): sizes 150, 300 (bottom 75^2 cells), 1000 (125^2), 3000 (375^2) and the controls 128
+and 200, dm = 2, rows = cg, this build and the parent commit's library in turn.  Their crossover: sizes 102, 142, 154, 162, 170, 182, 202, 282 (bottoms 51^2
+.. 141^2 cells), the library built with -DVDN_KRYLOV_GRID_MIN_POINTS_2D=1073741824 and with =0.
 usage: python tools/bottom_solver_probe.py [sizes, default 200,100,256 -- dm = 2: 200,100,128] [nsteps=10] [dm=3] [rows=both|cg|sweeps] [lib]
        (output: profiles/bottom_solver_probe.txt; dm = 2: profiles/bottom_solver_probe_2d.txt)"""
 import os

@@ -27,7 +27,7 @@
 // BoxLib 2-D layout p(lo1-ng:hi1+ng, lo2-ng:hi2+ng, nc).
 #include "vdn_dev.h"
 #include "mg_stop.h"
-#include "krylov_wg.h"
+#include "krylov_grid.h"
 #include <vector>
 #include <algorithm>
 
@@ -242,7 +242,8 @@ __global__ void kk_c2_periodic(C2 L, int per0, int per1) {
 // The V-cycles stop where an extent turns odd (200 -> 100 -> 50 -> 25) and there is no one-workgroup sweep kernel in this file: the 25^2 bottom takes
 // max(mg_nub, N^2) = 625 red-black sweeps of two to four launches each.  CG or BiCGStab by ONE workgroup in ONE launch takes their place.  c2_apply and the
 // level's arrays are used as they are; the Neumann / Dirichlet closures sit in bx / by and rely on ghost entries that read as zero (wg_krylov zeroes its
-// work arrays of the padded size c2_size; the periodic fill writes ghosts only along a periodic direction).
+// work arrays of the padded size c2_size; the periodic fill writes ghosts only along a periodic direction).  A bottom of VDN_KRYLOV_GRID_MIN_POINTS_2D cells
+// or more (n_cell = 1000: 125^2) is too much for one workgroup: there the same iteration runs over the whole GPU (krylov_grid.h, C2KrylovLevel below).
 DEVI void wg_c2_periodic(const C2 &L, int per0, int per1) {      // kk_c2_periodic by one workgroup; nothing without a periodic direction, else ends in a barrier
   if (!per0 && !per1) return;
   const int nx = L.n0 + 2, np = nx * (L.n1 + 2);
@@ -255,12 +256,24 @@ DEVI void wg_c2_periodic(const C2 &L, int per0, int per1) {      // kk_c2_period
   }
   __syncthreads();
 }
+// ... one ghost entry at a time, for the grid-wide form (krylov_grid.h): the 2 n1 entries beside the x faces when x is periodic, then the 2 n0 beside the y faces
+// when y is.  The corners wg_c2_periodic also writes are left out: the 5-point operator never reads them.  The source is a cell of the level, never a ghost.
+DEVI int c2_periodic_count(int n0, int n1, int per0, int per1) { return (per0 ? 2 * n1 : 0) + (per1 ? 2 * n0 : 0); }
+DEVI void c2_periodic_point(const C2 &L, int per0, int t) {
+  const int nx = per0 ? 2 * L.n1 : 0;
+  int i, j, si, sj;
+  if (t < nx) { j = sj = t >> 1; i = (t & 1) ? L.n0 : -1; si = (t & 1) ? 0 : L.n0 - 1; }
+  else { const int u = t - nx; i = si = u >> 1; j = (u & 1) ? L.n1 : -1; sj = (u & 1) ? 0 : L.n1 - 1; }
+  L.phi[c2i(L, i, j)] = L.phi[c2i(L, si, sj)];
+}
 struct C2KrylovOp {
   const C2 &L; int per0, per1, sing;
   DEVI int count() const { return L.n0 * L.n1; }
   DEVI bool point(int t, long &c, int &i, int &j, int &k) const { i = t % L.n0; j = t / L.n0; k = 0; c = c2i(L, i, j); return true; }
   DEVI void apply(const double *v, long, int i, int j, int, double &Av, double &diag) const { C2 Lv = L; Lv.phi = const_cast<double *>(v); c2_apply(Lv, i, j, Av, diag); }
   DEVI void fill(double *v) const { C2 Lv = L; Lv.phi = v; wg_c2_periodic(Lv, per0, per1); }
+  DEVI int fill_count() const { return c2_periodic_count(L.n0, L.n1, per0, per1); }
+  DEVI void fill_point(double *v, int t) const { C2 Lv = L; Lv.phi = v; c2_periodic_point(Lv, per0, t); }
   DEVI long size() const { return (long)(L.n0 + 2) * (L.n1 + 2); }
   DEVI const double *rhs() const { return L.rh; }
   DEVI double *x() const { return L.phi; }
@@ -270,6 +283,11 @@ __global__ void __launch_bounds__(1024) kk_c2_bottom_krylov(C2 L, KrylovArgs K, 
   const C2KrylovOp op{ L, per0, per1, singular };
   if (method == VDN_KRYLOV_CG) wg_krylov<VDN_KRYLOV_CG>(op, K); else wg_krylov<VDN_KRYLOV_BICGSTAB>(op, K);
 }
+// the level as the grid-wide form takes it (krylov_grid.h): by value, for bottom levels of VDN_KRYLOV_GRID_MIN_POINTS_2D cells and more
+struct C2KrylovLevel {
+  C2 L; int per0, per1, sing;
+  DEVI C2KrylovOp op() const { return C2KrylovOp{ L, per0, per1, sing }; }
+};
 struct C2Bc { int e[2][2]; int lo[2]; };               // elliptic boundary codes of the DOMAIN faces; lo: the domain's first cell
 struct C2Gx { C2 L; C2Bc B; int has_alpha; };           // what every box's load / store launch shares (kk_batched's `extra`)
 // The per-box descriptors of the gathered level (vdn_dev.h: kk_batched).  r: the points THIS box writes -- each point of the domain
@@ -339,7 +357,22 @@ static void gather_level(double *base, long ndoubles) {
 }
 static dim3 g2(int nx, int ny) { return dim3((nx + 63) / 64, (ny + 3) / 4, 1); }
 struct CC2MG { std::vector<C2> lev; int per[2]; double *d_nrm;
-  double *kry_w = nullptr; int kry_method = 0, kry_singular = 0, kry_maxit = 0; };      // Krylov bottom solver: its work arrays (nullptr = the bottom sweeps)
+  MgKrylov kry; int kry_singular = 0; };      // Krylov bottom solver (kry.w == nullptr: the bottom sweeps; kry.part: the grid-wide form)
+// one visit of the bottom level L by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU
+static void c2_krylov_visit(const CC2MG &M, const C2 &L) {
+  const double eps = ctx().prm.mg_bottom_solver_eps;
+  if (!M.kry.part) {
+    const KrylovArgs K{ M.kry.w, bottom_stats_dev(0), eps, M.kry.maxit };
+    hipLaunchKernelGGL(kk_c2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry.method, M.kry_singular, M.per[0], M.per[1]);
+    return;
+  }
+  const C2KrylovLevel lv{ L, M.per[0], M.per[1], M.kry_singular };
+  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(0), bottom_exhausted_dev(0), eps, M.kry.maxit };
+  const long np = (long)L.n0 * L.n1;
+  const long nfill = (M.per[0] ? 2 * L.n1 : 0) + (M.per[1] ? 2 * L.n0 : 0);      // c2_periodic_count
+  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, c2_size(L.n0, L.n1), np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
+  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, c2_size(L.n0, L.n1), np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
+}
 static void c2_gsrb(const CC2MG &M, const C2 &L, int ns) {
   hipStream_t st = ctx().stream;
   for (int s = 0; s < ns; s++) for (int col = 0; col < 2; col++) {
@@ -359,10 +392,7 @@ static void c2_vcycle(const CC2MG &M, int l) {
   const C2 &L = M.lev[l];
   HIPCHK(hipMemsetAsync(L.phi, 0, sizeof(double) * c2_size(L.n0, L.n1), ctx().stream));
   if (l == (int)M.lev.size() - 1) {
-    if (M.kry_w) {
-      const KrylovArgs K{ M.kry_w, bottom_stats_dev(0), P.mg_bottom_solver_eps, M.kry_maxit };
-      hipLaunchKernelGGL(kk_c2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry_method, M.kry_singular, M.per[0], M.per[1]);
-    } else c2_gsrb(M, L, c2_bottom(L));
+    if (M.kry.w) c2_krylov_visit(M, L); else c2_gsrb(M, L, c2_bottom(L));
     return;
   }
   const C2 &C = M.lev[l + 1];
@@ -397,19 +427,23 @@ int cc2_solve(CcRequest &rq) {
     n0 /= 2; n1 /= 2; h0 *= 2.0; h1 *= 2.0;
   }
   // Krylov bottom solver: on the last level of a hierarchy of more than one level (a one-level hierarchy -- an odd extent on the finest level -- keeps its sweeps);
-  // the statistics are those of this solve
+  // the statistics are those of this solve.  One workgroup below VDN_KRYLOV_GRID_MIN_POINTS_2D cells, the whole GPU from there on (krylov_grid.h), with the
+  // iteration budget of this kind of bottom system (bottom_budget_begin, which reads the previous solve's statistics: before they are reset)
   const int method = mg_krylov_method(ctx().prm.mg_bottom_solver);
-  if (method) bottom_stats_reset(0);
-  bottom_form_set(0, (method && M.lev.size() > 1) ? 1 : 0);      // dm = 2: always one workgroup (a 75^2 bottom is 5625 cells)
   if (method && M.lev.size() > 1) {
     const C2 &B = M.lev.back();
-    M.kry_method = method;
-    M.kry_w = (double *)arena_alloc(sizeof(double) * c2_size(B.n0, B.n1) * (method == VDN_KRYLOV_CG ? 4 : 7));
     bool dir = false;
     for (int d = 0; d < 2; d++) for (int sd = 0; sd < 2; sd++) if (bc[d][sd] == VDN_BC_DIR) dir = true;
     M.kry_singular = (!alpha && !dir) ? 1 : 0;
-    M.kry_maxit = 12 * std::max(B.n0, B.n1);
+    GraphKey k; k.put(2); k.put(method); k.put(B.n0); k.put(B.n1); k.put(alpha ? 1 : 0); k.put(M.kry_singular); k.put(M.per); k.put(ctx().prm.mg_bottom_solver_eps);
+    mg_krylov_setup(M.kry, method, c2_size(B.n0, B.n1), std::max(B.n0, B.n1), (long)B.n0 * B.n1, k, VDN_KRYLOV_GRID_MIN_POINTS_2D);
   }
+  if (method) {
+    const int budget = bottom_budget_begin(0, M.kry.kind, M.kry.maxit);
+    if (M.kry.part) M.kry.budget = budget;
+    bottom_stats_reset(0);
+  }
+  bottom_form_set(0, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
   C2Gx X; X.L = M.lev[0]; X.has_alpha = alpha ? 1 : 0;
   for (int d = 0; d < 2; d++) { X.B.lo[d] = pd.lo[d]; for (int s = 0; s < 2; s++) X.B.e[d][s] = bc[d][s]; }
   const C2 &L0 = M.lev[0];
@@ -735,6 +769,17 @@ DEVI void wg_n2_fill_nodes(const N2 &L, double *a, int per0, int per1) {      //
   }
   __syncthreads();
 }
+// ... one entry of the padded array at a time, for the grid-wide form (krylov_grid.h).  Without a periodic direction there is nothing to do: every written entry
+// would be a zero of the ring, which the visit's memsets (the work arrays) and the V-cycle's (phi) have left zero and no kernel of the solve writes.
+DEVI int n2_fill_count(const N2 &L, int per0, int per1) { return (per0 || per1) ? (L.n0 + 3) * (L.n1 + 3) : 0; }
+DEVI void n2_fill_point(const N2 &L, double *a, int per0, int per1, int t) {
+  const int nx = L.n0 + 3;
+  const int i = t % nx - 1, j = t / nx - 1;
+  int si = i, sj = j; bool g = false, zero = false;
+  if (per0) { if (i < 0) { si = i + L.n0; g = true; } else if (i >= L.n0) { si = i - L.n0; g = true; } } else if (i < 0 || i > L.n0) { g = true; zero = true; }
+  if (per1) { if (j < 0) { sj = j + L.n1; g = true; } else if (j >= L.n1) { sj = j - L.n1; g = true; } } else if (j < 0 || j > L.n1) { g = true; zero = true; }
+  if (g) a[n2i(L, i, j)] = zero ? 0.0 : a[n2i(L, si, sj)];      // (the source is a node no thread writes, as in wg_n2_fill_nodes)
+}
 struct N2KrylovOp {
   const N2 &L; int per0, per1;
   DEVI int count() const { return (L.n0 + 1) * (L.n1 + 1); }
@@ -745,6 +790,8 @@ struct N2KrylovOp {
   }
   DEVI void apply(const double *v, long, int i, int j, int, double &Av, double &diag) const { n2_apply(L, v, i, j, Av, diag); }
   DEVI void fill(double *v) const { wg_n2_fill_nodes(L, v, per0, per1); }
+  DEVI int fill_count() const { return n2_fill_count(L, per0, per1); }
+  DEVI void fill_point(double *v, int t) const { n2_fill_point(L, v, per0, per1, t); }
   DEVI long size() const { return (long)(L.n0 + 3) * (L.n1 + 3); }
   DEVI const double *rhs() const { return L.b; }
   DEVI double *x() const { return L.phi; }
@@ -754,6 +801,12 @@ __global__ void __launch_bounds__(1024) kk_n2_bottom_krylov(N2 L, KrylovArgs K, 
   const N2KrylovOp op{ L, per0, per1 };
   if (method == VDN_KRYLOV_CG) wg_krylov<VDN_KRYLOV_CG>(op, K); else wg_krylov<VDN_KRYLOV_BICGSTAB>(op, K);
 }
+// the level as the grid-wide form takes it (krylov_grid.h): by value -- L.phi is the array the level's phi names at the visit -- for bottom levels of
+// VDN_KRYLOV_GRID_MIN_POINTS_2D nodes and more
+struct N2KrylovLevel {
+  N2 L; int per0, per1;
+  DEVI N2KrylovOp op() const { return N2KrylovOp{ L, per0, per1 }; }
+};
 struct N2Gx { N2 L; int lo[2]; };                      // lo: the domain's first cell / node
 // gathered level (see cc2_solve): sigma on the box's cells, grown by the ghost cell at the domain's sides (the ring the smoother reads there)
 struct N2LoadSig { Range3 r; int g[3]; FV coeffs;
@@ -786,8 +839,25 @@ struct nd_divu2_K { FV u, rh; double gx, gy;
     P2(rh, i, j, 0) = G2(rh, i, j, 0) + (dux * gx + duy * gy);
   } };
 struct ND2MG { std::vector<N2> lev; int per[2]; double *d_nrm;
-  double *kry_w = nullptr; int kry_method = 0, kry_maxit = 0; };      // Krylov bottom solver: its work arrays (nullptr = the bottom sweeps)
+  MgKrylov kry; };      // Krylov bottom solver (kry.w == nullptr: the bottom sweeps; kry.part: the grid-wide form)
 static long n2_nsize(int n0, int n1) { return (long)(n0 + 3) * (n1 + 3); }
+// one visit of the bottom level L by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU.  The result is left in the array L.phi names now:
+// the sweeps above this level may have swapped phi and tmp, the Krylov solve swaps nothing
+static void n2_krylov_visit(const ND2MG &M, const N2 &L) {
+  const double eps = ctx().prm.hg_bottom_solver_eps;
+  if (!M.kry.part) {
+    const KrylovArgs K{ M.kry.w, bottom_stats_dev(1), eps, M.kry.maxit };
+    hipLaunchKernelGGL(kk_n2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry.method, M.per[0], M.per[1]);
+    return;
+  }
+  const N2KrylovLevel lv{ L, M.per[0], M.per[1] };
+  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(1), bottom_exhausted_dev(1), eps, M.kry.maxit };
+  const long np = (long)(L.n0 + 1) * (L.n1 + 1);
+  const long nfill = (M.per[0] || M.per[1]) ? n2_nsize(L.n0, L.n1) : 0;      // n2_fill_count
+  const bool singular = !(L.dirlo[0] || L.dirlo[1] || L.dirhi[0] || L.dirhi[1]);      // N2KrylovOp::singular
+  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, n2_nsize(L.n0, L.n1), np, nfill, singular, M.kry.budget, ctx().stream);
+  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, n2_nsize(L.n0, L.n1), np, nfill, singular, M.kry.budget, ctx().stream);
+}
 static void n2_fill(const ND2MG &M, const N2 &L, double *a) { hipLaunchKernelGGL(kk_n2_fill_nodes, g2(L.n0 + 3, L.n1 + 3), B2, 0, ctx().stream, L, a, M.per[0], M.per[1]); }
 static void n2_jacobi(const ND2MG &M, N2 &L, int ns) {
   for (int s = 0; s < ns; s++) {
@@ -808,10 +878,7 @@ static void n2_vcycle(ND2MG &M, int l) {
   N2 &L = M.lev[l];
   HIPCHK(hipMemsetAsync(L.phi, 0, sizeof(double) * n2_nsize(L.n0, L.n1), ctx().stream));
   if (l == (int)M.lev.size() - 1) {
-    if (M.kry_w) {      // (L.phi as it stands now: the sweeps above this level may have swapped phi and tmp, the Krylov solve swaps nothing)
-      const KrylovArgs K{ M.kry_w, bottom_stats_dev(1), P.hg_bottom_solver_eps, M.kry_maxit };
-      hipLaunchKernelGGL(kk_n2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry_method, M.per[0], M.per[1]);
-    } else n2_jacobi(M, L, n2_bottom(L));
+    if (M.kry.w) n2_krylov_visit(M, L); else n2_jacobi(M, L, n2_bottom(L));
     return;
   }
   N2 &C = M.lev[l + 1];
@@ -849,14 +916,17 @@ int nd2_solve(NdRequest &rq) {
   }
   // Krylov bottom solver: as in cc2_solve (more than one level; the statistics are those of this solve)
   const int method = mg_krylov_method(ctx().prm.hg_bottom_solver);
-  if (method) bottom_stats_reset(1);
-  bottom_form_set(1, (method && M.lev.size() > 1) ? 1 : 0);
   if (method && M.lev.size() > 1) {
     const N2 &B = M.lev.back();
-    M.kry_method = method;
-    M.kry_w = (double *)arena_alloc(sizeof(double) * n2_nsize(B.n0, B.n1) * (method == VDN_KRYLOV_CG ? 4 : 7));
-    M.kry_maxit = 12 * (std::max(B.n0, B.n1) + 1);
+    GraphKey k; k.put(3); k.put(method); k.put(B.n0); k.put(B.n1); k.put(B.dirlo); k.put(B.dirhi); k.put(M.per); k.put(ctx().prm.hg_bottom_solver_eps);
+    mg_krylov_setup(M.kry, method, n2_nsize(B.n0, B.n1), std::max(B.n0, B.n1) + 1, (long)(B.n0 + 1) * (B.n1 + 1), k, VDN_KRYLOV_GRID_MIN_POINTS_2D);
   }
+  if (method) {
+    const int budget = bottom_budget_begin(1, M.kry.kind, M.kry.maxit);
+    if (M.kry.part) M.kry.budget = budget;
+    bottom_stats_reset(1);
+  }
+  bottom_form_set(1, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
   N2 &L0 = M.lev[0];
   N2Gx X; X.L = L0; X.lo[0] = pd.lo[0]; X.lo[1] = pd.lo[1];
   if (u) {

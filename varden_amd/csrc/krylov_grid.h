@@ -4,7 +4,7 @@
 // preconditioner, x = 0 to start from, the mean of b taken off before and the mean of x after the iteration on singular systems, max |r| <= eps max |b| to
 // stop, b = 0 returns x = 0, the cap of 12 N iterations, a breakdown stops BEFORE the update that would use the bad value and is counted -- as a short, fixed
 // sequence of plain launches on the solve's stream.  No cooperative launch, no grid-wide barrier, no spin-wait, no atomics; every loop in a kernel is bounded.
-// `LV` is a level handed to a kernel by value (CcKrylovLevel in mg_cc.hip, NdKrylovLevel in mg_nd.hip); LV::op() is the adapter wg_krylov takes, with two more
+// `LV` is a level handed to a kernel by value (CcKrylovLevel in mg_cc.hip, NdKrylovLevel in mg_nd.hip, C2KrylovLevel and N2KrylovLevel in dim2.hip); LV::op() is the adapter wg_krylov takes, with two more
 // members: fill_count() and fill_point(v, t), the periodic fill of the level one point at a time (what wg_cc_periodic / wg_nd_fill loop over).
 //
 // Launch shape (krylov_grid_shape): a function of the number of points alone -- 256, 512 or 1024 threads per workgroup, at most KG_MAXWG workgroups, grid-stride
@@ -41,6 +41,25 @@
 #ifndef VDN_KRYLOV_GRID_MIN_POINTS
 #define VDN_KRYLOV_GRID_MIN_POINTS 4913
 #endif
+// The same for the two dm = 2 multigrids (dim2.hip), whose crossover lies higher: their V-cycles are plain launches, not hipGraphs, so an iteration of this form
+// costs its three to seven launches on the host as well (the launches a visit's budget leaves over after convergence included), and the 5- and 9-point operators
+// leave a workgroup less to do per point than the 7- and 27-point ones.  tools/bottom_solver_probe.py 102,142,154,162,170,182,202,282 5 2 cg <library>, the
+// library built with this constant at 2^30 and at 0 (MI355X, CG / CG, five steps after two warm-up steps; MAC + HG phase per step in ms, each phase 6 / 10 bottom
+// visits; every figure repeated within 0.1 ms (one workgroup) and 1.3 ms (grid-wide) by a second run; profiles/bottom_solver_probe_2d_wide.txt):
+//   bottom (cells, nodes)   CG iterations per visit   one workgroup     grid-wide
+//   51^2, 52^2               88, 38                     5.86 +  5.24     11.57 + 10.96
+//   71^2, 72^2              115, 49                    11.49 +  9.91     15.80 + 14.87
+//   77^2, 78^2              123, 52                    13.95 + 12.16     16.55 + 18.62
+//   81^2, 82^2              128, 55                    15.41 + 13.61     17.06 + 18.33
+//   85^2, 86^2              134, 58                    17.42 + 15.26     17.74 + 18.39
+//   91^2, 92^2              146, 62                    21.18 + 18.18     20.10 + 19.00
+//   101^2, 102^2            164, 68                    28.12 + 23.80     22.78 + 21.23
+//   141^2, 142^2            218, 93                    67.40 + 57.56     38.52 + 34.05
+// 101^2 is the smallest measured size from which neither operator is slower (at 91^2 the nodal one still is).  Not below 23 x 12 nodes: the largest bottom
+// level of tests/test_bottom_solver_2d_gpu.py, which stays one workgroup.
+#ifndef VDN_KRYLOV_GRID_MIN_POINTS_2D
+#define VDN_KRYLOV_GRID_MIN_POINTS_2D 10201
+#endif
 
 #define KG_MAXWG 256
 enum { KG_SB = 0, KG_CNT, KG_RHO, KG_BN, KG_D0, KG_D1, KG_E0, KG_E1, KG_SN, KG_X, KG_NPART };
@@ -57,17 +76,18 @@ struct KrylovGridArgs {
   DEVI double *st(int b) const { return part + KG_NPART * KG_MAXWG + b * KG_NST; }
 };
 
-// What a 3-D hierarchy (CCMG, NDMG) keeps of its Krylov bottom solver.  w: the work arrays, of the bottom level's padded size (nullptr = the bottom sweeps);
-// part: the grid-wide form's partial sums and state blocks, on a bottom level of VDN_KRYLOV_GRID_MIN_POINTS points (cells, or nodes) or more; budget: the
+// What a hierarchy (CCMG, NDMG; dm = 2: CC2MG, ND2MG) keeps of its Krylov bottom solver.  w: the work arrays, of the bottom level's padded size (nullptr = the bottom sweeps);
+// part: the grid-wide form's partial sums and state blocks, on a bottom level of VDN_KRYLOV_GRID_MIN_POINTS (dm = 2: ..._2D) points (cells, or nodes) or more; budget: the
 // iterations a visit of that form launches; kind: its key in bottom_budget_begin.
 struct MgKrylov { double *w = nullptr; int method = 0, maxit = 0; double *part = nullptr; int budget = 0; unsigned long long kind = 0; };
 // The set-up both builds share.  The arrays come from the arena here, so their addresses repeat with the hierarchy's.  sz: the bottom level's padded size;
-// N: its largest extent in points; np: its points; kind: what tells one solver's bottom systems apart (solver, method, extents, boundary, tolerance)
-inline void mg_krylov_setup(MgKrylov &K, int method, long sz, int N, long np, const GraphKey &kind) {
+// N: its largest extent in points; np: its points; kind: what tells one solver's bottom systems apart (solver, method, extents, boundary, tolerance);
+// min_points: the crossover of the caller's multigrids
+inline void mg_krylov_setup(MgKrylov &K, int method, long sz, int N, long np, const GraphKey &kind, long min_points = VDN_KRYLOV_GRID_MIN_POINTS) {
   K.method = method;
   K.w = (double *)arena_alloc(sizeof(double) * sz * (method == VDN_KRYLOV_CG ? 4 : 7));
   K.maxit = 12 * N;
-  if (np >= VDN_KRYLOV_GRID_MIN_POINTS) {
+  if (np >= min_points) {
     K.part = (double *)arena_alloc(sizeof(double) * KG_DOUBLES);
     K.kind = kind.h | 1ull;
     K.budget = K.maxit;
