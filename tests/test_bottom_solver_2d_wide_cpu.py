@@ -26,4 +26,7 @@ def test_the_crossovers_keep_the_small_bottoms_in_one_workgroup_and_the_wide_one
     assert 23 * 12 <= x3 and 23 * 12 <= x2 <= 101 * 101 <= 45 * 227 <= 21 * 487
     src = open(os.path.join(ROOT, "varden_amd", "csrc", "dim2.hip")).read()
     assert src.count("VDN_KRYLOV_GRID_MIN_POINTS_2D);") == 2, "both dm = 2 multigrids take the dm = 2 constant"
-    assert "krylov_grid_visit<VDN_KRYLOV_CG>" in src and "always one workgroup" not in src
+    # both dm = 2 multigrids visit their bottom through the one host visit of krylov_grid.h, which takes the grid-wide form above the crossover
+    assert src.count("mg_krylov_visit(M.kry,") == 2 and "always one workgroup" not in src
+    visit = txt[txt.index("void mg_krylov_visit("):]
+    assert "if (!kry.part)" in visit and "krylov_grid_visit<VDN_KRYLOV_CG>" in visit and "always one workgroup" not in txt

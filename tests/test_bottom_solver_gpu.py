@@ -2,9 +2,9 @@
 which each path can go wrong.  The solves are held against sparse DIRECT solutions of independently assembled systems (tests/assembled.py), exactly as
 tests/test_operators_assembled_gpu.py holds the default bottom sweeps: the same tolerances, Case and smooth().
 
-  (22, 22, 22)  one coarsening, then 11^3 cells / 12^3 nodes: more unknowns than the workgroup has threads, odd periodic extents; kk_*_bottom_krylov
+  (22, 22, 22)  one coarsening, then 11^3 cells / 12^3 nodes: more unknowns than the workgroup has threads, odd periodic extents; kk_bottom_krylov<LV>
   (22, 26, 30)  bottom 11 x 13 x 15: unequal extents
-  (24, 24, 24)  6^3 and 3^3 cells (7^3 and 4^3 nodes) sit inside the tail-cycle kernel: kk_*_tailcycle_krylov
+  (24, 24, 24)  6^3 and 3^3 cells (7^3 and 4^3 nodes) sit inside the tail-cycle kernel: kk_*_tailcycle<true>
   (40, 20, 12)  10 x 5 x 3: a small bottom outside the tail cycle
 """
 import functools

@@ -184,7 +184,7 @@ void k2_estdt_max(const vdn_multifab *u, const vdn_multifab *s, const vdn_multif
 // =====================================================================================================================
 struct C2 { int n0, n1, P; double hi2[2]; double *phi, *rh, *res, *bx, *by, *alpha; };
 DEVI long c2i(const C2 &L, int i, int j) { return (long)(i + 1) + (long)L.P * (j + 1); }
-static long c2_size(int n0, int n1) { return (long)(n0 + 2) * (n1 + 2); }
+KRY_HD long c2_size(int n0, int n1) { return (long)(n0 + 2) * (n1 + 2); }
 DEVI void c2_apply(const C2 &L, int i, int j, double &Ap, double &diag) {
   const long c = c2i(L, i, j);
   const double p0 = L.phi[c];
@@ -230,35 +230,34 @@ __global__ void kk_c2_coarsen(C2 F, C2 C) {
     C.alpha[c2i(C, i, j)] = (F.alpha[f] + F.alpha[f + 1] + F.alpha[f + F.P] + F.alpha[f + F.P + 1]) * 0.25;
   }
 }
-__global__ void kk_c2_periodic(C2 L, int per0, int per1) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
-  if (i > L.n0 || j > L.n1) return;
+// entry (i, j) of the level grown by one: a ghost entry along a periodic direction takes its image (the source is a cell of the level, never a ghost: no thread
+// reads what another writes)
+DEVI void c2_periodic_entry(const C2 &L, int per0, int per1, int i, int j) {
   int si = i, sj = j; bool g = false, ok = true;
   if (i < 0) { g = true; if (per0) si = i + L.n0; else ok = false; } else if (i >= L.n0) { g = true; if (per0) si = i - L.n0; else ok = false; }
   if (j < 0) { g = true; if (per1) sj = j + L.n1; else ok = false; } else if (j >= L.n1) { g = true; if (per1) sj = j - L.n1; else ok = false; }
   if (g && ok) L.phi[c2i(L, i, j)] = L.phi[c2i(L, si, sj)];
 }
-// ---- Krylov bottom solver (vdn_params.mg_bottom_solver = 1, 2, 3; krylov_wg.h) -- the 2-D counterpart of mg_cc.hip's CcKrylovOp ----
+__global__ void kk_c2_periodic(C2 L, int per0, int per1) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
+  if (i > L.n0 || j > L.n1) return;
+  c2_periodic_entry(L, per0, per1, i, j);
+}
+// ---- Krylov bottom solver (vdn_params.mg_bottom_solver = 1, 2, 3; krylov_wg.h) -- the 2-D counterpart of mg_cc.hip's CcKrylov ----
 // The V-cycles stop where an extent turns odd (200 -> 100 -> 50 -> 25) and there is no one-workgroup sweep kernel in this file: the 25^2 bottom takes
 // max(mg_nub, N^2) = 625 red-black sweeps of two to four launches each.  CG or BiCGStab by ONE workgroup in ONE launch takes their place.  c2_apply and the
 // level's arrays are used as they are; the Neumann / Dirichlet closures sit in bx / by and rely on ghost entries that read as zero (wg_krylov zeroes its
 // work arrays of the padded size c2_size; the periodic fill writes ghosts only along a periodic direction).  A bottom of VDN_KRYLOV_GRID_MIN_POINTS_2D cells
-// or more (n_cell = 1000: 125^2) is too much for one workgroup: there the same iteration runs over the whole GPU (krylov_grid.h, C2KrylovLevel below).
+// or more (n_cell = 1000: 125^2) is too much for one workgroup: there the same iteration runs over the whole GPU (krylov_grid.h).
 DEVI void wg_c2_periodic(const C2 &L, int per0, int per1) {      // kk_c2_periodic by one workgroup; nothing without a periodic direction, else ends in a barrier
   if (!per0 && !per1) return;
   const int nx = L.n0 + 2, np = nx * (L.n1 + 2);
-  for (int t = threadIdx.x; t < np; t += blockDim.x) {
-    const int i = t % nx - 1, j = t / nx - 1;
-    int si = i, sj = j; bool g = false, ok = true;
-    if (i < 0) { g = true; if (per0) si = i + L.n0; else ok = false; } else if (i >= L.n0) { g = true; if (per0) si = i - L.n0; else ok = false; }
-    if (j < 0) { g = true; if (per1) sj = j + L.n1; else ok = false; } else if (j >= L.n1) { g = true; if (per1) sj = j - L.n1; else ok = false; }
-    if (g && ok) L.phi[c2i(L, i, j)] = L.phi[c2i(L, si, sj)];      // (the source is a cell of the level, never a ghost: no thread reads what another writes)
-  }
+  for (int t = threadIdx.x; t < np; t += blockDim.x) c2_periodic_entry(L, per0, per1, t % nx - 1, t / nx - 1);
   __syncthreads();
 }
 // ... one ghost entry at a time, for the grid-wide form (krylov_grid.h): the 2 n1 entries beside the x faces when x is periodic, then the 2 n0 beside the y faces
 // when y is.  The corners wg_c2_periodic also writes are left out: the 5-point operator never reads them.  The source is a cell of the level, never a ghost.
-DEVI int c2_periodic_count(int n0, int n1, int per0, int per1) { return (per0 ? 2 * n1 : 0) + (per1 ? 2 * n0 : 0); }
+KRY_HD int c2_periodic_count(int n0, int n1, int per0, int per1) { return (per0 ? 2 * n1 : 0) + (per1 ? 2 * n0 : 0); }
 DEVI void c2_periodic_point(const C2 &L, int per0, int t) {
   const int nx = per0 ? 2 * L.n1 : 0;
   int i, j, si, sj;
@@ -266,27 +265,19 @@ DEVI void c2_periodic_point(const C2 &L, int per0, int t) {
   else { const int u = t - nx; i = si = u >> 1; j = (u & 1) ? L.n1 : -1; sj = (u & 1) ? 0 : L.n1 - 1; }
   L.phi[c2i(L, i, j)] = L.phi[c2i(L, si, sj)];
 }
-struct C2KrylovOp {
-  const C2 &L; int per0, per1, sing;
-  DEVI int count() const { return L.n0 * L.n1; }
+// the level as wg_krylov, the grid-wide kernels and the host (mg_krylov_visit) take it (krylov_wg.h): by value
+struct C2Krylov {
+  C2 L; int per0, per1, sing;
+  KRY_HD int count() const { return L.n0 * L.n1; }
   DEVI bool point(int t, long &c, int &i, int &j, int &k) const { i = t % L.n0; j = t / L.n0; k = 0; c = c2i(L, i, j); return true; }
   DEVI void apply(const double *v, long, int i, int j, int, double &Av, double &diag) const { C2 Lv = L; Lv.phi = const_cast<double *>(v); c2_apply(Lv, i, j, Av, diag); }
   DEVI void fill(double *v) const { C2 Lv = L; Lv.phi = v; wg_c2_periodic(Lv, per0, per1); }
-  DEVI int fill_count() const { return c2_periodic_count(L.n0, L.n1, per0, per1); }
+  KRY_HD int fill_count() const { return c2_periodic_count(L.n0, L.n1, per0, per1); }
   DEVI void fill_point(double *v, int t) const { C2 Lv = L; Lv.phi = v; c2_periodic_point(Lv, per0, t); }
-  DEVI long size() const { return (long)(L.n0 + 2) * (L.n1 + 2); }
+  KRY_HD long size() const { return c2_size(L.n0, L.n1); }
   DEVI const double *rhs() const { return L.rh; }
   DEVI double *x() const { return L.phi; }
-  DEVI bool singular() const { return sing != 0; }
-};
-__global__ void __launch_bounds__(1024) kk_c2_bottom_krylov(C2 L, KrylovArgs K, int method, int singular, int per0, int per1) {      // method: uniform over the launch
-  const C2KrylovOp op{ L, per0, per1, singular };
-  if (method == VDN_KRYLOV_CG) wg_krylov<VDN_KRYLOV_CG>(op, K); else wg_krylov<VDN_KRYLOV_BICGSTAB>(op, K);
-}
-// the level as the grid-wide form takes it (krylov_grid.h): by value, for bottom levels of VDN_KRYLOV_GRID_MIN_POINTS_2D cells and more
-struct C2KrylovLevel {
-  C2 L; int per0, per1, sing;
-  DEVI C2KrylovOp op() const { return C2KrylovOp{ L, per0, per1, sing }; }
+  KRY_HD bool singular() const { return sing != 0; }
 };
 struct C2Bc { int e[2][2]; int lo[2]; };               // elliptic boundary codes of the DOMAIN faces; lo: the domain's first cell
 struct C2Gx { C2 L; C2Bc B; int has_alpha; };           // what every box's load / store launch shares (kk_batched's `extra`)
@@ -358,21 +349,6 @@ static void gather_level(double *base, long ndoubles) {
 static dim3 g2(int nx, int ny) { return dim3((nx + 63) / 64, (ny + 3) / 4, 1); }
 struct CC2MG { std::vector<C2> lev; int per[2]; double *d_nrm;
   MgKrylov kry; int kry_singular = 0; };      // Krylov bottom solver (kry.w == nullptr: the bottom sweeps; kry.part: the grid-wide form)
-// one visit of the bottom level L by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU
-static void c2_krylov_visit(const CC2MG &M, const C2 &L) {
-  const double eps = ctx().prm.mg_bottom_solver_eps;
-  if (!M.kry.part) {
-    const KrylovArgs K{ M.kry.w, bottom_stats_dev(0), eps, M.kry.maxit };
-    hipLaunchKernelGGL(kk_c2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry.method, M.kry_singular, M.per[0], M.per[1]);
-    return;
-  }
-  const C2KrylovLevel lv{ L, M.per[0], M.per[1], M.kry_singular };
-  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(0), bottom_exhausted_dev(0), eps, M.kry.maxit };
-  const long np = (long)L.n0 * L.n1;
-  const long nfill = (M.per[0] ? 2 * L.n1 : 0) + (M.per[1] ? 2 * L.n0 : 0);      // c2_periodic_count
-  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, c2_size(L.n0, L.n1), np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
-  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, c2_size(L.n0, L.n1), np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
-}
 static void c2_gsrb(const CC2MG &M, const C2 &L, int ns) {
   hipStream_t st = ctx().stream;
   for (int s = 0; s < ns; s++) for (int col = 0; col < 2; col++) {
@@ -392,7 +368,7 @@ static void c2_vcycle(const CC2MG &M, int l) {
   const C2 &L = M.lev[l];
   HIPCHK(hipMemsetAsync(L.phi, 0, sizeof(double) * c2_size(L.n0, L.n1), ctx().stream));
   if (l == (int)M.lev.size() - 1) {
-    if (M.kry.w) c2_krylov_visit(M, L); else c2_gsrb(M, L, c2_bottom(L));
+    if (M.kry.w) mg_krylov_visit(M.kry, 0, P.mg_bottom_solver_eps, C2Krylov{ L, M.per[0], M.per[1], M.kry_singular }); else c2_gsrb(M, L, c2_bottom(L));
     return;
   }
   const C2 &C = M.lev[l + 1];
@@ -438,12 +414,7 @@ int cc2_solve(CcRequest &rq) {
     GraphKey k; k.put(2); k.put(method); k.put(B.n0); k.put(B.n1); k.put(alpha ? 1 : 0); k.put(M.kry_singular); k.put(M.per); k.put(ctx().prm.mg_bottom_solver_eps);
     mg_krylov_setup(M.kry, method, c2_size(B.n0, B.n1), std::max(B.n0, B.n1), (long)B.n0 * B.n1, k, VDN_KRYLOV_GRID_MIN_POINTS_2D);
   }
-  if (method) {
-    const int budget = bottom_budget_begin(0, M.kry.kind, M.kry.maxit);
-    if (M.kry.part) M.kry.budget = budget;
-    bottom_stats_reset(0);
-  }
-  bottom_form_set(0, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
+  mg_krylov_begin(M.kry, 0, method != 0);
   C2Gx X; X.L = M.lev[0]; X.has_alpha = alpha ? 1 : 0;
   for (int d = 0; d < 2; d++) { X.B.lo[d] = pd.lo[d]; for (int s = 0; s < 2; s++) X.B.e[d][s] = bc[d][s]; }
   const C2 &L0 = M.lev[0];
@@ -663,6 +634,7 @@ void do2_diff_scalar_solve(vdn_layout *mla, vdn_multifab *snew, const vdn_multif
 // nodal multigrid, 9-point Q1:  K phi = b,  b = -rh
 // =====================================================================================================================
 struct N2 { int n0, n1, PN, PS; double f[2]; double *phi, *tmp, *b, *res, *sig; int dirlo[2], dirhi[2]; };
+KRY_HD long n2_nsize(int n0, int n1) { return (long)(n0 + 3) * (n1 + 3); }
 DEVI long n2i(const N2 &L, int i, int j) { return (long)(i + 1) + (long)L.PN * (j + 1); }
 DEVI long s2i(const N2 &L, int i, int j) { return (long)(i + 1) + (long)L.PS * (j + 1); }
 DEVI bool n2_dir(const N2 &L, int i, int j) {
@@ -694,13 +666,18 @@ DEVI void n2_apply(const N2 &L, const double *__restrict__ phi, int i, int j, do
     }
   Kp = acc; diag = w[0] * ssum;
 }
-__global__ void kk_n2_fill_nodes(N2 L, double *a, int per0, int per1) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
-  if (i > L.n0 + 1 || j > L.n1 + 1) return;
+// entry (i, j) of the node array grown by one: the image along a periodic direction, zero on the ring beyond a physical face (the source is a node no thread
+// writes: below n along a periodic direction, on the level along the other)
+DEVI void n2_fill_entry(const N2 &L, double *a, int per0, int per1, int i, int j) {
   int si = i, sj = j; bool g = false, zero = false;
   if (per0) { if (i < 0) { si = i + L.n0; g = true; } else if (i >= L.n0) { si = i - L.n0; g = true; } } else if (i < 0 || i > L.n0) { g = true; zero = true; }
   if (per1) { if (j < 0) { sj = j + L.n1; g = true; } else if (j >= L.n1) { sj = j - L.n1; g = true; } } else if (j < 0 || j > L.n1) { g = true; zero = true; }
   if (g) a[n2i(L, i, j)] = zero ? 0.0 : a[n2i(L, si, sj)];
+}
+__global__ void kk_n2_fill_nodes(N2 L, double *a, int per0, int per1) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
+  if (i > L.n0 + 1 || j > L.n1 + 1) return;
+  n2_fill_entry(L, a, per0, per1, i, j);
 }
 __global__ void kk_n2_fill_cells(N2 L, int per0, int per1) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
@@ -753,36 +730,24 @@ __global__ void kk_n2_coarsen_sigma(N2 F, N2 C) {
   for (int b = 0; b < 2; b++) for (int a = 0; a < 2; a++) s = s + F.sig[s2i(F, 2 * i + a, 2 * j + b)];
   C.sig[s2i(C, i, j)] = s * 0.25;
 }
-// ---- Krylov bottom solver (vdn_params.hg_bottom_solver = 1, 2, 3; krylov_wg.h) -- the 2-D counterpart of mg_nd.hip's NdKrylovOp ----
+// ---- Krylov bottom solver (vdn_params.hg_bottom_solver = 1, 2, 3; krylov_wg.h) -- the 2-D counterpart of mg_nd.hip's NdKrylov ----
 // The 26^2-node bottom of a 200^2 problem takes max(hg_nub, 2 N^2) = 1250 Jacobi sweeps of two launches each.  K as n2_apply returns it is symmetric positive
 // semi-definite with a positive diagonal.  Dirichlet (outflow) nodes are not unknowns; along a periodic direction node n is the image of node 0, written by the
 // fill only and counted once.  The sigma = 0 ring beyond a physical face is the wall closure and the node ring there reads as zero (the fill writes it).  The
 // solve starts from phi = 0 and leaves its result in the array L.phi names at the launch (no ping-pong: the host's phi / tmp swap is that of zero sweeps).
-DEVI void wg_n2_fill_nodes(const N2 &L, double *a, int per0, int per1) {      // kk_n2_fill_nodes by one workgroup; ends in a barrier
-  const int nx = L.n0 + 3, np = nx * (L.n1 + 3);
-  for (int t = threadIdx.x; t < np; t += blockDim.x) {
-    const int i = t % nx - 1, j = t / nx - 1;
-    int si = i, sj = j; bool g = false, zero = false;
-    if (per0) { if (i < 0) { si = i + L.n0; g = true; } else if (i >= L.n0) { si = i - L.n0; g = true; } } else if (i < 0 || i > L.n0) { g = true; zero = true; }
-    if (per1) { if (j < 0) { sj = j + L.n1; g = true; } else if (j >= L.n1) { sj = j - L.n1; g = true; } } else if (j < 0 || j > L.n1) { g = true; zero = true; }
-    if (g) a[n2i(L, i, j)] = zero ? 0.0 : a[n2i(L, si, sj)];      // (the source is a node no thread writes: below n along a periodic direction, on the level along the other)
-  }
+// ... one entry of the padded array at a time (kg_fill of the grid-wide form, krylov_grid.h; wg_n2_fill_nodes).  Without a periodic direction the grid-wide form has nothing
+// to do: every written entry would be a zero of the ring, which the visit's memsets (the work arrays) and the V-cycle's (phi) have left zero and no kernel of the solve writes.
+KRY_HD int n2_fill_count(const N2 &L, int per0, int per1) { return (per0 || per1) ? (L.n0 + 3) * (L.n1 + 3) : 0; }
+DEVI void n2_fill_point(const N2 &L, double *a, int per0, int per1, int t) { const int nx = L.n0 + 3; n2_fill_entry(L, a, per0, per1, t % nx - 1, t / nx - 1); }
+DEVI void wg_n2_fill_nodes(const N2 &L, double *a, int per0, int per1) {      // kk_n2_fill_nodes by one workgroup (the zero ring included, whatever is periodic); ends in a barrier
+  const int np = (L.n0 + 3) * (L.n1 + 3);
+  for (int t = threadIdx.x; t < np; t += blockDim.x) n2_fill_point(L, a, per0, per1, t);
   __syncthreads();
 }
-// ... one entry of the padded array at a time, for the grid-wide form (krylov_grid.h).  Without a periodic direction there is nothing to do: every written entry
-// would be a zero of the ring, which the visit's memsets (the work arrays) and the V-cycle's (phi) have left zero and no kernel of the solve writes.
-DEVI int n2_fill_count(const N2 &L, int per0, int per1) { return (per0 || per1) ? (L.n0 + 3) * (L.n1 + 3) : 0; }
-DEVI void n2_fill_point(const N2 &L, double *a, int per0, int per1, int t) {
-  const int nx = L.n0 + 3;
-  const int i = t % nx - 1, j = t / nx - 1;
-  int si = i, sj = j; bool g = false, zero = false;
-  if (per0) { if (i < 0) { si = i + L.n0; g = true; } else if (i >= L.n0) { si = i - L.n0; g = true; } } else if (i < 0 || i > L.n0) { g = true; zero = true; }
-  if (per1) { if (j < 0) { sj = j + L.n1; g = true; } else if (j >= L.n1) { sj = j - L.n1; g = true; } } else if (j < 0 || j > L.n1) { g = true; zero = true; }
-  if (g) a[n2i(L, i, j)] = zero ? 0.0 : a[n2i(L, si, sj)];      // (the source is a node no thread writes, as in wg_n2_fill_nodes)
-}
-struct N2KrylovOp {
-  const N2 &L; int per0, per1;
-  DEVI int count() const { return (L.n0 + 1) * (L.n1 + 1); }
+// the level as wg_krylov, the grid-wide kernels and the host (mg_krylov_visit) take it (krylov_wg.h): by value -- L.phi is the array the level's phi names at the visit
+struct N2Krylov {
+  N2 L; int per0, per1;
+  KRY_HD int count() const { return (L.n0 + 1) * (L.n1 + 1); }
   DEVI bool point(int t, long &c, int &i, int &j, int &k) const {
     const int nx = L.n0 + 1;
     i = t % nx; j = t / nx; k = 0; c = n2i(L, i, j);
@@ -790,22 +755,12 @@ struct N2KrylovOp {
   }
   DEVI void apply(const double *v, long, int i, int j, int, double &Av, double &diag) const { n2_apply(L, v, i, j, Av, diag); }
   DEVI void fill(double *v) const { wg_n2_fill_nodes(L, v, per0, per1); }
-  DEVI int fill_count() const { return n2_fill_count(L, per0, per1); }
+  KRY_HD int fill_count() const { return n2_fill_count(L, per0, per1); }
   DEVI void fill_point(double *v, int t) const { n2_fill_point(L, v, per0, per1, t); }
-  DEVI long size() const { return (long)(L.n0 + 3) * (L.n1 + 3); }
+  KRY_HD long size() const { return n2_nsize(L.n0, L.n1); }
   DEVI const double *rhs() const { return L.b; }
   DEVI double *x() const { return L.phi; }
-  DEVI bool singular() const { return !(L.dirlo[0] || L.dirlo[1] || L.dirhi[0] || L.dirhi[1]); }
-};
-__global__ void __launch_bounds__(1024) kk_n2_bottom_krylov(N2 L, KrylovArgs K, int method, int per0, int per1) {      // method: uniform over the launch
-  const N2KrylovOp op{ L, per0, per1 };
-  if (method == VDN_KRYLOV_CG) wg_krylov<VDN_KRYLOV_CG>(op, K); else wg_krylov<VDN_KRYLOV_BICGSTAB>(op, K);
-}
-// the level as the grid-wide form takes it (krylov_grid.h): by value -- L.phi is the array the level's phi names at the visit -- for bottom levels of
-// VDN_KRYLOV_GRID_MIN_POINTS_2D nodes and more
-struct N2KrylovLevel {
-  N2 L; int per0, per1;
-  DEVI N2KrylovOp op() const { return N2KrylovOp{ L, per0, per1 }; }
+  KRY_HD bool singular() const { return !(L.dirlo[0] || L.dirlo[1] || L.dirhi[0] || L.dirhi[1]); }
 };
 struct N2Gx { N2 L; int lo[2]; };                      // lo: the domain's first cell / node
 // gathered level (see cc2_solve): sigma on the box's cells, grown by the ghost cell at the domain's sides (the ring the smoother reads there)
@@ -840,24 +795,6 @@ struct nd_divu2_K { FV u, rh; double gx, gy;
   } };
 struct ND2MG { std::vector<N2> lev; int per[2]; double *d_nrm;
   MgKrylov kry; };      // Krylov bottom solver (kry.w == nullptr: the bottom sweeps; kry.part: the grid-wide form)
-static long n2_nsize(int n0, int n1) { return (long)(n0 + 3) * (n1 + 3); }
-// one visit of the bottom level L by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU.  The result is left in the array L.phi names now:
-// the sweeps above this level may have swapped phi and tmp, the Krylov solve swaps nothing
-static void n2_krylov_visit(const ND2MG &M, const N2 &L) {
-  const double eps = ctx().prm.hg_bottom_solver_eps;
-  if (!M.kry.part) {
-    const KrylovArgs K{ M.kry.w, bottom_stats_dev(1), eps, M.kry.maxit };
-    hipLaunchKernelGGL(kk_n2_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, K, M.kry.method, M.per[0], M.per[1]);
-    return;
-  }
-  const N2KrylovLevel lv{ L, M.per[0], M.per[1] };
-  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(1), bottom_exhausted_dev(1), eps, M.kry.maxit };
-  const long np = (long)(L.n0 + 1) * (L.n1 + 1);
-  const long nfill = (M.per[0] || M.per[1]) ? n2_nsize(L.n0, L.n1) : 0;      // n2_fill_count
-  const bool singular = !(L.dirlo[0] || L.dirlo[1] || L.dirhi[0] || L.dirhi[1]);      // N2KrylovOp::singular
-  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, n2_nsize(L.n0, L.n1), np, nfill, singular, M.kry.budget, ctx().stream);
-  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, n2_nsize(L.n0, L.n1), np, nfill, singular, M.kry.budget, ctx().stream);
-}
 static void n2_fill(const ND2MG &M, const N2 &L, double *a) { hipLaunchKernelGGL(kk_n2_fill_nodes, g2(L.n0 + 3, L.n1 + 3), B2, 0, ctx().stream, L, a, M.per[0], M.per[1]); }
 static void n2_jacobi(const ND2MG &M, N2 &L, int ns) {
   for (int s = 0; s < ns; s++) {
@@ -878,7 +815,8 @@ static void n2_vcycle(ND2MG &M, int l) {
   N2 &L = M.lev[l];
   HIPCHK(hipMemsetAsync(L.phi, 0, sizeof(double) * n2_nsize(L.n0, L.n1), ctx().stream));
   if (l == (int)M.lev.size() - 1) {
-    if (M.kry.w) n2_krylov_visit(M, L); else n2_jacobi(M, L, n2_bottom(L));
+    // (the result is left in the array L.phi names now: the sweeps above this level may have swapped phi and tmp, the Krylov solve swaps nothing)
+    if (M.kry.w) mg_krylov_visit(M.kry, 1, P.hg_bottom_solver_eps, N2Krylov{ L, M.per[0], M.per[1] }); else n2_jacobi(M, L, n2_bottom(L));
     return;
   }
   N2 &C = M.lev[l + 1];
@@ -921,12 +859,7 @@ int nd2_solve(NdRequest &rq) {
     GraphKey k; k.put(3); k.put(method); k.put(B.n0); k.put(B.n1); k.put(B.dirlo); k.put(B.dirhi); k.put(M.per); k.put(ctx().prm.hg_bottom_solver_eps);
     mg_krylov_setup(M.kry, method, n2_nsize(B.n0, B.n1), std::max(B.n0, B.n1) + 1, (long)(B.n0 + 1) * (B.n1 + 1), k, VDN_KRYLOV_GRID_MIN_POINTS_2D);
   }
-  if (method) {
-    const int budget = bottom_budget_begin(1, M.kry.kind, M.kry.maxit);
-    if (M.kry.part) M.kry.budget = budget;
-    bottom_stats_reset(1);
-  }
-  bottom_form_set(1, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
+  mg_krylov_begin(M.kry, 1, method != 0);
   N2 &L0 = M.lev[0];
   N2Gx X; X.L = L0; X.lo[0] = pd.lo[0]; X.lo[1] = pd.lo[1];
   if (u) {

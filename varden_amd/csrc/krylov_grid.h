@@ -4,8 +4,9 @@
 // preconditioner, x = 0 to start from, the mean of b taken off before and the mean of x after the iteration on singular systems, max |r| <= eps max |b| to
 // stop, b = 0 returns x = 0, the cap of 12 N iterations, a breakdown stops BEFORE the update that would use the bad value and is counted -- as a short, fixed
 // sequence of plain launches on the solve's stream.  No cooperative launch, no grid-wide barrier, no spin-wait, no atomics; every loop in a kernel is bounded.
-// `LV` is a level handed to a kernel by value (CcKrylovLevel in mg_cc.hip, NdKrylovLevel in mg_nd.hip, C2KrylovLevel and N2KrylovLevel in dim2.hip); LV::op() is the adapter wg_krylov takes, with two more
-// members: fill_count() and fill_point(v, t), the periodic fill of the level one point at a time (what wg_cc_periodic / wg_nd_fill loop over).
+// `LV` is the level adapter wg_krylov takes, handed to a kernel by value (CcKrylov in mg_cc.hip, NdKrylov in mg_nd.hip, C2Krylov and N2Krylov in dim2.hip); used here besides what
+// wg_krylov uses: fill_count() and fill_point(v, t), the periodic fill of the level one point at a time (what wg_cc_periodic / wg_nd_fill loop over).
+// mg_krylov_visit (at the end) is the one bottom visit of all four multigrids: one workgroup (kk_bottom_krylov) or this form, sized from the adapter itself.
 //
 // Launch shape (krylov_grid_shape): a function of the number of points alone -- 256, 512 or 1024 threads per workgroup, at most KG_MAXWG workgroups, grid-stride
 // over the points.  Never a CU count: the replicated tail gives the same bits on every rank and on every run.
@@ -93,6 +94,19 @@ inline void mg_krylov_setup(MgKrylov &K, int method, long sz, int N, long np, co
     K.budget = K.maxit;
   }
 }
+// The start of one solve of multigrid `which` (0 cell-centred, 1 nodal): the form vdn_last_bottom_form reports; then, when `selected`, the iteration budget of this kind of bottom
+// system (bottom_budget_begin reads the previous solve's statistics: before they are reset) and the statistics, which are those of one solve.
+// The callers differ in when they call and in `selected`, and so in what vdn_last_bottom_stats reports for a bottom that keeps its sweeps although a method is selected:
+//   3-D (cc_solve, nd_solve): not on a kept, already-built hierarchy running fixed cycles (a composite solve's statistics are those of all its cycles); selected = kry.w is
+//       set, so such a bottom leaves the statistics of the last Krylov solve standing;
+//   2-D (cc2_solve, nd2_solve): every solve; selected = a method is selected, one-level hierarchies that keep their sweeps included, so such a bottom reports zeros.
+inline void mg_krylov_begin(MgKrylov &K, int which, bool selected) {
+  bottom_form_set(which, K.w ? (K.part ? 2 : 1) : 0);
+  if (!selected) return;
+  const int budget = bottom_budget_begin(which, K.kind, K.maxit);
+  if (K.part) K.budget = budget;
+  bottom_stats_reset(which);
+}
 
 DEVI double kg_sum(const double *p, int n) { double a = p[0]; for (int g = 1; g < n; g++) a = a + p[g]; return a; }
 DEVI double kg_max(const double *p, int n) { double a = p[0]; for (int g = 1; g < n; g++) a = nmax(a, p[g]); return a; }
@@ -109,18 +123,17 @@ DEVI void kg_carry(double *N, const double *S) {
 // ---- start of a visit ---------------------------------------------------------------------------------------------------------------------
 template <int METHOD, class LV> __global__ void __launch_bounds__(1024) kg_init0(LV lv, KrylovGridArgs K) {
   constexpr int NW = (METHOD == VDN_KRYLOV_CG) ? 4 : 7;
-  const auto op = lv.op();
-  const int np = op.count();
-  double *x = op.x();
-  const double *b = op.rhs();
-  double *dinv = K.w + (NW - 1) * op.size();
+  const int np = lv.count();
+  double *x = lv.x();
+  const double *b = lv.rhs();
+  double *dinv = K.w + (NW - 1) * lv.size();
   double s2[2] = { 0.0, 0.0 }, m1[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    const bool cand = op.point(t, c, i, j, k);
+    const bool cand = lv.point(t, c, i, j, k);
     x[c] = 0.0;
     if (cand) {
-      double Av, diag; op.apply(b, c, i, j, k, Av, diag);
+      double Av, diag; lv.apply(b, c, i, j, k, Av, diag);
       if (diag != 0.0) { dinv[c] = 1.0 / diag; s2[0] = s2[0] + b[c]; s2[1] = s2[1] + 1.0; }
     }
   }
@@ -129,17 +142,16 @@ template <int METHOD, class LV> __global__ void __launch_bounds__(1024) kg_init0
 }
 template <int METHOD, class LV> __global__ void __launch_bounds__(1024) kg_init1(LV lv, KrylovGridArgs K) {
   constexpr int NW = (METHOD == VDN_KRYLOV_CG) ? 4 : 7;
-  const auto op = lv.op();
-  const long sz = op.size();
-  const int np = op.count();
-  const double *b = op.rhs();
+  const long sz = lv.size();
+  const int np = lv.count();
+  const double *b = lv.rhs();
   double *r = K.w, *p = K.w + sz, *q = K.w + 2 * sz, *dinv = K.w + (NW - 1) * sz;
   const double nunk = kg_sum(kg_part(K, KG_CNT), gridDim.x);
-  const double bmean = (op.singular() && nunk > 0.0) ? kg_sum(kg_part(K, KG_SB), gridDim.x) / nunk : 0.0;
+  const double bmean = (lv.singular() && nunk > 0.0) ? kg_sum(kg_part(K, KG_SB), gridDim.x) / nunk : 0.0;
   double s1[1] = { 0.0 }, m1[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     const double di = dinv[c];
     if (di != 0.0) {
       const double rv = b[c] - bmean;
@@ -171,25 +183,23 @@ static __global__ void __launch_bounds__(64) kg_start(KrylovGridArgs K, int nwg,
 // periodic images of work array `a` (of x itself: a < 0); cur >= 0: not once the solve is done
 template <class LV> __global__ void __launch_bounds__(256) kg_fill(LV lv, KrylovGridArgs K, int a, int cur) {
   if (cur >= 0 && K.st(cur)[KG_DONE] != 0.0) return;
-  const auto op = lv.op();
-  double *v = a < 0 ? op.x() : K.w + (long)a * op.size();
-  const int nf = op.fill_count();
-  KG_POINTS(t, nf) op.fill_point(v, t);
+  double *v = a < 0 ? lv.x() : K.w + (long)a * lv.size();
+  const int nf = lv.fill_count();
+  KG_POINTS(t, nf) lv.fill_point(v, t);
 }
 
 // ---- conjugate gradients ----------------------------------------------------------------------------------------------------------------------
 template <class LV> __global__ void __launch_bounds__(1024) kg_cg_apply(LV lv, KrylovGridArgs K, int cur) {
   if (K.st(cur)[KG_DONE] != 0.0) return;
-  const auto op = lv.op();
-  const long sz = op.size();
-  const int np = op.count();
+  const long sz = lv.size();
+  const int np = lv.count();
   const double *p = K.w + sz, *dinv = K.w + 3 * sz;
   double *q = K.w + 2 * sz;
   double pq[1] = { 0.0 }, m1[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
-    if (dinv[c] != 0.0) { double Av, diag; op.apply(p, c, i, j, k, Av, diag); q[c] = Av; pq[0] = pq[0] + p[c] * Av; }
+    lv.point(t, c, i, j, k);
+    if (dinv[c] != 0.0) { double Av, diag; lv.apply(p, c, i, j, k, Av, diag); q[c] = Av; pq[0] = pq[0] + p[c] * Av; }
   }
   wg_reduce<1, 0>(pq, m1);
   kg_put(K, KG_D0, pq[0]);
@@ -201,15 +211,14 @@ template <class LV> __global__ void __launch_bounds__(1024) kg_cg_update(LV lv, 
   const double pq = kg_sum(kg_part(K, KG_D0), gridDim.x);
   const double alpha = S[KG_SRHO] / pq;
   if (!(pq > 0.0) || !kry_finite(pq) || !kry_finite(alpha)) { if (kg_first()) N[KG_H1] = 2.0; return; }
-  const auto op = lv.op();
-  const long sz = op.size();
-  const int np = op.count();
-  double *x = op.x(), *r = K.w;
+  const long sz = lv.size();
+  const int np = lv.count();
+  double *x = lv.x(), *r = K.w;
   const double *p = K.w + sz, *q = K.w + 2 * sz, *dinv = K.w + 3 * sz;
   double rz[1] = { 0.0 }, rn[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     const double di = dinv[c];
     if (di != 0.0) {
       x[c] = x[c] + alpha * p[c];
@@ -235,14 +244,13 @@ template <class LV> __global__ void __launch_bounds__(1024) kg_cg_dir(LV lv, Kry
   else if (!(rz > 0.0) || !kry_finite(rz)) { done = 1; broke = 1; }
   if (!done) {
     const double beta = rz / rho;
-    const auto op = lv.op();
-    const long sz = op.size();
-    const int np = op.count();
+    const long sz = lv.size();
+    const int np = lv.count();
     const double *r = K.w, *dinv = K.w + 3 * sz;
     double *p = K.w + sz;
     KG_POINTS(t, np) {
       long c; int i, j, k;
-      op.point(t, c, i, j, k);
+      lv.point(t, c, i, j, k);
       const double di = dinv[c];
       if (di != 0.0) p[c] = r[c] * di + beta * p[c];
     }
@@ -275,14 +283,13 @@ template <class LV> __global__ void __launch_bounds__(1024) kg_bi_dir(LV lv, Kry
   if (!code && !kry_finite(beta)) code = 2;
   if (code) { if (kg_first()) N[KG_H0] = (double)code; return; }
   if (kg_first()) { N[KG_SRHO] = rho; N[KG_RHO_OLD] = rho_old; }
-  const auto op = lv.op();
-  const long sz = op.size();
-  const int np = op.count();
+  const long sz = lv.size();
+  const int np = lv.count();
   const double *r = K.w, *v = K.w + 3 * sz, *dinv = K.w + 6 * sz;
   double *p = K.w + sz, *ph = K.w + 5 * sz;
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     const double di = dinv[c];
     if (di != 0.0) { const double pv = r[c] + beta * (p[c] - omega * v[c]); p[c] = pv; ph[c] = pv * di; }
   }
@@ -298,17 +305,16 @@ template <int SECOND, class LV> __global__ void __launch_bounds__(1024) kg_bi_ap
     if (!kry_finite(sn)) { if (kg_first()) N[KG_H3] = 2.0; return; }
     if (sn <= S[KG_TOL]) { if (kg_first()) N[KG_H3] = 1.0; return; }
   }
-  const auto op = lv.op();
-  const long sz = op.size();
-  const int np = op.count();
+  const long sz = lv.size();
+  const int np = lv.count();
   const double *r = K.w, *r0 = K.w + 2 * sz, *ph = K.w + 5 * sz, *dinv = K.w + 6 * sz;
   double *out = K.w + (SECOND ? 4 : 3) * sz;
   double s2[2] = { 0.0, 0.0 }, m1[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     if (dinv[c] != 0.0) {
-      double Av, diag; op.apply(ph, c, i, j, k, Av, diag);
+      double Av, diag; lv.apply(ph, c, i, j, k, Av, diag);
       out[c] = Av;
       if (SECOND) { s2[0] = s2[0] + Av * r[c]; s2[1] = s2[1] + Av * Av; } else s2[0] = s2[0] + r0[c] * Av;
     }
@@ -324,15 +330,14 @@ template <class LV> __global__ void __launch_bounds__(1024) kg_bi_half(LV lv, Kr
   const double alpha = N[KG_SRHO] / s1;
   if (s1 == 0.0 || !kry_finite(s1) || !kry_finite(alpha)) { if (kg_first()) N[KG_H2] = 2.0; return; }
   if (kg_first()) N[KG_ALPHA] = alpha;
-  const auto op = lv.op();
-  const long sz = op.size();
-  const int np = op.count();
-  double *x = op.x(), *r = K.w, *ph = K.w + 5 * sz;
+  const long sz = lv.size();
+  const int np = lv.count();
+  double *x = lv.x(), *r = K.w, *ph = K.w + 5 * sz;
   const double *v = K.w + 3 * sz, *dinv = K.w + 6 * sz;
   double s0[1] = { 0.0 }, sn[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     const double di = dinv[c];
     if (di != 0.0) {
       x[c] = x[c] + alpha * ph[c];
@@ -366,15 +371,14 @@ template <class LV> __global__ void __launch_bounds__(1024) kg_bi_full(LV lv, Kr
     }
     return;
   }
-  const auto op = lv.op();
-  const long sz = op.size();
-  const int np = op.count();
-  double *x = op.x(), *r = K.w;
+  const long sz = lv.size();
+  const int np = lv.count();
+  double *x = lv.x(), *r = K.w;
   const double *r0 = K.w + 2 * sz, *tt = K.w + 4 * sz, *ph = K.w + 5 * sz, *dinv = K.w + 6 * sz;
   double rr[1] = { 0.0 }, rn[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     if (dinv[c] != 0.0) {
       x[c] = x[c] + omega * ph[c];
       const double rv = r[c] - omega * tt[c];
@@ -394,13 +398,12 @@ template <class LV> __global__ void __launch_bounds__(1024) kg_bi_full(LV lv, Kr
 // ---- end of a visit -------------------------------------------------------------------------------------------------------------------------
 template <int METHOD, class LV> __global__ void __launch_bounds__(1024) kg_xsum(LV lv, KrylovGridArgs K) {
   constexpr int NW = (METHOD == VDN_KRYLOV_CG) ? 4 : 7;
-  const auto op = lv.op();
-  const int np = op.count();
-  const double *x = op.x(), *dinv = K.w + (NW - 1) * op.size();
+  const int np = lv.count();
+  const double *x = lv.x(), *dinv = K.w + (NW - 1) * lv.size();
   double sx[1] = { 0.0 }, m1[1] = { 0.0 };
   KG_POINTS(t, np) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     if (dinv[c] != 0.0) sx[0] = sx[0] + x[c];
   }
   wg_reduce<1, 0>(sx, m1);
@@ -409,17 +412,16 @@ template <int METHOD, class LV> __global__ void __launch_bounds__(1024) kg_xsum(
 template <int METHOD, class LV> __global__ void __launch_bounds__(1024) kg_finish(LV lv, KrylovGridArgs K, int cur) {
   constexpr int NW = (METHOD == VDN_KRYLOV_CG) ? 4 : 7;
   const double *S = K.st(cur);
-  const auto op = lv.op();
   const double nunk = S[KG_NUNK];
-  if (op.singular() && nunk > 0.0) {
+  if (lv.singular() && nunk > 0.0) {
     const double xm = kg_sum(kg_part(K, KG_X), gridDim.x) / nunk;
     if (kry_finite(xm)) {
-      const int np = op.count();
-      double *x = op.x();
-      const double *dinv = K.w + (NW - 1) * op.size();
+      const int np = lv.count();
+      double *x = lv.x();
+      const double *dinv = K.w + (NW - 1) * lv.size();
       KG_POINTS(t, np) {
         long c; int i, j, k;
-        op.point(t, c, i, j, k);
+        lv.point(t, c, i, j, k);
         if (dinv[c] != 0.0) x[c] = x[c] - xm;
       }
     }
@@ -450,9 +452,11 @@ static inline int krylov_grid_shape(long np, int &threads) {
   const long g = (np + threads - 1) / threads;
   return (int)(g > KG_MAXWG ? KG_MAXWG : (g < 1 ? 1 : g));
 }
-// one bottom visit: `budget` iterations (<= K.maxit) as plain launches on s
-template <int METHOD, class LV> static void krylov_grid_visit(const LV &lv, const KrylovGridArgs &K, long sz, long np, long nfill, bool singular, int budget, hipStream_t s) {
+// one bottom visit: `budget` iterations (<= K.maxit) as plain launches on s.  The shapes come from the adapter: the fill's launch from the fill's own count
+template <int METHOD, class LV> static void krylov_grid_visit(const LV &lv, const KrylovGridArgs &K, int budget, hipStream_t s) {
   constexpr int NW = (METHOD == VDN_KRYLOV_CG) ? 4 : 7;
+  const long sz = lv.size(), np = lv.count(), nfill = lv.fill_count();
+  const bool singular = lv.singular();
   int th; const int g = krylov_grid_shape(np, th);
   const dim3 G((unsigned)g), B((unsigned)th);
   const dim3 GF((unsigned)std::max(1L, std::min((long)KG_MAXWG, (nfill + 255) / 256))), BF(256);
@@ -480,4 +484,14 @@ template <int METHOD, class LV> static void krylov_grid_visit(const LV &lv, cons
   if (singular) hipLaunchKernelGGL((kg_xsum<METHOD, LV>), G, B, 0, s, lv, K);
   hipLaunchKernelGGL((kg_finish<METHOD, LV>), G, B, 0, s, lv, K, budget & 1);
   if (nfill) hipLaunchKernelGGL((kg_fill<LV>), GF, BF, 0, s, lv, K, -1, -1);
+}
+// what wg_krylov takes of a hierarchy's solver, for multigrid `which` (0 cell-centred, 1 nodal) with its tolerance eps (mg_krylov_visit; the tail-cycle launches)
+inline KrylovArgs mg_krylov_args(const MgKrylov &kry, int which, double eps) { return KrylovArgs{ kry.w, bottom_stats_dev(which), eps, kry.maxit }; }
+// One visit of the bottom level `lv` adapts by the Krylov solver the hierarchy selected: one workgroup, or -- kry.part set by mg_krylov_setup -- the whole GPU
+template <class LV> void mg_krylov_visit(const MgKrylov &kry, int which, double eps, const LV &lv) {
+  hipStream_t s = ctx().stream;
+  if (!kry.part) { hipLaunchKernelGGL((kk_bottom_krylov<LV>), dim3(1), dim3(1024), 0, s, lv, mg_krylov_args(kry, which, eps), kry.method); return; }
+  const KrylovGridArgs K{ kry.w, kry.part, bottom_stats_dev(which), bottom_exhausted_dev(which), eps, kry.maxit };
+  if (kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, kry.budget, s);
+  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, kry.budget, s);
 }

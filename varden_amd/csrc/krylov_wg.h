@@ -1,14 +1,18 @@
 // krylov_wg.h -- Krylov bottom solvers run by ONE workgroup (vdn_params.mg_bottom_solver / hg_bottom_solver).
 //
-// wg_krylov<METHOD>(op, K) solves  A x = b  on the coarsest level of a multigrid from the guess x = 0 (what a V-cycle's error equation starts from):
+// wg_krylov<METHOD>(lv, K) solves  A x = b  on the coarsest level of a multigrid from the guess x = 0 (what a V-cycle's error equation starts from):
 // METHOD 2 = conjugate gradients, METHOD 1 = BiCGStab, both preconditioned by the diagonal the level's operator returns.  It is a workgroup device
-// function in the style of wg_cc_gsrb / wg_nd_jacobi: called by a one-workgroup kernel of its own (kk_cc_bottom_krylov, kk_nd_bottom_krylov) and from
-// inside the tail-cycle kernels.  `op` adapts a level (CcKrylovOp in mg_cc.hip, NdKrylovOp in mg_nd.hip):
+// function in the style of wg_cc_gsrb / wg_nd_jacobi: called by a one-workgroup kernel of its own (kk_bottom_krylov<LV>, below) and from inside the
+// tail-cycle kernels (wg_krylov_any).  `lv` adapts a level: ONE struct per multigrid that holds the level by value, so the same object is a kernel
+// argument, the adapter on the device and what the host sizes its launches from (CcKrylov in mg_cc.hip, NdKrylov in mg_nd.hip, C2Krylov and N2Krylov
+// in dim2.hip):
 //   count()                        points the workgroup strides over
 //   point(t, c, i, j, k)           point t: its array offset and indices; false = not a candidate unknown (nodal Dirichlet nodes, periodic images)
 //   apply(v, c, i, j, k, Av, diag) the level's operator on the array v (cc_apply / nd_apply as they are)
 //   fill(v)                        periodic images of v (wg_cc_periodic / wg_nd_fill as they are; ends in a barrier when it does anything)
+//   fill_count(), fill_point(v, t) the same fill one entry at a time, for the grid-wide form (krylov_grid.h)
 //   size(), rhs(), x(), singular()
+// count(), fill_count(), size() and singular() are pure integer work and KRY_HD: the host (mg_krylov_visit) asks the adapter for them.
 //
 // Unknowns: candidate points whose diagonal is not zero.  Everything else keeps x = 0, has zero residual and search direction and takes part in no
 // dot product (a periodic nodal direction stores node n as an image of node 0: counted once, written by fill()).
@@ -25,7 +29,10 @@
 // Work arrays, each of the level's padded size: CG 4 (r, p, q, 1/diag), BiCGStab 7 (r -- which also holds s --, r0, p, v, t, the preconditioned
 // vector, 1/diag).  The workgroup zeroes them on entry (ghost entries outside a physical face must read as zero).
 #pragma once
+#include <type_traits>
 #include "vdn_dev.h"      // (METHOD: VDN_KRYLOV_BICGSTAB, VDN_KRYLOV_CG of mg_plan.h)
+
+#define KRY_HD __host__ __device__ __forceinline__      // the pure-integer members of a level adapter and the count helpers they call
 
 struct KrylovArgs {
   double *w;          // 4 (CG) or 7 (BiCGStab) arrays of the bottom level's padded size, from the arena
@@ -60,12 +67,12 @@ template <int NS, int NM> DEVI void wg_reduce(double *s, double *m) {
 }
 DEVI bool kry_finite(double v) { return fabs(v) < __builtin_huge_val(); }      // false for NaN too
 
-template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovArgs &K) {
+template <int METHOD, class LV> DEVI void wg_krylov(const LV &lv, const KrylovArgs &K) {
   constexpr int NW = (METHOD == VDN_KRYLOV_CG) ? 4 : 7;
-  const long sz = op.size();
-  const int np = op.count();
-  double *x = op.x();
-  const double *b = op.rhs();
+  const long sz = lv.size();
+  const int np = lv.count();
+  double *x = lv.x();
+  const double *b = lv.rhs();
   double *r = K.w, *p = K.w + sz, *q = K.w + 2 * sz, *dinv = K.w + (NW - 1) * sz;
   for (long t = threadIdx.x; t < (long)NW * sz; t += blockDim.x) K.w[t] = 0.0;
   __syncthreads();
@@ -73,22 +80,22 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
   double s2[2] = { 0.0, 0.0 }, m1[1] = { 0.0 };
   for (int t = threadIdx.x; t < np; t += blockDim.x) {
     long c; int i, j, k;
-    const bool cand = op.point(t, c, i, j, k);
+    const bool cand = lv.point(t, c, i, j, k);
     x[c] = 0.0;
     if (cand) {
-      double Av, diag; op.apply(b, c, i, j, k, Av, diag);        // (only diag is used: it does not depend on the array)
+      double Av, diag; lv.apply(b, c, i, j, k, Av, diag);        // (only diag is used: it does not depend on the array)
       if (diag != 0.0) { dinv[c] = 1.0 / diag; s2[0] = s2[0] + b[c]; s2[1] = s2[1] + 1.0; }
     }
   }
   wg_reduce<2, 0>(s2, m1);
   const double nunk = s2[1];
-  const double bmean = (op.singular() && nunk > 0.0) ? s2[0] / nunk : 0.0;
+  const double bmean = (lv.singular() && nunk > 0.0) ? s2[0] / nunk : 0.0;
   // r = b - mean on the unknowns; CG: p = z = r / diag, rho = r.z
   double rho = 0.0, bn = 0.0;
   s2[0] = 0.0;
   for (int t = threadIdx.x; t < np; t += blockDim.x) {
     long c; int i, j, k;
-    op.point(t, c, i, j, k);
+    lv.point(t, c, i, j, k);
     const double di = dinv[c];
     if (di != 0.0) {
       const double rv = b[c] - bmean;
@@ -108,12 +115,12 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
     if (METHOD == VDN_KRYLOV_CG) {
       while (it < K.maxit) {
         __syncthreads();                                           // p complete
-        op.fill(p);
+        lv.fill(p);
         double pq[1] = { 0.0 };
         for (int t = threadIdx.x; t < np; t += blockDim.x) {
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
-          if (dinv[c] != 0.0) { double Av, diag; op.apply(p, c, i, j, k, Av, diag); q[c] = Av; pq[0] = pq[0] + p[c] * Av; }
+          lv.point(t, c, i, j, k);
+          if (dinv[c] != 0.0) { double Av, diag; lv.apply(p, c, i, j, k, Av, diag); q[c] = Av; pq[0] = pq[0] + p[c] * Av; }
         }
         wg_reduce<1, 0>(pq, m1);
         if (!(pq[0] > 0.0) || !kry_finite(pq[0])) { broke = 1; break; }
@@ -122,7 +129,7 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
         double rz[1] = { 0.0 }, rn[1] = { 0.0 };
         for (int t = threadIdx.x; t < np; t += blockDim.x) {
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
+          lv.point(t, c, i, j, k);
           const double di = dinv[c];
           if (di != 0.0) {
             x[c] = x[c] + alpha * p[c];
@@ -141,7 +148,7 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
         rho = rz[0];
         for (int t = threadIdx.x; t < np; t += blockDim.x) {
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
+          lv.point(t, c, i, j, k);
           const double di = dinv[c];
           if (di != 0.0) p[c] = r[c] * di + beta * p[c];
         }
@@ -155,17 +162,17 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
         if (!kry_finite(beta)) { broke = 1; break; }
         for (int t = threadIdx.x; t < np; t += blockDim.x) {      // p = r + beta (p - omega v); ph = p / diag  (first pass: p = v = 0)
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
+          lv.point(t, c, i, j, k);
           const double di = dinv[c];
           if (di != 0.0) { const double pv = r[c] + beta * (p[c] - omega * v[c]); p[c] = pv; ph[c] = pv * di; }
         }
         __syncthreads();
-        op.fill(ph);
+        lv.fill(ph);
         double s1[1] = { 0.0 };
         for (int t = threadIdx.x; t < np; t += blockDim.x) {
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
-          if (dinv[c] != 0.0) { double Av, diag; op.apply(ph, c, i, j, k, Av, diag); v[c] = Av; s1[0] = s1[0] + r0[c] * Av; }
+          lv.point(t, c, i, j, k);
+          if (dinv[c] != 0.0) { double Av, diag; lv.apply(ph, c, i, j, k, Av, diag); v[c] = Av; s1[0] = s1[0] + r0[c] * Av; }
         }
         wg_reduce<1, 0>(s1, m1);
         if (s1[0] == 0.0 || !kry_finite(s1[0])) { broke = 1; break; }
@@ -174,7 +181,7 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
         double sn[1] = { 0.0 };
         for (int t = threadIdx.x; t < np; t += blockDim.x) {      // x += alpha ph; s = r - alpha v (kept in r); ph = s / diag
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
+          lv.point(t, c, i, j, k);
           const double di = dinv[c];
           if (di != 0.0) {
             x[c] = x[c] + alpha * ph[c];
@@ -187,12 +194,12 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
         it++;
         if (!kry_finite(sn[0])) { broke = 1; break; }
         if (sn[0] <= tol) break;
-        op.fill(ph);
+        lv.fill(ph);
         double ts[2] = { 0.0, 0.0 };
         for (int t = threadIdx.x; t < np; t += blockDim.x) {
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
-          if (dinv[c] != 0.0) { double Av, diag; op.apply(ph, c, i, j, k, Av, diag); tt[c] = Av; ts[0] = ts[0] + Av * r[c]; ts[1] = ts[1] + Av * Av; }
+          lv.point(t, c, i, j, k);
+          if (dinv[c] != 0.0) { double Av, diag; lv.apply(ph, c, i, j, k, Av, diag); tt[c] = Av; ts[0] = ts[0] + Av * r[c]; ts[1] = ts[1] + Av * Av; }
         }
         wg_reduce<2, 0>(ts, m1);
         if (!(ts[1] > 0.0) || !kry_finite(ts[1]) || !kry_finite(ts[0])) { broke = 1; break; }
@@ -201,7 +208,7 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
         double rr[1] = { 0.0 }, rn[1] = { 0.0 };
         for (int t = threadIdx.x; t < np; t += blockDim.x) {      // x += omega ph; r = s - omega t; rho = r0.r
           long c; int i, j, k;
-          op.point(t, c, i, j, k);
+          lv.point(t, c, i, j, k);
           if (dinv[c] != 0.0) {
             x[c] = x[c] + omega * ph[c];
             const double rv = r[c] - omega * tt[c];
@@ -218,11 +225,11 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
     }
   }
   __syncthreads();
-  if (op.singular() && nunk > 0.0) {                               // the mean of x over the same set
+  if (lv.singular() && nunk > 0.0) {                               // the mean of x over the same set
     double sx[1] = { 0.0 };
     for (int t = threadIdx.x; t < np; t += blockDim.x) {
       long c; int i, j, k;
-      op.point(t, c, i, j, k);
+      lv.point(t, c, i, j, k);
       if (dinv[c] != 0.0) sx[0] = sx[0] + x[c];
     }
     wg_reduce<1, 0>(sx, m1);
@@ -230,12 +237,12 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
     if (kry_finite(xm))
       for (int t = threadIdx.x; t < np; t += blockDim.x) {
         long c; int i, j, k;
-        op.point(t, c, i, j, k);
+        lv.point(t, c, i, j, k);
         if (dinv[c] != 0.0) x[c] = x[c] - xm;
       }
     __syncthreads();
   }
-  op.fill(x);
+  lv.fill(x);
   if (threadIdx.x == 0) {
     K.stats[0] = K.stats[0] + 1.0;
     K.stats[1] = K.stats[1] + (double)it;
@@ -244,3 +251,13 @@ template <int METHOD, class Op> DEVI void wg_krylov(const Op &op, const KrylovAr
   }
   __syncthreads();
 }
+template <class LV> DEVI void wg_krylov_any(int method, const LV &lv, const KrylovArgs &K) {      // method: uniform over the launch
+  if (method == VDN_KRYLOV_CG) wg_krylov<VDN_KRYLOV_CG>(lv, K); else wg_krylov<VDN_KRYLOV_BICGSTAB>(lv, K);
+}
+// the one-workgroup bottom visit of every multigrid (mg_krylov_visit in krylov_grid.h launches it: dim3(1), 1024 threads)
+template <class LV> __global__ void __launch_bounds__(1024) kk_bottom_krylov(LV lv, KrylovArgs K, int method) { wg_krylov_any(method, lv, K); }
+// What a tail-cycle kernel takes besides its levels: nothing in the sweeps instantiation, the solve's arguments in the Krylov one
+// (singular: the cell-centred hierarchy's flag; a nodal level knows its own)
+struct KrylovTailArgs { KrylovArgs K; int method, singular; };
+struct NoKrylovTailArgs {};
+template <bool KRYLOV> using KrylovTail = std::conditional_t<KRYLOV, KrylovTailArgs, NoKrylovTailArgs>;

@@ -701,7 +701,7 @@ __global__ void __launch_bounds__(1024) kk_cc_bottom(CLev L, int nsweeps, int pe
 #define CC_TAIL_MAX 4
 struct CcTailArgs { CLev L[CC_TAIL_MAX]; int nlev, nu1, nu2, nbot, per[3]; };
 // the periodic images of phi, one at a time: entry t of 6 faces of m x m, m the largest extent (wg_cc_periodic here, kg_fill in krylov_grid.h)
-DEVI int cc_periodic_count(const CLev &L, const int per[3]) {
+KRY_HD int cc_periodic_count(const CLev &L, const int per[3]) {
   if (!(per[0] || per[1] || per[2])) return 0;
   const int m = max(L.n[0], max(L.n[1], L.n[2]));
   return 6 * m * m;
@@ -773,59 +773,39 @@ DEVI void wg_cc_up(const CLev &F, const CLev &C) {
   }
   __syncthreads();
 }
-__global__ void __launch_bounds__(1024) kk_cc_tailcycle(CcTailArgs T) {
-  #pragma unroll
-  for (int l = 0; l < CC_TAIL_MAX - 1; l++)
-    if (l < T.nlev - 1) { wg_cc_gsrb(T.L[l], T.nu1, T.per); wg_cc_down(T.L[l], T.L[l + 1], T.per); }
-  #pragma unroll
-  for (int l = 0; l < CC_TAIL_MAX; l++)
-    if (l == T.nlev - 1) wg_cc_gsrb(T.L[l], T.nbot, T.per);
-  #pragma unroll
-  for (int l = CC_TAIL_MAX - 2; l >= 0; l--)
-    if (l < T.nlev - 1) { wg_cc_up(T.L[l], T.L[l + 1]); wg_cc_gsrb(T.L[l], T.nu2, T.per); }
-}
 
 // ---- Krylov bottom solvers (vdn_params.mg_bottom_solver = 1, 2, 3; krylov_wg.h) ------------------------------------------------------------------
 // The coarsest level of a hierarchy whose extents are not powers of two is large (200 -> 100 -> 50 -> 25: 25^3 cells, max(8, N^2) = 625 red-black sweeps by one
 // workgroup in every V-cycle); CG or BiCGStab with the diagonal of cc_apply as preconditioner reaches the reference's bottom_solver_eps in under a hundred
 // iterations.  The level's operator, its periodic fill and its arrays are used as they are; the solve starts from phi = 0, as every bottom visit does.
-struct CcKrylovOp {
-  const CLev &L; const int *per; int sing;
-  DEVI int count() const { return L.n[0] * L.n[1] * L.n[2]; }
+// CcKrylov is the level as wg_krylov, the grid-wide kernels and the host (mg_krylov_visit) take it (krylov_wg.h): by value.  The tail cycle, whose levels sit in
+// a kernel-argument array, takes the same members over a reference (CcKrylovRef: a copy there cost 41 VGPRs and 168 bytes of scratch, profiles/krylov_one_adapter.txt).
+template <bool REF> struct CcKrylovT {
+  std::conditional_t<REF, const CLev &, CLev> L; std::conditional_t<REF, const int *, int[3]> per; int sing;
+  KRY_HD int count() const { return L.n[0] * L.n[1] * L.n[2]; }
   DEVI bool point(int t, long &c, int &i, int &j, int &k) const { i = t % L.n[0]; j = (t / L.n[0]) % L.n[1]; k = t / (L.n[0] * L.n[1]); c = cidx(L, i, j, k); return true; }
   DEVI void apply(const double *v, long c, int, int, int, double &Av, double &diag) const { CLev Lv = L; Lv.phi = const_cast<double *>(v); cc_apply(Lv, c, Av, diag); }
   DEVI void fill(double *v) const { CLev Lv = L; Lv.phi = v; wg_cc_periodic(Lv, per); }
-  DEVI int fill_count() const { return cc_periodic_count(L, per); }
+  KRY_HD int fill_count() const { return cc_periodic_count(L, per); }
   DEVI void fill_point(double *v, int t) const { CLev Lv = L; Lv.phi = v; cc_periodic_point(Lv, per, t); }
-  DEVI long size() const { return L.sz; }
+  KRY_HD long size() const { return L.sz; }
   DEVI const double *rhs() const { return L.rh; }
   DEVI double *x() const { return L.phi; }
-  DEVI bool singular() const { return sing != 0; }
+  KRY_HD bool singular() const { return sing != 0; }
 };
-template <int METHOD> DEVI void wg_cc_krylov(const CLev &L, const int per[3], int singular, const KrylovArgs &K) {
-  const CcKrylovOp op{ L, per, singular };
-  wg_krylov<METHOD>(op, K);
-}
-DEVI void wg_cc_krylov_any(int method, const CLev &L, const int per[3], int singular, const KrylovArgs &K) {      // method: uniform over the launch
-  if (method == VDN_KRYLOV_CG) wg_cc_krylov<VDN_KRYLOV_CG>(L, per, singular, K); else wg_cc_krylov<VDN_KRYLOV_BICGSTAB>(L, per, singular, K);
-}
-__global__ void __launch_bounds__(1024) kk_cc_bottom_krylov(CLev L, KrylovArgs K, int method, int singular, int per0, int per1, int per2) {
-  const int per[3] = { per0, per1, per2 };
-  wg_cc_krylov_any(method, L, per, singular, K);
-}
-// the level as the grid-wide form takes it (krylov_grid.h): by value, for bottom levels of VDN_KRYLOV_GRID_MIN_POINTS cells and more
-struct CcKrylovLevel {
-  CLev L; int per[3]; int sing;
-  DEVI CcKrylovOp op() const { return CcKrylovOp{ L, per, sing }; }
-};
-// kk_cc_tailcycle with the Krylov solve in place of the nbot sweeps
-__global__ void __launch_bounds__(1024) kk_cc_tailcycle_krylov(CcTailArgs T, KrylovArgs K, int method, int singular) {
+using CcKrylov = CcKrylovT<false>;
+using CcKrylovRef = CcKrylovT<true>;
+// The small end of a V-cycle in one launch.  KRYLOV: the Krylov solve in place of the nbot sweeps (Q: its arguments; nothing in the sweeps instantiation)
+template <bool KRYLOV> __global__ void __launch_bounds__(1024) kk_cc_tailcycle(CcTailArgs T, KrylovTail<KRYLOV> Q) {
   #pragma unroll
   for (int l = 0; l < CC_TAIL_MAX - 1; l++)
     if (l < T.nlev - 1) { wg_cc_gsrb(T.L[l], T.nu1, T.per); wg_cc_down(T.L[l], T.L[l + 1], T.per); }
   #pragma unroll
   for (int l = 0; l < CC_TAIL_MAX; l++)
-    if (l == T.nlev - 1) wg_cc_krylov_any(method, T.L[l], T.per, singular, K);
+    if (l == T.nlev - 1) {
+      if constexpr (KRYLOV) wg_krylov_any(Q.method, CcKrylovRef{ T.L[l], T.per, Q.singular }, Q.K);
+      else wg_cc_gsrb(T.L[l], T.nbot, T.per);
+    }
   #pragma unroll
   for (int l = CC_TAIL_MAX - 2; l >= 0; l--)
     if (l < T.nlev - 1) { wg_cc_up(T.L[l], T.L[l + 1]); wg_cc_gsrb(T.L[l], T.nu2, T.per); }
@@ -1196,6 +1176,7 @@ struct CCMG {
   MgGather g_rh, g_b; GBox *d_gb_rh = nullptr, *d_gb_b = nullptr;                // cells (rhs, alpha) and face coefficients (mg_plan.h)
   double *sendbuf = nullptr, *recvbuf = nullptr;
   MgKrylov kry; int kry_singular = 0;      // Krylov bottom solver (mg_bottom_solver = 1, 2, 3; krylov_grid.h)
+  CcKrylov krylov(const CLev &L) const { return CcKrylov{ L, { per[0], per[1], per[2] }, kry_singular }; }      // its view of the bottom level L
 };
 
 static dim3 g3(int nx, int ny, int nz, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, nz); }
@@ -1416,19 +1397,6 @@ static void cc_build(CCMG &M, const vdn_multifab *rh, const double *dx, const in
     mg_krylov_setup(M.kry, method, B.sz, std::max(B.n[0], std::max(B.n[1], B.n[2])), (long)B.n[0] * B.n[1] * B.n[2], k);
   }
 }
-static KrylovArgs cc_krylov_args(const CCMG &M) { return KrylovArgs{ M.kry.w, bottom_stats_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry.maxit }; }
-// one visit of the bottom level L by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU
-static void cc_krylov_visit(const CCMG &M, const CLev &L) {
-  if (!M.kry.part) { hipLaunchKernelGGL(kk_cc_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, cc_krylov_args(M), M.kry.method, M.kry_singular, M.per[0], M.per[1], M.per[2]); return; }
-  const CcKrylovLevel lv{ L, { M.per[0], M.per[1], M.per[2] }, M.kry_singular };
-  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(0), bottom_exhausted_dev(0), ctx().prm.mg_bottom_solver_eps, M.kry.maxit };
-  const long np = (long)L.n[0] * L.n[1] * L.n[2];
-  const long m = std::max(L.n[0], std::max(L.n[1], L.n[2]));
-  const long nfill = (M.per[0] || M.per[1] || M.per[2]) ? 6 * m * m : 0;
-  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
-  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, M.kry_singular != 0, M.kry.budget, ctx().stream);
-}
-
 static void cc_halo(CCMG &M, CDLev &DL) { if (DL.halo) xplan_run(DL.halo); }
 // levels of at most 8^3 cells held in ONE box are smoothed by a single workgroup in one launch (all sweeps, both
 // colours, periodic images included): such levels are launch-latency bound, not bandwidth bound
@@ -1538,7 +1506,7 @@ static void cc_gsrb_t(const CCMG &M, const CLev &L, int nsweeps) {
   }
 }
 static void cc_bottom_t(const CCMG &M, const CLev &L) {      // max(nub, N^2) sweeps, N = largest extent (same rule as the oracle)
-  if (M.kry.w) { cc_krylov_visit(M, L); return; }
+  if (M.kry.w) { mg_krylov_visit(M.kry, 0, ctx().prm.mg_bottom_solver_eps, M.krylov(L)); return; }
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.mg_nub, N * N);
   hipLaunchKernelGGL(kk_cc_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, ns, M.per[0], M.per[1], M.per[2]);
@@ -1569,8 +1537,8 @@ static bool cc_small_end(const CCMG &M, int dl, int tl) {
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.mg_nu1; T.nu2 = P.mg_nu2; T.nbot = std::max(P.mg_nub, N * N);      // cc_bottom_t / cc_vcycle_d
   for (int d = 0; d < 3; d++) T.per[d] = M.per[d];
-  if (M.kry.w) { hipLaunchKernelGGL(kk_cc_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, cc_krylov_args(M), M.kry.method, M.kry_singular); return true; }
-  hipLaunchKernelGGL(kk_cc_tailcycle, dim3(1), dim3(1024), 0, ctx().stream, T);
+  if (M.kry.w) hipLaunchKernelGGL(kk_cc_tailcycle<true>, dim3(1), dim3(1024), 0, ctx().stream, T, KrylovTailArgs{ mg_krylov_args(M.kry, 0, P.mg_bottom_solver_eps), M.kry.method, M.kry_singular });
+  else hipLaunchKernelGGL(kk_cc_tailcycle<false>, dim3(1), dim3(1024), 0, ctx().stream, T, NoKrylovTailArgs{});
   return true;
 }
 // may tail level l run as kk_cc_lds_down / kk_cc_lds_up?  (round 6: the replicated levels of 16^3 .. 64^3 cells take the two-launch form of the one-box hierarchy too --
@@ -1737,7 +1705,7 @@ static void cc_vcycle_d(CCMG &M, int l) {
   if (cc_small_end(M, l, 0)) return;
   if (last && M.tail.empty()) {         // nothing below: bottom sweeps on the distributed level itself
     if (M.kry.w && DL.single_box && DL.boxes.size() == 1) {      // (one box: the Krylov bottom solver, when one is selected; several boxes keep the sweeps)
-      cc_krylov_visit(M, DL.boxes[0].L);
+      mg_krylov_visit(M.kry, 0, P.mg_bottom_solver_eps, M.krylov(DL.boxes[0].L));
       return;
     }
     const int N = std::max(DL.ng[0], std::max(DL.ng[1], DL.ng[2]));     // largest GLOBAL extent, as in the oracle
@@ -2060,10 +2028,7 @@ int cc_solve(CcRequest &q) {
     else if (!keep && !fixed && q.alpha && q.const_beta > 0.0 && cc_split_ok(M)) { cc_split_setup(M); g_mac_level_form = 1; }      // (phi goes over after the nested iteration, below)
   }
   // the bottom statistics are those of one solve (a composite solve: of all the cycles it runs on its kept hierarchy)
-  if (!fixed || !(keep && keep->built)) {
-    bottom_form_set(0, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
-    if (M.kry.w) { const int budget = bottom_budget_begin(0, M.kry.kind, M.kry.maxit); if (M.kry.part) M.kry.budget = budget; bottom_stats_reset(0); }
-  }
+  if (!fixed || !(keep && keep->built)) mg_krylov_begin(M.kry, 0, M.kry.w != nullptr);
   if (keep) keep->built = true;
   CDLev &D0 = M.dlev[0];
   const bool single = (M.dlev.size() == 1 && M.tail.empty());

@@ -878,7 +878,7 @@ __global__ void __launch_bounds__(1024) kk_nd_bottom(NLev L, double *a, double *
 #define ND_TAIL_MAX 4
 struct NdTailArgs { NLev L[ND_TAIL_MAX]; int nlev, nu1, nu2, nbot; double omega, om1, om2; int nsp; };      // om1, om2, nsp: the pre-smoothing sweeps' damping (NdOm)
 // nd_fill_nodes one entry at a time: entry t of the node array grown by one (wg_nd_fill here, kg_fill in krylov_grid.h)
-DEVI int nd_fill_count(const NLev &L) { return (L.per[0] || L.per[1] || L.per[2]) ? (L.n[0] + 3) * (L.n[1] + 3) * (L.n[2] + 3) : 0; }
+KRY_HD int nd_fill_count(const NLev &L) { return (L.per[0] || L.per[1] || L.per[2]) ? (L.n[0] + 3) * (L.n[1] + 3) * (L.n[2] + 3) : 0; }
 DEVI void nd_fill_point(const NLev &L, double *a, int t) {
   const int ex = L.n[0] + 3, ey = L.n[1] + 3;
   const int i = t % ex - 1, j = (t / ex) % ey - 1, k = t / (ex * ey) - 1;
@@ -951,31 +951,17 @@ DEVI void wg_nd_up(const NLev &F, double *fphi, const NLev &C, double *cphi) {  
   }
   __syncthreads();
 }
-// (The same with the levels copied into LDS for the duration was measured at 66 us per cycle against 57 us on the L2-resident arrays: a phase costs
-// ~2.5 us of dependent instructions of one wave per SIMD, not memory latency.)
-__global__ void __launch_bounds__(1024) kk_nd_tailcycle(NdTailArgs T) {
-  double *ph[ND_TAIL_MAX], *tm[ND_TAIL_MAX];
-  #pragma unroll
-  for (int l = 0; l < ND_TAIL_MAX; l++) { ph[l] = T.L[l].phi; tm[l] = T.L[l].tmp; }
-  #pragma unroll
-  for (int l = 0; l < ND_TAIL_MAX - 1; l++)
-    if (l < T.nlev - 1) { wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu1, T.omega, T.om1, T.om2, T.nsp); wg_nd_down(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); }
-  #pragma unroll
-  for (int l = 0; l < ND_TAIL_MAX; l++)
-    if (l == T.nlev - 1) wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nbot, T.omega);
-  #pragma unroll
-  for (int l = ND_TAIL_MAX - 2; l >= 0; l--)
-    if (l < T.nlev - 1) { wg_nd_up(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu2, T.omega); }
-}
 
 // ---- Krylov bottom solvers (vdn_params.hg_bottom_solver = 1, 2, 3; krylov_wg.h) ------------------------------------------------------------------
 // The 26^3-node bottom of a 200^3 problem takes max(hg_nub, 2 N^2) = 1250 Jacobi sweeps by one workgroup in every V-cycle.  K as nd_apply returns it has a positive
 // diagonal and is symmetric positive semi-definite, so CG applies with that diagonal as preconditioner.  Dirichlet (outflow) nodes are not unknowns; along a periodic
 // direction node n is the image of node 0, is written by wg_nd_fill only and is counted once.  The solve starts from phi = 0 and leaves its result in `phi` itself
 // (no ping-pong: the host's phi / tmp swap is that of zero sweeps).
-struct NdKrylovOp {
-  const NLev &L; double *phi;
-  DEVI int count() const { return (L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1); }
+// NdKrylov is the level as wg_krylov, the grid-wide kernels and the host (mg_krylov_visit) take it (krylov_wg.h): by value, its periodic flags set.  The tail cycle,
+// whose levels sit in a kernel-argument array, takes the same members over a reference (NdKrylovRef: a copy there cost scratch, profiles/krylov_one_adapter.txt).
+template <bool REF> struct NdKrylovT {
+  std::conditional_t<REF, const NLev &, NLev> L; double *phi;
+  KRY_HD int count() const { return (L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1); }
   DEVI bool point(int t, long &c, int &i, int &j, int &k) const {
     const int nx = L.n[0] + 1, ny = L.n[1] + 1;
     i = t % nx; j = (t / nx) % ny; k = t / (nx * ny); c = nidx(L, i, j, k);
@@ -983,28 +969,19 @@ struct NdKrylovOp {
   }
   DEVI void apply(const double *v, long, int i, int j, int k, double &Av, double &diag) const { nd_apply(L, v, i, j, k, Av, diag); }
   DEVI void fill(double *v) const { wg_nd_fill(L, v); }
-  DEVI int fill_count() const { return nd_fill_count(L); }
+  KRY_HD int fill_count() const { return nd_fill_count(L); }
   DEVI void fill_point(double *v, int t) const { nd_fill_point(L, v, t); }
-  DEVI long size() const { return L.sz; }
+  KRY_HD long size() const { return L.sz; }
   DEVI const double *rhs() const { return L.b; }
   DEVI double *x() const { return phi; }
-  DEVI bool singular() const { return !(L.dirlo[0] || L.dirlo[1] || L.dirlo[2] || L.dirhi[0] || L.dirhi[1] || L.dirhi[2]); }
+  KRY_HD bool singular() const { return !(L.dirlo[0] || L.dirlo[1] || L.dirlo[2] || L.dirhi[0] || L.dirhi[1] || L.dirhi[2]); }
 };
-template <int METHOD> DEVI void wg_nd_krylov(const NLev &L, double *phi, const KrylovArgs &K) {
-  const NdKrylovOp op{ L, phi };
-  wg_krylov<METHOD>(op, K);
-}
-DEVI void wg_nd_krylov_any(int method, const NLev &L, double *phi, const KrylovArgs &K) {      // method: uniform over the launch
-  if (method == VDN_KRYLOV_CG) wg_nd_krylov<VDN_KRYLOV_CG>(L, phi, K); else wg_nd_krylov<VDN_KRYLOV_BICGSTAB>(L, phi, K);
-}
-__global__ void __launch_bounds__(1024) kk_nd_bottom_krylov(NLev L, double *phi, KrylovArgs K, int method) { wg_nd_krylov_any(method, L, phi, K); }
-// the level as the grid-wide form takes it (krylov_grid.h): by value, for bottom levels of VDN_KRYLOV_GRID_MIN_POINTS nodes and more
-struct NdKrylovLevel {
-  NLev L; double *phi;
-  DEVI NdKrylovOp op() const { return NdKrylovOp{ L, phi }; }
-};
-// kk_nd_tailcycle with the Krylov solve in place of the nbot sweeps
-__global__ void __launch_bounds__(1024) kk_nd_tailcycle_krylov(NdTailArgs T, KrylovArgs K, int method) {
+using NdKrylov = NdKrylovT<false>;
+using NdKrylovRef = NdKrylovT<true>;
+// The small end of a V-cycle in one launch.  KRYLOV: the Krylov solve in place of the nbot sweeps (Q: its arguments; nothing in the sweeps instantiation)
+// (The same with the levels copied into LDS for the duration was measured at 66 us per cycle against 57 us on the L2-resident arrays: a phase costs
+// ~2.5 us of dependent instructions of one wave per SIMD, not memory latency.)
+template <bool KRYLOV> __global__ void __launch_bounds__(1024) kk_nd_tailcycle(NdTailArgs T, KrylovTail<KRYLOV> Q) {
   double *ph[ND_TAIL_MAX], *tm[ND_TAIL_MAX];
   #pragma unroll
   for (int l = 0; l < ND_TAIL_MAX; l++) { ph[l] = T.L[l].phi; tm[l] = T.L[l].tmp; }
@@ -1013,7 +990,10 @@ __global__ void __launch_bounds__(1024) kk_nd_tailcycle_krylov(NdTailArgs T, Kry
     if (l < T.nlev - 1) { wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu1, T.omega, T.om1, T.om2, T.nsp); wg_nd_down(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); }
   #pragma unroll
   for (int l = 0; l < ND_TAIL_MAX; l++)
-    if (l == T.nlev - 1) wg_nd_krylov_any(method, T.L[l], ph[l], K);
+    if (l == T.nlev - 1) {
+      if constexpr (KRYLOV) wg_krylov_any(Q.method, NdKrylovRef{ T.L[l], ph[l] }, Q.K);
+      else wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nbot, T.omega);
+    }
   #pragma unroll
   for (int l = ND_TAIL_MAX - 2; l >= 0; l--)
     if (l < T.nlev - 1) { wg_nd_up(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu2, T.omega); }
@@ -1372,18 +1352,6 @@ static void nd_build(NDMG &M, const vdn_multifab *coeffs, const double *dx, cons
     mg_krylov_setup(M.kry, method, B.sz, std::max(B.n[0], std::max(B.n[1], B.n[2])) + 1, (long)(B.n[0] + 1) * (B.n[1] + 1) * (B.n[2] + 1), k);
   }
 }
-static KrylovArgs nd_krylov_args(const NDMG &M) { return KrylovArgs{ M.kry.w, bottom_stats_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry.maxit }; }
-// one visit of the bottom level L (its periodic flags set) by the Krylov solver the hierarchy selected: one workgroup, or the whole GPU; the result is left in phi
-static void nd_krylov_visit(const NDMG &M, const NLev &L, double *phi) {
-  if (!M.kry.part) { hipLaunchKernelGGL(kk_nd_bottom_krylov, dim3(1), dim3(1024), 0, ctx().stream, L, phi, nd_krylov_args(M), M.kry.method); return; }
-  const NdKrylovLevel lv{ L, phi };
-  const KrylovGridArgs K{ M.kry.w, M.kry.part, bottom_stats_dev(1), bottom_exhausted_dev(1), ctx().prm.hg_bottom_solver_eps, M.kry.maxit };
-  const long np = (long)(L.n[0] + 1) * (L.n[1] + 1) * (L.n[2] + 1);
-  const long nfill = (L.per[0] || L.per[1] || L.per[2]) ? (long)(L.n[0] + 3) * (L.n[1] + 3) * (L.n[2] + 3) : 0;
-  const bool singular = !(L.dirlo[0] || L.dirlo[1] || L.dirlo[2] || L.dirhi[0] || L.dirhi[1] || L.dirhi[2]);
-  if (M.kry.method == VDN_KRYLOV_CG) krylov_grid_visit<VDN_KRYLOV_CG>(lv, K, L.sz, np, nfill, singular, M.kry.budget, ctx().stream);
-  else krylov_grid_visit<VDN_KRYLOV_BICGSTAB>(lv, K, L.sz, np, nfill, singular, M.kry.budget, ctx().stream);
-}
 
 // ---- distributed levels ------------------------------------------------------------------------------------------
 static void nd_halo_phi(NDLev &DL) { XPlan *P = DL.flip ? DL.halo_B : DL.halo_A; if (P) xplan_run(P); }
@@ -1500,7 +1468,7 @@ static void nd_jacobi_t(NLev &L, int nsweeps, bool pre = false) {
   }
 }
 static void nd_bottom_t(const NDMG &M, NLev &L) {          // max(nub, 2 N^2) sweeps (same rule as the oracle)
-  if (M.kry.w) { nd_krylov_visit(M, L, L.phi); return; }
+  if (M.kry.w) { mg_krylov_visit(M.kry, 1, ctx().prm.hg_bottom_solver_eps, NdKrylov{ L, L.phi }); return; }      // (the result is left in phi)
   const int N = std::max(L.n[0], std::max(L.n[1], L.n[2]));
   const int ns = std::max(ctx().prm.hg_nub, 2 * N * N);
   hipLaunchKernelGGL(kk_nd_bottom, dim3(1), dim3(1024), 0, ctx().stream, L, L.phi, L.tmp, ns, ctx().prm.hg_omega);
@@ -1613,9 +1581,8 @@ static bool nd_small_end(NDMG &M, int dl, int tl) {
   const NLev &B = T.L[nl - 1];
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.hg_nu1; T.nu2 = P.hg_nu2; T.nbot = std::max(P.hg_nub, 2 * N * N); T.omega = P.hg_omega; { const NdOm o = nd_om(true, P.hg_nu1); T.om1 = o.om1; T.om2 = o.om2; T.nsp = o.nsp; }     // nd_bottom_t / nd_bottom_sweeps_global
-  if (M.kry.w) { hipLaunchKernelGGL(kk_nd_tailcycle_krylov, dim3(1), dim3(1024), 0, ctx().stream, T, nd_krylov_args(M), M.kry.method); T.nbot = 0; /* no sweeps: no swap below */ }
-  else
-  hipLaunchKernelGGL(kk_nd_tailcycle, dim3(1), dim3(1024), 0, ctx().stream, T);
+  if (M.kry.w) { hipLaunchKernelGGL(kk_nd_tailcycle<true>, dim3(1), dim3(1024), 0, ctx().stream, T, KrylovTailArgs{ mg_krylov_args(M.kry, 1, P.hg_bottom_solver_eps), M.kry.method, 0 }); T.nbot = 0; /* no sweeps: no swap below */ }
+  else hipLaunchKernelGGL(kk_nd_tailcycle<false>, dim3(1), dim3(1024), 0, ctx().stream, T, NoKrylovTailArgs{});
   int m = 0;                                           // the ping-pong state the sweeps leave behind (nd_jacobi_d / nd_jacobi_t)
   if (dl >= 0) for (int q = dl; q < (int)M.dlev.size(); q++, m++) {
     const int sweeps = (m == nl - 1) ? T.nbot : T.nu1 + T.nu2;
@@ -1648,7 +1615,7 @@ static void nd_vcycle_d(NDMG &M, int l) {
     NBox &B = DL.boxes[0];
     NLev Lp = B.L;                      // (as nd_jacobi_d: the kernel refreshes periodic images itself)
     for (int d = 0; d < 3; d++) Lp.per[d] = DL.per[d];
-    nd_krylov_visit(M, Lp, B.L.phi);
+    mg_krylov_visit(M.kry, 1, P.hg_bottom_solver_eps, NdKrylov{ Lp, B.L.phi });
     return;
   }
   if (last && M.tail.empty()) { nd_jacobi_d(DL, nd_bottom_sweeps_global(DL)); return; }
@@ -1806,11 +1773,7 @@ int nd_solve(NdRequest &q) {
   const bool rebuild = !(keep && keep->built);
   if (rebuild) nd_build(M, coeffs, dx, q.bc);          // (of `coeffs` only the layout, the level and the boxes are used)
   NDLev &D0 = M.dlev[0];
-  if (!fixed_cycles || rebuild) {
-    bottom_form_set(1, M.kry.w ? (M.kry.part ? 2 : 1) : 0);
-    if (M.kry.w) { const int budget = bottom_budget_begin(1, M.kry.kind, M.kry.maxit); if (M.kry.part) M.kry.budget = budget; }
-  }
-  if (M.kry.w && (!fixed_cycles || rebuild)) bottom_stats_reset(1);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
+  if (!fixed_cycles || rebuild) mg_krylov_begin(M.kry, 1, M.kry.w != nullptr);      // the bottom statistics are those of one solve (a composite solve: of all the cycles on its kept hierarchy)
   M.pro_levels = 0; g_nd_pro_levels = 0;
   M.lds_levels = 0; g_nd_lds_levels = 0;
   if (rebuild) {
