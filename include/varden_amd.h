@@ -306,6 +306,39 @@ int vdn_tag_boxes(const vdn_multifab *s, int lev1, unsigned char *tags_host);
 int vdn_make_new_grids(const vdn_multifab *s, int lev1, int buf_wid, int nest, double min_eff, int min_width, int blocking,
                        int max_grid_size, int maxboxes, vdn_box *boxes_out, int *nboxes_out, long *ntagged);
 
+/* ---- refinement criteria chosen at run time ----------------------------------------------------------------------------------------
+ * The stand-in for editing src/tag_boxes.f90 (the file a user of the reference rewrites per problem; its aux_tag_mf hook ends in bl_error):
+ * a valid cell of level lev1 (1-based) is tagged when, for ANY of the ncrit criteria (1 .. VDN_TAG_MAX_CRITERIA),
+ *        gt[lev1-1] < value < lt[lev1-1]            both strict, as in tag_boxes.f90
+ * where `value` is what `field` names.  +-HUGE_VAL leaves a side open; gt = +HUGE_VAL switches the criterion off on that level; a NaN value
+ * tags nothing.  `comp` (0-based) is the component of s a SCALAR / SCALAR_GRAD criterion reads; velocity criteria ignore it.  All criteria are
+ * evaluated per cell in one pass on the device; no vorticity or gradient multifab is built.
+ *   VDN_TAG_VORTICITY, VDN_TAG_MAGVEL: the value vdn_make_vorticity / vdn_make_magvel would store for the same u, bit for bit (the same device
+ *     arithmetic), dm = 2: |v_x - u_y|.  The call fills the ghost cells of u the way those two do: the same-level fill, then (vorticity) physbc
+ *     -- so u is not const.  They need u; the vorticity also dx[dm] and the bc tower, and one ghost cell on u.
+ *   VDN_TAG_SCALAR_GRAD reads ONE ghost layer of s and fills nothing: the caller has filled it (same level, physical boundary), as the drivers
+ *     do before every regrid.
+ *   Ghost cells at a coarse-fine boundary are the caller's in both cases (vdn_ml_restrict_and_fill).
+ * u, dx and bct may be NULL when no criterion reads the velocity.  Refused (non-zero, vdn_last_error): an unknown field, a comp outside s, ncrit
+ * outside 1 .. 8, a velocity criterion without u, a gradient criterion on a state without ghost cells.
+ * vdn_tag_boxes_by / vdn_make_new_grids_by are vdn_tag_boxes / vdn_make_new_grids with this rule in place of the reference's; everything after the
+ * tag bitmap (the OR over the ranks, buffer, nesting, clustering, chop) is the same code.  dm = 2 and dm = 3 layouts. */
+#ifndef VDN_MAXLEV
+#define VDN_MAXLEV 4          /* deepest hierarchy (levels) */
+#endif
+#define VDN_TAG_SCALAR       0   /* s(comp) */
+#define VDN_TAG_SCALAR_GRAD  1   /* max over d < dm of max(|s(i+e_d) - s(i)|, |s(i) - s(i-e_d)|), undivided */
+#define VDN_TAG_VORTICITY    2   /* the value vdn_make_vorticity writes (dm = 2: its absolute value) */
+#define VDN_TAG_MAGVEL       3   /* the value vdn_make_magvel writes */
+#define VDN_TAG_MAX_CRITERIA 8
+typedef struct { int field; int comp; double gt[VDN_MAXLEV]; double lt[VDN_MAXLEV]; } vdn_tag_criterion;
+int vdn_tag_boxes_by(const vdn_multifab *s, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct, int lev1,
+                     int ncrit, const vdn_tag_criterion *crit, unsigned char *tags_host);
+int vdn_make_new_grids_by(const vdn_multifab *s, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct, int lev1,
+                          int ncrit, const vdn_tag_criterion *crit,
+                          int buf_wid, int nest, double min_eff, int min_width, int blocking,
+                          int max_grid_size, int maxboxes, vdn_box *boxes_out, int *nboxes_out, long *ntagged);
+
 /* ---- derived plot quantities of write_plotfile (src/varden.f90:532-540) ------------------------------------------------------------
  * make_vorticity(vort, comp, u, dx, bc)   src/makevort.f90:16-57  (fills the ghost cells of u first, as the reference does;
  *                                         3-D: |curl u| with one-sided differences next to inflow / no-slip faces, 2-D: v_x - u_y)

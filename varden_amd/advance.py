@@ -191,6 +191,70 @@ def tag_boxes(s, lev):
     return tags
 
 
+def tag_criteria(criteria):
+    """the ``vdn_tag_criterion`` array for a list of criteria, each a dict ``dict(field="vorticity", comp=1, gt=[...], lt=[...])`` or a tuple
+    ``(field, comp, gt, lt)`` (trailing entries may be left out).  field: scalar, scalar_grad, vorticity or magvel; comp: 1-based component of the
+    state (default 1; velocity fields ignore it); gt / lt: one threshold per level or a single number -- a list shorter than the hierarchy repeats its
+    last value (the reference's ``case default``), a side left out (or None) is open.  Returns (array, count)."""
+    if isinstance(criteria, C.Array) and criteria._type_ is capi.TagCriterion:      # built before (the drivers convert once, every regrid passes the array)
+        return criteria, len(criteria)
+    if isinstance(criteria, (dict, tuple)):
+        criteria = [criteria]
+    criteria = list(criteria)
+    if not 1 <= len(criteria) <= capi.TAG_MAX_CRITERIA:
+        raise ValueError("tag criteria: %d given, 1 .. %d allowed" % (len(criteria), capi.TAG_MAX_CRITERIA))
+    arr = (capi.TagCriterion * len(criteria))()
+    for q, c in enumerate(criteria):
+        if isinstance(c, capi.TagCriterion):
+            arr[q] = c
+            continue
+        if not isinstance(c, dict):
+            c = dict(zip(("field", "comp", "gt", "lt"), c))
+        unknown = set(c) - {"field", "comp", "gt", "lt"}
+        if unknown or "field" not in c:
+            raise ValueError("tag criterion %d: keys field, comp, gt, lt; got %s" % (q + 1, sorted(c)))
+        if c["field"] not in capi.TAG_FIELDS:
+            raise ValueError("tag criterion %d: unknown field %r (one of %s)" % (q + 1, c["field"], ", ".join(capi.TAG_FIELDS)))
+        arr[q].field = capi.TAG_FIELDS[c["field"]]
+        arr[q].comp = int(c.get("comp", 1)) - 1
+        for name, open_side in (("gt", -float("inf")), ("lt", float("inf"))):
+            v = c.get(name)
+            v = [open_side] if v is None else ([float(v)] if not hasattr(v, "__len__") else [float(x) for x in v])
+            if not 1 <= len(v) <= capi.MAXLEV:
+                raise ValueError("tag criterion %d: %s holds %d thresholds (1 .. %d)" % (q + 1, name, len(v), capi.MAXLEV))
+            for lev in range(capi.MAXLEV):
+                getattr(arr[q], name)[lev] = v[min(lev, len(v) - 1)]
+    return arr, len(criteria)
+
+
+def _by_args(u, dx, bct, criteria):
+    arr, n = tag_criteria(criteria)
+    d = None if dx is None else (C.c_double * 3)(*(list(dx) + [1.0] * 3)[:3])
+    return u.h if u is not None else None, d, bct.h if bct is not None else None, n, arr
+
+
+def make_new_grids_by(s, u, dx, bct, lev, criteria, buf_wid=2, nest=2, min_eff=0.9, min_width=4, blocking=4, max_grid_size=256, maxboxes=4096):
+    """make_new_grids with the cells of level `lev` (1-based) tagged by `criteria` (see tag_criteria) instead of src/tag_boxes.f90's rules; u, dx and
+    bct may be None when no criterion reads the velocity.  Returns the boxes of level lev+1 and the tag count."""
+    boxes = (capi.Box * maxboxes)()
+    nb, nt = C.c_int(), C.c_long()
+    uh, d, bh, n, arr = _by_args(u, dx, bct, criteria)
+    check(capi.load().vdn_make_new_grids_by(s.h, uh, d, bh, lev, n, arr, buf_wid, nest, min_eff, min_width, blocking, max_grid_size, maxboxes, boxes,
+                                            C.byref(nb), C.byref(nt)))
+    return [(tuple(boxes[i].lo), tuple(boxes[i].hi)) for i in range(nb.value)], nt.value
+
+
+def tag_boxes_by(s, u, dx, bct, lev, criteria):
+    """the tag bitmap of `criteria` on level `lev` (1-based): uint8 array over the level's domain (x first)"""
+    import numpy as np
+    lo, hi = s.mla.pd[s.lev]
+    n = tuple(hi[d] - lo[d] + 1 for d in range(3))
+    tags = np.zeros(n, dtype=np.uint8, order="F")
+    uh, d, bh, nc, arr = _by_args(u, dx, bct, criteria)
+    check(capi.load().vdn_tag_boxes_by(s.h, uh, d, bh, lev, nc, arr, tags.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return tags
+
+
 def fillpatch(fine, crse, icomp, nc):
     """fillpatch(fine, crse, 0, ...) of src/regrid.f90:311-325: valid cells of a new fine level from the coarser one"""
     check(capi.load().vdn_fillpatch(fine.h, crse.h, icomp, nc))

@@ -57,6 +57,16 @@ class Box(C.Structure):
     _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3)]
 
 
+MAXLEV = 4               # VDN_MAXLEV
+TAG_MAX_CRITERIA = 8     # VDN_TAG_MAX_CRITERIA
+TAG_FIELDS = {"scalar": 0, "scalar_grad": 1, "vorticity": 2, "magvel": 3}      # VDN_TAG_SCALAR .. VDN_TAG_MAGVEL
+
+
+class TagCriterion(C.Structure):
+    """mirror of ``vdn_tag_criterion``: a cell of level lev (1-based) is tagged when gt[lev-1] < value < lt[lev-1]; comp 0-based"""
+    _fields_ = [("field", C.c_int), ("comp", C.c_int), ("gt", C.c_double * MAXLEV), ("lt", C.c_double * MAXLEV)]
+
+
 # every symbol include/varden_amd.h declares: (restype, argtypes)
 _VP = C.c_void_p
 _PI = C.POINTER(C.c_int)
@@ -130,6 +140,9 @@ SIGNATURES = {
     "vdn_multifab_copy_layouts": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_int]),
     "vdn_tag_boxes": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_ubyte)]),
     "vdn_make_new_grids": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Box), _PI, C.POINTER(C.c_long)]),
+    "vdn_tag_boxes_by": (C.c_int, [_VP, _VP, _PD, _VP, C.c_int, C.c_int, C.POINTER(TagCriterion), C.POINTER(C.c_ubyte)]),
+    "vdn_make_new_grids_by": (C.c_int, [_VP, _VP, _PD, _VP, C.c_int, C.c_int, C.POINTER(TagCriterion), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.POINTER(Box), _PI, C.POINTER(C.c_long)]),
     "vdn_fabio_ml_multifab_write_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PI, C.POINTER(C.c_char_p), C.POINTER(Box), _PD, _PD, C.c_double, _PD, C.c_long]),
     "vdn_fabio_ml_multifab_info": (C.c_int, [C.c_char_p, _PI, _PI, _PI, _PI, _PI, _PI, _PD]),
     "vdn_fabio_ml_multifab_boxes": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(Box), C.c_int]),

@@ -14,7 +14,10 @@
 //      and recurse;
 //   4. the boxes are refined by ref_ratio and chopped to max_grid_size.
 // Output: boxes of level+1 in its own index space, disjoint, every tagged cell covered, blocking-factor aligned.
+// Step 1 has a second form, chosen at run time (vdn_tag_boxes_by / vdn_make_new_grids_by): up to 8 criteria over a scalar, its undivided gradient, the
+// vorticity or the velocity magnitude, ORed per cell in one pass (kk_tag_by); steps 2-4 are shared (new_grids_from_tags).
 #include "vdn_dev.h"
+#include "derived.h"
 #include "cluster.h"
 #include <vector>
 #include <algorithm>
@@ -25,6 +28,47 @@ __global__ void kk_tag(FV s, unsigned char *tags, int n0, int n1, int d0, int d1
   const double v = fv_get(s, i, j, k);
   const bool t = rule == 0 ? (v > tlo) : (v > tlo && v < thi);
   tags[(size_t)(i - d0) + (size_t)n0 * ((size_t)(j - d1) + (size_t)n1 * (size_t)(k - d2))] = t ? 1 : 0;
+}
+
+// ---- tagging by criteria ---------------------------------------------------------------------------------------------------------------------------
+// A cell is tagged when gt < value < lt holds for ANY row of the table (both strict, as in tag_boxes.f90; a NaN value fails both comparisons).  The table
+// travels by value in the kernel arguments (200 bytes).  MASK says at compile time which kinds of field the table holds, so a rule set reads only what it
+// needs: scalars alone touch neither u nor the neighbours of s -- 8 B read and 1 B written per cell, kk_tag's traffic; the vorticity reads the three
+// components of u once each (their neighbours are the same cache lines one row or plane on): 24 B per cell.  Nothing derived is stored: at 512^3 a
+// vorticity multifab would be 1 GB written and read back.  Streaming, no LDS, no atomics; x fastest, 64 x 4, as kk_tag.
+struct TagRule { int field, comp; double gt, lt; };
+struct TagTable { int n, pad; TagRule r[VDN_TAG_MAX_CRITERIA]; };
+enum { TAG_HAS_SCALAR = 1 << VDN_TAG_SCALAR, TAG_HAS_GRAD = 1 << VDN_TAG_SCALAR_GRAD, TAG_HAS_VORT = 1 << VDN_TAG_VORTICITY, TAG_HAS_MAGVEL = 1 << VDN_TAG_MAGVEL };
+DEVI double tag_max(double a, double b) { return (a >= b || a != a) ? a : b; }       // a NaN operand stays (fmax would drop it)
+// max(|s(i+e_D) - s(i)|, |s(i) - s(i-e_D)|), undivided
+template <int D> DEVI double tag_grad(const FV &s, int c, int i, int j, int k) {
+  const double s0 = fv_get(s, i, j, k, c);
+  return tag_max(fabs(fv_get(s, i + (D == 0), j + (D == 1), k + (D == 2), c) - s0), fabs(s0 - fv_get(s, i - (D == 0), j - (D == 1), k - (D == 2), c)));
+}
+template <int MASK>
+__global__ void __launch_bounds__(256) kk_tag_by(FV s, FV u, VortArgs A, TagTable T, unsigned char *tags, int n0, int n1, int d0, int d1, int d2, Range3 r) {
+  THREAD_IJK(r)
+  if (!in_range) return;
+  double vort = 0.0, mag = 0.0;
+  if (MASK & TAG_HAS_VORT) { vort = vort_value(u, A, i, j, k); if (A.dm == 2) vort = fabs(vort); }
+  if (MASK & TAG_HAS_MAGVEL) mag = magvel_value(u, A.dm, i, j, k);
+  bool t = false;
+  #pragma unroll
+  for (int q = 0; q < VDN_TAG_MAX_CRITERIA; q++) {
+    if (q >= T.n) break;
+    const int f = T.r[q].field, c = T.r[q].comp;
+    double v = mag;
+    if ((MASK & TAG_HAS_SCALAR) && f == VDN_TAG_SCALAR) v = fv_get(s, i, j, k, c);
+    else if ((MASK & TAG_HAS_GRAD) && f == VDN_TAG_SCALAR_GRAD) {
+      v = tag_max(tag_grad<0>(s, c, i, j, k), tag_grad<1>(s, c, i, j, k));
+      if (A.dm == 3) v = tag_max(v, tag_grad<2>(s, c, i, j, k));
+    } else if ((MASK & TAG_HAS_VORT) && f == VDN_TAG_VORTICITY) v = vort;
+    t = t || (v > T.r[q].gt && v < T.r[q].lt);
+  }
+  tags[(size_t)(i - d0) + (size_t)n0 * ((size_t)(j - d1) + (size_t)n1 * (size_t)(k - d2))] = t ? 1 : 0;
+}
+template <int MASK> static void launch_tag_by(const Range3 &r, FV s, FV u, const VortArgs &A, const TagTable &T, unsigned char *tags, const int *n, const vdn_box &pd) {
+  hipLaunchKernelGGL((kk_tag_by<MASK>), grid_for(r), dim3(64, 4, 1), 0, ctx().stream, s, u, A, T, tags, n[0], n[1], pd.lo[0], pd.lo[1], pd.lo[2], r);
 }
 
 // the byte maps of make_new_grids on the device: one byte per cell of the level's domain, x fastest
@@ -74,8 +118,23 @@ using namespace vdn_cluster;
 
 // tag_boxes (src/tag_boxes.f90:17-39 driver, 41-127 2-D, 128-216 3-D) of one level: a byte per cell of the level's DOMAIN (x fastest), 1 where
 // the first component of s exceeds the level's threshold; cells outside the level's boxes stay 0; all ranks end with the same bitmap.
-// Returns a device buffer the caller frees.
-static unsigned char *tag_level(const vdn_multifab *s, int lev1) {
+// Fills `tags` (freed with its owner).
+// a device buffer that goes with its scope: a throwing HIPCHK between hipMalloc and hipFree leaked the four buffers of make_new_grids
+template <class T> struct DevBuf {
+  T *p = nullptr;
+  DevBuf() {}
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  void alloc(size_t count) { HIPCHK(hipMalloc((void **)&p, count * sizeof(T))); }
+};
+typedef DevBuf<unsigned char> DevBytes;
+static size_t level_cells(const vdn_multifab *s, int n[3]) {
+  const vdn_box &pd = s->la->pd[s->lev];
+  for (int d = 0; d < 3; d++) n[d] = pd.hi[d] - pd.lo[d] + 1;
+  return (size_t)n[0] * n[1] * n[2];
+}
+static void tag_level(const vdn_multifab *s, int lev1, DevBytes &tags) {
   const vdn_box &pd = s->la->pd[s->lev];
   int n[3]; for (int d = 0; d < 3; d++) n[d] = pd.hi[d] - pd.lo[d] + 1;
   const int pt = ctx().prm.prob_type;
@@ -83,56 +142,122 @@ static unsigned char *tag_level(const vdn_multifab *s, int lev1) {
   int rule = 0; double tlo = 0.0, thi = 0.0;
   if (pt == 3) { rule = 1; tlo = 1.2; thi = 1.8; } else { tlo = lev1 == 1 ? 1.01 : (lev1 == 2 ? 1.1 : 1.5); }
   const size_t ncell = (size_t)n[0] * n[1] * n[2];
-  unsigned char *d_tags; HIPCHK(hipMalloc((void **)&d_tags, ncell));
+  tags.alloc(ncell);
+  unsigned char *d_tags = tags.p;
   HIPCHK(hipMemsetAsync(d_tags, 0, ncell, ctx().stream));
   for (int b = 0; b < s->nfabs(); b++) {
     Range3 r; for (int d = 0; d < 3; d++) { r.lo[d] = s->vbox[b].lo[d]; r.hi[d] = s->vbox[b].hi[d]; }
     hipLaunchKernelGGL(kk_tag, grid_for(r), dim3(64, 4, 1), 0, ctx().stream, s->fabs[b], d_tags, n[0], n[1], pd.lo[0], pd.lo[1], pd.lo[2], rule, tlo, thi, r);
   }
   comm_allreduce_max_u8_dev(d_tags, ncell);                // the tags of the other ranks' boxes: every rank sees the same bitmap
-  return d_tags;
+}
+// the same bitmap from criteria chosen at run time (include/varden_amd.h: vdn_tag_criterion): one launch of kk_tag_by per local box evaluates every
+// criterion.  Velocity criteria fill the ghost cells of u the way make_vorticity / make_magvel do (same-level fill, then physbc for the vorticity); the
+// gradient reads one ghost layer of s as the caller left it.  `who` names the entry point in the messages.
+static void tag_level_by(const char *who, const vdn_multifab *s, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct, int lev1,
+                         int ncrit, const vdn_tag_criterion *crit, DevBytes &tags) {
+  REQUIRE(s && crit, "%s: null argument", who);
+  REQUIRE(ncrit >= 1 && ncrit <= VDN_TAG_MAX_CRITERIA, "%s: %d criteria (1 .. %d)", who, ncrit, VDN_TAG_MAX_CRITERIA);
+  REQUIRE(lev1 >= 1 && lev1 <= VDN_MAXLEV, "%s: level %d (1 .. %d)", who, lev1, VDN_MAXLEV);
+  const int dm = ctx().prm.dm;
+  TagTable T; T.n = ncrit; T.pad = 0;
+  int mask = 0;
+  for (int q = 0; q < VDN_TAG_MAX_CRITERIA; q++) {
+    TagRule &r = T.r[q]; r.field = VDN_TAG_SCALAR; r.comp = 0; r.gt = __builtin_huge_val(); r.lt = -__builtin_huge_val();
+    if (q >= ncrit) continue;
+    const vdn_tag_criterion &c = crit[q];
+    REQUIRE(c.field >= VDN_TAG_SCALAR && c.field <= VDN_TAG_MAGVEL, "%s: criterion %d: unknown field %d", who, q, c.field);
+    if (c.field == VDN_TAG_SCALAR || c.field == VDN_TAG_SCALAR_GRAD) {
+      REQUIRE(c.comp >= 0 && c.comp < s->nc, "%s: criterion %d: component %d of a multifab with %d", who, q, c.comp, s->nc);
+      REQUIRE(c.field == VDN_TAG_SCALAR || s->ng >= 1, "%s: criterion %d: a gradient criterion reads one ghost cell, the state has none", who, q);
+      r.comp = c.comp;
+    } else {
+      REQUIRE(u, "%s: criterion %d reads the velocity: u is null", who, q);
+      REQUIRE(u->la == s->la && u->lev == s->lev && u->nfabs() == s->nfabs() && u->nc >= dm, "%s: u and s differ in level or boxes, or u has fewer than %d components", who, dm);
+      if (c.field == VDN_TAG_VORTICITY) REQUIRE(dx && bct && u->ng >= 1, "%s: criterion %d: the vorticity needs dx, the bc tower and one ghost cell of u", who, q);
+    }
+    r.field = c.field; r.gt = c.gt[lev1 - 1]; r.lt = c.lt[lev1 - 1];
+    mask |= 1 << c.field;
+  }
+  if (mask & TAG_HAS_VORT) { mf_fill_boundary(u); mf_physbc(u, 0, 0, dm, bct, false); }     // k_make_vorticity's fills
+  else if (mask & TAG_HAS_MAGVEL) mf_fill_boundary(u);                                        // k_make_magvel's
+  const vdn_box &pd = s->la->pd[s->lev];
+  int n[3]; const size_t ncell = level_cells(s, n);
+  tags.alloc(ncell);
+  HIPCHK(hipMemsetAsync(tags.p, 0, ncell, ctx().stream));
+  for (int b = 0; b < s->nfabs(); b++) {
+    Range3 r; for (int d = 0; d < 3; d++) { r.lo[d] = s->vbox[b].lo[d]; r.hi[d] = s->vbox[b].hi[d]; }
+    VortArgs A = VortArgs(); A.dm = dm;
+    if (mask & TAG_HAS_VORT) A = vort_args(u, b, bct, dx, dm, 0);
+    const FV fu = (mask & (TAG_HAS_VORT | TAG_HAS_MAGVEL)) ? u->fabs[b] : FV();
+    switch (mask) {
+#define TAG_CASE(M) case M: launch_tag_by<M>(r, s->fabs[b], fu, A, T, tags.p, n, pd); break;
+      TAG_CASE(1) TAG_CASE(2) TAG_CASE(3) TAG_CASE(4) TAG_CASE(5) TAG_CASE(6) TAG_CASE(7) TAG_CASE(8)
+      TAG_CASE(9) TAG_CASE(10) TAG_CASE(11) TAG_CASE(12) TAG_CASE(13) TAG_CASE(14) TAG_CASE(15)
+#undef TAG_CASE
+      default: vdn_fail("%s: no criterion", who);
+    }
+  }
+  comm_allreduce_max_u8_dev(tags.p, ncell);
+}
+static void tags_to_host(const vdn_multifab *s, const DevBytes &tags, unsigned char *tags_host) {
+  int n[3]; const size_t ncell = level_cells(s, n);
+  HIPCHK(hipMemcpyAsync(tags_host, tags.p, ncell, hipMemcpyDeviceToHost, ctx().stream));
+  HIPCHK(hipStreamSynchronize(ctx().stream));
 }
 // the tag bitmap alone (the parity test against the restated tag_boxes_3d): tags_host holds one byte per cell of the level's domain
 extern "C" int vdn_tag_boxes(const vdn_multifab *s, int lev1, unsigned char *tags_host) {
   VDN_TRY
   REQUIRE(s && tags_host, "vdn_tag_boxes: null argument");
-  const vdn_box &pd = s->la->pd[s->lev];
-  size_t ncell = 1; for (int d = 0; d < 3; d++) ncell *= (size_t)(pd.hi[d] - pd.lo[d] + 1);
-  unsigned char *d_tags = tag_level(s, lev1);
-  HIPCHK(hipMemcpyAsync(tags_host, d_tags, ncell, hipMemcpyDeviceToHost, ctx().stream));
-  HIPCHK(hipStreamSynchronize(ctx().stream));
-  HIPCHK(hipFree(d_tags));
+  DevBytes tags;
+  tag_level(s, lev1, tags);
+  tags_to_host(s, tags, tags_host);
+  VDN_CATCH
+}
+extern "C" int vdn_tag_boxes_by(const vdn_multifab *s, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct, int lev1,
+                                int ncrit, const vdn_tag_criterion *crit, unsigned char *tags_host) {
+  VDN_TRY
+  REQUIRE(ctx().inited, "vdn_init has not been called");
+  REQUIRE(s && tags_host, "vdn_tag_boxes_by: null argument");
+  DevBytes tags;
+  tag_level_by("vdn_tag_boxes_by", s, u, dx, bct, lev1, ncrit, crit, tags);
+  tags_to_host(s, tags, tags_host);
   VDN_CATCH
 }
 
-// s: the state of ONE level (valid cells of its local boxes; single rank).  boxes_out: boxes of the next finer level in ITS index space
-extern "C" int vdn_make_new_grids(const vdn_multifab *s, int lev1, int buf_wid, int nest, double min_eff, int min_width, int blocking,
-                                  int max_grid_size, int maxboxes, vdn_box *boxes_out, int *nboxes_out, long *ntagged) {
-  VDN_TRY
-  REQUIRE(s && boxes_out && nboxes_out, "vdn_make_new_grids: null argument");
-  REQUIRE(blocking >= 1 && min_width >= 1 && max_grid_size >= 2 * blocking, "vdn_make_new_grids: bad clustering parameters");
+// what make_new_grids checks before it tags
+static void check_grid_args(const char *who, const vdn_multifab *s, int min_width, int blocking, int max_grid_size, const vdn_box *boxes_out, const int *nboxes_out) {
+  REQUIRE(s && boxes_out && nboxes_out, "%s: null argument", who);
+  REQUIRE(blocking >= 1 && min_width >= 1 && max_grid_size >= 2 * blocking, "%s: bad clustering parameters", who);
+  int n[3]; level_cells(s, n);
+  const int dm = ctx().prm.dm;
+  for (int d = 0; d < dm; d++) REQUIRE(n[d] % blocking == 0, "%s: the domain extent %d is not a multiple of the blocking factor %d", who, n[d], blocking);
+}
+// steps 2-4 of make_new_grids from a tag bitmap of the level of `s` (one byte per cell of its domain, the same on every rank): the boxes of the next finer
+// level in ITS index space.  The bitmap is grown in place.
+static void new_grids_from_tags(const char *who, const vdn_multifab *s, DevBytes &tags, int buf_wid, int nest, double min_eff, int min_width, int blocking,
+                                int max_grid_size, int maxboxes, vdn_box *boxes_out, int *nboxes_out, long *ntagged) {
   const vdn_layout *la = s->la;
   const vdn_box &pd = la->pd[s->lev];
-  int n[3]; for (int d = 0; d < 3; d++) n[d] = pd.hi[d] - pd.lo[d] + 1;
+  int n[3]; const size_t ncell = level_cells(s, n);
   const int dm = ctx().prm.dm;
-  for (int d = 0; d < dm; d++) REQUIRE(n[d] % blocking == 0, "vdn_make_new_grids: the domain extent %d is not a multiple of the blocking factor %d", n[d], blocking);
-  // 1. tags on the device (tag_boxes.f90:142-210: thresholds by level, prob_type)
-  const size_t ncell = (size_t)n[0] * n[1] * n[2];
-  unsigned char *d_tags = tag_level(s, lev1);
+  Lattice G; for (int d = 0; d < 3; d++) G.n[d] = d < dm ? n[d] / blocking : 1;
+  *nboxes_out = 0;
+  {
   // 2. on the device (a 512^3 level is 134 M cells: the host loops of rounds 2-5 took 5 s of a 0.5 s step, tools/probes/regrid_profile_probe.py): count the tags,
   // grow them by buf_wid (box dilation, one direction after the other), inside[] = 1 on the cells of the level -- every box, on any rank --, shrunk by `nest`
   // the same way (cells outside the domain count as inside: a level may touch the domain boundary)
   hipStream_t st = ctx().stream;
-  unsigned char *d_in = nullptr, *d_tmp = nullptr; unsigned long long *d_cnt = nullptr;
-  HIPCHK(hipMalloc((void **)&d_in, ncell)); HIPCHK(hipMalloc((void **)&d_tmp, ncell)); HIPCHK(hipMalloc((void **)&d_cnt, sizeof(unsigned long long)));
+  DevBytes in, tmp; DevBuf<unsigned long long> cnt;                  // with `tags`: the four device buffers, freed at the end of this block, thrown or not
+  in.alloc(ncell); tmp.alloc(ncell); cnt.alloc(1);
+  unsigned char *&d_tags = tags.p, *&d_in = in.p, *&d_tmp = tmp.p; unsigned long long *d_cnt = cnt.p;
   HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), st));
   hipLaunchKernelGGL(kk_count_bytes, dim3((unsigned)std::min<size_t>((ncell + 255) / 256, 4096)), dim3(256), 0, st, d_tags, ncell, d_cnt);
   unsigned long long nt = 0;
   HIPCHK(hipMemcpyAsync(&nt, d_cnt, sizeof(nt), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (ntagged) *ntagged = (long)nt;
-  *nboxes_out = 0;
-  if (nt == 0) { HIPCHK(hipFree(d_tags)); HIPCHK(hipFree(d_in)); HIPCHK(hipFree(d_tmp)); HIPCHK(hipFree(d_cnt)); return 0; }
+  if (nt == 0) return;
   Range3 whole_cells; for (int d = 0; d < 3; d++) { whole_cells.lo[d] = 0; whole_cells.hi[d] = n[d] - 1; }
   auto sweep = [&](unsigned char *&a, unsigned char *&tmp, int width, int dilate) {
     if (width <= 0) return;
@@ -150,21 +275,21 @@ extern "C" int vdn_make_new_grids(const vdn_multifab *s, int lev1, int buf_wid, 
   sweep(d_in, d_tmp, nest, 0);
   // 3. cluster on the lattice of blocks; a block takes part only if it lies in the nesting region as a whole (a tagged cell outside the nesting region
   // cannot tag a block: the block is then not inside as a whole either)
-  Lattice G; for (int d = 0; d < 3; d++) G.n[d] = d < dm ? n[d] / blocking : 1;
   const size_t nblk = (size_t)G.n[0] * G.n[1] * G.n[2];
   G.t.assign(nblk, 0); G.ok.assign(nblk, 0);
   const int bz = dm == 3 ? blocking : 1;
   {
-    unsigned char *d_lat = nullptr; HIPCHK(hipMalloc((void **)&d_lat, 2 * nblk));
+    DevBytes lat; lat.alloc(2 * nblk);
+    unsigned char *d_lat = lat.p;
     Range3 rb; for (int d = 0; d < 3; d++) { rb.lo[d] = 0; rb.hi[d] = G.n[d] - 1; }
     hipLaunchKernelGGL(kk_block_lattice, grid_for(rb), dim3(64, 4, 1), 0, st, (const unsigned char *)d_tags, (const unsigned char *)d_in, d_lat, d_lat + nblk,
                        n[0], n[1], G.n[0], G.n[1], blocking, bz, rb);
     HIPCHK(hipMemcpyAsync(G.t.data(), d_lat, nblk, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(G.ok.data(), d_lat + nblk, nblk, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipFree(d_lat));
   }
-  HIPCHK(hipFree(d_tags)); HIPCHK(hipFree(d_in)); HIPCHK(hipFree(d_tmp)); HIPCHK(hipFree(d_cnt));
+  }
+  { unsigned char *p = tags.p; tags.p = nullptr; HIPCHK(hipFree(p)); }      // (the bitmap goes before the host half, as the other three just did)
   std::vector<IBox> cl;
   IBox whole; for (int d = 0; d < 3; d++) { whole.lo[d] = 0; whole.hi[d] = G.n[d] - 1; }
   cluster(G, whole, min_eff, std::max(1, (min_width + blocking - 1) / blocking), cl);
@@ -192,8 +317,32 @@ extern "C" int vdn_make_new_grids(const vdn_multifab *s, int lev1, int buf_wid, 
       out.push_back(o);
     }
   }
-  REQUIRE((int)out.size() <= maxboxes, "vdn_make_new_grids: %d boxes, room for %d", (int)out.size(), maxboxes);
+  REQUIRE((int)out.size() <= maxboxes, "%s: %d boxes, room for %d", who, (int)out.size(), maxboxes);
   for (size_t i = 0; i < out.size(); i++) boxes_out[i] = out[i];
   *nboxes_out = (int)out.size();
+}
+
+// s: the state of ONE level (valid cells of its local boxes).  boxes_out: boxes of the next finer level in ITS index space
+extern "C" int vdn_make_new_grids(const vdn_multifab *s, int lev1, int buf_wid, int nest, double min_eff, int min_width, int blocking,
+                                  int max_grid_size, int maxboxes, vdn_box *boxes_out, int *nboxes_out, long *ntagged) {
+  VDN_TRY
+  check_grid_args("vdn_make_new_grids", s, min_width, blocking, max_grid_size, boxes_out, nboxes_out);
+  // 1. tags on the device (tag_boxes.f90:142-210: thresholds by level, prob_type)
+  DevBytes tags;
+  tag_level(s, lev1, tags);
+  new_grids_from_tags("vdn_make_new_grids", s, tags, buf_wid, nest, min_eff, min_width, blocking, max_grid_size, maxboxes, boxes_out, nboxes_out, ntagged);
+  VDN_CATCH
+}
+// the same with step 1 by criteria (tag_level_by)
+extern "C" int vdn_make_new_grids_by(const vdn_multifab *s, vdn_multifab *u, const double *dx, const vdn_bc_tower *bct, int lev1,
+                                     int ncrit, const vdn_tag_criterion *crit,
+                                     int buf_wid, int nest, double min_eff, int min_width, int blocking,
+                                     int max_grid_size, int maxboxes, vdn_box *boxes_out, int *nboxes_out, long *ntagged) {
+  VDN_TRY
+  REQUIRE(ctx().inited, "vdn_init has not been called");
+  check_grid_args("vdn_make_new_grids_by", s, min_width, blocking, max_grid_size, boxes_out, nboxes_out);
+  DevBytes tags;
+  tag_level_by("vdn_make_new_grids_by", s, u, dx, bct, lev1, ncrit, crit, tags);
+  new_grids_from_tags("vdn_make_new_grids_by", s, tags, buf_wid, nest, min_eff, min_width, blocking, max_grid_size, maxboxes, boxes_out, nboxes_out, ntagged);
   VDN_CATCH
 }

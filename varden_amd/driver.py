@@ -12,7 +12,7 @@ from . import boxlib as bl
 from .capi import default_params
 
 
-def initdata_numpy(n, dx, prob_type=1, ng=3, nscal=2, lo=(0, 0, 0), centre=(0.5, 0.5, 0.5), dm=3):
+def initdata_numpy(n, dx, prob_type=1, ng=3, nscal=2, lo=(0, 0, 0), centre=(0.5, 0.5, 0.5), dm=3, tube_lo=None):
     """reference src/initdata.f90:212-259 (prob_type 1 bubble / 2 advected blob), numpy restatement used
     for synthetic bench input; fills the box [lo, lo+n) (with ng ghost layers left at the background value).
     dm = 2: initdata_2d (initdata.f90:127-171, densfact = 2), arrays of shape (nx+2ng, ny+2ng, 1, nc)."""
@@ -49,10 +49,13 @@ def initdata_numpy(n, dx, prob_type=1, ng=3, nscal=2, lo=(0, 0, 0), centre=(0.5,
     X, Y, Z = np.meshgrid(x, y, z, indexing="ij")
     g = ng
     if prob_type == 4:                                    # vortex tube, initdata.f90:276-306.  The reference measures x, y, z from the
-        # BOX's low corner (float(k - lo(3))): with the one 32^3 box of inputs_vortextube_3d that is the domain's; kept as written
-        xb = dx[0] * (np.arange(n[0]) + 0.5) - 0.5
-        yb = dx[1] * (np.arange(n[1]) + 0.5) - 0.5
-        zb = dx[2] * (np.arange(n[2]) + 0.5) - 0.5
+        # BOX's low corner (float(k - lo(3))): with the one 32^3 box of inputs_vortextube_3d that is the domain's; kept as written.  tube_lo: measure from this
+        # index instead -- the REFINED levels of a hierarchy pass the domain's corner (the reference never refines this problem: its tag_boxes refuses it; a
+        # tube per fine box would be no vortex tube)
+        off = [0, 0, 0] if tube_lo is None else [lo[d] - tube_lo[d] for d in range(3)]
+        xb = dx[0] * (off[0] + np.arange(n[0]) + 0.5) - 0.5
+        yb = dx[1] * (off[1] + np.arange(n[1]) + 0.5) - 0.5
+        zb = dx[2] * (off[2] + np.arange(n[2]) + 0.5) - 0.5
         Xb, Yb, Zb = np.meshgrid(xb, yb, zb, indexing="ij")
         r_yz = np.sqrt(Yb * Yb + Zb * Zb)
         u[g:-g, g:-g, g:-g, 0] = np.tanh((0.15 - r_yz) / 0.0333)
@@ -257,6 +260,28 @@ def extruded_initdata(prob_type, nscal, prob_hi2=(1.0, 1.0)):
     return fn
 
 
+def _tagged_level_by(mla, boxes, owner, rank, lev, ncs, ns, phys_bc, prob_type, init_fn, tag_criteria, cluster):
+    """VardenAMR.tagged_grids with criteria: state AND velocity of the initial data on the levels 0 .. lev-1, ghost cells filled, level lev-1 tagged"""
+    bct = bl.BCTower(mla, [[int(phys_bc[d][s]) for s in range(2)] for d in range(3)])
+    uold = [bl.MultiFab(mla, n, 3, 3) for n in range(lev)]
+    sold = [bl.MultiFab(mla, n, ns, 3) for n in range(lev)]
+    for n in range(lev):
+        dx = [1.0 / (ncs[0] << n)] * 3
+        for li, gi in enumerate([i for i, o in enumerate(owner[n]) if o == rank]):
+            blo, bhi = boxes[n][gi]
+            nb = tuple(bhi[d] - blo[d] + 1 for d in range(3))
+            ub, sb = initdata_numpy(nb, dx, prob_type, 3, ns, lo=blo, tube_lo=(0, 0, 0) if n else None) if init_fn is None else init_fn(n, blo, nb, dx)
+            uold[n].from_numpy(ub, li)
+            sold[n].from_numpy(sb, li)
+    adv.ml_restrict_and_fill(uold, 0, 0, 3, bct)
+    adv.ml_restrict_and_fill(sold, 0, 3, ns, bct)
+    new, _ = adv.make_new_grids_by(sold[lev - 1], uold[lev - 1], [1.0 / (ncs[0] << (lev - 1))] * 3, bct, lev, tag_criteria, **cluster)
+    for m in uold + sold:
+        m.destroy()
+    bct.destroy()
+    return new
+
+
 class VardenAMR:
     """multi-level hierarchy on fixed grids (the reference's fixed_grids mode, src/initialize.f90:93-150): level 0 = the domain
     [0,nc)^3 in one box or in `base_boxes` (equal boxes, what max_grid_size makes of it), level 1 = the given fine boxes (fine index
@@ -266,7 +291,7 @@ class VardenAMR:
     def __init__(self, nc, fine_boxes, phys_bc, params=None, prob_type=1, grav=-9.8, init_shrink=0.1, device=0, finer_levels=(),
                  regrid_int=-1, max_levs=None, max_grid_size=256, init_iter=0, do_initial_projection=0,
                  rank=0, nranks=1, comm_id=None, base_boxes=None, init_fn=None, restart=None, restart_step=0,
-                 fixed_dt=-1.0, stop_time=-1.0, amr_buf_width=-1, swap_state=False, extrude2d=None, extrude_zbc=None):
+                 fixed_dt=-1.0, stop_time=-1.0, amr_buf_width=-1, swap_state=False, extrude2d=None, extrude_zbc=None, tag_criteria=None):
         """nc: cells of level 0 per direction (an int: a cube; dx = dy = dz = 1 / nc[0]).
         extrude2d = nz: a 2-D problem of nc[0] x nc[1] cells (phys_bc: its two directions) run as its z-uniform copy -- nz cells of level 0 along a periodic z, gravity along y,
         initdata_2d on every plane, velpred_2d's outlet rule (include/varden_amd.h: vdn_set_extruded_2d).  With w = 0 and nothing varying along z the 3-D scheme is the 2-D one
@@ -274,8 +299,12 @@ class VardenAMR:
         -- tagging, regridding, composite solves -- run on the 3-D machinery; plane k = 0 is the 2-D answer (slice2d).
         init_fn(level, box_lo, box_shape, dx) -> (u, s) with 3 ghost layers replaces the analytic initial data of prob_type.
         several ranks (one per GPU): the boxes of every level are dealt to the ranks by cell count (`distribute`), `base_boxes` cuts
-        level 0 into several boxes, comm_id is the RCCL unique id broadcast by the caller; regridding is single-rank in this round"""
+        level 0 into several boxes, comm_id is the RCCL unique id broadcast by the caller; regridding is single-rank in this round.
+        tag_criteria: what regridding refines on, in place of the rules of src/tag_boxes.f90 -- a list of criteria as advance.tag_criteria takes them, e.g.
+        [dict(field="vorticity", gt=[8.0, 16.0])]; None: the reference's rules (which know prob_type 1 .. 3 only).  An extruded 2-D copy is a 3-D layout:
+        the 3-D vorticity rule |curl u| applies to it (equal to |v_x - u_y| away from inflow and wall faces, where the one-sided forms of makevort_3d and makevort_2d differ)."""
         self.prm = params or default_params()
+        self.tag_criteria = None if tag_criteria is None else adv.tag_criteria(tag_criteria)[0]
         self.grav, self.regrid_int, self.max_grid_size = grav, regrid_int, max_grid_size
         self.amr_buf_width = max(amr_buf_width, regrid_int, 1)    # the tag buffer of initialize.f90:248 AND regrid.f90:149 (probin.template:147-154)
         self.fixed_dt, self.stop_time = float(fixed_dt), float(stop_time)
@@ -333,7 +362,8 @@ class VardenAMR:
             for li, gi in enumerate(self.local[n]):         # each rank initialises the boxes it owns
                 blo, bhi = self.boxes[n][gi]
                 nb = tuple(bhi[d] - blo[d] + 1 for d in range(3))
-                ub, sb = initdata_numpy(nb, self.dx[n], prob_type, 3, ns, lo=blo) if init_fn is None else init_fn(n, blo, nb, self.dx[n])
+                ub, sb = (initdata_numpy(nb, self.dx[n], prob_type, 3, ns, lo=blo, tube_lo=(0, 0, 0) if n else None) if init_fn is None
+                          else init_fn(n, blo, nb, self.dx[n]))
                 self.uold[n].from_numpy(ub, li)
                 self.sold[n].from_numpy(sb, li)
         self.time, self.istep = 0.0, 0
@@ -358,10 +388,13 @@ class VardenAMR:
                                  self.ext_vel_force, self.ext_scal_force, self.bct, self.dt, self.time, self.dx, self.press_comp, bl.PRESSURE_ITERS)
 
     @staticmethod
-    def tagged_grids(nc, phys_bc, params=None, prob_type=1, max_levs=2, buf_wid=2, max_grid_size=256, device=0, rank=0, nranks=1, comm_id=None, base_boxes=None, extrude2d=None):
+    def tagged_grids(nc, phys_bc, params=None, prob_type=1, max_levs=2, buf_wid=2, max_grid_size=256, device=0, rank=0, nranks=1, comm_id=None, base_boxes=None, extrude2d=None, tag_criteria=None):
         """the grids the reference's initialize_with_adaptive_grids builds (src/initialize.f90:152-342): level by level, initial data on
         the level -> tag_boxes -> make_new_grids, until nothing is tagged or max_levs is reached.  Returns the box lists of the levels
-        1.. (each in its own index space).  Nesting: a new level keeps 2 cells of its parent level around itself."""
+        1.. (each in its own index space).  Nesting: a new level keeps 2 cells of its parent level around itself.
+        tag_criteria (see __init__): tag by these criteria instead; the velocity of the initial data is then built beside the state, on every level up to
+        the one being tagged, and the ghost cells of both are filled (ml_restrict_and_fill) -- a velocity or gradient criterion reads them.  An extruded
+        2-D copy is a 3-D layout: the 3-D vorticity rule applies."""
         prm = params or default_params()
         prm.prob_type = prob_type
         bl.initialize(prm, rank, nranks, device)
@@ -381,16 +414,21 @@ class VardenAMR:
         for lev in range(1, max_levs):
             owner = [distribute(lb, nranks) for lb in boxes]
             mla = bl.MLLayout(pd, boxes, owner=owner, rr=[(2, 2, 2)] * (lev - 1), pmask=tuple(1 if int(phys_bc[d][0]) == bl.PERIODIC else 0 for d in range(3)))
-            sold = bl.MultiFab(mla, lev - 1, ns, 3)
-            dx = [1.0 / (ncs[0] << (lev - 1))] * 3
-            for li, gi in enumerate([i for i, o in enumerate(owner[lev - 1]) if o == rank]):
-                blo, bhi = boxes[lev - 1][gi]
-                nb = tuple(bhi[d] - blo[d] + 1 for d in range(3))
-                _, sb = initdata_numpy(nb, dx, prob_type, 3, ns, lo=blo) if init_fn is None else init_fn(lev - 1, blo, nb, dx)
-                sold.from_numpy(sb, li)
-            new, _ = adv.make_new_grids(sold, lev, buf_wid=buf_wid, nest=0 if lev == 1 else 2, min_eff=prm_cluster(prm, "min_eff"),
-                                        min_width=prm_cluster(prm, "min_width"), blocking=prm_cluster(prm, "blocking"), max_grid_size=max_grid_size)
-            sold.destroy(); mla.destroy()
+            cluster = dict(buf_wid=buf_wid, nest=0 if lev == 1 else 2, min_eff=prm_cluster(prm, "min_eff"), min_width=prm_cluster(prm, "min_width"),
+                           blocking=prm_cluster(prm, "blocking"), max_grid_size=max_grid_size)
+            if tag_criteria is not None:
+                new = _tagged_level_by(mla, boxes, owner, rank, lev, ncs, ns, phys_bc, prob_type, init_fn, tag_criteria, cluster)
+                mla.destroy()
+            else:
+                sold = bl.MultiFab(mla, lev - 1, ns, 3)
+                dx = [1.0 / (ncs[0] << (lev - 1))] * 3
+                for li, gi in enumerate([i for i, o in enumerate(owner[lev - 1]) if o == rank]):
+                    blo, bhi = boxes[lev - 1][gi]
+                    nb = tuple(bhi[d] - blo[d] + 1 for d in range(3))
+                    _, sb = initdata_numpy(nb, dx, prob_type, 3, ns, lo=blo) if init_fn is None else init_fn(lev - 1, blo, nb, dx)
+                    sold.from_numpy(sb, li)
+                new, _ = adv.make_new_grids(sold, lev, **cluster)
+                sold.destroy(); mla.destroy()
             if not new:
                 break
             levels.append(new)
@@ -465,8 +503,13 @@ class VardenAMR:
         lev = 1
         while lev < self.max_levs:
             self._fill_levels(cur, lev)
-            new, _ = adv.make_new_grids(cur["sold"][lev - 1], lev, buf_wid=buf, nest=0 if lev == 1 else 2, min_eff=prm_cluster(self.prm, "min_eff"),
-                                        min_width=prm_cluster(self.prm, "min_width"), blocking=prm_cluster(self.prm, "blocking"), max_grid_size=self.max_grid_size)
+            cluster = dict(buf_wid=buf, nest=0 if lev == 1 else 2, min_eff=prm_cluster(self.prm, "min_eff"), min_width=prm_cluster(self.prm, "min_width"),
+                           blocking=prm_cluster(self.prm, "blocking"), max_grid_size=self.max_grid_size)
+            if self.tag_criteria is not None:
+                dxl = [1.0 / (self.ncs[0] << (lev - 1))] * 3
+                new, _ = adv.make_new_grids_by(cur["sold"][lev - 1], cur["uold"][lev - 1], dxl, cur["bct"], lev, self.tag_criteria, **cluster)
+            else:
+                new, _ = adv.make_new_grids(cur["sold"][lev - 1], lev, **cluster)
             if not new:
                 break
             nxt = self._alloc_state(cur["boxes"] + [new])

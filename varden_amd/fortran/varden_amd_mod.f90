@@ -48,6 +48,14 @@ module varden_amd
      integer(c_int) :: lo(3), hi(3)
   end type vdn_box
 
+  ! refinement criteria chosen at run time (include/varden_amd.h: vdn_tag_criterion): a cell of level lev is tagged when gt(lev) < value < lt(lev) for ANY
+  ! criterion; comp is 0-based here, as in C (make_tag_criterion takes the 1-based one)
+  integer, parameter, public :: VDN_TAG_SCALAR = 0, VDN_TAG_SCALAR_GRAD = 1, VDN_TAG_VORTICITY = 2, VDN_TAG_MAGVEL = 3, VDN_TAG_MAX_CRITERIA = 8, VDN_MAXLEV = 4
+  type, bind(C), public :: vdn_tag_criterion
+     integer(c_int) :: field, comp
+     real(c_double) :: gt(4), lt(4)
+  end type vdn_tag_criterion
+
   type, public :: ml_layout
      type(c_ptr) :: h = c_null_ptr
      integer :: nlevel = 0, dim = 3
@@ -71,6 +79,7 @@ module varden_amd
   public :: advance_timestep, estdt, hgproject, macproject
   public :: ml_cc_restriction, ml_edge_restriction, multifab_fill_ghost_cells, create_umac_grown, ml_restrict_and_fill
   public :: fillpatch, ml_nodal_prolongation, multifab_copy_layouts, make_new_grids, make_vorticity, make_magvel
+  public :: make_new_grids_by, tag_boxes_by, make_tag_criterion
   public :: fabio_ml_multifab_write_d, fabio_ml_multifab_info, fabio_ml_multifab_boxes, fabio_ml_multifab_read_d, checkpoint_write, checkpoint_info
   public :: fabio_ml_multifab_write_plane_d, fabio_ml_multifab_read_plane_d, checkpoint_write_plane, make_vorticity_plane
 
@@ -278,6 +287,26 @@ module varden_amd
        type(vdn_box), intent(out) :: boxes_out(*)
        integer(c_int), intent(out) :: nboxes_out
        integer(c_long), intent(out) :: ntagged
+     end function
+     integer(c_int) function vdn_make_new_grids_by(s, u, dx, bct, lev1, ncrit, crit, buf_wid, nest, min_eff, min_width, blocking, max_grid_size, maxboxes, &
+                                                   boxes_out, nboxes_out, ntagged) bind(C, name="vdn_make_new_grids_by")
+       import :: c_int, c_ptr, c_double, c_long, vdn_box, vdn_tag_criterion
+       type(c_ptr), value :: s, u, bct
+       real(c_double), intent(in) :: dx(*)
+       integer(c_int), value :: lev1, ncrit, buf_wid, nest, min_width, blocking, max_grid_size, maxboxes
+       type(vdn_tag_criterion), intent(in) :: crit(*)
+       real(c_double), value :: min_eff
+       type(vdn_box), intent(out) :: boxes_out(*)
+       integer(c_int), intent(out) :: nboxes_out
+       integer(c_long), intent(out) :: ntagged
+     end function
+     integer(c_int) function vdn_tag_boxes_by(s, u, dx, bct, lev1, ncrit, crit, tags_host) bind(C, name="vdn_tag_boxes_by")
+       import :: c_int, c_ptr, c_double, c_signed_char, vdn_tag_criterion
+       type(c_ptr), value :: s, u, bct
+       real(c_double), intent(in) :: dx(*)
+       integer(c_int), value :: lev1, ncrit
+       type(vdn_tag_criterion), intent(in) :: crit(*)
+       integer(c_signed_char), intent(out) :: tags_host(*)
      end function
      ! plot files and checkpoints inside the library (include/varden_amd.h; csrc/fabio.hip); optional C arguments travel as addresses (c_null_ptr: the default)
      integer(c_int) function vdn_fabio_ml_multifab_write_d(dirname, nlev, mfs, rr, names, pd0, prob_lo, prob_hi, time, dx0, staging_bytes) &
@@ -745,6 +774,73 @@ contains
     nboxes = nb
     new_grid = nb > 0
   end subroutine make_new_grids
+  ! the same with the cells tagged by criteria chosen at run time instead of the rules of src/tag_boxes.f90 (the stand-in for editing that file): crit(1:ncrit) as
+  ! make_tag_criterion builds them; u, dx and the_bc_tower are read by the velocity criteria (the call fills the ghost cells of u as make_vorticity does)
+  subroutine make_new_grids_by(new_grid, mf, u, dx, the_bc_tower, lev, ncrit, crit, buf_wid, nest, max_grid_size, boxes, nboxes)
+    logical       , intent(  out) :: new_grid
+    type(multifab), intent(in   ) :: mf
+    type(multifab), intent(inout) :: u
+    real(dp_t)    , intent(in   ) :: dx(:)
+    type(bc_tower), intent(in   ) :: the_bc_tower
+    integer       , intent(in   ) :: lev, ncrit, buf_wid, nest, max_grid_size
+    type(vdn_tag_criterion), intent(in) :: crit(:)
+    type(vdn_box) , intent(  out) :: boxes(:)
+    integer       , intent(  out) :: nboxes
+    integer(c_int)  :: nb
+    integer(c_long) :: nt
+    real(c_double)  :: d(3)
+    d = 1.0_c_double; d(1:min(3, size(dx))) = dx(1:min(3, size(dx)))
+    call chk(vdn_make_new_grids_by(mf%h, u%h, d, the_bc_tower%h, int(lev, c_int), int(ncrit, c_int), crit, int(buf_wid, c_int), int(nest, c_int), &
+                                   0.9_c_double, 4_c_int, 4_c_int, int(max_grid_size, c_int), int(size(boxes), c_int), boxes, nb, nt), 'make_new_grids_by')
+    nboxes = nb
+    new_grid = nb > 0
+  end subroutine make_new_grids_by
+  ! the tag bitmap of the criteria alone: one byte per cell of the level's domain, x fastest
+  subroutine tag_boxes_by(tags, mf, u, dx, the_bc_tower, lev, ncrit, crit)
+    integer(c_signed_char), intent(out) :: tags(*)
+    type(multifab), intent(in   ) :: mf
+    type(multifab), intent(inout) :: u
+    real(dp_t)    , intent(in   ) :: dx(:)
+    type(bc_tower), intent(in   ) :: the_bc_tower
+    integer       , intent(in   ) :: lev, ncrit
+    type(vdn_tag_criterion), intent(in) :: crit(:)
+    real(c_double)  :: d(3)
+    d = 1.0_c_double; d(1:min(3, size(dx))) = dx(1:min(3, size(dx)))
+    call chk(vdn_tag_boxes_by(mf%h, u%h, d, the_bc_tower%h, int(lev, c_int), int(ncrit, c_int), crit, tags), 'tag_boxes_by')
+  end subroutine tag_boxes_by
+  ! one criterion from the namelist's form: the field by name, comp 1-based, the thresholds of levels 1 .. 4 with `unset` where the inputs gave none -- an unset
+  ! level repeats the level before it (the reference's "case default"), a side never set is open
+  function make_tag_criterion(field, comp, gt, lt, unset) result(c)
+    use, intrinsic :: ieee_arithmetic, only: ieee_value, ieee_negative_inf, ieee_positive_inf
+    character(len=*), intent(in) :: field
+    integer         , intent(in) :: comp
+    real(dp_t)      , intent(in) :: gt(4), lt(4), unset
+    type(vdn_tag_criterion) :: c
+    integer :: l
+    select case (trim(field))
+    case ('scalar');      c%field = VDN_TAG_SCALAR
+    case ('scalar_grad'); c%field = VDN_TAG_SCALAR_GRAD
+    case ('vorticity');   c%field = VDN_TAG_VORTICITY
+    case ('magvel');      c%field = VDN_TAG_MAGVEL
+    case default
+       write(*, '(a,a)') 'varden_amd: unknown tag_field ', trim(field)
+       error stop 1
+    end select
+    c%comp = comp - 1
+    c%gt = ieee_value(1.0_c_double, ieee_negative_inf); c%lt = ieee_value(1.0_c_double, ieee_positive_inf)      ! open sides
+    do l = 1, 4
+       if (gt(l) /= unset) then
+          c%gt(l) = gt(l)
+       else if (l > 1) then
+          c%gt(l) = c%gt(l - 1)
+       end if
+       if (lt(l) /= unset) then
+          c%lt(l) = lt(l)
+       else if (l > 1) then
+          c%lt(l) = c%lt(l - 1)
+       end if
+    end do
+  end function make_tag_criterion
 
   ! ---- plot files and checkpoints (FBoxLib's fabio_module, src/checkpoint.f90): written and read inside the library, one rank ------------------------
   ! fabio_ml_multifab_write_d(mfs, rrs, dirname, names, bounding_box, prob_lo, prob_hi, time, dx)   (src/varden.f90:568-573, src/checkpoint.f90:45-48);

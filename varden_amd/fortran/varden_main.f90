@@ -29,11 +29,21 @@ program varden_main
   real(dp_t) :: init_shrink = 1.d0, cflfac = 0.8d0, max_dt_growth = 1.1d0, visc_coef = 0.d0, diff_coef = 0.d0, fixed_dt = -1.d0, cluster_min_eff = 0.9d0
   real(dp_t) :: u_bc(3,2) = 0.d0, v_bc(3,2) = 0.d0, w_bc(3,2) = 0.d0, rho_bc(3,2) = 1.d0, trac_bc(3,2) = 0.d0
   character(len=128) :: plot_base_name = 'plt', check_base_name = 'chk'
+  ! ---- the project's own keys (absent from src/_parameters): refinement criteria chosen at run time, the stand-in for editing src/tag_boxes.f90.  Criterion n
+  ! tags the cells of level lev where tag_gt(n,lev) < value < tag_lt(n,lev); tag_field(n): 'scalar', 'scalar_grad', 'vorticity' or 'magvel'; tag_comp(n): the
+  ! 1-based component of the state for the first two; a level without a threshold repeats the level before it, a side never given is open.  Without the keys
+  ! the run tags by tag_boxes.f90's rules, as before.
+  real(dp_t), parameter :: TAG_UNSET = -1.2345d300
+  character(len=16) :: tag_field(8) = ''
+  integer :: tag_comp(8) = 1
+  real(dp_t) :: tag_gt(8,4) = TAG_UNSET, tag_lt(8,4) = TAG_UNSET
+  type(vdn_tag_criterion) :: crit(8)
+  integer :: ncrit = 0
   namelist /probin/ dim_in, nscal, prob_type, boussinesq, max_step, max_levs, max_grid_size, regrid_int, amr_buf_width, n_cellx, n_celly, n_cellz, &
        init_iter, do_initial_projection, diffusion_type, slope_order, use_minion, stencil_order, verbose, mg_verbose, plot_int, chk_int, restart, ref_ratio, &
        bcx_lo, bcx_hi, bcy_lo, bcy_hi, bcz_lo, bcz_hi, cluster_min_width, cluster_blocking_factor, grav, stop_time, prob_hi_x, prob_hi_y, prob_hi_z, &
        prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc, &
-       plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels
+       plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels, tag_field, tag_comp, tag_gt, tag_lt
 
   ! one hierarchy: box lists, layout, boundary tower and the four multifabs regridding carries (regrid.f90:60-75)
   type hier
@@ -85,6 +95,14 @@ program varden_main
   end if
   if (prob_type < 1 .or. prob_type > 4) stop 'varden_main: prob_type 1 .. 4 (src/initdata.f90)'
   if (max_levs > MAXL) stop 'varden_main: at most 4 levels'
+  do n = 1, 8                                                    ! the criteria given, in the order of their numbers
+     if (tag_field(n) == '') then
+        if (any(tag_gt(n,:) /= TAG_UNSET) .or. any(tag_lt(n,:) /= TAG_UNSET)) stop 'varden_main: tag_gt / tag_lt without the tag_field of that criterion'
+        cycle
+     end if
+     ncrit = ncrit + 1
+     crit(ncrit) = make_tag_criterion(tag_field(n), tag_comp(n), tag_gt(n,:), tag_lt(n,:), TAG_UNSET)
+  end do
 
   call probin_defaults(prm)
   prm%dm = dim_in; prm%nscal = nscal; prm%slope_order = slope_order; prm%use_minion = use_minion; prm%boussinesq = boussinesq
@@ -120,7 +138,12 @@ program varden_main
      call alloc_state(H)
      call init_level(H, 1)
      do lev = 1, max_levs - 1
-        call make_new_grids(new_grid, H%sold(lev), lev, abw, merge(0, 2, lev == 1), mgs, newb, nnew)      ! (tag_boxes reads valid cells only)
+        if (ncrit > 0) then                                          ! (criteria may read ghost cells of the state and the velocity)
+           call fill_levels(H, lev)
+           call make_new_grids_by(new_grid, H%sold(lev), H%uold(lev), dx(lev,:), H%bct, lev, ncrit, crit, abw, merge(0, 2, lev == 1), mgs, newb, nnew)
+        else
+           call make_new_grids(new_grid, H%sold(lev), lev, abw, merge(0, 2, lev == 1), mgs, newb, nnew)   ! (tag_boxes reads valid cells only)
+        end if
         if (.not. new_grid) exit
         call grow_hierarchy(H, newb, nnew, carry=.true.)
         call init_level(H, lev + 1)
@@ -493,18 +516,20 @@ contains
 
   ! initdata_3d (src/initdata.f90:190-306) on every box of level l; ghost cells at the background state.  prob_type 1: the bubble (u = 0, rho = tracer = the
   ! tanh blob, :212-238); 2: the same blob advected by u = (1, 0, 0) (:240-259); 3: the Rayleigh-Taylor interface (:195-200, 261-274; tracer 0);
-  ! 4: the vortex tube (:276-306; coordinates measured from the BOX's low corner, as the reference writes it)
+  ! 4: the vortex tube (:276-306; coordinates measured from the BOX's low corner, as the reference writes it -- on level 1; the refined levels, which the reference
+  ! never builds for this problem, measure from the domain's corner: a tube per fine box would be no vortex tube)
   subroutine init_level(G, l)
     type(hier), intent(inout) :: G
     integer, intent(in) :: l
     real(dp_t), allocatable :: s0(:,:,:,:), u0(:,:,:,:)
-    integer :: b, i, j, k, lo(3), hi(3)
+    integer :: b, i, j, k, lo(3), hi(3), org(3)
     real(dp_t) :: x, y, z, dist, r, xb, yb, zb, ryz
     real(dp_t), parameter :: pi = 3.141592653589793238462643383279502884d0
     do b = 1, G%nb(l)
        lo = G%bx(b, l)%lo; hi = G%bx(b, l)%hi
        allocate(u0(lo(1)-3:hi(1)+3, lo(2)-3:hi(2)+3, lo(3)-3:hi(3)+3, dm), s0(lo(1)-3:hi(1)+3, lo(2)-3:hi(2)+3, lo(3)-3:hi(3)+3, nscal))
        u0 = 0.d0; s0(:,:,:,1) = 1.d0; s0(:,:,:,2:) = 0.d0
+       org = lo; if (l > 1) org = 0
        if (prob_type == 2) u0(:,:,:,1) = 1.d0
        do k = lo(3), hi(3)
           z = dx(l,3) * (k + 0.5d0)
@@ -533,7 +558,7 @@ contains
                 case (3)
                    s0(i,j,k,1) = 1.d0 + 0.5d0 + 0.5d0 * tanh((z - 0.5d0 - pert(x) - pert(y)) / 0.01d0)
                 case (4)
-                   xb = dx(l,1) * (i - lo(1) + 0.5d0) - 0.5d0; yb = dx(l,2) * (j - lo(2) + 0.5d0) - 0.5d0; zb = dx(l,3) * (k - lo(3) + 0.5d0) - 0.5d0
+                   xb = dx(l,1) * (i - org(1) + 0.5d0) - 0.5d0; yb = dx(l,2) * (j - org(2) + 0.5d0) - 0.5d0; zb = dx(l,3) * (k - org(3) + 0.5d0) - 0.5d0
                    ryz = sqrt(yb * yb + zb * zb)
                    u0(i,j,k,1) = tanh((0.15d0 - ryz) / 0.0333d0)
                    u0(i,j,k,3) = 0.05d0 * exp(-15.d0 * (xb * xb + yb * yb))
@@ -583,7 +608,11 @@ contains
     l = 1
     do while (l < max_levs)
        call fill_levels(C, l)
-       call make_new_grids(ng, C%sold(l), l, abw, merge(0, 2, l == 1), mgs, newb, nnew)
+       if (ncrit > 0) then
+          call make_new_grids_by(ng, C%sold(l), C%uold(l), dx(l,:), C%bct, l, ncrit, crit, abw, merge(0, 2, l == 1), mgs, newb, nnew)
+       else
+          call make_new_grids(ng, C%sold(l), l, abw, merge(0, 2, l == 1), mgs, newb, nnew)
+       end if
        if (.not. ng) exit
        allocate(N%bx(MAXB, MAXL))
        N%nlev = C%nlev + 1; N%nb = C%nb; N%bx = C%bx

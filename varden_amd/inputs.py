@@ -21,10 +21,10 @@ DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step
 
 
 def parse_namelist(text):
-    """key = value pairs of the first namelist group; Fortran literals (1.d0, .true., 'str'); indexed keys like u_bc(1,1) kept verbatim"""
+    """key = value pairs of the first namelist group; Fortran literals (1.d0, .true., 'str'); indexed keys like u_bc(1,1) or tag_field(1) kept verbatim"""
     out = {}
     body = re.sub(r"!.*", "", text)
-    for m in re.finditer(r"([A-Za-z_][\w]*(?:\(\s*\d+\s*,\s*\d+\s*\))?)\s*=\s*('[^'\n]*'|\"[^\"\n]*\"|[^\n,/]+)", body):
+    for m in re.finditer(r"([A-Za-z_][\w]*(?:\(\s*\d+\s*(?:,\s*\d+\s*)?\))?)\s*=\s*('[^'\n]*'|\"[^\"\n]*\"|[^\n,/]+)", body):
         key, val = m.group(1).replace(" ", ""), m.group(2).strip()
         low = val.lower()
         if low in (".true.", "t", ".t."):
@@ -39,6 +39,52 @@ def parse_namelist(text):
                 out[key] = int(num)
             except ValueError:
                 out[key] = float(num)
+    return out
+
+
+def namelist_tag_criteria(nl):
+    """the project's own keys (absent from the reference's _parameters): tag_field(n) = 'scalar' | 'scalar_grad' | 'vorticity' | 'magvel', tag_comp(n) (1-based,
+    default 1), tag_gt(n,lev), tag_lt(n,lev) for n = 1 .. 8 -- criterion n tags the cells of level lev where tag_gt < value < tag_lt (a side without a key is open; a
+    level without a key repeats the last level given).  Returns the list VardenAMR takes as tag_criteria, or None when no such key is present."""
+    from .capi import MAXLEV, TAG_FIELDS, TAG_MAX_CRITERIA
+    found = {}
+    for key, v in nl.items():
+        m = re.fullmatch(r"tag_(field|comp)\((\d+)\)|tag_(gt|lt)\((\d+),(\d+)\)", key)
+        if not m:
+            if key.startswith("tag_"):
+                raise ValueError("inputs: %s: the tagging keys are tag_field(n), tag_comp(n), tag_gt(n,lev), tag_lt(n,lev)" % key)
+            continue
+        n = int(m.group(2) or m.group(4))
+        if not 1 <= n <= TAG_MAX_CRITERIA:
+            raise ValueError("inputs: %s: criteria are numbered 1 .. %d" % (key, TAG_MAX_CRITERIA))
+        c = found.setdefault(n, dict(gt={}, lt={}))
+        if m.group(1):
+            c[m.group(1)] = v
+        else:
+            if not 1 <= int(m.group(5)) <= MAXLEV:
+                raise ValueError("inputs: %s: levels are numbered 1 .. %d" % (key, MAXLEV))
+            c[m.group(3)][int(m.group(5))] = float(v)
+    if not found:
+        return None
+    out = []
+    for n in sorted(found):
+        c = found[n]
+        if "field" not in c:
+            raise ValueError("inputs: criterion %d has thresholds but no tag_field(%d)" % (n, n))
+        if c["field"] not in TAG_FIELDS:
+            raise ValueError("inputs: tag_field(%d) = %r: one of %s" % (n, c["field"], ", ".join(TAG_FIELDS)))
+        crit = dict(field=str(c["field"]), comp=int(c.get("comp", 1)))
+        for side in ("gt", "lt"):
+            if c[side]:
+                vals, last = [], None
+                for lev in range(1, max(c[side]) + 1):
+                    if lev in c[side]:
+                        last = c[side][lev]
+                    elif last is None:
+                        raise ValueError("inputs: tag_%s(%d,%d) is missing (levels are given from 1 up)" % (side, n, lev))
+                    vals.append(last)
+                crit[side] = vals
+        out.append(crit)
     return out
 
 
@@ -76,6 +122,8 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
                   init_iter=int(nl["init_iter"]), do_initial_projection=int(nl["do_initial_projection"]), device=device,
                   fixed_dt=float(nl["fixed_dt"]), stop_time=float(nl["stop_time"]))
     decomp = tuple(max(1, -(-n[d] // mgs)) for d in range(dm)) + (1,) * (3 - dm)
+    tagc = namelist_tag_criteria(nl)
+    amr = dict(tag_criteria=tagc) if tagc is not None else {}       # (without the keys: the calls as they were)
 
     def copy_of_2d(boxes2d, **kw):
         """a 2-D hierarchy on the box lists of a dm = 2 checkpoint or grids file, as the z-uniform copy: plotfile.extrude_boxes, extrude_nz << n cells along z on level n"""
@@ -83,7 +131,7 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
             raise NotImplementedError("2-D hierarchies: prob_hi_x = 1 and square cells")
         b3 = [plotfile.extrude_boxes(b, int(extrude_nz) << lev, mgs) for lev, b in enumerate(boxes2d)]
         G = VardenAMR(n, b3[1], phys, params=params_of_copy(), finer_levels=b3[2:], base_boxes=b3[0], regrid_int=int(nl["regrid_int"]), amr_buf_width=abw,
-                      max_levs=max(int(nl["max_levs"]), len(b3)), max_grid_size=mgs, extrude2d=int(extrude_nz), extrude_zbc=extrude_zbc, **common, **kw)
+                      max_levs=max(int(nl["max_levs"]), len(b3)), max_grid_size=mgs, extrude2d=int(extrude_nz), extrude_zbc=extrude_zbc, **common, **amr, **kw)
         G.files_copy = files == "copy"
         return G
 
@@ -105,7 +153,7 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
                                           "checkpoints are read back" % (chk["name"], chk["dm"]))
             return nl, copy_of_2d(chk["boxes"], **rs)
         return nl, VardenAMR(n[0], chk["boxes"][1], phys, params=prm, finer_levels=chk["boxes"][2:], base_boxes=chk["boxes"][0],
-                             regrid_int=int(nl["regrid_int"]), amr_buf_width=abw, max_levs=int(nl["max_levs"]), max_grid_size=mgs, **common, **rs)
+                             regrid_int=int(nl["regrid_int"]), amr_buf_width=abw, max_levs=int(nl["max_levs"]), max_grid_size=mgs, **common, **amr, **rs)
     if nl["fixed_grids"]:                                   # initialize_with_fixed_grids, src/initialize.f90:93-150
         if dm == 2:                                         # (a grids file of write_grids: the footprints, dm = 2)
             domains, boxes = plotfile.read_grids(os.path.join(outdir, str(nl["fixed_grids"])))
@@ -120,7 +168,7 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
         if len(boxes) == 1:
             raise NotImplementedError("fixed_grids with one level: use max_grid_size")
         return nl, VardenAMR(n[0], boxes[1], phys, params=prm, finer_levels=boxes[2:], base_boxes=boxes[0], regrid_int=int(nl["regrid_int"]), amr_buf_width=abw,
-                             max_levs=max(int(nl["max_levs"]), len(boxes)), max_grid_size=mgs, **common)
+                             max_levs=max(int(nl["max_levs"]), len(boxes)), max_grid_size=mgs, **common, **amr)
     if int(nl["max_levs"]) <= 1:
         return nl, Varden(n, phys, prm, prob_hi=prob_hi, decomp=decomp, **common)
     if dm == 2:
@@ -136,11 +184,11 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
             base = [((kx * bs[0], ky * bs[1], kz * bs[2]), ((kx + 1) * bs[0] - 1, (ky + 1) * bs[1] - 1, (kz + 1) * bs[2] - 1))
                     for kz in range(nz // bs[2]) for ky in range(decomp[1]) for kx in range(decomp[0])]
         levels = VardenAMR.tagged_grids(n, phys, prm3, prob_type=int(nl["prob_type"]), max_levs=int(nl["max_levs"]), buf_wid=abw, max_grid_size=mgs, device=device,
-                                        base_boxes=base, extrude2d=nz)
+                                        base_boxes=base, extrude2d=nz, **amr)
         if not levels:
             return nl, Varden(n, phys, prm, prob_hi=prob_hi, decomp=decomp, **common)
         G = VardenAMR(n, levels[0], phys, params=prm3, finer_levels=levels[1:], regrid_int=int(nl["regrid_int"]), amr_buf_width=abw,
-                      max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, extrude2d=nz, extrude_zbc=extrude_zbc, **common)
+                      max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, extrude2d=nz, extrude_zbc=extrude_zbc, **common, **amr)
         G.files_copy = files == "copy"
         return nl, G
     if len(set(n)) != 1 or any(p != 1.0 for p in prob_hi):
@@ -152,11 +200,11 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
         base = [((kx * bs[0], ky * bs[1], kz * bs[2]), ((kx + 1) * bs[0] - 1, (ky + 1) * bs[1] - 1, (kz + 1) * bs[2] - 1))
                 for kz in range(decomp[2]) for ky in range(decomp[1]) for kx in range(decomp[0])]
     levels = VardenAMR.tagged_grids(n[0], phys, prm, prob_type=int(nl["prob_type"]), max_levs=int(nl["max_levs"]),
-                                    buf_wid=abw, max_grid_size=mgs, device=device, base_boxes=base)
+                                    buf_wid=abw, max_grid_size=mgs, device=device, base_boxes=base, **amr)
     if not levels:
         return nl, Varden(n, phys, prm, prob_hi=prob_hi, decomp=decomp, **common)
     return nl, VardenAMR(n[0], levels[0], phys, params=prm, finer_levels=levels[1:], regrid_int=int(nl["regrid_int"]), amr_buf_width=abw,
-                         max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, **common)
+                         max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, **common, **amr)
 
 
 def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane"):
