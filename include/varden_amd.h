@@ -347,6 +347,32 @@ int vdn_make_new_grids_by(const vdn_multifab *s, vdn_multifab *u, const double *
 int vdn_make_vorticity(vdn_multifab *vort, int comp, vdn_multifab *u, const double *dx /*[dm]*/, const vdn_bc_tower *bct);
 int vdn_make_magvel(vdn_multifab *magvel, int comp, vdn_multifab *u);
 
+/* ---- run diagnostics on the device: integrals, extrema and a finite check over the composite grid ------------------------------------
+ * No reference counterpart (multifab_min_c / max_c of src/hgproject.f90:89-95 is the nearest).  Every quantity runs over the COMPOSITE grid -- the valid
+ * cells of level n that no box of level n + 1 covers -- and every cell is weighted by its own dx dy dz (dm = 2: dx dy, one z plane).  u[nlev], s[nlev]: the
+ * velocity and the scalars of every level on the layout mla; dx: [nlev][3].  Component 0 of s is the density.
+ *   counts     cells, cells_lev; nonfinite: composite cells where any component of u or s is NaN or +-Inf (exact)
+ *   integrals  volume, volume_lev; sum_s[c] = int s_c dV (c = 0: the mass); momentum[d] = int rho u_d dV; kinetic = 1/2 int rho |u|^2 dV;
+ *              enstrophy = 1/2 int w^2 dV, w the value vdn_make_vorticity stores (dm = 3: |curl u|, dm = 2: v_x - u_y)
+ *   extrema    exact: the bits of a value that is in the field; -0 sorts below +0 (as in the plot files' Cell_H); magvel as vdn_make_magvel
+ * Entries beyond nscal, dm or nlev are 0.  enstrophy, vort_min and vort_max are computed only with VDN_DIAG_VORT in `what` (0 otherwise); they read ONE GHOST
+ * LAYER of u and, unlike vdn_make_vorticity, the call FILLS NOTHING: the caller has filled it (same level, physical boundary, coarse-fine: what the drivers do at
+ * the top of every step).  Without VDN_DIAG_VORT no ghost cell is read, and bct may be NULL.  The call reads its inputs and writes none of them.
+ * Deterministic: sums are added in a fixed order (inside a slab of a box, then slab by slab in level / box / k order), never by atomics -- two calls give the
+ * same bits, every rank gets the same bits, and the bits do not depend on the number of ranks (they do depend on how a level is cut into boxes).  Collective.
+ * Refused (non-zero, vdn_last_error): nlev outside 1 .. 4 or not the layout's; u / s not on mla (or on different box lists); a NULL dx; a NULL bct or u without
+ * a ghost cell with VDN_DIAG_VORT; dm = 2 with nlev > 1. */
+#define VDN_DIAG_VORT 1
+typedef struct vdn_diag {
+  long long cells, cells_lev[4], nonfinite;
+  double volume, volume_lev[4];
+  double sum_s[11], momentum[3], kinetic, enstrophy;
+  double s_min[11], s_max[11], u_min[3], u_max[3], magvel_max, vort_min, vort_max;
+} vdn_diag;
+int vdn_diagnostics(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s,
+                    const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct, int what, vdn_diag *out);
+size_t vdn_diag_sizeof(void);
+
 /* ---- plot files and checkpoints (FBoxLib's fabio_module and the reference's checkpoint_module) ------------------------------------------------------
  * The files are the ones varden_amd/plotfile.py defines (Header, Level_NN/Cell_H with es27.17e3 numbers, Level_NN/Cell_D_00000 with a FAB line in front of
  * every fab's doubles), byte for byte.  The valid points of every fab are packed on the device into a staging buffer of `staging_bytes` (<= 0: 256 MB; neither

@@ -1,6 +1,7 @@
-"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D] [--files plane|copy]: the reference executable's command line (src/main.f90
+"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D] [--files plane|copy] [--diag-int N]: the reference executable's command line (src/main.f90
 reads the inputs file named by the first argument and calls varden()).  Plot and checkpoint files go under --outdir; a 2-D hierarchy writes the 2-D run's own
-dm = 2 files (--files copy: those of the 3-D copy it runs as)."""
+dm = 2 files (--files copy: those of the 3-D copy it runs as).  --diag-int N overrides the namelist's diag_int: a line of run diagnostics (advance.diagnostics) for the
+starting state and after every N-th step, in <outdir>/<diag_file_name>."""
 import argparse
 import os
 import time
@@ -16,6 +17,7 @@ def main():
     ap.add_argument("--outdir", default=".")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--files", choices=["plane", "copy"], default="plane", help="files of a 2-D hierarchy: the 2-D run's (plane k = 0, dm = 2) or the 3-D copy's")
+    ap.add_argument("--diag-int", type=int, default=None, help="override diag_int: run diagnostics every N steps into diag_file_name (0: none)")
     a = ap.parse_args()
     os.makedirs(a.outdir, exist_ok=True)
 
@@ -24,7 +26,7 @@ def main():
                                                                                adv.last_solver_stats("hg")[0]), flush=True)
 
     t0 = time.time()
-    nl, G = inputs.run(open(a.inputs_file).read(), a.steps, report, device=a.device, outdir=a.outdir, files=a.files)
+    nl, G = inputs.run(open(a.inputs_file).read(), a.steps, report, device=a.device, outdir=a.outdir, files=a.files, diag_int=a.diag_int)
     print("Total Run time (s) = %.3f" % (time.time() - t0))
     for f in G.files_written:
         print("wrote", f)

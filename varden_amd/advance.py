@@ -371,3 +371,38 @@ def checkpoint_write_plane(dirname, state, pressure, rr, time, dt, comps, vanish
     check(capi.load().vdn_checkpoint_write_plane(str(dirname).encode(), len(state), handle_array(state), handle_array(pressure), _rr(rr), float(time), float(dt),
                                                  int(staging_bytes), len(comps), _iv(comps), len(vanish), _iv(vanish), out))
     return out[0], out[1]
+
+
+# ---- run diagnostics ---------------------------------------------------------------------------------------------------------------------
+def diagnostics(mla, u, s, dx, bct, vort=True):
+    """vdn_diagnostics over the composite grid of the hierarchy (u, s: one multifab per level; dx: one list per level): a dict of the members of vdn_diag --
+    cells, cells_lev, nonfinite, volume, volume_lev, sum_s (sum_s[0]: the mass), momentum, kinetic, enstrophy, s_min, s_max, u_min, u_max, magvel_max,
+    vort_min, vort_max -- arrays cut to nlev, nscal and dm entries.  vort=True adds the vorticity terms (0 otherwise): they read one ghost layer of u, which the
+    CALLER has filled (the drivers' fill_state_ghosts); bct may be None without them.  Sums have a fixed order, extrema are exact: equal bits call after call and
+    on any number of ranks."""
+    lib = capi.load()
+    prm = capi.Params()
+    check(lib.vdn_get_params(C.byref(prm)))
+    nlev, dm, ns = len(u), prm.dm, prm.nscal
+    levs = dx if hasattr(dx[0], "__len__") else [dx]
+    flat = [float(v) for lev in levs for v in (list(lev) + [1.0] * 3)[:3]]
+    out = capi.Diag()
+    check(lib.vdn_diagnostics(nlev, mla.h, handle_array(u), handle_array(s), (C.c_double * len(flat))(*flat), bct.h if bct is not None else None,
+                              capi.DIAG_VORT if vort else 0, C.byref(out)))
+    cut = dict(cells_lev=nlev, volume_lev=nlev, sum_s=ns, s_min=ns, s_max=ns, momentum=dm, u_min=dm, u_max=dm)
+    return {name: (list(getattr(out, name))[:cut[name]] if name in cut else getattr(out, name)) for name, _ in capi.Diag._fields_}
+
+
+def diag_columns(nscal, dm):
+    """the columns of a diagnostics file after step, time and dt (inputs.run with diag_int > 0; varden_main writes the same): vdn_diag's members in struct
+    order without the per-level arrays, arrays cut to nscal and dm entries"""
+    cols = ["cells", "nonfinite", "volume"] + ["sum_s%d" % (c + 1) for c in range(nscal)] + ["momentum%d" % (d + 1) for d in range(dm)] + ["kinetic", "enstrophy"]
+    for name, n in (("s_min", nscal), ("s_max", nscal), ("u_min", dm), ("u_max", dm)):
+        cols += ["%s%d" % (name, c + 1) for c in range(n)]
+    return cols + ["magvel_max", "vort_min", "vort_max"]
+
+
+def diag_values(d):
+    """the figures of one diagnostics dict in diag_columns' order"""
+    return ([d["cells"], d["nonfinite"], d["volume"]] + d["sum_s"] + d["momentum"] + [d["kinetic"], d["enstrophy"]] + d["s_min"] + d["s_max"] + d["u_min"] + d["u_max"]
+            + [d["magvel_max"], d["vort_min"], d["vort_max"]])

@@ -67,6 +67,18 @@ class TagCriterion(C.Structure):
     _fields_ = [("field", C.c_int), ("comp", C.c_int), ("gt", C.c_double * MAXLEV), ("lt", C.c_double * MAXLEV)]
 
 
+DIAG_VORT = 1            # VDN_DIAG_VORT
+
+
+class Diag(C.Structure):
+    """mirror of ``vdn_diag``: what vdn_diagnostics reports over the composite grid (counts, integrals, exact extrema); entries beyond nscal, dm or nlev are 0"""
+    _fields_ = [("cells", C.c_longlong), ("cells_lev", C.c_longlong * 4), ("nonfinite", C.c_longlong),
+                ("volume", C.c_double), ("volume_lev", C.c_double * 4),
+                ("sum_s", C.c_double * 11), ("momentum", C.c_double * 3), ("kinetic", C.c_double), ("enstrophy", C.c_double),
+                ("s_min", C.c_double * 11), ("s_max", C.c_double * 11), ("u_min", C.c_double * 3), ("u_max", C.c_double * 3),
+                ("magvel_max", C.c_double), ("vort_min", C.c_double), ("vort_max", C.c_double)]
+
+
 # every symbol include/varden_amd.h declares: (restype, argtypes)
 _VP = C.c_void_p
 _PI = C.POINTER(C.c_int)
@@ -143,6 +155,8 @@ SIGNATURES = {
     "vdn_tag_boxes_by": (C.c_int, [_VP, _VP, _PD, _VP, C.c_int, C.c_int, C.POINTER(TagCriterion), C.POINTER(C.c_ubyte)]),
     "vdn_make_new_grids_by": (C.c_int, [_VP, _VP, _PD, _VP, C.c_int, C.c_int, C.POINTER(TagCriterion), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.POINTER(Box), _PI, C.POINTER(C.c_long)]),
+    "vdn_diagnostics": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_int, C.POINTER(Diag)]),
+    "vdn_diag_sizeof": (C.c_size_t, []),
     "vdn_fabio_ml_multifab_write_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PI, C.POINTER(C.c_char_p), C.POINTER(Box), _PD, _PD, C.c_double, _PD, C.c_long]),
     "vdn_fabio_ml_multifab_info": (C.c_int, [C.c_char_p, _PI, _PI, _PI, _PI, _PI, _PI, _PD]),
     "vdn_fabio_ml_multifab_boxes": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(Box), C.c_int]),

@@ -151,6 +151,15 @@ void comm_allreduce_max_u8_dev(unsigned char *d, size_t n) {
   for (size_t off = 0; off < n; off += piece)
     NCCLCHK(g_rccl.AllReduce(d + off, d + off, std::min(piece, n - off), ncclUint8, ncclMax, g_rccl.comm, ctx().stream));
 }
+// all-reduce SUM of n device doubles, in place, on the launch stream (the partials of vdn_diagnostics: every entry is non-zero on one rank at the most)
+void comm_allreduce_sum_dev(double *d, size_t n) {
+  if (!comm_active() || n == 0) return;
+  need_comm();
+  g_cstat[3]++;
+  const size_t piece = (size_t)1 << 20;      // 8 MB at a time
+  for (size_t off = 0; off < n; off += piece)
+    NCCLCHK(g_rccl.AllReduce(d + off, d + off, std::min(piece, n - off), ncclFloat64, ncclSum, g_rccl.comm, ctx().stream));
+}
 // host values (per-box minima / maxima of the plot files, barriers of the file writers): MAX over the ranks, in place
 extern "C" int vdn_comm_allreduce_max(double *host, int n) {
   VDN_TRY

@@ -198,6 +198,12 @@ class Varden:
             self.sold[0].copy_c(0, self.snew[0], 0, self.nscal, 0)
         self.time += self.dt
 
+    def diagnostics(self, vort=True):
+        """advance.diagnostics of the current state (uold, sold): integrals, exact extrema and the finite check, as a dict.  Fills the ghost cells of the state
+        first, as the next step does at its top (the vorticity reads one layer of uold)."""
+        self.fill_state_ghosts()
+        return adv.diagnostics(self.mla, self.uold, self.sold, self.dx, self.bct, vort=vort)
+
     def gather_valid(self, mf):
         """valid cells of the LOCAL boxes assembled into a global array (NaN where other ranks own the data)"""
         out = np.full(self.n + (mf.nc,), np.nan, order="F")
@@ -548,6 +554,13 @@ class VardenAMR:
             self.snew[n].copy_c(0, self.sold[n], 0, self.nscal, 3)
             self.p[n].fill_boundary()
         self.nregrids += 1
+
+    def diagnostics(self, vort=True):
+        """advance.diagnostics of the current state (uold, sold) over the composite grid, as a dict.  Fills the ghost cells of the state first, as the next step
+        does at its top (restriction, same level, physical boundary, coarse-fine).  An extruded 2-D copy reports the 3-D COPY's figures: integrals and volume carry
+        the copy's extent along z, the vorticity is the 3-D rule's |curl u|; nothing is rescaled."""
+        self.fill_state_ghosts()
+        return adv.diagnostics(self.mla, self.uold, self.sold, self.dx, self.bct, vort=vort)
 
     def slice2d(self, mfs):
         """plane k = 0 of a per-level list of cell multifabs as level-domain arrays (nx << n, ny << n, nc), NaN outside the level's boxes: the 2-D answer of an extruded run"""

@@ -56,6 +56,16 @@ module varden_amd
      real(c_double) :: gt(4), lt(4)
   end type vdn_tag_criterion
 
+  ! run diagnostics over the composite grid (include/varden_amd.h: vdn_diag, vdn_diagnostics): counts, integrals (every cell weighted by its own volume), exact
+  ! extrema; entries beyond nscal, dm or the levels of the hierarchy are 0.  VDN_DIAG_VORT: the vorticity terms (they read one ghost layer of u)
+  integer, parameter, public :: VDN_DIAG_VORT = 1
+  type, bind(C), public :: vdn_diag
+     integer(c_long_long) :: cells, cells_lev(4), nonfinite
+     real(c_double) :: volume, volume_lev(4)
+     real(c_double) :: sum_s(11), momentum(3), kinetic, enstrophy
+     real(c_double) :: s_min(11), s_max(11), u_min(3), u_max(3), magvel_max, vort_min, vort_max
+  end type vdn_diag
+
   type, public :: ml_layout
      type(c_ptr) :: h = c_null_ptr
      integer :: nlevel = 0, dim = 3
@@ -80,6 +90,7 @@ module varden_amd
   public :: ml_cc_restriction, ml_edge_restriction, multifab_fill_ghost_cells, create_umac_grown, ml_restrict_and_fill
   public :: fillpatch, ml_nodal_prolongation, multifab_copy_layouts, make_new_grids, make_vorticity, make_magvel
   public :: make_new_grids_by, tag_boxes_by, make_tag_criterion
+  public :: diagnostics
   public :: fabio_ml_multifab_write_d, fabio_ml_multifab_info, fabio_ml_multifab_boxes, fabio_ml_multifab_read_d, checkpoint_write, checkpoint_info
   public :: fabio_ml_multifab_write_plane_d, fabio_ml_multifab_read_plane_d, checkpoint_write_plane, make_vorticity_plane
 
@@ -307,6 +318,17 @@ module varden_amd
        integer(c_int), value :: lev1, ncrit
        type(vdn_tag_criterion), intent(in) :: crit(*)
        integer(c_signed_char), intent(out) :: tags_host(*)
+     end function
+     integer(c_int) function vdn_diagnostics(nlev, mla, u, s, dx, bct, what, out) bind(C, name="vdn_diagnostics")
+       import :: c_int, c_ptr, c_double, vdn_diag
+       integer(c_int), value :: nlev, what
+       type(c_ptr), value :: mla, bct
+       type(c_ptr), intent(in) :: u(*), s(*)
+       real(c_double), intent(in) :: dx(*)
+       type(vdn_diag), intent(out) :: out
+     end function
+     integer(c_size_t) function vdn_diag_sizeof() bind(C, name="vdn_diag_sizeof")
+       import :: c_size_t
      end function
      ! plot files and checkpoints inside the library (include/varden_amd.h; csrc/fabio.hip); optional C arguments travel as addresses (c_null_ptr: the default)
      integer(c_int) function vdn_fabio_ml_multifab_write_d(dirname, nlev, mfs, rr, names, pd0, prob_lo, prob_hi, time, dx0, staging_bytes) &
@@ -745,6 +767,31 @@ contains
     d = 1.0_c_double; d(1:2) = dx(1:2)
     call chk(vdn_make_vorticity_plane(vort%h, int(comp - 1, c_int), u%h, d, the_bc_tower%h), 'make_vorticity_plane')
   end subroutine make_vorticity_plane
+  ! run diagnostics of the state (u, s) of levels 1 .. size(u) over the composite grid: see vdn_diagnostics.  vort (default .true.): the vorticity terms too -- the
+  ! CALLER has filled one ghost layer of u (same level, physical boundary, coarse-fine), as the drivers do at the top of every step; nothing is filled here
+  subroutine diagnostics(mla, u, s, dx, the_bc_tower, diag, vort)
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: u(:), s(:)
+    real(dp_t)     , intent(in   ) :: dx(:,:)
+    type(bc_tower) , intent(in   ) :: the_bc_tower
+    type(vdn_diag) , intent(  out) :: diag
+    logical, intent(in), optional  :: vort
+    real(c_double) :: dxc(3 * size(u))
+    integer :: n, d
+    integer(c_int) :: what
+    if (vdn_diag_sizeof() /= c_sizeof(diag)) error stop 'diagnostics: vdn_diag differs between the library and this module'
+    what = VDN_DIAG_VORT
+    if (present(vort)) then
+       if (.not. vort) what = 0
+    end if
+    dxc = 1.0_c_double
+    do n = 1, size(u)
+       do d = 1, min(3, size(dx, 2))
+          dxc((n - 1) * 3 + d) = dx(n, d)
+       end do
+    end do
+    call chk(vdn_diagnostics(int(size(u), c_int), mla%h, handles(u), handles(s), dxc, the_bc_tower%h, what, diag), 'diagnostics')
+  end subroutine diagnostics
   subroutine make_magvel(magvel, comp, u)
     type(multifab), intent(inout) :: magvel, u
     integer       , intent(in   ) :: comp

@@ -39,11 +39,17 @@ program varden_main
   real(dp_t) :: tag_gt(8,4) = TAG_UNSET, tag_lt(8,4) = TAG_UNSET
   type(vdn_tag_criterion) :: crit(8)
   integer :: ncrit = 0
+  ! ---- run diagnostics (the project's own keys too): diag_int > 0 writes one header line into diag_file_name, then one line for the state the run starts from and
+  ! one after every diag_int-th step -- step, time, dt, cells, nonfinite, volume, then the integrals and the extrema of vdn_diag (varden_amd_mod: diagnostics) with
+  ! es27.17e3 numbers: the file varden_amd/inputs.py writes, character for character.  0 (default): no call, no file
+  integer :: diag_int = 0
+  character(len=128) :: diag_file_name = 'varden_diag.out'
   namelist /probin/ dim_in, nscal, prob_type, boussinesq, max_step, max_levs, max_grid_size, regrid_int, amr_buf_width, n_cellx, n_celly, n_cellz, &
        init_iter, do_initial_projection, diffusion_type, slope_order, use_minion, stencil_order, verbose, mg_verbose, plot_int, chk_int, restart, ref_ratio, &
        bcx_lo, bcx_hi, bcy_lo, bcy_hi, bcz_lo, bcz_hi, cluster_min_width, cluster_blocking_factor, grav, stop_time, prob_hi_x, prob_hi_y, prob_hi_z, &
        prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc, &
-       plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels, tag_field, tag_comp, tag_gt, tag_lt
+       plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels, tag_field, tag_comp, tag_gt, tag_lt, &
+       diag_int, diag_file_name
 
   ! one hierarchy: box lists, layout, boundary tower and the four multifabs regridding carries (regrid.f90:60-75)
   type hier
@@ -186,6 +192,11 @@ program varden_main
      call dump(.false.)                                            ! varden.f90:207-221
   end if
 
+  if (diag_int > 0) then
+     call write_diag_header()
+     call write_diag()
+  end if
+
   ! ---- time loop (varden.f90:237-345) ----
   nregrids = 0
   do while (istep < max_step .and. (stop_time < 0.d0 .or. time < stop_time))
@@ -213,6 +224,9 @@ program varden_main
      time = time + dt
      write(*, '(a,i5,a,es25.17,a,es25.17,a,es25.17,a,i2,a,4i6)') ' step ', istep, '  time ', time, '  dt ', dt, '  |u|max ', umax, &
           '  levels ', H%nlev, '  boxes ', H%nb
+     if (diag_int > 0) then
+        if (mod(istep, diag_int) == 0) call write_diag()
+     end if
      call dump(.false.)                                            ! varden.f90:349-361
   end do
   if (istep > max(restart, 0)) call dump(.true.)                  ! varden.f90:374-377
@@ -223,6 +237,45 @@ program varden_main
   call varden_amd_finalize()
 
 contains
+
+  ! the header line of the diagnostics file: '#', the column names right-justified to the widths of the data lines (inputs.py: diag_header)
+  subroutine write_diag_header()
+    integer :: u, c
+    open(newunit=u, file=trim(diag_file_name), status='replace', action='write')
+    write(u, '(a)', advance='no') '#   step' // adjustr(wide('time')) // adjustr(wide('dt')) // '           cells       nonfinite' // adjustr(wide('volume'))
+    call names('sum_s', nscal); call names('momentum', dm)
+    write(u, '(a)', advance='no') adjustr(wide('kinetic')) // adjustr(wide('enstrophy'))
+    call names('s_min', nscal); call names('s_max', nscal); call names('u_min', dm); call names('u_max', dm)
+    write(u, '(a)') adjustr(wide('magvel_max')) // adjustr(wide('vort_min')) // adjustr(wide('vort_max'))
+    close(u)
+  contains
+    function wide(s) result(w)
+      character(len=*), intent(in) :: s
+      character(len=27) :: w
+      w = s
+    end function wide
+    subroutine names(base, cnt)
+      character(len=*), intent(in) :: base
+      integer, intent(in) :: cnt
+      character(len=27) :: w
+      do c = 1, cnt
+         write(w, '(a,i0)') base, c
+         write(u, '(a)', advance='no') adjustr(w)
+      end do
+    end subroutine names
+  end subroutine write_diag_header
+
+  ! one data line: the diagnostics of the current state (H%uold, H%sold), ghost cells filled as the next step fills them (inputs.py: diag_line)
+  subroutine write_diag()
+    type(vdn_diag) :: d
+    integer :: u
+    call fill_state_ghosts()
+    call diagnostics(H%mla, H%uold(1:H%nlev), H%sold(1:H%nlev), dx(1:H%nlev,:), H%bct, d)
+    open(newunit=u, file=trim(diag_file_name), status='old', position='append', action='write')
+    write(u, '(i8,2es27.17e3,2i16,*(es27.17e3))') istep, time, dt, d%cells, d%nonfinite, d%volume, d%sum_s(1:nscal), d%momentum(1:dm), d%kinetic, d%enstrophy, &
+         d%s_min(1:nscal), d%s_max(1:nscal), d%u_min(1:dm), d%u_max(1:dm), d%magvel_max, d%vort_min, d%vort_max
+    close(u)
+  end subroutine write_diag
 
   ! plot file and checkpoint after every plot_int-th / chk_int-th step; final: the last step once more if it has not been written
   subroutine dump(final)

@@ -5,6 +5,7 @@ continues from chk<n> (src/varden.f90:94-97, 207-229, 349-361)."""
 import os
 import re
 
+from . import advance as adv
 from . import boxlib as bl
 from . import plotfile
 from .capi import default_params
@@ -17,7 +18,8 @@ DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step
                 diffusion_type=1, slope_order=4, use_minion=0, stencil_order=2, verbose=0, mg_verbose=0,
                 mg_bottom_solver=-1, hg_bottom_solver=-1, max_mg_bottom_nlevels=1000,
                 bcx_lo=14, bcx_hi=14, bcy_lo=14, bcy_hi=14, bcz_lo=14, bcz_hi=14,
-                fixed_dt=-1.0, plot_int=0, chk_int=0, restart=-1, plot_base_name="plt", check_base_name="chk", grids_file_name="", job_name="", fixed_grids="")
+                fixed_dt=-1.0, plot_int=0, chk_int=0, restart=-1, plot_base_name="plt", check_base_name="chk", grids_file_name="", job_name="", fixed_grids="",
+                diag_int=0, diag_file_name="varden_diag.out")          # (the last two are the project's own keys, like tag_field)
 
 
 def parse_namelist(text):
@@ -207,9 +209,22 @@ def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, ext
                          max_levs=int(nl["max_levs"]), max_grid_size=mgs, base_boxes=base, **common, **amr)
 
 
-def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane"):
+def diag_header(nscal, dm):
+    """the header line of a diagnostics file"""
+    return "#" + "step".rjust(7) + "".join(c.rjust(27) for c in ["time", "dt"]) + "".join(c.rjust(16 if c in ("cells", "nonfinite") else 27) for c in adv.diag_columns(nscal, dm)) + "\n"
+
+
+def diag_line(istep, time, dt, d):
+    """one data line of a diagnostics file: step (i8), time, dt, cells and nonfinite (i16), then volume, the integrals and the extrema (es27.17e3)"""
+    v = adv.diag_values(d)
+    return "%8d" % istep + plotfile._es(time) + plotfile._es(dt) + "%16d%16d" % (v[0], v[1]) + "".join(plotfile._es(x) for x in v[2:]) + "\n"
+
+
+def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None):
     """the time loop of src/varden.f90:237-371 for max_step steps (or until stop_time); plot / checkpoint files at step 0 of a fresh
-    run and after every plot_int-th / chk_int-th step (:207-221, :349-361) under outdir"""
+    run and after every plot_int-th / chk_int-th step (:207-221, :349-361) under outdir.  diag_int > 0 (the namelist's key, or the argument over it): the run
+    diagnostics of the state the run starts from and after every diag_int-th step, one line each under a header line, in <outdir>/<diag_file_name>; 0: no
+    call, no file"""
     nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz, files=files)
     max_step = int(nl["max_step"]) if nsteps is None else nsteps
     stop_time = float(nl["stop_time"])
@@ -232,6 +247,17 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             G.files_written.append(plotfile.write_checkfile(G, base=os.path.join(outdir, str(nl["check_base_name"]))))
             last["chk"] = G.istep
 
+    diag_int = int(nl["diag_int"]) if diag_int is None else int(diag_int)
+    diag_path = os.path.join(outdir, str(nl["diag_file_name"]))
+
+    def diag():
+        with open(diag_path, "a") as f:
+            f.write(diag_line(G.istep, G.time, G.dt, G.diagnostics()))
+
+    if diag_int > 0:
+        with open(diag_path, "w") as f:
+            f.write(diag_header(G.nscal, G.dm))
+        diag()
     if int(nl["restart"]) < 0:
         dump()
     while G.istep < max_step and (stop_time < 0 or G.time < stop_time):
@@ -241,6 +267,8 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             plotfile.write_grids(grids_file, G, G.istep)
         if report:
             report(G)
+        if diag_int > 0 and G.istep % diag_int == 0:
+            diag()
         dump()
     if G.istep > (int(nl["restart"]) if int(nl["restart"]) >= 0 else 0):
         dump(final=True)
