@@ -373,6 +373,49 @@ int vdn_diagnostics(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multi
                     const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct, int what, vdn_diag *out);
 size_t vdn_diag_sizeof(void);
 
+/* ---- values at points and Lagrangian tracer particles (csrc/particles.hip, csrc/particle_plan.h).  No reference counterpart -------------
+ * Positions are physical, measured from the domain's low corner (prob_lo = 0); level l has spacing dx[l][d]; dm = 2 uses x and y (z is stored as 0).  The
+ * domain's extent is len_d = ncells_d(level 0) * dx[0][d]; a point is inside when 0 <= x_d <= len_d in every direction.
+ * Host cell and level: on level l the cell of a point is c_d = floor(x_d / dx[l][d]) (a true division), clamped to the level's domain, so that a point on the
+ * high domain face belongs to the last cell.  The host level is the FINEST level with a box whose valid region holds that cell (one lookup per level in a map
+ * over blocks, csrc/particle_plan.h; never a loop over boxes).
+ * Interpolation, trilinear (bilinear in dm = 2): xi_d = x_d / dx_d - 0.5, i_d = floor(xi_d), w_d = xi_d - i_d; the eight cells i_d, i_d + 1 are read from the
+ * HOST BOX's own fab -- at most one ghost layer, which the CALLER has filled (the call fills nothing) --; seven lerps a + w (b - a), along x, then y, then z.
+ * Face values: where the adv boundary type of component bccomp + c at a domain face is VDN_EXT_DIR the ghost cell holds the value ON the face (multifab_physbc's
+ * convention); in the half cell next to such a face the weight along that direction is 2 xi_d + 1 (low face, i_d = lo - 1) or 2 w_d (high face, i_d = hi), for
+ * that component alone.  Every other ghost value counts as cell-centred.
+ * Move (Heun between two time levels): k1 = u0(x); x* = bc(x + dt k1); k2 = u1(x*); x' = bc(x + (0.5 dt)(k1 + k2)).  bc, per direction: periodic -- p + len
+ * below 0, p - len from len on; SLIP_WALL, NO_SLIP_WALL, SYMMETRY -- -p below 0, len - (p - len) above len; then (both) clamped to [0, len]; INLET, OUTLET --
+ * crossed by x*: k2 := k1; crossed by x': the particle keeps its position, gets state 1 ("left") and is never sampled (value 0, level -1) or moved again.
+ * Particles keep their index.  Several ranks: every rank holds all particles, evaluates those whose host box it owns, writes +0.0 for the rest, and one sum
+ * all-reduce per stage fills them in (x + 0 + ... + 0 = x): the same bits on any number of ranks.  The calls are collective.
+ * Every call refuses (non-zero, vdn_last_error, nothing left allocated): an uninitialised library, null arguments, nlev other than the layout's, multifabs not
+ * on mla / nodal / with fewer than comp + nc components / without a ghost layer, a null bct or dx, n < 1, dm = 2 with nlev > 1, a level whose block map would
+ * exceed 2^25 entries (level and block size named), a face type without a rule. */
+typedef struct vdn_particles vdn_particles;
+/* mf's components comp .. comp + nc - 1 (nc <= 16) at n points: val_host[n][nc], lev_host[n] (may be NULL) = the host level; a point outside the domain (or not
+ * finite) gets level -1 and value 0 */
+int vdn_sample_points(int nlev, vdn_layout *mla, vdn_multifab *const *mf, int comp, int nc, int bccomp, const double *dx /*[nlev][3]*/,
+                      const vdn_bc_tower *bct, long n, const double *x_host /*[n][3]*/, double *val_host /*[n][nc]*/, int *lev_host /*[n]*/);
+/* n particles at x_host[n][3], state 0.  Refuses a non-finite position here; a position outside the domain at the first call that names the hierarchy */
+int vdn_particles_create(long n, const double *x_host /*[n][3]*/, vdn_particles **P);
+int vdn_particles_destroy(vdn_particles *P);
+/* n: the particles; active: those with state 0 (either may be NULL) */
+int vdn_particles_count(vdn_particles *P, long *n, long *active);
+/* positions x_host[n][3] and states state_host[n] (either may be NULL) */
+int vdn_particles_get(vdn_particles *P, double *x_host, int *state_host);
+/* one move; u0, u1: the velocity (components 0 .. dm-1, boundary components 0 .. dm-1) at the old and the new time, ghost cells filled */
+int vdn_particles_advance(vdn_particles *P, int nlev, vdn_layout *mla, vdn_multifab *const *u0, vdn_multifab *const *u1,
+                          const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct, double dt);
+/* vdn_sample_points at the particles' positions, which stay on the device; a particle that left gets value 0 and level -1 */
+int vdn_particles_sample(vdn_particles *P, int nlev, vdn_layout *mla, vdn_multifab *const *mf, int comp, int nc, int bccomp,
+                         const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct, double *val_host /*[n][nc]*/, int *lev_host /*[n], may be NULL*/);
+/* one file (rank 0 writes): the text lines "VDN_PARTICLES 1", "dm D", "n N", "ncol C", the C names (one word each), "time T" (17 significant digits), then
+ * little-endian int32 state[n], float64 x[n][3], float64 cols[ncol][n].  read: positions and states (the columns are the caller's to parse); a read followed
+ * by a write of the same columns gives the same bytes.  read refuses a file that is short, has another first line, or another dm than the run */
+int vdn_particles_write(vdn_particles *P, const char *path, double time, int ncol, const char *const *names, const double *cols /*[ncol][n]*/);
+int vdn_particles_read(const char *path, vdn_particles **P, double *time);
+
 /* ---- plot files and checkpoints (FBoxLib's fabio_module and the reference's checkpoint_module) ------------------------------------------------------
  * The files are the ones varden_amd/plotfile.py defines (Header, Level_NN/Cell_H with es27.17e3 numbers, Level_NN/Cell_D_00000 with a FAB line in front of
  * every fab's doubles), byte for byte.  The valid points of every fab are packed on the device into a staging buffer of `staging_bytes` (<= 0: 256 MB; neither

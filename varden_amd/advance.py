@@ -406,3 +406,131 @@ def diag_values(d):
     """the figures of one diagnostics dict in diag_columns' order"""
     return ([d["cells"], d["nonfinite"], d["volume"]] + d["sum_s"] + d["momentum"] + [d["kinetic"], d["enstrophy"]] + d["s_min"] + d["s_max"] + d["u_min"] + d["u_max"]
             + [d["magvel_max"], d["vort_min"], d["vort_max"]])
+
+
+# ---- values at points and tracer particles (csrc/particles.hip; include/varden_amd.h states the definitions) ------------------------------
+def _dx3(dx):
+    levs = dx if hasattr(dx[0], "__len__") else [dx]
+    flat = [float(v) for lev in levs for v in (list(lev) + [1.0] * 3)[:3]]
+    return (C.c_double * len(flat))(*flat)
+
+
+def _points(x):
+    """positions as a contiguous (n, 3) float64 array; (n, 2) input gets z = 0"""
+    import numpy as np
+    a = np.atleast_2d(np.asarray(x, dtype=np.float64))
+    if a.ndim != 2 or a.shape[1] not in (2, 3):
+        raise ValueError("positions: an (n, 2) or (n, 3) array, got shape %r" % (a.shape,))
+    if a.shape[1] == 2:
+        a = np.concatenate([a, np.zeros((a.shape[0], 1))], axis=1)
+    return np.ascontiguousarray(a)
+
+
+def sample_points(mla, mf, x, dx, bct, comp=0, nc=None, bccomp=0):
+    """vdn_sample_points: components comp .. comp + nc - 1 of the cell-centred multifabs mf (one per level, ghost cells filled by the caller) at the physical
+    points x (n, 3): (values (n, nc), host level (n,)); a point outside the domain has level -1 and value 0.  bccomp: the bc tower component of `comp`
+    (0 for the velocity, dm for the scalars).  Collective."""
+    import numpy as np
+    pts = _points(x)
+    nc = mf[0].nc - comp if nc is None else int(nc)
+    val = np.zeros((pts.shape[0], nc))
+    lev = np.zeros(pts.shape[0], dtype=np.int32)
+    check(capi.load().vdn_sample_points(len(mf), mla.h, handle_array(mf), comp, nc, bccomp, _dx3(dx), bct.h if bct is not None else None, pts.shape[0],
+                                        pts.ctypes.data_as(C.POINTER(C.c_double)), val.ctypes.data_as(C.POINTER(C.c_double)),
+                                        lev.ctypes.data_as(C.POINTER(C.c_int))))
+    return val, lev
+
+
+class Particles:
+    """Lagrangian tracer particles on the device (vdn_particles_*): created at the physical positions x0 (n, 3), moved by `advance` (Heun between two velocity
+    fields), never reordered.  state 0: active; 1: left through an inlet or outlet face (frozen at its last position inside)."""
+
+    def __init__(self, x0=None, _handle=None):
+        self.h = C.c_void_p()
+        if _handle is not None:
+            self.h = _handle
+            return
+        pts = _points(x0)
+        check(capi.load().vdn_particles_create(pts.shape[0], pts.ctypes.data_as(C.POINTER(C.c_double)), C.byref(self.h)))
+
+    def _count(self):
+        n, a = C.c_long(), C.c_long()
+        check(capi.load().vdn_particles_count(self.h, C.byref(n), C.byref(a)))
+        return n.value, a.value
+
+    @property
+    def n(self):
+        return self._count()[0]
+
+    @property
+    def active(self):
+        return self._count()[1]
+
+    def positions(self):
+        import numpy as np
+        x = np.zeros((self.n, 3))
+        check(capi.load().vdn_particles_get(self.h, x.ctypes.data_as(C.POINTER(C.c_double)), None))
+        return x
+
+    def state(self):
+        import numpy as np
+        s = np.zeros(self.n, dtype=np.int32)
+        check(capi.load().vdn_particles_get(self.h, None, s.ctypes.data_as(C.POINTER(C.c_int))))
+        return s
+
+    def advance(self, mla, u0, u1, dx, bct, dt):
+        """one move from the velocity u0 (old time) to u1 (new time), both with their ghost cells filled"""
+        check(capi.load().vdn_particles_advance(self.h, len(u0), mla.h, handle_array(u0), handle_array(u1), _dx3(dx), bct.h if bct is not None else None, float(dt)))
+
+    def sample(self, mla, mf, dx, bct, comp=0, nc=None, bccomp=0, levels=False):
+        """sample_points at the particles' positions (which stay on the device): values (n, nc); levels=True: (values, host levels)"""
+        import numpy as np
+        n = self.n
+        nc = mf[0].nc - comp if nc is None else int(nc)
+        val = np.zeros((n, nc))
+        lev = np.zeros(n, dtype=np.int32)
+        check(capi.load().vdn_particles_sample(self.h, len(mf), mla.h, handle_array(mf), comp, nc, bccomp, _dx3(dx), bct.h if bct is not None else None,
+                                               val.ctypes.data_as(C.POINTER(C.c_double)), lev.ctypes.data_as(C.POINTER(C.c_int))))
+        return (val, lev) if levels else val
+
+    def write(self, path, time=0.0, columns=None):
+        """one particle file: header, states, positions and the named columns (a dict name -> (n,) array, kept in its order)"""
+        import numpy as np
+        columns = columns or {}
+        names = [str(k) for k in columns]
+        cols = np.ascontiguousarray(np.array([np.asarray(columns[k], dtype=np.float64).ravel() for k in columns]).reshape(len(names), self.n if names else 0))
+        nm = (C.c_char_p * max(1, len(names)))(*[k.encode() for k in names])
+        check(capi.load().vdn_particles_write(self.h, str(path).encode(), float(time), len(names), nm if names else None,
+                                              cols.ctypes.data_as(C.POINTER(C.c_double)) if names else None))
+
+    @staticmethod
+    def read(path):
+        """(particles, time, columns) of a particle file; the columns are parsed here, positions and states by the library"""
+        import numpy as np
+        h, t = C.c_void_p(), C.c_double()
+        check(capi.load().vdn_particles_read(str(path).encode(), C.byref(h), C.byref(t)))
+        P = Particles(_handle=h)
+        raw = open(str(path), "rb").read()
+        lines = raw.split(b"\n", 4)
+        n, ncol = int(lines[2].split()[1]), int(lines[3].split()[1])
+        rest = lines[4].split(b"\n", ncol + 1)
+        names = [s.decode() for s in rest[:ncol]]
+        data = rest[ncol + 1][4 * n + 24 * n:]
+        cols = np.frombuffer(data, dtype="<f8", count=ncol * n).reshape(ncol, n)
+        return P, t.value, {k: cols[i].copy() for i, k in enumerate(names)}
+
+    def destroy(self):
+        if self.h:
+            capi.load().vdn_particles_destroy(self.h)
+            self.h = None
+
+
+def particle_lattice(nxyz, prob_hi):
+    """the centres of an even nx x ny x nz lattice over the domain (0 .. prob_hi), x fastest: (n, 3); a 2-D domain (two extents) takes nx x ny, z = 0"""
+    import numpy as np
+    dm = len(prob_hi)
+    ax = [(np.arange(int(nxyz[d])) + 0.5) * (float(prob_hi[d]) / int(nxyz[d])) for d in range(dm)]
+    if dm == 2:
+        ax.append(np.zeros(1))
+    Z, Y, X = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=1)

@@ -157,6 +157,15 @@ SIGNATURES = {
                                         C.c_int, C.POINTER(Box), _PI, C.POINTER(C.c_long)]),
     "vdn_diagnostics": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_int, C.POINTER(Diag)]),
     "vdn_diag_sizeof": (C.c_size_t, []),
+    "vdn_sample_points": (C.c_int, [C.c_int, _VP, _PVP, C.c_int, C.c_int, C.c_int, _PD, _VP, C.c_long, _PD, _PD, _PI]),
+    "vdn_particles_create": (C.c_int, [C.c_long, _PD, _PVP]),
+    "vdn_particles_destroy": (C.c_int, [_VP]),
+    "vdn_particles_count": (C.c_int, [_VP, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "vdn_particles_get": (C.c_int, [_VP, _PD, _PI]),
+    "vdn_particles_advance": (C.c_int, [_VP, C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_double]),
+    "vdn_particles_sample": (C.c_int, [_VP, C.c_int, _VP, _PVP, C.c_int, C.c_int, C.c_int, _PD, _VP, _PD, _PI]),
+    "vdn_particles_write": (C.c_int, [_VP, C.c_char_p, C.c_double, C.c_int, C.POINTER(C.c_char_p), _PD]),
+    "vdn_particles_read": (C.c_int, [C.c_char_p, _PVP, _PD]),
     "vdn_fabio_ml_multifab_write_d": (C.c_int, [C.c_char_p, C.c_int, _PVP, _PI, C.POINTER(C.c_char_p), C.POINTER(Box), _PD, _PD, C.c_double, _PD, C.c_long]),
     "vdn_fabio_ml_multifab_info": (C.c_int, [C.c_char_p, _PI, _PI, _PI, _PI, _PI, _PI, _PD]),
     "vdn_fabio_ml_multifab_boxes": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(Box), C.c_int]),

@@ -88,11 +88,13 @@ def _limit_dt(sim, dt, first=False):
 class Varden:
     def __init__(self, n, phys_bc, params=None, prob_type=1, grav=-9.8, prob_hi=(1.0, 1.0, 1.0), init_shrink=1.0,
                  init_iter=4, do_initial_projection=1, u0=None, s0=None, device=0, decomp=(1, 1, 1), rank=0, nranks=1,
-                 comm_id=None, restart=None, restart_step=0, fixed_dt=-1.0, stop_time=-1.0, swap_state=False, grav_dir=None, extruded2d=False):
+                 comm_id=None, restart=None, restart_step=0, fixed_dt=-1.0, stop_time=-1.0, swap_state=False, grav_dir=None, extruded2d=False, particles=None):
         """decomp = (bx, by, bz): the domain is cut into bx*by*bz equal boxes (max_grid_size of the reference,
         src/_parameters:27), dealt round-robin to the ranks (one rank per GPU).  comm_id: the 128-byte RCCL unique
         id broadcast by the caller when nranks > 1.  restart: a checkpoint read by plotfile.read_checkfile -- the state comes from it
-        and the start-up sequence (initial projection, pressure iterations) is skipped, src/varden.f90:94-97, 119, 180, 227."""
+        and the start-up sequence (initial projection, pressure iterations) is skipped, src/varden.f90:94-97, 119, 180, 227.
+        particles: physical positions (n, 3) of Lagrangian tracer particles (or an advance.Particles, e.g. read from a file), moved by every step() from uold to
+        unew (advance.Particles.advance); they rest during the start-up iterations.  None: no particle code runs."""
         self.prm = params or default_params()
         self.fixed_dt, self.stop_time = float(fixed_dt), float(stop_time)
         self.swap_state = bool(swap_state)     # uold <- unew by exchanging the handles instead of copying (see step)
@@ -108,6 +110,7 @@ class Varden:
             bl.set_extruded_2d(True)
         if nranks > 1:
             bl.comm_init(comm_id)
+        self.particles = None if particles is None else (particles if isinstance(particles, adv.Particles) else adv.Particles(particles))
         self.phys = [[int(phys_bc[d][s]) for s in range(2)] if d < dm else [bl.INTERIOR, bl.INTERIOR] for d in range(3)]
         pmask = tuple(1 if self.phys[d][0] == bl.PERIODIC else 0 for d in range(3))
         lo, hi = (0, 0, 0), tuple(x - 1 for x in self.n)
@@ -187,6 +190,11 @@ class Varden:
         if self.istep > 1:
             self.dt = _limit_dt(self, self.estdt(self.dt))
         self.advance(bl.REGULAR_TIMESTEP, self.istep)
+        if self.particles is not None:
+            # uold still holds u^n with the ghost cells filled above; unew gets the fill the next step's top repeats on the same values
+            self.unew[0].fill_boundary()
+            self.unew[0].physbc(0, 0, self.dm, self.bct)
+            self.particles.advance(self.mla, self.uold, self.unew, self.dx, self.bct, self.dt)
         if self.swap_state:
             # varden.f90:323-326 copies the valid cells; exchanging the handles gives the same next step because every ghost cell of
             # uold / sold is refilled before it is read (fill_state_ghosts above) and advance_timestep overwrites unew / snew. After such a
@@ -217,6 +225,8 @@ class Varden:
         return out
 
     def close(self):
+        if self.particles is not None:
+            self.particles.destroy()
         for lst in (self.uold, self.sold, self.unew, self.snew, self.gp, self.p, self.ext_vel_force, self.ext_scal_force):
             lst[0].destroy()
         self.bct.destroy()
@@ -297,7 +307,7 @@ class VardenAMR:
     def __init__(self, nc, fine_boxes, phys_bc, params=None, prob_type=1, grav=-9.8, init_shrink=0.1, device=0, finer_levels=(),
                  regrid_int=-1, max_levs=None, max_grid_size=256, init_iter=0, do_initial_projection=0,
                  rank=0, nranks=1, comm_id=None, base_boxes=None, init_fn=None, restart=None, restart_step=0,
-                 fixed_dt=-1.0, stop_time=-1.0, amr_buf_width=-1, swap_state=False, extrude2d=None, extrude_zbc=None, tag_criteria=None):
+                 fixed_dt=-1.0, stop_time=-1.0, amr_buf_width=-1, swap_state=False, extrude2d=None, extrude_zbc=None, tag_criteria=None, particles=None):
         """nc: cells of level 0 per direction (an int: a cube; dx = dy = dz = 1 / nc[0]).
         extrude2d = nz: a 2-D problem of nc[0] x nc[1] cells (phys_bc: its two directions) run as its z-uniform copy -- nz cells of level 0 along a periodic z, gravity along y,
         initdata_2d on every plane, velpred_2d's outlet rule (include/varden_amd.h: vdn_set_extruded_2d).  With w = 0 and nothing varying along z the 3-D scheme is the 2-D one
@@ -308,7 +318,8 @@ class VardenAMR:
         level 0 into several boxes, comm_id is the RCCL unique id broadcast by the caller; regridding is single-rank in this round.
         tag_criteria: what regridding refines on, in place of the rules of src/tag_boxes.f90 -- a list of criteria as advance.tag_criteria takes them, e.g.
         [dict(field="vorticity", gt=[8.0, 16.0])]; None: the reference's rules (which know prob_type 1 .. 3 only).  An extruded 2-D copy is a 3-D layout:
-        the 3-D vorticity rule |curl u| applies to it (equal to |v_x - u_y| away from inflow and wall faces, where the one-sided forms of makevort_3d and makevort_2d differ)."""
+        the 3-D vorticity rule |curl u| applies to it (equal to |v_x - u_y| away from inflow and wall faces, where the one-sided forms of makevort_3d and makevort_2d differ).
+        particles: as for Varden; a regrid needs nothing (the particles' box locator is rebuilt for the new layout at their next move)."""
         self.prm = params or default_params()
         self.tag_criteria = None if tag_criteria is None else adv.tag_criteria(tag_criteria)[0]
         self.grav, self.regrid_int, self.max_grid_size = grav, regrid_int, max_grid_size
@@ -330,6 +341,7 @@ class VardenAMR:
                 init_fn = extruded_initdata(prob_type, self.prm.nscal, (1.0, nc2[1] / float(nc2[0])))
         if nranks > 1:
             bl.comm_init(comm_id)
+        self.particles = None if particles is None else (particles if isinstance(particles, adv.Particles) else adv.Particles(particles))
         self.nc = nc
         self.ncs = _ncs(nc)
         self.init_fn = init_fn
@@ -459,6 +471,9 @@ class VardenAMR:
             self.dt = _limit_dt(self, self.estdt(self.dt))
         adv.advance_timestep(self.istep, self.mla, self.sold, self.uold, self.snew, self.unew, self.gp, self.p,
                              self.ext_vel_force, self.ext_scal_force, self.bct, self.dt, self.time, self.dx, self.press_comp, bl.REGULAR_TIMESTEP)
+        if self.particles is not None:               # see Varden.step
+            adv.ml_restrict_and_fill(self.unew, 0, 0, self.dm, self.bct)
+            self.particles.advance(self.mla, self.uold, self.unew, self.dx, self.bct, self.dt)
         for n in range(self.nlev):
             if self.swap_state:                      # see Varden.step
                 self.uold[n], self.unew[n] = self.unew[n], self.uold[n]
@@ -578,6 +593,8 @@ class VardenAMR:
         return out
 
     def close(self):
+        if self.particles is not None:
+            self.particles.destroy()
         for lst in (self.uold, self.sold, self.unew, self.snew, self.gp, self.p, self.ext_vel_force, self.ext_scal_force):
             for m in lst:
                 m.destroy()

@@ -80,6 +80,12 @@ module varden_amd
      type(c_ptr) :: h = c_null_ptr
   end type bc_tower
 
+  ! Lagrangian tracer particles on the device (include/varden_amd.h: vdn_particles_*; DESIGN section 21); n: their number
+  type, public :: particles
+     type(c_ptr) :: h = c_null_ptr
+     integer :: n = 0
+  end type particles
+
   public :: varden_amd_initialize, varden_amd_finalize, probin_defaults, varden_amd_set_extruded_2d
   public :: ml_layout_build, ml_layout_destroy
   public :: bc_tower_build, bc_tower_destroy
@@ -91,6 +97,7 @@ module varden_amd
   public :: fillpatch, ml_nodal_prolongation, multifab_copy_layouts, make_new_grids, make_vorticity, make_magvel
   public :: make_new_grids_by, tag_boxes_by, make_tag_criterion
   public :: diagnostics
+  public :: sample_points, particles_create, particles_destroy, particles_count, particles_get, particles_advance, particles_sample, particles_write, particles_read
   public :: fabio_ml_multifab_write_d, fabio_ml_multifab_info, fabio_ml_multifab_boxes, fabio_ml_multifab_read_d, checkpoint_write, checkpoint_info
   public :: fabio_ml_multifab_write_plane_d, fabio_ml_multifab_read_plane_d, checkpoint_write_plane, make_vorticity_plane
 
@@ -329,6 +336,70 @@ module varden_amd
      end function
      integer(c_size_t) function vdn_diag_sizeof() bind(C, name="vdn_diag_sizeof")
        import :: c_size_t
+     end function
+     ! values at points and tracer particles (include/varden_amd.h; csrc/particles.hip)
+     integer(c_int) function vdn_sample_points(nlev, mla, mf, comp, nc, bccomp, dx, bct, n, x_host, val_host, lev_host) bind(C, name="vdn_sample_points")
+       import :: c_int, c_ptr, c_double, c_long
+       integer(c_int), value :: nlev, comp, nc, bccomp
+       type(c_ptr), value :: mla, bct
+       type(c_ptr), intent(in) :: mf(*)
+       real(c_double), intent(in) :: dx(*), x_host(*)
+       integer(c_long), value :: n
+       real(c_double), intent(out) :: val_host(*)
+       integer(c_int), intent(out) :: lev_host(*)
+     end function
+     integer(c_int) function vdn_particles_create(n, x_host, P) bind(C, name="vdn_particles_create")
+       import :: c_int, c_ptr, c_double, c_long
+       integer(c_long), value :: n
+       real(c_double), intent(in) :: x_host(*)
+       type(c_ptr), intent(out) :: P
+     end function
+     integer(c_int) function vdn_particles_destroy(P) bind(C, name="vdn_particles_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: P
+     end function
+     integer(c_int) function vdn_particles_count(P, n, active) bind(C, name="vdn_particles_count")
+       import :: c_int, c_ptr, c_long
+       type(c_ptr), value :: P
+       integer(c_long), intent(out) :: n, active
+     end function
+     integer(c_int) function vdn_particles_get(P, x_host, state_host) bind(C, name="vdn_particles_get")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: P
+       real(c_double), intent(out) :: x_host(*)
+       integer(c_int), intent(out) :: state_host(*)
+     end function
+     integer(c_int) function vdn_particles_advance(P, nlev, mla, u0, u1, dx, bct, dt) bind(C, name="vdn_particles_advance")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: P, mla, bct
+       integer(c_int), value :: nlev
+       type(c_ptr), intent(in) :: u0(*), u1(*)
+       real(c_double), intent(in) :: dx(*)
+       real(c_double), value :: dt
+     end function
+     integer(c_int) function vdn_particles_sample(P, nlev, mla, mf, comp, nc, bccomp, dx, bct, val_host, lev_host) bind(C, name="vdn_particles_sample")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: P, mla, bct
+       integer(c_int), value :: nlev, comp, nc, bccomp
+       type(c_ptr), intent(in) :: mf(*)
+       real(c_double), intent(in) :: dx(*)
+       real(c_double), intent(out) :: val_host(*)
+       integer(c_int), intent(out) :: lev_host(*)
+     end function
+     integer(c_int) function vdn_particles_write(P, path, time, ncol, names, cols) bind(C, name="vdn_particles_write")
+       import :: c_int, c_ptr, c_double, c_char
+       type(c_ptr), value :: P
+       character(kind=c_char), intent(in) :: path(*)
+       real(c_double), value :: time
+       integer(c_int), value :: ncol
+       type(c_ptr), intent(in) :: names(*)
+       real(c_double), intent(in) :: cols(*)
+     end function
+     integer(c_int) function vdn_particles_read(path, P, time) bind(C, name="vdn_particles_read")
+       import :: c_int, c_ptr, c_double, c_char
+       character(kind=c_char), intent(in) :: path(*)
+       type(c_ptr), intent(out) :: P
+       real(c_double), intent(out) :: time
      end function
      ! plot files and checkpoints inside the library (include/varden_amd.h; csrc/fabio.hip); optional C arguments travel as addresses (c_null_ptr: the default)
      integer(c_int) function vdn_fabio_ml_multifab_write_d(dirname, nlev, mfs, rr, names, pd0, prob_lo, prob_hi, time, dx0, staging_bytes) &
@@ -1067,6 +1138,119 @@ contains
     nlev = nl
     rr = 2; if (nl > 1) rr(1:nl - 1) = r(1:nl - 1)
   end subroutine checkpoint_info
+
+  ! ---- values at points and tracer particles: the definitions are stated with the C entries in include/varden_amd.h.  Components are 1-based here; positions are
+  ! x(3, n), values val(nc, n), columns cols(n, ncol) ----------------------------------------------------------------------------------------------------------
+  function dx_levels(dx, nlev) result(dxc)
+    real(dp_t), intent(in) :: dx(:,:)
+    integer, intent(in) :: nlev
+    real(c_double) :: dxc(3 * nlev)
+    integer :: n, d
+    dxc = 1.0_c_double
+    do n = 1, nlev
+       do d = 1, min(3, size(dx, 2))
+          dxc((n - 1) * 3 + d) = dx(n, d)
+       end do
+    end do
+  end function dx_levels
+
+  subroutine sample_points(mla, mf, comp, nc, bccomp, dx, the_bc_tower, x, val, lev)
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: mf(:)
+    integer        , intent(in   ) :: comp, nc, bccomp
+    real(dp_t)     , intent(in   ) :: dx(:,:), x(:,:)
+    type(bc_tower) , intent(in   ) :: the_bc_tower
+    real(dp_t)     , intent(  out) :: val(:,:)
+    integer        , intent(  out) :: lev(:)
+    integer(c_int) :: levc(size(x, 2))
+    call chk(vdn_sample_points(int(size(mf), c_int), mla%h, handles(mf), int(comp - 1, c_int), int(nc, c_int), int(bccomp - 1, c_int), dx_levels(dx, size(mf)), &
+                               the_bc_tower%h, int(size(x, 2), c_long), x, val, levc), 'sample_points')
+    lev = levc
+  end subroutine sample_points
+
+  subroutine particles_create(p, x)
+    type(particles), intent(  out) :: p
+    real(dp_t)     , intent(in   ) :: x(:,:)
+    call chk(vdn_particles_create(int(size(x, 2), c_long), x, p%h), 'particles_create')
+    p%n = size(x, 2)
+  end subroutine particles_create
+
+  subroutine particles_destroy(p)
+    type(particles), intent(inout) :: p
+    call chk(vdn_particles_destroy(p%h), 'particles_destroy')
+    p%h = c_null_ptr; p%n = 0
+  end subroutine particles_destroy
+
+  function particles_count(p) result(active)
+    type(particles), intent(in) :: p
+    integer :: active
+    integer(c_long) :: n, a
+    call chk(vdn_particles_count(p%h, n, a), 'particles_count')
+    active = int(a)
+  end function particles_count
+
+  subroutine particles_get(p, x, state)
+    type(particles), intent(in   ) :: p
+    real(dp_t)     , intent(  out) :: x(:,:)
+    integer        , intent(  out) :: state(:)
+    integer(c_int) :: st(p%n)
+    call chk(vdn_particles_get(p%h, x, st), 'particles_get')
+    state = st
+  end subroutine particles_get
+
+  ! one move from the velocity u0 (old time) to u1 (new time), both with their ghost cells filled
+  subroutine particles_advance(p, mla, u0, u1, dx, the_bc_tower, dt)
+    type(particles), intent(inout) :: p
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: u0(:), u1(:)
+    real(dp_t)     , intent(in   ) :: dx(:,:), dt
+    type(bc_tower) , intent(in   ) :: the_bc_tower
+    call chk(vdn_particles_advance(p%h, int(size(u0), c_int), mla%h, handles(u0), handles(u1), dx_levels(dx, size(u0)), the_bc_tower%h, dt), 'particles_advance')
+  end subroutine particles_advance
+
+  subroutine particles_sample(p, mla, mf, comp, nc, bccomp, dx, the_bc_tower, val, lev)
+    type(particles), intent(in   ) :: p
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: mf(:)
+    integer        , intent(in   ) :: comp, nc, bccomp
+    real(dp_t)     , intent(in   ) :: dx(:,:)
+    type(bc_tower) , intent(in   ) :: the_bc_tower
+    real(dp_t)     , intent(  out) :: val(:,:)
+    integer        , intent(  out) :: lev(:)
+    integer(c_int) :: levc(p%n)
+    call chk(vdn_particles_sample(p%h, int(size(mf), c_int), mla%h, handles(mf), int(comp - 1, c_int), int(nc, c_int), int(bccomp - 1, c_int), &
+                                  dx_levels(dx, size(mf)), the_bc_tower%h, val, levc), 'particles_sample')
+    lev = levc
+  end subroutine particles_sample
+
+  ! one particle file: header, states, positions and the columns cols(n, ncol) under names(ncol) (one word each, 64 characters at the most)
+  subroutine particles_write(p, path, time, names, cols)
+    type(particles) , intent(in) :: p
+    character(len=*), intent(in) :: path, names(:)
+    real(dp_t)      , intent(in) :: time, cols(:,:)
+    character(kind=c_char), target :: cbuf(65, max(1, size(names)))
+    type(c_ptr) :: ptrs(max(1, size(names)))
+    integer :: i, j, n
+    do i = 1, size(names)
+       n = min(64, len_trim(names(i)))
+       do j = 1, n
+          cbuf(j, i) = names(i)(j:j)
+       end do
+       cbuf(n + 1, i) = c_null_char
+       ptrs(i) = c_loc(cbuf(1, i))
+    end do
+    call chk(vdn_particles_write(p%h, trim(path) // c_null_char, time, int(size(names), c_int), ptrs, cols), 'particles_write')
+  end subroutine particles_write
+
+  subroutine particles_read(path, p, time)
+    character(len=*), intent(in   ) :: path
+    type(particles) , intent(  out) :: p
+    real(dp_t)      , intent(  out) :: time
+    integer(c_long) :: n, a
+    call chk(vdn_particles_read(trim(path) // c_null_char, p%h, time), 'particles_read')
+    call chk(vdn_particles_count(p%h, n, a), 'particles_read')
+    p%n = int(n)
+  end subroutine particles_read
 
   function handles(mfs) result(h)
     type(multifab), intent(in) :: mfs(:)

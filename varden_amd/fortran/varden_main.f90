@@ -44,12 +44,19 @@ program varden_main
   ! es27.17e3 numbers: the file varden_amd/inputs.py writes, character for character.  0 (default): no call, no file
   integer :: diag_int = 0
   character(len=128) :: diag_file_name = 'varden_diag.out'
+  ! ---- Lagrangian tracer particles (the project's own keys too): particle_lattice = nx ny nz particles at the centres of an even lattice over the domain (all zero:
+  ! none -- no call, no file), moved by every step between uold and unew (varden_amd_mod: particles_advance); <particle_base_name>NNNNN with positions, states,
+  ! velocity and scalars at the particles at the start and after every particle_int-th step; a file Particles inside every checkpoint, read back by restart: the files
+  ! varden_amd/inputs.py writes, byte for byte
+  integer :: particle_lattice(3) = 0
+  integer :: particle_int = 0
+  character(len=128) :: particle_base_name = 'part'
   namelist /probin/ dim_in, nscal, prob_type, boussinesq, max_step, max_levs, max_grid_size, regrid_int, amr_buf_width, n_cellx, n_celly, n_cellz, &
        init_iter, do_initial_projection, diffusion_type, slope_order, use_minion, stencil_order, verbose, mg_verbose, plot_int, chk_int, restart, ref_ratio, &
        bcx_lo, bcx_hi, bcy_lo, bcy_hi, bcz_lo, bcz_hi, cluster_min_width, cluster_blocking_factor, grav, stop_time, prob_hi_x, prob_hi_y, prob_hi_z, &
        prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc, &
        plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels, tag_field, tag_comp, tag_gt, tag_lt, &
-       diag_int, diag_file_name
+       diag_int, diag_file_name, particle_lattice, particle_int, particle_base_name
 
   ! one hierarchy: box lists, layout, boundary tower and the four multifabs regridding carries (regrid.f90:60-75)
   type hier
@@ -75,6 +82,8 @@ program varden_main
   integer :: nnew, last_plt = -1, last_chk = -1
   real(dp_t) :: copy_defect(2) = 0.d0                             ! z-uniformity of an extruded copy as the last plane writer measured it
   logical :: new_grid
+  type(particles) :: tracers
+  logical :: have_tracers = .false.
 
   if (command_argument_count() < 1) stop 'usage: varden_main <inputs file> [max_step]'
   call get_command_argument(1, fname)
@@ -192,6 +201,7 @@ program varden_main
      call dump(.false.)                                            ! varden.f90:207-221
   end if
 
+  call start_tracers()
   if (diag_int > 0) then
      call write_diag_header()
      call write_diag()
@@ -216,6 +226,10 @@ program varden_main
      end if
      call advance_timestep(istep, H%mla, H%sold(1:H%nlev), H%uold(1:H%nlev), snew(1:H%nlev), unew(1:H%nlev), H%gp(1:H%nlev), H%p(1:H%nlev), &
                            ext_vel_force(1:H%nlev), ext_scal_force(1:H%nlev), H%bct, dt, time, dx(1:H%nlev,:), press_comp, regular_timestep)
+     if (have_tracers) then                                        ! uold still holds u^n with its ghost cells; unew gets the fill the next step's top repeats
+        call ml_restrict_and_fill(H%nlev, unew(1:H%nlev), H%bct, 1, 1, dm, .false.)
+        call particles_advance(tracers, H%mla, H%uold(1:H%nlev), unew(1:H%nlev), dx(1:H%nlev,:), H%bct, dt)
+     end if
      umax = 0.d0
      do lev = 1, H%nlev
         call multifab_copy_c(H%uold(lev), 1, unew(lev), 1, dm); call multifab_copy_c(H%sold(lev), 1, snew(lev), 1, nscal)
@@ -227,11 +241,15 @@ program varden_main
      if (diag_int > 0) then
         if (mod(istep, diag_int) == 0) call write_diag()
      end if
+     if (have_tracers .and. particle_int > 0) then
+        if (mod(istep, particle_int) == 0) call write_tracers()
+     end if
      call dump(.false.)                                            ! varden.f90:349-361
   end do
   if (istep > max(restart, 0)) call dump(.true.)                  ! varden.f90:374-377
   write(*, '(a,i4)') ' regrids: ', nregrids
 
+  if (have_tracers) call particles_destroy(tracers)
   call free_temporaries()
   call free_state(H)
   call varden_amd_finalize()
@@ -276,6 +294,65 @@ contains
          d%s_min(1:nscal), d%s_max(1:nscal), d%u_min(1:dm), d%u_max(1:dm), d%magvel_max, d%vort_min, d%vort_max
     close(u)
   end subroutine write_diag
+
+  ! the particles of the run: a restart reads the checkpoint's Particles file (when it has one), a fresh run seeds the lattice -- x fastest, centres
+  ! (i + 0.5) (L / n) of an even lattice over the domain (advance.particle_lattice) -- and writes its first particle file
+  subroutine start_tracers()
+    character(len=256) :: pfile
+    real(dp_t), allocatable :: x(:,:)
+    real(dp_t) :: t0, len3(3)
+    integer :: i, j, k, q, np(3)
+    logical :: there
+    if (restart >= 0) then
+       write(pfile, '(a,i5.5,a)') trim(check_base_name), restart, '/Particles'
+       inquire(file=trim(pfile), exist=there)
+       if (there) then
+          call particles_read(trim(pfile), tracers, t0)
+          have_tracers = .true.
+       end if
+       return
+    end if
+    if (all(particle_lattice == 0)) return
+    if (any(particle_lattice < 0)) stop 'varden_main: particle_lattice: counts are >= 0'
+    np = max(1, particle_lattice)
+    len3 = nn * dx(1, :)
+    allocate(x(3, product(np)))
+    q = 0
+    do k = 0, np(3) - 1
+       do j = 0, np(2) - 1
+          do i = 0, np(1) - 1
+             q = q + 1
+             x(1, q) = (i + 0.5d0) * (len3(1) / np(1)); x(2, q) = (j + 0.5d0) * (len3(2) / np(2)); x(3, q) = (k + 0.5d0) * (len3(3) / np(3))
+          end do
+       end do
+    end do
+    call particles_create(tracers, x)
+    have_tracers = .true.
+    if (particle_int > 0) call write_tracers()
+  end subroutine start_tracers
+
+  ! one particle file: positions, states, and the velocity and the scalars sampled at the particles (ghost cells filled as the next step fills them)
+  subroutine write_tracers()
+    character(len=256) :: pfile
+    character(len=8) :: names(dm + nscal)
+    real(dp_t), allocatable :: val(:,:), cols(:,:)
+    integer, allocatable :: lev(:)
+    integer :: c
+    allocate(val(max(dm, nscal), tracers%n), cols(tracers%n, dm + nscal), lev(tracers%n))
+    call fill_state_ghosts()
+    call particles_sample(tracers, H%mla, H%uold(1:H%nlev), 1, dm, 1, dx(1:H%nlev,:), H%bct, val(1:dm, :), lev)
+    do c = 1, dm
+       write(names(c), '(a,i0)') 'vel', c
+       cols(:, c) = val(c, :)
+    end do
+    call particles_sample(tracers, H%mla, H%sold(1:H%nlev), 1, nscal, dm + 1, dx(1:H%nlev,:), H%bct, val(1:nscal, :), lev)
+    do c = 1, nscal
+       write(names(dm + c), '(a,i0)') 's', c
+       cols(:, dm + c) = val(c, :)
+    end do
+    write(pfile, '(a,i5.5)') trim(particle_base_name), istep
+    call particles_write(tracers, trim(pfile), time, names, cols)
+  end subroutine write_tracers
 
   ! plot file and checkpoint after every plot_int-th / chk_int-th step; final: the last step once more if it has not been written
   subroutine dump(final)
@@ -339,6 +416,8 @@ contains
     type(multifab) :: st(MAXL)
     character(len=256) :: dir
     integer :: l, i, rr(MAXL)
+    character(len=1) :: no_names(0)
+    real(dp_t) :: no_cols(1, 0)
     do l = 1, H%nlev
        call multifab_build(st(l), H%mla, l, 2 * dm + nscal, 0)
        call multifab_copy_c(st(l), 1, H%uold(l), 1, dm); call multifab_copy_c(st(l), dm + 1, H%sold(l), 1, nscal)
@@ -352,6 +431,7 @@ contains
     else
        call checkpoint_write(trim(dir), st(1:H%nlev), H%p(1:H%nlev), rr(1:H%nlev - 1), time, dt)
     end if
+    if (have_tracers) call particles_write(tracers, trim(dir) // '/Particles', time, no_names, no_cols)
     do l = 1, H%nlev
        call multifab_destroy(st(l))
     end do

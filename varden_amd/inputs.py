@@ -19,7 +19,8 @@ DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step
                 mg_bottom_solver=-1, hg_bottom_solver=-1, max_mg_bottom_nlevels=1000,
                 bcx_lo=14, bcx_hi=14, bcy_lo=14, bcy_hi=14, bcz_lo=14, bcz_hi=14,
                 fixed_dt=-1.0, plot_int=0, chk_int=0, restart=-1, plot_base_name="plt", check_base_name="chk", grids_file_name="", job_name="", fixed_grids="",
-                diag_int=0, diag_file_name="varden_diag.out")          # (the last two are the project's own keys, like tag_field)
+                diag_int=0, diag_file_name="varden_diag.out",          # (these two and the particle keys are the project's own, like tag_field)
+                particle_lattice=(0, 0, 0), particle_int=0, particle_base_name="part")
 
 
 def parse_namelist(text):
@@ -88,6 +89,41 @@ def namelist_tag_criteria(nl):
                 crit[side] = vals
         out.append(crit)
     return out
+
+
+def namelist_particle_lattice(nl, text=""):
+    """the project's own key particle_lattice(1:3) = nx ny nz: tracer particles at the centres of an even lattice over the domain (all zero: none).  Taken from the
+    indexed keys particle_lattice(1) .. (3) or from one line `particle_lattice = nx, ny, nz`"""
+    out = [int(v) for v in DEFAULTS["particle_lattice"]]
+    m = re.search(r"^[^!\n]*\bparticle_lattice\s*=\s*(\d+)[\s,]+(\d+)(?:[\s,]+(\d+))?", text, flags=re.M)
+    if m:
+        out = [int(m.group(1)), int(m.group(2)), int(m.group(3) or 0)]
+    for d in range(3):
+        if "particle_lattice(%d)" % (d + 1) in nl:
+            out[d] = int(nl["particle_lattice(%d)" % (d + 1)])
+    if any(v < 0 for v in out):
+        raise ValueError("inputs: particle_lattice = %r: counts are >= 0" % (out,))
+    return tuple(out)
+
+
+def domain_extent(G):
+    """the physical extent of the domain a driver object runs on, per direction of its dm"""
+    cells = G.n if hasattr(G, "n") else G.ncs
+    return [cells[d] * G.dx[0][d] for d in range(G.dm)]
+
+
+PARTICLE_FILE = "Particles"          # inside a checkpoint directory
+
+
+def particle_columns(G):
+    """what a particle file carries beside positions and states: the velocity and the nscal scalars at the particles (ghost cells filled first, as the next
+    step's top fills them)"""
+    G.fill_state_ghosts()
+    u = G.particles.sample(G.mla, G.uold, G.dx, G.bct, comp=0, nc=G.dm, bccomp=0)
+    sc = G.particles.sample(G.mla, G.sold, G.dx, G.bct, comp=0, nc=G.nscal, bccomp=G.dm)
+    cols = {"vel%d" % (d + 1): u[:, d] for d in range(G.dm)}
+    cols.update({"s%d" % (c + 1): sc[:, c] for c in range(G.nscal)})
+    return cols
 
 
 def namelist_params(nl, dm=None):
@@ -220,11 +256,13 @@ def diag_line(istep, time, dt, d):
     return "%8d" % istep + plotfile._es(time) + plotfile._es(dt) + "%16d%16d" % (v[0], v[1]) + "".join(plotfile._es(x) for x in v[2:]) + "\n"
 
 
-def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None):
+def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None, particles=None, particle_int=None):
     """the time loop of src/varden.f90:237-371 for max_step steps (or until stop_time); plot / checkpoint files at step 0 of a fresh
     run and after every plot_int-th / chk_int-th step (:207-221, :349-361) under outdir.  diag_int > 0 (the namelist's key, or the argument over it): the run
     diagnostics of the state the run starts from and after every diag_int-th step, one line each under a header line, in <outdir>/<diag_file_name>; 0: no
-    call, no file"""
+    call, no file.  Tracer particles (the namelist's particle_lattice, particle_int, particle_base_name; the arguments particles = (nx, ny, nz) and particle_int over
+    them): moved by every step, <particle_base_name>NNNNN with positions, states, velocity and scalars at the start and after every particle_int-th step, a file
+    Particles inside every checkpoint, read back by a restart; no lattice: no call, no file"""
     nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz, files=files)
     max_step = int(nl["max_step"]) if nsteps is None else nsteps
     stop_time = float(nl["stop_time"])
@@ -245,7 +283,24 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             last["plt"] = G.istep
         if chk_int > 0 and (G.istep % chk_int == 0 or final) and last["chk"] != G.istep:
             G.files_written.append(plotfile.write_checkfile(G, base=os.path.join(outdir, str(nl["check_base_name"]))))
+            if G.particles is not None:
+                G.particles.write(os.path.join(outdir, "%s%05d" % (nl["check_base_name"], G.istep), PARTICLE_FILE), time=G.time)
             last["chk"] = G.istep
+
+    # tracer particles: a fresh run seeds the lattice, a restart reads the checkpoint's Particles file; with neither nothing below runs
+    particle_int = int(nl["particle_int"]) if particle_int is None else int(particle_int)
+    lattice = namelist_particle_lattice(nl, text) if particles is None else tuple(int(v) for v in particles)
+    if int(nl["restart"]) >= 0:
+        pfile = os.path.join(outdir, "%s%05d" % (nl["check_base_name"], int(nl["restart"])), PARTICLE_FILE)
+        if os.path.exists(pfile):
+            G.particles = adv.Particles.read(pfile)[0]
+    elif any(lattice):
+        G.particles = adv.Particles(adv.particle_lattice([max(1, v) for v in lattice[:G.dm]], domain_extent(G)))
+
+    def particle_file():
+        path = os.path.join(outdir, "%s%05d" % (nl["particle_base_name"], G.istep))
+        G.particles.write(path, time=G.time, columns=particle_columns(G))
+        G.files_written.append(path)
 
     diag_int = int(nl["diag_int"]) if diag_int is None else int(diag_int)
     diag_path = os.path.join(outdir, str(nl["diag_file_name"]))
@@ -260,6 +315,8 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
         diag()
     if int(nl["restart"]) < 0:
         dump()
+        if G.particles is not None and particle_int > 0:
+            particle_file()
     while G.istep < max_step and (stop_time < 0 or G.time < stop_time):
         G.step()
         if grids_file and getattr(G, "nregrids", 0) != regrids_seen[0]:      # varden.f90:263-264
@@ -269,6 +326,8 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             report(G)
         if diag_int > 0 and G.istep % diag_int == 0:
             diag()
+        if G.particles is not None and particle_int > 0 and G.istep % particle_int == 0:
+            particle_file()
         dump()
     if G.istep > (int(nl["restart"]) if int(nl["restart"]) >= 0 else 0):
         dump(final=True)
