@@ -373,6 +373,39 @@ int vdn_diagnostics(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multi
                     const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct, int what, vdn_diag *out);
 size_t vdn_diag_sizeof(void);
 
+/* ---- plane-averaged profiles of a hierarchy along one axis, computed on the device -------------------------------------------------------
+ * No reference counterpart.  nlev levels, axis a (0 .. dm-1), L = nlev - 1 the finest level OF THE HIERARCHY, whether or not it covers a given plane.
+ *   bins      the planes of level L's index space along a: nbins = ncells_a(level 0) << L; bin m is m h <= x_a < (m + 1) h, h = dx[L][a]
+ *   cells     the composite grid exactly as vdn_diagnostics defines it: the valid cells of level l that no box of level l + 1 covers.  Such a cell with index i_a
+ *             along a lies in the r = 1 << (L - l) bins i_a r .. i_a r + r - 1 and contributes to EACH of them with the weight w_l = (dx dy dz of level l) / r
+ *             (dm = 2: dx dy / r); w_l is formed once per level on the host (the division by a power of two is exact)
+ *   rows      per bin, rho = s_0; products are associated as written, left to right, then multiplied by w_l:
+ *               volume      (number of the bin's composite cells of level l) * w_l, added over the levels       1
+ *               s[c]        s_c w_l                                                                          nscal
+ *               ss[c]       (s_c s_c) w_l                                                                    nscal
+ *               u[d]        u_d w_l                                                                          dm
+ *               ru[d]       (rho u_d) w_l                                                                    dm
+ *               ruu[d,e]    ((rho u_d) u_e) w_l, d <= e, in the order (0,0) (0,1) [(0,2)] (1,1) [(1,2) (2,2)]    dm (dm + 1) / 2
+ *               sua[c]      (s_c u_a) w_l, c >= 1: the flux of tracer c along the axis                        nscal - 1
+ *               s_min[c], s_max[c], u_min[d], u_max[d]   exact extrema over the bin's composite cells (the bits of a value that is in the field; -0 sorts
+ *                           below +0, as in vdn_diagnostics); 0 where a bin holds no cell                     2 nscal + 2 dm
+ *             and, in an array of its own, cells[m]: the number of composite cells lying in bin m (a coarse cell counts in each of its r bins).
+ * A plane average is row / volume; the host wrappers offer it, the library does not.  vdn_profiles_layout fills the offsets of the row groups and their count nrow
+ * for (dm, nscal) -- a pure host function, callable before vdn_init; a caller never hard-codes a row number.  The result is out[nrow][nbins], row-major, and
+ * cells[nbins].  u[nlev], s[nlev]: the velocity and the scalars of every level on the layout mla; dx: [nlev][3].
+ * No ghost cell is read, the call writes none of its inputs.  Collective; every rank receives the full result.  Deterministic: sums are added in a fixed order
+ * (inside a piece of a box, then slot by slot in level / box / piece order), never by atomics -- two calls give the same bits, every rank gets the same bits, and
+ * the bits do not depend on the number of ranks (they do depend on how a level is cut into boxes).
+ * vdn_profiles_nbins returns the number of bins, or -1 (vdn_last_error) for a NULL layout, an nlev that is not the layout's or an axis outside 0 .. dm-1.
+ * vdn_profiles refuses (non-zero, vdn_last_error, nothing left allocated): an uninitialised library; nlev outside 1 .. 4 or not the layout's; u / s not on mla
+ * (or on different box lists); a NULL dx, out or cells; axis outside 0 .. dm-1; nbins other than vdn_profiles_nbins; dm = 2 with nlev > 1. */
+typedef struct vdn_profile_layout { int nrow, volume, s, ss, u, ru, ruu, sua, s_min, s_max, u_min, u_max; } vdn_profile_layout;
+int  vdn_profiles_layout(int dm, int nscal, vdn_profile_layout *lay);
+size_t vdn_profile_layout_sizeof(void);
+long vdn_profiles_nbins(int nlev, vdn_layout *mla, int axis);
+int  vdn_profiles(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s, const double *dx /*[nlev][3]*/,
+                  int axis, long nbins, double *out_host /*[nrow][nbins]*/, long long *cells_host /*[nbins]*/);
+
 /* ---- values at points and Lagrangian tracer particles (csrc/particles.hip, csrc/particle_plan.h).  No reference counterpart -------------
  * Positions are physical, measured from the domain's low corner (prob_lo = 0); level l has spacing dx[l][d]; dm = 2 uses x and y (z is stored as 0).  The
  * domain's extent is len_d = ncells_d(level 0) * dx[0][d]; a point is inside when 0 <= x_d <= len_d in every direction.

@@ -1,8 +1,10 @@
-"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D] [--files plane|copy] [--diag-int N] [--particles NX,NY,NZ] [--particle-int N]: the reference executable's command line (src/main.f90
+"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D] [--files plane|copy] [--diag-int N] [--particles NX,NY,NZ] [--particle-int N] [--prof-int N] [--prof-axis A]: the reference executable's command line (src/main.f90
 reads the inputs file named by the first argument and calls varden()).  Plot and checkpoint files go under --outdir; a 2-D hierarchy writes the 2-D run's own
 dm = 2 files (--files copy: those of the 3-D copy it runs as).  --diag-int N overrides the namelist's diag_int: a line of run diagnostics (advance.diagnostics) for the
 starting state and after every N-th step, in <outdir>/<diag_file_name>.  --particles NX,NY,NZ and --particle-int N set the namelist's particle_lattice and
-particle_int: tracer particles on an even lattice, moved by every step, written every N steps to <outdir>/<particle_base_name>NNNNN."""
+particle_int: tracer particles on an even lattice, moved by every step, written every N steps to <outdir>/<particle_base_name>NNNNN.  --prof-int N and --prof-axis A (numbered from 1; -1: the last
+direction) override prof_int and prof_axis: the plane-averaged profiles (advance.profiles) of the starting state and after every N-th step, one file
+<outdir>/<prof_base_name>NNNNN each."""
 import argparse
 import os
 import time
@@ -21,6 +23,8 @@ def main():
     ap.add_argument("--diag-int", type=int, default=None, help="override diag_int: run diagnostics every N steps into diag_file_name (0: none)")
     ap.add_argument("--particles", default=None, help="override particle_lattice: NX,NY,NZ tracer particles on an even lattice (0,0,0: none)")
     ap.add_argument("--particle-int", type=int, default=None, help="override particle_int: a particle file every N steps (0: none)")
+    ap.add_argument("--prof-int", type=int, default=None, help="override prof_int: a file of plane-averaged profiles every N steps (0: none)")
+    ap.add_argument("--prof-axis", type=int, default=None, help="override prof_axis: the direction of the profiles, numbered from 1 (-1: the last direction)")
     a = ap.parse_args()
     lattice = None if a.particles is None else tuple(int(v) for v in (a.particles.split(",") + ["0", "0"])[:3])
     os.makedirs(a.outdir, exist_ok=True)
@@ -31,7 +35,7 @@ def main():
 
     t0 = time.time()
     nl, G = inputs.run(open(a.inputs_file).read(), a.steps, report, device=a.device, outdir=a.outdir, files=a.files, diag_int=a.diag_int, particles=lattice,
-                        particle_int=a.particle_int)
+                        particle_int=a.particle_int, prof_int=a.prof_int, prof_axis=a.prof_axis)
     print("Total Run time (s) = %.3f" % (time.time() - t0))
     for f in G.files_written:
         print("wrote", f)

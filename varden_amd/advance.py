@@ -408,6 +408,75 @@ def diag_values(d):
             + [d["magvel_max"], d["vort_min"], d["vort_max"]])
 
 
+# ---- plane-averaged profiles (csrc/profiles.hip; include/varden_amd.h states the definition) ----------------------------------------------
+PROFILE_GROUPS = ("volume", "s", "ss", "u", "ru", "ruu", "sua", "s_min", "s_max", "u_min", "u_max")      # the row groups in row order (vdn_profile_layout)
+
+
+def profiles_layout(dm, nscal):
+    """vdn_profiles_layout as a dict: nrow and, per row group of PROFILE_GROUPS, (first row, number of rows)"""
+    lay = capi.ProfileLayout()
+    check(capi.load().vdn_profiles_layout(int(dm), int(nscal), C.byref(lay)))
+    first = [getattr(lay, g) for g in PROFILE_GROUPS] + [lay.nrow]
+    out = {g: (first[i], first[i + 1] - first[i]) for i, g in enumerate(PROFILE_GROUPS)}
+    out["nrow"] = lay.nrow
+    return out
+
+
+def profile_columns(nscal, dm):
+    """the names of the rows in row order (the columns of a profile file after x and cells): components are numbered from 1, ruu by its pair (ruu12 = rho u1 u2),
+    sua from the first tracer (sua2)"""
+    one = lambda base, n, first=1: ["%s%d" % (base, c + first) for c in range(n)]      # noqa: E731
+    return (["volume"] + one("s", nscal) + one("ss", nscal) + one("u", dm) + one("ru", dm) + ["ruu%d%d" % (d + 1, e + 1) for d in range(dm) for e in range(d, dm)]
+            + one("sua", nscal - 1, 2) + one("s_min", nscal) + one("s_max", nscal) + one("u_min", dm) + one("u_max", dm))
+
+
+class Profiles:
+    """the result of vdn_profiles along `axis`: x (bin centres), cells (composite cells per bin), rows (nrow, nbins) and every row group by name -- P["volume"] is
+    (nbins,), every other group (rows of the group, nbins); ruu_pairs names the (d, e) of ruu's rows.  mean(name) = rows / volume: the plane averages."""
+
+    def __init__(self, axis, dm, nscal, x, rows, cells):
+        self.axis, self.dm, self.nscal, self.x, self.rows, self.cells = axis, dm, nscal, x, rows, cells
+        self.layout = profiles_layout(dm, nscal)
+        self.ruu_pairs = [(d, e) for d in range(dm) for e in range(d, dm)]
+
+    def __getitem__(self, name):
+        if name == "cells":
+            return self.cells
+        if name == "x":
+            return self.x
+        first, n = self.layout[name]
+        return self.rows[first] if name == "volume" else self.rows[first:first + n]
+
+    def keys(self):
+        return ("x", "cells") + PROFILE_GROUPS
+
+    def mean(self, name):
+        if name not in ("s", "ss", "u", "ru", "ruu", "sua"):
+            raise KeyError("mean(%r): a plane average is a sum row divided by the volume row" % (name,))
+        return self[name] / self["volume"]
+
+
+def profiles(mla, u, s, dx, axis):
+    """vdn_profiles over the composite grid of the hierarchy (u, s: one multifab per level; dx: one list per level; axis 0-based): a Profiles object.  Bins are the
+    planes of the FINEST level along the axis; a coarse cell contributes to each of the fine bins it spans.  No ghost cell is read.  Sums have a fixed order, extrema
+    are exact: equal bits call after call and on any number of ranks.  Collective."""
+    import numpy as np
+    lib = capi.load()
+    prm = capi.Params()
+    check(lib.vdn_get_params(C.byref(prm)))
+    nlev, axis = len(u), int(axis)
+    levs = dx if hasattr(dx[0], "__len__") else [dx]
+    nbins = lib.vdn_profiles_nbins(nlev, mla.h, axis)
+    if nbins < 0:
+        check(1)
+    nrow = profiles_layout(prm.dm, prm.nscal)["nrow"]
+    rows, cells = np.zeros((nrow, nbins)), np.zeros(nbins, dtype=np.int64)
+    check(lib.vdn_profiles(nlev, mla.h, handle_array(u), handle_array(s), _dx3(levs), axis, nbins, rows.ctypes.data_as(C.POINTER(C.c_double)),
+                           cells.ctypes.data_as(C.POINTER(C.c_longlong))))
+    x = (np.arange(nbins) + 0.5) * float(levs[nlev - 1][axis])
+    return Profiles(axis, prm.dm, prm.nscal, x, rows, cells)
+
+
 # ---- values at points and tracer particles (csrc/particles.hip; include/varden_amd.h states the definitions) ------------------------------
 def _dx3(dx):
     levs = dx if hasattr(dx[0], "__len__") else [dx]

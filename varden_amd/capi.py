@@ -79,6 +79,11 @@ class Diag(C.Structure):
                 ("magvel_max", C.c_double), ("vort_min", C.c_double), ("vort_max", C.c_double)]
 
 
+class ProfileLayout(C.Structure):
+    """mirror of ``vdn_profile_layout``: the number of rows of vdn_profiles' result and the first row of every row group (vdn_profiles_layout fills it)"""
+    _fields_ = [(name, C.c_int) for name in ("nrow", "volume", "s", "ss", "u", "ru", "ruu", "sua", "s_min", "s_max", "u_min", "u_max")]
+
+
 # every symbol include/varden_amd.h declares: (restype, argtypes)
 _VP = C.c_void_p
 _PI = C.POINTER(C.c_int)
@@ -157,6 +162,10 @@ SIGNATURES = {
                                         C.c_int, C.POINTER(Box), _PI, C.POINTER(C.c_long)]),
     "vdn_diagnostics": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_int, C.POINTER(Diag)]),
     "vdn_diag_sizeof": (C.c_size_t, []),
+    "vdn_profiles_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(ProfileLayout)]),
+    "vdn_profile_layout_sizeof": (C.c_size_t, []),
+    "vdn_profiles_nbins": (C.c_long, [C.c_int, _VP, C.c_int]),
+    "vdn_profiles": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, C.c_int, C.c_long, _PD, C.POINTER(C.c_longlong)]),
     "vdn_sample_points": (C.c_int, [C.c_int, _VP, _PVP, C.c_int, C.c_int, C.c_int, _PD, _VP, C.c_long, _PD, _PD, _PI]),
     "vdn_particles_create": (C.c_int, [C.c_long, _PD, _PVP]),
     "vdn_particles_destroy": (C.c_int, [_VP]),

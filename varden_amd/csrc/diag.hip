@@ -192,7 +192,8 @@ __global__ void __launch_bounds__(64) kk_diag_final(const double *__restrict__ p
 // the cells of a level that the next level covers: a byte per valid cell of every local box, set box pair by box pair (the box-batched cell launch of vdn_dev.h)
 struct cover_K { unsigned char *m; int blo[3], bnx, bny;
   __device__ void cell(int i, int j, int k) const { m[((long)(k - blo[2]) * bny + (j - blo[1])) * bnx + (i - blo[0])] = 1; } };
-// returns the mask of every local box of level n of `mf` (arena memory)
+}   // namespace
+// returns the mask of every local box of level n of `mf` (arena memory); declared in vdn_internal.h: vdn_profiles (profiles.hip) masks the same cells
 std::vector<unsigned char *> cover_masks(const vdn_layout *la, const vdn_multifab *mf, int n) {
   hipStream_t st = ctx().stream;
   const int nb = mf->nfabs();
@@ -223,6 +224,7 @@ std::vector<unsigned char *> cover_masks(const vdn_layout *la, const vdn_multifa
   launch_cells(v, st);
   return m;
 }
+namespace {
 
 template <int NS> void launch_diag(bool vort, int nd, const DiagD *d, double *part, int nscal, int dm, double vol) {
   hipStream_t st = ctx().stream;

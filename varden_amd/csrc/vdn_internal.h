@@ -209,6 +209,9 @@ void  arena_release(size_t mark);
 vdn_multifab *mf_temp(const vdn_layout *la, int lev, int nc, int ng, int face_dir /* -1 cell, 0..2 face, 3 nodal */,
                       bool fill, double val);
 void mf_temp_free(vdn_multifab *mf);
+// diag.hip: per local box of level n of `mf`, one byte per valid cell (x fastest, arena memory), != 0 where a box of level n + 1 covers the cell: the cells that are
+// not part of the composite grid (vdn_diagnostics, vdn_profiles)
+std::vector<unsigned char *> cover_masks(const vdn_layout *la, const vdn_multifab *mf, int n);
 void fabio_release();      // fabio.hip: frees the pinned staging buffer of the file writers (vdn_finalize)
 
 // exchange.hip: ghost exchange plans and the RCCL transport

@@ -212,6 +212,11 @@ class Varden:
         self.fill_state_ghosts()
         return adv.diagnostics(self.mla, self.uold, self.sold, self.dx, self.bct, vort=vort)
 
+    def profiles(self, axis=None):
+        """advance.profiles of the current state (uold, sold) along `axis` (0-based; default: the last direction, dm - 1): the plane sums per bin, the exact extrema
+        and the cell counts.  No ghost cell is read, so nothing is filled first."""
+        return adv.profiles(self.mla, self.uold, self.sold, self.dx, self.dm - 1 if axis is None else int(axis))
+
     def gather_valid(self, mf):
         """valid cells of the LOCAL boxes assembled into a global array (NaN where other ranks own the data)"""
         out = np.full(self.n + (mf.nc,), np.nan, order="F")
@@ -576,6 +581,12 @@ class VardenAMR:
         the copy's extent along z, the vorticity is the 3-D rule's |curl u|; nothing is rescaled."""
         self.fill_state_ghosts()
         return adv.diagnostics(self.mla, self.uold, self.sold, self.dx, self.bct, vort=vort)
+
+    def profiles(self, axis=None):
+        """advance.profiles of the current state (uold, sold) over the composite grid along `axis` (0-based; default: the last direction, dm - 1); the bins are the planes
+        of the finest level the hierarchy has at the moment.  No ghost cell is read, so nothing is filled first.  An extruded 2-D copy reports the 3-D COPY's figures, as
+        diagnostics() does: dm = 3, the volume carries the copy's extent along z, and the default axis is z."""
+        return adv.profiles(self.mla, self.uold, self.sold, self.dx, self.dm - 1 if axis is None else int(axis))
 
     def slice2d(self, mfs):
         """plane k = 0 of a per-level list of cell multifabs as level-domain arrays (nx << n, ny << n, nc), NaN outside the level's boxes: the 2-D answer of an extruded run"""

@@ -66,6 +66,12 @@ module varden_amd
      real(c_double) :: s_min(11), s_max(11), u_min(3), u_max(3), magvel_max, vort_min, vort_max
   end type vdn_diag
 
+  ! plane-averaged profiles along one axis (include/varden_amd.h: vdn_profile_layout, vdn_profiles): the number of rows of the result and the first row (0-based,
+  ! as the library counts them; row r is out(:, r + 1)) of every row group
+  type, bind(C), public :: vdn_profile_layout
+     integer(c_int) :: nrow, volume, s, ss, u, ru, ruu, sua, s_min, s_max, u_min, u_max
+  end type vdn_profile_layout
+
   type, public :: ml_layout
      type(c_ptr) :: h = c_null_ptr
      integer :: nlevel = 0, dim = 3
@@ -97,6 +103,7 @@ module varden_amd
   public :: fillpatch, ml_nodal_prolongation, multifab_copy_layouts, make_new_grids, make_vorticity, make_magvel
   public :: make_new_grids_by, tag_boxes_by, make_tag_criterion
   public :: diagnostics
+  public :: profiles_layout, profiles_nbins, profiles
   public :: sample_points, particles_create, particles_destroy, particles_count, particles_get, particles_advance, particles_sample, particles_write, particles_read
   public :: fabio_ml_multifab_write_d, fabio_ml_multifab_info, fabio_ml_multifab_boxes, fabio_ml_multifab_read_d, checkpoint_write, checkpoint_info
   public :: fabio_ml_multifab_write_plane_d, fabio_ml_multifab_read_plane_d, checkpoint_write_plane, make_vorticity_plane
@@ -336,6 +343,29 @@ module varden_amd
      end function
      integer(c_size_t) function vdn_diag_sizeof() bind(C, name="vdn_diag_sizeof")
        import :: c_size_t
+     end function
+     integer(c_int) function vdn_profiles_layout(dm, nscal, lay) bind(C, name="vdn_profiles_layout")
+       import :: c_int, vdn_profile_layout
+       integer(c_int), value :: dm, nscal
+       type(vdn_profile_layout), intent(out) :: lay
+     end function
+     integer(c_size_t) function vdn_profile_layout_sizeof() bind(C, name="vdn_profile_layout_sizeof")
+       import :: c_size_t
+     end function
+     integer(c_long) function vdn_profiles_nbins(nlev, mla, axis) bind(C, name="vdn_profiles_nbins")
+       import :: c_int, c_long, c_ptr
+       integer(c_int), value :: nlev, axis
+       type(c_ptr), value :: mla
+     end function
+     integer(c_int) function vdn_profiles(nlev, mla, u, s, dx, axis, nbins, out_host, cells_host) bind(C, name="vdn_profiles")
+       import :: c_int, c_long, c_long_long, c_ptr, c_double
+       integer(c_int), value :: nlev, axis
+       integer(c_long), value :: nbins
+       type(c_ptr), value :: mla
+       type(c_ptr), intent(in) :: u(*), s(*)
+       real(c_double), intent(in) :: dx(*)
+       real(c_double), intent(out) :: out_host(*)
+       integer(c_long_long), intent(out) :: cells_host(*)
      end function
      ! values at points and tracer particles (include/varden_amd.h; csrc/particles.hip)
      integer(c_int) function vdn_sample_points(nlev, mla, mf, comp, nc, bccomp, dx, bct, n, x_host, val_host, lev_host) bind(C, name="vdn_sample_points")
@@ -863,6 +893,50 @@ contains
     end do
     call chk(vdn_diagnostics(int(size(u), c_int), mla%h, handles(u), handles(s), dxc, the_bc_tower%h, what, diag), 'diagnostics')
   end subroutine diagnostics
+  ! plane-averaged profiles (see vdn_profiles): the offsets of the row groups for (dm, nscal) ...
+  subroutine profiles_layout(dm, nscal, lay)
+    integer, intent(in) :: dm, nscal
+    type(vdn_profile_layout), intent(out) :: lay
+    if (vdn_profile_layout_sizeof() /= c_sizeof(lay)) error stop 'profiles_layout: vdn_profile_layout differs between the library and this module'
+    call chk(vdn_profiles_layout(int(dm, c_int), int(nscal, c_int), lay), 'profiles_layout')
+  end subroutine profiles_layout
+  ! ... the number of bins of a hierarchy of nlev levels along axis (1-based): the planes of its finest level ...
+  function profiles_nbins(mla, nlev, axis) result(nbins)
+    type(ml_layout), intent(in) :: mla
+    integer, intent(in) :: nlev, axis
+    integer :: nbins
+    integer(c_long) :: n
+    n = vdn_profiles_nbins(int(nlev, c_int), mla%h, int(axis - 1, c_int))
+    if (n < 0) call chk(1_c_int, 'profiles_nbins')
+    nbins = int(n)
+  end function profiles_nbins
+  ! ... and the profiles of the state (u, s) of levels 1 .. size(u) over the composite grid along axis (1-based): out(bin, row) -- row r of vdn_profile_layout's
+  ! 0-based count is out(:, r + 1) -- and cells(bin), both of profiles_nbins bins.  No ghost cell is read
+  subroutine profiles(mla, u, s, dx, axis, out, cells)
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: u(:), s(:)
+    real(dp_t)     , intent(in   ) :: dx(:,:)
+    integer        , intent(in   ) :: axis
+    real(dp_t)     , intent(  out) :: out(:,:)
+    integer(c_long_long), intent(out) :: cells(:)
+    real(c_double) :: dxc(3 * size(u))
+    real(c_double), allocatable :: o(:)
+    integer(c_long_long), allocatable :: cc(:)
+    integer :: n, d, nb, nr
+    nb = profiles_nbins(mla, size(u), axis)
+    nr = size(out, 2)
+    if (size(out, 1) /= nb .or. size(cells) /= nb) error stop 'profiles: out(nbins, nrow) and cells(nbins) with nbins = profiles_nbins expected'
+    dxc = 1.0_c_double
+    do n = 1, size(u)
+       do d = 1, min(3, size(dx, 2))
+          dxc((n - 1) * 3 + d) = dx(n, d)
+       end do
+    end do
+    allocate(o(nb * nr), cc(nb))
+    call chk(vdn_profiles(int(size(u), c_int), mla%h, handles(u), handles(s), dxc, int(axis - 1, c_int), int(nb, c_long), o, cc), 'profiles')
+    out = reshape(o, (/ nb, nr /))
+    cells = cc
+  end subroutine profiles
   subroutine make_magvel(magvel, comp, u)
     type(multifab), intent(inout) :: magvel, u
     integer       , intent(in   ) :: comp

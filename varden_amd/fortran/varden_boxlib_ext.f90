@@ -15,6 +15,8 @@
 !   fillpatch_module, ml_prolongation_module   fillpatch(fine, crse, ...) / ml_nodal_prolongation(fine, crse, ir)   (src/regrid.f90:279-280, 317-344)
 !   fabio_module        fabio_mkdir / fabio_ml_multifab_write_d(mfs, rrs, dirname[, names, bounding_box, prob_lo, prob_hi, time, dx]) / fabio_ml_multifab_read_d(mfs,
 !                       dirname)   (src/varden.f90:568-573, src/checkpoint.f90:40-48, 130-134): the library packs and writes (csrc/fabio.hip); one rank
+!   profiles_module     profiles_layout / profiles_nbins(mla, axis) / profiles(mla, u, s, dx, axis, out, cells): the plane-averaged profiles of varden_amd on these
+!                       container types (the project's own analysis call; the reference has none)
 ! probin_module (varden_boxlib.f90) carries every entry of src/_parameters with its default, the &PROBIN namelist, probin_init and probin_close.
 ! NOT here (listed by the report as the maintainer's remaining work): FBoxLib's host-side box calculus (list_box_module, box_util_module), plotfile_module,
 ! bl_timer, layouts built one level at a time (layout_build_ba, make_new_grids_module, tag_boxes_module --
@@ -212,3 +214,35 @@ contains
     call vamd_read_d(v, dirname)
   end subroutine fabio_ml_multifab_read_d
 end module fabio_module
+
+! plane-averaged profiles of a hierarchy along one axis on the reference's container types (no reference counterpart; include/varden_amd.h: vdn_profiles):
+! profiles_layout(dm, nscal, lay) and type(vdn_profile_layout) as in varden_amd, profiles_nbins(mla, axis), profiles(mla, u, s, dx, axis, out, cells) with
+! out(nbins, nrow), cells(nbins); axis numbered from 1
+module profiles_module
+  use iso_c_binding, only: c_long_long
+  use multifab_module
+  use ml_layout_module
+  use varden_amd, only: vdn_profile_layout, profiles_layout, vamd_profiles_nbins => profiles_nbins, vamd_profiles => profiles, vamd_multifab => multifab
+  implicit none
+contains
+  function profiles_nbins(mla, axis) result(nbins)
+    type(ml_layout), intent(in) :: mla
+    integer, intent(in) :: axis
+    integer :: nbins
+    nbins = vamd_profiles_nbins(mla%v, mla%nlevel, axis)
+  end function profiles_nbins
+  subroutine profiles(mla, u, s, dx, axis, out, cells)
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: u(:), s(:)
+    real(dp_t)     , intent(in   ) :: dx(:,:)
+    integer        , intent(in   ) :: axis
+    real(dp_t)     , intent(  out) :: out(:,:)
+    integer(c_long_long), intent(out) :: cells(:)
+    type(vamd_multifab) :: uv(size(u)), sv(size(s))
+    integer :: n
+    do n = 1, size(u)
+       uv(n) = u(n)%v; sv(n) = s(n)%v
+    end do
+    call vamd_profiles(mla%v, uv, sv, dx, axis, out, cells)
+  end subroutine profiles
+end module profiles_module

@@ -51,12 +51,19 @@ program varden_main
   integer :: particle_lattice(3) = 0
   integer :: particle_int = 0
   character(len=128) :: particle_base_name = 'part'
+  ! ---- plane-averaged profiles (the project's own keys too): prof_int > 0 writes <prof_base_name>NNNNN for the state the run starts from and after every prof_int-th
+  ! step -- the format tag, dm, axis, nbins, step and time on a header line each, the column names, then per bin the centre, the cell count and every row of
+  ! vdn_profiles (varden_amd_mod: profiles) with es27.17e3 numbers: the file varden_amd/inputs.py writes, character for character.  prof_axis: the direction,
+  ! numbered from 1 (-1: the last one).  0 (default): no call, no file
+  integer :: prof_int = 0
+  integer :: prof_axis = -1
+  character(len=128) :: prof_base_name = 'prof'
   namelist /probin/ dim_in, nscal, prob_type, boussinesq, max_step, max_levs, max_grid_size, regrid_int, amr_buf_width, n_cellx, n_celly, n_cellz, &
        init_iter, do_initial_projection, diffusion_type, slope_order, use_minion, stencil_order, verbose, mg_verbose, plot_int, chk_int, restart, ref_ratio, &
        bcx_lo, bcx_hi, bcy_lo, bcy_hi, bcz_lo, bcz_hi, cluster_min_width, cluster_blocking_factor, grav, stop_time, prob_hi_x, prob_hi_y, prob_hi_z, &
        prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc, &
        plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels, tag_field, tag_comp, tag_gt, tag_lt, &
-       diag_int, diag_file_name, particle_lattice, particle_int, particle_base_name
+       diag_int, diag_file_name, particle_lattice, particle_int, particle_base_name, prof_int, prof_axis, prof_base_name
 
   ! one hierarchy: box lists, layout, boundary tower and the four multifabs regridding carries (regrid.f90:60-75)
   type hier
@@ -206,6 +213,7 @@ program varden_main
      call write_diag_header()
      call write_diag()
   end if
+  if (prof_int > 0) call write_prof()
 
   ! ---- time loop (varden.f90:237-345) ----
   nregrids = 0
@@ -240,6 +248,9 @@ program varden_main
           '  levels ', H%nlev, '  boxes ', H%nb
      if (diag_int > 0) then
         if (mod(istep, diag_int) == 0) call write_diag()
+     end if
+     if (prof_int > 0) then
+        if (mod(istep, prof_int) == 0) call write_prof()
      end if
      if (have_tracers .and. particle_int > 0) then
         if (mod(istep, particle_int) == 0) call write_tracers()
@@ -294,6 +305,58 @@ contains
          d%s_min(1:nscal), d%s_max(1:nscal), d%u_min(1:dm), d%u_max(1:dm), d%magvel_max, d%vort_min, d%vort_max
     close(u)
   end subroutine write_diag
+
+  ! one profile file: the profiles of the current state (H%uold, H%sold) along prof_axis (inputs.py: profile_text)
+  subroutine write_prof()
+    type(vdn_profile_layout) :: lay
+    real(dp_t), allocatable :: rows(:,:)
+    integer(c_long_long), allocatable :: cells(:)
+    integer :: u, ax, nb, m, c, d, e
+    character(len=256) :: fname
+    ax = prof_axis
+    if (ax < 1) ax = dm
+    call profiles_layout(dm, nscal, lay)
+    nb = profiles_nbins(H%mla, H%nlev, ax)
+    allocate(rows(nb, lay%nrow), cells(nb))
+    call profiles(H%mla, H%uold(1:H%nlev), H%sold(1:H%nlev), dx(1:H%nlev,:), ax, rows, cells)
+    write(fname, '(a,i5.5)') trim(prof_base_name), istep
+    open(newunit=u, file=trim(fname), status='replace', action='write')
+    write(u, '(a)') '# VDN_PROFILES 1'
+    write(u, '(a,i0)') '# dm ', dm
+    write(u, '(a,i0)') '# axis ', ax
+    write(u, '(a,i0)') '# nbins ', nb
+    write(u, '(a,i0)') '# step ', istep
+    write(u, '(a,es27.17e3)') '# time', time
+    write(u, '(a)', advance='no') '#' // repeat(' ', 25) // 'x' // repeat(' ', 11) // 'cells' // adjustr(wide('volume'))
+    call names('s', nscal, 1); call names('ss', nscal, 1); call names('u', dm, 1); call names('ru', dm, 1)
+    do d = 1, dm
+       do e = d, dm
+          call names('ruu', 1, 10 * d + e)
+       end do
+    end do
+    call names('sua', nscal - 1, 2)
+    call names('s_min', nscal, 1); call names('s_max', nscal, 1); call names('u_min', dm, 1); call names('u_max', dm, 1)
+    write(u, '(a)') ''
+    do m = 1, nb
+       write(u, '(es27.17e3,i16,*(es27.17e3))') (real(m - 1, dp_t) + 0.5d0) * dx(H%nlev, ax), cells(m), rows(m, :)
+    end do
+    close(u)
+  contains
+    function wide(s) result(w)
+      character(len=*), intent(in) :: s
+      character(len=27) :: w
+      w = s
+    end function wide
+    subroutine names(base, cnt, first)
+      character(len=*), intent(in) :: base
+      integer, intent(in) :: cnt, first
+      character(len=27) :: w
+      do c = 1, cnt
+         write(w, '(a,i0)') base, first + c - 1
+         write(u, '(a)', advance='no') adjustr(w)
+      end do
+    end subroutine names
+  end subroutine write_prof
 
   ! the particles of the run: a restart reads the checkpoint's Particles file (when it has one), a fresh run seeds the lattice -- x fastest, centres
   ! (i + 0.5) (L / n) of an even lattice over the domain (advance.particle_lattice) -- and writes its first particle file

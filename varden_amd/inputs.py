@@ -19,7 +19,7 @@ DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step
                 mg_bottom_solver=-1, hg_bottom_solver=-1, max_mg_bottom_nlevels=1000,
                 bcx_lo=14, bcx_hi=14, bcy_lo=14, bcy_hi=14, bcz_lo=14, bcz_hi=14,
                 fixed_dt=-1.0, plot_int=0, chk_int=0, restart=-1, plot_base_name="plt", check_base_name="chk", grids_file_name="", job_name="", fixed_grids="",
-                diag_int=0, diag_file_name="varden_diag.out",          # (these two and the particle keys are the project's own, like tag_field)
+                diag_int=0, diag_file_name="varden_diag.out", prof_int=0, prof_axis=-1, prof_base_name="prof",          # (these two and the particle keys are the project's own, like tag_field)
                 particle_lattice=(0, 0, 0), particle_int=0, particle_base_name="part")
 
 
@@ -256,13 +256,26 @@ def diag_line(istep, time, dt, d):
     return "%8d" % istep + plotfile._es(time) + plotfile._es(dt) + "%16d%16d" % (v[0], v[1]) + "".join(plotfile._es(x) for x in v[2:]) + "\n"
 
 
-def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None, particles=None, particle_int=None):
+def profile_text(P, istep, time):
+    """a profile file (prof_int > 0): the format tag, dm, the axis (numbered from 1, as the reference numbers directions), nbins, step and time on a header line each,
+    the column names, then one line per bin: the bin centre (es27.17e3), the cell count (i16), every row of advance.profile_columns (es27.17e3).  varden_main writes the
+    same, character for character."""
+    cols = adv.profile_columns(P.nscal, P.dm)
+    head = "# VDN_PROFILES 1\n# dm %d\n# axis %d\n# nbins %d\n# step %d\n# time%s\n" % (P.dm, P.axis + 1, len(P.x), istep, plotfile._es(time))
+    head += "#" + "x".rjust(26) + "cells".rjust(16) + "".join(c.rjust(27) for c in cols) + "\n"
+    body = ["".join([plotfile._es(P.x[m]), "%16d" % P.cells[m]] + [plotfile._es(v) for v in P.rows[:, m]]) + "\n" for m in range(len(P.x))]
+    return head + "".join(body)
+
+
+def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None, particles=None, particle_int=None, prof_int=None, prof_axis=None):
     """the time loop of src/varden.f90:237-371 for max_step steps (or until stop_time); plot / checkpoint files at step 0 of a fresh
     run and after every plot_int-th / chk_int-th step (:207-221, :349-361) under outdir.  diag_int > 0 (the namelist's key, or the argument over it): the run
     diagnostics of the state the run starts from and after every diag_int-th step, one line each under a header line, in <outdir>/<diag_file_name>; 0: no
     call, no file.  Tracer particles (the namelist's particle_lattice, particle_int, particle_base_name; the arguments particles = (nx, ny, nz) and particle_int over
     them): moved by every step, <particle_base_name>NNNNN with positions, states, velocity and scalars at the start and after every particle_int-th step, a file
-    Particles inside every checkpoint, read back by a restart; no lattice: no call, no file"""
+    Particles inside every checkpoint, read back by a restart; no lattice: no call, no file.  prof_int > 0 (the namelist's key, or the argument over it): the plane-averaged profiles
+    (advance.profiles) of the state the run starts from and after every prof_int-th step along prof_axis (numbered from 1; -1: the problem's last direction), one
+    file <prof_base_name>NNNNN each (profile_text); 0: no call, no file"""
     nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz, files=files)
     max_step = int(nl["max_step"]) if nsteps is None else nsteps
     stop_time = float(nl["stop_time"])
@@ -309,10 +322,21 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
         with open(diag_path, "a") as f:
             f.write(diag_line(G.istep, G.time, G.dt, G.diagnostics()))
 
+    prof_int = int(nl["prof_int"]) if prof_int is None else int(prof_int)
+    prof_axis = int(nl["prof_axis"]) if prof_axis is None else int(prof_axis)
+
+    def prof():
+        path = os.path.join(outdir, "%s%05d" % (nl["prof_base_name"], G.istep))
+        with open(path, "w") as f:
+            f.write(profile_text(G.profiles(int(nl["dim_in"]) - 1 if prof_axis < 1 else prof_axis - 1), G.istep, G.time))
+        G.files_written.append(path)
+
     if diag_int > 0:
         with open(diag_path, "w") as f:
             f.write(diag_header(G.nscal, G.dm))
         diag()
+    if prof_int > 0:
+        prof()
     if int(nl["restart"]) < 0:
         dump()
         if G.particles is not None and particle_int > 0:
@@ -326,6 +350,8 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             report(G)
         if diag_int > 0 and G.istep % diag_int == 0:
             diag()
+        if prof_int > 0 and G.istep % prof_int == 0:
+            prof()
         if G.particles is not None and particle_int > 0 and G.istep % particle_int == 0:
             particle_file()
         dump()
