@@ -406,6 +406,60 @@ long vdn_profiles_nbins(int nlev, vdn_layout *mla, int axis);
 int  vdn_profiles(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s, const double *dx /*[nlev][3]*/,
                   int axis, long nbins, double *out_host /*[nrow][nbins]*/, long long *cells_host /*[nbins]*/);
 
+/* ---- how much of the fluid has which value: PDFs and conditional sums of a hierarchy's fields, computed on the device (csrc/pdf.hip) -------
+ * No reference counterpart.  vdn_profiles bins by position; these two bin by VALUE.
+ *   cells     the composite grid exactly as vdn_diagnostics defines it: the valid cells of level l that no box of level l + 1 covers.  A cell of level l carries
+ *             dV_l = dx dy dz of its level (dm = 2: dx dy).
+ *   bin field q, chosen by (field, comp), comp 0-based:
+ *               VDN_PDF_SCALAR     s(comp), comp 0 .. nscal-1
+ *               VDN_PDF_VELOCITY   u(comp), comp 0 .. dm-1
+ *               VDN_PDF_MAGVEL     the velocity magnitude, bit for bit the value vdn_make_magvel stores for the same u (comp is not read)
+ *               VDN_PDF_VORTICITY  the vorticity, bit for bit the value vdn_make_vorticity stores for the same u (comp is not read): its magnitude for dm = 3, signed
+ *                                  for dm = 2.  It reads ONE ghost layer of u, which the caller has filled, and needs bct, as VDN_DIAG_VORT does.
+ *             The other three fields read no ghost cell.
+ *   slots     the axis is {field, comp, nbins, lo, hi} with w = (hi - lo) / nbins formed once on the host in double.  nbins + 2 slots: slot 0 is "below", slots
+ *             1 .. nbins are the bins, slot nbins + 1 is "above".  In this order (csrc/pdf_bin.h):
+ *               1.  q != q: the cell counts in nan_cells and in nothing else
+ *               2.  q <  lo: slot 0
+ *               3.  q >= hi: slot nbins + 1
+ *               4.  otherwise m = (int)floor((q - lo) / w), a true division, not contracted; m is clamped to nbins - 1; the slot is 1 + m
+ *             +-Inf fall out of rules 2 and 3; -0 with lo = 0 lands in bin 0.
+ * vdn_pdf, one axis, nbins 1 .. VDN_PDF_MAX_BINS, returns
+ *   cells[VDN_MAXLEV][nbins + 2]   the exact number of composite cells of each level in each slot (0 beyond nlev)
+ *   nan_cells                      the composite cells whose q is NaN
+ *   out[nrow][nbins + 2]           row-major; rho = s_0; products are associated as written and then multiplied by dV_l:
+ *               volume      not summed per cell: the sum over the levels 0 .. nlev-1, ascending, of cells[l][slot] * dV_l        1
+ *               q           q dV_l                                                                                               1
+ *               s[c]        s_c dV_l                                                                                             nscal
+ *               u[d]        u_d dV_l                                                                                             dm
+ *               ru[d]       (rho u_d) dV_l                                                                                       dm
+ *               ke          ((0.5 rho) (u.u)) dV_l, u.u added as the velocity magnitude adds it: (u_0 u_0 + u_1 u_1) [+ u_2 u_2]     1
+ * vdn_pdf_layout fills the first row of every group and nrow = nscal + 2 dm + 3 for (dm, nscal) -- a pure host function, callable before vdn_init; a caller never
+ * hard-codes a row number.  The PDF itself is volume[1 .. nbins] / (sum of volume * w), a conditional mean is row / volume: the host wrappers offer both, the library
+ * does not.  A NaN (or Inf - Inf) in a summed field of a cell whose q is finite makes that slot's row NaN; the counts and volume stay exact.
+ * vdn_pdf2, two axes, each nbins 1 .. VDN_PDF2_MAX_BINS, returns cells[VDN_MAXLEV][n1 + 2][n2 + 2], volume[n1 + 2][n2 + 2] formed from the counts as above, and
+ * nan_cells, which counts a cell when EITHER value is NaN.  Counts only, no conditional sums.
+ * Both calls write none of their inputs and are collective; every rank receives the full result.  Deterministic: counts are integers; sums are added in a fixed order
+ * (inside a slab of a box by a fixed thread map and tree, then slab by slab in level / box / k order), never by floating-point atomics -- two calls give the same bits,
+ * every rank gets the same bits, and the bits do not depend on the number of ranks (they do depend on how a level is cut into boxes).  Every temporary lives in the
+ * arena for the duration of the call.
+ * Both refuse (non-zero, vdn_last_error, nothing left allocated, a following call unaffected): an uninitialised library; NULL arguments (mla, u, s, dx, an output);
+ * nlev outside 1 .. 4 or not the layout's; u / s not on mla or on different box lists; a field code outside 0 .. 3; comp out of range for VDN_PDF_SCALAR /
+ * VDN_PDF_VELOCITY; nbins out of range; a non-finite lo or hi, or !(lo < hi); VDN_PDF_VORTICITY with a NULL bct or a u without a ghost layer; dm = 2 with nlev > 1;
+ * a refinement ratio other than 2. */
+enum { VDN_PDF_SCALAR = 0, VDN_PDF_VELOCITY = 1, VDN_PDF_MAGVEL = 2, VDN_PDF_VORTICITY = 3 };
+#define VDN_PDF_MAX_BINS 256
+#define VDN_PDF2_MAX_BINS 64
+typedef struct vdn_pdf_layout_t { int nrow, volume, q, s, u, ru, ke; } vdn_pdf_layout_t;    /* (the entry below has the plain name) */
+int  vdn_pdf_layout(int dm, int nscal, vdn_pdf_layout_t *lay);
+size_t vdn_pdf_layout_sizeof(void);
+int  vdn_pdf(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s, const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct,
+             int field, int comp, int nbins, double lo, double hi,
+             double *out_host /*[nrow][nbins+2]*/, long long *cells_host /*[VDN_MAXLEV][nbins+2]*/, long long *nan_cells);
+int  vdn_pdf2(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s, const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct,
+              int field1, int comp1, int nbins1, double lo1, double hi1, int field2, int comp2, int nbins2, double lo2, double hi2,
+              long long *cells_host /*[VDN_MAXLEV][n1+2][n2+2]*/, double *volume_host /*[n1+2][n2+2]*/, long long *nan_cells);
+
 /* ---- values at points and Lagrangian tracer particles (csrc/particles.hip, csrc/particle_plan.h).  No reference counterpart -------------
  * Positions are physical, measured from the domain's low corner (prob_lo = 0); level l has spacing dx[l][d]; dm = 2 uses x and y (z is stored as 0).  The
  * domain's extent is len_d = ncells_d(level 0) * dx[0][d]; a point is inside when 0 <= x_d <= len_d in every direction.

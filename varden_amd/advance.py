@@ -477,6 +477,122 @@ def profiles(mla, u, s, dx, axis):
     return Profiles(axis, prm.dm, prm.nscal, x, rows, cells)
 
 
+# ---- PDFs and conditional sums by value (csrc/pdf.hip; include/varden_amd.h states the definition) ------------------------------------------
+PDF_GROUPS = ("volume", "q", "s", "u", "ru", "ke")      # the row groups in row order (vdn_pdf_layout)
+PDF_FIELDS = {"scalar": 0, "velocity": 1, "magvel": 2, "vorticity": 3}      # VDN_PDF_SCALAR ...
+PDF_MAX_BINS, PDF2_MAX_BINS, _MAXLEV = 256, 64, 4
+
+
+def pdf_layout(dm, nscal):
+    """vdn_pdf_layout as a dict: nrow and, per row group of PDF_GROUPS, (first row, number of rows)"""
+    lay = capi.PdfLayout()
+    check(capi.load().vdn_pdf_layout(int(dm), int(nscal), C.byref(lay)))
+    first = [getattr(lay, g) for g in PDF_GROUPS] + [lay.nrow]
+    out = {g: (first[i], first[i + 1] - first[i]) for i, g in enumerate(PDF_GROUPS)}
+    out["nrow"] = lay.nrow
+    return out
+
+
+def pdf_columns(nscal, dm):
+    """the names of the rows in row order (the columns of a pdf file after the slot centre and cells): components are numbered from 1"""
+    one = lambda base, n: ["%s%d" % (base, c + 1) for c in range(n)]      # noqa: E731
+    return ["volume", "q"] + one("s", nscal) + one("u", dm) + one("ru", dm) + ["ke"]
+
+
+def _pdf_field(field):
+    if isinstance(field, str):
+        if field not in PDF_FIELDS:
+            raise ValueError("pdf field %r: one of %s" % (field, ", ".join(sorted(PDF_FIELDS))))
+        return PDF_FIELDS[field]
+    return int(field)
+
+
+class Pdf:
+    """the result of vdn_pdf on the axis (field, comp, lo, hi, nbins): nbins + 2 slots -- "below", the bins, "above".  edges (nbins + 1,), centres (nbins + 2,: lo +
+    (m + 0.5) w for m = -1 .. nbins), cells (nlev, nbins + 2), nan_cells, rows (nrow, nbins + 2) and every row group by name -- P["volume"], P["q"], P["ke"] are
+    (nbins + 2,), P["s"], P["u"], P["ru"] (rows of the group, nbins + 2).  density(): the PDF over the bins; mean(name): the conditional means row / volume."""
+
+    def __init__(self, field, comp, lo, hi, nbins, dm, nscal, rows, cells, nan_cells):
+        import numpy as np
+        self.field, self.comp, self.lo, self.hi, self.nbins, self.dm, self.nscal = field, int(comp), float(lo), float(hi), int(nbins), dm, nscal
+        self.rows, self.cells, self.nan_cells = rows, cells, int(nan_cells)
+        self.w = (self.hi - self.lo) / self.nbins
+        self.edges = self.lo + np.arange(self.nbins + 1) * self.w
+        self.edges[-1] = self.hi
+        self.centres = self.lo + (np.arange(-1, self.nbins + 1) + 0.5) * self.w
+        self.layout = pdf_layout(dm, nscal)
+
+    def __getitem__(self, name):
+        if name in ("cells", "edges", "centres", "nan_cells"):
+            return getattr(self, name)
+        first, n = self.layout[name]
+        return self.rows[first] if name in ("volume", "q", "ke") else self.rows[first:first + n]
+
+    def keys(self):
+        return ("edges", "centres", "cells", "nan_cells") + PDF_GROUPS
+
+    def density(self):
+        """volume[1 .. nbins] / (sum of volume over the bins * w): integrates to 1 over [lo, hi) (NaN where no cell lies in the range)"""
+        v = self["volume"][1:-1]
+        return v / (v.sum() * self.w)
+
+    def mean(self, name):
+        """the conditional mean of a summed group per slot: row / volume (NaN in an empty slot)"""
+        if name not in ("q", "s", "u", "ru", "ke"):
+            raise KeyError("mean(%r): a conditional mean is a sum row divided by the volume row" % (name,))
+        import numpy as np
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self[name] / self["volume"]
+
+
+class Pdf2:
+    """the result of vdn_pdf2: cells (nlev, n1 + 2, n2 + 2), volume (n1 + 2, n2 + 2), nan_cells, edges1 (n1 + 1,), edges2 (n2 + 1,)"""
+
+    def __init__(self, cells, volume, nan_cells, edges1, edges2):
+        self.cells, self.volume, self.nan_cells, self.edges1, self.edges2 = cells, volume, int(nan_cells), edges1, edges2
+
+
+def _pdf_state(u, dx):
+    lib = capi.load()
+    prm = capi.Params()
+    check(lib.vdn_get_params(C.byref(prm)))
+    levs = dx if hasattr(dx[0], "__len__") else [dx]
+    flat = [float(v) for lev in levs for v in (list(lev) + [1.0] * 3)[:3]]
+    return lib, prm, len(u), (C.c_double * len(flat))(*flat)
+
+
+def pdf(mla, u, s, dx, bct, field, comp, lo, hi, nbins):
+    """vdn_pdf over the composite grid of the hierarchy (u, s: one multifab per level; dx: one list per level): a Pdf object.  field: 'scalar' | 'velocity' | 'magvel' |
+    'vorticity' (or the VDN_PDF_ code), comp 0-based.  The vorticity reads one ghost layer of u, which the CALLER has filled (the drivers' fill_state_ghosts), and
+    needs bct; the others read no ghost cell and take bct = None.  Counts are exact, sums have a fixed order: equal bits call after call and on any number of ranks.
+    Collective."""
+    import numpy as np
+    lib, prm, nlev, dxc = _pdf_state(u, dx)
+    nbins, code = int(nbins), _pdf_field(field)
+    nrow = pdf_layout(prm.dm, prm.nscal)["nrow"]
+    width = max(nbins, 0) + 2
+    rows, cells, nan = np.zeros((nrow, width)), np.zeros((_MAXLEV, width), dtype=np.int64), C.c_longlong(0)
+    check(lib.vdn_pdf(nlev, mla.h, handle_array(u), handle_array(s), dxc, bct.h if bct is not None else None, code, int(comp), nbins, float(lo), float(hi),
+                      rows.ctypes.data_as(C.POINTER(C.c_double)), cells.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(nan)))
+    return Pdf(field, comp, lo, hi, nbins, prm.dm, prm.nscal, rows, cells[:nlev], nan.value)
+
+
+def pdf2(mla, u, s, dx, bct, field1, comp1, lo1, hi1, nbins1, field2, comp2, lo2, hi2, nbins2):
+    """vdn_pdf2: the joint distribution of two bin fields over the composite grid, counts and volume only: a Pdf2 object.  Fields and ghost cells as for pdf"""
+    import numpy as np
+    lib, prm, nlev, dxc = _pdf_state(u, dx)
+    n1, n2 = int(nbins1), int(nbins2)
+    shape = (max(n1, 0) + 2, max(n2, 0) + 2)
+    cells, volume, nan = np.zeros((_MAXLEV,) + shape, dtype=np.int64), np.zeros(shape), C.c_longlong(0)
+    check(lib.vdn_pdf2(nlev, mla.h, handle_array(u), handle_array(s), dxc, bct.h if bct is not None else None, _pdf_field(field1), int(comp1), n1, float(lo1), float(hi1),
+                       _pdf_field(field2), int(comp2), n2, float(lo2), float(hi2), cells.ctypes.data_as(C.POINTER(C.c_longlong)),
+                       volume.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nan)))
+    e1 = float(lo1) + np.arange(n1 + 1) * ((float(hi1) - float(lo1)) / n1)
+    e2 = float(lo2) + np.arange(n2 + 1) * ((float(hi2) - float(lo2)) / n2)
+    e1[-1], e2[-1] = float(hi1), float(hi2)
+    return Pdf2(cells[:nlev], volume, nan.value, e1, e2)
+
+
 # ---- values at points and tracer particles (csrc/particles.hip; include/varden_amd.h states the definitions) ------------------------------
 def _dx3(dx):
     levs = dx if hasattr(dx[0], "__len__") else [dx]

@@ -84,6 +84,11 @@ class ProfileLayout(C.Structure):
     _fields_ = [(name, C.c_int) for name in ("nrow", "volume", "s", "ss", "u", "ru", "ruu", "sua", "s_min", "s_max", "u_min", "u_max")]
 
 
+class PdfLayout(C.Structure):
+    """mirror of ``vdn_pdf_layout``: the number of rows of vdn_pdf's result and the first row of every row group (vdn_pdf_layout fills it)"""
+    _fields_ = [(name, C.c_int) for name in ("nrow", "volume", "q", "s", "u", "ru", "ke")]
+
+
 # every symbol include/varden_amd.h declares: (restype, argtypes)
 _VP = C.c_void_p
 _PI = C.POINTER(C.c_int)
@@ -166,6 +171,11 @@ SIGNATURES = {
     "vdn_profile_layout_sizeof": (C.c_size_t, []),
     "vdn_profiles_nbins": (C.c_long, [C.c_int, _VP, C.c_int]),
     "vdn_profiles": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, C.c_int, C.c_long, _PD, C.POINTER(C.c_longlong)]),
+    "vdn_pdf_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(PdfLayout)]),
+    "vdn_pdf_layout_sizeof": (C.c_size_t, []),
+    "vdn_pdf": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _PD, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "vdn_pdf2": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                           C.POINTER(C.c_longlong), _PD, C.POINTER(C.c_longlong)]),
     "vdn_sample_points": (C.c_int, [C.c_int, _VP, _PVP, C.c_int, C.c_int, C.c_int, _PD, _VP, C.c_long, _PD, _PD, _PI]),
     "vdn_particles_create": (C.c_int, [C.c_long, _PD, _PVP]),
     "vdn_particles_destroy": (C.c_int, [_VP]),

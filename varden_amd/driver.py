@@ -212,6 +212,20 @@ class Varden:
         self.fill_state_ghosts()
         return adv.diagnostics(self.mla, self.uold, self.sold, self.dx, self.bct, vort=vort)
 
+    def pdf(self, field, comp, lo, hi, nbins=64):
+        """advance.pdf of the current state (uold, sold): counts, volume and conditional sums per slot of the axis (field, comp, lo, hi, nbins); field 'scalar' |
+        'velocity' | 'magvel' | 'vorticity', comp 0-based.  The vorticity reads one ghost layer of uold, so the ghost cells of the state are filled first, as
+        diagnostics() does; the other fields read none and nothing is filled."""
+        if adv._pdf_field(field) == adv.PDF_FIELDS["vorticity"]:
+            self.fill_state_ghosts()
+        return adv.pdf(self.mla, self.uold, self.sold, self.dx, self.bct, field, comp, lo, hi, nbins)
+
+    def pdf2(self, field1, comp1, lo1, hi1, nbins1, field2, comp2, lo2, hi2, nbins2):
+        """advance.pdf2 of the current state: the joint distribution of two bin fields, counts and volume only"""
+        if adv.PDF_FIELDS["vorticity"] in (adv._pdf_field(field1), adv._pdf_field(field2)):
+            self.fill_state_ghosts()
+        return adv.pdf2(self.mla, self.uold, self.sold, self.dx, self.bct, field1, comp1, lo1, hi1, nbins1, field2, comp2, lo2, hi2, nbins2)
+
     def profiles(self, axis=None):
         """advance.profiles of the current state (uold, sold) along `axis` (0-based; default: the last direction, dm - 1): the plane sums per bin, the exact extrema
         and the cell counts.  No ghost cell is read, so nothing is filled first."""
@@ -581,6 +595,21 @@ class VardenAMR:
         the copy's extent along z, the vorticity is the 3-D rule's |curl u|; nothing is rescaled."""
         self.fill_state_ghosts()
         return adv.diagnostics(self.mla, self.uold, self.sold, self.dx, self.bct, vort=vort)
+
+    def pdf(self, field, comp, lo, hi, nbins=64):
+        """advance.pdf of the current state (uold, sold) over the composite grid: counts, volume and conditional sums per slot of the axis (field, comp, lo, hi, nbins); field 'scalar' |
+        'velocity' | 'magvel' | 'vorticity', comp 0-based.  The vorticity reads one ghost layer of uold, so the ghost cells of the state are filled first, as
+        diagnostics() does; the other fields read none and nothing is filled.  An extruded 2-D copy reports the 3-D COPY's
+        figures, as diagnostics() does: dm = 3, the volume carries the copy's extent along z, the vorticity is the 3-D rule's |curl u|."""
+        if adv._pdf_field(field) == adv.PDF_FIELDS["vorticity"]:
+            self.fill_state_ghosts()
+        return adv.pdf(self.mla, self.uold, self.sold, self.dx, self.bct, field, comp, lo, hi, nbins)
+
+    def pdf2(self, field1, comp1, lo1, hi1, nbins1, field2, comp2, lo2, hi2, nbins2):
+        """advance.pdf2 of the current state: the joint distribution of two bin fields, counts and volume only"""
+        if adv.PDF_FIELDS["vorticity"] in (adv._pdf_field(field1), adv._pdf_field(field2)):
+            self.fill_state_ghosts()
+        return adv.pdf2(self.mla, self.uold, self.sold, self.dx, self.bct, field1, comp1, lo1, hi1, nbins1, field2, comp2, lo2, hi2, nbins2)
 
     def profiles(self, axis=None):
         """advance.profiles of the current state (uold, sold) over the composite grid along `axis` (0-based; default: the last direction, dm - 1); the bins are the planes

@@ -19,7 +19,8 @@ DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step
                 mg_bottom_solver=-1, hg_bottom_solver=-1, max_mg_bottom_nlevels=1000,
                 bcx_lo=14, bcx_hi=14, bcy_lo=14, bcy_hi=14, bcz_lo=14, bcz_hi=14,
                 fixed_dt=-1.0, plot_int=0, chk_int=0, restart=-1, plot_base_name="plt", check_base_name="chk", grids_file_name="", job_name="", fixed_grids="",
-                diag_int=0, diag_file_name="varden_diag.out", prof_int=0, prof_axis=-1, prof_base_name="prof",          # (these two and the particle keys are the project's own, like tag_field)
+                diag_int=0, diag_file_name="varden_diag.out", prof_int=0, prof_axis=-1, prof_base_name="prof",          # (the diag_, prof_, pdf_ and particle keys are the project's own, like tag_field)
+                pdf_int=0, pdf_field="scalar", pdf_comp=1, pdf_lo=0.0, pdf_hi=0.0, pdf_nbins=64, pdf_base_name="pdf",
                 particle_lattice=(0, 0, 0), particle_int=0, particle_base_name="part")
 
 
@@ -137,13 +138,15 @@ def namelist_params(nl, dm=None):
     return prm
 
 
-def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, extrude_zbc=None, files="plane"):
+def build(text, device=0, max_grid_size_cap=None, outdir=".", extrude_nz=16, extrude_zbc=None, files="plane", nl=None):
     """the driver object for an inputs text: Varden (one level) or VardenAMR (max_levs > 1, grids from the tagged initial data);
     restart >= 0: grids and state from the checkpoint <outdir>/<check_base_name><restart:05d> (src/varden.f90:94-97).
-    files: what a 2-D hierarchy (run as its z-uniform 3-D copy) writes and restarts from -- "plane": the 2-D run's own dm = 2 files, "copy": the 3-D copy's"""
+    files: what a 2-D hierarchy (run as its z-uniform 3-D copy) writes and restarts from -- "plane": the 2-D run's own dm = 2 files, "copy": the 3-D copy's.
+    nl: the namelist of `text` over DEFAULTS where the caller has parsed it already (run has)"""
     assert files in ("plane", "copy"), files
-    nl = dict(DEFAULTS)
-    nl.update(parse_namelist(text))
+    if nl is None:
+        nl = dict(DEFAULTS)
+        nl.update(parse_namelist(text))
     dm = int(nl["dim_in"])
     prm = namelist_params(nl)
     for name in ("u_bc", "v_bc", "w_bc", "rho_bc", "trac_bc"):           # inflow data, probin.template:21-23: name(direction, side)
@@ -267,7 +270,38 @@ def profile_text(P, istep, time):
     return head + "".join(body)
 
 
-def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None, particles=None, particle_int=None, prof_int=None, prof_axis=None):
+def pdf_text(P, istep, time):
+    """a pdf file (pdf_int > 0): the format tag, dm, the field's name, comp (numbered from 1), nbins, lo, hi, step, time and nan_cells on a header line each, the column
+    names, then one line per slot -- "below", the bins, "above": the slot centre lo + (m + 0.5) w for m = -1 .. nbins (es27.17e3), the cells of all levels (i16), every
+    row of advance.pdf_columns (es27.17e3): the layout of a profile file (profile_text)."""
+    cols = adv.pdf_columns(P.nscal, P.dm)
+    name = P.field if isinstance(P.field, str) else {v: k for k, v in adv.PDF_FIELDS.items()}[int(P.field)]
+    head = "# VDN_PDF 1\n# dm %d\n# field %s\n# comp %d\n# nbins %d\n# lo%s\n# hi%s\n# step %d\n# time%s\n# nan_cells %d\n" % (
+        P.dm, name, P.comp + 1, P.nbins, plotfile._es(P.lo), plotfile._es(P.hi), istep, plotfile._es(time), P.nan_cells)
+    head += "#" + "centre".rjust(26) + "cells".rjust(16) + "".join(c.rjust(27) for c in cols) + "\n"
+    total = P.cells.sum(axis=0)
+    body = ["".join([plotfile._es(P.centres[m]), "%16d" % total[m]] + [plotfile._es(v) for v in P.rows[:, m]]) + "\n" for m in range(P.nbins + 2)]
+    return head + "".join(body)
+
+
+def pdf_keys(nl, pdf_int=None, pdf_field=None, pdf_comp=None, pdf_range=None, pdf_nbins=None):
+    """the pdf keys of a namelist with the arguments over them: (pdf_int, field name, comp numbered from 1, lo, hi, nbins).  With pdf_int > 0 a range with lo < hi and a
+    known field are required"""
+    k = int(nl["pdf_int"]) if pdf_int is None else int(pdf_int)
+    field = str(nl["pdf_field"] if pdf_field is None else pdf_field).strip()
+    comp = int(nl["pdf_comp"]) if pdf_comp is None else int(pdf_comp)
+    lo, hi = (float(nl["pdf_lo"]), float(nl["pdf_hi"])) if pdf_range is None else (float(pdf_range[0]), float(pdf_range[1]))
+    nbins = int(nl["pdf_nbins"]) if pdf_nbins is None else int(pdf_nbins)
+    if k > 0:
+        if not lo < hi:
+            raise ValueError("inputs: pdf_int > 0 needs a range: pdf_lo = %r < pdf_hi = %r" % (lo, hi))
+        if field not in adv.PDF_FIELDS:
+            raise ValueError("inputs: pdf_field = %r: one of %s" % (field, ", ".join(sorted(adv.PDF_FIELDS))))
+    return k, field, comp, lo, hi, nbins
+
+
+def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None, particles=None, particle_int=None, prof_int=None, prof_axis=None,
+        pdf_int=None, pdf_field=None, pdf_comp=None, pdf_range=None, pdf_nbins=None):
     """the time loop of src/varden.f90:237-371 for max_step steps (or until stop_time); plot / checkpoint files at step 0 of a fresh
     run and after every plot_int-th / chk_int-th step (:207-221, :349-361) under outdir.  diag_int > 0 (the namelist's key, or the argument over it): the run
     diagnostics of the state the run starts from and after every diag_int-th step, one line each under a header line, in <outdir>/<diag_file_name>; 0: no
@@ -275,8 +309,13 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
     them): moved by every step, <particle_base_name>NNNNN with positions, states, velocity and scalars at the start and after every particle_int-th step, a file
     Particles inside every checkpoint, read back by a restart; no lattice: no call, no file.  prof_int > 0 (the namelist's key, or the argument over it): the plane-averaged profiles
     (advance.profiles) of the state the run starts from and after every prof_int-th step along prof_axis (numbered from 1; -1: the problem's last direction), one
-    file <prof_base_name>NNNNN each (profile_text); 0: no call, no file"""
-    nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz, files=files)
+    file <prof_base_name>NNNNN each (profile_text); 0: no call, no file.  pdf_int > 0 (the namelist's key, or the argument over it): the distribution by value (advance.pdf)
+    of pdf_field / pdf_comp (numbered from 1) on [pdf_lo, pdf_hi) in pdf_nbins bins for the state the run starts from and after every pdf_int-th step, one file
+    <pdf_base_name>NNNNN each (pdf_text); pdf_range = (lo, hi) goes over pdf_lo and pdf_hi; 0: no call, no file"""
+    nl = dict(DEFAULTS)
+    nl.update(parse_namelist(text))
+    pdf_int, pdf_field, pdf_comp, pdf_lo, pdf_hi, pdf_nbins = pdf_keys(nl, pdf_int, pdf_field, pdf_comp, pdf_range, pdf_nbins)      # (refused before anything is built)
+    nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz, files=files, nl=nl)
     max_step = int(nl["max_step"]) if nsteps is None else nsteps
     stop_time = float(nl["stop_time"])
     plot_int, chk_int = int(nl["plot_int"]), int(nl["chk_int"])
@@ -331,12 +370,20 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             f.write(profile_text(G.profiles(int(nl["dim_in"]) - 1 if prof_axis < 1 else prof_axis - 1), G.istep, G.time))
         G.files_written.append(path)
 
+    def pdf():
+        path = os.path.join(outdir, "%s%05d" % (nl["pdf_base_name"], G.istep))
+        with open(path, "w") as f:
+            f.write(pdf_text(G.pdf(pdf_field, pdf_comp - 1, pdf_lo, pdf_hi, pdf_nbins), G.istep, G.time))
+        G.files_written.append(path)
+
     if diag_int > 0:
         with open(diag_path, "w") as f:
             f.write(diag_header(G.nscal, G.dm))
         diag()
     if prof_int > 0:
         prof()
+    if pdf_int > 0:
+        pdf()
     if int(nl["restart"]) < 0:
         dump()
         if G.particles is not None and particle_int > 0:
@@ -352,6 +399,8 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             diag()
         if prof_int > 0 and G.istep % prof_int == 0:
             prof()
+        if pdf_int > 0 and G.istep % pdf_int == 0:
+            pdf()
         if G.particles is not None and particle_int > 0 and G.istep % particle_int == 0:
             particle_file()
         dump()
