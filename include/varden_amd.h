@@ -142,7 +142,9 @@ const char *vdn_debug_switches(void);
  * the same objects with the switch table and the test-transport seam compiled in (the test suite, the A/B tools, the one-GPU transport rehearsal).
  * The testing build alone also exports `unsigned vdn_nd_prolong_fused_levels(void)`: bit l is set when level l of the last nodal solve took its coarse
  * correction inside the first post-smoothing march (the read-back of tests/test_nd_prolong_fused_gpu.py; not part of the product's interface), and
- * `unsigned vdn_nd_lds_levels(void)`: bit l is set when level l of the last nodal solve ran as one launch down and one up (tests/test_nd_lds_levels_gpu.py). */
+ * `unsigned vdn_nd_lds_levels(void)`: bit l is set when level l of the last nodal solve ran as one launch down and one up (tests/test_nd_lds_levels_gpu.py), and
+ * `int vdn_last_tail_form(int which)`: the body the last one-workgroup tail cycle of a cell-centred (which = 0) or the nodal (1) solve took, 0: on global memory,
+ * 1: levels in LDS (tests/test_tail_cycles_gpu.py). */
 const char *vdn_build_flavour(void);
 int  vdn_finalize(void);
 const char *vdn_last_error(void);

@@ -16,6 +16,7 @@
 #include "mg_stop.h"
 #include "krylov_wg.h"
 #include "krylov_grid.h"
+#include "tail_plan.h"
 #include <chrono>
 #include <tuple>
 #include <algorithm>
@@ -811,6 +812,137 @@ template <bool KRYLOV> __global__ void __launch_bounds__(1024) kk_cc_tailcycle(C
     if (l < T.nlev - 1) { wg_cc_up(T.L[l], T.L[l + 1]); wg_cc_gsrb(T.L[l], T.nu2, T.per); }
 }
 
+// ---- the same cycle with its levels in LDS and the per-cell constants in registers ----------------------------------------------------------------
+// A phase of the body above (the work between two barriers) handles at most 512 cells and costs ~1 us: three integer divisions to find the cell, six face
+// coefficients, the right-hand side and seven phi from global memory, diag once more, a global store and the wait for it in front of the barrier -- 38 times
+// per launch.  Here a thread owns one cell of every level (tail_plan.h), and on entering the kernel it finds that cell, loads the cell's coefficients and
+// forms diag, once, by cc_apply_vals, the expressions of cc_apply: the same doubles as before.  phi of every level lives in LDS with its ghost layer, the
+// residual passes through LDS to the restriction, and a coarse right-hand side is born in the register of the thread that owns the coarse cell.  A colour pass
+// is then six LDS reads, cc_apply_vals, one division, one LDS write and the barrier.  Same passes in the same order, same expressions: the same bits
+// (tests/test_tail_cycles_gpu.py holds it equal to the launch-by-launch form, VDN_MG_TAILCYCLE=0).
+//   Periodic boxes: kept.  The owner of a cell next to a periodic face writes the ghost image together with the cell, which is what the fill in front of the
+//   next pass copied; tail_plan refuses a periodic axis of odd extent (the cell across the face would have the same colour and read the image while it is written).
+//   Two phases fewer than the body above: the restriction writes registers only, and the zeroing of the coarse phi rides in the residual's phase.
+//   Krylov bottom solvers and level sets that tail_plan refuses keep the body above (cc_small_end).
+//   (Built, measured and dropped: the levels of at most 64 points -- 4^3 and 2^3 cells, 3^3 nodes -- run by the first wave alone with a wavefront fence in
+//   place of the workgroup barrier between its phases, the other waves waiting at one barrier.  Same bits; 16.4 -> 16.2 us here, 22.0 -> 22.5 us in the nodal
+//   kernel, the benchmark 23.84 .. 23.96 -> 23.96 .. 24.08 ms per step: a phase of one wave costs its chain of dependent instructions, not the barrier.)
+//   Global memory on exit: phi, rh (levels below the first) and res (levels above the last) of every level, as the body above leaves them -- phi of the first
+//   level is what the caller reads; the deeper arrays have no reader before the next cycle overwrites them (cc_fmg starts at levels of >= 4096 cells, the
+//   Krylov statistics come from its own kernel), but three stores per thread after the last barrier cost nothing, so nothing depends on that finding.
+//   The ghost cells of the global phi arrays are left alone: non-periodic ones stay zero, periodic ones are refreshed by every reader (cc_periodic_t, cc_halo).
+struct CcTailLdsArgs { CLev L[TAIL_MAX_LEVELS]; TailPlan P; int nu1, nu2, nbot, per[3]; };
+struct CcOwn {
+  double b[6], a0, rh, diag, res;      // bxm, bxp, bym, byp, bzm, bzp (cc_apply_vals' order); res: the residual of the level's visit, stored on exit
+  long gc;                             // the cell in the level's global arrays
+  int lc, rc, up;                      // the cell in the level's LDS phi; in the residual array; its parent in the next level's LDS phi
+  int fine;                            // the first of its eight children in the residual array (levels below the first)
+  int colour, img;                     // img: bit 2d + s set -- the cell lies at side s of periodic axis d
+  bool ok;
+};
+DEVI void cct_enter(const CcTailLdsArgs &T, int l, CcOwn &o) {
+  const CLev &L = T.L[l]; const TailLevel &P = T.P.L[l];
+  int i, j, k;
+  o.ok = tail_owner(TAIL_CELLS, P.n, threadIdx.x, i, j, k, o.colour);
+  o.gc = cidx(L, i, j, k);
+  o.lc = P.phi + tail_index(P, i, j, k);
+  o.rc = T.P.res + i + P.n[0] * (j + P.n[1] * k);
+  o.up = l + 1 < T.P.nlev ? T.P.L[l + 1].phi + tail_index(T.P.L[l + 1], i >> 1, j >> 1, k >> 1) : 0;
+  o.fine = l > 0 ? T.P.res + 2 * i + T.P.L[l - 1].n[0] * (2 * j + T.P.L[l - 1].n[1] * 2 * k) : 0;
+  o.img = 0;
+  const int q[3] = { i, j, k };
+  for (int d = 0; d < 3; d++) if (T.per[d]) { if (q[d] == 0) o.img |= 1 << (2 * d); if (q[d] == P.n[d] - 1) o.img |= 2 << (2 * d); }
+  const long sy = L.PX, sz = (long)L.PX * L.PY;
+  for (int m = 0; m < 6; m++) o.b[m] = 0.0;
+  o.a0 = 0.0; o.rh = 0.0; o.res = 0.0;
+  if (o.ok) {
+    o.b[0] = L.b[0][o.gc]; o.b[1] = L.b[0][o.gc + 1];
+    o.b[2] = L.b[1][o.gc]; o.b[3] = L.b[1][o.gc + sy];
+    o.b[4] = L.b[2][o.gc]; o.b[5] = L.b[2][o.gc + sz];
+    if (L.alpha) o.a0 = L.alpha[o.gc];
+    if (l == 0) o.rh = L.rh[o.gc];
+  }
+  const double p[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+  double Ap; cc_apply_vals(L, p, o.b, o.a0, L.alpha != nullptr, Ap, o.diag);
+}
+// A phi of the thread's cell from the level's LDS array
+DEVI double cct_apply(const CLev &L, const TailLevel &P, const double *lds, const CcOwn &o, double &p0) {
+  const int sy = P.e[0], sz = P.e[0] * P.e[1];
+  const double p[7] = { lds[o.lc], lds[o.lc - 1], lds[o.lc + 1], lds[o.lc - sy], lds[o.lc + sy], lds[o.lc - sz], lds[o.lc + sz] };
+  double Ap, diag; cc_apply_vals(L, p, o.b, o.a0, L.alpha != nullptr, Ap, diag);
+  p0 = p[0];
+  return Ap;
+}
+// phi of the thread's cell and its periodic images
+DEVI void cct_put(const TailLevel &P, double *lds, const CcOwn &o, double v) {
+  lds[o.lc] = v;
+  if (o.img) {
+    const int st[3] = { 1, P.e[0], P.e[0] * P.e[1] };
+    #pragma unroll
+    for (int d = 0; d < 3; d++) {
+      if (o.img & (1 << (2 * d))) lds[o.lc + P.n[d] * st[d]] = v;
+      if (o.img & (2 << (2 * d))) lds[o.lc - P.n[d] * st[d]] = v;
+    }
+  }
+}
+DEVI void cct_gsrb(const CLev &L, const TailLevel &P, double *lds, const CcOwn &o, int nsweeps) {
+  for (int s = 0; s < nsweeps; s++) for (int color = 0; color < 2; color++) {
+    if (o.ok && o.colour == color) {
+      double p0; const double Ap = cct_apply(L, P, lds, o, p0);
+      if (o.diag != 0.0) cct_put(P, lds, o, p0 + (o.rh - Ap) / o.diag);
+    }
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(TAIL_THREADS) kk_cc_tailcycle_lds(CcTailLdsArgs T) {
+  __shared__ double lds[TAIL_LDS_DOUBLES];
+  CcOwn o[TAIL_MAX_LEVELS];
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS; l++) if (l < T.P.nlev) cct_enter(T, l, o[l]);
+  {   // phi of the first level as the caller left it (zero inside a V-cycle), ghost layer included: behind a periodic face the image, as the fill would write it
+    const CLev &L = T.L[0]; const TailLevel &P = T.P.L[0];
+    for (int t = threadIdx.x; t < tail_array(P); t += TAIL_THREADS) {
+      int q[3] = { t % P.e[0] - 1, (t / P.e[0]) % P.e[1] - 1, t / (P.e[0] * P.e[1]) - 1 };
+      for (int d = 0; d < 3; d++) if (T.per[d]) { if (q[d] < 0) q[d] += P.n[d]; else if (q[d] >= P.n[d]) q[d] -= P.n[d]; }
+      lds[P.phi + t] = L.phi[cidx(L, q[0], q[1], q[2])];
+    }
+  }
+  __syncthreads();
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS - 1; l++)
+    if (l < T.P.nlev - 1) {
+      const CLev &L = T.L[l]; const TailLevel &P = T.P.L[l], &PC = T.P.L[l + 1];
+      cct_gsrb(L, P, lds, o[l], T.nu1);
+      if (o[l].ok) { double p0; o[l].res = o[l].rh - cct_apply(L, P, lds, o[l], p0); lds[o[l].rc] = o[l].res; }
+      for (int t = threadIdx.x; t < tail_array(PC); t += TAIL_THREADS) lds[PC.phi + t] = 0.0;      // the error equation starts from zero, ghost layer included
+      __syncthreads();
+      if (o[l + 1].ok) {
+        const double *r = lds; const int f = o[l + 1].fine, sy = P.n[0], sz = P.n[0] * P.n[1];
+        const double s = r[f] + r[f + 1] + r[f + sy] + r[f + sy + 1] + r[f + sz] + r[f + sz + 1] + r[f + sz + sy] + r[f + sz + sy + 1];
+        o[l + 1].rh = s * 0.125;
+      }
+      // (no barrier: nothing in LDS was written, and the residual array is not written again before the next level's residual, barriers away)
+      if (T.nu1 == 0) __syncthreads();      // ... unless there are no sweeps between the two
+    }
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS; l++)
+    if (l == T.P.nlev - 1) cct_gsrb(T.L[l], T.P.L[l], lds, o[l], T.nbot);
+  #pragma unroll
+  for (int l = TAIL_MAX_LEVELS - 2; l >= 0; l--)
+    if (l < T.P.nlev - 1) {
+      if (o[l].ok) cct_put(T.P.L[l], lds, o[l], lds[o[l].lc] + lds[o[l].up]);
+      __syncthreads();
+      cct_gsrb(T.L[l], T.P.L[l], lds, o[l], T.nu2);
+    }
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS; l++)
+    if (l < T.P.nlev && o[l].ok) {
+      T.L[l].phi[o[l].gc] = lds[o[l].lc];
+      if (l > 0) T.L[l].rh[o[l].gc] = o[l].rh;
+      if (l < T.P.nlev - 1) T.L[l].res[o[l].gc] = o[l].res;
+    }
+}
+
 // ---- levels of 16^3 .. 64^3 cells: one launch down, one launch up (round 3) ------------------------------------------------------------------
 // Below the 128^3 level a V-cycle is a chain of ~5 us launches: eleven per level and cycle (four colour passes, residual, restriction;
 // prolongation, four colour passes), each waiting for the one before -- ~300 launches per MAC solve on the 64^3, 32^3 and 16^3 levels of a 256^3
@@ -1513,7 +1645,9 @@ static void cc_bottom_t(const CCMG &M, const CLev &L) {      // max(nub, N^2) sw
 }
 // The small end of the hierarchy in one launch (kk_cc_tailcycle): distributed levels dl .. end when they are one box of at most 8^3 cells
 // each (dl < 0: none), then the replicated tail levels tl .. end (one rank and one box: the gather between the two is the plain restriction).
+static int g_cc_tail_form = 0;
 static bool cc_small_end(const CCMG &M, int dl, int tl) {
+  g_cc_tail_form = 0;
   if (!sw().mg_tailcycle) return false;
   static const long tail_cells = SMALL_LEVEL_CELLS;     // largest level the one-workgroup cycle takes (measured: 16^3 no gain, MAC 15.33 -> 15.39 ms)
   const vdn_params &P = ctx().prm;
@@ -1537,10 +1671,26 @@ static bool cc_small_end(const CCMG &M, int dl, int tl) {
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.mg_nu1; T.nu2 = P.mg_nu2; T.nbot = std::max(P.mg_nub, N * N);      // cc_bottom_t / cc_vcycle_d
   for (int d = 0; d < 3; d++) T.per[d] = M.per[d];
-  if (M.kry.w) hipLaunchKernelGGL(kk_cc_tailcycle<true>, dim3(1), dim3(1024), 0, ctx().stream, T, KrylovTailArgs{ mg_krylov_args(M.kry, 0, P.mg_bottom_solver_eps), M.kry.method, M.kry_singular });
-  else hipLaunchKernelGGL(kk_cc_tailcycle<false>, dim3(1), dim3(1024), 0, ctx().stream, T, NoKrylovTailArgs{});
+  g_cc_tail_form = 0;
+  if (M.kry.w) { hipLaunchKernelGGL(kk_cc_tailcycle<true>, dim3(1), dim3(1024), 0, ctx().stream, T, KrylovTailArgs{ mg_krylov_args(M.kry, 0, P.mg_bottom_solver_eps), M.kry.method, M.kry_singular }); return true; }
+  // the sweeps: levels in LDS, per-cell constants in registers (kk_cc_tailcycle_lds) wherever tail_plan takes the level set
+  int tn[TAIL_MAX_LEVELS][3] = {};
+  for (int l = 0; l < std::min(nl, TAIL_MAX_LEVELS); l++) for (int d = 0; d < 3; d++) tn[l][d] = T.L[l].n[d];
+  const TailPlan TP = tail_plan(TAIL_CELLS, nl, tn, T.per);
+  if (TP.fits) {
+    CcTailLdsArgs A; memset(&A, 0, sizeof A);
+    for (int l = 0; l < nl; l++) A.L[l] = T.L[l];
+    A.P = TP; A.nu1 = T.nu1; A.nu2 = T.nu2; A.nbot = T.nbot;
+    for (int d = 0; d < 3; d++) A.per[d] = T.per[d];
+    hipLaunchKernelGGL(kk_cc_tailcycle_lds, dim3(1), dim3(TAIL_THREADS), 0, ctx().stream, A);
+    g_cc_tail_form = 1;
+    return true;
+  }
+  hipLaunchKernelGGL(kk_cc_tailcycle<false>, dim3(1), dim3(1024), 0, ctx().stream, T, NoKrylovTailArgs{});
   return true;
 }
+// testing build (vdn_last_tail_form): the body the last tail cycle of a MAC or viscous solve took -- 0: on global memory, 1: levels in LDS
+int cc_last_tail_form() { return g_cc_tail_form; }
 // may tail level l run as kk_cc_lds_down / kk_cc_lds_up?  (round 6: the replicated levels of 16^3 .. 64^3 cells take the two-launch form of the one-box hierarchy too --
 // they were eleven launches per level and cycle; cc_lds_level's conditions)
 static bool cc_lds_tail_level(const CCMG &M, int l) {

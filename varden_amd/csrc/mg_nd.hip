@@ -16,6 +16,7 @@
 #include "krylov_wg.h"
 #include "krylov_grid.h"
 #include "nd_lds_plan.h"
+#include "tail_plan.h"
 #include <tuple>
 #include <algorithm>
 
@@ -63,17 +64,24 @@ DEVI NdW nd_weights(const double f[3]) {
   W.iso = (W.w1 == 0.0 && W.w2 == 0.0 && W.w4 == 0.0);
   return W;
 }
-DEVI void nd_stencil(const NdW &W, const double p[3][3][3], const double sg[2][2][2], double &Kp, double &diag) {
-  double cz[2][2], cy[2][2], cx[2][2];
+// The stencil in two halves: what depends on sigma alone (NdCoef: the eight sigmas, the twelve pair sums, diag = w0 S8) and its application to phi.  nd_stencil
+// runs one after the other; the tail cycle in LDS (kk_nd_tailcycle_lds) forms the first half once per visit of a level and applies it in every phase.
+struct NdCoef { double sg[2][2][2], cz[2][2], cy[2][2], cx[2][2], dg; };
+DEVI void nd_stencil_coef(const NdW &W, const double sg[2][2][2], NdCoef &K) {
   #pragma unroll
   for (int b = 0; b < 2; b++)
     #pragma unroll
     for (int a = 0; a < 2; a++) {
-      cz[b][a] = sg[0][b][a] + sg[1][b][a];          // [dj][di]: the two cells that share an xy-diagonal neighbour
-      cy[b][a] = sg[b][0][a] + sg[b][1][a];          // [dk][di]: xz-diagonal
-      cx[b][a] = sg[b][a][0] + sg[b][a][1];          // [dk][dj]: yz-diagonal
+      K.sg[0][b][a] = sg[0][b][a]; K.sg[1][b][a] = sg[1][b][a];
+      K.cz[b][a] = sg[0][b][a] + sg[1][b][a];          // [dj][di]: the two cells that share an xy-diagonal neighbour
+      K.cy[b][a] = sg[b][0][a] + sg[b][1][a];          // [dk][di]: xz-diagonal
+      K.cx[b][a] = sg[b][a][0] + sg[b][a][1];          // [dk][dj]: yz-diagonal
     }
-  const double S8 = (cz[0][0] + cz[0][1]) + (cz[1][0] + cz[1][1]);
+  const double S8 = (K.cz[0][0] + K.cz[0][1]) + (K.cz[1][0] + K.cz[1][1]);
+  K.dg = W.w0 * S8;
+}
+DEVI void nd_stencil_apply(const NdW &W, const double p[3][3][3], const NdCoef &K, double &Kp) {
+  const auto &sg = K.sg; const auto &cz = K.cz; const auto &cy = K.cy; const auto &cx = K.cx;
   // the weights of a row sum to zero (K 1 = 0), so K phi = sum of coefficient * (phi_neighbour - phi_node): differences first, which
   // keeps the terms at the size of the answer instead of the size of diag * phi (at 256^3 the plain sum stalls at a residual of
   // ~2e-12 |rhs|, short of the 1e-12 of hgproject.f90:113-114)
@@ -85,7 +93,6 @@ DEVI void nd_stencil(const NdW &W, const double p[3][3][3], const double sg[2][2
   double A3 = cz[0][0] * D(1, 0, 0); A3 = fma(cz[0][1], D(1, 0, 2), A3); A3 = fma(cz[1][0], D(1, 2, 0), A3); A3 = fma(cz[1][1], D(1, 2, 2), A3);
   double A5 = cy[0][0] * D(0, 1, 0); A5 = fma(cy[0][1], D(0, 1, 2), A5); A5 = fma(cy[1][0], D(2, 1, 0), A5); A5 = fma(cy[1][1], D(2, 1, 2), A5);
   double A6 = cx[0][0] * D(0, 0, 1); A6 = fma(cx[0][1], D(0, 2, 1), A6); A6 = fma(cx[1][0], D(2, 0, 1), A6); A6 = fma(cx[1][1], D(2, 2, 1), A6);
-  const double dg = W.w0 * S8;
   double acc = W.w3 * A3;
   acc = fma(W.w5, A5, acc); acc = fma(W.w6, A6, acc); acc = fma(W.w7, A7, acc);
   if (!W.iso) {                                      // uniform over the launch
@@ -95,7 +102,13 @@ DEVI void nd_stencil(const NdW &W, const double p[3][3][3], const double sg[2][2
     acc = fma(W.w1, A1, acc); acc = fma(W.w2, A2, acc); acc = fma(W.w4, A4, acc);
   }
   #undef D
-  Kp = acc; diag = dg;
+  Kp = acc;
+}
+DEVI void nd_stencil(const NdW &W, const double p[3][3][3], const double sg[2][2][2], double &Kp, double &diag) {
+  NdCoef K;
+  nd_stencil_coef(W, sg, K);
+  nd_stencil_apply(W, p, K, Kp);
+  diag = K.dg;
 }
 // from a level in the multigrid layout
 DEVI void nd_apply(const NLev &L, const double *__restrict__ phi, int i, int j, int k, double &Kp, double &diag) {
@@ -607,8 +620,8 @@ __global__ void kk_nd_restrict(NLev F, NLev C) {
 // strided reads of the plain kernel are served by L2 lines the neighbouring threads share anyway)
 // trilinear interpolation of the coarse field at fine node offsets (oi,oj,ok) of coarse node (I,J,K): the eight coarse values are
 // loaded in one unconditional batch and added under predicates in the order (c,b,a) ascending of the oracle's loops
-DEVI double nd_interp8(const NLev &C, const double *__restrict__ cp, int I, int J, int K, int oi, int oj, int ok) {
-  const long c0 = nidx(C, I, J, K), sy = C.PX, sz = (long)C.PX * C.PY;
+// (nd_interp8_at: the same from any array, c0 the index of the coarse node, sy and sz its strides)
+DEVI double nd_interp8_at(const double *__restrict__ cp, long c0, long sy, long sz, int oi, int oj, int ok) {
   const double v000 = cp[c0], v100 = cp[c0 + 1], v010 = cp[c0 + sy], v110 = cp[c0 + sy + 1];
   const double v001 = cp[c0 + sz], v101 = cp[c0 + sz + 1], v011 = cp[c0 + sz + sy], v111 = cp[c0 + sz + sy + 1];
   double s = 0.0;
@@ -621,6 +634,9 @@ DEVI double nd_interp8(const NLev &C, const double *__restrict__ cp, int I, int 
   s = (ok && oj) ? s + v011 : s;
   s = (ok && oi && oj) ? s + v111 : s;
   return s * (1.0 / (double)((1 + oi) * (1 + oj) * (1 + ok)));
+}
+DEVI double nd_interp8(const NLev &C, const double *__restrict__ cp, int I, int J, int K, int oi, int oj, int ok) {
+  return nd_interp8_at(cp, nidx(C, I, J, K), C.PX, (long)C.PX * C.PY, oi, oj, ok);
 }
 // phi_F += the interpolated phi_C (nd_interp8's sums, in its order), k-marching: a thread owns a fine (i,j) column of a slab of planes and keeps the four
 // coarse values of planes K and K+1 in registers -- 4 coarse loads per TWO fine planes instead of 8 per node.  c0: the coarse index of the box's node 0
@@ -979,8 +995,10 @@ template <bool REF> struct NdKrylovT {
 using NdKrylov = NdKrylovT<false>;
 using NdKrylovRef = NdKrylovT<true>;
 // The small end of a V-cycle in one launch.  KRYLOV: the Krylov solve in place of the nbot sweeps (Q: its arguments; nothing in the sweeps instantiation)
-// (The same with the levels copied into LDS for the duration was measured at 66 us per cycle against 57 us on the L2-resident arrays: a phase costs
-// ~2.5 us of dependent instructions of one wave per SIMD, not memory latency.)
+// (An early trial copied the levels into LDS for the duration and changed nothing else: 66 us per cycle against 57 us on the L2-resident arrays -- a phase
+// costs dependent instructions of one wave per SIMD, not memory latency.  What that trial lacked is taking those instructions out of the phases:
+// kk_nd_tailcycle_lds below forms the per-node constants once per visit of a level and then keeps phi in LDS, 22.0 us per launch against this body's 37.6 us,
+// 1.2 us per phase against 1.9 (profiles/tail_cycles_ab.txt).  This body stays for the Krylov bottom solvers, periodic boxes and level sets tail_plan refuses.)
 template <bool KRYLOV> __global__ void __launch_bounds__(1024) kk_nd_tailcycle(NdTailArgs T, KrylovTail<KRYLOV> Q) {
   double *ph[ND_TAIL_MAX], *tm[ND_TAIL_MAX];
   #pragma unroll
@@ -997,6 +1015,155 @@ template <bool KRYLOV> __global__ void __launch_bounds__(1024) kk_nd_tailcycle(N
   #pragma unroll
   for (int l = ND_TAIL_MAX - 2; l >= 0; l--)
     if (l < T.nlev - 1) { wg_nd_up(T.L[l], ph[l], T.L[l + 1], ph[l + 1]); wg_nd_jacobi(T.L[l], ph[l], tm[l], T.nu2, T.omega); }
+}
+
+// ---- the same cycle with its levels in LDS and the per-node constants in registers ----------------------------------------------------------------
+// What the LDS trial quoted above lacked: it moved phi and nothing else, and a phase went on decoding (i, j, k) by three divisions, testing nd_is_dir, loading
+// eight sigmas and forming the twelve pair sums, S8 and diag for every node -- the dependent instructions that cost the time.  Here a thread owns one node of
+// every level (tail_plan.h).  On every visit of a level, on the way down and again on the way up, it forms nd_stencil's coefficient half (nd_stencil_coef: the
+// same expressions, the same doubles) from the level's sigma, which the kernel copies into LDS once; a sweep is then 27 LDS reads, nd_stencil_apply, one
+// division, one LDS write and the barrier.  The ping-pong of the sweeps, the residual and the coarse phi live in LDS, a coarse right-hand side is born in the
+// register of the thread that owns the coarse node, and the restriction shares its phase with the next level's first sweep.  Same sweeps, same order: same bits.
+//   Periodic boxes, Krylov bottom solvers and level sets that tail_plan refuses keep the body above (nd_small_end).
+//   Global memory on exit: of every level the result in the array the host's swap parity names (phi after an even number of sweeps, tmp after an odd one), b of
+//   the levels below the first and res of the levels above the last, as the body above leaves them.  The other array of the ping-pong, which the body above
+//   leaves holding the last sweep's input, is not written: every sweep, restriction and load that writes into it (nd_jacobi_*, kk_nd_bottom, wg_nd_jacobi,
+//   kk_nd_restrict's zeroing) writes all nodes 0 .. n before anything reads them, and its ghost nodes stay the zeros they are.
+struct NdTailLdsArgs { NLev L[TAIL_MAX_LEVELS]; TailPlan P; int nu1, nu2, nbot; double omega, om1, om2; int nsp; };
+// the thread's node of one level: its indices packed (the LDS and global positions are a few integer operations away, and three levels' worth of them
+// kept in registers next to the 27 phi and the 21 coefficients of a sweep did not fit 128 VGPRs)
+struct NdOwn {
+  double b;                            // right-hand side of the thread's node
+  int ijk;                             // i | j << 10 | k << 20
+  bool ok, dir;
+  DEVI int i() const { return ijk & 1023; }
+  DEVI int j() const { return (ijk >> 10) & 1023; }
+  DEVI int k() const { return ijk >> 20; }
+  DEVI int lc(const TailLevel &P) const { return tail_index(P, i(), j(), k()); }                                     // the node in a ghosted LDS array
+  DEVI int sc(const TailLevel &P) const { return i() + (P.n[0] + 2) * (j() + (P.n[1] + 2) * k()); }                   // cell (i-1, j-1, k-1) in the sigma array
+};
+DEVI void ndt_enter(const NdTailLdsArgs &T, int l, NdOwn &o) {
+  const NLev &L = T.L[l]; const TailLevel &P = T.P.L[l];
+  int i, j, k, colour;
+  o.ok = tail_owner(TAIL_NODES, P.n, threadIdx.x, i, j, k, colour);
+  o.dir = nd_is_dir(L, i, j, k);
+  o.ijk = i | (j << 10) | (k << 20);
+  o.b = (l == 0 && o.ok) ? L.b[nidx(L, i, j, k)] : 0.0;
+}
+DEVI void ndt_coef(const NdW &W, const TailLevel &P, const double *lds, const NdOwn &o, NdCoef &K) {
+  const int sy = P.n[0] + 2, sz = (P.n[0] + 2) * (P.n[1] + 2);
+  const double *s = lds + P.sig + o.sc(P);
+  double sg[2][2][2];
+  #pragma unroll
+  for (int c = 0; c < 2; c++)
+    #pragma unroll
+    for (int b = 0; b < 2; b++)
+      #pragma unroll
+      for (int a = 0; a < 2; a++) sg[c][b][a] = s[a + b * sy + c * sz];
+  nd_stencil_coef(W, sg, K);
+}
+DEVI double ndt_apply(const NdW &W, const TailLevel &P, const double *src, int lc, const NdCoef &K, double &p0) {
+  const int sy = P.e[0], sz = P.e[0] * P.e[1];
+  double p[3][3][3];
+  #pragma unroll
+  for (int c = 0; c < 3; c++)
+    #pragma unroll
+    for (int b = 0; b < 3; b++)
+      #pragma unroll
+      for (int a = 0; a < 3; a++) p[c][b][a] = src[lc + (a - 1) + (b - 1) * sy + (c - 1) * sz];
+  double Kp; nd_stencil_apply(W, p, K, Kp);
+  p0 = p[1][1][1];
+  return Kp;
+}
+// cur: 0 when the level's phi array holds the iterate, 1 when tmp does
+DEVI void ndt_jacobi(const NdW &W, const TailLevel &P, double *lds, const NdOwn &o, const NdCoef &K, int &cur, int nsweeps, double omega, double om1 = 0.0, double om2 = 0.0, int nsp = 0) {
+  const int lc = o.lc(P);
+  for (int s = 0; s < nsweeps; s++) {
+    const double *src = lds + (cur ? P.tmp : P.phi);
+    double *dst = lds + (cur ? P.phi : P.tmp);
+    if (o.ok) {
+      double p0 = src[lc], v = p0;
+      if (!o.dir) {
+        const double Kp = ndt_apply(W, P, src, lc, K, p0);
+        v = p0;
+        if (K.dg != 0.0) v = p0 + (s < nsp ? (s == 0 ? om1 : om2) : omega) * ((o.b - Kp) / K.dg);
+      }
+      dst[lc] = v;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+__global__ void __launch_bounds__(TAIL_THREADS) kk_nd_tailcycle_lds(NdTailLdsArgs T) {
+  __shared__ double lds[TAIL_LDS_DOUBLES];
+  NdOwn o[TAIL_MAX_LEVELS];
+  int cur[TAIL_MAX_LEVELS];
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS; l++) { cur[l] = 0; if (l < T.P.nlev) ndt_enter(T, l, o[l]); }
+  // everything in LDS starts from zero: the ghost nodes of every array, and phi of the levels below the first (the error equation); then sigma of every
+  // level with its ghost cells, and phi of the first level as the caller left it
+  for (int t = threadIdx.x; t < T.P.total; t += TAIL_THREADS) lds[t] = 0.0;
+  __syncthreads();
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS; l++)
+    if (l < T.P.nlev) {
+      const NLev &L = T.L[l]; const TailLevel &P = T.P.L[l];
+      const int s0 = P.n[0] + 2, s1 = P.n[1] + 2, ns = s0 * s1 * (P.n[2] + 2);
+      for (int t = threadIdx.x; t < ns; t += TAIL_THREADS) lds[P.sig + t] = L.sig[nidx(L, t % s0 - 1, (t / s0) % s1 - 1, t / (s0 * s1) - 1)];
+      if (l == 0) for (int t = threadIdx.x; t < tail_array(P); t += TAIL_THREADS) lds[P.phi + t] = L.phi[nidx(L, t % P.e[0] - 1, (t / P.e[0]) % P.e[1] - 1, t / (P.e[0] * P.e[1]) - 1)];
+    }
+  __syncthreads();
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS - 1; l++)
+    if (l < T.P.nlev - 1) {
+      const TailLevel &P = T.P.L[l];
+      const NdW W = nd_weights(T.L[l].f);
+      NdCoef K; ndt_coef(W, P, lds, o[l], K);
+      ndt_jacobi(W, P, lds, o[l], K, cur[l], T.nu1, T.omega, T.om1, T.om2, T.nsp);
+      if (o[l].ok) {
+        double r = 0.0;
+        if (!o[l].dir) { double p0; r = o[l].b - ndt_apply(W, P, lds + (cur[l] ? P.tmp : P.phi), o[l].lc(P), K, p0); }
+        lds[P.res + o[l].lc(P)] = r;              // (stays there until the end of the launch: stored to global memory then)
+      }
+      __syncthreads();
+      if (o[l + 1].ok) {
+        double s = 0.0;
+        if (!o[l + 1].dir) s = nd_fw27(lds + P.res + tail_index(P, 2 * o[l + 1].i(), 2 * o[l + 1].j(), 2 * o[l + 1].k()), P.e[0], P.e[0] * P.e[1]);
+        o[l + 1].b = s * 0.125;
+      }
+      // (no barrier: nothing in LDS was written, and this residual array is not written again in this launch)
+    }
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS; l++)
+    if (l == T.P.nlev - 1) {
+      const NdW W = nd_weights(T.L[l].f);
+      NdCoef K; ndt_coef(W, T.P.L[l], lds, o[l], K);
+      ndt_jacobi(W, T.P.L[l], lds, o[l], K, cur[l], T.nbot, T.omega);
+    }
+  #pragma unroll
+  for (int l = TAIL_MAX_LEVELS - 2; l >= 0; l--)
+    if (l < T.P.nlev - 1) {
+      const TailLevel &P = T.P.L[l], &PC = T.P.L[l + 1];
+      double *fphi = lds + (cur[l] ? P.tmp : P.phi);
+      if (o[l].ok && !o[l].dir) {
+        const int i = o[l].i(), j = o[l].j(), k = o[l].k(), lc = o[l].lc(P);
+        fphi[lc] = fphi[lc] + nd_interp8_at(lds + (cur[l + 1] ? PC.tmp : PC.phi), tail_index(PC, i >> 1, j >> 1, k >> 1), PC.e[0], PC.e[0] * PC.e[1], i & 1, j & 1, k & 1);
+      }
+      __syncthreads();
+      const NdW W = nd_weights(T.L[l].f);
+      NdCoef K; ndt_coef(W, P, lds, o[l], K);
+      ndt_jacobi(W, P, lds, o[l], K, cur[l], T.nu2, T.omega);
+    }
+  #pragma unroll
+  for (int l = 0; l < TAIL_MAX_LEVELS; l++)
+    if (l < T.P.nlev && o[l].ok) {
+      const TailLevel &P = T.P.L[l];
+      const long gc = nidx(T.L[l], o[l].i(), o[l].j(), o[l].k());
+      const int lc = o[l].lc(P);
+      (cur[l] ? T.L[l].tmp : T.L[l].phi)[gc] = lds[(cur[l] ? P.tmp : P.phi) + lc];
+      if (l > 0) T.L[l].b[gc] = o[l].b;
+      if (l < T.P.nlev - 1) T.L[l].res[gc] = lds[P.res + lc];
+    }
 }
 
 // (round 3, built, measured and removed: the 17^3 .. 65^3 levels as one LDS-tiled launch down -- two Jacobi sweeps on a 16^3 region around a
@@ -1557,7 +1724,10 @@ static int nd_bottom_sweeps_global(const NDLev &DL) {
 }
 // The small end of the hierarchy in one launch (kk_nd_tailcycle): distributed levels dl .. end when they are one box of at most 9^3 nodes
 // each (dl < 0: none), then the replicated tail levels tl .. end (one rank and one box: the gather between the two is the plain restriction).
+static int g_nd_tail_form = 0;            // the body the last tail cycle took; the testing build hands it out (vdn_last_tail_form in runtime.hip)
+int nd_last_tail_form() { return g_nd_tail_form; }
 static bool nd_small_end(NDMG &M, int dl, int tl) {
+  g_nd_tail_form = 0;
   if (!sw().mg_tailcycle) return false;
   static const long tail_nodes = SMALL_LEVEL_NODES;    // largest level the one-workgroup cycle takes (measured: 17^3 is slower, HG 16.9 -> 17.6 ms)
   const vdn_params &P = ctx().prm;
@@ -1582,7 +1752,19 @@ static bool nd_small_end(NDMG &M, int dl, int tl) {
   const int N = std::max(B.n[0], std::max(B.n[1], B.n[2]));
   T.nlev = nl; T.nu1 = P.hg_nu1; T.nu2 = P.hg_nu2; T.nbot = std::max(P.hg_nub, 2 * N * N); T.omega = P.hg_omega; { const NdOm o = nd_om(true, P.hg_nu1); T.om1 = o.om1; T.om2 = o.om2; T.nsp = o.nsp; }     // nd_bottom_t / nd_bottom_sweeps_global
   if (M.kry.w) { hipLaunchKernelGGL(kk_nd_tailcycle<true>, dim3(1), dim3(1024), 0, ctx().stream, T, KrylovTailArgs{ mg_krylov_args(M.kry, 1, P.hg_bottom_solver_eps), M.kry.method, 0 }); T.nbot = 0; /* no sweeps: no swap below */ }
-  else hipLaunchKernelGGL(kk_nd_tailcycle<false>, dim3(1), dim3(1024), 0, ctx().stream, T, NoKrylovTailArgs{});
+  else {
+    // the sweeps: levels in LDS, per-node constants in registers (kk_nd_tailcycle_lds) wherever tail_plan takes the level set
+    int tn[TAIL_MAX_LEVELS][3] = {}, per[3] = { 0, 0, 0 };
+    for (int l = 0; l < nl; l++) for (int d = 0; d < 3; d++) { if (l < TAIL_MAX_LEVELS) tn[l][d] = T.L[l].n[d]; if (T.L[l].per[d]) per[d] = 1; }
+    const TailPlan TP = tail_plan(TAIL_NODES, nl, tn, per);
+    if (TP.fits) {
+      NdTailLdsArgs A; memset(&A, 0, sizeof A);
+      for (int l = 0; l < nl; l++) A.L[l] = T.L[l];
+      A.P = TP; A.nu1 = T.nu1; A.nu2 = T.nu2; A.nbot = T.nbot; A.omega = T.omega; A.om1 = T.om1; A.om2 = T.om2; A.nsp = T.nsp;
+      hipLaunchKernelGGL(kk_nd_tailcycle_lds, dim3(1), dim3(TAIL_THREADS), 0, ctx().stream, A);
+      g_nd_tail_form = 1;
+    } else hipLaunchKernelGGL(kk_nd_tailcycle<false>, dim3(1), dim3(1024), 0, ctx().stream, T, NoKrylovTailArgs{});
+  }
   int m = 0;                                           // the ping-pong state the sweeps leave behind (nd_jacobi_d / nd_jacobi_t)
   if (dl >= 0) for (int q = dl; q < (int)M.dlev.size(); q++, m++) {
     const int sweeps = (m == nl - 1) ? T.nbot : T.nu1 + T.nu2;

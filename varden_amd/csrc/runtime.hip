@@ -226,6 +226,11 @@ extern "C" unsigned vdn_nd_prolong_fused_levels(void) { return nd_last_prolong_l
 // ... and which ran as kk_nd_lds_down / kk_nd_lds_up (tests/test_nd_lds_levels_gpu.py)
 unsigned nd_last_lds_levels();
 extern "C" unsigned vdn_nd_lds_levels(void) { return nd_last_lds_levels(); }
+// ... and the body the last one-workgroup tail cycle took (tests/test_tail_cycles_gpu.py): 0 on global memory, 1 with its levels in LDS; which = 0: the
+// cell-centred solves, 1: the nodal solve.  Set when a cycle's launches are issued or captured (0 when it has no tail cycle); a replayed graph leaves it as it is.
+int cc_last_tail_form();
+int nd_last_tail_form();
+extern "C" int vdn_last_tail_form(int which) { return which == 0 ? cc_last_tail_form() : nd_last_tail_form(); }
 #endif
 extern "C" const char *vdn_debug_switches(void) {
   static std::string out;
