@@ -144,7 +144,8 @@ const char *vdn_debug_switches(void);
  * correction inside the first post-smoothing march (the read-back of tests/test_nd_prolong_fused_gpu.py; not part of the product's interface), and
  * `unsigned vdn_nd_lds_levels(void)`: bit l is set when level l of the last nodal solve ran as one launch down and one up (tests/test_nd_lds_levels_gpu.py), and
  * `int vdn_last_tail_form(int which)`: the body the last one-workgroup tail cycle of a cell-centred (which = 0) or the nodal (1) solve took, 0: on global memory,
- * 1: levels in LDS (tests/test_tail_cycles_gpu.py). */
+ * 1: levels in LDS (tests/test_tail_cycles_gpu.py), and `int vdn_last_slopes_form(void)`: the form the last slope launch of velpred / mkflux took, 0: one thread
+ * per cell, 1: the k-march with one cell per lane, 2: its pair form (tests/test_slopes_march_gpu.py). */
 const char *vdn_build_flavour(void);
 int  vdn_finalize(void);
 const char *vdn_last_error(void);
@@ -575,6 +576,9 @@ int  vdn_last_mac_level_form(void);
 /* slope_module (src/slope.f90): slopes of comps [0,nc) in direction dir on [lo-1,hi+1]^3;
  * slope multifab must have ng=1, nc comps; bccomp = 0-based first adv_bc component             */
 int  vdn_k_slope(const vdn_multifab *s, vdn_multifab *slope, int dir, int bccomp, const vdn_bc_tower *bct);
+/* the slope launch of velpred and mkflux by itself: the slopes of the 2 or 3 components of s (ng >= 3) along x, y and z into sl0, sl1, sl2 (ng = 1, the
+ * components of s), on [lo-1,hi+1]^3 of every local box, in the launch form the predictors take; vmax (may be NULL): max |s| over the valid cells */
+int  vdn_k_slopes_march(const vdn_multifab *s, vdn_multifab *sl0, vdn_multifab *sl1, vdn_multifab *sl2, int bccomp, const vdn_bc_tower *bct, double *vmax);
 /* velpred (src/velpred.f90:16): u(3,ng3), force(3,ng1) -> umac[3] (face, ng1), incl. fill_boundary */
 int  vdn_k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *force,
                    const double *dx, double dt, const vdn_bc_tower *bct);

@@ -81,6 +81,13 @@ def slope(s, slope_mf, dir, bccomp, bct):
     check(capi.load().vdn_k_slope(s.h, slope_mf.h, dir, bccomp, bct.h))
 
 
+def slopes_march(s, sl, bccomp, bct, want_max=False):
+    """the predictors' slope launch by itself: the slopes of s along x, y, z into the three multifabs sl; want_max: returns max |s| over the valid cells"""
+    m = C.c_double(0.0)
+    check(capi.load().vdn_k_slopes_march(s.h, sl[0].h, sl[1].h, sl[2].h, bccomp, bct.h, C.byref(m) if want_max else None))
+    return m.value if want_max else None
+
+
 def velpred(u, umac, force, dx, dt, bct):
     check(capi.load().vdn_k_velpred(u.h, handle_array(umac), force.h, _dx(dx), float(dt), bct.h))
 

@@ -202,6 +202,7 @@ SIGNATURES = {
     "vdn_last_bottom_form": (C.c_int, [C.c_int]),
     "vdn_last_mac_level_form": (C.c_int, []),
     "vdn_k_slope": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP]),
+    "vdn_k_slopes_march": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, _VP, C.POINTER(C.c_double)]),
     "vdn_k_velpred": (C.c_int, [_VP, _PVP, _VP, _PD, C.c_double, _VP]),
     "vdn_k_mkflux": (C.c_int, [_VP, _PVP, _PVP, _PVP, _VP, _VP, _PD, C.c_double, _VP, C.c_int, _PI]),
     "vdn_k_update": (C.c_int, [_VP, _PVP, _PVP, _PVP, _VP, _VP, _PD, C.c_double, C.c_int, _PI, _VP]),

@@ -331,6 +331,9 @@ extern "C" int vdn_macproject(vdn_layout *mla, vdn_multifab **umac, vdn_multifab
 extern "C" int vdn_k_slope(const vdn_multifab *s, vdn_multifab *slope, int dir, int bccomp, const vdn_bc_tower *bct) {
   HOOK_BEGIN(s) k_slope(s, slope, dir, bccomp, bct); HOOK_END
 }
+extern "C" int vdn_k_slopes_march(const vdn_multifab *s, vdn_multifab *sl0, vdn_multifab *sl1, vdn_multifab *sl2, int bccomp, const vdn_bc_tower *bct, double *vmax) {
+  HOOK_BEGIN(s) k_slopes_march(s, sl0, sl1, sl2, bccomp, bct, vmax); HOOK_END
+}
 extern "C" int vdn_k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *force, const double *dx, double dt,
                              const vdn_bc_tower *bct) {
   HOOK_BEGIN(u)

@@ -16,6 +16,7 @@
 // The per-box dead-band eps needs a max-reduction: wave shuffles + one atomic per wave, consumed from
 // device memory by the next kernel (no host round trip).
 #include "vdn_dev.h"
+#include "slopes_plan.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -121,6 +122,8 @@ __global__ void __launch_bounds__(256) kk_slopes(FV s, FV sl0, FV sl1, FV sl2, G
 // kept: the XCD-aware tile order of the other marches (xcd_tile) 0.645 -> 0.674 ms, with 64 x 8 workgroups 0.87 ms; fewer k-chunks no better.)
 // (Measured on this form and not kept: one fromm_of per cell along x and z -- the neighbours' from the lanes next door / carried from plane to plane -- instead of
 // three: 0.659 -> 0.737 ms for three components, 0.390 -> 0.412 for two; the kernel is not bound by its arithmetic.)
+// (Re-measured before the pair form below replaced it as the default: 0.667 / 0.413 ms per launch for three / two components at 256^3, 1.73 / 1.13 GB fetched for 0.43 / 0.29 GB of s,
+// the texture addresser busy 70 % of the kernel's cycles -- profiles/slopes_march_ab.txt.  It stays for boxes of odd width and misaligned arrays, and as VDN_SLOPES_MARCH=1.)
 template <int NC> __global__ void __launch_bounds__(256) kk_slopes_my(FV s, FV sl0, FV sl1, FV sl2, GArgs A, Range3 r, int klen, double *vmax) {
   const int lane = threadIdx.x, row = threadIdx.y;
   const int i = r.lo[0] - 2 + (int)blockIdx.x * 60 + lane, j = r.lo[1] + (int)blockIdx.y * 4 + row;
@@ -167,9 +170,109 @@ template <int NC> __global__ void __launch_bounds__(256) kk_slopes_my(FV s, FV s
   #undef SPEC
   if (vmax) block_atomic_max(vmax, m);
 }
+// Pair form of the march above (slopes_plan.h): a lane owns the cells (i, i + 1) and moves them as 16-byte values -- per pair and component 1 + 1/2 loads and
+// 3 stores where kk_slopes_my issues 10 and 6.  Five planes of the pair's column stay in registers, the plane after them is loaded one iteration ahead; the
+// x-neighbours are the two values of the lanes next door.  Each y-neighbour is fetched once: the workgroup (SLP_WAVES waves, one full-width row or 64 >> lw
+// narrow ones each) stages plane k of its rows and of two halo rows either side in LDS -- own rows from the registers, the halo rows loaded one plane ahead by
+// the first 4 * 2^lw threads -- double-buffered, one barrier per plane, and reads the rows j - 2, j - 1, j + 1, j + 2 from there.  The last pairs of a row that
+// fill no 62-pair segment march in narrow segments of the same launch (a 258-cell row: two full segments and 5 pairs in 8-lane segments, 64 rows per
+// workgroup).  slope_vals on the same values: the same bits.  Loads are clamped into the box grown by three, pairwise: no lane leaves the allocation.
+// A workgroup marches ONE component (blockIdx.z): the components share nothing but max |u|, and three of them in one thread are 162 VGPRs, 107 spilled SGPRs
+// and 64 bytes of scratch (the lane masks of slope_vals' position tests for two cells, three components, two directions); one is 97 VGPRs, no scratch, 24 KB
+// of LDS, two workgroups per CU.
+// (Measured at 256^3, three / two components, per launch: kk_slopes_my 0.667 / 0.413 ms; pairs alone, the y-neighbours still from memory: 0.537 / 0.332 with
+// four waves, 0.547 / 0.352 with eight; with the rows staged: 0.476 / 0.318, four waves 0.474 / 0.309, sixteen 0.593 / 0.411.  Eight are kept: they stage 12
+// rows for 8 where four stage 8 for 4.  Workgroups per component (SLP_WG_TARGET) 512: 0.486 / 0.349, 1024: 0.475 / 0.320, 2048: 0.480 / 0.325, 4096: 0.477 / 0.315.)
+template <int NC> __global__ void __launch_bounds__(64 * SLP_WAVES) kk_slopes_pr(FV s, FV sl0, FV sl1, FV sl2, GArgs A, Range3 r, SlopesPlan P, double *vmax) {
+  __shared__ double2 sm[2][(SLP_WAVES + 4) * 64];
+  const int tid = threadIdx.x, c = blockIdx.z;                       // grid: tiles x k-chunks x NC components
+  int lw, pair0, by, pl, rr, hrow, hslot;
+  slopes_tile(P, (int)blockIdx.x, lw, pair0, by);
+  const bool own_l = slopes_lane(lw, tid, pl, rr), hal = slopes_halo(lw, tid, hrow, hslot);
+  const int W = 1 << lw, j0 = r.lo[1] + by * (SLP_WAVES * (64 >> lw));
+  const int i_ = r.lo[0] + 2 * (pair0 + pl - 1), j_ = j0 + rr;
+  const bool own = own_l && i_ <= r.hi[0] && j_ <= r.hi[1];
+  const int ic = min(max(i_, A.lo[0] - 3), A.hi[0] + 2), jc = min(max(j_, A.lo[1] - 3), A.hi[1] + 3), jh = min(max(j0 + hrow, A.lo[1] - 3), A.hi[1] + 3);
+  const int k0 = r.lo[2] + (int)blockIdx.y * P.klen, k1 = min(k0 + P.klen - 1, r.hi[2]);
+  const long sp = (long)s.n0 * s.n1, slp = (long)sl0.n0 * sl0.n1;
+  const double *pw = s.p + s.sc * c + fv_idx(s, ic, jc, s.a2), *ph = s.p + s.sc * c + fv_idx(s, ic, hal ? jh : jc, s.a2);
+  const long so = fv_idx(sl0, own ? i_ : r.lo[0], own ? j_ : r.lo[1], sl0.a2) + sl0.sc * c;         // sl0, sl1, sl2: one layout (launch_slopes)
+  #define SPL(p, kk) (*(const double2 *)((p) + (long)(min(max((kk), A.lo[2] - 3), A.hi[2] + 3) - s.a2) * sp))
+  #define SPEC(d, sd) (A.adv[d][sd][c] == VDN_EXT_DIR || A.adv[d][sd][c] == VDN_HOEXTRAP)
+  const bool xl = SPEC(0, 0), xh = SPEC(0, 1), yl = SPEC(1, 0), yh = SPEC(1, 1), zl = SPEC(2, 0), zh = SPEC(2, 1);
+  const int o = A.slope_order;
+  double2 w[5], nx, hv;
+  w[0] = make_double2(0.0, 0.0);
+  #pragma unroll
+  for (int q = 1; q < 5; q++) w[q] = SPL(pw, k0 - 3 + q);
+  nx = SPL(pw, k0 + 2);
+  hv = SPL(ph, k0);
+  const int o0 = (rr + 2) * W + pl, oh = hslot * W + pl;
+  double m = 0.0;
+  int b = 0;
+  for (int k = k0; k <= k1; k++, b ^= 1) {
+    w[0] = w[1]; w[1] = w[2]; w[2] = w[3]; w[3] = w[4]; w[4] = nx;
+    sm[b][o0] = w[2];
+    if (hal) sm[b][oh] = hv;
+    nx = SPL(pw, k + 3);
+    if (hal) hv = SPL(ph, k + 1);
+    __syncthreads();
+    const double2 s0 = w[2];
+    const double2 y0 = sm[b][o0 - 2 * W], y1 = sm[b][o0 - W], y2 = sm[b][o0 + W], y3 = sm[b][o0 + 2 * W];
+    const double pa = lane_prev(s0.x), pb = lane_prev(s0.y), na = lane_next(s0.x), nb = lane_next(s0.y);
+    if (own) {
+      const int i = i_, j = j_;
+      double2 d0, d1, d2;
+      d0.x = slope_vals(pa, pb, s0.x, s0.y, na, i, A.lo[0], A.hi[0], xl, xh, o);
+      d0.y = slope_vals(pb, s0.x, s0.y, na, nb, i + 1, A.lo[0], A.hi[0], xl, xh, o);
+      d2.x = slope_vals(w[0].x, w[1].x, s0.x, w[3].x, w[4].x, k, A.lo[2], A.hi[2], zl, zh, o);
+      d2.y = slope_vals(w[0].y, w[1].y, s0.y, w[3].y, w[4].y, k, A.lo[2], A.hi[2], zl, zh, o);
+      d1.x = slope_vals(y0.x, y1.x, s0.x, y2.x, y3.x, j, A.lo[1], A.hi[1], yl, yh, o);
+      d1.y = slope_vals(y0.y, y1.y, s0.y, y2.y, y3.y, j, A.lo[1], A.hi[1], yl, yh, o);
+      const long oc = so + (long)(k - sl0.a2) * slp;
+      *(double2 *)(sl0.p + oc) = d0; *(double2 *)(sl2.p + oc) = d2; *(double2 *)(sl1.p + oc) = d1;
+      if (vmax && j >= A.lo[1] && j <= A.hi[1] && k >= A.lo[2] && k <= A.hi[2]) {
+        if (i >= A.lo[0] && i <= A.hi[0]) m = fmax(m, fabs(s0.x));
+        if (i + 1 >= A.lo[0] && i + 1 <= A.hi[0]) m = fmax(m, fabs(s0.y));
+      }
+    }
+  }
+  #undef SPL
+  #undef SPEC
+  if (vmax) block_atomic_max(vmax, m);
+}
+// testing build (vdn_last_slopes_form): the form the last slope launch took -- 0: kk_slopes, one thread per cell; 1: kk_slopes_my; 2: kk_slopes_pr
+static int g_slopes_form = 0;
+int slopes_last_form() { return g_slopes_form; }
+// whether a box's arrays take the pair form: the range is the box grown by one, its width even, every 16-byte access aligned (slopes_pair_ok) and the
+// three slope arrays of one layout
+static bool slopes_pair_fits(const FV &s, const FV sl[3], const GArgs &A, const Range3 &rg) {
+  for (int d = 0; d < 3; d++) {
+    if (rg.lo[d] != A.lo[d] - 1 || rg.hi[d] != A.hi[d] + 1) return false;
+    const int a = d == 0 ? s.a0 : d == 1 ? s.a1 : s.a2, n = d == 0 ? s.n0 : d == 1 ? s.n1 : s.n2;
+    const int b = d == 0 ? sl[0].a0 : d == 1 ? sl[0].a1 : sl[0].a2, nb = d == 0 ? sl[0].n0 : d == 1 ? sl[0].n1 : sl[0].n2;
+    if (a > A.lo[d] - 3 || a + n - 1 < A.hi[d] + 3 || b > rg.lo[d] || b + nb - 1 < rg.hi[d]) return false;
+  }
+  const SlopesLayout Ls = { (long)rg.lo[0] - s.a0, s.n0, s.sc, (uintptr_t)s.p };
+  for (int d = 0; d < 3; d++) {
+    if (sl[d].a0 != sl[0].a0 || sl[d].a1 != sl[0].a1 || sl[d].a2 != sl[0].a2 || sl[d].n0 != sl[0].n0 || sl[d].n1 != sl[0].n1 || sl[d].sc != sl[0].sc) return false;
+    const SlopesLayout Ll = { (long)rg.lo[0] - sl[d].a0, sl[d].n0, sl[d].sc, (uintptr_t)sl[d].p };
+    if (!slopes_pair_ok(rg.hi[0] - rg.lo[0] + 1, rg.lo[0] - (A.lo[0] - 3), A.hi[0] + 3 - rg.hi[0], Ls, Ll)) return false;
+  }
+  return true;
+}
 static void launch_slopes(const FV &s, const FV sl[3], const GArgs &A, const Range3 &rg, int ncomp, double *vmax, hipStream_t st) {
   if (sw().slopes_march && (ncomp == 2 || ncomp == 3) && s.a0 <= A.lo[0] - 3 && s.a1 <= A.lo[1] - 3 && s.a2 <= A.lo[2] - 3) {
     const int nx = rg.hi[0] - rg.lo[0] + 1, ny = rg.hi[1] - rg.lo[1] + 1, nz = rg.hi[2] - rg.lo[2] + 1;
+    if (sw().slopes_march >= 2 && slopes_pair_fits(s, sl, A, rg)) {
+      const SlopesPlan P = slopes_plan(nx, ny, nz);
+      const dim3 g(P.tiles, P.chunks, ncomp), blk(64 * SLP_WAVES, 1, 1);
+      if (ncomp == 3) hipLaunchKernelGGL(kk_slopes_pr<3>, g, blk, 0, st, s, sl[0], sl[1], sl[2], A, rg, P, vmax);
+      else hipLaunchKernelGGL(kk_slopes_pr<2>, g, blk, 0, st, s, sl[0], sl[1], sl[2], A, rg, P, vmax);
+      g_slopes_form = 2;
+      return;
+    }
+    g_slopes_form = 1;
     const int tiles = ((nx + 59) / 60) * ((ny + 3) / 4);
     int chunks = std::max(1, std::min(nz / 8, (32 * 256 + tiles - 1) / tiles));      // (measured at 256^3, three / two components: 4 x 256 workgroups 0.741 / 0.477 ms, 8 x 0.667 / 0.418, 16 x 0.661 / 0.406, 32 x 0.645 / 0.384)
     const int klen = (nz + chunks - 1) / chunks;
@@ -178,6 +281,7 @@ static void launch_slopes(const FV &s, const FV sl[3], const GArgs &A, const Ran
     else hipLaunchKernelGGL(kk_slopes_my<2>, g, blk, 0, st, s, sl[0], sl[1], sl[2], A, rg, klen, vmax);
     return;
   }
+  g_slopes_form = 0;
   hipLaunchKernelGGL(kk_slopes, grid_for(rg), dim3(64, 4, 1), 0, st, s, sl[0], sl[1], sl[2], A, rg, 7, vmax);
 }
 
@@ -1158,6 +1262,23 @@ void k_slope(const vdn_multifab *s, vdn_multifab *slope, int dir, int bccomp, co
     Range3 r; for (int d = 0; d < 3; d++) { r.lo[d] = A.lo[d] - 1; r.hi[d] = A.hi[d] + 1; }
     hipLaunchKernelGGL(kk_slopes, grid_for(r), dim3(64, 4, 1), 0, ctx().stream, s->fabs[i], slope->fabs[i], slope->fabs[i], slope->fabs[i], A, r, 1 << dir);
   }
+}
+
+// the slope launch of the predictors by itself (unit-test hook): all three directions of the two or three components of s, box by box through launch_slopes,
+// so in whichever form the switches and the layouts choose; vmax (may be null): the largest |s| over the valid cells of all boxes rides along, as in velpred
+void k_slopes_march(const vdn_multifab *s, vdn_multifab *sl0, vdn_multifab *sl1, vdn_multifab *sl2, int bccomp, const vdn_bc_tower *bct, double *vmax) {
+  REQUIRE((s->nc == 2 || s->nc == 3) && s->ng >= 3, "k_slopes_march: s needs 2 or 3 components and 3 ghost cells");
+  REQUIRE(sl0->ng == 1 && sl1->ng == 1 && sl2->ng == 1 && sl0->nc == s->nc && sl1->nc == s->nc && sl2->nc == s->nc, "k_slopes_march: the slope multifabs need 1 ghost cell and the components of s");
+  hipStream_t st = ctx().stream;
+  double *dmax = nullptr;
+  if (vmax) { dmax = (double *)arena_alloc(256); HIPCHK(hipMemsetAsync(dmax, 0, sizeof(double), st)); }
+  for (int ib = 0; ib < s->nfabs(); ib++) {
+    GArgs A; fill_gargs(A, s, ib, bct, bccomp, s->nc, nullptr, 0.0);
+    Range3 rg; for (int d = 0; d < 3; d++) { rg.lo[d] = A.lo[d] - 1; rg.hi[d] = A.hi[d] + 1; }
+    const FV sl[3] = { sl0->fabs[ib], sl1->fabs[ib], sl2->fabs[ib] };
+    launch_slopes(s->fabs[ib], sl, A, rg, s->nc, dmax, st);
+  }
+  if (vmax) *vmax = read_scalar1(dmax);
 }
 
 // one window of at most three components (k_mkflux below); bccomp: the bc-tower component of the window's first component

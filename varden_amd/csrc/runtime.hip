@@ -231,6 +231,10 @@ extern "C" unsigned vdn_nd_lds_levels(void) { return nd_last_lds_levels(); }
 int cc_last_tail_form();
 int nd_last_tail_form();
 extern "C" int vdn_last_tail_form(int which) { return which == 0 ? cc_last_tail_form() : nd_last_tail_form(); }
+// ... and the form the last slope launch of the Godunov predictors took (tests/test_slopes_march_gpu.py): 0 one thread per cell (kk_slopes), 1 the march with one
+// cell per lane (kk_slopes_my), 2 the pair form (kk_slopes_pr)
+int slopes_last_form();
+extern "C" int vdn_last_slopes_form(void) { return slopes_last_form(); }
 #endif
 extern "C" const char *vdn_debug_switches(void) {
   static std::string out;

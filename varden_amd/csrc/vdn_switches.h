@@ -42,7 +42,7 @@
   X(no_graphs, "VDN_NO_GRAPHS", PRESENT, false, "launch every multigrid cycle eagerly instead of replaying its hipGraph") \
   X(no_slope_cache, "VDN_NO_SLOPE_CACHE", PRESENT, false, "velocity mkflux recomputes the slopes of uold that velpred computed in the same step") \
   X(no_force_reuse, "VDN_NO_FORCE_REUSE", SET, false, "1: every forcing term is computed where the reference computes it (advance_premac AND velocity_advance, ...)") \
-  X(slopes_march, "VDN_SLOPES_MARCH", ON, true, "0: the per-cell slopes kernel instead of the k-marching one") \
+  X(slopes_march, "VDN_SLOPES_MARCH", INT, 2, "0: the per-cell slopes kernel instead of the k-marching one; 1: the march with one cell per lane and its y-neighbours from memory (kk_slopes_my); default 2: its pair form (kk_slopes_pr) wherever the layouts take it") \
   X(godunov_batch, "VDN_GODUNOV_BATCH", SET, false, "1: the descriptor (box-batched) Godunov kernels also on a level of one box") \
   X(godunov_plain, "VDN_GODUNOV_PLAIN", PRESENT, false, "the face-centred one-thread-per-cell Godunov kernels of round 1 (the fused marches' bit-for-bit reference, and their fallback where they refuse the field layouts)") \
   X(god_segw, "VDN_GOD_SEGW", ON, true, "0: the box-batched fused Godunov marches use full-width (64 x 8) tiles for every box") \
