@@ -32,7 +32,7 @@ def bits(x):
 
 
 def okey(a):
-    """the order-preserving 64-bit image of doubles (csrc/fabio.hip: dkey): -0 sorts below +0"""
+    """the order-preserving 64-bit image of doubles (csrc/vdn_dev.h: key_of): -0 sorts below +0"""
     b = np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
     return np.where(b >> np.uint64(63) != 0, ~b, b | np.uint64(1 << 63))
 

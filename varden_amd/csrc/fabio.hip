@@ -9,7 +9,7 @@
 // launch of kk_fab_pack moves one range [a, b) of the space -- which may begin or end inside a fab, a component or a row -- into the staging buffer, one
 // workgroup per piece of FAB_PIECE values of one segment, consecutive lanes writing consecutive staging entries.  The same pass reduces the minimum and the
 // maximum of every (box, component) for Cell_H: wave shuffles, LDS, then one atomic pair per workgroup on the ORDER-PRESERVING 64-bit image of the double
-// (sign bit flipped for non-negative values, all bits for negative ones), so the values are exact -- not the shifted sums of vdn_multifab_min_max.  With that
+// (key_of, vdn_dev.h: sign bit flipped for non-negative values, all bits for negative ones), so the values are exact -- not the shifted sums of vdn_multifab_min_max.  With that
 // image -0 sorts below +0: a field holding both reports min = -0, max = +0.  kk_fab_unpack is the inverse over the same table; it writes valid points only.
 // dm = 2: the fabs keep the 3-D layout with one valid z-plane (k = 0), which the segment's origin and extents address like any other box.
 //
@@ -33,15 +33,6 @@ const char *const FAB_DESC = "FAB ((8, (64 11 52 0 1 12 0 1023)),(8, (8 7 6 5 4 
 
 // one (box, component): p = its first valid point; rows of nx contiguous doubles, sy / sz = the fab's row and plane strides
 struct FabSeg { double *p; long off, piece0, sy, sz; int len, nx, ny, pad; };
-
-DEVI unsigned long long dkey(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-double key_to_double(unsigned long long k) {
-  const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  double v; memcpy(&v, &b, 8); return v;
-}
 
 // the piece of the linear space workgroup blockIdx.x takes, clipped to [a, b): segment *S, elements [e0, e1)
 DEVI bool fab_piece(const FabSeg *segs, int nseg, long P0, long a, long b, FabSeg &S, int &s, long &e0, long &e1) {
@@ -68,7 +59,7 @@ __global__ void __launch_bounds__(FAB_THREADS) kk_fab_pack(const FabSeg *segs, i
   for (long e = e0 + threadIdx.x; e < e1; e += FAB_THREADS) {
     const double v = S.p[fab_src_index(S, (unsigned)(e - S.off))];
     stage[e - a] = v;
-    const unsigned long long key = dkey(v);
+    const unsigned long long key = key_of(v);
     mn = key < mn ? key : mn; mx = key > mx ? key : mx;
   }
   for (int o = 32; o > 0; o >>= 1) {
@@ -118,12 +109,12 @@ __global__ void __launch_bounds__(FAB_THREADS) kk_plane_defect(const DefSeg *seg
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (as_constant(segs + mid).piece0 <= gp) lo = mid; else hi = mid - 1; }
   const DefSeg S = as_constant(segs + lo);
   const unsigned npts = (unsigned)S.nx * (unsigned)S.ny, q0 = (unsigned)(gp - S.piece0) * DEF_PIECE, q1 = q0 + DEF_PIECE < npts ? q0 + DEF_PIECE : npts;
-  unsigned long long mx = dkey(0.0);
+  unsigned long long mx = key_of(0.0);
   for (unsigned q = q0 + threadIdx.x; q < q1; q += FAB_THREADS) {
     const unsigned j = q / (unsigned)S.nx, i = q - j * (unsigned)S.nx;
     const double r = S.ref ? S.ref[(long)i + S.rsy * (long)j] : 0.0;
     const double *c = S.p + (long)i + S.sy * (long)j;
-    for (int k = 0; k < S.nz; k++) { const unsigned long long key = dkey(fabs(c[S.sz * (long)k] - r)); mx = key > mx ? key : mx; }
+    for (int k = 0; k < S.nz; k++) { const unsigned long long key = key_of(fabs(c[S.sz * (long)k] - r)); mx = key > mx ? key : mx; }
   }
   for (int o = 32; o > 0; o >>= 1) { const unsigned long long x2 = __shfl_down(mx, o, 64); mx = x2 > mx ? x2 : mx; }
   __shared__ unsigned long long sm[FAB_THREADS / 64];
@@ -406,7 +397,7 @@ void write_level(const std::string &dir, const LevelPlan &P, const int *nodal, i
   for (int g = 0; g < nb; g++) h += fmt("FabOnDisk: Cell_D_00000 %ld\n", foff[g]);
   for (int w = 0; w < 2; w++) {
     h += fmt("\n%d,%d\n", nb, nc);
-    for (int g = 0; g < nb; g++) { for (int q = 0; q < nc; q++) h += es(key_to_double(mm[(size_t)w * nseg + (size_t)g * nc + q])) + ","; h += "\n"; }
+    for (int g = 0; g < nb; g++) { for (int q = 0; q < nc; q++) h += es(key_value(mm[(size_t)w * nseg + (size_t)g * nc + q])) + ","; h += "\n"; }
   }
   File fh(dir + "/Cell_H", "wb"); fh.puts(h); fh.close();
   arena_release(mark);
@@ -646,7 +637,7 @@ void write_plane(const char *who, const char *dirname, int nlev, vdn_multifab *c
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h_out, d_out, 16, hipMemcpyDeviceToHost, c.stream));
   HIPCHK(hipStreamSynchronize(c.stream));
-  defect[0] = key_to_double(h_out[0]); defect[1] = key_to_double(h_out[1]);
+  defect[0] = key_value(h_out[0]); defect[1] = key_value(h_out[1]);
   arena_release(mark);
 }
 

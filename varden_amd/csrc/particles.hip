@@ -12,8 +12,6 @@
 #include "vdn_dev.h"
 #include "particle_plan.h"
 
-void comm_allreduce_sum_dev(double *d, size_t n);      // exchange.hip
-
 namespace {
 constexpr int PT_THREADS = 256, PT_MAXC = VDN_MAXCOMP;
 constexpr const char *PT_MAGIC = "VDN_PARTICLES 1";
@@ -336,7 +334,6 @@ void pt_sample_all(vdn_particles *P, int nlev, const vdn_layout *mla, vdn_multif
   }
   if (comm_active()) comm_allreduce_sum_dev(d_out, (size_t)nc * P->n);
 }
-struct Giveback { size_t mark; bool armed; ~Giveback() { if (armed) ctx().arena_off = mark; } };     // a refusal leaves nothing allocated in the arena
 vdn_particles *pt_new(long n, int dm) {
   vdn_particles *P = new vdn_particles;
   P->n = n; P->dm = dm;
@@ -424,8 +421,7 @@ extern "C" int vdn_particles_advance(vdn_particles *P, int nlev, vdn_layout *mla
   const PBox *B0 = pt_table(P, nlev, mla, u0, 0, dm, 0, bct);
   const PBox *B1 = pt_table(P, nlev, mla, u1, 0, dm, 0, bct);
   B0 = pt_table(P, nlev, mla, u0, 0, dm, 0, bct);      // (the second table may have emptied a full cache)
-  const size_t mark = arena_mark();
-  Giveback giveback{ mark, true };
+  ArenaScope arena;
   const long n = P->n;
   double *k1 = (double *)arena_alloc(sizeof(double) * 3 * (size_t)n), *k2 = (double *)arena_alloc(sizeof(double) * 3 * (size_t)n);
   const bool ranks = comm_active();
@@ -444,8 +440,7 @@ extern "C" int vdn_particles_advance(vdn_particles *P, int nlev, vdn_layout *mla
     if (ranks) comm_allreduce_sum_dev(k2, 2 * (size_t)n);
     hipLaunchKernelGGL((kk_update<2>), grid, dim3(PT_THREADS), 0, st, (const PLoc *)P->d_loc, P->d_x, P->d_state, n, (const double *)k1, (const double *)k2, dt, 0.5 * dt);
   }
-  giveback.armed = false;
-  arena_release(mark);
+  arena.release();
   VDN_CATCH
 }
 
@@ -457,8 +452,7 @@ static void pt_sample_to_host(vdn_particles *P, const char *who, int nlev, vdn_l
   REQUIRE(bccomp >= 0 && bccomp + nc <= bct->ncomp_adv, "%s: boundary components %d .. %d, the tower holds %d", who, bccomp, bccomp + nc - 1, bct->ncomp_adv);
   REQUIRE(val_host, "%s: null argument (val_host)", who);
   pt_locator(P, who, nlev, mla, dx, bct);
-  const size_t mark = arena_mark();
-  Giveback giveback{ mark, true };
+  ArenaScope arena;
   const long n = P->n;
   double *d_out = (double *)arena_alloc(sizeof(double) * (size_t)nc * n);
   int *d_lev = (int *)arena_alloc(sizeof(int) * (size_t)n);
@@ -468,8 +462,7 @@ static void pt_sample_to_host(vdn_particles *P, const char *who, int nlev, vdn_l
   if (lev_host) HIPCHK(hipMemcpyAsync(lev_host, d_lev, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, ctx().stream));
   HIPCHK(hipStreamSynchronize(ctx().stream));
   for (long t = 0; t < n; t++) for (int c = 0; c < nc; c++) val_host[(size_t)t * nc + c] = soa[(size_t)c * n + t];
-  giveback.armed = false;
-  arena_release(mark);
+  arena.release();
 }
 
 extern "C" int vdn_particles_sample(vdn_particles *P, int nlev, vdn_layout *mla, vdn_multifab *const *mf, int comp, int nc, int bccomp, const double *dx,

@@ -6,7 +6,7 @@
 // q dV, s_c dV, u_d dV, (rho u_d) dV and ((0.5 rho) (u.u)) dV over the slot's cells, dV the cell volume of the cell's level.  volume is formed on the host from the
 // counts: sum over the levels, ascending, of cells[l][slot] * dV_l.
 //
-// Launch form.  The slab cut of diag_plan.h, unchanged: one launch per level (kk_pdf), a workgroup of four waves per slab, the thread -> cell map of kk_diag -- cell
+// Launch form.  The slab cut of diag_plan.h, unchanged: one launch per level (kk_pdf), a workgroup of four waves per slab, the thread -> cell map of composite.h -- cell
 // t + 256 e of a trip, (i, j, k) stepped by constants with one carry each --, the loads of the UNR cells of a trip issued before the first is used.
 //   counts   the destination of a cell depends on its value, so a thread cannot keep a register per slot.  Integer atomics into 32-bit LDS counters (a slab holds
 //            at most 64 K cells), flushed with 64-bit integer atomics into a (level, slot) table in memory.  Integer addition is exact in any order.  Between ranks
@@ -17,33 +17,26 @@
 //            those lanes.  Covered cells, the lanes past the slab's end and NaN-q cells take no part.  A wave's entry therefore depends on the slab alone: fixed map,
 //            cells in order, trips in order, fixed tree.  The four waves meet as (w0 + w1) + (w2 + w3), and ONE partial per (slab, slot, row) goes to the slab's place
 //            in an array indexed by the GLOBAL slab number.  Several ranks: the places of foreign slabs are zero and one sum all-reduce fills them (x + 0 + ... + 0
-//            is x).  kk_pdf_final then gives a wave to every (slot, row): starting from +0 it adds the slabs in slab order, 64 loaded at once and added lane by lane
-//            (kk_diag_final's scheme).  The bits of a result depend on the box lists and the fields alone -- not on the call, the rank or the number of ranks.
+//            is x).  kk_pdf_final then gives a wave to every (slot, row): starting from +0 it adds the slabs in slab order (slot_sum of composite.h).  The bits of
+//            a result depend on the box lists and the fields alone -- not on the call, the rank or the number of ranks; composite.h states what that rests on.
 // LDS budget (dynamic, sized by the call): 4 wave copies x (nbins + 2) slots x nr rows x 8 B, nr = nscal + 2 dm + 2 (every row but volume), plus 4 (nbins + 3) B of
 // counters.  64 bins, nscal = 2, dm = 3: 21 KB.  256 bins: 258 x 10 x 8 = 20.2 KB a copy, 82 KB in all, at nscal = 2; 258 x 19 x 8 = 38.3 KB a copy, 153.2 KB in all
 // (157,900 B with the counters), at nscal = 11 -- under the 160 KB (163,840 B) a workgroup of a gfx950 CU may hold, so every case keeps four copies and one tree.
 // More than 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize, set once per instantiation.  One workgroup per CU is then resident; a slab per CU is what the
 // plan gives a 256^3 box anyway.
 // vdn_pdf2 is the same march with two slot computations and a (n1 + 2) x (n2 + 2) table of 32-bit LDS counters (66 x 66 at most: 17 KB, static); counts only.
-// Memory: descriptors, partials, counters, the covered-cell masks (cover_masks of diag.hip) and the result live in the arena between arena_mark and arena_release;
+// Memory: descriptors, partials, counters, the covered-cell masks and the result live in the arena of the call's ArenaScope;
 // one copy brings the result home.  The calls write none of their inputs; only VDN_PDF_VORTICITY reads a ghost cell (one layer of u).
-#include "vdn_dev.h"
-#include "derived.h"
-#include "diag_plan.h"
+#include "composite.h"
 #include "pdf_bin.h"
 #include <atomic>
 
-void comm_allreduce_sum_dev(double *d, size_t n);      // exchange.hip
-
 namespace {
-constexpr int PD_THREADS = 256, PD_WAVES = PD_THREADS / 64, PD_MAXS = 11;
+constexpr int PD_THREADS = COMP_THREADS, PD_WAVES = COMP_WAVES, PD_MAXS = 11;
 constexpr size_t PD_LDS_MAX = 160 * 1024, PD_LDS_PLAIN = 64 * 1024;
 static_assert(VDN_PDF_MAX_BINS + 2 <= 65536 && DIAG_SLAB_CELLS <= 0xffffffffl, "a slab's count fits a 32-bit counter");
-typedef unsigned long long u64;
 
 struct PdfAx { int field, comp, nbins; double lo, hi, w; };
-// one slab: planes lo[2] .. hi[2] of a local box; mask (or NULL): one byte per valid cell of the box, x fastest, != 0 where the next level covers the cell
-struct PdfD { FV u, s; const unsigned char *mask; int lo[3], hi[3]; int blo[3], bnx, bny; int slab; VortArgs A; };
 
 template <bool VORT>
 DEVI double pdf_q(const PdfAx &X, const FV &fu, const FV &fs, const VortArgs &A, int dm, int i, int j, int k) {
@@ -53,21 +46,6 @@ DEVI double pdf_q(const PdfAx &X, const FV &fu, const FV &fs, const VortArgs &A,
   if constexpr (VORT) return vort_value(fu, A, i, j, k);
   return 0.0;
 }
-DEVI double pd_wave_sum(double x) {                    // the shuffle tree of kk_diag: lane 0 holds the sum of all 64 lanes
-  #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = x + __shfl_down(x, o, 64);
-  return x;
-}
-// the thread -> cell map of kk_diag for one wave-uniform trip loop: the cell of index t is (t % nx, (t / nx) % ny, t / (nx ny)) from the slab's corner; a thread's
-// cells are PD_THREADS apart, so it divides once and then steps by the constants (di, dj, dk) with one carry each
-struct PdMap {
-  int nx, ny, di, dj, dk, ci, cj, ck;
-  DEVI PdMap(int nx_, int ny_, int t) : nx(nx_), ny(ny_) {
-    const int dr = PD_THREADS / nx; di = PD_THREADS % nx; dj = dr % ny; dk = dr / ny;
-    const int r = t / nx; ci = t - r * nx; ck = r / ny; cj = r - ck * ny;
-  }
-  DEVI void step() { ci += di; const int c1 = ci >= nx ? 1 : 0; ci -= c1 ? nx : 0; cj += dj + c1; const int c2 = cj >= ny ? 1 : 0; cj -= c2 ? ny : 0; ck += dk + c2; }
-};
 
 // NS: the scalars the instantiation can carry (nscal <= NS; the loops over them are unrolled so that every term is a register); VORT: q may be the vorticity.
 // The rows of a thread's terms: q, s[NS], u[3], ru[3], ke; row j of them lives at column pd_col(j) of the LDS table, whose nr = nscal + 2 dm + 2 columns are the
@@ -80,11 +58,11 @@ template <int NS> DEVI int pd_col(int j, int nscal, int dm) {
   return 1 + nscal + 2 * dm;
 }
 template <int NS, bool VORT>
-__global__ void __launch_bounds__(PD_THREADS) kk_pdf(const PdfD *descs, PdfAx X, double *__restrict__ part, u64 *__restrict__ gcnt, u64 *__restrict__ gnan,
+__global__ void __launch_bounds__(PD_THREADS) kk_pdf(const CompBoxV *descs, PdfAx X, double *__restrict__ part, u64 *__restrict__ gcnt, u64 *__restrict__ gnan,
                                                      int nscal, int dm, double vol) {
   extern __shared__ double pd_lds[];
   constexpr int NRT = NS + 8, UNR = NS <= 4 ? 4 : 2;
-  const PdfD &D = as_constant(descs + blockIdx.x);
+  const CompBoxV &D = as_constant(descs + blockIdx.x);
   const int nslot = X.nbins + 2, nr = nscal + 2 * dm + 2, ne = nslot * nr;
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
   double *mine = pd_lds + (long)wave * ne;                                   // this wave's copy of the (slot, row) table
@@ -96,7 +74,7 @@ __global__ void __launch_bounds__(PD_THREADS) kk_pdf(const PdfD *descs, PdfAx X,
   const int tot = nx * ny * nz;
   const unsigned char *mask = D.mask;
   const FV fu = D.u, fs = D.s;
-  PdMap M(nx, ny, t);
+  CellMap M(nx, ny, t);
   int nnan = 0;
   // the trip loop is wave-uniform (it runs on the wave's first cell), so that every lane takes part in every ballot and shuffle; a lane past the slab's end loads
   // the slab's first cell and is dropped, as a covered cell is
@@ -108,12 +86,7 @@ __global__ void __launch_bounds__(PD_THREADS) kk_pdf(const PdfD *descs, PdfAx X,
       live[e] = t0 + lane + e * PD_THREADS < tot;
       const int i = D.lo[0] + (live[e] ? M.ci : 0), j = D.lo[1] + (live[e] ? M.cj : 0), k = D.lo[2] + (live[e] ? M.ck : 0);
       M.step();
-      if (mask) live[e] = live[e] && mask[((long)(k - D.blo[2]) * D.bny + (j - D.blo[1])) * D.bnx + (i - D.blo[0])] == 0;
-      const long iu = fv_idx(fu, i, j, k), is = fv_idx(fs, i, j, k);
-      #pragma unroll
-      for (int d = 0; d < 3; d++) uv[e][d] = d < dm ? fu.p[iu + fu.sc * d] : 0.0;
-      #pragma unroll
-      for (int c = 0; c < NS; c++) sv[e][c] = c < nscal ? fs.p[is + fs.sc * c] : 0.0;
+      live[e] = load_cell<NS>(D, fu, fs, mask, i, j, k, live[e], nscal, dm, uv[e], sv[e]);
       wv[e] = 0.0;
       if constexpr (VORT) { if (X.field == VDN_PDF_VORTICITY) wv[e] = vort_value(fu, D.A, i, j, k); }
     }
@@ -154,7 +127,7 @@ __global__ void __launch_bounds__(PD_THREADS) kk_pdf(const PdfD *descs, PdfAx X,
         // and with them the bits, are the same
         double v[NRT];
         #pragma unroll
-        for (int j = 0; j < NRT; j++) v[j] = pd_wave_sum(member ? r[j] : 0.0);      // (rows beyond nscal / dm too: zeros, and no branch between the trees)
+        for (int j = 0; j < NRT; j++) v[j] = wave_sum(member ? r[j] : 0.0);      // (rows beyond nscal / dm too: zeros, and no branch between the trees)
         if (lane == 0) {
           #pragma unroll
           for (int j = 0; j < NRT; j++) {
@@ -169,24 +142,19 @@ __global__ void __launch_bounds__(PD_THREADS) kk_pdf(const PdfD *descs, PdfAx X,
   if (nnan) atomicAdd(&cnt[nslot], (unsigned)nnan);
   __syncthreads();
   // the four waves: (w0 + w1) + (w2 + w3), one partial per (slot, row) into the slab's place; the counters into the level's table
-  double *out = part + (long)D.slab * ne;
-  for (int e = t; e < ne; e += PD_THREADS) out[e] = (pd_lds[e] + pd_lds[ne + e]) + (pd_lds[2 * ne + e] + pd_lds[3 * ne + e]);
+  double *out = part + (long)D.slot * ne;
+  for (int e = t; e < ne; e += PD_THREADS) out[e] = sum4(pd_lds[e], pd_lds[ne + e], pd_lds[2 * ne + e], pd_lds[3 * ne + e]);
   for (int e = t; e <= nslot; e += PD_THREADS) {
     const unsigned c = cnt[e];
     if (c) atomicAdd(e < nslot ? gcnt + e : gnan, (u64)c);
   }
 }
 
-// a wave per (slot, row): starting from +0, the slabs in slab order -- 64 loaded at once, one per lane, added lane by lane (kk_diag_final)
+// a wave per (slot, row): starting from +0, the slabs in slab order
 __global__ void __launch_bounds__(PD_THREADS) kk_pdf_final(const double *__restrict__ part, int ne, int nslab, double *__restrict__ out) {
   const int g = (int)blockIdx.x * PD_WAVES + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
   if (g >= ne) return;
-  double v = 0.0;
-  for (int base = 0; base < nslab; base += 64) {
-    const int s = base + lane, n = nslab - base < 64 ? nslab - base : 64;
-    const double x = s < nslab ? part[(long)s * ne + g] : 0.0;
-    for (int l = 0; l < n; l++) v = v + __shfl(x, l, 64);
-  }
+  const double v = slot_sum(0.0, part, ne, g, nullptr, 0, nslab, lane);
   if (lane == 0) out[g] = v;
 }
 // the 64-bit counters as doubles (exact: a hierarchy holds far fewer than 2^53 cells), the form the all-reduce and the copy home take
@@ -197,10 +165,10 @@ __global__ void kk_pdf_counts(const u64 *__restrict__ cnt, int n, double *__rest
 
 constexpr int PD2_SIDE = VDN_PDF2_MAX_BINS + 2;
 template <bool VORT>
-__global__ void __launch_bounds__(PD_THREADS) kk_pdf2(const PdfD *descs, PdfAx X1, PdfAx X2, u64 *__restrict__ gcnt, u64 *__restrict__ gnan, int dm) {
+__global__ void __launch_bounds__(PD_THREADS) kk_pdf2(const CompBoxV *descs, PdfAx X1, PdfAx X2, u64 *__restrict__ gcnt, u64 *__restrict__ gnan, int dm) {
   __shared__ unsigned cnt[PD2_SIDE * PD2_SIDE + 1];                          // [n1 + 2][n2 + 2], then the NaN cells
   constexpr int UNR = 4;
-  const PdfD &D = as_constant(descs + blockIdx.x);
+  const CompBoxV &D = as_constant(descs + blockIdx.x);
   const int t = (int)threadIdx.x, n2 = X2.nbins + 2, ne = (X1.nbins + 2) * n2;
   for (int e = t; e <= ne; e += PD_THREADS) cnt[e] = 0u;
   __syncthreads();
@@ -208,7 +176,7 @@ __global__ void __launch_bounds__(PD_THREADS) kk_pdf2(const PdfD *descs, PdfAx X
   const int tot = nx * ny * nz;
   const unsigned char *mask = D.mask;
   const FV fu = D.u, fs = D.s;
-  PdMap M(nx, ny, t);
+  CellMap M(nx, ny, t);
   int nnan = 0;
   for (int t0 = t; t0 < tot; t0 += UNR * PD_THREADS) {
     double q1[UNR], q2[UNR];
@@ -218,7 +186,7 @@ __global__ void __launch_bounds__(PD_THREADS) kk_pdf2(const PdfD *descs, PdfAx X
       live[e] = t0 + e * PD_THREADS < tot;
       const int i = D.lo[0] + (live[e] ? M.ci : 0), j = D.lo[1] + (live[e] ? M.cj : 0), k = D.lo[2] + (live[e] ? M.ck : 0);
       M.step();
-      if (mask) live[e] = live[e] && mask[((long)(k - D.blo[2]) * D.bny + (j - D.blo[1])) * D.bnx + (i - D.blo[0])] == 0;
+      live[e] = live[e] && cell_open(D, mask, i, j, k);
       q1[e] = pdf_q<VORT>(X1, fu, fs, D.A, dm, i, j, k);
       q2[e] = pdf_q<VORT>(X2, fu, fs, D.A, dm, i, j, k);
     }
@@ -239,7 +207,7 @@ __global__ void __launch_bounds__(PD_THREADS) kk_pdf2(const PdfD *descs, PdfAx X
 }
 
 // more than 64 KB of dynamic LDS: the function attribute, once per instantiation
-template <int NS, bool VORT> void launch_pdf(int nd, size_t lds, const PdfD *d, const PdfAx &X, double *part, u64 *gcnt, u64 *gnan, int nscal, int dm, double vol) {
+template <int NS, bool VORT> void launch_pdf(int nd, size_t lds, const CompBoxV *d, const PdfAx &X, double *part, u64 *gcnt, u64 *gnan, int nscal, int dm, double vol) {
   static std::atomic<bool> raised{ false };
   if (lds > PD_LDS_PLAIN && !raised.load()) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&kk_pdf<NS, VORT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PD_LDS_MAX));
@@ -254,26 +222,6 @@ bool layout_of(int dm, int nscal, vdn_pdf_layout_t *lay) {
   return true;
 }
 
-// what both calls ask of their arguments; `name` starts every message
-void check_state(const char *name, int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s, const double *dx, const vdn_bc_tower *bct, bool vort) {
-  REQUIRE(ctx().inited, "%s: vdn_init has not been called", name);
-  REQUIRE(mla && u && s, "%s: null argument (mla, u, s)", name);
-  REQUIRE(nlev >= 1 && nlev <= VDN_MAXLEV, "%s: nlev = %d is outside 1 .. %d", name, nlev, VDN_MAXLEV);
-  REQUIRE(nlev == mla->nlev, "%s: nlev = %d does not match the layout's %d levels", name, nlev, mla->nlev);
-  const int dm = ctx().prm.dm, nscal = ctx().prm.nscal;
-  REQUIRE(dm == 3 || nlev == 1, "%s: dm = 2 runs on one level (nlev = %d)", name, nlev);
-  REQUIRE(dx, "%s: dx is NULL (every cell is weighted by its volume)", name);
-  REQUIRE(!vort || bct, "%s: VDN_PDF_VORTICITY needs the bc tower (bct is NULL)", name);
-  for (int n = 0; n < nlev; n++) {
-    REQUIRE(u[n] && s[n], "%s: level %d: null multifab", name, n);
-    REQUIRE(u[n]->la == mla && s[n]->la == mla && u[n]->lev == n && s[n]->lev == n, "%s: level %d: the layouts of u and s differ (from each other or from mla)", name, n);
-    REQUIRE(u[n]->nfabs() == s[n]->nfabs(), "%s: level %d: the layouts of u and s differ (%d and %d local boxes)", name, n, u[n]->nfabs(), s[n]->nfabs());
-    REQUIRE(u[n]->nc >= dm && s[n]->nc >= nscal, "%s: level %d: u carries %d components (dm = %d), s %d (nscal = %d)", name, n, u[n]->nc, dm, s[n]->nc, nscal);
-    for (int d = 0; d < 3; d++) REQUIRE(!u[n]->nodal[d] && !s[n]->nodal[d], "%s: level %d: cell-centred multifabs expected", name, n);
-    REQUIRE(!vort || u[n]->ng >= 1, "%s: level %d: VDN_PDF_VORTICITY reads one ghost layer of u (ng = %d)", name, n, u[n]->ng);
-    if (n < nlev - 1) for (int d = 0; d < 3; d++) REQUIRE(mla->rr[3 * n + d] == 2, "%s: level %d: a refinement ratio of 2 is expected (it is %d along %d)", name, n, mla->rr[3 * n + d], d);
-  }
-}
 PdfAx check_axis(const char *name, const char *which, int field, int comp, int nbins, double lo, double hi, int maxbins) {
   const int dm = ctx().prm.dm, nscal = ctx().prm.nscal;
   REQUIRE(field >= VDN_PDF_SCALAR && field <= VDN_PDF_VORTICITY, "%s: %sfield = %d is not a VDN_PDF_ code (0 .. 3)", name, which, field);
@@ -286,42 +234,6 @@ PdfAx check_axis(const char *name, const char *which, int field, int comp, int n
   return X;
 }
 
-// the slabs of level n that this rank owns, as descriptors on the device; returns their number
-int level_slabs(const char *name, int n, int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s, const double *dx, const vdn_bc_tower *bct, bool vort,
-                const std::vector<DiagSlab> &slabs, PdfD **d_desc) {
-  const int dm = ctx().prm.dm;
-  const std::vector<int> mine = diag_plan_local(slabs, n, mla->owner.data(), ctx().rank);
-  if (mine.empty()) return 0;
-  std::map<int, int> local_of;                           // global box -> local index
-  for (int i = 0; i < (int)mla->local[n].size(); i++) local_of[mla->local[n][i]] = i;
-  std::vector<unsigned char *> mask;
-  if (n < nlev - 1) mask = cover_masks(mla, u[n], n);
-  std::vector<PdfD> v(mine.size());
-  for (size_t q = 0; q < mine.size(); q++) {
-    const DiagSlab &S = slabs[mine[q]];
-    const auto it = local_of.find(S.box);
-    REQUIRE(it != local_of.end() && it->second < u[n]->nfabs(), "%s: level %d: box %d is not local", name, n, S.box);
-    const int b = it->second;
-    PdfD &D = v[q];
-    D.u = u[n]->fabs[b]; D.s = s[n]->fabs[b]; D.mask = mask.empty() ? nullptr : mask[b]; D.slab = mine[q];
-    for (int d = 0; d < 3; d++) {
-      REQUIRE(u[n]->vbox[b].lo[d] == s[n]->vbox[b].lo[d] && u[n]->vbox[b].hi[d] == s[n]->vbox[b].hi[d], "%s: level %d: the layouts of u and s differ", name, n);
-      D.lo[d] = D.blo[d] = u[n]->vbox[b].lo[d]; D.hi[d] = u[n]->vbox[b].hi[d];
-    }
-    REQUIRE(S.k0 >= D.lo[2] && S.k1 <= D.hi[2] && S.k0 <= S.k1, "%s: level %d: box %d differs between the layout and the multifab", name, n, S.box);
-    D.lo[2] = S.k0; D.hi[2] = S.k1;
-    D.bnx = u[n]->vbox[b].hi[0] - u[n]->vbox[b].lo[0] + 1; D.bny = u[n]->vbox[b].hi[1] - u[n]->vbox[b].lo[1] + 1;
-    if (vort) D.A = vort_args(u[n], b, bct, dx + 3 * n, dm, 0); else { D.A = VortArgs(); D.A.dm = dm; }
-  }
-  *d_desc = (PdfD *)arena_alloc(sizeof(PdfD) * v.size());
-  upload_staged(*d_desc, v.data(), sizeof(PdfD) * v.size());
-  return (int)v.size();
-}
-double cell_volume(const double *dx, int n, int dm) {
-  double vol = dx[3 * n] * dx[3 * n + 1];
-  if (dm == 3) vol = vol * dx[3 * n + 2];
-  return vol;
-}
 }   // namespace
 
 extern "C" size_t vdn_pdf_layout_sizeof(void) { return sizeof(vdn_pdf_layout_t); }
@@ -336,7 +248,7 @@ extern "C" int vdn_pdf(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_mu
                        int field, int comp, int nbins, double lo, double hi, double *out_host, long long *cells_host, long long *nan_cells) {
   VDN_TRY
   const bool vort = field == VDN_PDF_VORTICITY;
-  check_state("vdn_pdf", nlev, mla, u, s, dx, bct, vort);
+  composite_check("vdn_pdf", nlev, mla, u, s, dx, bct, vort ? "VDN_PDF_VORTICITY" : nullptr, true);
   REQUIRE(out_host && cells_host && nan_cells, "vdn_pdf: null output (out, cells, nan_cells)");
   const PdfAx X = check_axis("vdn_pdf", "", field, comp, nbins, lo, hi, VDN_PDF_MAX_BINS);
   const int dm = ctx().prm.dm, nscal = ctx().prm.nscal;
@@ -346,8 +258,7 @@ extern "C" int vdn_pdf(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_mu
   const size_t lds = sizeof(double) * (size_t)PD_WAVES * ne + sizeof(unsigned) * (size_t)(nslot + 1);
   REQUIRE(lds <= PD_LDS_MAX, "vdn_pdf: %zu bytes of LDS wanted, a workgroup holds %zu", lds, PD_LDS_MAX);
   hipStream_t st = ctx().stream;
-  const size_t mark = arena_mark();
-  struct Giveback { size_t mark; bool armed; ~Giveback() { if (armed) ctx().arena_off = mark; } } giveback{ mark, true };     // a refusal below leaves nothing allocated either
+  ArenaScope arena;
   int lev_start[VDN_MAXLEV + 1];
   const std::vector<DiagSlab> slabs = diag_plan(nlev, mla->boxes.data(), lev_start);
   const int nslab = lev_start[nlev];
@@ -364,9 +275,10 @@ extern "C" int vdn_pdf(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_mu
   double vol[VDN_MAXLEV];
   for (int n = 0; n < nlev; n++) {
     vol[n] = cell_volume(dx, n, dm);
-    PdfD *d_desc = nullptr;
-    const int nd = level_slabs("vdn_pdf", n, nlev, mla, u, s, dx, bct, vort, slabs, &d_desc);
-    if (nd == 0) continue;
+    const std::vector<CompPiece> mine = slab_pieces(slabs, n, mla);
+    if (mine.empty()) continue;
+    const CompBoxV *d_desc = composite_level_vort("vdn_pdf", n, nlev, mla, u, s, mine, dx, bct, vort);
+    const int nd = (int)mine.size();
     u64 *gc = d_cnt + (size_t)n * nslot, *gn = d_cnt + (size_t)nlev * nslot;
     if (nscal <= 4) { if (vort) launch_pdf<4, true>(nd, lds, d_desc, X, d_part, gc, gn, nscal, dm, vol[n]); else launch_pdf<4, false>(nd, lds, d_desc, X, d_part, gc, gn, nscal, dm, vol[n]); }
     else            { if (vort) launch_pdf<PD_MAXS, true>(nd, lds, d_desc, X, d_part, gc, gn, nscal, dm, vol[n]); else launch_pdf<PD_MAXS, false>(nd, lds, d_desc, X, d_part, gc, gn, nscal, dm, vol[n]); }
@@ -377,8 +289,7 @@ extern "C" int vdn_pdf(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_mu
   std::vector<double> h((size_t)ncnt + ne);
   HIPCHK(hipMemcpyAsync(h.data(), d_cntd, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  giveback.armed = false;
-  arena_release(mark);
+  arena.release();
   for (int n = 0; n < VDN_MAXLEV; n++)
     for (int m = 0; m < nslot; m++) cells_host[(size_t)n * nslot + m] = n < nlev ? (long long)h[(size_t)n * nslot + m] : 0;
   *nan_cells = (long long)h[(size_t)nlev * nslot];
@@ -396,15 +307,14 @@ extern "C" int vdn_pdf2(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_m
                         long long *cells_host, double *volume_host, long long *nan_cells) {
   VDN_TRY
   const bool vort = field1 == VDN_PDF_VORTICITY || field2 == VDN_PDF_VORTICITY;
-  check_state("vdn_pdf2", nlev, mla, u, s, dx, bct, vort);
+  composite_check("vdn_pdf2", nlev, mla, u, s, dx, bct, vort ? "VDN_PDF_VORTICITY" : nullptr, true);
   REQUIRE(cells_host && volume_host && nan_cells, "vdn_pdf2: null output (cells, volume, nan_cells)");
   const PdfAx X1 = check_axis("vdn_pdf2", "axis 1: ", field1, comp1, nbins1, lo1, hi1, VDN_PDF2_MAX_BINS);
   const PdfAx X2 = check_axis("vdn_pdf2", "axis 2: ", field2, comp2, nbins2, lo2, hi2, VDN_PDF2_MAX_BINS);
   const int dm = ctx().prm.dm;
   const int ne = (nbins1 + 2) * (nbins2 + 2), ncnt = nlev * ne + 1;
   hipStream_t st = ctx().stream;
-  const size_t mark = arena_mark();
-  struct Giveback { size_t mark; bool armed; ~Giveback() { if (armed) ctx().arena_off = mark; } } giveback{ mark, true };
+  ArenaScope arena;
   int lev_start[VDN_MAXLEV + 1];
   const std::vector<DiagSlab> slabs = diag_plan(nlev, mla->boxes.data(), lev_start);
   REQUIRE(lev_start[nlev] > 0, "vdn_pdf2: the hierarchy holds no cell");
@@ -414,20 +324,20 @@ extern "C" int vdn_pdf2(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_m
   double vol[VDN_MAXLEV];
   for (int n = 0; n < nlev; n++) {
     vol[n] = cell_volume(dx, n, dm);
-    PdfD *d_desc = nullptr;
-    const int nd = level_slabs("vdn_pdf2", n, nlev, mla, u, s, dx, bct, vort, slabs, &d_desc);
-    if (nd == 0) continue;
+    const std::vector<CompPiece> mine = slab_pieces(slabs, n, mla);
+    if (mine.empty()) continue;
+    const CompBoxV *d_desc = composite_level_vort("vdn_pdf2", n, nlev, mla, u, s, mine, dx, bct, vort);
+    const int nd = (int)mine.size();
     u64 *gc = d_cnt + (size_t)n * ne, *gn = d_cnt + (size_t)nlev * ne;
-    if (vort) hipLaunchKernelGGL((kk_pdf2<true>), dim3(nd), dim3(PD_THREADS), 0, st, (const PdfD *)d_desc, X1, X2, gc, gn, dm);
-    else      hipLaunchKernelGGL((kk_pdf2<false>), dim3(nd), dim3(PD_THREADS), 0, st, (const PdfD *)d_desc, X1, X2, gc, gn, dm);
+    if (vort) hipLaunchKernelGGL((kk_pdf2<true>), dim3(nd), dim3(PD_THREADS), 0, st, d_desc, X1, X2, gc, gn, dm);
+    else      hipLaunchKernelGGL((kk_pdf2<false>), dim3(nd), dim3(PD_THREADS), 0, st, d_desc, X1, X2, gc, gn, dm);
   }
   hipLaunchKernelGGL(kk_pdf_counts, dim3((ncnt + 255) / 256), dim3(256), 0, st, (const u64 *)d_cnt, ncnt, d_cntd);
   if (comm_active()) comm_allreduce_sum_dev(d_cntd, (size_t)ncnt);
   std::vector<double> h((size_t)ncnt);
   HIPCHK(hipMemcpyAsync(h.data(), d_cntd, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  giveback.armed = false;
-  arena_release(mark);
+  arena.release();
   for (int n = 0; n < VDN_MAXLEV; n++)
     for (int m = 0; m < ne; m++) cells_host[(size_t)n * ne + m] = n < nlev ? (long long)h[(size_t)n * ne + m] : 0;
   *nan_cells = (long long)h[(size_t)nlev * ne];

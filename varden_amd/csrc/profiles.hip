@@ -5,30 +5,26 @@
 // << L, bin m is m h <= x_a < (m + 1) h with h = dx[L][a].  The sums run over the composite grid of vdn_diagnostics: the valid cells of level l that no box of level
 // l + 1 covers.  Such a cell with index i_a lies in the r = 1 << (L - l) bins i_a r .. i_a r + r - 1 and contributes to EACH with the weight w_l = (dx dy dz of level
 // l) / r (dm = 2: dx dy / r), formed once per level on the host.  Per bin and row the term named in varden_amd.h is summed: products associated left to right, then
-// multiplied by w_l; `volume` is (the bin's composite cells of level l) * w_l, added over the levels; extrema are exact, through the order-preserving key of diag.hip.
+// multiplied by w_l; `volume` is (the bin's composite cells of level l) * w_l, added over the levels; extrema are exact, through the order-preserving key of vdn_dev.h.
 //
 // Launch form.  profile_plan.h cuts every box into pieces and gives every piece one SLOT of partials per cell index along a, numbered in (level, global box, piece)
 // order.  One launch per level, kk_profile<NS, AXIS>:
 //   AXIS = 0      a workgroup takes a piece (<= 64 cells along x, a run of k-planes); lane i of every wave owns the index lo + i and walks the piece's (j, k) rows
 //                 wave, wave + 4, ... in ascending order -- no cross-lane step; the four waves of a lane meet as (w0 + w1) + (w2 + w3) through LDS
-//   AXIS = 1, 2   a workgroup takes one cross-section of a piece (one index along a): per-thread accumulation in a fixed thread -> cell map, the shuffle tree and
-//                 the (w0 + w1) + (w2 + w3) LDS step of kk_diag
+//   AXIS = 1, 2   a workgroup takes one cross-section of a piece (one index along a): per-thread accumulation in the thread -> cell map, the shuffle tree and
+//                 the (w0 + w1) + (w2 + w3) LDS step of composite.h
 // and stores ONE partial per column into the slot.  Sums are doubles, an extremum travels as its 64-bit key cut into two halves that a double holds exactly (a minimum
 // as the complement, so that an empty slot is 0), the cell count as a double.  Several ranks: the slots of foreign boxes are zero and ONE sum all-reduce of the slot
 // array fills them.  kk_profile_final then gives a wave to every (bin, row): starting from +0 it adds, level by level, the slots the level's table names for the index
-// m >> (L - l), in table order (64 slots loaded at once, added lane by lane); key rows take the maximum.  No floating-point atomic anywhere: the bits of a result
-// depend on the box lists alone -- not on the number of ranks, not on the call.
-// Memory: descriptors, tables, partials, the covered-cell masks (cover_masks of diag.hip) and the result live in the arena between arena_mark and arena_release; one
-// copy brings rows and counts home.  The call writes none of its inputs and reads no ghost cell.
-#include "vdn_dev.h"
+// m >> (L - l), in table order (slot_sum); key rows take the maximum (slot_max).  No floating-point atomic anywhere: the bits of a result depend on the box lists
+// alone -- not on the number of ranks, not on the call; composite.h states what that rests on.
+// Memory: descriptors, tables, partials, the covered-cell masks and the result live in the arena of the call's ArenaScope; one copy brings rows and counts home.  The call writes none of its inputs and reads no ghost cell.
+#include "composite.h"
 #include "profile_plan.h"
 
-void comm_allreduce_sum_dev(double *d, size_t n);      // exchange.hip
-
 namespace {
-constexpr int PF_THREADS = 256, PF_MAXS = 11, PF_MAXROW = 80;
+constexpr int PF_THREADS = COMP_THREADS, PF_MAXS = 11, PF_MAXROW = 80;
 static_assert(PROF_MAXLEV == VDN_MAXLEV && PROF_XW == 64, "profile_plan.h and the kernels");
-typedef unsigned long long u64;
 
 // the columns of a slot's partial in an instantiation that carries NS scalars and three velocity components (unused ones stay 0); ruu: (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
 template <int NS> struct PT {
@@ -38,15 +34,6 @@ template <int NS> struct PT {
   static_assert(NSUM <= 64 && NKEY <= 64, "one thread per column in the last step of a workgroup");
 };
 constexpr int ruu_col(int d, int e) { return d * 3 - d * (d - 1) / 2 + (e - d); }
-
-DEVI u64 pf_key(double v) {                             // diag.hip's dg_key: monotone in the value, -0 below +0
-  const u64 b = (u64)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-DEVI u64 pf_max(u64 a, u64 b) { return a > b ? a : b; }
-
-// a piece: the cells lo .. hi of a local box; mask (or NULL): one byte per valid cell of the box, x fastest, != 0 where the next level covers the cell
-struct ProfD { FV u, s; const unsigned char *mask; int lo[3], hi[3]; int blo[3], bnx, bny; int slot0; };
 
 template <int NS, int AXIS> struct Acc {
   double a[PT<NS>::NSUM]; u64 kx[PT<NS>::NKEY]; int ncell;
@@ -66,8 +53,8 @@ template <int NS, int AXIS> struct Acc {
       a[T::S + c] = a[T::S + c] + s[c] * w;
       a[T::SS + c] = a[T::SS + c] + (s[c] * s[c]) * w;
       if (c >= 1) a[T::SUA + (c >= 1 ? c - 1 : 0)] = a[T::SUA + (c >= 1 ? c - 1 : 0)] + (s[c] * u[AXIS]) * w;
-      const u64 key = pf_key(s[c]);
-      kx[T::K_SMIN + c] = pf_max(kx[T::K_SMIN + c], ~key); kx[T::K_SMAX + c] = pf_max(kx[T::K_SMAX + c], key);
+      const u64 key = key_of(s[c]);
+      kx[T::K_SMIN + c] = key_max(kx[T::K_SMIN + c], ~key); kx[T::K_SMAX + c] = key_max(kx[T::K_SMAX + c], key);
     }
     #pragma unroll
     for (int d = 0; d < 3; d++) if (d < dm) {
@@ -76,50 +63,36 @@ template <int NS, int AXIS> struct Acc {
       a[T::RU + d] = a[T::RU + d] + ru * w;
       #pragma unroll
       for (int e = d; e < 3; e++) if (e < dm) a[T::RUU + ruu_col(d, e)] = a[T::RUU + ruu_col(d, e)] + (ru * u[e]) * w;
-      const u64 key = pf_key(u[d]);
-      kx[T::K_UMIN + d] = pf_max(kx[T::K_UMIN + d], ~key); kx[T::K_UMAX + d] = pf_max(kx[T::K_UMAX + d], key);
+      const u64 key = key_of(u[d]);
+      kx[T::K_UMIN + d] = key_max(kx[T::K_UMIN + d], ~key); kx[T::K_UMAX + d] = key_max(kx[T::K_UMAX + d], key);
     }
   }
 };
 
-// the values of cell (i, j, k), which is a valid cell of the box whatever `live` says; returns live && not covered
-template <int NS>
-DEVI bool pf_load(const ProfD &D, const FV &fu, const FV &fs, const unsigned char *mask, int i, int j, int k, bool live, int nscal, int dm, double (&u)[3], double (&s)[NS]) {
-  if (mask) live = live && mask[((long)(k - D.blo[2]) * D.bny + (j - D.blo[1])) * D.bnx + (i - D.blo[0])] == 0;
-  const long iu = fv_idx(fu, i, j, k), is = fv_idx(fs, i, j, k);
-  #pragma unroll
-  for (int d = 0; d < 3; d++) u[d] = d < dm ? fu.p[iu + fu.sc * d] : 0.0;
-  #pragma unroll
-  for (int c = 0; c < NS; c++) s[c] = c < nscal ? fs.p[is + fs.sc * c] : 0.0;
-  return live;
-}
-
 // NS: the scalars the instantiation can carry (nscal <= NS; the loops over them are unrolled so that every accumulator is a register).
 // AXIS = 0: one workgroup per piece (start unused); AXIS = 1, 2: one per (piece, index along the axis), start[p]: the first workgroup of piece p
 template <int NS, int AXIS>
-__global__ void __launch_bounds__(PF_THREADS) kk_profile(const ProfD *descs, const int *start, int npiece, double *__restrict__ part, int nscal, int dm, double w) {
+__global__ void __launch_bounds__(PF_THREADS) kk_profile(const CompBox *descs, const int *start, int npiece, double *__restrict__ part, int nscal, int dm, double w) {
   typedef PT<NS> T;
   constexpr int UNR = NS <= 4 ? 4 : 2;                   // cells per thread and trip whose loads are all issued before the first is used
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
   Acc<NS, AXIS> A; A.zero();
   if constexpr (AXIS == 0) {
-    const ProfD &D = as_constant(descs + blockIdx.x);
+    const CompBox &D = as_constant(descs + blockIdx.x);
     const unsigned char *mask = D.mask;
     const FV fu = D.u, fs = D.s;
     const bool ilive = D.lo[0] + lane <= D.hi[0];
     const int i = ilive ? D.lo[0] + lane : D.lo[0];
     const int ny = D.hi[1] - D.lo[1] + 1, nz = D.hi[2] - D.lo[2] + 1, rows = ny * nz;
-    // row r of the piece is (r % ny, r / ny); a wave's rows are 4 apart: it divides once and then steps by the constants (dj, dk) with one carry
-    const int dj = 4 % ny, dk = 4 / ny;
-    int cj = wave % ny, ck = wave / ny;
+    RowMap M(ny, wave, COMP_WAVES);                       // row r of the piece is (r % ny, r / ny); a wave's rows are 4 apart
     for (int r0 = wave; r0 < rows; r0 += 4 * UNR) {
       double uv[UNR][3], sv[UNR][NS]; bool live[UNR];
       #pragma unroll
       for (int e = 0; e < UNR; e++) {
         const bool rl = r0 + 4 * e < rows;
-        const int j = D.lo[1] + (rl ? cj : 0), k = D.lo[2] + (rl ? ck : 0);
-        { cj += dj; const int c1 = cj >= ny ? 1 : 0; cj -= c1 ? ny : 0; ck += dk + c1; }
-        live[e] = pf_load<NS>(D, fu, fs, mask, i, j, k, rl && ilive, nscal, dm, uv[e], sv[e]);
+        const int j = D.lo[1] + (rl ? M.ci : 0), k = D.lo[2] + (rl ? M.cr : 0);
+        M.step();
+        live[e] = load_cell<NS>(D, fu, fs, mask, i, j, k, rl && ilive, nscal, dm, uv[e], sv[e]);
       }
       #pragma unroll
       for (int e = 0; e < UNR; e++) if (live[e]) A.add(uv[e], sv[e], nscal, dm, w);
@@ -140,15 +113,13 @@ __global__ void __launch_bounds__(PF_THREADS) kk_profile(const ProfD *descs, con
       for (int o = t; o < CH * 64; o += PF_THREADS) {
         const int li = o / CH, qq = o % CH, q = qb + qq;
         if (q >= T::NQ || D.lo[0] + li > D.hi[0]) continue;
-        double *out = part + (long)(D.slot0 + li) * T::PQ;
+        double *out = part + (long)(D.slot + li) * T::PQ;
         if (q < T::NSUM) {
-          const double v = (sh[qq][0][li] + sh[qq][1][li]) + (sh[qq][2][li] + sh[qq][3][li]);
+          const double v = sum4(sh[qq][0][li], sh[qq][1][li], sh[qq][2][li], sh[qq][3][li]);
           if (q == T::VOL) { out[T::CELLS] = v; out[T::VOL] = v * w; } else out[q] = v;
         } else {
-          const u64 key = pf_max(pf_max((u64)__double_as_longlong(sh[qq][0][li]), (u64)__double_as_longlong(sh[qq][1][li])),
-                                 pf_max((u64)__double_as_longlong(sh[qq][2][li]), (u64)__double_as_longlong(sh[qq][3][li])));
-          const int c = q - T::NSUM;
-          out[T::KEYS + 2 * c] = (double)(unsigned)(key >> 32); out[T::KEYS + 2 * c + 1] = (double)(unsigned)(key & 0xffffffffull);
+          key_split(max4((u64)__double_as_longlong(sh[qq][0][li]), (u64)__double_as_longlong(sh[qq][1][li]), (u64)__double_as_longlong(sh[qq][2][li]),
+                         (u64)__double_as_longlong(sh[qq][3][li])), out + T::KEYS + 2 * (q - T::NSUM));
         }
       }
       __syncthreads();
@@ -158,58 +129,39 @@ __global__ void __launch_bounds__(PF_THREADS) kk_profile(const ProfD *descs, con
     int p = 0;
     { int hi = npiece - 1; const int bid = (int)blockIdx.x;
       while (p < hi) { const int mid = (p + hi + 1) >> 1; if (as_constant(start + mid) <= bid) p = mid; else hi = mid - 1; } }
-    const ProfD &D = as_constant(descs + p);
+    const CompBox &D = as_constant(descs + p);
     const int off = (int)blockIdx.x - as_constant(start + p), ia = D.lo[AXIS] + off;
     const unsigned char *mask = D.mask;
     const FV fu = D.u, fs = D.s;
     const int nx = D.hi[0] - D.lo[0] + 1, nr = D.hi[C] - D.lo[C] + 1, tot = nx * nr;
-    // the cell of index e is (e % nx, e / nx) from the cross-section's corner; a thread's cells are PF_THREADS apart, so it divides once and then steps by constants
-    const int di = PF_THREADS % nx, dr = PF_THREADS / nx;
-    int ci = t % nx, cr = t / nx;
+    RowMap M(nx, t);                                      // the cell of index e is (e % nx, e / nx) from the cross-section's corner
     for (int t0 = t; t0 < tot; t0 += UNR * PF_THREADS) {
       double uv[UNR][3], sv[UNR][NS]; bool live[UNR];
       #pragma unroll
       for (int e = 0; e < UNR; e++) {
         const bool cl = t0 + e * PF_THREADS < tot;
-        const int i = D.lo[0] + (cl ? ci : 0), r = D.lo[C] + (cl ? cr : 0);
-        { ci += di; const int c1 = ci >= nx ? 1 : 0; ci -= c1 ? nx : 0; cr += dr + c1; }
+        const int i = D.lo[0] + (cl ? M.ci : 0), r = D.lo[C] + (cl ? M.cr : 0);
+        M.step();
         const int j = AXIS == 1 ? ia : r, k = AXIS == 1 ? r : ia;
-        live[e] = pf_load<NS>(D, fu, fs, mask, i, j, k, cl, nscal, dm, uv[e], sv[e]);
+        live[e] = load_cell<NS>(D, fu, fs, mask, i, j, k, cl, nscal, dm, uv[e], sv[e]);
       }
       #pragma unroll
       for (int e = 0; e < UNR; e++) if (live[e]) A.add(uv[e], sv[e], nscal, dm, w);
     }
     A.a[T::VOL] = (double)A.ncell;
-    // the wave: a shuffle tree, the same for every call
+    // the wave, then the four waves through LDS, one thread per column
     #pragma unroll
-    for (int q = 0; q < T::NSUM; q++) {
-      #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) A.a[q] = A.a[q] + __shfl_down(A.a[q], o, 64);
-    }
+    for (int q = 0; q < T::NSUM; q++) A.a[q] = wave_sum(A.a[q]);
     #pragma unroll
-    for (int q = 0; q < T::NKEY; q++) {
-      #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) A.kx[q] = pf_max(A.kx[q], __shfl_down(A.kx[q], o, 64));
-    }
-    // the four waves: (w0 + w1) + (w2 + w3) through LDS, one thread per column
-    __shared__ double shd[PF_THREADS / 64][T::NSUM];
-    __shared__ u64 shk[PF_THREADS / 64][T::NKEY];
-    if (lane == 0) {
-      #pragma unroll
-      for (int q = 0; q < T::NSUM; q++) shd[wave][q] = A.a[q];
-      #pragma unroll
-      for (int q = 0; q < T::NKEY; q++) shk[wave][q] = A.kx[q];
-    }
+    for (int q = 0; q < T::NKEY; q++) A.kx[q] = wave_max(A.kx[q]);
+    __shared__ WaveMeet<T::NSUM, T::NKEY> sh;
+    if (lane == 0) sh.put(wave, A.a, A.kx);
     __syncthreads();
-    double *out = part + (long)(D.slot0 + off) * T::PQ;
+    double *out = part + (long)(D.slot + off) * T::PQ;
     if (t < T::NSUM) {
-      const double v = (shd[0][t] + shd[1][t]) + (shd[2][t] + shd[3][t]);
+      const double v = sh.sum(t);
       if (t == T::VOL) { out[T::CELLS] = v; out[T::VOL] = v * w; } else out[t] = v;
-    } else if (t >= 64 && t < 64 + T::NKEY) {
-      const int c = t - 64;
-      const u64 key = pf_max(pf_max(shk[0][c], shk[1][c]), pf_max(shk[2][c], shk[3][c]));
-      out[T::KEYS + 2 * c] = (double)(unsigned)(key >> 32); out[T::KEYS + 2 * c + 1] = (double)(unsigned)(key & 0xffffffffull);
-    }
+    } else if (t >= 64 && t < 64 + T::NKEY) key_split(sh.max(t - 64), out + T::KEYS + 2 * (t - 64));
   }
 }
 
@@ -230,38 +182,21 @@ __global__ void __launch_bounds__(PF_THREADS) kk_profile_final(const double *__r
     double v = 0.0;
     for (int l = 0; l <= L; l++) {
       const long ci = m >> (L - l);
-      const int p0 = T.ptr[l][ci], p1 = T.ptr[l][ci + 1];
-      for (int base = p0; base < p1; base += 64) {
-        const int s = base + lane, n = p1 - base < 64 ? p1 - base : 64;
-        const double x = s < p1 ? part[(long)T.idx[l][s] * pq + col] : 0.0;
-        for (int k = 0; k < n; k++) v = v + __shfl(x, k, 64);
-      }
+      v = slot_sum(v, part, pq, col, T.idx[l], T.ptr[l][ci], T.ptr[l][ci + 1], lane);
     }
     if (lane == 0) { if (kind == PK_CELLS) cells[m] = (long long)v; else out[(long)r * nbins + m] = v; }
   } else {
     u64 key = 0;
     for (int l = 0; l <= L; l++) {
       const long ci = m >> (L - l);
-      const int p0 = T.ptr[l][ci], p1 = T.ptr[l][ci + 1];
-      for (int s = p0 + lane; s < p1; s += 64) {
-        const double *p = part + (long)T.idx[l][s] * pq + col;
-        key = pf_max(key, ((u64)(unsigned)p[0] << 32) | (u64)(unsigned)p[1]);
-      }
+      key = slot_max(key, part, pq, col, T.idx[l], T.ptr[l][ci], T.ptr[l][ci + 1], lane);
     }
-    #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) key = pf_max(key, __shfl_down(key, o, 64));
-    if (lane == 0) {
-      double v = 0.0;                                                       // 0: no cell contributed
-      if (key != 0) {
-        if (kind == PK_MIN) key = ~key;
-        v = __longlong_as_double((long long)((key >> 63) ? (key & 0x7fffffffffffffffull) : ~key));
-      }
-      out[(long)r * nbins + m] = v;
-    }
+    key = wave_max(key);
+    if (lane == 0) out[(long)r * nbins + m] = extremum_value(key, kind == PK_MIN);
   }
 }
 
-template <int NS> void launch_profile(int axis, int nblock, const ProfD *d, const int *start, int npiece, double *part, int nscal, int dm, double w) {
+template <int NS> void launch_profile(int axis, int nblock, const CompBox *d, const int *start, int npiece, double *part, int nscal, int dm, double w) {
   hipStream_t st = ctx().stream;
   if (axis == 0)      hipLaunchKernelGGL((kk_profile<NS, 0>), dim3(nblock), dim3(PF_THREADS), 0, st, d, start, npiece, part, nscal, dm, w);
   else if (axis == 1) hipLaunchKernelGGL((kk_profile<NS, 1>), dim3(nblock), dim3(PF_THREADS), 0, st, d, start, npiece, part, nscal, dm, w);
@@ -317,32 +252,19 @@ extern "C" long vdn_profiles_nbins(int nlev, vdn_layout *mla, int axis) {
 extern "C" int vdn_profiles(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *const *s, const double *dx, int axis, long nbins,
                             double *out_host, long long *cells_host) {
   VDN_TRY
-  REQUIRE(ctx().inited, "vdn_profiles: vdn_init has not been called");
-  REQUIRE(mla && u && s, "vdn_profiles: null argument (mla, u, s)");
+  composite_check("vdn_profiles", nlev, mla, u, s, dx, nullptr, nullptr, true);
   REQUIRE(out_host && cells_host, "vdn_profiles: null output (out, cells)");
-  REQUIRE(nlev >= 1 && nlev <= VDN_MAXLEV, "vdn_profiles: nlev = %d is outside 1 .. %d", nlev, VDN_MAXLEV);
-  REQUIRE(nlev == mla->nlev, "vdn_profiles: nlev = %d does not match the layout's %d levels", nlev, mla->nlev);
   const int dm = ctx().prm.dm, nscal = ctx().prm.nscal;
-  REQUIRE(dm == 3 || nlev == 1, "vdn_profiles: dm = 2 runs on one level (nlev = %d)", nlev);
-  REQUIRE(dx, "vdn_profiles: dx is NULL (every cell is weighted by its volume)");
   REQUIRE(axis >= 0 && axis < dm, "vdn_profiles: axis = %d is outside 0 .. %d", axis, dm - 1);
-  for (int n = 0; n < nlev; n++) {
-    REQUIRE(u[n] && s[n], "vdn_profiles: level %d: null multifab", n);
-    REQUIRE(u[n]->la == mla && s[n]->la == mla && u[n]->lev == n && s[n]->lev == n, "vdn_profiles: level %d: the layouts of u and s differ (from each other or from mla)", n);
-    REQUIRE(u[n]->nfabs() == s[n]->nfabs(), "vdn_profiles: level %d: the layouts of u and s differ (%d and %d local boxes)", n, u[n]->nfabs(), s[n]->nfabs());
-    REQUIRE(u[n]->nc >= dm && s[n]->nc >= nscal, "vdn_profiles: level %d: u carries %d components (dm = %d), s %d (nscal = %d)", n, u[n]->nc, dm, s[n]->nc, nscal);
-    for (int d = 0; d < 3; d++) REQUIRE(!u[n]->nodal[d] && !s[n]->nodal[d], "vdn_profiles: level %d: cell-centred multifabs expected", n);
-    if (n < nlev - 1) for (int d = 0; d < 3; d++) REQUIRE(mla->rr[3 * n + d] == 2, "vdn_profiles: level %d: the bins assume a refinement ratio of 2 (it is %d along %d)", n, mla->rr[3 * n + d], d);
+  for (int n = 0; n < nlev; n++)
     REQUIRE(mla->pd[n].lo[axis] == mla->pd[0].lo[axis] * (1 << n) && mla->pd[n].hi[axis] - mla->pd[n].lo[axis] + 1 == (mla->pd[0].hi[axis] - mla->pd[0].lo[axis] + 1) << n,
             "vdn_profiles: level %d: the domain is not level 0's refined by %d", n, 1 << n);
-  }
   const long want = (long)(mla->pd[0].hi[axis] - mla->pd[0].lo[axis] + 1) << (nlev - 1);
   REQUIRE(nbins == want, "vdn_profiles: nbins = %ld, vdn_profiles_nbins gives %ld", nbins, want);
   vdn_profile_layout lay;
   REQUIRE(layout_of(dm, nscal, &lay), "vdn_profiles: dm = %d, nscal = %d", dm, nscal);
   hipStream_t st = ctx().stream;
-  const size_t mark = arena_mark();
-  struct Giveback { size_t mark; bool armed; ~Giveback() { if (armed) ctx().arena_off = mark; } } giveback{ mark, true };     // a refusal below leaves nothing allocated either
+  ArenaScope arena;
   const ProfPlan P = profile_plan(nlev, mla->boxes.data(), mla->pd.data(), axis);
   const int nslot = P.slot_start[nlev];
   REQUIRE(nslot > 0, "vdn_profiles: the hierarchy holds no cell");
@@ -370,37 +292,20 @@ extern "C" int vdn_profiles(int nlev, vdn_layout *mla, vdn_multifab *const *u, v
   for (int n = 0; n < nlev; n++) {
     const std::vector<int> mine = profile_plan_local(P, n, mla->owner.data(), ctx().rank);
     if (mine.empty()) continue;
-    std::map<int, int> local_of;                           // global box -> local index
-    for (int i = 0; i < (int)mla->local[n].size(); i++) local_of[mla->local[n][i]] = i;
-    std::vector<unsigned char *> mask;
-    if (n < nlev - 1) mask = cover_masks(mla, u[n], n);
-    std::vector<ProfD> v(mine.size()); std::vector<int> start(mine.size());
+    std::vector<CompPiece> pieces(mine.size()); std::vector<int> start(mine.size());
     int nblock = 0;
     for (size_t q = 0; q < mine.size(); q++) {
       const ProfPiece &S = P.pieces[mine[q]];
-      const auto it = local_of.find(S.box);
-      REQUIRE(it != local_of.end() && it->second < u[n]->nfabs(), "vdn_profiles: level %d: box %d is not local", n, S.box);
-      const int b = it->second;
-      ProfD &D = v[q];
-      D.u = u[n]->fabs[b]; D.s = s[n]->fabs[b]; D.mask = mask.empty() ? nullptr : mask[b]; D.slot0 = S.slot0;
-      for (int d = 0; d < 3; d++) {
-        REQUIRE(u[n]->vbox[b].lo[d] == s[n]->vbox[b].lo[d] && u[n]->vbox[b].hi[d] == s[n]->vbox[b].hi[d], "vdn_profiles: level %d: the layouts of u and s differ", n);
-        D.blo[d] = u[n]->vbox[b].lo[d]; D.lo[d] = S.lo[d]; D.hi[d] = S.hi[d];
-        REQUIRE(S.lo[d] >= u[n]->vbox[b].lo[d] && S.hi[d] <= u[n]->vbox[b].hi[d] && S.lo[d] <= S.hi[d], "vdn_profiles: level %d: box %d differs between the layout and the multifab", n, S.box);
-      }
-      D.bnx = u[n]->vbox[b].hi[0] - u[n]->vbox[b].lo[0] + 1; D.bny = u[n]->vbox[b].hi[1] - u[n]->vbox[b].lo[1] + 1;
+      pieces[q] = CompPiece{ S.box, { S.lo[0], S.lo[1], S.lo[2] }, { S.hi[0], S.hi[1], S.hi[2] }, S.slot0 };
       start[q] = nblock;
       nblock += axis == 0 ? 1 : S.hi[axis] - S.lo[axis] + 1;
     }
-    ProfD *d_desc = (ProfD *)arena_alloc(sizeof(ProfD) * v.size());
+    const CompBox *d_desc = composite_level("vdn_profiles", n, nlev, mla, u, s, pieces);
     int *d_start = (int *)arena_alloc(sizeof(int) * start.size());
-    upload_staged(d_desc, v.data(), sizeof(ProfD) * v.size());
     upload_staged(d_start, start.data(), sizeof(int) * start.size());
-    double vol = dx[3 * n] * dx[3 * n + 1];
-    if (dm == 3) vol = vol * dx[3 * n + 2];
-    const double w = vol / (double)(1 << (nlev - 1 - n));                   // a power of two: exact
-    if (wide) launch_profile<PF_MAXS>(axis, nblock, d_desc, d_start, (int)v.size(), d_part, nscal, dm, w);
-    else      launch_profile<4>(axis, nblock, d_desc, d_start, (int)v.size(), d_part, nscal, dm, w);
+    const double w = cell_volume(dx, n, dm) / (double)(1 << (nlev - 1 - n));      // a power of two: exact
+    if (wide) launch_profile<PF_MAXS>(axis, nblock, d_desc, d_start, (int)pieces.size(), d_part, nscal, dm, w);
+    else      launch_profile<4>(axis, nblock, d_desc, d_start, (int)pieces.size(), d_part, nscal, dm, w);
   }
   if (ranks) comm_allreduce_sum_dev(d_part, (size_t)pq * nslot);
   const long nwave = nbins * nq;
@@ -409,8 +314,7 @@ extern "C" int vdn_profiles(int nlev, vdn_layout *mla, vdn_multifab *const *u, v
   std::vector<double> h((size_t)nq * nbins);
   HIPCHK(hipMemcpyAsync(h.data(), d_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  giveback.armed = false;
-  arena_release(mark);
+  arena.release();
   memcpy(out_host, h.data(), sizeof(double) * (size_t)lay.nrow * nbins);
   memcpy(cells_host, h.data() + (size_t)lay.nrow * nbins, sizeof(long long) * (size_t)nbins);
   VDN_CATCH

@@ -29,6 +29,23 @@ DEVI long fv_idx(const FV &f, int i, int j, int k) {
 DEVI double &fv_at(const FV &f, int i, int j, int k, int c = 0) { return f.p[fv_idx(f, i, j, k) + f.sc * c]; }
 DEVI double fv_get(const FV &f, int i, int j, int k, int c = 0) { return f.p[fv_idx(f, i, j, k) + f.sc * c]; }
 
+// ---- exact extrema: the order-preserving 64-bit key of a double ------------------------------------------------------------------
+// Monotone in the value (sign bit flipped for non-negative values, all bits for negative ones), -0 below +0, so an integer maximum (or atomicMax) of keys is the
+// exact maximum of the values; no key of a double is 0.  key_split / key_join carry a key through an array of doubles (two 32-bit halves, each exact in a double
+// and under a sum with zeros).
+typedef unsigned long long u64;
+DEVI u64 key_of(double v) {
+  const u64 b = (u64)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__host__ __device__ inline double key_value(u64 k) {
+  const u64 b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  double v; __builtin_memcpy(&v, &b, 8); return v;
+}
+DEVI u64 key_max(u64 a, u64 b) { return a > b ? a : b; }
+DEVI void key_split(u64 key, double *p) { p[0] = (double)(unsigned)(key >> 32); p[1] = (double)(unsigned)(key & 0xffffffffull); }
+DEVI u64 key_join(const double *p) { return ((u64)(unsigned)p[0] << 32) | (u64)(unsigned)p[1]; }
+
 // thread -> (i,j,k) of a box [lo,hi] with blockDim = (64,4,1), grid = (ceil(nx/64), ceil(ny/4), nz)
 struct Range3 { int lo[3], hi[3]; };
 static inline dim3 grid_for(const Range3 &r, dim3 block = dim3(64, 4, 1)) {

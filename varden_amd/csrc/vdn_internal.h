@@ -209,9 +209,15 @@ void  arena_release(size_t mark);
 vdn_multifab *mf_temp(const vdn_layout *la, int lev, int nc, int ng, int face_dir /* -1 cell, 0..2 face, 3 nodal */,
                       bool fill, double val);
 void mf_temp_free(vdn_multifab *mf);
-// diag.hip: per local box of level n of `mf`, one byte per valid cell (x fastest, arena memory), != 0 where a box of level n + 1 covers the cell: the cells that are
-// not part of the composite grid (vdn_diagnostics, vdn_profiles)
-std::vector<unsigned char *> cover_masks(const vdn_layout *la, const vdn_multifab *mf, int n);
+// the arena of one public call that allocates past its entry: marks on construction; a refusal (an exception) on the way hands back what was allocated since, so it
+// leaves nothing allocated either; release() on success
+struct ArenaScope {
+  size_t mark; bool armed = true;
+  ArenaScope() : mark(arena_mark()) {}
+  ArenaScope(const ArenaScope &) = delete;
+  ~ArenaScope() { if (armed) ctx().arena_off = mark; }
+  void release() { armed = false; arena_release(mark); }
+};
 void fabio_release();      // fabio.hip: frees the pinned staging buffer of the file writers (vdn_finalize)
 
 // exchange.hip: ghost exchange plans and the RCCL transport
@@ -246,6 +252,7 @@ struct SrcView {
 SrcView make_view(const vdn_multifab *src, const std::vector<vdn_box> &footprint, const std::vector<int> &dst_owner, int scomp, int nc, unsigned long cache_tag);
 void view_cache_purge(unsigned long layout_uid);
 bool   comm_active();
+void   comm_allreduce_sum_dev(double *d, size_t n);
 void   comm_allreduce_max_dev(double *d, int n);
 void   comm_allreduce_max_u8_dev(unsigned char *d, size_t n);
 void   comm_allgather_dev(const double *send, double *recv, size_t count);
