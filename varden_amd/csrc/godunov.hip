@@ -17,6 +17,7 @@
 // device memory by the next kernel (no host round trip).
 #include "vdn_dev.h"
 #include "slopes_plan.h"
+#include "godunov_plan.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -480,25 +481,15 @@ __global__ void __launch_bounds__(256) kk_mk_D(FV s, FV sl0, FV sl1, FV sl2, FV 
 // the face owner then applies the complete rule to the pair it has assembled.
 // Code shape: every plane starts with ONE unconditional batch of loads (indices clamped into the arrays; threads outside
 // the computable region produce values nobody uses), the rare boundary work sits in one branch after it.
-// VDN_GODUNOV_BATCH=1 launches the descriptor (box-batched) kernels also for a level of one box. Measured at 256^3: they need
-// fewer VGPRs (mk_D<1> 116 vs 174) yet run slower there (scalar 6.6 vs 5.6 ms, velocity 10.0 vs 8.2 ms), so one box keeps the by-value kernels
-// one launch per stage for all boxes (descriptors) or one set of launches per box (arguments by value)?  A level of an adaptive
-// hierarchy (hundreds of 16^3 .. 32^3 boxes) is launch-bound box by box; a level of a few large boxes -- 512^3 cut into eight 256^3
-// boxes -- runs faster box by box: the by-value kernels need fewer registers (measured,
-// eight 256^3 boxes on one GPU: scalar 52 -> 42 ms, velocity 76 -> 54 ms per step).  VDN_GODUNOV_BATCH=1 forces the descriptors.
-static bool use_batched(const vdn_multifab *s) {
-  if (s->nfabs() == 0) return false;
-  if (sw().godunov_batch) return true;
-  if (s->nfabs() == 1) return false;
+static bool use_batched(const vdn_multifab *s) {             // the rule and its measurements: god_use_batched
   long cells = 0;
   for (int b = 0; b < s->nfabs(); b++) cells += (long)(s->vbox[b].hi[0] - s->vbox[b].lo[0] + 1) * (s->vbox[b].hi[1] - s->vbox[b].lo[1] + 1) * (s->vbox[b].hi[2] - s->vbox[b].lo[2] + 1);
-  return !(s->nfabs() <= 16 && cells / s->nfabs() >= 96L * 96 * 96);
+  return god_use_batched(s->nfabs(), cells, sw().godunov_batch);
 }
 bool god_per_box(const vdn_multifab *s) { return s->nfabs() >= 1 && !use_batched(s); }
 // tile order of the marching kernels: XCD-aware (vdn_dev.h xcd_tile)
 __constant__ int g_god_xcd = 1;
 DEVI void xcd_remap(int &bx, int &by, int &bz) { if (g_god_xcd) xcd_tile(bx, by, bz); else { bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z; } }
-constexpr int TNY = 8;              // rows per tile: workgroup = 64 x TNY threads
 DEVI double shfl_prev(double v) { return lane_prev(v); }
 
 // ---- stages B + C + D in one march (one component per launch) ------------------------------------------------------------------
@@ -567,48 +558,7 @@ DEVI double tvq(bool cons, double q, double sp, double s0, double mp, double m0)
   if (cons) return q * (sp * mp - s0 * m0);
   return q * (mp + m0) * (sp - s0);
 }
-constexpr int FNX = 62, FNY = TNY - 2;      // cells a tile owns per row / rows it owns
-// SP: the launch-uniform flags of a one-box march as a template argument -- cons, use_minion and (UPD) the update's forcing mode compiled in, so that
-// neither arm of a flag nor the copies around it stay in the plane loop (f_bases, tvq, the stage-D chains, the update); SP_RT: read from FArgs at run
-// time (the box-batched launches, whose descriptors differ in them, and the rarely taken forms).  vp_F_m_body: use_minion only.
-constexpr int SP_RT = -1, SP_CONS = 1, SP_MINION = 2, SP_FMODE1 = 4;
 constexpr int PH_EDGE = 0, PH_STEADY = 1;   // phases of a march's plane function
-static dim3 fused_grid(const Range3 &r, int &klen) {
-  // one 512-thread workgroup per CU at a time: the chunk count is the one that fills the last round of workgroups best
-  const int nx = r.hi[0] - r.lo[0] + 1, ny = r.hi[1] - r.lo[1] + 1, nz = r.hi[2] - r.lo[2] + 1;
-  const int tiles = ((nx + FNX - 1) / FNX) * ((ny + FNY - 1) / FNY);
-  const int env = sw().fused_kchunks;
-  int best = 1; double best_cost = 1e300;
-  for (int ch = 1; ch <= 16 && ch <= nz; ch++) {
-    const int kl = (nz + ch - 1) / ch, nch = (nz + kl - 1) / kl;
-    const double cost = std::ceil((double)tiles * nch / 256.0) * (kl + 4);      // rounds x iterations per workgroup
-    if (cost < best_cost) { best_cost = cost; best = ch; }
-  }
-  const int chunks = env ? env : best;
-  klen = (nz + chunks - 1) / chunks; if (klen < 1) klen = 1;
-  return dim3((nx + FNX - 1) / FNX, (ny + FNY - 1) / FNY, (nz + klen - 1) / klen);
-}
-// the grid of a fused march whose remainder tile column runs in narrow segments (kk_mk_F_mc, kk_vp_F_mc): `full` 62-cell tile columns + one column of
-// segments of segw lanes; false when the box has no remainder column worth it.  The chunk count is chosen for the workgroups that do work.
-static bool fused_grid_cols(const Range3 &rf, dim3 &g, int &klen, int &full, int &segw) {
-  const bool narrow_env = sw().god_narrow;
-  const int nx = rf.hi[0] - rf.lo[0] + 1, ny = rf.hi[1] - rf.lo[1] + 1, nz = rf.hi[2] - rf.lo[2] + 1;
-  full = nx / FNX;
-  const int rem = nx - full * FNX;
-  if (!narrow_env || full < 1 || rem <= 0 || rem + 2 > 32) return false;
-  segw = rem + 2;
-  const int rows = TNY * (64 / segw) - 2;
-  const int tiles = full * ((ny + FNY - 1) / FNY) + (ny + rows - 1) / rows;
-  int best = 1; double best_cost = 1e300;
-  for (int ch = 1; ch <= 16 && ch <= nz; ch++) {
-    const int kl = (nz + ch - 1) / ch, nch = (nz + kl - 1) / kl;
-    const double cost = std::ceil((double)tiles * nch / 256.0) * (kl + 4);
-    if (cost < best_cost) { best_cost = cost; best = ch; }
-  }
-  klen = (nz + best - 1) / best;
-  g = dim3(full + 1, (ny + FNY - 1) / FNY, (nz + klen - 1) / klen);
-  return true;
-}
 // The boundary rules in compact form.  bc_pair always leaves L = R = v, and upwind_mac(v, v, .) = v, so on a physical boundary face every
 // stage's output IS v -- the inflow value, zero, the inner state, or the inner state clamped (bc_pair / the edge-state rule of mk_D_one: the same four cases):
 //   mode 1: ghost value   2: zero   3: inner state   4: inner state, min(.,0) on a lo face / max(.,0) on a hi face
@@ -641,9 +591,9 @@ template <bool NAR> DEVI SegGeo seg_geo(int W_) {
     G.o0 = G.om = G.op = 0;
     return G;
   }
-  const int tid = threadIdx.x, rpw = 64 / W_, seg = tid / W_;
-  G.W = W_; G.ROWS = TNY * rpw; G.live = seg < rpw; G.lane = tid - seg * W_;
-  G.row = G.live ? (int)threadIdx.y * rpw + seg : G.ROWS - 1;
+  const int tid = threadIdx.x, rpw = 64 / W_;
+  G.W = W_;
+  GOD_THREAD(W_, tid, (int)threadIdx.y, G.ROWS, G.live, G.lane, G.row)
   G.rowm = G.row >= 1 ? G.row - 1 : 0; G.rowp = G.row + 1 < G.ROWS ? G.row + 1 : G.ROWS - 1;
   G.o0 = G.live ? G.row * W_ + G.lane : G.ROWS * W_ + (int)threadIdx.y * (64 - rpw * W_) + (tid - rpw * W_);
   G.om = G.rowm * W_ + G.lane; G.op = G.rowp * W_ + G.lane;
@@ -672,13 +622,12 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, int SP = SP_R
   const SegGeo G = seg_geo<NAR>(segw);
   const int lane = G.lane, row = G.row;
   const int ownx = NAR ? G.W - 2 : FNX, owny = NAR ? G.ROWS - 2 : FNY;
-  const int i = r.lo[0] - 1 + BX * ownx + lane, j = r.lo[1] - 1 + BY * owny + row;
-  const bool own_ij = G.live && lane >= 1 && lane <= ownx && row >= 1 && row <= owny && i <= r.hi[0] && j <= r.hi[1];
+  GOD_CELL(r.lo, r.hi, ownx, owny, BX, BY, lane, row, G.live, i, j, own_ij)      // the tile -> cell map: godunov_plan.h
   const int ic = min(max(i, F.lo[0] - 1), F.hi[0] + 1), jc = min(max(j, F.lo[1] - 1), F.hi[1] + 1);
   const bool ing_ij = i == ic && j == jc;                            // a cell of the grown box
   const bool vx = i >= F.lo[0] && i <= F.hi[0], vy = j >= F.lo[1] && j <= F.hi[1];
   const int rowm = G.rowm, rowp = G.rowp;
-  const int k0 = r.lo[2] + BZ * klen, k1 = min(k0 + klen - 1, r.hi[2]);
+  GOD_PLANES(r.lo[2], r.hi[2], klen, BZ, k0, k1)
   const int KB = F.lo[2] - 1, KT = F.hi[2] + 1;                       // the planes loads are clamped to
   const double eps = eps_from(umax);
   const bool cons = SP != SP_RT ? (SP & SP_CONS) != 0 : F.cons != 0, minion = SP != SP_RT ? (SP & SP_MINION) != 0 : F.use_minion != 0;
@@ -958,21 +907,16 @@ template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, int SP = SP_R
   #undef PREMOD
   #undef Z_WORD
 }
+// touch = true: the workgroup (bx, by, bz) of tw lanes x th rows, ownx columns its own, comes near a face of F's box that carries a rule for F's component (footprint and rule: godunov_plan.h)
+#define MK_TOUCH(touch, F, r, tw, th, ownx, klen, UPD, bx, by, bz) {                                                                    \
+    GOD_FOOTPRINT(r.lo, r.hi, tw, th, ownx, klen, UPD, bx, by, bz, a0, a1)                                                                  \
+    GOD_TOUCH(touch, a0, a1, F.lo, F.hi, d, bc_mode(F.phys[d][0], F.is_vel != 0, F.c == d), bc_mode(F.phys[d][1], F.is_vel != 0, F.c == d)) }
 template <bool BC = true, bool INL = true, bool UPD = false, bool PW2 = false, int SP = SP_RT> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_m(FArgs F, Range3 r, int klen, const double *umax) {
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
   // a workgroup whose tile and k-chunk stay clear of every face that carries a rule runs the body without the boundary code (same values:
   // none of its cells is flagged); compiled into one kernel the lean path keeps its own register allocation (0.69 against 0.96 ms per launch)
   bool touch = false;
-  if (BC) {
-    const int i0 = r.lo[0] - 1 + bx_ * FNX, i1 = i0 + 63, j0 = r.lo[1] - 1 + by_ * FNY, j1 = j0 + TNY - 1;
-    const int k0 = r.lo[2] + bz_ * klen - 2, k1 = min(r.lo[2] + bz_ * klen + klen - 1, r.hi[2]) + 2 + (UPD ? 1 : 0);
-    const int a0[3] = { i0, j0, k0 }, a1[3] = { i1, j1, k1 };
-    #pragma unroll
-    for (int d = 0; d < 3; d++) {
-      if (bc_mode(F.phys[d][0], F.is_vel != 0, F.c == d) && a0[d] <= F.lo[d] + 1) touch = true;
-      if (bc_mode(F.phys[d][1], F.is_vel != 0, F.c == d) && a1[d] >= F.hi[d] - 1) touch = true;
-    }
-  }
+  if (BC) MK_TOUCH(touch, F, r, 64, TNY, FNX, klen, UPD, bx_, by_, bz_)
   __shared__ FShared<UPD> S;
   constexpr bool PEEL = SP != SP_RT || !UPD;       // (the update forms with run-time flags stay unpeeled: peeled, the inflow one needs scratch -- profiles/godunov_phases_ab.txt)
   if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2, false, SP, PEEL>(S, F, r, klen, umax, bx_, by_, bz_);
@@ -987,7 +931,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, int SP = SP_RT> __global__ void
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
   const bool narrow = bx_ == full;
   Range3 rr = r;
-  int tw = 64, th = TNY, ownx = FNX;
+  int tw = 64, th = TNY, ownx = FNX;      // (GOD_COL's map in this kernel's own text, as in kk_vp_F_mc: expanded from the header it changes the code of every instantiation)
   if (narrow) {
     tw = segw; th = TNY * (64 / segw); ownx = segw - 2;
     rr.lo[0] = r.lo[0] + full * FNX;
@@ -995,16 +939,7 @@ template <bool BC, bool INL, bool UPD, bool PW2, int SP = SP_RT> __global__ void
     bx_ = 0;
   } else rr.hi[0] = r.lo[0] + full * FNX - 1;
   bool touch = false;
-  if (BC) {
-    const int i0 = rr.lo[0] - 1 + bx_ * ownx, i1 = i0 + tw - 1, j0 = rr.lo[1] - 1 + by_ * (th - 2), j1 = j0 + th - 1;
-    const int k0 = rr.lo[2] + bz_ * klen - 2, k1 = min(rr.lo[2] + bz_ * klen + klen - 1, rr.hi[2]) + 2 + (UPD ? 1 : 0);
-    const int a0[3] = { i0, j0, k0 }, a1[3] = { i1, j1, k1 };
-    #pragma unroll
-    for (int d = 0; d < 3; d++) {
-      if (bc_mode(F.phys[d][0], F.is_vel != 0, F.c == d) && a0[d] <= F.lo[d] + 1) touch = true;
-      if (bc_mode(F.phys[d][1], F.is_vel != 0, F.c == d) && a1[d] >= F.hi[d] - 1) touch = true;
-    }
-  }
+  if (BC) MK_TOUCH(touch, F, rr, tw, th, ownx, klen, UPD, bx_, by_, bz_)
   __shared__ FShared<UPD> S;
   constexpr bool PEEL = SP != SP_RT;               // (as in kk_mk_F_m)
   if (narrow) {
@@ -1015,22 +950,6 @@ template <bool BC, bool INL, bool UPD, bool PW2, int SP = SP_RT> __global__ void
     else mk_F_m_body<false, false, UPD, PW2, false, SP, PEEL>(S, F, rr, klen, umax, bx_, by_, bz_);
   }
 }
-// The update-carrying power-of-two marches of a one-box level (what a step on 2^n cells runs) with the launch's flags compiled in: the combinations
-// that occur -- a conservative or a convective scalar with the force of the call, a velocity component with the forcing term formed in place, each
-// with and without use_minion; anything else takes the run-time form.  (uses blk and st of the caller)
-static int mk_sp(const FArgs &F) {
-  if (F.cons && F.fmode) return SP_RT;
-  return (F.cons ? SP_CONS : 0) | (F.use_minion ? SP_MINION : 0) | (F.fmode == 1 ? SP_FMODE1 : 0);
-}
-#define MK_LAUNCH_SP_(K, BC_, SP_, G_, ...) hipLaunchKernelGGL((K<BC_, false, true, true, SP_>), G_, blk, 0, st, __VA_ARGS__)
-#define MK_LAUNCH_SP(K, BC_, F_, G_, ...) switch (mk_sp(F_)) {                                                                \
-    case 0: MK_LAUNCH_SP_(K, BC_, 0, G_, __VA_ARGS__); break;                                                                  \
-    case SP_CONS: MK_LAUNCH_SP_(K, BC_, SP_CONS, G_, __VA_ARGS__); break;                                                      \
-    case SP_MINION: MK_LAUNCH_SP_(K, BC_, SP_MINION, G_, __VA_ARGS__); break;                                                  \
-    case SP_CONS | SP_MINION: MK_LAUNCH_SP_(K, BC_, SP_CONS | SP_MINION, G_, __VA_ARGS__); break;                              \
-    case SP_FMODE1: MK_LAUNCH_SP_(K, BC_, SP_FMODE1, G_, __VA_ARGS__); break;                                                  \
-    case SP_FMODE1 | SP_MINION: MK_LAUNCH_SP_(K, BC_, SP_FMODE1 | SP_MINION, G_, __VA_ARGS__); break;                          \
-    default: MK_LAUNCH_SP_(K, BC_, SP_RT, G_, __VA_ARGS__); }
 // the launch arguments of the fused march for component c; false when the field layouts do not allow the shared offsets
 static bool fused_args(FArgs &F, const GArgs &A, int c, const FV &s, const FV sl[3], const FV &um, const FV &vm, const FV &wm, const FV &force, const FV &macrhs,
                        const FV &sex, const FV &sey, const FV &sez, const FV &flx, const FV &fly, const FV &flz) {
@@ -1119,7 +1038,7 @@ DEVI int locate_box(const int *start, int nbox, int bid) {
   const D &q = as_constant(descs + ib_);                                                \
   const int l_ = (int)blockIdx.x - as_constant(start + ib_);                            \
   const int gy_ = q.G[1] > 0 ? q.G[1] : 1;                                               \
-  const int BX = l_ % q.G[0], BY = (l_ / q.G[0]) % gy_, BZ = l_ / (q.G[0] * gy_);
+  GOD_BATCH_WG(q.G[0], gy_, l_, BX, BY, BZ)
 template <class D> __global__ void __launch_bounds__(256) kk_slopes_b(const D *descs, const int *start, int nbox, int dirmask) {
   BATCH_LOCATE(D, gs)
   // gs[1] == 0: the plane flattened over the workgroup's 256 threads (gs[0] workgroups per plane) -- a 14 x 14 plane of a grown 8^3 box is one
@@ -1154,40 +1073,14 @@ __global__ void kk_velmax_b(const VpD *descs, const int *start, int nbox) {
   block_atomic_max(q.umax, m);
 }
 // the fused march for every box of a level in one launch (a descriptor per box and component; see kk_batched for the scheme)
-struct FBatchD { FArgs F; Range3 r; int klen; const double *umax; int g[3], sw; };      // sw: lanes of a row segment (NAR launches; seg_geo)
+struct FBatchD { FArgs F; Range3 r; int klen; const double *umax; int g[3], segw; };      // segw: lanes of a row segment (NAR launches; seg_geo)
 template <bool INL, bool PW2 = false, bool NAR = false> __global__ void __launch_bounds__(64 * TNY) kk_mk_F_mb(const FBatchD *descs, const int *start, int nbox) {
   BATCH_LOCATE(FBatchD, g)
   bool touch = false;                                // see kk_mk_F_m
-  {
-    const int tw = NAR ? q.sw : 64, th = NAR ? TNY * (64 / q.sw) : TNY;
-    const int i0 = q.r.lo[0] - 1 + BX * (tw - 2), i1 = i0 + tw - 1, j0 = q.r.lo[1] - 1 + BY * (th - 2), j1 = j0 + th - 1;
-    const int k0 = q.r.lo[2] + BZ * q.klen - 2, k1 = min(q.r.lo[2] + BZ * q.klen + q.klen - 1, q.r.hi[2]) + 2;
-    const int a0[3] = { i0, j0, k0 }, a1[3] = { i1, j1, k1 };
-    #pragma unroll
-    for (int d = 0; d < 3; d++) {
-      if (bc_mode(q.F.phys[d][0], q.F.is_vel != 0, q.F.c == d) && a0[d] <= q.F.lo[d] + 1) touch = true;
-      if (bc_mode(q.F.phys[d][1], q.F.is_vel != 0, q.F.c == d) && a1[d] >= q.F.hi[d] - 1) touch = true;
-    }
-  }
+  { const int tw = NAR ? q.segw : 64, th = NAR ? TNY * (64 / q.segw) : TNY; MK_TOUCH(touch, q.F, q.r, tw, th, tw - 2, q.klen, false, BX, BY, BZ) }
   __shared__ FShared<false> S;
-  if (touch) mk_F_m_body<true, INL, false, PW2, NAR>(S, q.F, q.r, q.klen, q.umax, BX, BY, BZ, q.sw);
-  else mk_F_m_body<false, false, false, PW2, NAR>(S, q.F, q.r, q.klen, q.umax, BX, BY, BZ, q.sw);
-}
-// k-chunks of a box in the batched launch: the boxes of a level fill the device together, so a box is cut only when it is tall
-// sw: 0 = full-width tiles (64 x TNY threads own 62 x 6 cells), else the width of the row segments that take the fewest workgroups (seg_geo: a
-// workgroup owns (sw - 2) x (TNY * (64 / sw) - 2) cells)
-static void fused_grid_small(const Range3 &r, int &klen, int g[3], int &sw) {
-  const int nx = r.hi[0] - r.lo[0] + 1, ny = r.hi[1] - r.lo[1] + 1, nz = r.hi[2] - r.lo[2] + 1;
-  const int chunks = std::max(1, (nz + 47) / 48);
-  klen = (nz + chunks - 1) / chunks;
-  g[0] = (nx + FNX - 1) / FNX; g[1] = (ny + FNY - 1) / FNY; g[2] = (nz + klen - 1) / klen;
-  sw = 0;
-  if (!::sw().god_segw) return;      // (the global accessor: sw is the segment width here)
-  int best = g[0] * g[1];
-  for (int w = 6; w <= 32; w++) {
-    const int ox = w - 2, oy = TNY * (64 / w) - 2, c = ((nx + ox - 1) / ox) * ((ny + oy - 1) / oy);
-    if (c < best) { best = c; sw = w; g[0] = (nx + ox - 1) / ox; g[1] = (ny + oy - 1) / oy; }
-  }
+  if (touch) mk_F_m_body<true, INL, false, PW2, NAR>(S, q.F, q.r, q.klen, q.umax, BX, BY, BZ, q.segw);
+  else mk_F_m_body<false, false, false, PW2, NAR>(S, q.F, q.r, q.klen, q.umax, BX, BY, BZ, q.segw);
 }
 
 // host side of a batch: grids of the slope and the reduction launch per box, their prefix sums, and the upload
@@ -1238,12 +1131,66 @@ static vdn_multifab comp_window(const vdn_multifab *m, int c0, int nc) {
   for (FV &f : v.fabs) f.p += f.sc * c0;
   return v;
 }
-static FV work_fv(double *p, const BoxP &b, int nc_unused) {
-  (void)nc_unused;
-  FV f; f.p = p; f.a0 = b.lo[0] - 1; f.a1 = b.lo[1] - 1; f.a2 = b.lo[2] - 1;
+static FV work_fv(const BoxP &b) {              // a field over the box grown by one, no memory yet
+  FV f; f.p = nullptr; f.a0 = b.lo[0] - 1; f.a1 = b.lo[1] - 1; f.a2 = b.lo[2] - 1;
   f.n0 = b.hi[0] - b.lo[0] + 3; f.n1 = b.hi[1] - b.lo[1] + 3; f.n2 = b.hi[2] - b.lo[2] + 3;
   f.sc = (long)f.n0 * f.n1 * f.n2;
   return f;
+}
+// ---- host side of the fused marches: tiling, grids and forms are godunov_plan.h's -------------------------------------------------------------
+// what both predictors set up per box (dm = 3), batched or box by box: the arguments, a work field over the grown box and its bytes, the ranges of the
+// slopes (rg: the grown box) and of the faces (rf), the three slope fields -- the step's kept ones (cached: ctx().slope_cache) or ncomp components each
+// from the arena -- and whether a face carries a rule (any) or is an inlet (inflow).  is_cons: null for velpred
+struct GodBox { GArgs A; FV w, sl[3]; size_t fld; Range3 rg, rf; bool any, inflow; };
+static GodBox god_box(const vdn_multifab *s, int ib, const vdn_bc_tower *bct, int bccomp, int ncomp, const double *dx, double dt, bool is_vel, const int *is_cons, bool cached) {
+  GodBox B;
+  fill_gargs(B.A, s, ib, bct, bccomp, ncomp, dx, dt);
+  B.A.is_vel = is_vel ? 1 : 0;
+  for (int c = 0; c < ncomp && is_cons; c++) B.A.cons[c] = is_cons[c] ? 1 : 0;
+  B.w = work_fv(make_boxp(s, ib, bct)); B.fld = (size_t)B.w.sc * sizeof(double);
+  B.any = B.inflow = false;
+  for (int d = 0; d < 3; d++) {
+    B.rg.lo[d] = B.A.lo[d] - 1; B.rg.hi[d] = B.A.hi[d] + 1; B.rf.lo[d] = B.A.lo[d]; B.rf.hi[d] = B.A.hi[d] + 1;
+    B.sl[d] = B.w; B.sl[d].p = cached ? ctx().slope_cache[d][ib] : (double *)arena_alloc(B.fld * ncomp);
+    for (int sd = 0; sd < 2; sd++) { B.any = B.any || bc_mode_host(B.A.phys[d][sd]); B.inflow = B.inflow || B.A.phys[d][sd] == VDN_INLET; }
+  }
+  return B;
+}
+struct Ext3 { int n[3]; Ext3(const Range3 &r) { for (int d = 0; d < 3; d++) n[d] = r.hi[d] - r.lo[d] + 1; } };
+// the grid of a descriptor's box in the batched launch (D: FBatchD, VBatchD)
+template <class D> static void batch_grid(D &q) {
+  const Ext3 e(q.r);
+  const GodGrid G = god_grid_small(e.n[0], e.n[1], e.n[2], sw().god_segw);
+  q.klen = G.klen; q.segw = G.segw; for (int d = 0; d < 3; d++) q.g[d] = G.g[d];
+}
+// the batched march of a level in two launches: the boxes in full-width tiles, then the narrow ones in row segments (seg_geo) -- the descriptors in
+// that order, each with the first workgroup of its box in its launch, one upload.  launch: the dispatch of the kernel family
+template <class D> static void launch_batched(std::vector<D> &fd, GodForm f, hipStream_t st, void (*launch)(const GodForm &, int, hipStream_t, const D *, const int *, int)) {
+  std::stable_partition(fd.begin(), fd.end(), [](const D &q) { return q.segw == 0; });
+  const int n = (int)fd.size(), nwide = (int)std::count_if(fd.begin(), fd.end(), [](const D &q) { return q.segw == 0; });
+  std::vector<int> start(n);
+  int tot[2] = { 0, 0 };
+  for (int t = 0; t < n; t++) { int &T = tot[t < nwide ? 0 : 1]; start[t] = T; T += fd[t].g[0] * fd[t].g[1] * fd[t].g[2]; }
+  D *dd = (D *)desc_scratch(sizeof(D) * n); int *ds = (int *)desc_scratch(sizeof(int) * n);
+  upload_staged(dd, fd.data(), sizeof(D) * n); upload_staged(ds, start.data(), sizeof(int) * n);
+  if (nwide) launch(f, tot[0], st, dd, ds, nwide);
+  f.nar = true;
+  if (nwide < n) launch(f, tot[1], st, dd + nwide, ds + nwide, n - nwide);
+}
+// one dispatch per kernel family: the instantiation of the form f from the family's list in godunov_plan.h, launched on the grid g and the stream st of
+// the dispatching function; a form outside the list is an error.  GOD_X_*: a list entry of a family as such a case, with the family's arguments
+#define GOD_CASE(FORM_, K, ...) if (f == FORM_) { hipLaunchKernelGGL(K, g, dim3(64, TNY, 1), 0, st, __VA_ARGS__); return; }
+#define GOD_NO_FORM(what) REQUIRE(false, what ": no march of the form bc %d inl %d upd %d pw2 %d sp %d nar %d cols %d", f.bc, f.inl, f.upd, f.pw2, f.sp, f.nar, f.cols)
+#define GOD_X_MK_M(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_mk_F_m<bc, inl, upd, pw2, sp>), F, r, G.klen, umax)
+#define GOD_X_MK_MC(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_mk_F_mc<bc, inl, upd, pw2, sp>), F, r, G.klen, umax, G.full, G.segw)
+#define GOD_X_MK_MB(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_mk_F_mb<inl, pw2, nar>), dd, ds, n)
+static void launch_mk(const GodForm &f, const GodGrid &G, hipStream_t st, const FArgs &F, const Range3 &r, const double *umax) {
+  const dim3 g(G.g[0], G.g[1], G.g[2]);
+  GOD_MK_M_FORMS(GOD_X_MK_M) GOD_MK_MC_FORMS(GOD_X_MK_MC) GOD_NO_FORM("mkflux");
+}
+static void launch_mk_b(const GodForm &f, int tot, hipStream_t st, const FBatchD *dd, const int *ds, int n) {
+  const dim3 g(tot);
+  GOD_MK_MB_FORMS(GOD_X_MK_MB) GOD_NO_FORM("mkflux, batched");
 }
 
 void k_slope(const vdn_multifab *s, vdn_multifab *slope, int dir, int bccomp, const vdn_bc_tower *bct) {
@@ -1251,9 +1198,9 @@ void k_slope(const vdn_multifab *s, vdn_multifab *slope, int dir, int bccomp, co
   if (s->nc > 3) {                                     // windows of three components (comp_window)
     for (int c0 = 0; c0 < s->nc; c0 += 3) {
       const int w = std::min(3, s->nc - c0);
-      const vdn_multifab sw = comp_window(s, c0, w);
+      const vdn_multifab sv = comp_window(s, c0, w);
       vdn_multifab lw = comp_window(slope, c0, w);
-      k_slope(&sw, &lw, dir, bccomp + c0, bct);
+      k_slope(&sv, &lw, dir, bccomp + c0, bct);
     }
     return;
   }
@@ -1298,56 +1245,27 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
     double *umax = (double *)arena_alloc(sizeof(double) * nb);
     HIPCHK(hipMemsetAsync(umax, 0, sizeof(double) * nb, st));
     std::vector<FBatchD> fd((size_t)nb * ncomp);
-    std::vector<int> fstart((size_t)nb * ncomp);
     bool ok = true, inflow = false;
     for (int ib = 0; ib < nb && ok; ib++) {
       MkD &q = B.d[ib];
-      fill_gargs(q.A, s, ib, bct, bccomp, ncomp, dx, dt);
-      q.A.is_vel = is_vel ? 1 : 0;
-      for (int c = 0; c < ncomp; c++) q.A.cons[c] = is_cons[c] ? 1 : 0;
-      BoxP bp = make_boxp(s, ib, bct);
-      FV w = work_fv(nullptr, bp, 0);
-      const size_t fld = (size_t)w.sc * sizeof(double);
-      q.sl0 = q.sl1 = q.sl2 = w;
-      q.sl0.p = (double *)arena_alloc(fld * ncomp); q.sl1.p = (double *)arena_alloc(fld * ncomp); q.sl2.p = (double *)arena_alloc(fld * ncomp);
-      for (int d = 0; d < 3; d++) { q.rg.lo[d] = q.A.lo[d] - 1; q.rg.hi[d] = q.A.hi[d] + 1; q.rf.lo[d] = q.A.lo[d]; q.rf.hi[d] = q.A.hi[d] + 1; }
-      q.rm = q.rf;
+      const GodBox X = god_box(s, ib, bct, bccomp, ncomp, dx, dt, is_vel, is_cons, false);
+      q.A = X.A; q.sl0 = X.sl[0]; q.sl1 = X.sl[1]; q.sl2 = X.sl[2]; q.rg = X.rg; q.rf = q.rm = X.rf;
       q.s = s->fabs[ib]; q.um = umac[0]->fabs[ib]; q.vm = umac[1]->fabs[ib]; q.wm = umac[2]->fabs[ib]; q.force = force->fabs[ib]; q.macrhs = mac_rhs->fabs[ib];
       q.sex = sedge[0]->fabs[ib]; q.sey = sedge[1]->fabs[ib]; q.sez = sedge[2]->fabs[ib]; q.flx = flux[0]->fabs[ib]; q.fly = flux[1]->fabs[ib]; q.flz = flux[2]->fabs[ib];
       q.umax = umax + ib;
-      const FV sl[3] = { q.sl0, q.sl1, q.sl2 };
-      for (int d = 0; d < 3; d++) inflow = inflow || q.A.phys[d][0] == VDN_INLET || q.A.phys[d][1] == VDN_INLET;
+      inflow = inflow || X.inflow;
       for (int c0 = 0; c0 < ncomp && ok; c0++) {
         FBatchD &f = fd[(size_t)c0 * nb + ib];
-        ok = fused_args(f.F, q.A, c0, q.s, sl, q.um, q.vm, q.wm, q.force, q.macrhs, q.sex, q.sey, q.sez, q.flx, q.fly, q.flz);
+        ok = fused_args(f.F, q.A, c0, q.s, X.sl, q.um, q.vm, q.wm, q.force, q.macrhs, q.sex, q.sey, q.sez, q.flx, q.fly, q.flz);
         f.r = q.rf; f.umax = q.umax;
-        fused_grid_small(f.r, f.klen, f.g, f.sw);
+        batch_grid(f);
       }
     }
     if (ok) {
       B.finish();
-      const dim3 blk(64, TNY, 1);
-      hipLaunchKernelGGL(kk_macmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);
+      hipLaunchKernelGGL(kk_macmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);      // per-box max |umac|
       hipLaunchKernelGGL(kk_slopes_b<MkD>, dim3(B.tot[0]), dim3(64, 4, 1), 0, st, B.dev, B.st[0], nb, 7);
-      // two launches: the boxes in full-width tiles, the narrow ones in row segments (seg_geo)
-      std::stable_partition(fd.begin(), fd.end(), [](const FBatchD &f) { return f.sw == 0; });
-      const size_t nwide = std::count_if(fd.begin(), fd.end(), [](const FBatchD &f) { return f.sw == 0; });
-      int tot = 0, totn = 0;
-      for (size_t t = 0; t < fd.size(); t++) { int &T = t < nwide ? tot : totn; fstart[t] = T; T += fd[t].g[0] * fd[t].g[1] * fd[t].g[2]; }
-      FBatchD *dd = (FBatchD *)desc_scratch(sizeof(FBatchD) * fd.size()); int *ds = (int *)desc_scratch(sizeof(int) * fstart.size());
-      upload_staged(dd, fd.data(), sizeof(FBatchD) * fd.size()); upload_staged(ds, fstart.data(), sizeof(int) * fstart.size());
-      const bool p2 = fd[0].F.p2 != 0;
-      if (nwide) {
-        if (inflow) hipLaunchKernelGGL(kk_mk_F_mb<true>, dim3(tot), blk, 0, st, dd, ds, (int)nwide);
-        else if (p2) hipLaunchKernelGGL((kk_mk_F_mb<false, true>), dim3(tot), blk, 0, st, dd, ds, (int)nwide);
-        else hipLaunchKernelGGL(kk_mk_F_mb<false>, dim3(tot), blk, 0, st, dd, ds, (int)nwide);
-      }
-      if (nwide < fd.size()) {
-        const int nn = (int)(fd.size() - nwide);
-        if (inflow) hipLaunchKernelGGL((kk_mk_F_mb<true, false, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
-        else if (p2) hipLaunchKernelGGL((kk_mk_F_mb<false, true, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
-        else hipLaunchKernelGGL((kk_mk_F_mb<false, false, true>), dim3(totn), blk, 0, st, dd + nwide, ds + nwide, nn);
-      }
+      launch_batched(fd, god_mk_form(true, inflow, fd[0].F.p2 != 0, false, SP_RT, false, true), st, launch_mk_b);      // (batched: inflow and p2 alone decide)
       arena_release(mark);
       return false;
     }
@@ -1355,17 +1273,9 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
   }
   for (int ib = 0; ib < s->nfabs(); ib++) {
     size_t mark = arena_mark();
-    GArgs A; fill_gargs(A, s, ib, bct, bccomp, ncomp, dx, dt);
-    A.is_vel = is_vel ? 1 : 0;
-    for (int c = 0; c < ncomp; c++) A.cons[c] = is_cons[c] ? 1 : 0;
-    BoxP bp = make_boxp(s, ib, bct);
-    FV w = work_fv(nullptr, bp, 0);
-    const size_t fld = (size_t)w.sc * sizeof(double);
-    FV sl[3];
-    const bool cached = is_vel && ncomp == 3 && (int)ctx().slope_src.size() == s->nfabs() && ctx().slope_src[ib] == s->fabs[ib].p;
-    for (int d = 0; d < 3; d++) { sl[d] = w; sl[d].p = cached ? ctx().slope_cache[d][ib] : (double *)arena_alloc(fld * ncomp); }
-    Range3 rg, rf;
-    for (int d = 0; d < 3; d++) { rg.lo[d] = A.lo[d] - 1; rg.hi[d] = A.hi[d] + 1; rf.lo[d] = A.lo[d]; rf.hi[d] = A.hi[d] + 1; }
+    const bool cached = is_vel && ncomp == 3 && (int)ctx().slope_src.size() == s->nfabs() && ctx().slope_src[ib] == s->fabs[ib].p;      // advance_timestep: velpred's slopes of the same u
+    const GodBox X = god_box(s, ib, bct, bccomp, ncomp, dx, dt, is_vel, is_cons, cached);
+    const GArgs &A = X.A; const FV *sl = X.sl; const Range3 &rg = X.rg, &rf = X.rf;
     const FV &um = umac[0]->fabs[ib], &vm = umac[1]->fabs[ib], &wm = umac[2]->fabs[ib];
     const bool mm_keep = (int)ctx().macmax_cache.size() == s->nfabs();       // advance_timestep: one reduction serves both mkflux calls of the step
     double *umax = mm_keep ? ctx().macmax_cache[ib] : (double *)arena_alloc(256);
@@ -1383,40 +1293,22 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
     if (fused) {                   // stages B + C + D in one march per component, boundary rules inside (see mk_F_m_body)
       bool do_upd = upd && sw().god_update;                  // (every box of a box-by-box level: the conditions are geometric and the same for all of them -- checked below)
       for (int c0 = 0; c0 < ncomp && do_upd; c0++) do_upd = fused_update_args(FA[c0], A, c0, upd->snew->fabs[ib], force->fabs[ib], *upd, ib);
-      int klF;
-      const dim3 gF = fused_grid(rf, klF), blk(64, TNY, 1);
+      // full 62-cell tiles, or where the form allows it and it saves workgroups the remainder column in narrow segments (kk_mk_F_mc)
+      const Ext3 e(rf);
+      const GodGrid gF = god_grid_tiles(e.n[0], e.n[1], e.n[2], sw().fused_kchunks);
+      GodGrid gM = gF;
+      const bool cols = god_grid_cols(e.n[0], e.n[1], e.n[2], sw().god_narrow, gM);
       for (int c0 = 0; c0 < ncomp; c0++) {
-        bool inflow = false;
-        for (int d = 0; d < 3; d++) inflow = inflow || A.phys[d][0] == VDN_INLET || A.phys[d][1] == VDN_INLET;
-        bool any = false;
-        for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) any = any || bc_mode_host(A.phys[d][sd]);
-        if (do_upd) {
-          const bool p2 = FA[c0].p2 != 0;                              // (the inflow variants keep the division: fewer instantiations)
-          if (!any) { if (p2) { MK_LAUNCH_SP(kk_mk_F_m, false, FA[c0], gF, FA[c0], rf, klF, umax) } else hipLaunchKernelGGL((kk_mk_F_m<false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); }
-          else if (inflow) hipLaunchKernelGGL((kk_mk_F_m<true, true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-          else if (p2) {
-            // full 62-cell tiles, then the remainder column in narrow segments (kk_mk_F_mc) where that saves workgroups
-            dim3 gM; int klM, full, segw;
-            if (fused_grid_cols(rf, gM, klM, full, segw)) {
-              MK_LAUNCH_SP(kk_mk_F_mc, true, FA[c0], gM, FA[c0], rf, klM, umax, full, segw)
-            } else { MK_LAUNCH_SP(kk_mk_F_m, true, FA[c0], gF, FA[c0], rf, klF, umax) }
-          }
-          else hipLaunchKernelGGL((kk_mk_F_m<true, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-          continue;
-        }
-        const bool p2 = FA[c0].p2 != 0;
-        if (!any) { if (p2) hipLaunchKernelGGL((kk_mk_F_m<false, false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax); else hipLaunchKernelGGL((kk_mk_F_m<false, false>), gF, blk, 0, st, FA[c0], rf, klF, umax); }      // no physical face on this box
-        else if (inflow) hipLaunchKernelGGL((kk_mk_F_m<true, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-        else if (p2) hipLaunchKernelGGL((kk_mk_F_m<true, false, false, true>), gF, blk, 0, st, FA[c0], rf, klF, umax);
-        else hipLaunchKernelGGL((kk_mk_F_m<true, false>), gF, blk, 0, st, FA[c0], rf, klF, umax);
+        const GodForm f = god_mk_form(X.any, X.inflow, FA[c0].p2 != 0, do_upd, god_mk_sp(FA[c0].cons != 0, FA[c0].use_minion != 0, FA[c0].fmode), cols, false);
+        launch_mk(f, f.cols ? gM : gF, st, FA[c0], rf, umax);
       }
       REQUIRE(ib == 0 || updated == do_upd, "mkflux: the update would ride along on some boxes of the level only");
       updated = do_upd;
     } else {                       // the face-centred stages: VDN_GODUNOV_PLAIN, or field layouts the fused march refuses
       REQUIRE(!updated, "mkflux: the update rode along on an earlier box of the level but cannot on box %d", ib);      // (every box or none)
-      FV SI = w, SC = w;
-      SI.p = (double *)arena_alloc(fld * 3 * ncomp);
-      SC.p = (double *)arena_alloc(fld * 6 * ncomp);
+      FV SI = X.w, SC = X.w;
+      SI.p = (double *)arena_alloc(X.fld * 3 * ncomp);
+      SC.p = (double *)arena_alloc(X.fld * 6 * ncomp);
       hipLaunchKernelGGL(kk_mk_B, grid_for(rg), dim3(64, 4, 1), 0, st, s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SI, A, rg, umax);
       hipLaunchKernelGGL(kk_mk_C, grid_for(rg), dim3(64, 4, 1), 0, st, s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SI, SC, A, rg, umax);
       hipLaunchKernelGGL(kk_mk_D, grid_for(rf), dim3(64, 4, 1), 0, st, s->fabs[ib], sl[0], sl[1], sl[2], um, vm, wm, force->fabs[ib], mac_rhs->fabs[ib], SC,
@@ -1445,13 +1337,13 @@ bool k_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab **flux, 
   bool updated = false;
   for (int c0 = 0; c0 < ncomp; c0 += 3) {
     const int w = std::min(3, ncomp - c0);
-    const vdn_multifab sw = comp_window(s, c0, w), fw = comp_window(force, c0, w);
+    const vdn_multifab sv = comp_window(s, c0, w), fw = comp_window(force, c0, w);
     vdn_multifab ew[3], xw[3], nw;
     vdn_multifab *ep[3] = { nullptr, nullptr, nullptr }, *xp[3] = { nullptr, nullptr, nullptr };
     for (int d = 0; d < dm; d++) { ew[d] = comp_window(sedge[d], c0, w); xw[d] = comp_window(flux[d], c0, w); ep[d] = &ew[d]; xp[d] = &xw[d]; }
     MkUpdate U;
     if (upd) { U = *upd; nw = comp_window(upd->snew, c0, w); U.snew = &nw; }
-    const bool u = mkflux_window(&sw, ep, xp, umac, &fw, mac_rhs, dx, dt, bct, is_vel, bccomp + c0, is_cons + c0, upd ? &U : nullptr);
+    const bool u = mkflux_window(&sv, ep, xp, umac, &fw, mac_rhs, dx, dt, bct, is_vel, bccomp + c0, is_cons + c0, upd ? &U : nullptr);
     REQUIRE(c0 == 0 || u == updated, "mkflux: the update rode along in some component windows of the level only");    // every window or none
     updated = u;
   }
@@ -1667,13 +1559,12 @@ template <bool BC, bool INL, bool PW2, bool NAR = false, int SP = SP_RT> __devic
   const SegGeo G = seg_geo<NAR>(segw);
   const int lane = G.lane, row = G.row;
   const int ownx = NAR ? G.W - 2 : FNX, owny = NAR ? G.ROWS - 2 : FNY;
-  const int i = r.lo[0] - 1 + BX * ownx + lane, j = r.lo[1] - 1 + BY * owny + row;
-  const bool own_ij = G.live && lane >= 1 && lane <= ownx && row >= 1 && row <= owny && i <= r.hi[0] && j <= r.hi[1];
+  GOD_CELL(r.lo, r.hi, ownx, owny, BX, BY, lane, row, G.live, i, j, own_ij)      // the tile -> cell map: godunov_plan.h
   const int ic = min(max(i, F.lo[0] - 1), F.hi[0] + 1), jc = min(max(j, F.lo[1] - 1), F.hi[1] + 1);
   const bool ing_ij = i == ic && j == jc;
   const bool vx = i >= F.lo[0] && i <= F.hi[0], vy = j >= F.lo[1] && j <= F.hi[1];
   const int rowm = G.rowm, rowp = G.rowp;
-  const int k0 = r.lo[2] + BZ * klen, k1 = min(k0 + klen - 1, r.hi[2]);
+  GOD_PLANES(r.lo[2], r.hi[2], klen, BZ, k0, k1)
   const int KB = F.lo[2] - 1, KT = F.hi[2] + 1;
   const double eps = eps_from(umax);
   // packed boundary codes of this thread: wf: x-face (3 comps x 4 bits, +8 = hi side), y-face (bits 12..23), stage-D code of the x-face (24..27) and
@@ -1958,6 +1849,8 @@ template <bool BC = true, bool INL = true, bool PW2 = false, int SP = SP_RT> __g
 // the remainder tile column in narrow segments inside the same launch (see kk_mk_F_mc)
 template <bool BC, bool INL, bool PW2, int SP = SP_RT> __global__ void __launch_bounds__(64 * TNY) kk_vp_F_mc(VArgs F, Range3 r, int klen, const double *umax, int full, int segw) {
   int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
+  // GOD_COL's map in this kernel's own text (expanded from the header it costs both instantiations two VGPRs): the same origin, cut and early exit, to be
+  // changed with it -- tests/cpp/godunov_plan_check.cpp holds GOD_COL, tests/test_godunov_phases_gpu.py this kernel against the face-centred stages
   Range3 rr = r;
   if (bx_ == full) {
     rr.lo[0] = r.lo[0] + full * FNX;
@@ -1994,10 +1887,10 @@ static bool vfused_args(VArgs &F, const GArgs &A, const FV &u, const FV sl[3], c
   return true;
 }
 
-struct VBatchD { VArgs F; Range3 r; int klen; const double *umax; int g[3], sw; };      // sw: lanes of a row segment (NAR launches; seg_geo)
+struct VBatchD { VArgs F; Range3 r; int klen; const double *umax; int g[3], segw; };      // segw: lanes of a row segment (NAR launches; seg_geo)
 template <bool BC, bool INL, bool PW2 = false, bool NAR = false> __global__ void __launch_bounds__(64 * TNY) kk_vp_F_mb(const VBatchD *descs, const int *start, int nbox) {
   BATCH_LOCATE(VBatchD, g)
-  vp_F_m_body<BC, INL, PW2, NAR>(q.F, q.r, q.klen, q.umax, BX, BY, BZ, q.sw);
+  vp_F_m_body<BC, INL, PW2, NAR>(q.F, q.r, q.klen, q.umax, BX, BY, BZ, q.segw);
 }
 
 // ====================================================================================================
@@ -2217,6 +2110,17 @@ static void k2_mkflux(const vdn_multifab *s, vdn_multifab **sedge, vdn_multifab 
   }
 }
 
+#define GOD_X_VP_M(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_vp_F_m<bc, inl, pw2, sp>), F, r, G.klen, umax)
+#define GOD_X_VP_MC(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_vp_F_mc<bc, inl, pw2, sp>), F, r, G.klen, umax, G.full, G.segw)
+#define GOD_X_VP_MB(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_vp_F_mb<bc, inl, pw2, nar>), dd, ds, n)
+static void launch_vp(const GodForm &f, const GodGrid &G, hipStream_t st, const VArgs &F, const Range3 &r, const double *umax) {
+  const dim3 g(G.g[0], G.g[1], G.g[2]);
+  GOD_VP_M_FORMS(GOD_X_VP_M) GOD_VP_MC_FORMS(GOD_X_VP_MC) GOD_NO_FORM("velpred");
+}
+static void launch_vp_b(const GodForm &f, int tot, hipStream_t st, const VBatchD *dd, const int *ds, int n) {
+  const dim3 g(tot);
+  GOD_VP_MB_FORMS(GOD_X_VP_MB) GOD_NO_FORM("velpred, batched");
+}
 void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *force, const double *dx, double dt,
                const vdn_bc_tower *bct) {
   Prof prof_("velpred");
@@ -2230,47 +2134,24 @@ void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *f
     double *umax = (double *)arena_alloc(sizeof(double) * nb);
     HIPCHK(hipMemsetAsync(umax, 0, sizeof(double) * nb, st));
     std::vector<VBatchD> fd(nb);
-    std::vector<int> fstart(nb);
     bool ok = true, inflow = false, any = false;
     for (int ib = 0; ib < nb && ok; ib++) {
       VpD &q = B.d[ib];
-      fill_gargs(q.A, u, ib, bct, 0, 3, dx, dt);
-      q.A.is_vel = 1;
-      BoxP bp = make_boxp(u, ib, bct);
-      FV w = work_fv(nullptr, bp, 0);
-      const size_t fld = (size_t)w.sc * sizeof(double);
-      q.sl0 = q.sl1 = q.sl2 = w;
-      q.sl0.p = (double *)arena_alloc(fld * 3); q.sl1.p = (double *)arena_alloc(fld * 3); q.sl2.p = (double *)arena_alloc(fld * 3);
-      for (int d = 0; d < 3; d++) { q.rm.lo[d] = q.A.lo[d]; q.rm.hi[d] = q.A.hi[d]; q.rg.lo[d] = q.A.lo[d] - 1; q.rg.hi[d] = q.A.hi[d] + 1; q.rf.lo[d] = q.A.lo[d]; q.rf.hi[d] = q.A.hi[d] + 1; }
+      const GodBox X = god_box(u, ib, bct, 0, 3, dx, dt, true, nullptr, false);
+      q.A = X.A; q.sl0 = X.sl[0]; q.sl1 = X.sl[1]; q.sl2 = X.sl[2]; q.rg = X.rg; q.rf = X.rf;
+      for (int d = 0; d < 3; d++) { q.rm.lo[d] = q.A.lo[d]; q.rm.hi[d] = q.A.hi[d]; }
       q.s = u->fabs[ib]; q.force = force->fabs[ib]; q.um = umac[0]->fabs[ib]; q.vm = umac[1]->fabs[ib]; q.wm = umac[2]->fabs[ib];
       q.umax = umax + ib;
-      const FV sl[3] = { q.sl0, q.sl1, q.sl2 };
-      for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) { inflow = inflow || q.A.phys[d][sd] == VDN_INLET; any = any || bc_mode_host(q.A.phys[d][sd]); }
-      ok = vfused_args(fd[ib].F, q.A, q.s, sl, q.force, q.um, q.vm, q.wm);
+      any = any || X.any; inflow = inflow || X.inflow;
+      ok = vfused_args(fd[ib].F, q.A, q.s, X.sl, q.force, q.um, q.vm, q.wm);
       fd[ib].r = q.rf; fd[ib].umax = q.umax;
-      fused_grid_small(fd[ib].r, fd[ib].klen, fd[ib].g, fd[ib].sw);
+      batch_grid(fd[ib]);
     }
     if (ok) {
       B.finish();
-      const dim3 blk(64, TNY, 1);
-      hipLaunchKernelGGL(kk_velmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);
+      hipLaunchKernelGGL(kk_velmax_b, dim3(B.tot[1]), dim3(64, 4, 1), 0, st, B.dev, B.st[1], nb);       // per-box max |u| over the valid cells
       hipLaunchKernelGGL(kk_slopes_b<VpD>, dim3(B.tot[0]), dim3(64, 4, 1), 0, st, B.dev, B.st[0], nb, 7);
-      // two launches: the boxes in full-width tiles, the narrow ones in row segments (seg_geo)
-      std::stable_partition(fd.begin(), fd.end(), [](const VBatchD &f) { return f.sw == 0; });
-      const int nwide = (int)std::count_if(fd.begin(), fd.end(), [](const VBatchD &f) { return f.sw == 0; });
-      int tot = 0, totn = 0;
-      for (int t = 0; t < nb; t++) { int &T = t < nwide ? tot : totn; fstart[t] = T; T += fd[t].g[0] * fd[t].g[1] * fd[t].g[2]; }
-      VBatchD *dd = (VBatchD *)desc_scratch(sizeof(VBatchD) * nb); int *ds = (int *)desc_scratch(sizeof(int) * nb);
-      upload_staged(dd, fd.data(), sizeof(VBatchD) * nb); upload_staged(ds, fstart.data(), sizeof(int) * nb);
-      const bool p2 = fd[0].F.p2 != 0;
-      #define VP_LAUNCH(NARROW, T, D0, S0, N)                                                                                                          \
-        if (!any) { if (p2) hipLaunchKernelGGL((kk_vp_F_mb<false, false, true, NARROW>), dim3(T), blk, 0, st, D0, S0, N); else hipLaunchKernelGGL((kk_vp_F_mb<false, false, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N); } \
-        else if (inflow) hipLaunchKernelGGL((kk_vp_F_mb<true, true, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N);                                      \
-        else if (p2) hipLaunchKernelGGL((kk_vp_F_mb<true, false, true, NARROW>), dim3(T), blk, 0, st, D0, S0, N);                                          \
-        else hipLaunchKernelGGL((kk_vp_F_mb<true, false, false, NARROW>), dim3(T), blk, 0, st, D0, S0, N);
-      if (nwide) { VP_LAUNCH(false, tot, dd, ds, nwide) }
-      if (nwide < nb) { VP_LAUNCH(true, totn, dd + nwide, ds + nwide, nb - nwide) }
-      #undef VP_LAUNCH
+      launch_batched(fd, god_vp_form(any, inflow, fd[0].F.p2 != 0, false, false, true), st, launch_vp_b);
       arena_release(mark);
       return;
     }
@@ -2278,43 +2159,25 @@ void k_velpred(const vdn_multifab *u, vdn_multifab **umac, const vdn_multifab *f
   }
   for (int ib = 0; ib < u->nfabs(); ib++) {
     size_t mark = arena_mark();
-    GArgs A; fill_gargs(A, u, ib, bct, 0, 3, dx, dt);
-    A.is_vel = 1;
-    BoxP bp = make_boxp(u, ib, bct);
-    FV w = work_fv(nullptr, bp, 0);
-    const size_t fld = (size_t)w.sc * sizeof(double);
-    FV sl[3];
     const bool keep = (int)ctx().slope_src.size() == u->nfabs();           // advance_timestep: mkflux(uold) reuses these slopes
-    for (int d = 0; d < 3; d++) { sl[d] = w; sl[d].p = keep ? ctx().slope_cache[d][ib] : (double *)arena_alloc(fld * 3); }
+    const GodBox X = god_box(u, ib, bct, 0, 3, dx, dt, true, nullptr, keep);
+    const GArgs &A = X.A; const FV *sl = X.sl; const Range3 &rg = X.rg, &rf = X.rf;
     if (keep) ctx().slope_src[ib] = u->fabs[ib].p;
     double *umax = (double *)arena_alloc(256);
     HIPCHK(hipMemsetAsync(umax, 0, sizeof(double), st));
-    Range3 rg, rf;
-    for (int d = 0; d < 3; d++) { rg.lo[d] = A.lo[d] - 1; rg.hi[d] = A.hi[d] + 1; rf.lo[d] = A.lo[d]; rf.hi[d] = A.hi[d] + 1; }
     launch_slopes(u->fabs[ib], sl, A, rg, 3, umax, st);      // + max |u| (kk_velmax)
     VArgs VA;
     if (!sw().godunov_plain && vfused_args(VA, A, u->fabs[ib], sl, force->fabs[ib], umac[0]->fabs[ib], umac[1]->fabs[ib], umac[2]->fabs[ib])) {
-      int klF;                     // stages B + C + D in one march, boundary rules inside (see vp_F_m_body)
-      const dim3 gF = fused_grid(rf, klF), blk(64, TNY, 1);
-      bool any = false, inflow = false;
-      for (int d = 0; d < 3; d++) for (int sd = 0; sd < 2; sd++) { any = any || bc_mode_host(A.phys[d][sd]); inflow = inflow || A.phys[d][sd] == VDN_INLET; }
-      const bool p2 = VA.p2 != 0;
-      // (the power-of-two forms with use_minion compiled in: SP of vp_F_m_body)
-      #define VP_LAUNCH_SP(K, BC_, G_, ...) { if (VA.use_minion) hipLaunchKernelGGL((K<BC_, false, true, SP_MINION>), G_, blk, 0, st, __VA_ARGS__); \
-                                              else hipLaunchKernelGGL((K<BC_, false, true, 0>), G_, blk, 0, st, __VA_ARGS__); }
-      if (!any) { if (p2) VP_LAUNCH_SP(kk_vp_F_m, false, gF, VA, rf, klF, umax) else hipLaunchKernelGGL((kk_vp_F_m<false, false>), gF, blk, 0, st, VA, rf, klF, umax); }
-      else if (inflow) hipLaunchKernelGGL((kk_vp_F_m<true, true>), gF, blk, 0, st, VA, rf, klF, umax);
-      else if (p2) {
-        dim3 gM; int klM, full, segw;
-        if (fused_grid_cols(rf, gM, klM, full, segw)) VP_LAUNCH_SP(kk_vp_F_mc, true, gM, VA, rf, klM, umax, full, segw)
-        else VP_LAUNCH_SP(kk_vp_F_m, true, gF, VA, rf, klF, umax)
-      }
-      else hipLaunchKernelGGL((kk_vp_F_m<true, false>), gF, blk, 0, st, VA, rf, klF, umax);
-      #undef VP_LAUNCH_SP
+      const Ext3 e(rf);             // stages B + C + D in one march, boundary rules inside (see vp_F_m_body)
+      const GodGrid gF = god_grid_tiles(e.n[0], e.n[1], e.n[2], sw().fused_kchunks);
+      GodGrid gM = gF;
+      const bool cols = god_grid_cols(e.n[0], e.n[1], e.n[2], sw().god_narrow, gM);
+      const GodForm f = god_vp_form(X.any, X.inflow, VA.p2 != 0, VA.use_minion != 0, cols, false);
+      launch_vp(f, f.cols ? gM : gF, st, VA, rf, umax);
     } else {                       // the face-centred stages: VDN_GODUNOV_PLAIN, or field layouts the fused march refuses
-      FV UI = w, XC = w;
-      UI.p = (double *)arena_alloc(fld * 9);
-      XC.p = (double *)arena_alloc(fld * 6);
+      FV UI = X.w, XC = X.w;
+      UI.p = (double *)arena_alloc(X.fld * 9);
+      XC.p = (double *)arena_alloc(X.fld * 6);
       hipLaunchKernelGGL(kk_vp_B, grid_for(rg), dim3(64, 4, 1), 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, A, rg, umax);
       hipLaunchKernelGGL(kk_vp_C, grid_for(rg), dim3(64, 4, 1), 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC, A, rg, umax);
       hipLaunchKernelGGL(kk_vp_D, grid_for(rf), dim3(64, 4, 1), 0, st, u->fabs[ib], sl[0], sl[1], sl[2], force->fabs[ib], UI, XC,
