@@ -145,7 +145,8 @@ const char *vdn_debug_switches(void);
  * `unsigned vdn_nd_lds_levels(void)`: bit l is set when level l of the last nodal solve ran as one launch down and one up (tests/test_nd_lds_levels_gpu.py), and
  * `int vdn_last_tail_form(int which)`: the body the last one-workgroup tail cycle of a cell-centred (which = 0) or the nodal (1) solve took, 0: on global memory,
  * 1: levels in LDS (tests/test_tail_cycles_gpu.py), and `int vdn_last_slopes_form(void)`: the form the last slope launch of velpred / mkflux took, 0: one thread
- * per cell, 1: the k-march with one cell per lane, 2: its pair form (tests/test_slopes_march_gpu.py). */
+ * per cell, 1: the k-march with one cell per lane, 2: its pair form (tests/test_slopes_march_gpu.py), and `int vdn_last_mkflux_form(void)`: the family of the last
+ * one-box mkflux march, 0: kk_mk_F_m, 1: kk_mk_F_mc, 16 / 32: kk_mk_F_mh in segments of that many lanes (tests/test_godunov_half_gpu.py). */
 const char *vdn_build_flavour(void);
 int  vdn_finalize(void);
 const char *vdn_last_error(void);

@@ -583,17 +583,17 @@ DEVI double bc_v(int m, int side, double in, double ghost) {
 // segment own nothing, load clamped addresses and park their stores in the slots the rows do not use.  A level of 997 boxes of which 670 are 8 cells wide
 // marches 0.52 x the wave-planes of the full-width tiling (tools/box_histogram.py).
 struct SegGeo { int W, ROWS, lane, row, rowm, rowp, o0, om, op; bool live; };
-template <bool NAR> DEVI SegGeo seg_geo(int W_) {
+template <bool NAR, int TY = TNY> DEVI SegGeo seg_geo(int W_) {      // TY: the waves of the workgroup (THY: kk_mk_F_mh)
   SegGeo G;
   if (!NAR) {
-    G.W = 64; G.ROWS = TNY; G.lane = threadIdx.x; G.row = threadIdx.y; G.live = true;
-    G.rowm = G.row >= 1 ? G.row - 1 : 0; G.rowp = G.row + 1 < TNY ? G.row + 1 : TNY - 1;
+    G.W = 64; G.ROWS = TY; G.lane = threadIdx.x; G.row = threadIdx.y; G.live = true;
+    G.rowm = G.row >= 1 ? G.row - 1 : 0; G.rowp = G.row + 1 < TY ? G.row + 1 : TY - 1;
     G.o0 = G.om = G.op = 0;
     return G;
   }
   const int tid = threadIdx.x, rpw = 64 / W_;
   G.W = W_;
-  GOD_THREAD(W_, tid, (int)threadIdx.y, G.ROWS, G.live, G.lane, G.row)
+  GOD_THREAD_T(TY, W_, tid, (int)threadIdx.y, G.ROWS, G.live, G.lane, G.row)
   G.rowm = G.row >= 1 ? G.row - 1 : 0; G.rowp = G.row + 1 < G.ROWS ? G.row + 1 : G.ROWS - 1;
   G.o0 = G.live ? G.row * W_ + G.lane : G.ROWS * W_ + (int)threadIdx.y * (64 - rpw * W_) + (tid - rpw * W_);
   G.om = G.rowm * W_ + G.lane; G.op = G.rowp * W_ + G.lane;
@@ -615,11 +615,11 @@ template <bool NAR> DEVI SegGeo seg_geo(int W_) {
 // lB / lC / lD, last iteration's lSI / lSC / lE) behind it.  Same expressions, same operands, same bits; the buffers stay double: a wave that has
 // passed barrier kk reads buffer kk & 1 and last iteration's lSI / lSC / lE while the fastest wave writes buffer (kk + 1) & 1 and this iteration's.
 // the y-exchange arrays of the march, ONE allocation per kernel shared by the bodies inlined into it (boundary / lean, full-width / narrow)
-template <bool UPD> struct FShared { double lB[2][TNY][64], lSI[2][TNY][64], lC[2][2][TNY][64], lSC[2][2][TNY][64], lD[2][TNY][64], lE[UPD ? 2 : 1][UPD ? TNY : 1][64]; };
-template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, int SP = SP_RT, bool PEEL = false> __device__ __forceinline__ void mk_F_m_body(FShared<UPD> &S, const FArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
-  double (&lB)[2][TNY][64] = S.lB, (&lSI)[2][TNY][64] = S.lSI, (&lC)[2][2][TNY][64] = S.lC, (&lSC)[2][2][TNY][64] = S.lSC, (&lD)[2][TNY][64] = S.lD;
-  double (&lE)[UPD ? 2 : 1][UPD ? TNY : 1][64] = S.lE;
-  const SegGeo G = seg_geo<NAR>(segw);
+template <bool UPD, int TY = TNY> struct FShared { double lB[2][TY][64], lSI[2][TY][64], lC[2][2][TY][64], lSC[2][2][TY][64], lD[2][TY][64], lE[UPD ? 2 : 1][UPD ? TY : 1][64]; };
+template <bool BC, bool INL, bool UPD, bool PW2, bool NAR = false, int SP = SP_RT, bool PEEL = false, int TY = TNY> __device__ __forceinline__ void mk_F_m_body(FShared<UPD, TY> &S, const FArgs &F, const Range3 &r, int klen, const double *umax, const int BX, const int BY, const int BZ, const int segw = 64) {
+  double (&lB)[2][TY][64] = S.lB, (&lSI)[2][TY][64] = S.lSI, (&lC)[2][2][TY][64] = S.lC, (&lSC)[2][2][TY][64] = S.lSC, (&lD)[2][TY][64] = S.lD;
+  double (&lE)[UPD ? 2 : 1][UPD ? TY : 1][64] = S.lE;
+  const SegGeo G = seg_geo<NAR, TY>(segw);
   const int lane = G.lane, row = G.row;
   const int ownx = NAR ? G.W - 2 : FNX, owny = NAR ? G.ROWS - 2 : FNY;
   GOD_CELL(r.lo, r.hi, ownx, owny, BX, BY, lane, row, G.live, i, j, own_ij)      // the tile -> cell map: godunov_plan.h
@@ -950,6 +950,19 @@ template <bool BC, bool INL, bool UPD, bool PW2, int SP = SP_RT> __global__ void
     else mk_F_m_body<false, false, UPD, PW2, false, SP, PEEL>(S, F, rr, klen, umax, bx_, by_, bz_);
   }
 }
+// Half workgroups on wide one-box levels.  At 231 to 251 VGPRs a CU holds eight waves of these marches, and in kk_mk_F_mc they are ONE workgroup: one
+// batch of loads and one barrier per plane, so all eight wait for memory together and compute together.  Here a workgroup is 64 x THY threads with half
+// the shared arrays (32 KB), and two of them share a CU -- the same occupancy, but the two march independently.  Every tile runs the segmented body (NAR)
+// in segments of segw = 16 or 32 lanes: THY * 64 / segw rows, all lanes live; grid and chunk rule: god_grid_half.  Same body, same values.
+template <bool BC, bool INL, bool UPD, bool PW2, int SP = SP_RT> __global__ void __launch_bounds__(64 * THY, 2) kk_mk_F_mh(FArgs F, Range3 r, int klen, const double *umax, int segw) {
+  int bx_, by_, bz_; xcd_remap(bx_, by_, bz_);
+  bool touch = false;
+  if (BC) MK_TOUCH(touch, F, r, segw, THY * (64 / segw), segw - 2, klen, UPD, bx_, by_, bz_)
+  __shared__ FShared<UPD, THY> S;
+  constexpr bool PEEL = SP != SP_RT;               // (as in kk_mk_F_m)
+  if (BC && touch) mk_F_m_body<BC, INL, UPD, PW2, true, SP, PEEL, THY>(S, F, r, klen, umax, bx_, by_, bz_, segw);
+  else mk_F_m_body<false, false, UPD, PW2, true, SP, PEEL, THY>(S, F, r, klen, umax, bx_, by_, bz_, segw);
+}
 // the launch arguments of the fused march for component c; false when the field layouts do not allow the shared offsets
 static bool fused_args(FArgs &F, const GArgs &A, int c, const FV &s, const FV sl[3], const FV &um, const FV &vm, const FV &wm, const FV &force, const FV &macrhs,
                        const FV &sex, const FV &sey, const FV &sez, const FV &flx, const FV &fly, const FV &flz) {
@@ -1183,10 +1196,16 @@ template <class D> static void launch_batched(std::vector<D> &fd, GodForm f, hip
 #define GOD_NO_FORM(what) REQUIRE(false, what ": no march of the form bc %d inl %d upd %d pw2 %d sp %d nar %d cols %d", f.bc, f.inl, f.upd, f.pw2, f.sp, f.nar, f.cols)
 #define GOD_X_MK_M(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_mk_F_m<bc, inl, upd, pw2, sp>), F, r, G.klen, umax)
 #define GOD_X_MK_MC(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_mk_F_mc<bc, inl, upd, pw2, sp>), F, r, G.klen, umax, G.full, G.segw)
+#define GOD_X_MK_MH(bc, inl, upd, pw2, sp, nar, cols) if (f == GOD_FORM_HALF(bc, inl, upd, pw2, sp, nar, cols)) { hipLaunchKernelGGL((kk_mk_F_mh<bc, inl, upd, pw2, sp>), g, dim3(64, THY, 1), 0, st, F, r, G.klen, umax, G.segw); return; }
 #define GOD_X_MK_MB(bc, inl, upd, pw2, sp, nar, cols) GOD_CASE(GOD_FORM(bc, inl, upd, pw2, sp, nar, cols), (kk_mk_F_mb<inl, pw2, nar>), dd, ds, n)
+// testing build (vdn_last_mkflux_form): the family the last one-box mkflux march came from -- 0: kk_mk_F_m; 1: kk_mk_F_mc; 16 / 32: kk_mk_F_mh in segments of
+// that many lanes; -1: none yet
+static int g_mk_form = -1;
+int mkflux_last_form() { return g_mk_form; }
 static void launch_mk(const GodForm &f, const GodGrid &G, hipStream_t st, const FArgs &F, const Range3 &r, const double *umax) {
   const dim3 g(G.g[0], G.g[1], G.g[2]);
-  GOD_MK_M_FORMS(GOD_X_MK_M) GOD_MK_MC_FORMS(GOD_X_MK_MC) GOD_NO_FORM("mkflux");
+  g_mk_form = f.half ? G.segw : f.cols ? 1 : 0;
+  GOD_MK_M_FORMS(GOD_X_MK_M) GOD_MK_MC_FORMS(GOD_X_MK_MC) GOD_MK_MH_FORMS(GOD_X_MK_MH) GOD_NO_FORM("mkflux");
 }
 static void launch_mk_b(const GodForm &f, int tot, hipStream_t st, const FBatchD *dd, const int *ds, int n) {
   const dim3 g(tot);
@@ -1298,9 +1317,13 @@ static bool mkflux_window(const vdn_multifab *s, vdn_multifab **sedge, vdn_multi
       const GodGrid gF = god_grid_tiles(e.n[0], e.n[1], e.n[2], sw().fused_kchunks);
       GodGrid gM = gF;
       const bool cols = god_grid_cols(e.n[0], e.n[1], e.n[2], sw().god_narrow, gM);
+      // a wide box: half workgroups in place of the column grid (kk_mk_F_mh)
+      const GodHalf H = god_half_switch(sw().god_narrow);
+      const bool half = god_half_fits(e.n[0], e.n[1], H.on, H.min);
+      const GodGrid gH = half ? god_grid_half(e.n[0], e.n[1], e.n[2], H.W, sw().fused_kchunks) : gF;
       for (int c0 = 0; c0 < ncomp; c0++) {
-        const GodForm f = god_mk_form(X.any, X.inflow, FA[c0].p2 != 0, do_upd, god_mk_sp(FA[c0].cons != 0, FA[c0].use_minion != 0, FA[c0].fmode), cols, false);
-        launch_mk(f, f.cols ? gM : gF, st, FA[c0], rf, umax);
+        const GodForm f = god_mk_form(X.any, X.inflow, FA[c0].p2 != 0, do_upd, god_mk_sp(FA[c0].cons != 0, FA[c0].use_minion != 0, FA[c0].fmode), cols, false, half);
+        launch_mk(f, f.half ? gH : f.cols ? gM : gF, st, FA[c0], rf, umax);
       }
       REQUIRE(ib == 0 || updated == do_upd, "mkflux: the update would ride along on some boxes of the level only");
       updated = do_upd;

@@ -1,10 +1,10 @@
 // godunov_plan.h -- the tiling and the launch forms of the fused Godunov marches (kk_mk_F_* and kk_vp_F_* in godunov.hip): the tile constants, the
-// k-chunk rule, the three grids built on it, which thread of which workgroup computes and owns which cell, a workgroup's footprint and the rule that
+// k-chunk rule, the four grids built on it, which thread of which workgroup computes and owns which cell, a workgroup's footprint and the rule that
 // decides from it whether the workgroup needs the boundary code, the template instantiation a launch takes, and when a level is batched.  Integers and
 // plain structs only: no HIP runtime, no ctx(), no sw() -- what a switch decides arrives as an argument.  The kernels and the launchers read it, and so
 // does tests/cpp/godunov_plan_check.cpp with a host compiler, so the mapping exists in one place.
 //
-// A workgroup is 64 x TNY threads and marches its tile through k0 .. k1 of the face range r.  Its rows are cut into segments of W lanes (W = 64: one
+// A workgroup is 64 x TNY threads (64 x THY in the half form, god_grid_half) and marches its tile through k0 .. k1 of the face range r.  Its rows are cut into segments of W lanes (W = 64: one
 // row per wave, the full-width tile; W < 64: 64 / W rows per wave): the first and last lane of a segment and the first and last row of a workgroup only
 // feed their neighbours, so tiles overlap by two cells.  The workgroup index (bx, by, bz) is the one after the XCD-aware remap (a bijection of the grid).
 #pragma once
@@ -19,6 +19,7 @@
 #endif
 
 constexpr int TNY = 8;                      // rows per tile: workgroup = 64 x TNY threads
+constexpr int THY = 4;                      // the half workgroup (kk_mk_F_mh): 64 x THY threads, two of them per compute unit
 constexpr int FNX = 62, FNY = TNY - 2;      // cells a full-width tile owns per row / rows it owns
 // SP: the launch-uniform flags of a one-box march as a template argument -- cons, use_minion and (UPD) the update's forcing mode compiled in, so that
 // neither arm of a flag nor the copies around it stay in the plane loop (f_bases, tvq, the stage-D chains, the update); SP_RT: read from FArgs at run
@@ -32,10 +33,12 @@ constexpr int SP_RT = -1, SP_CONS = 1, SP_MINION = 2, SP_FMODE1 = 4;
 // instruction for instruction -- and the functions of the next section, which the host and the check call, are the same macros expanded: one text.
 // thread (tx, ty) of a workgroup in segments of W lanes: the rows the workgroup carries, the thread's lane in its segment and its row; live = false: a
 // lane left over after the wave's last segment (it owns nothing and rides along in the last row)
-#define GOD_THREAD(W, tx, ty, rows, live, lane, row)                                                                                     \
+// (TY: the waves of the workgroup, TNY or THY)
+#define GOD_THREAD_T(TY, W, tx, ty, rows, live, lane, row)                                                                               \
   const int rpw_ = 64 / (W), seg_ = (tx) / (W);                                                                                          \
-  rows = TNY * rpw_; live = seg_ < rpw_; lane = (tx) - seg_ * (W);                                                                       \
+  rows = (TY) * rpw_; live = seg_ < rpw_; lane = (tx) - seg_ * (W);                                                                      \
   row = live ? (ty) * rpw_ + seg_ : rows - 1;
+#define GOD_THREAD(W, tx, ty, rows, live, lane, row) GOD_THREAD_T(TNY, W, tx, ty, rows, live, lane, row)
 // the cell (i, j) that lane / row of workgroup (bx, by) computes in the range lo .. hi, and whether it owns it (ownx, owny: GodSeg)
 #define GOD_CELL(lo, hi, ownx, owny, bx, by, lane, row, live, i, j, own)                                                                 \
   const int i = (lo)[0] - 1 + (bx) * (ownx) + (lane), j = (lo)[1] - 1 + (by) * (owny) + (row);                                           \
@@ -76,10 +79,10 @@ constexpr int SP_RT = -1, SP_CONS = 1, SP_MINION = 2, SP_FMODE1 = 4;
 
 // ---- segments, threads, cells, footprints ---------------------------------------------------------------------------------------------------------
 struct GodSeg { int W, rows, ownx, owny; };         // lanes of a row segment, rows a workgroup carries, columns / rows it owns
-GOD_FN GodSeg god_seg(int W) { return GodSeg{ W, TNY * (64 / W), W - 2, TNY * (64 / W) - 2 }; }
-GOD_FN bool god_thread(int W, int tx, int ty, int &lane, int &row) {
+GOD_FN GodSeg god_seg(int W, int TY = TNY) { return GodSeg{ W, TY * (64 / W), W - 2, TY * (64 / W) - 2 }; }
+GOD_FN bool god_thread(int W, int tx, int ty, int &lane, int &row, int TY = TNY) {
   int rows; bool live;
-  GOD_THREAD(W, tx, ty, rows, live, lane, row)
+  GOD_THREAD_T(TY, W, tx, ty, rows, live, lane, row)
   return live;
 }
 struct GodCell { int i, j; bool own; };             // the cell a thread computes, and whether it stores it
@@ -117,6 +120,16 @@ GOD_FN int god_chunks(int tiles, int nz) {
   }
   return best;
 }
+// two 256-thread workgroups per CU at a time (kk_mk_F_mh) are 512 workgroup slots: god_chunks' rule with the slot count as an argument
+GOD_FN int god_chunks_slots(int tiles, int nz, int slots) {
+  int best = 1; long long best_cost = -1;
+  for (int ch = 1; ch <= 16 && ch <= nz; ch++) {
+    const int kl = (nz + ch - 1) / ch, nch = (nz + kl - 1) / kl;
+    const long long cost = (((long long)tiles * nch + slots - 1) / slots) * (kl + 4);
+    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = ch; }
+  }
+  return best;
+}
 // g: workgroups per direction; klen: planes per k-chunk; segw: lanes of the narrow segments (0: full-width tiles only); full: the full tile columns in
 // front of the remainder column (column grid only)
 struct GodGrid { int g[3], klen, segw, full; };
@@ -140,6 +153,23 @@ GOD_FN bool god_grid_cols(int nx, int ny, int nz, bool narrow, GodGrid &G) {
   G.g[0] = G.full + 1; G.g[1] = (ny + FNY - 1) / FNY; G.g[2] = (nz + G.klen - 1) / G.klen;
   return true;
 }
+// half workgroups (kk_mk_F_mh) over an nx x ny x nz range: every tile in segments of W lanes (16 or 32: no lane of a wave is left over), THY * 64 / W rows,
+// so a tile owns (W - 2) x (4 * 64 / W - 2) cells; kchunks: VDN_FUSED_KCHUNKS (0: god_chunks_slots over the 512 slots of two workgroups per CU)
+GOD_FN GodGrid god_grid_half(int nx, int ny, int nz, int W, int kchunks) {
+  const GodSeg S = god_seg(W, THY);
+  GodGrid G; G.segw = W; G.full = 0; G.g[0] = (nx + S.ownx - 1) / S.ownx; G.g[1] = (ny + S.owny - 1) / S.owny;
+  const int chunks = kchunks ? kchunks : god_chunks_slots(G.g[0] * G.g[1], nz, 512);
+  G.klen = (nz + chunks - 1) / chunks; if (G.klen < 1) G.klen = 1;
+  G.g[2] = (nz + G.klen - 1) / G.klen;
+  return G;
+}
+// what VDN_GOD_NARROW = v says about the half form (the list of vdn_switches.h keeps its length, so the entry carries it): on for the default 1 (boxes
+// whose face range is at least 128 wide in x and y, 16-lane segments) and for 16 / 32 (segments of that many lanes, boxes of any width: the tests);
+// 0, 2 and anything else: off.  Whether the remainder column runs in narrow segments is v != 0, as before.
+struct GodHalf { bool on; int min, W; };
+GOD_FN GodHalf god_half_switch(int v) { return GodHalf{ v == 1 || v == 16 || v == 32, v == 1 ? 128 : 1, v == 32 ? 32 : 16 }; }
+// the half form pays on wide boxes only (on, min: god_half_switch; min: the least width of the face range in x and y)
+GOD_FN bool god_half_fits(int nx, int ny, bool on, int min) { return on && nx >= min && ny >= min; }
 // a box of a batched launch: the boxes of a level fill the device together, so a box is cut along k only when it is tall; segments of the width that
 // takes the fewest workgroups (segs: VDN_GOD_SEGW; 0: full-width tiles for every box)
 GOD_FN GodGrid god_grid_small(int nx, int ny, int nz, bool segs) {
@@ -168,10 +198,12 @@ GOD_FN bool god_use_batched(int nboxes, long cells, bool force) {
 
 // ---- launch forms -------------------------------------------------------------------------------------------------------------------------------
 // the template arguments of a launch: bc: boundary code; inl: an inflow face (the ghost-value reads); upd: the update rides along (mkflux); pw2: every dx a
-// power of two, divisions by dx as multiplications; sp: the compiled-in flags or SP_RT; nar: narrow segments (batched); cols: the column grid (_mc)
-struct GodForm { bool bc, inl, upd, pw2; int sp; bool nar, cols; };
-#define GOD_FORM(bc, inl, upd, pw2, sp, nar, cols) (GodForm{ (bc) != 0, (inl) != 0, (upd) != 0, (pw2) != 0, (sp), (nar) != 0, (cols) != 0 })
-GOD_FN bool operator==(const GodForm &a, const GodForm &b) { return a.bc == b.bc && a.inl == b.inl && a.upd == b.upd && a.pw2 == b.pw2 && a.sp == b.sp && a.nar == b.nar && a.cols == b.cols; }
+// power of two, divisions by dx as multiplications; sp: the compiled-in flags or SP_RT; nar: narrow segments (batched); cols: the column grid (_mc);
+// half: half workgroups (_mh)
+struct GodForm { bool bc, inl, upd, pw2; int sp; bool nar, cols, half; };
+#define GOD_FORM(bc, inl, upd, pw2, sp, nar, cols) (GodForm{ (bc) != 0, (inl) != 0, (upd) != 0, (pw2) != 0, (sp), (nar) != 0, (cols) != 0, false })
+#define GOD_FORM_HALF(bc, inl, upd, pw2, sp, nar, cols) (GodForm{ (bc) != 0, (inl) != 0, (upd) != 0, (pw2) != 0, (sp), (nar) != 0, (cols) != 0, true })
+GOD_FN bool operator==(const GodForm &a, const GodForm &b) { return a.bc == b.bc && a.inl == b.inl && a.upd == b.upd && a.pw2 == b.pw2 && a.sp == b.sp && a.nar == b.nar && a.cols == b.cols && a.half == b.half; }
 // The update-carrying power-of-two marches of a one-box level (what a step on 2^n cells runs) with the launch's flags compiled in: the combinations
 // that occur -- a conservative or a convective scalar with the force of the call, a velocity component with the forcing term formed in place, each
 // with and without use_minion; anything else takes the run-time form.
@@ -184,12 +216,14 @@ GOD_FN int god_mk_sp(bool cons, bool minion, int fmode) {
 //   * sp is compiled in only where pw2 is, and in kk_mk_F_m / _mc only with the update; the update forms with run-time flags stay unpeeled (peeled, the
 //     inflow one needs scratch -- profiles/godunov_phases_ab.txt);
 //   * the column grid exists for launches with boundary code only, so a box without a physical face keeps full tiles;
+//   * the half workgroups exist where the column grid does (launches with boundary code and the update, sp compiled in or SP_RT) and take its place;
 //   * the batched mkflux march has no bc = 0 form (its workgroups choose the lean body themselves: god_touch), the batched marches no sp and no update.
 #define GOD_MK_SP_FORMS(X, bc, cols) X(bc, 0, 1, 1, 0, 0, cols) X(bc, 0, 1, 1, SP_CONS, 0, cols) X(bc, 0, 1, 1, SP_MINION, 0, cols) X(bc, 0, 1, 1, SP_CONS | SP_MINION, 0, cols) \
   X(bc, 0, 1, 1, SP_FMODE1, 0, cols) X(bc, 0, 1, 1, SP_FMODE1 | SP_MINION, 0, cols) X(bc, 0, 1, 1, SP_RT, 0, cols)
 #define GOD_MK_M_FORMS(X) GOD_MK_SP_FORMS(X, 0, 0) GOD_MK_SP_FORMS(X, 1, 0) X(0, 0, 1, 0, SP_RT, 0, 0) X(1, 1, 1, 0, SP_RT, 0, 0) X(1, 0, 1, 0, SP_RT, 0, 0) \
   X(0, 0, 0, 1, SP_RT, 0, 0) X(0, 0, 0, 0, SP_RT, 0, 0) X(1, 1, 0, 0, SP_RT, 0, 0) X(1, 0, 0, 1, SP_RT, 0, 0) X(1, 0, 0, 0, SP_RT, 0, 0)
 #define GOD_MK_MC_FORMS(X) GOD_MK_SP_FORMS(X, 1, 1)
+#define GOD_MK_MH_FORMS(X) GOD_MK_SP_FORMS(X, 1, 0)          // (as GOD_FORM_HALF)
 #define GOD_MK_MB_FORMS_(X, nar) X(1, 1, 0, 0, SP_RT, nar, 0) X(1, 0, 0, 1, SP_RT, nar, 0) X(1, 0, 0, 0, SP_RT, nar, 0)
 #define GOD_MK_MB_FORMS(X) GOD_MK_MB_FORMS_(X, 0) GOD_MK_MB_FORMS_(X, 1)
 #define GOD_VP_SP_FORMS(X, bc, cols) X(bc, 0, 0, 1, SP_MINION, 0, cols) X(bc, 0, 0, 1, 0, 0, cols)
@@ -199,14 +233,15 @@ GOD_FN int god_mk_sp(bool cons, bool minion, int fmode) {
 #define GOD_VP_MB_FORMS(X) GOD_VP_MB_FORMS_(X, 0) GOD_VP_MB_FORMS_(X, 1)
 // The form of a launch from what the host knows.  any: a face of the box (batched: of any box) carries a rule; inflow: one of them is an inlet; p2: the
 // power-of-two spacings; cols: the column grid applies (god_grid_cols); batched: the descriptor launch, whose caller sets nar for its narrow boxes.
-// mkflux -- upd: the update rides along; sp: god_mk_sp of the component.
-GOD_FN GodForm god_mk_form(bool any, bool inflow, bool p2, bool upd, int sp, bool cols, bool batched) {
-  if (batched) return GodForm{ true, inflow, false, p2 && !inflow, SP_RT, false, false };
-  const bool bc = any, inl = any && inflow, pw2 = p2 && !inl;
-  return GodForm{ bc, inl, upd, pw2, upd && pw2 ? sp : SP_RT, false, upd && pw2 && bc && cols };
+// mkflux -- upd: the update rides along; sp: god_mk_sp of the component; half: the box is wide enough for half workgroups (god_half_fits) -- they
+// take the launches whose form admits the column grid, whether or not the box has a remainder column.
+GOD_FN GodForm god_mk_form(bool any, bool inflow, bool p2, bool upd, int sp, bool cols, bool batched, bool half = false) {
+  if (batched) return GodForm{ true, inflow, false, p2 && !inflow, SP_RT, false, false, false };
+  const bool bc = any, inl = any && inflow, pw2 = p2 && !inl, h = half && upd && pw2 && bc;
+  return GodForm{ bc, inl, upd, pw2, upd && pw2 ? sp : SP_RT, false, upd && pw2 && bc && cols && !h, h };
 }
 // velpred -- minion: use_minion, the one flag its marches compile in
 GOD_FN GodForm god_vp_form(bool any, bool inflow, bool p2, bool minion, bool cols, bool batched) {
   const bool bc = any, inl = any && inflow, pw2 = p2 && !inl;
-  return GodForm{ bc, inl, false, pw2, pw2 && !batched ? (minion ? SP_MINION : 0) : SP_RT, false, pw2 && bc && cols && !batched };
+  return GodForm{ bc, inl, false, pw2, pw2 && !batched ? (minion ? SP_MINION : 0) : SP_RT, false, pw2 && bc && cols && !batched, false };
 }

@@ -235,6 +235,9 @@ extern "C" int vdn_last_tail_form(int which) { return which == 0 ? cc_last_tail_
 // cell per lane (kk_slopes_my), 2 the pair form (kk_slopes_pr)
 int slopes_last_form();
 extern "C" int vdn_last_slopes_form(void) { return slopes_last_form(); }
+// ... and the family of the last one-box mkflux march (tests/test_godunov_half_gpu.py): 0 kk_mk_F_m, 1 kk_mk_F_mc, 16 / 32 kk_mk_F_mh in segments of that width
+int mkflux_last_form();
+extern "C" int vdn_last_mkflux_form(void) { return mkflux_last_form(); }
 #endif
 extern "C" const char *vdn_debug_switches(void) {
   static std::string out;

@@ -76,7 +76,7 @@
   X(ndm_neg, "VDN_NDM_NEG", SET, false, "1: the composite nodal solve copies -res into the correction's right-hand side instead of loading it directly") \
   X(fb_faces, "VDN_FB_FACES", ON, true, "0: the ghost exchanges of the composite cell-centred solve fill edges and corners too") \
   X(mlcc_rho, "VDN_MLCC_RHO", ON, true, "0: the composite MAC solve reads stored face coefficients on its finest level too") \
-  X(god_narrow, "VDN_GOD_NARROW", ON, true, "0: the remainder tile column of the fused mkflux + update march in full 64-lane tiles instead of narrow segments (kk_mk_F_mn)") \
+  X(god_narrow, "VDN_GOD_NARROW", INT, 1, "the tiling of the fused mkflux + update march of a one-box level.  0: full 64-lane tiles everywhere; 2: the remainder tile column in narrow segments (kk_mk_F_mc), no half workgroups; default 1: that, and two 256-thread workgroups per compute unit in 16-lane segments (kk_mk_F_mh) on face ranges at least 128 wide; 16 / 32: the half workgroups in segments of that many lanes on boxes of any width") \
   X(keep_sets, "VDN_KEEP_SETS", ON, true, "0: the descriptor arrays of the inter-level operators and composite solves are rebuilt and uploaded at every call") \
   X(kept_bound, "VDN_KEPT_BOUND", INT, 0, "n > 0: the kept descriptor tables hold at most n entries each (default 4096 / 64 / 512): the eviction paths in a test") \
   X(mlcc_glue, "VDN_MLCC_GLUE", ON, true, "0: the level-0 correction of the composite MAC solve stored and added in separate passes") \
