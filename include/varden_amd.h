@@ -464,6 +464,62 @@ int  vdn_pdf2(int nlev, vdn_layout *mla, vdn_multifab *const *u, vdn_multifab *c
               int field1, int comp1, int nbins1, double lo1, double hi1, int field2, int comp2, int nbins2, double lo2, double hi2,
               long long *cells_host /*[VDN_MAXLEV][n1+2][n2+2]*/, double *volume_host /*[n1+2][n2+2]*/, long long *nan_cells);
 
+/* ---- where a field takes a value: the isosurface q = iso of a hierarchy's field, extracted on the device (csrc/iso.hip, csrc/iso_cell.h) ------
+ * No reference counterpart; dm = 3 only.  The library is built -ffp-contract=off, so every expression below has the order written.
+ *   cells     the composite grid exactly as vdn_diagnostics defines it: the valid cells of level l that no box of level l + 1 covers.  Each such cell is cut on its own;
+ *             the pieces tile the domain without gap or overlap.
+ *   field     mf[nlev], comp, bccomp as vdn_sample_points takes them: any cell-centred multifab with at least one ghost layer, which the CALLER has filled (same level,
+ *             physical boundary, coarse-fine).  The call fills nothing and writes none of its inputs.
+ *   nodes     node (i, j, k) of level l is the low corner of cell (i, j, k), at (i dx, j dy, k dz): one multiplication per direction.  Its value comes from the eight
+ *             cells (i-1..i, j-1..j, k-1..k), read from the fab of the box that owns the cell being cut, as a pairwise mean m = 0.5 a + 0.5 b along x, then along y,
+ *             then along z.  The face-value rule of vdn_sample_points: where the node lies on a domain face whose adv boundary type of component bccomp is EXT_DIR, the
+ *             ghost cell holds the value ON the face; along that direction m is the ghost value alone.  A cell forms its eight nodes itself; the same expression on the
+ *             same values gives the same bits in every cell of a level that shares the node (a same-level ghost cell holds its neighbour's bits).
+ *   tetrahedra   six Kuhn tetrahedra around the diagonal (0,0,0)-(1,1,1): for the axis orders (x,y,z), (x,z,y), (y,x,z), (y,z,x), (z,x,y), (z,y,x), in this order,
+ *             v0 = corner (0,0,0), v1 = v0 + e_a, v2 = v1 + e_b, v3 = (1,1,1).  The triangulation matches across the faces of neighbouring cells of a level: the
+ *             surface is watertight within a level.
+ *   above     a vertex is above when q > iso (strict).  An edge is crossed between a not-above end A and an above end B, so q_B - q_A > 0 always:
+ *             t = (iso - q_A) / (q_B - q_A), p_d = x_A,d + t (x_B,d - x_A,d), always from A to B: two tetrahedra that share the edge form the same bits.
+ *   triangles one or three vertices above: one triangle; two: two; none or four: none.  (p1 - p0) x (p2 - p0) points towards the not-above side.  csrc/iso_cell.h holds the
+ *             case table, once, and states the vertex order of every case.
+ *   sums      per triangle the area 0.5 |cross|, cross = (p1 - p0) x (p2 - p0), |c| = sqrt((c_x c_x + c_y c_y) + c_z c_z), and area_vec 0.5 cross (a closed surface sums
+ *             to zero).  The volume above under the linear interpolant, V_tet = ((dx dy) dz) / 6: one vertex above ((V_tet (1 - t1)) (1 - t2)) (1 - t3); three above
+ *             V_tet - ((V_tet t1) t2) t3; four V_tet; two: the wedge as three tetrahedra, each |det| / 6 -- csrc/iso_cell.h writes the association.  A cell's sums start
+ *             from +0 and take tetrahedron 0 .. 5, triangle 0 .. 1 in order.
+ *   non-finite   a cell with a non-finite node value emits nothing, adds nothing and is counted in nonfinite_cells.
+ *   order     level, then global box number, then cell with i fastest, then j, then k; inside a cell tetrahedron 0 .. 5, then triangle 0 .. 1: a function of the box lists
+ *             and the field alone.
+ *   levels    the two sides of a coarse-fine face see different node values: the surface has cracks there.  Area and volume still tile, because the cells do.
+ * vdn_iso: ntri, cut_cells (the cells that emit a triangle), their parts per level, nonfinite_cells; area and its parts per level, area_vec, volume_above; volume: the
+ * volume of the cells that were cut up -- all composite cells but the non-finite ones --, the sum over the levels, ascending, of their number times dx dy dz of the level.
+ * The counts and sums are always returned.  Triangles ([ntri][vertex][direction]) and their levels are written only when tri_host is given and ntri <= max_tri; written
+ * is then ntri, else 0 and the buffers are untouched: a caller sizes a second call from the first.  lev_host may be NULL.
+ * Collective; every rank receives the full result.  Deterministic: counts are integers, sums run in a fixed order (thread map, trees, then slab by slab in output order),
+ * positions come from integer scans, no atomic takes part: two calls give the same bits and the bits do not depend on the number of ranks.  Every temporary lives in the
+ * arena for the duration of the call.
+ * Refuses (non-zero, vdn_last_error, nothing left allocated, a following call unaffected): what vdn_sample_points refuses -- an uninitialised library; NULL mla, mf, dx,
+ * bct, out; nlev outside 1 .. 4 or not the layout's; a bc tower of another layout; a dx that is not positive and finite; a level's mf NULL, of another layout or level,
+ * nodal, without component comp or without a ghost layer; bccomp outside the tower --, and: a non-finite iso; dm = 2; a refinement ratio other than 2; max_tri < 0;
+ * max_tri > 0 with a NULL tri_host.
+ * vdn_isosurface_write: binary PLY, little endian -- "ply", "format binary_little_endian 1.0", "comment VDN_ISO 1 iso <%.17g> time <%.17g>", "element vertex <3 ntri>" with
+ * "property double x / y / z", "element face <ntri>" with "property list uchar int vertex_indices" and "property uchar level", "end_header"; then the vertices and the
+ * faces (3, three indices, the level): a triangle soup, no vertex merged.  Rank 0 writes; the same arguments give the same bytes.  A host function: it needs no
+ * vdn_init.  Refuses a NULL path, ntri < 0 or 3 ntri beyond 32 bits, triangles without tri_host and lev_host, a file it cannot write. */
+typedef struct vdn_iso {
+  long long ntri, ntri_lev[4], cut_cells, cut_cells_lev[4], nonfinite_cells, written;
+  double area, area_lev[4], area_vec[3], volume_above, volume;
+} vdn_iso;
+size_t vdn_iso_sizeof(void);
+int  vdn_isosurface(int nlev, vdn_layout *mla, vdn_multifab *const *mf, int comp, int bccomp, const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct, double iso,
+                    long long max_tri, double *tri_host /*[max_tri][3][3] or NULL*/, unsigned char *lev_host /*[max_tri] or NULL*/, vdn_iso *out);
+int  vdn_isosurface_write(const char *path, long long ntri, const double *tri_host, const unsigned char *lev_host, double iso, double time);
+/* vdn_isosurface with the form of its second pass chosen by the caller -- 0: every cell forms its nodes and counts again, 1: the first pass stores a count per cell and the
+ * second reads it, loading the neighbourhood of cut cells alone -- and ms[0], ms[1]: the device time in milliseconds of the launches of pass 1 and pass 2 (events
+ * around them; 0 for a pass that did not run).  The same refusals, and a form other than 0 or 1 or a NULL ms; the same bits from both forms.  It exists for the
+ * measurement that chose the form vdn_isosurface runs (tools/iso_probe.py). */
+int  vdn_isosurface_timed(int nlev, vdn_layout *mla, vdn_multifab *const *mf, int comp, int bccomp, const double *dx /*[nlev][3]*/, const vdn_bc_tower *bct, double iso,
+                          long long max_tri, double *tri_host, unsigned char *lev_host, vdn_iso *out, int form, double *ms /*[2]*/);
+
 /* ---- values at points and Lagrangian tracer particles (csrc/particles.hip, csrc/particle_plan.h).  No reference counterpart -------------
  * Positions are physical, measured from the domain's low corner (prob_lo = 0); level l has spacing dx[l][d]; dm = 2 uses x and y (z is stored as 0).  The
  * domain's extent is len_d = ncells_d(level 0) * dx[0][d]; a point is inside when 0 <= x_d <= len_d in every direction.

@@ -1,11 +1,13 @@
-"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D] [--files plane|copy] [--diag-int N] [--particles NX,NY,NZ] [--particle-int N] [--prof-int N] [--prof-axis A] [--pdf-int N --pdf-field F --pdf-range LO,HI [--pdf-comp C --pdf-nbins B]]: the reference executable's command line (src/main.f90
+"""python -m varden_amd <inputs file> [--steps N] [--outdir DIR] [--device D] [--files plane|copy] [--diag-int N] [--particles NX,NY,NZ] [--particle-int N] [--prof-int N] [--prof-axis A] [--pdf-int N --pdf-field F --pdf-range LO,HI [--pdf-comp C --pdf-nbins B]] [--iso-int N --iso-field F --iso-comp C --iso-value V]: the reference executable's command line (src/main.f90
 reads the inputs file named by the first argument and calls varden()).  Plot and checkpoint files go under --outdir; a 2-D hierarchy writes the 2-D run's own
 dm = 2 files (--files copy: those of the 3-D copy it runs as).  --diag-int N overrides the namelist's diag_int: a line of run diagnostics (advance.diagnostics) for the
 starting state and after every N-th step, in <outdir>/<diag_file_name>.  --particles NX,NY,NZ and --particle-int N set the namelist's particle_lattice and
 particle_int: tracer particles on an even lattice, moved by every step, written every N steps to <outdir>/<particle_base_name>NNNNN.  --prof-int N and --prof-axis A (numbered from 1; -1: the last
 direction) override prof_int and prof_axis: the plane-averaged profiles (advance.profiles) of the starting state and after every N-th step, one file
 <outdir>/<prof_base_name>NNNNN each.  --pdf-int N, --pdf-field F, --pdf-range LO,HI, --pdf-comp C (numbered from 1) and --pdf-nbins B override pdf_int, pdf_field, pdf_lo and
-pdf_hi, pdf_comp and pdf_nbins: the distribution by value (advance.pdf) of the starting state and after every N-th step, one file <outdir>/<pdf_base_name>NNNNN each."""
+pdf_hi, pdf_comp and pdf_nbins: the distribution by value (advance.pdf) of the starting state and after every N-th step, one file <outdir>/<pdf_base_name>NNNNN each.  --iso-int N, --iso-field F, --iso-comp C (numbered from 1) and --iso-value V override
+iso_int, iso_field, iso_comp and iso_value: the isosurface (advance.isosurface) of the starting state and after every N-th step, one binary PLY file
+<outdir>/<iso_base_name>NNNNN.ply each and a line of its triangle count, area and volume above in <outdir>/<iso_base_name>.dat."""
 import argparse
 import os
 import time
@@ -31,6 +33,10 @@ def main():
     ap.add_argument("--pdf-range", default=None, help="override pdf_lo and pdf_hi: LO,HI, the range the bins divide")
     ap.add_argument("--pdf-comp", type=int, default=None, help="override pdf_comp: the component of a scalar or velocity field, numbered from 1")
     ap.add_argument("--pdf-nbins", type=int, default=None, help="override pdf_nbins: the number of bins (1 .. 256)")
+    ap.add_argument("--iso-int", type=int, default=None, help="override iso_int: an isosurface file (binary PLY) and a line of its area and volume every N steps (0: none)")
+    ap.add_argument("--iso-field", default=None, choices=("scalar", "velocity"), help="override iso_field: the field whose surface is extracted")
+    ap.add_argument("--iso-comp", type=int, default=None, help="override iso_comp: the component of the field, numbered from 1")
+    ap.add_argument("--iso-value", type=float, default=None, help="override iso_value: the value the surface takes")
     a = ap.parse_args()
     pdf_range = None if a.pdf_range is None else tuple(float(v) for v in a.pdf_range.split(","))
     if pdf_range is not None and len(pdf_range) != 2:
@@ -45,7 +51,8 @@ def main():
     t0 = time.time()
     nl, G = inputs.run(open(a.inputs_file).read(), a.steps, report, device=a.device, outdir=a.outdir, files=a.files, diag_int=a.diag_int, particles=lattice,
                         particle_int=a.particle_int, prof_int=a.prof_int, prof_axis=a.prof_axis, pdf_int=a.pdf_int,
-                        pdf_field=a.pdf_field, pdf_comp=a.pdf_comp, pdf_range=pdf_range, pdf_nbins=a.pdf_nbins)
+                        pdf_field=a.pdf_field, pdf_comp=a.pdf_comp, pdf_range=pdf_range, pdf_nbins=a.pdf_nbins,
+                        iso_int=a.iso_int, iso_field=a.iso_field, iso_comp=a.iso_comp, iso_value=a.iso_value)
     print("Total Run time (s) = %.3f" % (time.time() - t0))
     for f in G.files_written:
         print("wrote", f)

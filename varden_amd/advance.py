@@ -9,6 +9,7 @@
 Multifab arguments are lists with one :class:`MultiFab` per level, as in the Fortran (``sold(:)``).
 """
 import ctypes as C
+import os
 
 from . import capi
 from .boxlib import handle_array
@@ -605,6 +606,70 @@ def _dx3(dx):
     levs = dx if hasattr(dx[0], "__len__") else [dx]
     flat = [float(v) for lev in levs for v in (list(lev) + [1.0] * 3)[:3]]
     return (C.c_double * len(flat))(*flat)
+
+
+# ---- isosurfaces (csrc/iso.hip, csrc/iso_cell.h; include/varden_amd.h states the definitions) ---------------------------------------------
+ISO_DAT_COLUMNS = ("ntri", "cut_cells", "area", "volume_above")      # the columns of an isosurface .dat file after step and time
+
+
+class Iso:
+    """the result of vdn_isosurface: the members of vdn_iso by name (ntri, ntri_lev, cut_cells, cut_cells_lev, nonfinite_cells, written, area, area_lev, area_vec,
+    volume_above, volume; the per-level lists cut to nlev), value (the iso value), tri (written, 3, 3) float64 -- [triangle][vertex][direction] in the output order
+    -- and level (written,) uint8; both are None when no triangles were asked for."""
+
+    def __init__(self, value, nlev, out, tri=None, level=None):
+        self.value, self.nlev, self.tri, self.level = float(value), int(nlev), tri, level
+        for name, ctype in capi.Iso._fields_:
+            v = getattr(out, name)
+            setattr(self, name, list(v)[:nlev if name.endswith("_lev") else 3] if hasattr(v, "__len__") else v)
+
+
+def isosurface(mla, mf, comp, bccomp, dx, bct, value, triangles=True):
+    """vdn_isosurface: the surface mf(comp) = value over the composite grid of the hierarchy by marching tetrahedra: an Iso.  mf: one cell-centred multifab per level
+    with at least one ghost layer that the CALLER has filled; bccomp: the bc tower component of `comp` (0 for the velocity, dm for the scalars); dm = 3 only.
+    triangles=True: the call sizes itself -- a count call first, then the triangles.  Counts are exact, sums and the triangle order are fixed: equal bits call after
+    call and on any number of ranks.  Collective."""
+    import numpy as np
+    lib, out, nlev = capi.load(), capi.Iso(), len(mf)
+    args = (nlev, mla.h, handle_array(mf), int(comp), int(bccomp), _dx3(dx), bct.h if bct is not None else None, float(value))
+    check(lib.vdn_isosurface(*args, 0, None, None, C.byref(out)))
+    if not triangles:
+        return Iso(value, nlev, out)
+    n = int(out.ntri)
+    tri, level = np.zeros((n, 3, 3)), np.zeros(n, dtype=np.uint8)
+    if n > 0:
+        check(lib.vdn_isosurface(*args, n, tri.ctypes.data_as(C.POINTER(C.c_double)), level.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(out)))
+        if out.written != n:
+            raise capi.VardenError("vdn_isosurface: %d triangles counted, %d written" % (n, out.written))
+    return Iso(value, nlev, out, tri, level)
+
+
+def write_iso(path, iso, time):
+    """vdn_isosurface_write: the triangles of an Iso as binary PLY (little endian, a triangle soup with a level per face); rank 0 writes"""
+    import numpy as np
+    if iso.tri is None:
+        raise ValueError("write_iso: the Iso carries no triangles (isosurface(..., triangles=True))")
+    tri, level = np.ascontiguousarray(iso.tri, dtype=np.float64), np.ascontiguousarray(iso.level, dtype=np.uint8)
+    check(capi.load().vdn_isosurface_write(os.fsencode(path), tri.shape[0], tri.ctypes.data_as(C.POINTER(C.c_double)), level.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                           float(iso.value), float(time)))
+
+
+def read_iso(path):
+    """a file of write_iso: a dict with iso, time, tri (ntri, 3, 3) float64 and level (ntri,) uint8"""
+    import numpy as np
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode("ascii").split("\n")
+    if head[:2] != ["ply", "format binary_little_endian 1.0"] or not head[2].startswith("comment VDN_ISO 1 iso "):
+        raise ValueError("%s: not an isosurface file" % (path,))
+    words = head[2].split()
+    nvert, ntri = int(head[3].split()[2]), int(head[7].split()[2])
+    if nvert != 3 * ntri or len(raw) != end + 24 * nvert + 14 * ntri:
+        raise ValueError("%s: %d vertices and %d faces do not fit %d bytes" % (path, nvert, ntri, len(raw)))
+    tri = np.frombuffer(raw, dtype="<f8", count=3 * nvert, offset=end).reshape(ntri, 3, 3).copy()
+    faces = np.frombuffer(raw, dtype=np.dtype([("n", "u1"), ("v", "<i4", 3), ("level", "u1")]), count=ntri, offset=end + 24 * nvert)
+    return dict(iso=float(words[4]), time=float(words[6]), tri=tri, level=faces["level"].copy(), indices=faces["v"].copy())
 
 
 def _points(x):

@@ -89,6 +89,13 @@ class PdfLayout(C.Structure):
     _fields_ = [(name, C.c_int) for name in ("nrow", "volume", "q", "s", "u", "ru", "ke")]
 
 
+class Iso(C.Structure):
+    """mirror of ``vdn_iso``: what vdn_isosurface reports (triangle and cell counts, area, area vector, volumes); entries beyond nlev are 0"""
+    _fields_ = [("ntri", C.c_longlong), ("ntri_lev", C.c_longlong * 4), ("cut_cells", C.c_longlong), ("cut_cells_lev", C.c_longlong * 4),
+                ("nonfinite_cells", C.c_longlong), ("written", C.c_longlong),
+                ("area", C.c_double), ("area_lev", C.c_double * 4), ("area_vec", C.c_double * 3), ("volume_above", C.c_double), ("volume", C.c_double)]
+
+
 # every symbol include/varden_amd.h declares: (restype, argtypes)
 _VP = C.c_void_p
 _PI = C.POINTER(C.c_int)
@@ -176,6 +183,10 @@ SIGNATURES = {
     "vdn_pdf": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _PD, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "vdn_pdf2": (C.c_int, [C.c_int, _VP, _PVP, _PVP, _PD, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                            C.POINTER(C.c_longlong), _PD, C.POINTER(C.c_longlong)]),
+    "vdn_iso_sizeof": (C.c_size_t, []),
+    "vdn_isosurface": (C.c_int, [C.c_int, _VP, _PVP, C.c_int, C.c_int, _PD, _VP, C.c_double, C.c_longlong, _PD, C.POINTER(C.c_ubyte), C.POINTER(Iso)]),
+    "vdn_isosurface_timed": (C.c_int, [C.c_int, _VP, _PVP, C.c_int, C.c_int, _PD, _VP, C.c_double, C.c_longlong, _PD, C.POINTER(C.c_ubyte), C.POINTER(Iso), C.c_int, _PD]),
+    "vdn_isosurface_write": (C.c_int, [C.c_char_p, C.c_longlong, _PD, C.POINTER(C.c_ubyte), C.c_double, C.c_double]),
     "vdn_sample_points": (C.c_int, [C.c_int, _VP, _PVP, C.c_int, C.c_int, C.c_int, _PD, _VP, C.c_long, _PD, _PD, _PI]),
     "vdn_particles_create": (C.c_int, [C.c_long, _PD, _PVP]),
     "vdn_particles_destroy": (C.c_int, [_VP]),

@@ -85,6 +85,23 @@ def _limit_dt(sim, dt, first=False):
     return dt
 
 
+ISO_FIELDS = ("scalar", "velocity")
+
+
+def _state_isosurface(sim, field, comp, value, triangles):
+    """advance.isosurface of a driver's state after its ghost fill: 'scalar' reads sold with bc component dm + comp, 'velocity' uold with bc component comp"""
+    if field not in ISO_FIELDS:
+        raise ValueError("isosurface field %r: one of %s (other fields: advance.isosurface with a multifab of your own)" % (field, ", ".join(ISO_FIELDS)))
+    if sim.dm != 3:
+        raise ValueError("isosurface: dm = %d: surfaces are extracted from 3-D fields only" % (sim.dm,))
+    comp, ncomp = int(comp), sim.nscal if field == "scalar" else sim.dm
+    if not 0 <= comp < ncomp:
+        raise ValueError("isosurface: comp = %d is outside 0 .. %d" % (comp, ncomp - 1))
+    sim.fill_state_ghosts()
+    mf, bccomp = (sim.sold, sim.dm + comp) if field == "scalar" else (sim.uold, comp)
+    return adv.isosurface(sim.mla, mf, comp, bccomp, sim.dx, sim.bct, value, triangles=triangles)
+
+
 class Varden:
     def __init__(self, n, phys_bc, params=None, prob_type=1, grav=-9.8, prob_hi=(1.0, 1.0, 1.0), init_shrink=1.0,
                  init_iter=4, do_initial_projection=1, u0=None, s0=None, device=0, decomp=(1, 1, 1), rank=0, nranks=1,
@@ -225,6 +242,12 @@ class Varden:
         if adv.PDF_FIELDS["vorticity"] in (adv._pdf_field(field1), adv._pdf_field(field2)):
             self.fill_state_ghosts()
         return adv.pdf2(self.mla, self.uold, self.sold, self.dx, self.bct, field1, comp1, lo1, hi1, nbins1, field2, comp2, lo2, hi2, nbins2)
+
+    def isosurface(self, field="scalar", comp=0, value=0.0, triangles=True):
+        """advance.isosurface of the current state: the surface field(comp) = value -- 'scalar' reads sold (bc component dm + comp), 'velocity' uold (bc component
+        comp); comp 0-based -- with its area, area vector, the volume above and, with triangles=True, the triangles.  The node values read one ghost layer, so the
+        ghost cells of the state are filled first, as diagnostics() does.  dm = 3 only.  Other fields: advance.isosurface with a multifab the caller made and filled."""
+        return _state_isosurface(self, field, comp, value, triangles)
 
     def profiles(self, axis=None):
         """advance.profiles of the current state (uold, sold) along `axis` (0-based; default: the last direction, dm - 1): the plane sums per bin, the exact extrema
@@ -610,6 +633,13 @@ class VardenAMR:
         if adv.PDF_FIELDS["vorticity"] in (adv._pdf_field(field1), adv._pdf_field(field2)):
             self.fill_state_ghosts()
         return adv.pdf2(self.mla, self.uold, self.sold, self.dx, self.bct, field1, comp1, lo1, hi1, nbins1, field2, comp2, lo2, hi2, nbins2)
+
+    def isosurface(self, field="scalar", comp=0, value=0.0, triangles=True):
+        """advance.isosurface of the current state over the composite grid: the surface field(comp) = value -- 'scalar' reads sold (bc component dm + comp), 'velocity'
+        uold (bc component comp); comp 0-based -- with its area, area vector, the volume above and, with triangles=True, the triangles in (level, box, cell) order.
+        The ghost cells of the state are filled first, as diagnostics() does.  The surface has cracks along coarse-fine faces; area and volume tile all the same.
+        An extruded 2-D copy reports the 3-D COPY's surface."""
+        return _state_isosurface(self, field, comp, value, triangles)
 
     def profiles(self, axis=None):
         """advance.profiles of the current state (uold, sold) over the composite grid along `axis` (0-based; default: the last direction, dm - 1); the bins are the planes

@@ -72,6 +72,12 @@ module varden_amd
      integer(c_int) :: nrow, volume, s, ss, u, ru, ruu, sua, s_min, s_max, u_min, u_max
   end type vdn_profile_layout
 
+  ! what vdn_isosurface reports (include/varden_amd.h: vdn_iso): triangle and cut-cell counts, their parts per level, area, area vector, volumes
+  type, bind(C), public :: vdn_iso
+     integer(c_long_long) :: ntri, ntri_lev(4), cut_cells, cut_cells_lev(4), nonfinite_cells, written
+     real(c_double) :: area, area_lev(4), area_vec(3), volume_above, volume
+  end type vdn_iso
+
   type, public :: ml_layout
      type(c_ptr) :: h = c_null_ptr
      integer :: nlevel = 0, dim = 3
@@ -104,6 +110,7 @@ module varden_amd
   public :: make_new_grids_by, tag_boxes_by, make_tag_criterion
   public :: diagnostics
   public :: profiles_layout, profiles_nbins, profiles
+  public :: isosurface, isosurface_write
   public :: sample_points, particles_create, particles_destroy, particles_count, particles_get, particles_advance, particles_sample, particles_write, particles_read
   public :: fabio_ml_multifab_write_d, fabio_ml_multifab_info, fabio_ml_multifab_boxes, fabio_ml_multifab_read_d, checkpoint_write, checkpoint_info
   public :: fabio_ml_multifab_write_plane_d, fabio_ml_multifab_read_plane_d, checkpoint_write_plane, make_vorticity_plane
@@ -366,6 +373,27 @@ module varden_amd
        real(c_double), intent(in) :: dx(*)
        real(c_double), intent(out) :: out_host(*)
        integer(c_long_long), intent(out) :: cells_host(*)
+     end function
+     ! isosurfaces (include/varden_amd.h; csrc/iso.hip): tri_host and lev_host are addresses, c_null_ptr for "none"
+     integer(c_size_t) function vdn_iso_sizeof() bind(C, name="vdn_iso_sizeof")
+       import :: c_size_t
+     end function
+     integer(c_int) function vdn_isosurface(nlev, mla, mf, comp, bccomp, dx, bct, iso, max_tri, tri_host, lev_host, out) bind(C, name="vdn_isosurface")
+       import :: c_int, c_long_long, c_ptr, c_double, vdn_iso
+       integer(c_int), value :: nlev, comp, bccomp
+       type(c_ptr), value :: mla, bct, tri_host, lev_host
+       type(c_ptr), intent(in) :: mf(*)
+       real(c_double), intent(in) :: dx(*)
+       real(c_double), value :: iso
+       integer(c_long_long), value :: max_tri
+       type(vdn_iso), intent(out) :: out
+     end function
+     integer(c_int) function vdn_isosurface_write(path, ntri, tri_host, lev_host, iso, time) bind(C, name="vdn_isosurface_write")
+       import :: c_int, c_long_long, c_ptr, c_double, c_char
+       character(kind=c_char), intent(in) :: path(*)
+       integer(c_long_long), value :: ntri
+       type(c_ptr), value :: tri_host, lev_host
+       real(c_double), value :: iso, time
      end function
      ! values at points and tracer particles (include/varden_amd.h; csrc/particles.hip)
      integer(c_int) function vdn_sample_points(nlev, mla, mf, comp, nc, bccomp, dx, bct, n, x_host, val_host, lev_host) bind(C, name="vdn_sample_points")
@@ -1241,6 +1269,46 @@ contains
                                the_bc_tower%h, int(size(x, 2), c_long), x, val, levc), 'sample_points')
     lev = levc
   end subroutine sample_points
+
+  ! the surface mf(comp) = value over the composite grid of levels 1 .. size(mf) (see vdn_isosurface): counts, area, area vector and volumes in iso; with tri and
+  ! lev also the triangles, tri(direction, vertex, triangle) in output order, and their levels (numbered from 0, as the library numbers them) -- the call sizes
+  ! itself: a count call first, then the triangles.  comp and bccomp are numbered from 1; the CALLER has filled the ghost cells of mf; dm = 3 only
+  subroutine isosurface(mla, mf, comp, bccomp, dx, the_bc_tower, value, iso, tri, lev)
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: mf(:)
+    integer        , intent(in   ) :: comp, bccomp
+    real(dp_t)     , intent(in   ) :: dx(:,:), value
+    type(bc_tower) , intent(in   ) :: the_bc_tower
+    type(vdn_iso)  , intent(  out) :: iso
+    real(dp_t)        , allocatable, target, intent(out), optional :: tri(:,:,:)
+    integer(c_int8_t), allocatable, target, intent(out), optional :: lev(:)
+    integer(c_long_long) :: n
+    if (vdn_iso_sizeof() /= c_sizeof(iso)) error stop 'isosurface: vdn_iso differs between the library and this module'
+    if (present(tri) .neqv. present(lev)) error stop 'isosurface: tri and lev come together'
+    call chk(vdn_isosurface(int(size(mf), c_int), mla%h, handles(mf), int(comp - 1, c_int), int(bccomp - 1, c_int), dx_levels(dx, size(mf)), the_bc_tower%h, &
+                            value, 0_c_long_long, c_null_ptr, c_null_ptr, iso), 'isosurface')
+    if (.not. present(tri)) return
+    n = iso%ntri
+    allocate(tri(3, 3, n), lev(n))
+    if (n == 0) return
+    call chk(vdn_isosurface(int(size(mf), c_int), mla%h, handles(mf), int(comp - 1, c_int), int(bccomp - 1, c_int), dx_levels(dx, size(mf)), the_bc_tower%h, &
+                            value, n, c_loc(tri), c_loc(lev), iso), 'isosurface')
+    if (iso%written /= n) error stop 'isosurface: the triangles counted were not written'
+  end subroutine isosurface
+
+  ! the triangles of isosurface as binary PLY (see vdn_isosurface_write); rank 0 writes
+  subroutine isosurface_write(path, tri, lev, value, time)
+    character(len=*) , intent(in) :: path
+    real(dp_t)       , intent(in), target, contiguous :: tri(:,:,:)
+    integer(c_int8_t), intent(in), target, contiguous :: lev(:)
+    real(dp_t)       , intent(in) :: value, time
+    if (size(tri, 1) /= 3 .or. size(tri, 2) /= 3 .or. size(tri, 3) /= size(lev)) error stop 'isosurface_write: tri(3, 3, ntri) and lev(ntri) expected'
+    if (size(lev) == 0) then
+       call chk(vdn_isosurface_write(trim(path) // c_null_char, 0_c_long_long, c_null_ptr, c_null_ptr, value, time), 'isosurface_write')
+    else
+       call chk(vdn_isosurface_write(trim(path) // c_null_char, int(size(lev), c_long_long), c_loc(tri), c_loc(lev), value, time), 'isosurface_write')
+    end if
+  end subroutine isosurface_write
 
   subroutine particles_create(p, x)
     type(particles), intent(  out) :: p

@@ -916,6 +916,38 @@ contains
   end subroutine advance_timestep
 end module advance_module
 
+! isosurfaces of a hierarchy's field on the reference's container types (no reference counterpart; include/varden_amd.h: vdn_isosurface):
+! isosurface(mla, mf, comp, bccomp, dx, the_bc_tower, value, iso[, tri, lev]) and isosurface_write(path, tri, lev, value, time) as in varden_amd
+module isosurface_module
+  use iso_c_binding, only: c_int8_t
+  use multifab_module
+  use ml_layout_module
+  use define_bc_module
+  use varden_amd, only: vdn_iso, isosurface_write, vamd_isosurface => isosurface, vamd_multifab => multifab
+  implicit none
+contains
+  subroutine isosurface(mla, mf, comp, bccomp, dx, the_bc_tower, value, iso, tri, lev)
+    type(ml_layout), intent(in   ) :: mla
+    type(multifab) , intent(in   ) :: mf(:)
+    integer        , intent(in   ) :: comp, bccomp
+    real(dp_t)     , intent(in   ) :: dx(:,:), value
+    type(bc_tower) , intent(in   ) :: the_bc_tower
+    type(vdn_iso)  , intent(  out) :: iso
+    real(dp_t)       , allocatable, target, intent(out), optional :: tri(:,:,:)
+    integer(c_int8_t), allocatable, target, intent(out), optional :: lev(:)
+    type(vamd_multifab) :: v(size(mf))
+    integer :: n
+    do n = 1, size(mf)
+       v(n) = mf(n)%v
+    end do
+    if (present(tri) .and. present(lev)) then
+       call vamd_isosurface(mla%v, v, comp, bccomp, dx, the_bc_tower%v, value, iso, tri, lev)
+    else
+       call vamd_isosurface(mla%v, v, comp, bccomp, dx, the_bc_tower%v, value, iso)
+    end if
+  end subroutine isosurface
+end module isosurface_module
+
 ! the reference's generated probin_module (src/probin.template + src/_parameters through FBoxLib's write_probin.py): EVERY entry of src/_parameters with its default,
 ! the &PROBIN namelist, probin_init (the inputs file: $PROBIN, else the first command-line argument, else ./inputs_varden -- probin.template:62-98; the command-line
 ! overrides `--name value` of the generated file are not parsed) and probin_close.  The values reach the library with probin_to_library (vdn_params).

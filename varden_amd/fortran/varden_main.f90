@@ -58,12 +58,21 @@ program varden_main
   integer :: prof_int = 0
   integer :: prof_axis = -1
   character(len=128) :: prof_base_name = 'prof'
+  ! ---- isosurfaces (the project's own keys too): iso_int > 0 writes, for the state the run starts from and after every iso_int-th step, the surface
+  ! iso_field (scalar | velocity) / iso_comp (numbered from 1) = iso_value as binary PLY in <iso_base_name>NNNNN.ply (varden_amd_mod: isosurface, isosurface_write) and a
+  ! line -- step, time, ntri, cut_cells, area, volume_above -- in <iso_base_name>.dat: the files varden_amd/inputs.py writes, byte for byte.  0 (default): no call, no file
+  integer :: iso_int = 0
+  character(len=16) :: iso_field = 'scalar'
+  integer :: iso_comp = 1
+  real(dp_t) :: iso_value = 0.0_dp_t
+  character(len=128) :: iso_base_name = 'iso'
   namelist /probin/ dim_in, nscal, prob_type, boussinesq, max_step, max_levs, max_grid_size, regrid_int, amr_buf_width, n_cellx, n_celly, n_cellz, &
        init_iter, do_initial_projection, diffusion_type, slope_order, use_minion, stencil_order, verbose, mg_verbose, plot_int, chk_int, restart, ref_ratio, &
        bcx_lo, bcx_hi, bcy_lo, bcy_hi, bcz_lo, bcz_hi, cluster_min_width, cluster_blocking_factor, grav, stop_time, prob_hi_x, prob_hi_y, prob_hi_z, &
        prob_lo_x, prob_lo_y, prob_lo_z, init_shrink, cflfac, max_dt_growth, visc_coef, diff_coef, fixed_dt, cluster_min_eff, u_bc, v_bc, w_bc, rho_bc, trac_bc, &
        plot_base_name, check_base_name, mg_bottom_solver, hg_bottom_solver, max_mg_bottom_nlevels, tag_field, tag_comp, tag_gt, tag_lt, &
-       diag_int, diag_file_name, particle_lattice, particle_int, particle_base_name, prof_int, prof_axis, prof_base_name
+       diag_int, diag_file_name, particle_lattice, particle_int, particle_base_name, prof_int, prof_axis, prof_base_name, &
+       iso_int, iso_field, iso_comp, iso_value, iso_base_name
 
   ! one hierarchy: box lists, layout, boundary tower and the four multifabs regridding carries (regrid.f90:60-75)
   type hier
@@ -213,6 +222,12 @@ program varden_main
      call write_diag_header()
      call write_diag()
   end if
+  if (iso_int > 0) then
+     if (dm /= 3) error stop 'varden_main: iso_int > 0 needs dim_in = 3: surfaces are extracted from 3-D fields only'
+     if (trim(iso_field) /= 'scalar' .and. trim(iso_field) /= 'velocity') error stop 'varden_main: iso_field: scalar or velocity'
+     call write_iso_header()
+     call write_iso()
+  end if
   if (prof_int > 0) call write_prof()
 
   ! ---- time loop (varden.f90:237-345) ----
@@ -251,6 +266,9 @@ program varden_main
      end if
      if (prof_int > 0) then
         if (mod(istep, prof_int) == 0) call write_prof()
+     end if
+     if (iso_int > 0) then
+        if (mod(istep, iso_int) == 0) call write_iso()
      end if
      if (have_tracers .and. particle_int > 0) then
         if (mod(istep, particle_int) == 0) call write_tracers()
@@ -305,6 +323,36 @@ contains
          d%s_min(1:nscal), d%s_max(1:nscal), d%u_min(1:dm), d%u_max(1:dm), d%magvel_max, d%vort_min, d%vort_max
     close(u)
   end subroutine write_diag
+
+  ! the header line of <iso_base_name>.dat (inputs.py: iso_header)
+  subroutine write_iso_header()
+    integer :: u
+    character(len=27) :: t, a, v
+    t = 'time'; a = 'area'; v = 'volume_above'
+    open(newunit=u, file=trim(iso_base_name) // '.dat', status='replace', action='write')
+    write(u, '(a)') '#   step' // adjustr(t) // '            ntri       cut_cells' // adjustr(a) // adjustr(v)
+    close(u)
+  end subroutine write_iso_header
+
+  ! one surface: <iso_base_name>NNNNN.ply and a line of the .dat file for the current state, ghost cells filled as the next step fills them (inputs.py: run, iso_line)
+  subroutine write_iso()
+    type(vdn_iso) :: r
+    real(dp_t), allocatable, target :: tri(:,:,:)
+    integer(c_int8_t), allocatable, target :: lev(:)
+    integer :: u
+    character(len=256) :: fname
+    call fill_state_ghosts()
+    if (trim(iso_field) == 'scalar') then
+       call isosurface(H%mla, H%sold(1:H%nlev), iso_comp, dm + iso_comp, dx(1:H%nlev,:), H%bct, iso_value, r, tri, lev)
+    else
+       call isosurface(H%mla, H%uold(1:H%nlev), iso_comp, iso_comp, dx(1:H%nlev,:), H%bct, iso_value, r, tri, lev)
+    end if
+    write(fname, '(a,i5.5,a)') trim(iso_base_name), istep, '.ply'
+    call isosurface_write(trim(fname), tri, lev, iso_value, time)
+    open(newunit=u, file=trim(iso_base_name) // '.dat', status='old', position='append', action='write')
+    write(u, '(i8,es27.17e3,2i16,2es27.17e3)') istep, time, r%ntri, r%cut_cells, r%area, r%volume_above
+    close(u)
+  end subroutine write_iso
 
   ! one profile file: the profiles of the current state (H%uold, H%sold) along prof_axis (inputs.py: profile_text)
   subroutine write_prof()

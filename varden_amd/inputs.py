@@ -9,7 +9,7 @@ from . import advance as adv
 from . import boxlib as bl
 from . import plotfile
 from .capi import default_params
-from .driver import Varden, VardenAMR
+from .driver import ISO_FIELDS, Varden, VardenAMR
 
 # src/_parameters: the defaults that matter to the path
 DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step=1, stop_time=-1.0, max_levs=1, max_grid_size=256,
@@ -21,6 +21,7 @@ DEFAULTS = dict(dim_in=2, nscal=2, prob_type=1, grav=0.0, boussinesq=0, max_step
                 fixed_dt=-1.0, plot_int=0, chk_int=0, restart=-1, plot_base_name="plt", check_base_name="chk", grids_file_name="", job_name="", fixed_grids="",
                 diag_int=0, diag_file_name="varden_diag.out", prof_int=0, prof_axis=-1, prof_base_name="prof",          # (the diag_, prof_, pdf_ and particle keys are the project's own, like tag_field)
                 pdf_int=0, pdf_field="scalar", pdf_comp=1, pdf_lo=0.0, pdf_hi=0.0, pdf_nbins=64, pdf_base_name="pdf",
+                iso_int=0, iso_field="scalar", iso_comp=1, iso_value=0.0, iso_base_name="iso",
                 particle_lattice=(0, 0, 0), particle_int=0, particle_base_name="part")
 
 
@@ -300,8 +301,35 @@ def pdf_keys(nl, pdf_int=None, pdf_field=None, pdf_comp=None, pdf_range=None, pd
     return k, field, comp, lo, hi, nbins
 
 
+def iso_keys(nl, iso_int=None, iso_field=None, iso_comp=None, iso_value=None):
+    """the iso keys of a namelist with the arguments over them: (iso_int, field name, comp numbered from 1, value).  With iso_int > 0 a known field, a 3-D problem
+    and a finite value are required"""
+    k = int(nl["iso_int"]) if iso_int is None else int(iso_int)
+    field = str(nl["iso_field"] if iso_field is None else iso_field).strip()
+    comp = int(nl["iso_comp"]) if iso_comp is None else int(iso_comp)
+    value = float(nl["iso_value"]) if iso_value is None else float(iso_value)
+    if k > 0:
+        if field not in ISO_FIELDS:
+            raise ValueError("inputs: iso_field = %r: one of %s" % (field, ", ".join(ISO_FIELDS)))
+        if int(nl["dim_in"]) != 3:
+            raise ValueError("inputs: iso_int > 0 needs dim_in = 3 (it is %d): surfaces are extracted from 3-D fields only" % int(nl["dim_in"]))
+        if not abs(value) < float("inf"):
+            raise ValueError("inputs: iso_value = %r is not finite" % (value,))
+    return k, field, comp, value
+
+
+def iso_header():
+    """the header line of an isosurface .dat file"""
+    return "#" + "step".rjust(7) + "time".rjust(27) + "".join(c.rjust(16 if c in ("ntri", "cut_cells") else 27) for c in adv.ISO_DAT_COLUMNS) + "\n"
+
+
+def iso_line(istep, time, iso):
+    """one data line of an isosurface .dat file, in the format of a diagnostics line: step (i8), time (es27.17e3), ntri and cut_cells (i16), area and volume_above (es27.17e3)"""
+    return "%8d" % istep + plotfile._es(time) + "%16d%16d" % (iso.ntri, iso.cut_cells) + plotfile._es(iso.area) + plotfile._es(iso.volume_above) + "\n"
+
+
 def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, files="plane", diag_int=None, particles=None, particle_int=None, prof_int=None, prof_axis=None,
-        pdf_int=None, pdf_field=None, pdf_comp=None, pdf_range=None, pdf_nbins=None):
+        pdf_int=None, pdf_field=None, pdf_comp=None, pdf_range=None, pdf_nbins=None, iso_int=None, iso_field=None, iso_comp=None, iso_value=None):
     """the time loop of src/varden.f90:237-371 for max_step steps (or until stop_time); plot / checkpoint files at step 0 of a fresh
     run and after every plot_int-th / chk_int-th step (:207-221, :349-361) under outdir.  diag_int > 0 (the namelist's key, or the argument over it): the run
     diagnostics of the state the run starts from and after every diag_int-th step, one line each under a header line, in <outdir>/<diag_file_name>; 0: no
@@ -311,10 +339,13 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
     (advance.profiles) of the state the run starts from and after every prof_int-th step along prof_axis (numbered from 1; -1: the problem's last direction), one
     file <prof_base_name>NNNNN each (profile_text); 0: no call, no file.  pdf_int > 0 (the namelist's key, or the argument over it): the distribution by value (advance.pdf)
     of pdf_field / pdf_comp (numbered from 1) on [pdf_lo, pdf_hi) in pdf_nbins bins for the state the run starts from and after every pdf_int-th step, one file
-    <pdf_base_name>NNNNN each (pdf_text); pdf_range = (lo, hi) goes over pdf_lo and pdf_hi; 0: no call, no file"""
+    <pdf_base_name>NNNNN each (pdf_text); pdf_range = (lo, hi) goes over pdf_lo and pdf_hi; 0: no call, no file.  iso_int > 0 (the namelist's key, or the argument over it):
+    the surface iso_field / iso_comp (numbered from 1) = iso_value (the drivers' isosurface) of the state the run starts from and after every iso_int-th step, one binary PLY
+    file <iso_base_name>NNNNN.ply each (advance.write_iso) and one line -- step, time, ntri, cut_cells, area, volume_above -- in <iso_base_name>.dat; 0: no call, no file"""
     nl = dict(DEFAULTS)
     nl.update(parse_namelist(text))
     pdf_int, pdf_field, pdf_comp, pdf_lo, pdf_hi, pdf_nbins = pdf_keys(nl, pdf_int, pdf_field, pdf_comp, pdf_range, pdf_nbins)      # (refused before anything is built)
+    iso_int, iso_field, iso_comp, iso_value = iso_keys(nl, iso_int, iso_field, iso_comp, iso_value)
     nl, G = build(text, device=device, outdir=outdir, extrude_nz=extrude_nz, files=files, nl=nl)
     max_step = int(nl["max_step"]) if nsteps is None else nsteps
     stop_time = float(nl["stop_time"])
@@ -376,10 +407,26 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             f.write(pdf_text(G.pdf(pdf_field, pdf_comp - 1, pdf_lo, pdf_hi, pdf_nbins), G.istep, G.time))
         G.files_written.append(path)
 
+    iso_dat = os.path.join(outdir, "%s.dat" % (nl["iso_base_name"],))
+
+    def iso():
+        path = os.path.join(outdir, "%s%05d.ply" % (nl["iso_base_name"], G.istep))
+        S = G.isosurface(iso_field, iso_comp - 1, iso_value)
+        adv.write_iso(path, S, G.time)
+        if getattr(G, "rank", 0) == 0:
+            with open(iso_dat, "a") as f:
+                f.write(iso_line(G.istep, G.time, S))
+        G.files_written.append(path)
+
     if diag_int > 0:
         with open(diag_path, "w") as f:
             f.write(diag_header(G.nscal, G.dm))
         diag()
+    if iso_int > 0:
+        if getattr(G, "rank", 0) == 0:
+            with open(iso_dat, "w") as f:
+                f.write(iso_header())
+        iso()
     if prof_int > 0:
         prof()
     if pdf_int > 0:
@@ -401,6 +448,8 @@ def run(text, nsteps=None, report=print, device=0, outdir=".", extrude_nz=16, fi
             prof()
         if pdf_int > 0 and G.istep % pdf_int == 0:
             pdf()
+        if iso_int > 0 and G.istep % iso_int == 0:
+            iso()
         if G.particles is not None and particle_int > 0 and G.istep % particle_int == 0:
             particle_file()
         dump()
